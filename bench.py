@@ -6,11 +6,15 @@ connected components -> per-cluster objects) over one batch of F synthetic 1280x
 resident in HBM when the timed region starts.  Multi-GPU = frame sharding (weak scaling: every rank owns F pairs);
 the only collective is the RCCL broadcast of the camera-intrinsics/parameter block before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps, writes
+the last step's outputs when --dump-outputs is given and prints the headline line.  With --full the line also carries:
   roofline     — the dominant kernel (longest average launch; HIP events on the launch stream inside the timed region),
                  priced with SURVEY.md §8(d)'s algorithmic bytes per pixel; per-kernel numbers of an untimed breakdown
                  pass (events around every kernel group) alongside
-  cpu_baseline — the CPU oracle ("port": op-for-op restatement of the reference loops) timed on this box's host cores
+  cpu_baseline — the CPU oracle ("port": op-for-op restatement of the reference loops) timed on this box's host cores, and
+                 whether the GPU's outputs match it bit for bit
+  latency      — frame-at-a-time steps of 1 / 8 / 64 pairs
+  config5      — on-GPU SGM disparity -> scene flow -> clusters
 """
 from __future__ import annotations
 
@@ -45,15 +49,22 @@ B_FUSED = 44                   # bytes/px: 16 in + 24 out + 4 label (mask never 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None, help="ranks of the job (default: WORLD_SIZE when a launcher set it, else 1)")
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures outside the headline: roofline (with an untimed per-kernel breakdown pass), frame-at-a-time "
+                         "latency leg, config-5 leg and CPU baseline with its check of the GPU's outputs against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's frames) as DIR/<name>.npy: the six cloud "
+                         "planes, cluster labels and dynamic-mask bit at a fixed seeded sample of at most 2^20 pixels, the objects of "
+                         "every frame in full; every value is finite, NaN / inf are written as 0 with a code in DIR/nonfinite.npy")
     ap.add_argument("--frames", type=int, default=512, help="stereo pairs per step and per GPU")
     ap.add_argument("--distinct", type=int, default=16, help="distinct synthetic pairs generated per GPU (tiled to --frames)")
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=720)
     ap.add_argument("--camera", default="zed", choices=["zed", "kitti"], help="synthetic camera: ZED-like (config 2) or KITTI-style (config 3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=24, help="pairs timed on the CPU (bounded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--cpu-sample", type=int, default=24, help="pairs timed on the CPU (bounded sample, --full)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal on a 1-GPU box: every rank uses cuda:0")
     ap.add_argument("--workload", default="sequence", choices=["sequence", "pairs", "nominal"],
@@ -73,14 +84,17 @@ def parse():
     ap.add_argument("--no-dist", action="store_true",
                     help="N = 1 only: skip the process group (by default a one-rank RCCL group is brought up so that the single-GPU "
                          "line drives the communicator, the device broadcast and the device all-reduce of the N-rank run)")
-    ap.add_argument("--no-latency", action="store_true", help="skip the frame-at-a-time leg (steps of 1 / 8 / 64 pairs, outside `value`)")
-    ap.add_argument("--no-config5", action="store_true", help="skip the short config-5 leg (on-GPU SGM disparity, outside `value`)")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the frame-at-a-time leg (steps of 1 / 8 / 64 pairs, outside `value`)")
+    ap.add_argument("--no-config5", action="store_true", help="--full without the short config-5 leg (on-GPU SGM disparity, outside `value`)")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous + config broadcast + stream sharding only, no GPU work (exercises the N-rank launch path on a CPU box)")
     ap.add_argument("--fail-rank", type=int, default=None,
                     help="rehearsal of a rank failure: this rank raises after the rendezvous (the job must exit non-zero, name the rank on "
                          "stderr and print no JSON line)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(cam, prm, batch, n_sample, sgm=None):
@@ -282,6 +296,54 @@ def latency_leg(dev, local_rank, cam_s, prm_s, host, W, H, sizes=(1, 8, 64)):
     return out
 
 
+def dump_outputs(out_dir, ws, F, H, W, max_pixels=1 << 20, seed=0):
+    """--dump-outputs: what the last step handed its caller, as float32 / float64 .npy files, for comparing two builds output for
+    output.  The per-pixel outputs are taken at one fixed seeded sample of pixel positions (every pixel when there are no more than
+    `max_pixels`), so that the files stay under 64 MB at 512 pairs of 1280x720; the objects of every frame are written in full.
+    Every value written is finite: where the path wrote NaN or an infinity (a plane's invalid pixels), the file holds 0 and a code
+    array says what stood there (0 finite, 1 NaN, 2 +inf, 3 -inf): `nonfinite` packs the six planes' codes, plane i in bits 2i, 2i + 1."""
+    import numpy as np
+    import torch
+
+    from moving_object_detector_amd.pipeline import OBJECT_DTYPE, PLANES
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = F * H * W
+    pos = np.arange(n) if n <= max_pixels else np.sort(np.random.default_rng(seed).choice(n, max_pixels, replace=False))
+    p = torch.from_numpy(pos).to(ws["planes"].device)
+    out = {"pixel_index": pos.astype(np.float64)}                 # flat index f * H * W + y * W + x of each sampled pixel
+
+    def finite(a):
+        code = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1, 2, 3], 0)
+        return np.where(code == 0, a, 0).astype(a.dtype), code
+
+    nonfinite = np.zeros(len(pos), np.int64)
+    for i, k in enumerate(PLANES):
+        if ws["xy"] or k not in ("x", "y"):
+            out[k], code = finite(ws["planes"][i].reshape(-1)[p].cpu().numpy())
+            nonfinite |= code << (2 * i)
+    out["nonfinite"] = nonfinite.astype(np.float32)
+    if ws["labels"] is not None:
+        out["labels"] = ws["labels"].reshape(-1)[p].cpu().numpy().astype(np.float64)
+    f, y, x = p // (H * W), (p // W) % H, p % W                   # dynamic mask: bit x % 64 of word x / 64 of row (f, y)
+    words = ws["mask"].reshape(-1)[(f * H + y) * ws["mask"].shape[2] + x // 64]
+    out["dynamic_mask"] = ((words >> (x % 64)) & 1).cpu().numpy().astype(np.float32)
+    n_obj = ws["n_objects"].cpu().numpy()
+    out["n_objects"] = n_obj.astype(np.float64)
+    out["n_clusters"] = ws["n_clusters"].cpu().numpy().astype(np.float64)
+    # objects: (F, most objects in a frame, 15) = id, n_points, center xyz, orientation xyzw, velocity xyz, bounding box xyz; 0 past n_objects
+    k = int(min(n_obj.max(initial=0), ws["objects"].shape[1]))
+    raw = np.ascontiguousarray(ws["objects"][:, :k].cpu().numpy())
+    rec = raw.reshape(-1).view(OBJECT_DTYPE).reshape(F, k)
+    cols = [rec["id"][..., None], rec["n_points"][..., None], rec["center"], rec["orientation"], rec["velocity"], rec["bounding_box"]]
+    objs = np.concatenate([c.astype(np.float64) for c in cols], axis=-1)
+    objs[np.arange(k)[None, :] >= n_obj[:, None]] = 0.0
+    out["objects"], code = finite(objs)
+    out["objects_nonfinite"] = code.astype(np.float32)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     """Rank-level failures are fatal and visible: one line on stderr that names the rank, a non-zero exit code (the launcher then
     stops the other ranks and fails too), and no JSON line — the line is written last, by rank 0, after every rank's timed work."""
@@ -444,14 +506,17 @@ def run():
     elapsed = time.perf_counter() - t0
     sf_timed = ctx.stage_time(capi.MOD_STAGE_SCENE_FLOW)
     cl_timed = ctx.stage_time(capi.MOD_STAGE_CLUSTER_GROUP)
-    # Untimed breakdown pass over the same batch: every kernel bracketed (reported next to the roofline kernel); with these
-    # timers on the call runs its cluster stage in ONE chunk, each kernel alone on the GPU.
-    ctx.set_profiling(True)
-    ctx.reset_stage_times()
-    for _ in range(max(1, min(args.steps, 10))):
-        ctx.process(batch, ws)
-    torch.cuda.synchronize()
-    stage = [ctx.stage_time(i) for i in range(capi.MOD_STAGE_COUNT)]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ws, F, H, W)
+    if args.full:
+        # Untimed breakdown pass over the same batch: every kernel bracketed (reported next to the roofline kernel); with these
+        # timers on the call runs its cluster stage in ONE chunk, each kernel alone on the GPU.
+        ctx.set_profiling(True)
+        ctx.reset_stage_times()
+        for _ in range(max(1, min(args.steps, 10))):
+            ctx.process(batch, ws)
+        torch.cuda.synchronize()
+        stage = [ctx.stage_time(i) for i in range(capi.MOD_STAGE_COUNT)]
     ctx.set_profiling(False)
     elapsed = mdist.max_over_ranks(elapsed, device=dev if on_dev else None)     # the slowest rank's time (device all-reduce on RCCL)
     # The job's collective work ends here: the group goes down on every rank BEFORE rank 0's solo legs (config 5, ~15 s of CPU
@@ -466,91 +531,91 @@ def run():
         N = W * H
         pairs = world * F * args.steps
         value = pairs / elapsed
-        ms = [(t / n if n else float("nan")) for t, n in stage]                 # average launch duration per kernel
-        breakdown_sf_ms = ms[capi.MOD_STAGE_SCENE_FLOW]
-        ms[capi.MOD_STAGE_SCENE_FLOW] = sf_timed[0] / sf_timed[1]               # the priced kernel: from the timed region
-        # the bytes of the planes a non-headline call does not produce are not priced either
-        B_SCENE_FLOW = 40 - (8 if args.objects_only else 0)
-        B_CLUSTER = 20 - (4 if args.no_labels else 0)
-        B_FUSED = 44 - (8 if args.objects_only else 0) - (4 if args.no_labels else 0)
-        per_kernel = [capi.MOD_STAGE_SCENE_FLOW] + list(capi.MOD_PER_KERNEL_CLUSTER_STAGES)
-        kernels = {capi.STAGE_NAMES[i]: ms[i] for i in per_kernel}
-        sf_ms = ms[capi.MOD_STAGE_SCENE_FLOW]
-        cl_sum_ms = sum(ms[i] for i in capi.MOD_PER_KERNEL_CLUSTER_STAGES)     # the group's kernels one after the other, each alone
-        cl_ms = cl_timed[0] / cl_timed[1]                                       # the group as the timed region ran it
-        sf_gbs = F * N * B_SCENE_FLOW / (sf_ms * 1e-3) / 1e9
-        cl_gbs = F * N * B_CLUSTER / (cl_ms * 1e-3) / 1e9
-        dom = max(per_kernel, key=lambda i: ms[i])                             # the single kernel with the longest launch
-        # algorithmic bytes of that kernel per launch: the scene-flow kernel moves its group's 40 B/px; a cluster kernel is
-        # priced with the whole cluster group's 20 B/px (the group's bytes are not separable per kernel)
-        dom_bytes = F * N * (B_SCENE_FLOW if dom == capi.MOD_STAGE_SCENE_FLOW else B_CLUSTER)
-        ach = dom_bytes / (ms[dom] * 1e-3) / 1e9
-        traffic = None
-        import glob
-        tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))   # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
-        tpath = tfiles[-1] if tfiles else None                                          # the latest round's
-        if tpath:
-            tj = json.load(open(tpath))
-            if tj.get("frames_per_launch") == F and tj.get("width") == W and tj.get("height") == H:
-                traffic = tj["kernels"].get(capi.STAGE_NAMES[dom].split("+")[0], {}).get("hbm_bytes_per_launch")
-        roof = {
-            "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
-            "kernel": capi.STAGE_NAMES[dom], "algorithmic_bytes_per_launch": dom_bytes,
-            "algorithmic_bytes_per_px": B_SCENE_FLOW if dom == capi.MOD_STAGE_SCENE_FLOW else B_CLUSTER,
-            "frames_per_launch": F, "avg_launch_ms": ms[dom],
-            "measured_in": "timed region" if dom == capi.MOD_STAGE_SCENE_FLOW else "breakdown pass (all stage timers on)",
-            "scene_flow_ms_in_breakdown_pass": breakdown_sf_ms, "frac_of_measured_copy_ceiling": ach / HBM_COPY_GBS,
-            "frac_of_measured_read_write_bound": (ach / SF_RW_BOUND_GBS) if (dom == capi.MOD_STAGE_SCENE_FLOW and not args.objects_only) else None,
-            "traffic_from_committed_profile": traffic is not None,       # a separate rocprofv3 --pmc run of this command, not this run
-            "traffic_source": (f"profiles/{os.path.basename(tpath)} at commit {tj.get('head', '?')} (rocprofv3 --pmc FETCH_SIZE x2 on gfx950 + "
-                               f"WRITE_SIZE in separate passes of this same command; counters cannot be read inside the run)"
-                               if traffic else None),
-            "kernels_ms_per_launch": kernels,
-            "groups": {
-                "scene_flow": {"ms_per_launch": sf_ms, "GBps": sf_gbs, "frac": sf_gbs / HBM_PEAK_GBS, "bytes_per_px": B_SCENE_FLOW},
-                "cluster": {"ms_per_launch": cl_ms, "GBps": cl_gbs, "frac": cl_gbs / HBM_PEAK_GBS, "bytes_per_px": B_CLUSTER,
-                            "measured_in": "timed region: HIP events around the whole group, first launch to last"
-                                           + (f" (in {args.chunks & 0xff} chunks side by side: ModConfig.batch_chunks)" if (args.chunks & 0xff) > 1 else ""),
-                            "kernels_one_after_the_other_ms": cl_sum_ms,
-                            "frac_kernels_one_after_the_other": F * N * B_CLUSTER / (cl_sum_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
-                "fused_end_to_end": {"GBps": F * N * B_FUSED / ((sf_ms + cl_ms) * 1e-3) / 1e9, "bytes_per_px": B_FUSED},
-            },
-        }
-        n_chk = min(args.cpu_sample, G)
-        planes = ws["planes"][:, :n_chk].cpu().numpy()   # the sampled pairs' outputs, for the same-run check against the oracle
-        checked_planes = [i for i, k in enumerate(PLANES) if not (args.objects_only and k in ("x", "y"))]
-        labels = ws["labels"][:n_chk].cpu().numpy() if ws["labels"] is not None else None
-        c5 = c5_check = None
-        lat = None
-        if not args.no_latency or not args.no_config5:
-            ctx.close()                                       # frees the 512-pair context's scratch before the SGM volumes come
-            ctx._ws = None
-            del batch, ws, d_now, d_prev, flow
-            torch.cuda.empty_cache()
-        if not args.no_latency:                               # rank 0 alone, the group is down (like config 5 and the CPU baseline)
-            try:
-                lat = latency_leg(dev, local_rank, cam_s, prm_s, host, W, H)
-            except Exception as e:                            # noqa: BLE001  (outside `value`)
-                lat = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if not args.no_config5:
-            try:
-                c5, c5_check = config5_leg(dev, local_rank)
-            except Exception as e:                            # noqa: BLE001  (the leg is outside `value`; its failure must not cost the line)
-                c5 = {"error": f"{type(e).__name__}: {e}"[:300]}
-        cpu = None
-        if not args.no_cpu_baseline:                     # rank 0 only, also when N > 1 (the group is down by now: the other ranks have left)
-            prm = synth.Params()
-            cpu, refs = cpu_baseline(cam, prm, host, args.cpu_sample, sgm=c5_check)
-            ok = True
-            for f, (ref, lab, objs) in enumerate(refs):
-                if f >= n_chk:
-                    break
-                for i in checked_planes:
-                    a, r = planes[i, f], ref[PLANES[i]]
-                    ok &= bool(((a.view(np.uint32) == r.view(np.uint32)) | (np.isnan(a) & np.isnan(r))).all())
-                if labels is not None:
-                    ok &= bool(np.array_equal(labels[f], lab))
-            cpu["gpu_outputs_match_oracle"] = ok
+        roof = cpu = lat = c5 = None
+        if args.full:
+            ms = [(t / n if n else float("nan")) for t, n in stage]                 # average launch duration per kernel
+            breakdown_sf_ms = ms[capi.MOD_STAGE_SCENE_FLOW]
+            ms[capi.MOD_STAGE_SCENE_FLOW] = sf_timed[0] / sf_timed[1]               # the priced kernel: from the timed region
+            # the bytes of the planes a non-headline call does not produce are not priced either
+            B_SCENE_FLOW = 40 - (8 if args.objects_only else 0)
+            B_CLUSTER = 20 - (4 if args.no_labels else 0)
+            B_FUSED = 44 - (8 if args.objects_only else 0) - (4 if args.no_labels else 0)
+            per_kernel = [capi.MOD_STAGE_SCENE_FLOW] + list(capi.MOD_PER_KERNEL_CLUSTER_STAGES)
+            kernels = {capi.STAGE_NAMES[i]: ms[i] for i in per_kernel}
+            sf_ms = ms[capi.MOD_STAGE_SCENE_FLOW]
+            cl_sum_ms = sum(ms[i] for i in capi.MOD_PER_KERNEL_CLUSTER_STAGES)     # the group's kernels one after the other, each alone
+            cl_ms = cl_timed[0] / cl_timed[1]                                       # the group as the timed region ran it
+            sf_gbs = F * N * B_SCENE_FLOW / (sf_ms * 1e-3) / 1e9
+            cl_gbs = F * N * B_CLUSTER / (cl_ms * 1e-3) / 1e9
+            dom = max(per_kernel, key=lambda i: ms[i])                             # the single kernel with the longest launch
+            # algorithmic bytes of that kernel per launch: the scene-flow kernel moves its group's 40 B/px; a cluster kernel is
+            # priced with the whole cluster group's 20 B/px (the group's bytes are not separable per kernel)
+            dom_bytes = F * N * (B_SCENE_FLOW if dom == capi.MOD_STAGE_SCENE_FLOW else B_CLUSTER)
+            ach = dom_bytes / (ms[dom] * 1e-3) / 1e9
+            traffic = None
+            import glob
+            tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_traffic.json")))   # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes
+            tpath = tfiles[-1] if tfiles else None                                          # the latest round's
+            if tpath:
+                tj = json.load(open(tpath))
+                if tj.get("frames_per_launch") == F and tj.get("width") == W and tj.get("height") == H:
+                    traffic = tj["kernels"].get(capi.STAGE_NAMES[dom].split("+")[0], {}).get("hbm_bytes_per_launch")
+            roof = {
+                "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS, "traffic": traffic,
+                "kernel": capi.STAGE_NAMES[dom], "algorithmic_bytes_per_launch": dom_bytes,
+                "algorithmic_bytes_per_px": B_SCENE_FLOW if dom == capi.MOD_STAGE_SCENE_FLOW else B_CLUSTER,
+                "frames_per_launch": F, "avg_launch_ms": ms[dom],
+                "measured_in": "timed region" if dom == capi.MOD_STAGE_SCENE_FLOW else "breakdown pass (all stage timers on)",
+                "scene_flow_ms_in_breakdown_pass": breakdown_sf_ms, "frac_of_measured_copy_ceiling": ach / HBM_COPY_GBS,
+                "frac_of_measured_read_write_bound": (ach / SF_RW_BOUND_GBS) if (dom == capi.MOD_STAGE_SCENE_FLOW and not args.objects_only) else None,
+                "traffic_from_committed_profile": traffic is not None,       # a separate rocprofv3 --pmc run of this command, not this run
+                "traffic_source": (f"profiles/{os.path.basename(tpath)} at commit {tj.get('head', '?')} (rocprofv3 --pmc FETCH_SIZE x2 on gfx950 + "
+                                   f"WRITE_SIZE in separate passes of this same command; counters cannot be read inside the run)"
+                                   if traffic else None),
+                "kernels_ms_per_launch": kernels,
+                "groups": {
+                    "scene_flow": {"ms_per_launch": sf_ms, "GBps": sf_gbs, "frac": sf_gbs / HBM_PEAK_GBS, "bytes_per_px": B_SCENE_FLOW},
+                    "cluster": {"ms_per_launch": cl_ms, "GBps": cl_gbs, "frac": cl_gbs / HBM_PEAK_GBS, "bytes_per_px": B_CLUSTER,
+                                "measured_in": "timed region: HIP events around the whole group, first launch to last"
+                                               + (f" (in {args.chunks & 0xff} chunks side by side: ModConfig.batch_chunks)" if (args.chunks & 0xff) > 1 else ""),
+                                "kernels_one_after_the_other_ms": cl_sum_ms,
+                                "frac_kernels_one_after_the_other": F * N * B_CLUSTER / (cl_sum_ms * 1e-3) / 1e9 / HBM_PEAK_GBS},
+                    "fused_end_to_end": {"GBps": F * N * B_FUSED / ((sf_ms + cl_ms) * 1e-3) / 1e9, "bytes_per_px": B_FUSED},
+                },
+            }
+            n_chk = min(args.cpu_sample, G)
+            planes = ws["planes"][:, :n_chk].cpu().numpy()   # the sampled pairs' outputs, for the same-run check against the oracle
+            checked_planes = [i for i, k in enumerate(PLANES) if not (args.objects_only and k in ("x", "y"))]
+            labels = ws["labels"][:n_chk].cpu().numpy() if ws["labels"] is not None else None
+            c5_check = None
+            if not args.no_latency or not args.no_config5:
+                ctx.close()                                       # frees the 512-pair context's scratch before the SGM volumes come
+                ctx._ws = None
+                del batch, ws, d_now, d_prev, flow
+                torch.cuda.empty_cache()
+            if not args.no_latency:                               # rank 0 alone, the group is down (like config 5 and the CPU baseline)
+                try:
+                    lat = latency_leg(dev, local_rank, cam_s, prm_s, host, W, H)
+                except Exception as e:                            # noqa: BLE001  (outside `value`)
+                    lat = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if not args.no_config5:
+                try:
+                    c5, c5_check = config5_leg(dev, local_rank)
+                except Exception as e:                            # noqa: BLE001  (the leg is outside `value`; its failure must not cost the line)
+                    c5 = {"error": f"{type(e).__name__}: {e}"[:300]}
+            if not args.no_cpu_baseline:                     # rank 0 only, also when N > 1 (the group is down by now: the other ranks have left)
+                prm = synth.Params()
+                cpu, refs = cpu_baseline(cam, prm, host, args.cpu_sample, sgm=c5_check)
+                ok = True
+                for f, (ref, lab, objs) in enumerate(refs):
+                    if f >= n_chk:
+                        break
+                    for i in checked_planes:
+                        a, r = planes[i, f], ref[PLANES[i]]
+                        ok &= bool(((a.view(np.uint32) == r.view(np.uint32)) | (np.isnan(a) & np.isnan(r))).all())
+                    if labels is not None:
+                        ok &= bool(np.array_equal(labels[f], lab))
+                cpu["gpu_outputs_match_oracle"] = ok
         line = {
             "metric": "stereo pairs/sec (scene-flow+cluster) at 1280x720", "value": value, "unit": "stereo pairs/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
@@ -571,8 +636,9 @@ def run():
                        "collective_executed": coll["executed"], "collective_backend": coll["backend"],
                        "collective_on_device": bool(coll["executed"] and on_dev), "collective_world_size": coll["world_size"],
                        "collective_error": group_error},
-            "roofline": roof, "cpu_baseline": cpu,
         }
+        if args.full:
+            line["roofline"], line["cpu_baseline"] = roof, cpu
         if lat is not None:
             line["latency"] = lat
         if c5 is not None:

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage (GPU box): bash tools/ab_libs.sh <tag> <bench args...> -- <lib1> <lib2> ...   A/B of library builds through bench.py (MOD_SF_LIB)
 tag=$1; shift
-args=()
+args=(--full)
 while [ "$1" != "--" ] && [ $# -gt 0 ]; do args+=("$1"); shift; done
 shift
 for rep in $(seq 1 ${REPS:-2}); do

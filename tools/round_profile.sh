@@ -4,17 +4,17 @@
 # (the profiled commands skip bench.py's config-5 leg: its small scene-flow launches would dilute the per-launch averages)
 out=$PWD/gpurun_out/final
 rm -rf $out; mkdir -p $out
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --no-latency --workload pairs > $out/bench_pairs.json 2> $out/bench_pairs.err
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --no-latency --frames 64 > $out/bench_64.json 2> $out/bench_64.err
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --no-latency --camera kitti > $out/bench_kitti.json 2> $out/bench_kitti.err
-timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-config5 --no-latency --workload nominal > $out/bench_nominal.json 2> $out/bench_nominal.err
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --no-latency --workload pairs > $out/bench_pairs.json 2> $out/bench_pairs.err
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --no-latency --frames 64 > $out/bench_64.json 2> $out/bench_64.err
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --no-latency --camera kitti > $out/bench_kitti.json 2> $out/bench_kitti.err
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-config5 --no-latency --workload nominal > $out/bench_nominal.json 2> $out/bench_nominal.err
 # the committed line (the driver's own command) AFTER the four short runs: the first GPU process on a fresh box runs its kernels 3-6 % slower
 # than the ones that follow it (round 5: 95.3 k first, 98.9-101.1 k in the three traced runs minutes later on the same box)
-timeout -k 10 500 python3 bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 500 python3 bench.py --full --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench_default.err
 echo "bench rc=$?"
 repo=$PWD
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $repo/bench.py --no-cpu-baseline --no-config5 --no-latency > $out/stats_bench.json 2> $out/stats.err
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $repo/bench.py --full --no-cpu-baseline --no-config5 --no-latency > $out/stats_bench.json 2> $out/stats.err
 echo "stats rc=$?"
 for ctr in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 400 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $out/pmc_$ctr -- python3 $repo/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-config5 --no-latency > $out/pmc_$ctr.json 2> $out/pmc_$ctr.err
@@ -42,9 +42,9 @@ timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_C
 echo "sgm pmc rc=$?"
 timeout -k 10 300 rocprofv3 --pmc GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $out/sgm_clk -- python3 $repo/tools/time_sgm.py > /dev/null 2> $out/sgm_clk.err
 echo "sgm clk rc=$?"
-timeout -k 10 200 python3 $repo/bench.py --no-cpu-baseline --no-config5 --no-latency --objects-only > $out/bench_objects_only.json 2> $out/bench_objects_only.err
-timeout -k 10 200 python3 $repo/bench.py --no-cpu-baseline --no-config5 --no-latency --chunks 1 > $out/bench_chunks1.json 2> $out/bench_chunks1.err
-timeout -k 10 200 python3 $repo/bench.py --no-cpu-baseline --no-config5 --no-latency --chunks 2 > $out/bench_chunks2.json 2> $out/bench_chunks2.err
-timeout -k 10 200 python3 $repo/bench.py --no-cpu-baseline --no-config5 --no-latency --chunks 1 --steps 200 --warmup 50 > $out/bench_chunks1_long.json 2> $out/bench_chunks1_long.err
-timeout -k 10 200 python3 $repo/bench.py --no-cpu-baseline --no-config5 --no-latency --chunks 2 --steps 200 --warmup 50 > $out/bench_chunks2_long.json 2> $out/bench_chunks2_long.err
+timeout -k 10 200 python3 $repo/bench.py --full --no-cpu-baseline --no-config5 --no-latency --objects-only > $out/bench_objects_only.json 2> $out/bench_objects_only.err
+timeout -k 10 200 python3 $repo/bench.py --full --no-cpu-baseline --no-config5 --no-latency --chunks 1 > $out/bench_chunks1.json 2> $out/bench_chunks1.err
+timeout -k 10 200 python3 $repo/bench.py --full --no-cpu-baseline --no-config5 --no-latency --chunks 2 > $out/bench_chunks2.json 2> $out/bench_chunks2.err
+timeout -k 10 200 python3 $repo/bench.py --full --no-cpu-baseline --no-config5 --no-latency --chunks 1 --steps 200 --warmup 50 > $out/bench_chunks1_long.json 2> $out/bench_chunks1_long.err
+timeout -k 10 200 python3 $repo/bench.py --full --no-cpu-baseline --no-config5 --no-latency --chunks 2 --steps 200 --warmup 50 > $out/bench_chunks2_long.json 2> $out/bench_chunks2_long.err
 ls $out
