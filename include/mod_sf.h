@@ -230,6 +230,32 @@ int  mod_sgm_census_dev(ModContext *ctx, int32_t frames, const uint8_t *image, u
 int  mod_sgm_path_dev(ModContext *ctx, int32_t frames, const uint32_t *census_left, const uint32_t *census_right,
                       const ModSgmParams *params, int32_t direction, uint8_t *path_cost, uint8_t *matching_cost);
 
+/* ---- on-GPU optical flow --------------------------------------------------------------------------------------------------- */
+/* The reference obtains the flow from pwc_net_.estimateOpticalFlow(previous_left, left) (scene_flow_constructor.cpp:279-290), a
+ * Caffe CNN whose weights this project does not have.  This estimator is NOT PWC-Net and claims no parity with it: coarse-to-fine
+ * census block matching, deterministic and integer up to the sub-pixel step (tests/models/flow_model.py
+ * restates it bit for bit).  Pyramid of `levels` (2 x 2 rounded mean), the SGM path's 9 x 7 census on every level, cost = sum of
+ * Hamming distances over a window x window square (a prev sample outside the image costs 31), full search [-radius, radius]^2 on
+ * the coarsest level and +-1 around twice the coarser winner on every finer one; largest displacement
+ * radius * 2^(levels-1) + 2^(levels-1) - 1 px (39 at the defaults).  Sub-pixel: a parabola through the winner and its two
+ * neighbours per axis.  Forward-backward check: the backward field must cancel the forward one within fb_check px, else NaN.
+ * Output: 32FC2 (x then y) [frames][H][W][2] indexed at the NOW pixel, prev = now - flow — the `flow` every entry point above takes.
+ * Images are 8-bit [frames][H][W] of the configured camera size.  Defaults: levels 4, radius 4, window 5, subpixel 1, fb_check 1. */
+typedef struct ModFlowParams {
+  int32_t levels;     /* 1..6; the coarsest level (W >> (levels-1), H >> (levels-1)) must be at least 16 px on either side */
+  int32_t radius;     /* 1..8: search radius on the coarsest level */
+  int32_t window;     /* 3, 5 or 7: matching window */
+  int32_t subpixel;   /* 0 / 1: sub-pixel parabola on level 0 */
+  int32_t fb_check;   /* tolerance of the forward-backward check in px; < 0 = off */
+} ModFlowParams;
+/* estimateOpticalFlow on device images.  Ordered on the context's stream; scratch (pyramids, census planes, integer flow planes for
+ * max_width x max_height x max_frames) is allocated on first use.  frames <= max_frames and <= 32767.  NULL image ->
+ * MOD_SKIP_NO_FLOW, as a failed estimateOpticalFlow. */
+int  mod_flow_compute_dev(ModContext *ctx, int32_t frames, const uint8_t *prev, const uint8_t *now, const ModFlowParams *params,
+                          float *flow);
+/* the same for one frame in host memory; synchronous */
+int  mod_flow_compute_host(ModContext *ctx, const uint8_t *prev, const uint8_t *now, const ModFlowParams *params, float *flow);
+
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()
  * would publish nothing.  cloud_aos: W*H*32 bytes; labels: W*H int32; objects: capacity `max_objects`.
@@ -296,6 +322,19 @@ int  mod_submit_stereo_host(ModContext *ctx, const uint8_t *left, const uint8_t 
                             const float *flow, const ModTransform *transform, double dt,
                             void *cloud_aos, int32_t *labels, ModObject *objects, int32_t max_objects,
                             float *disparity, int32_t *ticket);
+/* Stereo images in, moving objects out, with the flow estimated on the GPU too: mod_submit_stereo_host whose `flow` is
+ * mod_flow_compute_dev(previous left image, this left image, flow_prm).  The left image stays resident in HBM (a ring indexed like
+ * the disparity ring) as the next submit's previous image, and the flow goes straight into the frame's flow buffer: no flow crosses
+ * PCIe.  Without a previous left image — the first frame, after mod_forget_previous, after a submit of another kind, after a frame
+ * with a NULL image — the frame behaves exactly like mod_submit_stereo_host with flow = NULL (MOD_SKIP_NO_FLOW; its disparity and
+ * left image still serve the next frame).  flow_prm is read at submit time.
+ *   flow_out   optional host copy of the flow image (32FC2, the reference's ~optical_flow, scene_flow_constructor.cpp:99-100),
+ *              valid after collect; like `disparity`, written for ticketed frames only
+ * Other arguments, skip codes and collection as mod_submit_stereo_host. */
+int  mod_submit_images_host(ModContext *ctx, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm,
+                            const ModFlowParams *flow_prm, const ModTransform *transform, double dt, void *cloud_aos,
+                            int32_t *labels, ModObject *objects, int32_t max_objects, float *disparity, float *flow_out,
+                            int32_t *ticket);
 /* disparity_now_.reset() of a failed estimateDisparity (scene_flow_constructor.cpp:272-276): the next submit without an
  * explicit disparity_prev reports MOD_SKIP_NO_DISPARITY_PREV instead of pairing with a stale frame. */
 int  mod_forget_previous(ModContext *ctx);

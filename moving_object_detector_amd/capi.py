@@ -42,6 +42,7 @@ EXPORTS = [
     "mod_malloc", "mod_free", "mod_memcpy_h2d", "mod_memcpy_d2h", "mod_set_profiling",
     "mod_get_stage_time", "mod_reset_stage_times", "mod_depth_image_dev", "mod_depth_image_host", "mod_static_flow_host",
     "mod_sgm_census_dev", "mod_sgm_path_dev", "mod_sgm_compute_dev", "mod_sgm_compute_host",
+    "mod_flow_compute_dev", "mod_flow_compute_host", "mod_submit_images_host",
 ]
 
 
@@ -84,6 +85,20 @@ class ModSceneFlowPlanes(C.Structure):
 class ModSgmParams(C.Structure):
     _fields_ = [("disparities", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("paths", C.c_int32), ("lr_check", C.c_int32),
                 ("median", C.c_int32)]
+
+
+class ModFlowParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("radius", C.c_int32), ("window", C.c_int32), ("subpixel", C.c_int32), ("fb_check", C.c_int32)]
+
+
+def flow_params(levels: int = 4, radius: int = 4, window: int = 5, subpixel: bool = True, fb_check: int = 1) -> ModFlowParams:
+    """ModFlowParams with the defaults of include/mod_sf.h (fb_check < 0 turns the forward-backward check off)."""
+    return ModFlowParams(int(levels), int(radius), int(window), int(bool(subpixel)), int(fb_check))
+
+
+def flow_max_displacement(p: ModFlowParams) -> int:
+    """Largest displacement (px) the coarse-to-fine search can reach: radius * 2^(levels-1) + 2^(levels-1) - 1."""
+    return p.radius * (1 << (p.levels - 1)) + (1 << (p.levels - 1)) - 1
 
 
 class ModClusterOut(C.Structure):
@@ -135,6 +150,10 @@ def load(require_torch_first: bool = True):
     L.mod_sgm_compute_dev.argtypes = [vp, i32, vp, vp, C.POINTER(ModSgmParams), vp]
     L.mod_sgm_compute_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), vp]
     L.mod_sgm_path_dev.argtypes = [vp, i32, vp, vp, C.POINTER(ModSgmParams), i32, vp, vp]
+    L.mod_flow_compute_dev.argtypes = [vp, i32, vp, vp, C.POINTER(ModFlowParams), vp]
+    L.mod_flow_compute_host.argtypes = [vp, vp, vp, C.POINTER(ModFlowParams), vp]
+    L.mod_submit_images_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModTransform), C.c_double,
+                                         vp, vp, vp, i32, vp, vp, C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

@@ -54,6 +54,11 @@ struct Buffers {
   // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
   hipStream_t sgm_side[8] = {};
   hipEvent_t sgm_fork[2] = {}, sgm_join[2][8] = {};
+  // on-GPU optical flow (allocated on first use, every level sized for max_width x max_height x max_frames; see flow_level_offset)
+  uint8_t *flow_img = nullptr;              // pyramid levels 1 .. kFlowMaxLevels - 1 of both images
+  uint32_t *flow_census = nullptr;          // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
+  short2 *flow_int = nullptr;               // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
+  short4 *flow_sub = nullptr;               // [maxF][maxN] sub-pixel terms of level 0
 };
 
 }  // namespace
@@ -94,6 +99,12 @@ struct ModContext {
     hipEvent_t ev_plane_read[MOD_PIPELINE_DEPTH + 1] = {};
     bool plane_read_pending[MOD_PIPELINE_DEPTH + 1] = {};
     bool ring_by_kernels = false;
+    // mod_submit_images_host: the left images, a ring indexed like the disparity planes (frame t's image is frame t+1's previous one;
+    // a frame that ends at a guard takes a plane but no ticket, so the ticket slots would not do)
+    uint8_t *limg[MOD_PIPELINE_DEPTH + 1] = {};
+    hipEvent_t ev_limg[MOD_PIPELINE_DEPTH + 1] = {};   // the last kernel that reads the image has been enqueued (context stream)
+    bool limg_used[MOD_PIPELINE_DEPTH + 1] = {};
+    bool have_prev_img = false;                    // limg[(dring - 1) % (DEPTH + 1)] holds the previous submit's left image
     int64_t dring = 0;                             // disparity planes handed out so far: plane of the next frame = dring % (DEPTH + 1)
     int64_t seq = 0;                               // frames submitted so far
     int in_flight = 0;
@@ -533,7 +544,8 @@ void mod_destroy(ModContext *c) {
   (void)hipStreamSynchronize(c->stream);
   Buffers &b = c->b;
   void *dev[] = {b.rayx, b.rayy, b.fc, b.mask, b.lroot, b.zrange, b.parent, b.rsize, b.rkey, b.cbox, b.counters, b.clusters, b.mbits, b.mpix,
-                 b.worklist, b.dbg, b.requests, b.tilehdr, b.tilelist, b.h_dnow, b.h_dprev, b.h_flow, b.h_planes, b.h_aos, b.h_labels, b.h_nobj, b.h_objects, b.sgm_census, b.sgm_maps, b.sgm_S};
+                 b.worklist, b.dbg, b.requests, b.tilehdr, b.tilelist, b.h_dnow, b.h_dprev, b.h_flow, b.h_planes, b.h_aos, b.h_labels, b.h_nobj, b.h_objects, b.sgm_census, b.sgm_maps, b.sgm_S,
+                 b.flow_img, b.flow_census, b.flow_int, b.flow_sub};
   for (void *p : dev) if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++) {
     if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
@@ -555,6 +567,10 @@ void mod_destroy(ModContext *c) {
       for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
     }
     if (p.ev_ring) (void)hipEventDestroy(p.ev_ring);
+    for (int i = 0; i <= MOD_PIPELINE_DEPTH; i++) {
+      if (p.limg[i]) (void)hipFree(p.limg[i]);
+      if (p.ev_limg[i]) (void)hipEventDestroy(p.ev_limg[i]);
+    }
     for (hipEvent_t e : p.ev_plane_read) if (e) (void)hipEventDestroy(e);
   }
   for (hipStream_t q : c->b.sgm_side) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
@@ -863,8 +879,97 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   return MOD_OK;
 }
 
+// ---- on-GPU optical flow (flow.hip) ---------------------------------------------------------------------------------------
+constexpr int kFlowMaxLevels = 6;
+constexpr int kFlowMinCoarse = 16;      // px on either side of the coarsest level
+
+// elements before level l in the per-level scratch regions: level k holds [2][maxF][(max_width >> k) * (max_height >> k)]
+static size_t flow_level_offset(const ModContext *c, int l) {
+  size_t off = 0;
+  for (int k = 0; k < l; k++) off += (size_t)2 * c->cfg.max_frames * (size_t)(c->cfg.max_width >> k) * (size_t)(c->cfg.max_height >> k);
+  return off;
+}
+
+static int check_flow_params(ModContext *c, const ModFlowParams *p, int frames) {
+  if (!p) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow parameters");
+  if (p->levels < 1 || p->levels > kFlowMaxLevels) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow levels must be in 1..6");
+  if (p->radius < 1 || p->radius > 8) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow radius must be in 1..8");
+  if (p->window != 3 && p->window != 5 && p->window != 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow window must be 3, 5 or 7");
+  if (p->subpixel != 0 && p->subpixel != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow subpixel must be 0 or 1");
+  if ((c->dc.W >> (p->levels - 1)) < kFlowMinCoarse || (c->dc.H >> (p->levels - 1)) < kFlowMinCoarse)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "too many flow levels: the coarsest would be smaller than 16 px");
+  if (2 * frames > 65535) return fail(c, MOD_ERR_CAPACITY, "flow takes at most 32767 frames per call");   // both images ride in grid.z
+  return MOD_OK;
+}
+
+static int ensure_flow_scratch(ModContext *c) {
+  Buffers &b = c->b;
+  if (b.flow_sub) return MOD_OK;                     // the last buffer of the set exists: all do
+  const size_t N = c->maxN, F = (size_t)c->cfg.max_frames;
+  HIP_TRY(c, dalloc(&b.flow_img, flow_level_offset(c, kFlowMaxLevels) - flow_level_offset(c, 1)));
+  HIP_TRY(c, dalloc(&b.flow_census, flow_level_offset(c, kFlowMaxLevels)));
+  HIP_TRY(c, dalloc(&b.flow_int, 2 * 2 * F * N));
+  HIP_TRY(c, dalloc(&b.flow_sub, F * N));
+  return MOD_OK;
+}
+
+int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, const uint8_t *now, const ModFlowParams *p, float *flow) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!prev || !now) return MOD_SKIP_NO_FLOW;                  // no image pair: no flow (estimateOpticalFlow fails, :279-290)
+  if (!flow) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow plane");
+  if ((rc = check_flow_params(c, p, frames))) return rc;
+  if ((rc = ensure_flow_scratch(c))) return rc;
+  Buffers &b = c->b;
+  const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
+  int Wl[kFlowMaxLevels], Hl[kFlowMaxLevels];
+  Wl[0] = c->dc.W; Hl[0] = c->dc.H;
+  for (int l = 1; l < L; l++) { Wl[l] = Wl[l - 1] >> 1; Hl[l] = Hl[l - 1] >> 1; }
+  const size_t img0 = flow_level_offset(c, 1);
+  auto img = [&](int l) { return b.flow_img + (flow_level_offset(c, l) - img0); };     // level l >= 1: [2][F][Hl][Wl]
+  auto cen = [&](int l) { return b.flow_census + flow_level_offset(c, l); };           // level l: [2][F][Hl][Wl]
+  for (int l = 1; l < L; l++) {
+    const size_t Ns = (size_t)Wl[l - 1] * Hl[l - 1];
+    launch_flow_pyramid(Wl[l - 1], Hl[l - 1], Wl[l], Hl[l], F, l == 1 ? prev : img(l - 1), l == 1 ? now : img(l - 1) + F * Ns, img(l), c->stream);
+  }
+  const size_t N = (size_t)Wl[0] * Hl[0];
+  launch_sgm_census(Wl[0], Hl[0], F, prev, cen(0), c->stream);
+  launch_sgm_census(Wl[0], Hl[0], F, now, cen(0) + F * N, c->stream);
+  for (int l = 1; l < L; l++) launch_sgm_census(Wl[l], Hl[l], 2 * F, img(l), cen(l), c->stream);
+  // coarse to fine; level l writes integer plane set (l & 1) and reads set ((l + 1) & 1)
+  const size_t set = 2 * (size_t)c->cfg.max_frames * c->maxN;
+  for (int l = L - 1; l >= 0; l--) {
+    const bool coarsest = l == L - 1;
+    launch_flow_match(Wl[l], Hl[l], coarsest ? 0 : Wl[l + 1], coarsest ? 0 : Hl[l + 1], F, dirs, p->window, p->radius, cen(l),
+                      coarsest ? nullptr : b.flow_int + ((l + 1) & 1) * set, b.flow_int + (l & 1) * set, (l == 0 && p->subpixel) ? b.flow_sub : nullptr,
+                      c->stream);
+  }
+  launch_flow_finish(Wl[0], Hl[0], F, b.flow_int, dirs == 2 ? b.flow_int + (size_t)F * N : nullptr, p->subpixel ? b.flow_sub : nullptr,
+                     p->fb_check, flow, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
 // ---- host-pointer convenience --------------------------------------------------------------------------------------
 static int ensure_host_staging(ModContext *c);
+
+int mod_flow_compute_host(ModContext *c, const uint8_t *prev, const uint8_t *now, const ModFlowParams *p, float *flow) {
+  int rc = check_ready(c, 1);
+  if (rc) return rc;
+  if (!prev || !now) return MOD_SKIP_NO_FLOW;
+  if (!flow) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow image");
+  if ((rc = check_flow_params(c, p, 1))) return rc;
+  if ((rc = ensure_host_staging(c))) return rc;
+  const size_t N = (size_t)c->dc.W * c->dc.H;
+  Buffers &b = c->b;
+  uint8_t *dimg = reinterpret_cast<uint8_t *>(b.h_flow);          // staging: the 8 N bytes of the flow slot hold both images
+  HIP_TRY(c, hipMemcpyAsync(dimg, prev, N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(dimg + N, now, N, hipMemcpyHostToDevice, c->stream));
+  if ((rc = mod_flow_compute_dev(c, 1, dimg, dimg + N, p, b.h_planes))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(flow, b.h_planes, 8 * N, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return MOD_OK;
+}
 
 int mod_sgm_compute_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *p, float *disparity) {
   int rc = check_ready(c, 1);
@@ -1073,6 +1178,7 @@ int mod_submit_frame_host(ModContext *c, const float *disparity_now, const float
   if (!ticket) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ticket");
   *ticket = -1;
   ModContext::Pipe &p = c->pipe;
+  p.have_prev_img = false;          // mod_submit_images_host pairs only with a left image of its own previous submit
   // the guards of construct() (scene_flow_constructor.cpp:104,110,122,127,133), in its order
   if (!flow) return MOD_SKIP_NO_FLOW;
   if (!disparity_prev && !p.have_prev) return MOD_SKIP_NO_DISPARITY_PREV;
@@ -1124,29 +1230,42 @@ int mod_submit_frame_host(ModContext *c, const float *disparity_now, const float
   return MOD_OK;
 }
 
-int mod_submit_stereo_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm, const float *flow,
-                           const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels, ModObject *objects,
-                           int32_t max_objects, float *disparity, int32_t *ticket) {
+// mod_submit_stereo_host (flow from the caller, fprm == nullptr) and mod_submit_images_host (flow == nullptr, estimated on the GPU
+// from the previous submit's left image with fprm)
+static int submit_stereo(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm, const float *flow,
+                         const ModFlowParams *fprm, const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels,
+                         ModObject *objects, int32_t max_objects, float *disparity, float *flow_out, int32_t *ticket) {
   int rc = check_ready(c, 1);
   if (rc) return rc;
   if (!ticket) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ticket");
   *ticket = -1;
   ModContext::Pipe &p = c->pipe;
+  const bool images = fprm != nullptr;
   if (!left || !right) {            // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276)
     p.have_prev = false;            // ... which becomes the next frame's (missing) previous disparity (:397-398)
+    p.have_prev_img = false;        // ... and the next frame has no previous image to estimate the flow from
     return MOD_SKIP_NO_DISPARITY_NOW;
   }
   if ((rc = check_sgm_params(c, sgm))) return rc;
+  if (images && (rc = check_flow_params(c, fprm, 1))) return rc;
   if (p.in_flight >= MOD_PIPELINE_DEPTH) return fail(c, MOD_ERR_CAPACITY, "MOD_PIPELINE_DEPTH frames are already in flight");
   if ((rc = ensure_pipe(c))) return rc;
   constexpr int R = MOD_PIPELINE_DEPTH + 1;
   const int slot = (int)(p.seq % MOD_PIPELINE_DEPTH), nowi = (int)(p.dring % R), previ = (int)((p.dring + R - 1) % R);
   const size_t N = (size_t)c->dc.W * c->dc.H;
   if (!p.img[slot]) HIP_TRY(c, dalloc(&p.img[slot], 2 * c->maxN));
+  if (images && !p.limg[nowi]) HIP_TRY(c, dalloc(&p.limg[nowi], c->maxN));
+  if (images && !p.ev_limg[nowi]) HIP_TRY(c, hipEventCreateWithFlags(&p.ev_limg[nowi], hipEventDisableTiming));
   // images (and flow) on the copy stream; the slot's image buffer may still be read by the estimator of a frame that ended at a
-  // guard (it took no ticket, so nobody waited for it): the copy queues behind that estimator
+  // guard (it took no ticket, so nobody waited for it): the copy queues behind that estimator.  A resident left image is replaced
+  // only after the last kernel that reads it (its own frame's and the next frame's estimators).
   if (p.img_used[slot]) HIP_TRY(c, hipStreamWaitEvent(p.h2d, p.ev_img[slot], 0));
-  HIP_TRY(c, hipMemcpyAsync(p.img[slot], left, N, hipMemcpyHostToDevice, p.h2d));
+  uint8_t *dleft = p.img[slot];
+  if (images) {
+    if (p.limg_used[nowi]) HIP_TRY(c, hipStreamWaitEvent(p.h2d, p.ev_limg[nowi], 0));
+    dleft = p.limg[nowi];
+  }
+  HIP_TRY(c, hipMemcpyAsync(dleft, left, N, hipMemcpyHostToDevice, p.h2d));
   HIP_TRY(c, hipMemcpyAsync(p.img[slot] + N, right, N, hipMemcpyHostToDevice, p.h2d));
   if (flow) HIP_TRY(c, hipMemcpyAsync(p.flow[slot], flow, 8 * N, hipMemcpyHostToDevice, p.h2d));
   HIP_TRY(c, hipEventRecord(p.ev_in[slot], p.h2d));
@@ -1154,16 +1273,23 @@ int mod_submit_stereo_host(ModContext *c, const uint8_t *left, const uint8_t *ri
   // estimateDisparity (:258-279) on the GPU, straight into the ring: this plane is `now` here and `previous` of the next frame.
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   if (p.plane_read_pending[nowi]) { HIP_TRY(c, hipStreamWaitEvent(c->stream, p.ev_plane_read[nowi], 0)); p.plane_read_pending[nowi] = false; }
-  if ((rc = mod_sgm_compute_dev(c, 1, p.img[slot], p.img[slot] + N, sgm, p.dnow[nowi]))) return rc;
+  if ((rc = mod_sgm_compute_dev(c, 1, dleft, p.img[slot] + N, sgm, p.dnow[nowi]))) return rc;
   HIP_TRY(c, hipEventRecord(p.ev_img[slot], c->stream));
   HIP_TRY(c, hipEventRecord(p.ev_ring, c->stream));
+  if (images) { HIP_TRY(c, hipEventRecord(p.ev_limg[nowi], c->stream)); p.limg_used[nowi] = true; }
   p.img_used[slot] = true; p.ring_by_kernels = true;
-  const bool had_prev = p.have_prev;
+  const bool had_prev = p.have_prev, has_flow = images ? p.have_prev_img : flow != nullptr;
   p.dring++; p.have_prev = true;    // disparity_previous_ = disparity_now_, whatever construct() does with the frame (:397-398)
+  p.have_prev_img = images;         // previous_left = left (:279-290), for the images stream only
   // the guards of construct() (:104,110,122,127,133), in its order; disparity_now exists by now
-  if (!flow) return MOD_SKIP_NO_FLOW;
+  if (!has_flow) return MOD_SKIP_NO_FLOW;
   if (!had_prev) return MOD_SKIP_NO_DISPARITY_PREV;
   if (!transform) return MOD_SKIP_NO_TRANSFORM;
+  if (images) {                     // estimateOpticalFlow (:279-290) on the GPU, straight into the frame's flow buffer
+    if ((rc = mod_flow_compute_dev(c, 1, p.limg[previ], p.limg[nowi], fprm, p.flow[slot]))) return rc;
+    HIP_TRY(c, hipEventRecord(p.ev_limg[previ], c->stream));
+    HIP_TRY(c, hipEventRecord(p.ev_limg[nowi], c->stream));
+  }
   ModFrameBatch in{};
   in.frames = 1; in.disparity_now = p.dnow[nowi]; in.disparity_prev = p.dnow[previ];
   in.flow = p.flow[slot]; in.transforms = transform; in.dt = &dt;
@@ -1186,6 +1312,8 @@ int mod_submit_stereo_host(ModContext *c, const uint8_t *left, const uint8_t *ri
     HIP_TRY(c, hipEventRecord(p.ev_plane_read[nowi], p.d2h));
     p.plane_read_pending[nowi] = true;
   }
+  // the slot's flow buffer is next written by the frame that takes this slot after this ticket has been collected
+  if (flow_out) HIP_TRY(c, hipMemcpyAsync(flow_out, p.flow[slot], 8 * N, hipMemcpyDeviceToHost, p.d2h));
   const int32_t ncopy = objects ? std::max(0, std::min(max_objects, (int32_t)c->max_objects)) : 0;
   if (ncopy > 0) HIP_TRY(c, hipMemcpyAsync(p.h_obj[slot], p.objects[slot], sizeof(ModObject) * ncopy, hipMemcpyDeviceToHost, p.d2h));
   p.user_obj[slot] = objects; p.user_cap[slot] = ncopy;
@@ -1194,6 +1322,19 @@ int mod_submit_stereo_host(ModContext *c, const uint8_t *left, const uint8_t *ri
   *ticket = (int32_t)(p.seq & 0x7fffffff);
   p.seq++; p.in_flight++;
   return MOD_OK;
+}
+
+int mod_submit_stereo_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm, const float *flow,
+                           const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels, ModObject *objects,
+                           int32_t max_objects, float *disparity, int32_t *ticket) {
+  return submit_stereo(c, left, right, sgm, flow, nullptr, transform, dt, cloud_aos, labels, objects, max_objects, disparity, nullptr, ticket);
+}
+
+int mod_submit_images_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm, const ModFlowParams *flow_prm,
+                           const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels, ModObject *objects,
+                           int32_t max_objects, float *disparity, float *flow_out, int32_t *ticket) {
+  if (c && !flow_prm) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow parameters");
+  return submit_stereo(c, left, right, sgm, nullptr, flow_prm, transform, dt, cloud_aos, labels, objects, max_objects, disparity, flow_out, ticket);
 }
 
 int mod_collect_frame_host(ModContext *c, int32_t ticket, int32_t *n_objects) {
@@ -1216,6 +1357,7 @@ int mod_collect_frame_host(ModContext *c, int32_t ticket, int32_t *n_objects) {
 int mod_forget_previous(ModContext *c) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   c->pipe.have_prev = false;
+  c->pipe.have_prev_img = false;
   return MOD_OK;
 }
 

@@ -161,6 +161,28 @@ class Context:
         return self._check(self.lib.mod_process_dev(self.h, C.byref(batch), C.byref(self._planes_struct(ws)),
                                                     C.byref(self._cluster_struct(ws))))
 
+    def estimate_flow(self, prev: torch.Tensor, now: torch.Tensor, params: Optional[capi.ModFlowParams] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """On-GPU optical flow (mod_flow_compute_dev) from `prev` to `now`: device uint8 tensors (F,H,W) or (H,W) of the camera size.
+        Returns (F,H,W,2) / (H,W,2) float32 indexed at the now pixel, prev = now - flow (NaN where the forward-backward check fails).
+        Enqueued on the context's stream."""
+        single = now.dim() == 2
+        p4, n4 = (prev[None], now[None]) if single else (prev, now)
+        if p4.shape != n4.shape or p4.dtype != torch.uint8 or n4.dtype != torch.uint8 or p4.shape[1:] != (self.height, self.width):
+            raise ValueError("prev / now must be uint8 tensors of the same shape (F, H, W) at the camera size")
+        if not (p4.is_contiguous() and n4.is_contiguous()):
+            raise ValueError("prev / now must be contiguous")
+        F = n4.shape[0]
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 2), dtype=torch.float32, device=now.device)
+        elif out.shape != (F, self.height, self.width, 2) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor (F, H, W, 2)")
+        prm = params if params is not None else capi.flow_params()
+        rc = self._check(self.lib.mod_flow_compute_dev(self.h, F, p4.data_ptr(), n4.data_ptr(), C.byref(prm), out.data_ptr()))
+        if rc != 0:
+            raise capi.ModError(rc, "mod_flow_compute_dev skipped")
+        return out[0] if single and out.dim() == 4 else out
+
     def synchronize(self) -> None:
         self._check(self.lib.mod_synchronize(self.h))
 

@@ -469,3 +469,91 @@ def make_box_flow(truth: np.ndarray, shift: float = 24.0) -> np.ndarray:
     flow = np.zeros((H, W, 2), np.float32)
     flow[truth > truth.min(), 0] = -np.float32(shift)
     return flow
+
+
+def make_moving_images(W: int, H: int, seed: int = 0, D: int = 128, n_boxes: int = 4, shift=(8, 20), frames: int = 2):
+    """Two consecutive stereo pairs in the style of make_stereo_images, seen by a camera that stands still: a static textured
+    background and `n_boxes` textured boxes (one per cell of a grid, so they never overlap) that translate by an integer (sx, sy),
+    |sx|, |sy| in `shift` (at most 24 px), between the pairs; every layer carries its texture along.  Returns a dict:
+      left0, right0, left1, right1   uint8 [H][W]  (pair 0 = previous, pair 1 = now; pairs 2 .. frames-1 likewise when frames > 2:
+                                     the boxes keep moving by the same shift)
+      disparity0, disparity1         float32 [H][W] true left disparities
+      flow                           float32 [H][W][2] true optical flow from pair 0 to pair 1 at the NOW pixel (prev = now - flow), x
+                                     then y; NaN where the pixel was not visible in the previous left image (disoccluded, or outside it);
+                                     flow1 .. flow{frames-1}: the same from pair k-1 to pair k
+      boxes                          list of (x0, y0, w, h) in pair 0, (sx, sy), disparity"""
+    lo, hi = int(shift[0]), int(shift[1])
+    if not 0 <= lo <= hi <= 24:
+        raise ValueError("shifts must lie in 0..24 px")
+    rng = np.random.Generator(np.random.PCG64([0x5F10000 + seed]))
+    if frames < 2:
+        raise ValueError("at least two pairs")
+    hi_total = hi * (frames - 1)                  # how far a box travels over the sequence
+    pad = D + 8 + 2 * hi_total
+
+    def texture():
+        t = rng.integers(0, 256, size=(H + 2 * hi_total, W + pad)).astype(np.float32)
+        k = np.array([1, 2, 1], np.float32) / 4
+        t = np.apply_along_axis(lambda r: np.convolve(r, k, mode="same"), 1, t)
+        t = np.apply_along_axis(lambda c: np.convolve(c, k, mode="same"), 0, t)
+        return np.clip(t, 0, 255).astype(np.uint8)
+
+    dmax = max(2, min(D - 1, W // 3))
+    d_bg = int(rng.integers(1, max(2, dmax // 8)))
+    cols = max(1, int(np.ceil(np.sqrt(n_boxes * W / H))))
+    rows = max(1, int(np.ceil(n_boxes / cols)))
+    cw, ch = W // cols, H // rows
+    cells = rng.permutation(rows * cols)[:n_boxes]
+    boxes = []
+    for cell in cells:
+        r, cl = divmod(int(cell), cols)
+        bw = int(rng.integers(max(8, cw // 3), max(9, cw - 2 * hi_total - 8)))
+        bh = int(rng.integers(max(8, ch // 3), max(9, ch - 2 * hi_total - 8)))
+        x0 = cl * cw + hi_total + 4 + int(rng.integers(0, max(1, cw - bw - 2 * hi_total - 8)))
+        y0 = r * ch + hi_total + 4 + int(rng.integers(0, max(1, ch - bh - 2 * hi_total - 8)))
+        sx = int(rng.integers(lo, hi + 1)) * (1 if rng.integers(0, 2) else -1)
+        sy = int(rng.integers(lo, hi + 1)) * (1 if rng.integers(0, 2) else -1)
+        boxes.append(((x0, y0, bw, bh), (sx, sy), int(rng.integers(dmax // 6 + 1, dmax))))
+    layers = [(d_bg, None, (0, 0), texture())] + [(d, rect, s, texture()) for rect, s, d in boxes]
+    layers.sort(key=lambda l: l[0])                                                 # far to near
+    xs = np.arange(W)
+    out = {}
+    owner = []
+    for k in range(frames):
+        left = np.zeros((H, W), np.uint8)
+        right = np.zeros((H, W), np.uint8)
+        truth = np.zeros((H, W), np.float32)
+        own = np.full((H, W), -1, np.int32)
+        for j, (d, rect, (sx, sy), tex) in enumerate(layers):
+            t = tex[hi_total - sy * k:hi_total - sy * k + H, hi_total - sx * k:hi_total - sx * k + W + D + 8]     # the texture moves with its layer
+            ml = np.ones((H, W), bool)
+            if rect is not None:
+                x0, y0, bw, bh = rect
+                ml = np.zeros((H, W), bool)
+                ml[y0 + sy * k:y0 + sy * k + bh, x0 + sx * k:x0 + sx * k + bw] = True
+            mr = np.zeros((H, W), bool)
+            mr[:, :W - d] = ml[:, d:]
+            if rect is None:
+                mr[:] = True
+            left = np.where(ml, t[:, xs], left)
+            right = np.where(mr, t[:, xs + d], right)
+            truth = np.where(ml, np.float32(d), truth)
+            own = np.where(ml, j, own)
+        noise = rng.integers(-2, 3, size=(2, H, W))
+        out[f"left{k}"] = np.clip(left.astype(np.int32) + noise[0], 0, 255).astype(np.uint8)
+        out[f"right{k}"] = np.clip(right.astype(np.int32) + noise[1], 0, 255).astype(np.uint8)
+        out[f"disparity{k}"] = truth
+        owner.append(own)
+    ys, xg = np.mgrid[0:H, 0:W]
+    for k in range(1, frames):
+        flow = np.full((H, W, 2), np.nan, np.float32)
+        for j, (d, rect, (sx, sy), tex) in enumerate(layers):
+            px, py = xg - sx, ys - sy
+            inside = (px >= 0) & (px < W) & (py >= 0) & (py < H)
+            seen = inside & (owner[k] == j)
+            seen[seen] = owner[k - 1][py[seen], px[seen]] == j                         # the same layer was visible there before
+            flow[seen] = (np.float32(sx), np.float32(sy))
+        out[f"flow{k}"] = flow
+    out["flow"] = out["flow1"]
+    out["boxes"] = boxes
+    return out

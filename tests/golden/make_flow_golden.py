@@ -1,0 +1,34 @@
+"""Writes tests/golden/flow/flow_320x240.npz (a directory of its own: the scene-flow fixture tests take every .npz of
+tests/golden): two image pairs (moving textured boxes, moving_object_detector_amd.synth.make_moving_images)
+and the flow of the numpy restatement (tests/models/flow_model.py) under two parameter sets.  The fixture pins the model against
+drift; tests/test_flow_model.py and tests/test_gpu_flow.py read it.  Run from the repository root:
+    python tests/golden/make_flow_golden.py"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "models"))
+
+import flow_model as fm  # noqa: E402
+from moving_object_detector_amd import synth  # noqa: E402
+
+W, H = 320, 240
+PARAMS = [(4, 4, 5, 1, 1), (3, 3, 3, 1, -1)]      # levels, radius, window, subpixel, fb_check
+
+
+def main():
+    prev, now, flow = [], [], []
+    for k, prm in enumerate(PARAMS):
+        m = synth.make_moving_images(W, H, seed=20 + k, n_boxes=3, shift=(3, 12))
+        prev.append(m["left0"]); now.append(m["left1"])
+        flow.append(fm.flow(m["left0"], m["left1"], fm.FlowParams(*prm)))
+    np.savez_compressed(os.path.join(HERE, "flow", "flow_320x240.npz"), pairs=np.int32(len(PARAMS)), params=np.array(PARAMS, np.int32),
+                        prev=np.stack(prev), now=np.stack(now), flow=np.stack(flow))
+
+
+if __name__ == "__main__":
+    main()
