@@ -256,6 +256,53 @@ int  mod_flow_compute_dev(ModContext *ctx, int32_t frames, const uint8_t *prev, 
 /* the same for one frame in host memory; synchronous */
 int  mod_flow_compute_host(ModContext *ctx, const uint8_t *prev, const uint8_t *now, const ModFlowParams *params, float *flow);
 
+/* ---- on-GPU stereo ego-motion ---------------------------------------------------------------------------------------------- */
+/* The reference obtains transform_prev2now_ from libviso2 (VisualOdometryStereo::process + getMotion(),
+ * scene_flow_constructor.cpp:214-256), sparse features matched in four images on the CPU.  This estimator is NOT libviso2 and
+ * claims no parity with it: it keeps libviso2's model (RANSAC, then Gauss-Newton on the stereo reprojection error of previous-frame
+ * 3D points seen in the current pair) and its output convention (motion prev -> now, P_now = R P_prev + t), but works from the
+ * dense correspondences already in HBM: disparity_prev, disparity_now and the flow of the frame.  Deterministic; integer stages
+ * bit-exact with tests/models/ego_model.py, which restates every step:
+ *   correspondences  now pixels on a `stride` grid with valid disparity now, finite flow, prev pixel roundf(x - flow) in the image
+ *                    with valid disparity; valid = finite, >= max(camera min_disparity, min_disparity), <= max_disparity, > 0
+ *   hypotheses       `hypotheses` triples drawn by splitmix64(seed, h, k); closed-form triad alignment of prev and now points
+ *   scoring          inlier = all three residuals (left u, v, right u) of the moved point below inlier_threshold px; most inliers
+ *                    wins, ties to the lowest h
+ *   refinement       Gauss-Newton (rotation vector + t) on the best hypothesis's inliers, inliers selected again, Gauss-Newton
+ *                    again; at most `iterations` steps in all; fixed-order f64 sums
+ * The transform is the quaternion of tf2::Matrix3x3::getRotation (host/messages.hpp transform_from_motion), as the reference
+ * hands construct() (scene_flow_constructor.cpp:248-249).  Failure: status != MOD_EGO_OK and an all-NaN transform. */
+#define MOD_EGO_OK           0
+#define MOD_EGO_FEW_POINTS   1   /* fewer than max(3, min_inliers) correspondences */
+#define MOD_EGO_FEW_INLIERS  2   /* best (or refined) inlier count below min_inliers */
+#define MOD_EGO_DIVERGED     3   /* singular or non-finite Gauss-Newton system */
+#define MOD_EGO_MAX_HYPOTHESES 4096
+typedef struct ModEgoParams {   /* defaults: 4, 256, 10, 50, 2.0f, 1.0f, 0, 0 */
+  int32_t  stride;              /* 1..64: grid step of the now pixels */
+  int32_t  hypotheses;          /* 1..MOD_EGO_MAX_HYPOTHESES */
+  int32_t  iterations;          /* 0..100 Gauss-Newton steps in all */
+  int32_t  min_inliers;         /* >= 0 */
+  float    inlier_threshold;    /* > 0, px */
+  float    min_disparity;       /* finite: correspondences need a larger disparity (far points carry little translation) */
+  uint32_t seed;                /* RANSAC draws; independent of the frame's place in a batch */
+  int32_t  reserved;
+} ModEgoParams;
+typedef struct ModEgoResult {
+  int32_t status;               /* MOD_EGO_* */
+  int32_t correspondences;
+  int32_t inliers;              /* of the final motion (on failure: the count that failed) */
+  int32_t iterations;           /* Gauss-Newton steps taken */
+  double  rms_px;               /* rms of the inliers' residuals (NaN on failure) */
+} ModEgoResult;
+/* Device planes [frames][H][W] (flow [frames][H][W][2]); transforms: device [frames]; results: device [frames] or NULL.  Ordered on
+ * the context's stream; scratch is allocated on first use (grows to the smallest stride seen).  NULL plane -> the skip code of
+ * construct()'s guard for it (MOD_SKIP_NO_DISPARITY_PREV / _NOW, MOD_SKIP_NO_FLOW). */
+int  mod_egomotion_dev(ModContext *ctx, int32_t frames, const float *disparity_prev, const float *disparity_now, const float *flow,
+                       const ModEgoParams *params, ModTransform *transforms, ModEgoResult *results);
+/* one frame in host memory; synchronous; MOD_SKIP_NO_TRANSFORM when the estimate failed (transform NaN, result says why) */
+int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const float *disparity_now, const float *flow,
+                        const ModEgoParams *params, ModTransform *transform, ModEgoResult *result);
+
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()
  * would publish nothing.  cloud_aos: W*H*32 bytes; labels: W*H int32; objects: capacity `max_objects`.
@@ -335,6 +382,19 @@ int  mod_submit_images_host(ModContext *ctx, const uint8_t *left, const uint8_t 
                             const ModFlowParams *flow_prm, const ModTransform *transform, double dt, void *cloud_aos,
                             int32_t *labels, ModObject *objects, int32_t max_objects, float *disparity, float *flow_out,
                             int32_t *ticket);
+/* Stereo images in, moving objects out, nothing else on the host: mod_submit_images_host whose transform is estimated on the GPU
+ * (mod_egomotion_dev on the frame's disparity pair and flow, ego_prm).  sgm -> flow -> ego-motion -> scene flow + clusters on the
+ * context's stream; the estimator's last kernel writes the frame's constants for the scene-flow kernel straight into HBM, so no
+ * transform crosses PCIe before the scene flow runs.  First frame, mod_forget_previous, NULL images, a submit of another kind: as
+ * mod_submit_images_host.  A frame whose estimate fails (visual odometry failed, scene_flow_constructor.cpp:251-255) still runs
+ * with the NaN transform — every velocity NaN, every label -1, no object — and mod_collect_frame_host returns
+ * MOD_SKIP_NO_TRANSFORM for its ticket with 0 objects.
+ *   transform_out, ego_out   optional host copies of the estimate, valid after collect
+ * Other arguments as mod_submit_images_host. */
+int  mod_submit_odometry_host(ModContext *ctx, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm,
+                              const ModFlowParams *flow_prm, const ModEgoParams *ego_prm, double dt, void *cloud_aos, int32_t *labels,
+                              ModObject *objects, int32_t max_objects, float *disparity, float *flow_out, ModTransform *transform_out,
+                              ModEgoResult *ego_out, int32_t *ticket);
 /* disparity_now_.reset() of a failed estimateDisparity (scene_flow_constructor.cpp:272-276): the next submit without an
  * explicit disparity_prev reports MOD_SKIP_NO_DISPARITY_PREV instead of pairing with a stale frame. */
 int  mod_forget_previous(ModContext *ctx);

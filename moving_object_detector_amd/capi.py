@@ -30,6 +30,8 @@ MOD_STAGE_FINAL, MOD_STAGE_MEDIAN, MOD_STAGE_CLUSTER_GROUP, MOD_STAGE_COUNT = 4,
 MOD_PROFILE_ALL = 0x7F
 MOD_PER_KERNEL_CLUSTER_STAGES = (1, 2, 3, 4, 5)
 MOD_PIPELINE_DEPTH = 3
+MOD_EGO_OK, MOD_EGO_FEW_POINTS, MOD_EGO_FEW_INLIERS, MOD_EGO_DIVERGED = 0, 1, 2, 3
+MOD_EGO_MAX_HYPOTHESES = 4096
 STAGE_NAMES = ("k_scene_flow", "k_ccl_bits+k_ccl_tile_list", "k_ccl_link", "k_ccl_merge", "k_final", "k_median+k_median_ties",
                "cluster group (first launch to last)")
 
@@ -43,6 +45,7 @@ EXPORTS = [
     "mod_get_stage_time", "mod_reset_stage_times", "mod_depth_image_dev", "mod_depth_image_host", "mod_static_flow_host",
     "mod_sgm_census_dev", "mod_sgm_path_dev", "mod_sgm_compute_dev", "mod_sgm_compute_host",
     "mod_flow_compute_dev", "mod_flow_compute_host", "mod_submit_images_host",
+    "mod_egomotion_dev", "mod_egomotion_host", "mod_submit_odometry_host",
 ]
 
 
@@ -101,6 +104,23 @@ def flow_max_displacement(p: ModFlowParams) -> int:
     return p.radius * (1 << (p.levels - 1)) + (1 << (p.levels - 1)) - 1
 
 
+class ModEgoParams(C.Structure):
+    _fields_ = [("stride", C.c_int32), ("hypotheses", C.c_int32), ("iterations", C.c_int32), ("min_inliers", C.c_int32),
+                ("inlier_threshold", C.c_float), ("min_disparity", C.c_float), ("seed", C.c_uint32), ("reserved", C.c_int32)]
+
+
+class ModEgoResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("correspondences", C.c_int32), ("inliers", C.c_int32), ("iterations", C.c_int32),
+                ("rms_px", C.c_double)]
+
+
+def ego_params(stride: int = 4, hypotheses: int = 256, iterations: int = 10, min_inliers: int = 50, inlier_threshold: float = 2.0,
+               min_disparity: float = 1.0, seed: int = 0) -> ModEgoParams:
+    """ModEgoParams with the defaults of include/mod_sf.h."""
+    return ModEgoParams(int(stride), int(hypotheses), int(iterations), int(min_inliers), float(inlier_threshold), float(min_disparity),
+                        int(seed) & 0xFFFFFFFF, 0)
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -154,6 +174,10 @@ def load(require_torch_first: bool = True):
     L.mod_flow_compute_host.argtypes = [vp, vp, vp, C.POINTER(ModFlowParams), vp]
     L.mod_submit_images_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModTransform), C.c_double,
                                          vp, vp, vp, i32, vp, vp, C.POINTER(i32)]
+    L.mod_egomotion_dev.argtypes = [vp, i32, vp, vp, vp, C.POINTER(ModEgoParams), vp, vp]
+    L.mod_egomotion_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.POINTER(ModEgoResult)]
+    L.mod_submit_odometry_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.c_double,
+                                           vp, vp, vp, i32, vp, vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

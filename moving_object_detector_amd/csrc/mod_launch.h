@@ -1,5 +1,6 @@
 // mod_launch.h — host-callable launchers of the gfx950 kernels (internal to libmod_sf.so).
 #pragma once
+#include "../../include/mod_sf.h"
 #include "mod_device.h"
 
 struct SfArgs {
@@ -95,3 +96,27 @@ void launch_flow_match(int W, int H, int W1, int H1, int frames, int dirs, int w
                        const short2 *coarse, short2 *out, short4 *sub, hipStream_t s);
 // level 0 winners (+ backward field G when fb >= 0, + sub-pixel terms) -> flow [frames][H][W][2] f32
 void launch_flow_finish(int W, int H, int frames, const short2 *F, const short2 *G, const short4 *sub, int fb, float *flow, hipStream_t s);
+
+// on-GPU stereo ego-motion (egomotion.hip).  One launch sequence for `frames` frames; all pointers device.
+struct EgoArgs {
+  int W, H, frames, stride, gw, gh;   // grid of now pixels: gw = ceil(W / stride) columns, gh rows
+  int cap;                            // correspondences per frame the scratch holds (>= gw * gh)
+  int hyps, iterations, min_inliers;
+  uint32_t seed;
+  float dlo, dhi;                     // disparity range: max(camera min_disparity, min_disparity), camera max_disparity
+  double th;                          // inlier_threshold
+  double fx, fy, cx, cy, Tx, Ty, fT;  // fT = f64 of the F32 product disp_f * disp_T (DevCam.fT)
+  const float *dprev, *dnow, *flow;   // [F][H][W], [F][H][W], [F][H][W][2]
+  double *corr;                       // [F][9][cap]: P xyz, Q xyz, O (u, v, u_r) of the kept samples, raster order
+  int32_t *blkcnt;                    // [F][ego_grid_blocks]: kept samples per block
+  int32_t *ncorr;                     // [F]
+  double *hyp;                        // [F][hyps][12]: row-major 3 x 4 motion of every hypothesis
+  int32_t *hcnt;                      // [F][hyps]: inlier count, -1 = invalid hypothesis
+  uint8_t *flag;                      // [F][cap]: inlier of the refinement's current selection
+  double *tf;                         // [F][7] ModTransform
+  ModEgoResult *res;                  // [F]
+  FrameConst *fc;                     // [F] or null: the frames' scene-flow constants from the estimate, with dt
+  double dt;
+};
+int ego_grid_blocks(int gw, int gh);   // blocks of the correspondence kernels per frame
+void launch_egomotion(const EgoArgs &a, hipStream_t s);

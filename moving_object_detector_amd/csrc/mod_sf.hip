@@ -2,6 +2,7 @@
 // Host-side only; the kernels live in sceneflow.hip and cluster.hip.
 #include "../../include/mod_sf.h"
 #include "exact_div.h"
+#include "frame_const.h"
 #include "mod_launch.h"
 #include "mod_sf_debug.h"
 
@@ -59,6 +60,16 @@ struct Buffers {
   uint32_t *flow_census = nullptr;          // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
   short2 *flow_int = nullptr;               // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
   short4 *flow_sub = nullptr;               // [maxF][maxN] sub-pixel terms of level 0
+  // on-GPU ego-motion (allocated on first use; the correspondence buffers grow to the smallest stride seen: see ensure_ego_scratch)
+  double *ego_corr = nullptr;               // [maxF][9][ego_cap]
+  uint8_t *ego_flag = nullptr;              // [maxF][ego_cap]
+  int32_t *ego_blkcnt = nullptr;            // [maxF][blocks of the grid at the smallest stride]
+  size_t ego_cap = 0;
+  int32_t *ego_ncorr = nullptr;             // [maxF]
+  double *ego_hyp = nullptr;                // [maxF][MOD_EGO_MAX_HYPOTHESES][12]
+  int32_t *ego_hcnt = nullptr;              // [maxF][MOD_EGO_MAX_HYPOTHESES]
+  ModTransform *ego_tf = nullptr;           // [maxF] mod_egomotion_host / a NULL `results` of mod_egomotion_dev
+  ModEgoResult *ego_res = nullptr;          // [maxF]
 };
 
 }  // namespace
@@ -105,6 +116,13 @@ struct ModContext {
     hipEvent_t ev_limg[MOD_PIPELINE_DEPTH + 1] = {};   // the last kernel that reads the image has been enqueued (context stream)
     bool limg_used[MOD_PIPELINE_DEPTH + 1] = {};
     bool have_prev_img = false;                    // limg[(dring - 1) % (DEPTH + 1)] holds the previous submit's left image
+    // mod_submit_odometry_host: the slot's estimate on the device and its pinned host copy; collect reads the status
+    struct EgoSlot { ModTransform tf; ModEgoResult res; };
+    EgoSlot *ego = nullptr;                        // device [DEPTH]
+    EgoSlot *h_ego[MOD_PIPELINE_DEPTH] = {};       // pinned
+    bool odo[MOD_PIPELINE_DEPTH] = {};             // the slot's ticket came from the odometry stream
+    ModTransform *user_tf[MOD_PIPELINE_DEPTH] = {};
+    ModEgoResult *user_ego[MOD_PIPELINE_DEPTH] = {};
     int64_t dring = 0;                             // disparity planes handed out so far: plane of the next frame = dring % (DEPTH + 1)
     int64_t seq = 0;                               // frames submitted so far
     int in_flight = 0;
@@ -122,6 +140,8 @@ struct ModContext {
   // a small batch feels (a launch costs it ~8 us of GPU time whatever it does).  False while a call is being enqueued; a call that
   // failed half-way leaves it false and the next one clears the scratch itself.
   bool scratch_clean = false;
+  // the odometry stream's estimator has written the frame's FrameConst into b.fc on the stream: the scene-flow launch reads it there
+  bool fc_resident = false;
   int profiling = 0;                          // stage mask of mod_set_profiling
   std::vector<EventPair> pending[MOD_STAGE_COUNT];
   std::vector<EventPair> free_events;
@@ -157,19 +177,6 @@ float floor_to_f32(double th) {
   float t = (float)th;
   if ((double)t > th) t = std::nextafterf(t, -INFINITY);
   return t;
-}
-
-// Eigen::Quaterniond::toRotationMatrix operation order (tf2::transformToEigen, scene_flow_constructor.cpp:411);
-// the quaternion is used as given, without normalisation.
-void transform_to_rows(const ModTransform &tf, double m[12]) {
-  const double x = tf.q[0], y = tf.q[1], z = tf.q[2], w = tf.q[3];
-  const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
-  const double twx = tx * w, twy = ty * w, twz = tz * w;
-  const double txx = tx * x, txy = ty * x, txz = tz * x;
-  const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
-  m[0] = 1.0 - (tyy + tzz); m[1] = txy - twz;         m[2] = txz + twy;          m[3] = tf.t[0];
-  m[4] = txy + twz;         m[5] = 1.0 - (txx + tzz); m[6] = tyz - twx;          m[7] = tf.t[1];
-  m[8] = txz - twy;         m[9] = tyz + twx;         m[10] = 1.0 - (txx + tyy); m[11] = tf.t[2];
 }
 
 // Smallest F32 a >= 0 with sqrtf(a) >= th, so that the kernels test a sum of squares instead of taking its root:
@@ -242,32 +249,14 @@ void drain_timers(ModContext *c) {
   }
 }
 
-void fill_frame_const(FrameConst &h, const ModTransform &tf, double dt) {
-  transform_to_rows(tf, h.m);
-  h.dt = dt;
-  // |t_i + (m_i0 x + (m_i1 y + m_i2 z))| <= tmax + 3 mmax B stays below FLT_MAX / 2 (so the F32 cast is finite, and no
-  // intermediate can overflow or turn NaN) for every |x|,|y|,|z| <= B.  Non-finite transforms get B = 0: always compute.
-  double mmax = 0.0, tmax = 0.0;
-  bool finite = true;
-  for (int i = 0; i < 12; i++) {
-    const double v = std::fabs(h.m[i]);
-    finite = finite && std::isfinite(v);
-    if (i % 4 == 3) tmax = std::max(tmax, v); else mmax = std::max(mmax, v);
-  }
-  double B = 0.0;
-  if (finite && tmax < 1e37) B = std::min((1.7e38 - tmax) / (3.0 * std::max(mmax, 1e-30)), 1e30);
-  h.pad[0] = B;
-  // velocity = difference / dt through the correctly rounded reciprocal (exact_div.h) when dt is an ordinary number
-  const bool usable = exact_div::reciprocal_usable(h.dt);
-  h.pad[1] = usable ? 1.0 / h.dt : 0.0;
-  h.pad[2] = usable ? 1.0 : 0.0;
-}
+void fill_frame_const(FrameConst &h, const ModTransform &tf, double dt) { fill_frame_const(h, tf.t, tf.q, dt); }   // frame_const.h
 
 // The per-frame constants of a batch.  Up to MOD_SF_INLINE_FRAMES frames: into `inl`, which the scene-flow launch passes in its
 // kernel arguments (inl->used) — nothing is copied, nothing waited for.  Larger batches: through the pinned ring into c->b.fc.
 struct InlineConsts { FrameConst v[MOD_SF_INLINE_FRAMES]; bool used = false; };
 
 int upload_frame_consts(ModContext *c, const ModFrameBatch *in, InlineConsts *inl) {
+  if (c->fc_resident) return MOD_OK;
   if (inl && in->frames <= MOD_SF_INLINE_FRAMES) {
     for (int f = 0; f < in->frames; f++) fill_frame_const(inl->v[f], in->transforms[f], in->dt[f]);
     inl->used = true;
@@ -545,7 +534,8 @@ void mod_destroy(ModContext *c) {
   Buffers &b = c->b;
   void *dev[] = {b.rayx, b.rayy, b.fc, b.mask, b.lroot, b.zrange, b.parent, b.rsize, b.rkey, b.cbox, b.counters, b.clusters, b.mbits, b.mpix,
                  b.worklist, b.dbg, b.requests, b.tilehdr, b.tilelist, b.h_dnow, b.h_dprev, b.h_flow, b.h_planes, b.h_aos, b.h_labels, b.h_nobj, b.h_objects, b.sgm_census, b.sgm_maps, b.sgm_S,
-                 b.flow_img, b.flow_census, b.flow_int, b.flow_sub};
+                 b.flow_img, b.flow_census, b.flow_int, b.flow_sub, b.ego_corr, b.ego_flag, b.ego_blkcnt, b.ego_ncorr, b.ego_hyp,
+                 b.ego_hcnt, b.ego_tf, b.ego_res};
   for (void *p : dev) if (p) (void)hipFree(p);
   for (int i = 0; i < kRing; i++) {
     if (c->pinned[i]) (void)hipHostFree(c->pinned[i]);
@@ -572,6 +562,8 @@ void mod_destroy(ModContext *c) {
       if (p.ev_limg[i]) (void)hipEventDestroy(p.ev_limg[i]);
     }
     for (hipEvent_t e : p.ev_plane_read) if (e) (void)hipEventDestroy(e);
+    if (p.ego) (void)hipFree(p.ego);
+    for (auto *h : p.h_ego) if (h) (void)hipHostFree(h);
   }
   for (hipStream_t q : c->b.sgm_side) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
   for (int k = 0; k < 2; k++) {
@@ -971,6 +963,105 @@ int mod_flow_compute_host(ModContext *c, const uint8_t *prev, const uint8_t *now
   return MOD_OK;
 }
 
+// ---- on-GPU ego-motion (egomotion.hip) -------------------------------------------------------------------------------------
+static int check_ego_params(ModContext *c, const ModEgoParams *p) {
+  if (!p) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ego-motion parameters");
+  if (p->stride < 1 || p->stride > 64) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion stride must be in 1..64");
+  if (p->hypotheses < 1 || p->hypotheses > MOD_EGO_MAX_HYPOTHESES)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion hypotheses must be in 1..4096");
+  if (p->iterations < 0 || p->iterations > 100) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion iterations must be in 0..100");
+  if (p->min_inliers < 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion min_inliers must be >= 0");
+  if (!(p->inlier_threshold > 0.0f) || !std::isfinite(p->inlier_threshold))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion inlier_threshold must be a positive number");
+  if (!std::isfinite(p->min_disparity)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion min_disparity must be finite");
+  return MOD_OK;
+}
+
+// Correspondence scratch for `stride` (max_width x max_height x max_frames / stride^2); grows, after a sync, when a smaller stride comes.
+static int ensure_ego_scratch(ModContext *c, int stride) {
+  Buffers &b = c->b;
+  const size_t F = (size_t)c->cfg.max_frames;
+  const int gw = (c->cfg.max_width + stride - 1) / stride, gh = (c->cfg.max_height + stride - 1) / stride;
+  const size_t cap = (size_t)gw * gh;
+  if (cap > b.ego_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (void *q : {(void *)b.ego_corr, (void *)b.ego_flag, (void *)b.ego_blkcnt}) if (q) HIP_TRY(c, hipFree(q));
+    b.ego_corr = nullptr; b.ego_flag = nullptr; b.ego_blkcnt = nullptr; b.ego_cap = 0;
+    HIP_TRY(c, dalloc(&b.ego_corr, F * 9 * cap));
+    HIP_TRY(c, dalloc(&b.ego_flag, F * cap));
+    HIP_TRY(c, dalloc(&b.ego_blkcnt, F * (size_t)ego_grid_blocks(gw, gh)));
+    b.ego_cap = cap;
+  }
+  if (!b.ego_res) {
+    HIP_TRY(c, dalloc(&b.ego_ncorr, F));
+    HIP_TRY(c, dalloc(&b.ego_hyp, F * MOD_EGO_MAX_HYPOTHESES * 12));
+    HIP_TRY(c, dalloc(&b.ego_hcnt, F * MOD_EGO_MAX_HYPOTHESES));
+    HIP_TRY(c, dalloc(&b.ego_tf, F));
+    HIP_TRY(c, dalloc(&b.ego_res, F));
+  }
+  return MOD_OK;
+}
+
+// the estimator over `frames` frames; fc != null: also the frames' scene-flow constants (with dt) into fc
+static int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p,
+                         ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt) {
+  int rc = ensure_ego_scratch(c, p->stride);
+  if (rc) return rc;
+  Buffers &b = c->b;
+  EgoArgs a;
+  a.W = c->dc.W; a.H = c->dc.H; a.frames = frames; a.stride = p->stride;
+  a.gw = (a.W + p->stride - 1) / p->stride; a.gh = (a.H + p->stride - 1) / p->stride;
+  a.cap = (int)b.ego_cap;
+  a.hyps = p->hypotheses; a.iterations = p->iterations; a.min_inliers = p->min_inliers; a.seed = p->seed;
+  a.dlo = std::max(c->cam.min_disparity, p->min_disparity); a.dhi = c->cam.max_disparity;
+  a.th = (double)p->inlier_threshold;
+  a.fx = c->cam.fx; a.fy = c->cam.fy; a.cx = c->cam.cx; a.cy = c->cam.cy; a.Tx = c->cam.Tx; a.Ty = c->cam.Ty; a.fT = (double)c->dc.fT;
+  a.dprev = dprev; a.dnow = dnow; a.flow = flow;
+  a.corr = b.ego_corr; a.blkcnt = b.ego_blkcnt; a.ncorr = b.ego_ncorr; a.hyp = b.ego_hyp; a.hcnt = b.ego_hcnt; a.flag = b.ego_flag;
+  a.tf = reinterpret_cast<double *>(tf); a.res = res ? res : b.ego_res; a.fc = fc; a.dt = dt;
+  static_assert(sizeof(ModTransform) == 7 * sizeof(double), "ModTransform is 7 doubles");
+  launch_egomotion(a, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_egomotion_dev(ModContext *c, int32_t frames, const float *disparity_prev, const float *disparity_now, const float *flow,
+                      const ModEgoParams *p, ModTransform *transforms, ModEgoResult *results) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if ((rc = check_ego_params(c, p))) return rc;
+  if (!transforms) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null transforms");
+  if (!flow) return MOD_SKIP_NO_FLOW;                          // construct()'s guards, in its order
+  if (!disparity_prev) return MOD_SKIP_NO_DISPARITY_PREV;
+  if (!disparity_now) return MOD_SKIP_NO_DISPARITY_NOW;
+  return run_egomotion(c, frames, disparity_prev, disparity_now, flow, p, transforms, results, nullptr, 0.0);
+}
+
+int mod_egomotion_host(ModContext *c, const float *disparity_prev, const float *disparity_now, const float *flow, const ModEgoParams *p,
+                       ModTransform *transform, ModEgoResult *result) {
+  int rc = check_ready(c, 1);
+  if (rc) return rc;
+  if ((rc = check_ego_params(c, p))) return rc;
+  if (!transform) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null transform");
+  if (!flow) return MOD_SKIP_NO_FLOW;
+  if (!disparity_prev) return MOD_SKIP_NO_DISPARITY_PREV;
+  if (!disparity_now) return MOD_SKIP_NO_DISPARITY_NOW;
+  if ((rc = ensure_host_staging(c))) return rc;
+  const size_t N = (size_t)c->dc.W * c->dc.H;
+  Buffers &b = c->b;
+  HIP_TRY(c, hipMemcpyAsync(b.h_dprev, disparity_prev, 4 * N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(b.h_dnow, disparity_now, 4 * N, hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(b.h_flow, flow, 8 * N, hipMemcpyHostToDevice, c->stream));
+  if ((rc = ensure_ego_scratch(c, p->stride))) return rc;
+  if ((rc = run_egomotion(c, 1, b.h_dprev, b.h_dnow, b.h_flow, p, b.ego_tf, b.ego_res, nullptr, 0.0))) return rc;
+  ModEgoResult r{};
+  HIP_TRY(c, hipMemcpyAsync(transform, b.ego_tf, sizeof(ModTransform), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(&r, b.ego_res, sizeof(ModEgoResult), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (result) *result = r;
+  return r.status == MOD_EGO_OK ? MOD_OK : MOD_SKIP_NO_TRANSFORM;   // visual odometry failed: construct() publishes nothing (:251-255)
+}
+
 int mod_sgm_compute_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *p, float *disparity) {
   int rc = check_ready(c, 1);
   if (rc) return rc;
@@ -1223,6 +1314,7 @@ int mod_submit_frame_host(ModContext *c, const float *disparity_now, const float
   const int32_t ncopy = objects ? std::max(0, std::min(max_objects, (int32_t)c->max_objects)) : 0;
   if (ncopy > 0) HIP_TRY(c, hipMemcpyAsync(p.h_obj[slot], p.objects[slot], sizeof(ModObject) * ncopy, hipMemcpyDeviceToHost, p.d2h));
   p.user_obj[slot] = objects; p.user_cap[slot] = ncopy;
+  p.odo[slot] = false;
   if (cloud_aos) HIP_TRY(c, hipMemcpyAsync(cloud_aos, p.aos[slot], 32 * N, hipMemcpyDeviceToHost, p.d2h));
   HIP_TRY(c, hipEventRecord(p.ev_out[slot], p.d2h));
   *ticket = (int32_t)(p.seq & 0x7fffffff);
@@ -1230,17 +1322,18 @@ int mod_submit_frame_host(ModContext *c, const float *disparity_now, const float
   return MOD_OK;
 }
 
-// mod_submit_stereo_host (flow from the caller, fprm == nullptr) and mod_submit_images_host (flow == nullptr, estimated on the GPU
-// from the previous submit's left image with fprm)
+// mod_submit_stereo_host (flow from the caller, fprm == nullptr), mod_submit_images_host (flow == nullptr, estimated on the GPU
+// from the previous submit's left image with fprm) and mod_submit_odometry_host (eprm != nullptr: the transform estimated on the GPU too)
 static int submit_stereo(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm, const float *flow,
                          const ModFlowParams *fprm, const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels,
-                         ModObject *objects, int32_t max_objects, float *disparity, float *flow_out, int32_t *ticket) {
+                         ModObject *objects, int32_t max_objects, float *disparity, float *flow_out, int32_t *ticket,
+                         const ModEgoParams *eprm = nullptr, ModTransform *transform_out = nullptr, ModEgoResult *ego_out = nullptr) {
   int rc = check_ready(c, 1);
   if (rc) return rc;
   if (!ticket) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ticket");
   *ticket = -1;
   ModContext::Pipe &p = c->pipe;
-  const bool images = fprm != nullptr;
+  const bool images = fprm != nullptr, odo = eprm != nullptr;
   if (!left || !right) {            // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276)
     p.have_prev = false;            // ... which becomes the next frame's (missing) previous disparity (:397-398)
     p.have_prev_img = false;        // ... and the next frame has no previous image to estimate the flow from
@@ -1248,6 +1341,7 @@ static int submit_stereo(ModContext *c, const uint8_t *left, const uint8_t *righ
   }
   if ((rc = check_sgm_params(c, sgm))) return rc;
   if (images && (rc = check_flow_params(c, fprm, 1))) return rc;
+  if (odo && (rc = check_ego_params(c, eprm))) return rc;
   if (p.in_flight >= MOD_PIPELINE_DEPTH) return fail(c, MOD_ERR_CAPACITY, "MOD_PIPELINE_DEPTH frames are already in flight");
   if ((rc = ensure_pipe(c))) return rc;
   constexpr int R = MOD_PIPELINE_DEPTH + 1;
@@ -1284,15 +1378,23 @@ static int submit_stereo(ModContext *c, const uint8_t *left, const uint8_t *righ
   // the guards of construct() (:104,110,122,127,133), in its order; disparity_now exists by now
   if (!has_flow) return MOD_SKIP_NO_FLOW;
   if (!had_prev) return MOD_SKIP_NO_DISPARITY_PREV;
-  if (!transform) return MOD_SKIP_NO_TRANSFORM;
+  if (!transform && !odo) return MOD_SKIP_NO_TRANSFORM;
   if (images) {                     // estimateOpticalFlow (:279-290) on the GPU, straight into the frame's flow buffer
     if ((rc = mod_flow_compute_dev(c, 1, p.limg[previ], p.limg[nowi], fprm, p.flow[slot]))) return rc;
     HIP_TRY(c, hipEventRecord(p.ev_limg[previ], c->stream));
     HIP_TRY(c, hipEventRecord(p.ev_limg[nowi], c->stream));
   }
+  // the odometry stream: libviso2's process + getMotion (:214-256) on the GPU; its last kernel writes the frame's constants into b.fc,
+  // which the scene-flow launch below reads (fc_resident).  The slot's estimate was last copied out before its ticket was collected.
+  static const ModTransform kUnused = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};   // stands for the transform in HBM (never read)
+  if (odo) {
+    if (!p.ego) HIP_TRY(c, dalloc(&p.ego, MOD_PIPELINE_DEPTH));
+    if (!p.h_ego[slot]) HIP_TRY(c, hipHostMalloc((void **)&p.h_ego[slot], sizeof(ModContext::Pipe::EgoSlot), hipHostMallocDefault));
+    if ((rc = run_egomotion(c, 1, p.dnow[previ], p.dnow[nowi], p.flow[slot], eprm, &p.ego[slot].tf, &p.ego[slot].res, c->b.fc, dt))) return rc;
+  }
   ModFrameBatch in{};
   in.frames = 1; in.disparity_now = p.dnow[nowi]; in.disparity_prev = p.dnow[previ];
-  in.flow = p.flow[slot]; in.transforms = transform; in.dt = &dt;
+  in.flow = p.flow[slot]; in.transforms = odo ? &kUnused : transform; in.dt = &dt;
   ModSceneFlowPlanes pl;
   memset(&pl, 0, sizeof(pl));
   float *q = p.planes[slot];                 // z, vx, vy, vz for the cluster stage; no x, y planes (see scene_flow_staged)
@@ -1301,9 +1403,14 @@ static int submit_stereo(ModContext *c, const uint8_t *left, const uint8_t *righ
   ModClusterOut out{};
   out.labels = labels ? p.labels[slot] : nullptr; out.objects = p.objects[slot]; out.n_objects = p.nobj[slot]; out.n_clusters = p.nobj[slot] + 1;
   const bool cluster = labels || objects;     // neither asked for: the scene-flow stage alone (see mod_process_frame_host)
-  if ((rc = cluster ? mod_process_dev(c, &in, &pl, &out) : scene_flow_staged(c, &in, &pl))) return rc;
+  c->fc_resident = odo;
+  rc = cluster ? mod_process_dev(c, &in, &pl, &out) : scene_flow_staged(c, &in, &pl);
+  c->fc_resident = false;
+  if (rc) return rc;
   HIP_TRY(c, hipEventRecord(p.ev_done[slot], c->stream));
   HIP_TRY(c, hipStreamWaitEvent(p.d2h, p.ev_done[slot], 0));
+  if (odo) HIP_TRY(c, hipMemcpyAsync(p.h_ego[slot], &p.ego[slot], sizeof(ModContext::Pipe::EgoSlot), hipMemcpyDeviceToHost, p.d2h));
+  p.odo[slot] = odo; p.user_tf[slot] = transform_out; p.user_ego[slot] = ego_out;
   if (cluster) HIP_TRY(c, hipMemcpyAsync(p.h_n[slot], p.nobj[slot], sizeof(int32_t), hipMemcpyDeviceToHost, p.d2h));
   else *p.h_n[slot] = 0;
   if (labels) HIP_TRY(c, hipMemcpyAsync(labels, p.labels[slot], sizeof(int32_t) * N, hipMemcpyDeviceToHost, p.d2h));
@@ -1337,6 +1444,15 @@ int mod_submit_images_host(ModContext *c, const uint8_t *left, const uint8_t *ri
   return submit_stereo(c, left, right, sgm, nullptr, flow_prm, transform, dt, cloud_aos, labels, objects, max_objects, disparity, flow_out, ticket);
 }
 
+int mod_submit_odometry_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *sgm, const ModFlowParams *flow_prm,
+                             const ModEgoParams *ego_prm, double dt, void *cloud_aos, int32_t *labels, ModObject *objects, int32_t max_objects,
+                             float *disparity, float *flow_out, ModTransform *transform_out, ModEgoResult *ego_out, int32_t *ticket) {
+  if (c && !flow_prm) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow parameters");
+  if (c && !ego_prm) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ego-motion parameters");
+  return submit_stereo(c, left, right, sgm, nullptr, flow_prm, nullptr, dt, cloud_aos, labels, objects, max_objects, disparity, flow_out, ticket,
+                       ego_prm, transform_out, ego_out);
+}
+
 int mod_collect_frame_host(ModContext *c, int32_t ticket, int32_t *n_objects) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   ModContext::Pipe &p = c->pipe;
@@ -1346,6 +1462,15 @@ int mod_collect_frame_host(ModContext *c, int32_t ticket, int32_t *n_objects) {
   if (ticket != (int32_t)(oldest & 0x7fffffff)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "tickets are collected in submission order");
   const int slot = (int)(oldest % MOD_PIPELINE_DEPTH);
   HIP_TRY(c, hipEventSynchronize(p.ev_out[slot]));
+  if (p.odo[slot]) {
+    const ModContext::Pipe::EgoSlot &e = *p.h_ego[slot];
+    if (p.user_tf[slot]) *p.user_tf[slot] = e.tf;
+    if (p.user_ego[slot]) *p.user_ego[slot] = e.res;
+    if (e.res.status != MOD_EGO_OK) {   // visual odometry failed: the reference publishes nothing (scene_flow_constructor.cpp:251-255)
+      p.in_flight--;
+      return MOD_SKIP_NO_TRANSFORM;
+    }
+  }
   const int32_t n = *p.h_n[slot];
   if (n_objects) *n_objects = n;
   const int32_t ncopy = std::min(n, p.user_cap[slot]);
@@ -1398,11 +1523,14 @@ int mod_memcpy_d2h(ModContext *c, void *h, const void *d, uint64_t bytes) {
 
 #if defined(MOD_PHASE_COUNTERS) || defined(MOD_ABLATION) || defined(MOD_CHECKED)
 // diagnostic builds only (declared in mod_sf_debug.h; a product build does not export them)
-// copy an internal buffer to the host (0 member norms, 4 member pixels, 1 clusters, 2 counters)
+// copy an internal buffer to the host (0 member norms, 4 member pixels, 1 clusters, 2 counters; ego-motion: 5 correspondence counts,
+// 6 correspondences, 7 hypothesis inlier counts)
 int mod_debug_read(ModContext *c, int which, void *dst, unsigned long long bytes) {
   if (!c || !dst) return MOD_ERR_INVALID_ARGUMENT;
   const void *src = which == 0 ? (const void *)c->b.mbits : which == 4 ? (const void *)c->b.mpix : which == 1 ? (const void *)c->b.clusters
+                  : which == 5 ? (const void *)c->b.ego_ncorr : which == 6 ? (const void *)c->b.ego_corr : which == 7 ? (const void *)c->b.ego_hcnt
                   : (const void *)c->b.counters;
+  if (!src) return MOD_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return MOD_OK;

@@ -15,6 +15,8 @@ PLANES = ("x", "y", "z", "vx", "vy", "vz")
 OBJECT_DTYPE = np.dtype([("id", "<i4"), ("n_points", "<i4"), ("center", "<f8", 3), ("orientation", "<f8", 4),
                          ("velocity", "<f8", 3), ("bounding_box", "<f8", 3)])
 assert OBJECT_DTYPE.itemsize == capi.MOD_OBJECT_BYTES
+EGO_RESULT_DTYPE = np.dtype([("status", "<i4"), ("correspondences", "<i4"), ("inliers", "<i4"), ("iterations", "<i4"), ("rms_px", "<f8")])
+assert EGO_RESULT_DTYPE.itemsize == C.sizeof(capi.ModEgoResult)
 
 
 # Planes of one call are carved from ONE block with their bases 1 MiB further apart than their size: at 512 x 1280 x 720 a plane is a
@@ -182,6 +184,28 @@ class Context:
         if rc != 0:
             raise capi.ModError(rc, "mod_flow_compute_dev skipped")
         return out[0] if single and out.dim() == 4 else out
+
+    def estimate_egomotion(self, disp_prev: torch.Tensor, disp_now: torch.Tensor, flow: torch.Tensor,
+                           params: Optional[capi.ModEgoParams] = None):
+        """On-GPU stereo ego-motion (mod_egomotion_dev) of device float32 tensors (F,H,W), (F,H,W), (F,H,W,2) — or one frame without the
+        F axis.  Returns (transforms (F,7) float64 [t xyz, q xyzw] prev -> now, NaN where the estimate failed; results: structured
+        numpy array with status, correspondences, inliers, iterations, rms_px).  Synchronises the context's stream."""
+        single = disp_now.dim() == 2
+        dp, dn, fl = (disp_prev[None], disp_now[None], flow[None]) if single else (disp_prev, disp_now, flow)
+        F = dn.shape[0]
+        if dp.shape != dn.shape or dn.shape[1:] != (self.height, self.width) or fl.shape != (F, self.height, self.width, 2):
+            raise ValueError("disp_prev / disp_now must be (F, H, W) and flow (F, H, W, 2) at the camera size")
+        if any(t.dtype != torch.float32 or not t.is_contiguous() for t in (dp, dn, fl)):
+            raise ValueError("disparities and flow must be contiguous float32 tensors")
+        prm = params if params is not None else capi.ego_params()
+        tf = torch.empty((F, 7), dtype=torch.float64, device=dn.device)
+        res = torch.empty((F, C.sizeof(capi.ModEgoResult)), dtype=torch.uint8, device=dn.device)
+        rc = self._check(self.lib.mod_egomotion_dev(self.h, F, dp.data_ptr(), dn.data_ptr(), fl.data_ptr(), C.byref(prm), tf.data_ptr(),
+                                                    res.data_ptr()))
+        if rc != 0:
+            raise capi.ModError(rc, "mod_egomotion_dev skipped")
+        self.synchronize()
+        return tf.cpu().numpy(), np.frombuffer(res.cpu().numpy().tobytes(), dtype=EGO_RESULT_DTYPE).copy()
 
     def synchronize(self) -> None:
         self._check(self.lib.mod_synchronize(self.h))

@@ -557,3 +557,100 @@ def make_moving_images(W: int, H: int, seed: int = 0, D: int = 128, n_boxes: int
     out["flow"] = out["flow1"]
     out["boxes"] = boxes
     return out
+
+
+def make_ego_images(W: int, H: int, seed: int = 0, frames: int = 2, D: int = 128, n_static: int = 3, n_boxes: int = 3, shift=(8, 16)):
+    """Consecutive stereo pairs seen by a camera that translates along x by T/4 per pair (T = the camera's baseline): a textured static
+    background and `n_static` static textured slabs at other depths, plus `n_boxes` boxes that also move of their own accord by an
+    integer (sx, sy), |sx|, |sy| in `shift`, as in make_moving_images.  Every disparity is a multiple of 4, so every layer shifts by an
+    integer number of pixels per pair (d / 4 for the camera's motion, plus its own motion); the static layers lie at different depths
+    (with a single plane, yaw and lateral translation are close to degenerate).  Returns a dict:
+      left{k}, right{k}               uint8 [H][W], k = 0 .. frames-1
+      disparity{k}                    float32 [H][W] true left disparities
+      flow{k}                         float32 [H][W][2] true flow from pair k-1 to pair k at the NOW pixel (NaN where not visible before)
+      t, q                            float64 [frames-1][3], [frames-1][4] (x, y, z, w): the true camera motion pair k-1 -> k,
+                                      P_now = R P_prev + t (here R = I, t = (-T/4, 0, 0))
+      boxes                           list of (x0, y0, w, h) in pair 0, own (sx, sy), disparity of the moving boxes"""
+    lo, hi = int(shift[0]), int(shift[1])
+    if not 0 <= lo <= hi <= 24 or frames < 2:
+        raise ValueError("shifts must lie in 0..24 px, at least two pairs")
+    cam = make_camera(W, H)
+    rng = np.random.Generator(np.random.PCG64([0x5E90000 + seed]))
+    dmax = max(8, min(D - 1, W // 4)) // 4 * 4
+    ego = lambda d: -(d // 4)                       # image shift of a static layer of disparity d per pair
+    span = (hi + dmax // 4) * (frames - 1)          # how far a layer's texture travels over the sequence
+    pad = D + 8 + 2 * span
+
+    def texture():
+        t = rng.integers(0, 256, size=(H + 2 * span, W + pad)).astype(np.float32)
+        k = np.array([1, 2, 1], np.float32) / 4
+        t = np.apply_along_axis(lambda r: np.convolve(r, k, mode="same"), 1, t)
+        t = np.apply_along_axis(lambda c: np.convolve(c, k, mode="same"), 0, t)
+        return np.clip(t, 0, 255).astype(np.uint8)
+
+    d_bg = 4 * int(rng.integers(1, 3))
+    layers = [(d_bg, None, (ego(d_bg), 0), texture())]
+    sd = rng.permutation(np.arange(d_bg // 4 + 1, dmax // 4 + 1))[:n_static] * 4
+    for d in sd:                                    # static slabs: wide horizontal bands at their own depth
+        bw, bh = int(rng.integers(W // 3, W // 2)), int(rng.integers(H // 8, H // 5))
+        x0, y0 = int(rng.integers(0, W - bw)), int(rng.integers(0, H - bh))
+        layers.append((int(d), (x0, y0, bw, bh), (ego(int(d)), 0), texture()))
+    cols = max(1, int(np.ceil(np.sqrt(n_boxes * W / H))))
+    rows = max(1, int(np.ceil(n_boxes / cols)))
+    cw, ch = W // cols, H // rows
+    boxes = []
+    for cell in rng.permutation(rows * cols)[:n_boxes]:
+        r, cl = divmod(int(cell), cols)
+        d = 4 * int(rng.integers(dmax // 16 + 1, dmax // 8 + 1))
+        m = hi * (frames - 1) + 4
+        bw = int(rng.integers(max(8, cw // 4), max(9, min(cw // 2, cw - 2 * m))))
+        bh = int(rng.integers(max(8, ch // 4), max(9, min(ch // 2, ch - 2 * m))))
+        x0 = cl * cw + m + int(rng.integers(0, max(1, cw - bw - 2 * m)))
+        y0 = r * ch + m + int(rng.integers(0, max(1, ch - bh - 2 * m)))
+        sx = int(rng.integers(lo, hi + 1)) * (1 if rng.integers(0, 2) else -1)
+        sy = int(rng.integers(lo, hi + 1)) * (1 if rng.integers(0, 2) else -1)
+        boxes.append(((x0, y0, bw, bh), (sx, sy), d))
+        layers.append((d, (x0, y0, bw, bh), (sx + ego(d), sy), texture()))
+    layers.sort(key=lambda l: l[0])                                                 # far to near
+    xs = np.arange(W)
+    out, owner = {}, []
+    for k in range(frames):
+        left = np.zeros((H, W), np.uint8)
+        right = np.zeros((H, W), np.uint8)
+        truth = np.zeros((H, W), np.float32)
+        own = np.full((H, W), -1, np.int32)
+        for j, (d, rect, (sx, sy), tex) in enumerate(layers):
+            t = tex[span - sy * k:span - sy * k + H, span - sx * k:span - sx * k + W + D + 8]     # the texture moves with its layer
+            ml = np.ones((H, W), bool)
+            if rect is not None:
+                x0, y0, bw, bh = rect
+                ml = np.zeros((H, W), bool)
+                ml[max(0, y0 + sy * k):max(0, y0 + sy * k + bh), max(0, x0 + sx * k):max(0, x0 + sx * k + bw)] = True
+            mr = np.zeros((H, W), bool)
+            mr[:, :W - d] = ml[:, d:]
+            if rect is None:
+                mr[:] = True
+            left = np.where(ml, t[:, xs], left)
+            right = np.where(mr, t[:, xs + d], right)
+            truth = np.where(ml, np.float32(d), truth)
+            own = np.where(ml, j, own)
+        noise = rng.integers(-2, 3, size=(2, H, W))
+        out[f"left{k}"] = np.clip(left.astype(np.int32) + noise[0], 0, 255).astype(np.uint8)
+        out[f"right{k}"] = np.clip(right.astype(np.int32) + noise[1], 0, 255).astype(np.uint8)
+        out[f"disparity{k}"] = truth
+        owner.append(own)
+    ys, xg = np.mgrid[0:H, 0:W]
+    for k in range(1, frames):
+        flow = np.full((H, W, 2), np.nan, np.float32)
+        for j, (d, rect, (sx, sy), tex) in enumerate(layers):
+            px, py = xg - sx, ys - sy
+            inside = (px >= 0) & (px < W) & (py >= 0) & (py < H)
+            seen = inside & (owner[k] == j)
+            seen[seen] = owner[k - 1][py[seen], px[seen]] == j
+            flow[seen] = (np.float32(sx), np.float32(sy))
+        out[f"flow{k}"] = flow
+    step = float(cam.disp_T) / 4.0
+    out["t"] = np.tile(np.array([[-step, 0.0, 0.0]]), (frames - 1, 1))
+    out["q"] = np.tile(np.array([[0.0, 0.0, 0.0, 1.0]]), (frames - 1, 1))
+    out["boxes"] = boxes
+    return out

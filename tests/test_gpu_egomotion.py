@@ -1,0 +1,322 @@
+"""GPU: the on-GPU stereo ego-motion estimator (csrc/egomotion.hip) — bit for bit against the numpy restatement
+(tests/models/ego_model.py) on the correspondence list, every hypothesis's inlier count and the chosen hypothesis; batches against
+single frames, repeats and the host form; accuracy on synth.make_frame; the scene flow and clusters it feeds; the odometry stream
+(mod_submit_odometry_host) against the images stream fed its transforms; failure and argument codes."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, os.path.join(HERE, "models"))
+sys.path.insert(0, HERE)
+import ego_model as em  # noqa: E402
+
+CHECKED = os.path.join(ROOT, "moving_object_detector_amd", "libmod_sf_checked.so")
+
+
+def _frames(W, H, F, seed):
+    from moving_object_detector_amd import synth
+    cams, frs = zip(*[synth.make_frame(W, H, seed=seed + f) for f in range(F)])
+    return cams[0], list(frs)
+
+
+def _model_prm(p):
+    return em.EgoParams(p.stride, p.hypotheses, p.iterations, p.min_inliers, p.inlier_threshold, p.min_disparity, p.seed)
+
+
+def _ctx(W, H, F, cam):
+    from moving_object_detector_amd import synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F)
+    ctx.set_camera(cam)
+    ctx.set_params(synth.Params())
+    return ctx
+
+
+def _dev(ctx, frs):
+    d = ctx.device if ctx is not None else torch.device("cuda", 0)
+    return (torch.from_numpy(np.stack([f.disparity_prev for f in frs])).to(d), torch.from_numpy(np.stack([f.disparity_now for f in frs])).to(d),
+            torch.from_numpy(np.stack([f.flow for f in frs])).to(d))
+
+
+class _Checked:
+    """A context of the diagnostic build, which can read the estimator's scratch (mod_debug_read 5, 6, 7)."""
+
+    def __init__(self, W, H, F, cam):
+        from moving_object_detector_amd import capi, synth
+        import moving_object_detector_amd.pipeline  # noqa: F401  (torch first: one HIP runtime)
+        L = C.CDLL(CHECKED)
+        vp = C.c_void_p
+        L.mod_create.argtypes = [C.POINTER(capi.ModConfig), C.POINTER(vp)]
+        L.mod_destroy.argtypes = [vp]
+        L.mod_destroy.restype = None
+        L.mod_set_camera.argtypes = [vp, C.POINTER(capi.ModCamera)]
+        L.mod_set_params.argtypes = [vp, C.POINTER(capi.ModParams)]
+        L.mod_egomotion_dev.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.ModEgoParams), vp, vp]
+        L.mod_synchronize.argtypes = [vp]
+        L.mod_debug_read.argtypes = [vp, C.c_int, vp, C.c_ulonglong]
+        self.L, self.h = L, C.c_void_p()
+        assert L.mod_create(C.byref(capi.ModConfig(0, W, H, F, 0, 0, None)), C.byref(self.h)) == 0
+        assert L.mod_set_camera(self.h, C.byref(capi.camera_struct(cam))) == 0
+        assert L.mod_set_params(self.h, C.byref(capi.params_struct(synth.Params()))) == 0
+        self.W, self.H, self.F = W, H, F
+
+    def run(self, dp, dn, fl, prm):
+        F = dn.shape[0]
+        tf = torch.empty((F, 7), dtype=torch.float64, device=dn.device)
+        res = torch.empty((F, 24), dtype=torch.uint8, device=dn.device)
+        assert self.L.mod_egomotion_dev(self.h, F, dp.data_ptr(), dn.data_ptr(), fl.data_ptr(), C.byref(prm), tf.data_ptr(), res.data_ptr()) == 0
+        assert self.L.mod_synchronize(self.h) == 0
+        cap = -(-self.W // prm.stride) * -(-self.H // prm.stride)
+        n = np.zeros(self.F, np.int32)
+        corr = np.zeros((self.F, 9, cap), np.float64)
+        cnt = np.zeros(F * prm.hypotheses, np.int32)          # [frames][hypotheses] of this call
+        for which, a in ((5, n), (6, corr), (7, cnt)):
+            assert self.L.mod_debug_read(self.h, which, a.ctypes.data, a.nbytes) == 0
+        cnt = cnt.reshape(F, prm.hypotheses)
+        from moving_object_detector_amd.pipeline import EGO_RESULT_DTYPE
+        return tf.cpu().numpy(), np.frombuffer(res.cpu().numpy().tobytes(), dtype=EGO_RESULT_DTYPE), n, corr, cnt
+
+    def close(self):
+        self.L.mod_destroy(self.h)
+
+
+@pytest.mark.parametrize("W,H,F,strides,hyps", [(320, 240, 1, (8, 4, 2), (1, 64, 256)), (320, 240, 3, (8, 4, 2), (256, 1, 64)),
+                                                 (1280, 720, 1, (8, 4), (64, 256)), (1280, 720, 3, (8, 4, 2), (256, 1, 64))])
+def test_gpu_matches_the_model_bit_for_bit(W, H, F, strides, hyps):
+    from moving_object_detector_amd import capi
+    if not os.path.exists(CHECKED):
+        pytest.fail("the diagnostic build libmod_sf_checked.so is missing (build() makes it)")
+    cam, frs = _frames(W, H, F, seed=11 * F + W)
+    ck = _Checked(W, H, F, cam)
+    dp, dn, fl = _dev(None, frs)
+    for s in strides:                                   # descending: the scratch grows on the way
+        for hn in hyps:
+            p = capi.ego_params(stride=s, hypotheses=hn, seed=7 * s + hn)
+            tf, res, n, corr, cnt = ck.run(dp, dn, fl, p)
+            for f in range(F):
+                m = em.estimate(cam, frs[f].disparity_prev, frs[f].disparity_now, frs[f].flow, _model_prm(p))
+                k = len(m["corr"]["pix"])
+                assert n[f] == k == res["correspondences"][f], (s, hn, f)
+                got = corr[f, :, :k]
+                want = np.concatenate([m["corr"]["P"].T, m["corr"]["Q"].T, m["corr"]["O"].T])
+                assert np.array_equal(got.view(np.uint64), want.view(np.uint64)), (s, hn, f)
+                assert np.array_equal(cnt[f, :hn], m["counts"]), (s, hn, f)
+                best = int(np.argmax(cnt[f, :hn]))
+                assert best == m["best"] and cnt[f, best] == m["counts"][m["best"]]
+                assert res["status"][f] == m["status"] and res["inliers"][f] == m["inliers"] and res["iterations"][f] == m["iterations"], (s, hn, f)
+                if m["status"] == em.OK:
+                    assert np.abs(tf[f] - m["transform"]).max() <= 1e-6, (s, hn, f, tf[f], m["transform"])
+                else:
+                    assert np.isnan(tf[f]).all()
+    ck.close()
+
+
+def test_batch_equals_single_frames_repeats_and_the_host_form():
+    from moving_object_detector_amd import capi
+    W, H, F = 640, 480, 3
+    cam, frs = _frames(W, H, F, seed=40)
+    ctx = _ctx(W, H, F, cam)
+    dp, dn, fl = _dev(ctx, frs)
+    p = capi.ego_params(seed=5)
+    tf, res = ctx.estimate_egomotion(dp, dn, fl, p)
+    tf2, res2 = ctx.estimate_egomotion(dp, dn, fl, p)
+    assert tf.tobytes() == tf2.tobytes() and res.tobytes() == res2.tobytes()
+    for f in range(F):
+        t1, r1 = ctx.estimate_egomotion(dp[f], dn[f], fl[f], p)
+        assert t1.tobytes() == tf[f:f + 1].tobytes() and r1.tobytes() == res[f:f + 1].tobytes(), f
+        ht, hr = capi.ModTransform(), capi.ModEgoResult()
+        assert ctx.lib.mod_egomotion_host(ctx.h, frs[f].disparity_prev.ctypes.data, frs[f].disparity_now.ctypes.data, frs[f].flow.ctypes.data,
+                                          C.byref(p), C.byref(ht), C.byref(hr)) == 0
+        assert bytes(ht) == tf[f].tobytes() and bytes(hr) == res[f:f + 1].tobytes(), f
+    ctx.close()
+
+
+def test_accuracy_on_make_frame_720p():
+    W, H = 1280, 720
+    cam, frs = _frames(W, H, 8, seed=0)
+    ctx = _ctx(W, H, 8, cam)
+    tf, res = ctx.estimate_egomotion(*_dev(ctx, frs))
+    for f, fr in enumerate(frs):
+        assert res["status"][f] == 0, res[f]
+        assert np.linalg.norm(tf[f, :3] - fr.translation) <= 0.01, (f, tf[f], fr.translation)
+        assert em.rotation_error_deg(tf[f, 3:], fr.quaternion) <= 0.02, (f, tf[f], fr.quaternion)
+    ctx.close()
+
+
+def test_downstream_objects_with_the_estimated_transform():
+    W, H, F = 1280, 720, 4
+    cam, frs = _frames(W, H, F, seed=20)
+    ctx = _ctx(W, H, F, cam)
+    dp, dn, fl = _dev(ctx, frs)
+    tf, res = ctx.estimate_egomotion(dp, dn, fl)
+    assert (res["status"] == 0).all()
+    ws = ctx.workspace(F)
+    out = {}
+    for name, ts, qs in (("true", [f.translation for f in frs], [f.quaternion for f in frs]), ("est", tf[:, :3], tf[:, 3:])):
+        b = ctx.make_batch(dn, dp, fl, ts, qs, [f.dt for f in frs])
+        assert ctx.process(b, ws) == 0
+        ctx.synchronize()
+        out[name] = (ws["n_objects"].cpu().numpy().copy(), ws["mask"].cpu().numpy().copy())
+    assert np.array_equal(out["true"][0], out["est"][0]), (out["true"][0], out["est"][0])
+    bits = lambda m: np.unpackbits(m.view(np.uint8), bitorder="little")
+    diff = np.count_nonzero(bits(out["true"][1]) != bits(out["est"][1]))
+    assert diff <= 0.005 * F * W * H, diff
+    ctx.close()
+
+
+def _odo_scene(W, H, FR, seed=2):
+    from moving_object_detector_amd import synth
+    m = synth.make_ego_images(W, H, seed=seed, frames=FR)
+    cam = synth.make_camera(W, H)
+    cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
+    return m, cam, synth.Params()
+
+
+def test_odometry_stream_matches_the_images_stream_fed_its_transforms():
+    from moving_object_detector_amd import capi
+    from moving_object_detector_amd.pipeline import OBJECT_DTYPE, Context
+    W, H, FR, CAP, DT = 1280, 720, 6, 64, 1.0 / 15.0
+    m, cam, prm = _odo_scene(W, H, FR)
+    L = [np.ascontiguousarray(m[f"left{f}"]) for f in range(FR)]
+    R = [np.ascontiguousarray(m[f"right{f}"]) for f in range(FR)]
+    sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
+    ctx = Context(W, H, max_frames=1)
+    ctx.set_camera(cam)
+    ctx.set_params(prm)
+    N = W * H
+    k = {n: np.full((FR,) + s, -7, t) for n, s, t in (("disp", (H, W), np.float32), ("flow", (H, W, 2), np.float32), ("lab", (H, W), np.int32),
+                                                      ("aos", (N * 8,), np.float32))}
+    objs = [(capi.ModObject * CAP)() for _ in range(FR)]
+    tfs = [capi.ModTransform() for _ in range(FR)]
+    egos = [capi.ModEgoResult() for _ in range(FR)]
+    t, n = C.c_int32(-1), C.c_int32(-1)
+    sub = lambda f: ctx.lib.mod_submit_odometry_host(ctx.h, L[f].ctypes.data, R[f].ctypes.data, C.byref(sp), C.byref(fp), C.byref(ep), DT,
+                                                     k["aos"][f].ctypes.data, k["lab"][f].ctypes.data, objs[f], CAP, k["disp"][f].ctypes.data,
+                                                     k["flow"][f].ctypes.data, C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
+    assert sub(0) == capi.MOD_SKIP_NO_FLOW and t.value == -1
+    pending, counts = [], {}
+    for f in range(1, FR):
+        if len(pending) == 3:
+            tk, g = pending.pop(0)
+            assert ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(n)) == 0
+            counts[g] = n.value
+        assert sub(f) == 0, ctx.lib.mod_last_error(ctx.h)
+        pending.append((t.value, f))
+    for tk, g in pending:
+        assert ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(n)) == 0
+        counts[g] = n.value
+    # the images stream fed the estimated transforms gives the same bits
+    ref = {n: np.full_like(v, -9) for n, v in k.items()}
+    robjs = [(capi.ModObject * CAP)() for _ in range(FR)]
+    assert ctx.lib.mod_forget_previous(ctx.h) == 0
+    for f in range(FR):
+        rc = ctx.lib.mod_submit_images_host(ctx.h, L[f].ctypes.data, R[f].ctypes.data, C.byref(sp), C.byref(fp), C.byref(tfs[f]), DT,
+                                            ref["aos"][f].ctypes.data, ref["lab"][f].ctypes.data, robjs[f], CAP, ref["disp"][f].ctypes.data,
+                                            ref["flow"][f].ctypes.data, C.byref(t))
+        if f == 0:
+            assert rc == capi.MOD_SKIP_NO_FLOW
+            continue
+        assert rc == 0
+        assert ctx.lib.mod_collect_frame_host(ctx.h, t.value, C.byref(n)) == 0
+        assert n.value == counts[f], f
+    for f in range(1, FR):
+        for name in k:
+            assert k[name][f].tobytes() == ref[name][f].tobytes(), (name, f)
+        assert bytes(objs[f])[:112 * counts[f]] == bytes(robjs[f])[:112 * counts[f]], f
+        # accuracy: the camera moved by (-T/4, 0, 0) with no rotation
+        assert egos[f].status == 0, f
+        assert np.linalg.norm(np.array(tfs[f].t) - m["t"][f - 1]) <= 0.01, (f, list(tfs[f].t))
+        assert em.rotation_error_deg(list(tfs[f].q), m["q"][f - 1]) <= 0.02, (f, list(tfs[f].q))
+        # every moving box above cluster_size is found: an object's centre projects into it (box at frame f: its own motion plus the
+        # camera's d / 4 px per pair)
+        got = np.frombuffer(bytes(objs[f]), dtype=OBJECT_DTYPE)[: counts[f]]
+        big = [(x0 + (sx - d // 4) * f, y0 + sy * f, bw, bh) for (x0, y0, bw, bh), (sx, sy), d in m["boxes"] if bw * bh > prm.cluster_size]
+        hit = set()
+        for o in got:
+            X, Y, Z = o["center"]
+            u, v = cam.fx * X / Z + cam.cx, cam.fy * Y / Z + cam.cy
+            hit |= {i for i, (x0, y0, bw, bh) in enumerate(big) if x0 <= u < x0 + bw and y0 <= v < y0 + bh}
+        assert hit == set(range(len(big))) and counts[f] >= len(big), (f, counts[f], len(big), hit)
+    ctx.close()
+
+
+def test_odometry_stream_failed_estimate_and_recovery():
+    from moving_object_detector_amd import capi
+    from moving_object_detector_amd.pipeline import Context
+    W, H, FR, DT = 640, 480, 6, 1.0 / 15.0
+    m, cam, prm = _odo_scene(W, H, FR, seed=4)
+    L = [np.ascontiguousarray(m[f"left{f}"]) for f in range(FR)]
+    R = [np.ascontiguousarray(m[f"right{f}"]) for f in range(FR)]
+    R[2] = np.zeros_like(R[2])                          # frame 2: nothing to match
+    sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
+    ctx = Context(W, H, max_frames=1)
+    ctx.set_camera(cam)
+    ctx.set_params(prm)
+    lab = np.full((FR, H, W), -7, np.int32)
+    objs = [(capi.ModObject * 64)() for _ in range(FR)]
+    tfs = [capi.ModTransform() for _ in range(FR)]
+    egos = [capi.ModEgoResult() for _ in range(FR)]
+    t, n = C.c_int32(-1), C.c_int32(-1)
+    codes = []
+    for f in range(FR):
+        rc = ctx.lib.mod_submit_odometry_host(ctx.h, L[f].ctypes.data, R[f].ctypes.data, C.byref(sp), C.byref(fp), C.byref(ep), DT, None,
+                                              lab[f].ctypes.data, objs[f], 64, None, None, C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
+        if f == 0:
+            assert rc == capi.MOD_SKIP_NO_FLOW
+            continue
+        assert rc == 0
+        n.value = -1
+        codes.append((f, ctx.lib.mod_collect_frame_host(ctx.h, t.value, C.byref(n)), n.value))
+    assert codes[1] == (2, capi.MOD_SKIP_NO_TRANSFORM, 0), codes
+    assert egos[2].status != 0 and np.isnan(list(tfs[2].t) + list(tfs[2].q)).all()
+    assert (lab[2] == -1).all()
+    for f, rc, cnt in codes[-2:]:                       # the stream recovers
+        assert rc == 0 and cnt > 0 and egos[f].status == 0, codes
+    ctx.close()
+
+
+def test_argument_and_capacity_codes():
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    W, H = 320, 240
+    cam, frs = _frames(W, H, 2, seed=1)
+    ctx = Context(W, H, max_frames=1)
+    dp, dn, fl = _dev(ctx, frs)
+    tf = torch.empty((2, 7), dtype=torch.float64, device=ctx.device)
+    call = lambda F, p, a=dp, b=dn, c=fl, o=tf: ctx.lib.mod_egomotion_dev(ctx.h, F, a.data_ptr() if a is not None else None,
+                                                                          b.data_ptr() if b is not None else None, c.data_ptr() if c is not None else None,
+                                                                          C.byref(p) if p is not None else None, o.data_ptr() if o is not None else None, None)
+    assert call(1, capi.ego_params()) == capi.MOD_ERR_NOT_CONFIGURED
+    ctx.set_camera(cam)
+    ctx.set_params(synth.Params())
+    assert call(1, capi.ego_params()) == 0
+    assert call(2, capi.ego_params()) == capi.MOD_ERR_CAPACITY
+    assert call(1, None) == capi.MOD_ERR_INVALID_ARGUMENT
+    assert call(1, capi.ego_params(), o=None) == capi.MOD_ERR_INVALID_ARGUMENT
+    for bad in (dict(stride=0), dict(stride=65), dict(hypotheses=0), dict(hypotheses=4097), dict(iterations=-1), dict(min_inliers=-1),
+                dict(inlier_threshold=0.0), dict(inlier_threshold=float("nan")), dict(min_disparity=float("inf"))):
+        assert call(1, capi.ego_params(**bad)) == capi.MOD_ERR_INVALID_ARGUMENT, bad
+    assert call(1, capi.ego_params(), c=None) == capi.MOD_SKIP_NO_FLOW
+    assert call(1, capi.ego_params(), a=None) == capi.MOD_SKIP_NO_DISPARITY_PREV
+    assert call(1, capi.ego_params(), b=None) == capi.MOD_SKIP_NO_DISPARITY_NOW
+    ht, hr = capi.ModTransform(), capi.ModEgoResult()
+    nan = np.full_like(frs[0].disparity_prev, np.nan)
+    assert ctx.lib.mod_egomotion_host(ctx.h, nan.ctypes.data, frs[0].disparity_now.ctypes.data, frs[0].flow.ctypes.data, C.byref(capi.ego_params()),
+                                      C.byref(ht), C.byref(hr)) == capi.MOD_SKIP_NO_TRANSFORM
+    assert hr.status == capi.MOD_EGO_FEW_POINTS and np.isnan(list(ht.t)).all()
+    l8 = np.zeros((H, W), np.uint8)
+    tk = C.c_int32()
+    sub = lambda sp, fp, ep: ctx.lib.mod_submit_odometry_host(ctx.h, l8.ctypes.data, l8.ctypes.data, sp, fp, ep, 0.1, None, None, None, 0, None, None,
+                                                              None, None, C.byref(tk))
+    sp, fp = C.byref(capi.ModSgmParams(64, 6, 96, 8, 1, 1)), C.byref(capi.flow_params(levels=3))
+    assert sub(sp, fp, None) == capi.MOD_ERR_INVALID_ARGUMENT
+    assert sub(sp, None, C.byref(capi.ego_params())) == capi.MOD_ERR_INVALID_ARGUMENT
+    assert sub(sp, fp, C.byref(capi.ego_params(stride=0))) == capi.MOD_ERR_INVALID_ARGUMENT
+    ctx.close()
