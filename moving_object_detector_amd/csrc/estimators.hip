@@ -1,0 +1,296 @@
+// estimators.hip — the C ABI's on-GPU estimators (SGM disparity, census optical flow, stereo ego-motion): their *_dev entry points
+// and scratch.  Host-side only; the kernels live in sgm.hip, flow.hip and egomotion.hip.
+#include "mod_context.h"
+
+#include <algorithm>
+#include <cmath>
+
+// ---- on-GPU disparity (sgm.hip) --------------------------------------------------------------------------------------------
+int check_sgm_params(ModContext *c, const ModSgmParams *p) {
+  if (!p) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null SGM parameters");
+  if (p->disparities < 1 || p->disparities > MOD_SGM_MAX_DISPARITIES) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparities must be in 1..128");
+  if (p->p1 < 0 || p->p2 < p->p1 || 31 + p->p2 > 255) return fail(c, MOD_ERR_INVALID_ARGUMENT, "need 0 <= P1 <= P2 <= 224 (path costs are uint8)");
+  if (p->paths != 4 && p->paths != 8) return fail(c, MOD_ERR_INVALID_ARGUMENT, "paths must be 4 or 8");
+  if (c->dc.W < 2) return fail(c, MOD_ERR_INVALID_ARGUMENT, "the disparity estimator needs images at least 2 pixels wide");
+  if ((size_t)c->dc.W * 8 + 4 > 64 * 1024) return fail(c, MOD_ERR_CAPACITY, "image row does not fit the census row buffer in LDS");
+  return MOD_OK;
+}
+
+// scratch of the complete estimator for a GROUP of frames (one wave walks a path line, so a single frame cannot fill the GPU; the
+// frames of a group run side by side): per frame two census planes, one uint8 cost volume PER PATH (written once, never read
+// back by the path kernels: a running sum would put its load latency into every step of a path), four disparity maps.  Census
+// planes and volumes exist twice: consecutive groups overlap (mod_sgm_compute_dev).
+constexpr int kSgmPaths = 8;
+constexpr int kSgmGroup = 8;                             // frames per group (4 .. 16 measured in round 3: 8 is the knee)
+constexpr size_t kSgmVolumeBudget = (size_t)24 << 30;    // bytes of cost volumes a context may hold
+
+static int ensure_sgm_scratch(ModContext *c, int D, int frames, int *group) {
+  Buffers &b = c->b;
+  const size_t N = c->maxN;
+  const int even = (frames + kSgmGroup - 1) / kSgmGroup;          // groups of equal size: 11 frames go as 6 + 5, not 8 + 3
+  int g = (frames + even - 1) / even;
+  while (g > 1 && 2 * (size_t)g * N * D * kSgmPaths > kSgmVolumeBudget) g--;
+  *group = g;
+  if (!b.sgm_fork[0]) {
+    for (int k = 0; k < 2; k++) {
+      HIP_TRY(c, hipEventCreateWithFlags(b.sgm_fork[k].put(), hipEventDisableTiming));
+      for (int i = 0; i < 8; i++) HIP_TRY(c, hipEventCreateWithFlags(b.sgm_join[k][i].put(), hipEventDisableTiming));
+    }
+    // (a CU-masked path stream that kept one CU in 8 / 4 / 3 free for the winner-take-all of the group before was measured in
+    // round 3 and changed nothing: plain non-blocking side streams)
+    for (int i = 0; i < 8; i++) HIP_TRY(c, hipStreamCreateWithFlags(b.sgm_side[i].put(), hipStreamNonBlocking));
+  }
+  if (b.sgm_S && b.sgm_D >= D && b.sgm_G >= g) return MOD_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // grow-only in BOTH dimensions: calls that alternate between (few disparities, large group) and (many, small) settle on the
+  // maxima after one reallocation each instead of freeing and allocating gigabytes on every call
+  const int D2 = std::max(D, b.sgm_D), g2 = std::max(g, b.sgm_G);
+  b.sgm_S.reset(); b.sgm_census.reset(); b.sgm_maps.reset(); b.sgm_D = 0; b.sgm_G = 0;
+  // two sets (see mod_sgm_compute_dev) behind 128 words of lead: the D == 128 path kernels read up to 127 words to the left of a
+  // right census plane unconditionally (discarded: disparities that do not exist) — inside the allocation even for tiny images
+  HIP_TRY(c, dalloc(b.sgm_census, 2 * 2 * N * g2 + 128));
+  HIP_TRY(c, dalloc(b.sgm_maps, 4 * N * g2));
+  HIP_TRY(c, dalloc(b.sgm_S, 2 * N * (size_t)D2 * g2 * kSgmPaths));
+  b.sgm_D = D2; b.sgm_G = g2;
+  return MOD_OK;
+}
+
+// ---- on-GPU optical flow (flow.hip) ---------------------------------------------------------------------------------------
+constexpr int kFlowMaxLevels = 6;
+constexpr int kFlowMinCoarse = 16;      // px on either side of the coarsest level
+
+// elements before level l in the per-level scratch regions: level k holds [2][maxF][(max_width >> k) * (max_height >> k)]
+static size_t flow_level_offset(const ModContext *c, int l) {
+  size_t off = 0;
+  for (int k = 0; k < l; k++) off += (size_t)2 * c->cfg.max_frames * (size_t)(c->cfg.max_width >> k) * (size_t)(c->cfg.max_height >> k);
+  return off;
+}
+
+int check_flow_params(ModContext *c, const ModFlowParams *p, int frames) {
+  if (!p) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow parameters");
+  if (p->levels < 1 || p->levels > kFlowMaxLevels) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow levels must be in 1..6");
+  if (p->radius < 1 || p->radius > 8) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow radius must be in 1..8");
+  if (p->window != 3 && p->window != 5 && p->window != 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow window must be 3, 5 or 7");
+  if (p->subpixel != 0 && p->subpixel != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow subpixel must be 0 or 1");
+  if ((c->dc.W >> (p->levels - 1)) < kFlowMinCoarse || (c->dc.H >> (p->levels - 1)) < kFlowMinCoarse)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "too many flow levels: the coarsest would be smaller than 16 px");
+  if (2 * frames > 65535) return fail(c, MOD_ERR_CAPACITY, "flow takes at most 32767 frames per call");   // both images ride in grid.z
+  return MOD_OK;
+}
+
+static int ensure_flow_scratch(ModContext *c) {
+  Buffers &b = c->b;
+  if (b.flow_sub) return MOD_OK;                     // the last buffer of the set exists: all do
+  const size_t N = c->maxN, F = (size_t)c->cfg.max_frames;
+  HIP_TRY(c, dalloc(b.flow_img, flow_level_offset(c, kFlowMaxLevels) - flow_level_offset(c, 1)));
+  HIP_TRY(c, dalloc(b.flow_census, flow_level_offset(c, kFlowMaxLevels)));
+  HIP_TRY(c, dalloc(b.flow_int, 2 * 2 * F * N));
+  HIP_TRY(c, dalloc(b.flow_sub, F * N));
+  return MOD_OK;
+}
+
+// ---- on-GPU ego-motion (egomotion.hip) -------------------------------------------------------------------------------------
+int check_ego_params(ModContext *c, const ModEgoParams *p) {
+  if (!p) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ego-motion parameters");
+  if (p->stride < 1 || p->stride > 64) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion stride must be in 1..64");
+  if (p->hypotheses < 1 || p->hypotheses > MOD_EGO_MAX_HYPOTHESES)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion hypotheses must be in 1..4096");
+  if (p->iterations < 0 || p->iterations > 100) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion iterations must be in 0..100");
+  if (p->min_inliers < 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion min_inliers must be >= 0");
+  if (!(p->inlier_threshold > 0.0f) || !std::isfinite(p->inlier_threshold))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion inlier_threshold must be a positive number");
+  if (!std::isfinite(p->min_disparity)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ego-motion min_disparity must be finite");
+  return MOD_OK;
+}
+
+// Correspondence scratch for `stride` (max_width x max_height x max_frames / stride^2); grows, after a sync, when a smaller stride comes.
+static int ensure_ego_scratch(ModContext *c, int stride) {
+  Buffers &b = c->b;
+  const size_t F = (size_t)c->cfg.max_frames;
+  const int gw = (c->cfg.max_width + stride - 1) / stride, gh = (c->cfg.max_height + stride - 1) / stride;
+  const size_t cap = (size_t)gw * gh;
+  if (cap > b.ego_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    b.ego_corr.reset(); b.ego_flag.reset(); b.ego_blkcnt.reset(); b.ego_cap = 0;
+    HIP_TRY(c, dalloc(b.ego_corr, F * 9 * cap));
+    HIP_TRY(c, dalloc(b.ego_flag, F * cap));
+    HIP_TRY(c, dalloc(b.ego_blkcnt, F * (size_t)ego_grid_blocks(gw, gh)));
+    b.ego_cap = cap;
+  }
+  if (!b.ego_res) {
+    HIP_TRY(c, dalloc(b.ego_ncorr, F));
+    HIP_TRY(c, dalloc(b.ego_hyp, F * MOD_EGO_MAX_HYPOTHESES * 12));
+    HIP_TRY(c, dalloc(b.ego_hcnt, F * MOD_EGO_MAX_HYPOTHESES));
+    HIP_TRY(c, dalloc(b.ego_tf, F));
+    HIP_TRY(c, dalloc(b.ego_res, F));
+  }
+  return MOD_OK;
+}
+
+int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p,
+                  ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt) {
+  int rc = ensure_ego_scratch(c, p->stride);
+  if (rc) return rc;
+  Buffers &b = c->b;
+  EgoArgs a;
+  a.W = c->dc.W; a.H = c->dc.H; a.frames = frames; a.stride = p->stride;
+  a.gw = (a.W + p->stride - 1) / p->stride; a.gh = (a.H + p->stride - 1) / p->stride;
+  a.cap = (int)b.ego_cap;
+  a.hyps = p->hypotheses; a.iterations = p->iterations; a.min_inliers = p->min_inliers; a.seed = p->seed;
+  a.dlo = std::max(c->cam.min_disparity, p->min_disparity); a.dhi = c->cam.max_disparity;
+  a.th = (double)p->inlier_threshold;
+  a.fx = c->cam.fx; a.fy = c->cam.fy; a.cx = c->cam.cx; a.cy = c->cam.cy; a.Tx = c->cam.Tx; a.Ty = c->cam.Ty; a.fT = (double)c->dc.fT;
+  a.dprev = dprev; a.dnow = dnow; a.flow = flow;
+  a.corr = b.ego_corr; a.blkcnt = b.ego_blkcnt; a.ncorr = b.ego_ncorr; a.hyp = b.ego_hyp; a.hcnt = b.ego_hcnt; a.flag = b.ego_flag;
+  a.tf = reinterpret_cast<double *>(tf ? tf : b.ego_tf.get()); a.res = res ? res : b.ego_res.get(); a.fc = fc; a.dt = dt;
+  static_assert(sizeof(ModTransform) == 7 * sizeof(double), "ModTransform is 7 doubles");
+  launch_egomotion(a, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+extern "C" {
+
+// ---- on-GPU disparity, first stages ---------------------------------------------------------------
+int mod_sgm_census_dev(ModContext *c, int32_t frames, const uint8_t *image, uint32_t *census) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!image || !census) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null image / census plane");
+  launch_sgm_census(c->dc.W, c->dc.H, frames, image, census, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_sgm_path_dev(ModContext *c, int32_t frames, const uint32_t *census_left, const uint32_t *census_right, const ModSgmParams *p,
+                     int32_t direction, uint8_t *path_cost, uint8_t *matching_cost) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!census_left || !census_right || !path_cost) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null plane");
+  if ((rc = check_sgm_params(c, p))) return rc;
+  if (direction < 0 || direction > 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "direction must be 0..7");
+  // (stage entry point, tests and tracing) the D == 128 kernels read up to 127 words before the right plane: give them a padded copy
+  const size_t words = (size_t)frames * c->dc.W * c->dc.H;
+  uint32_t *padded = nullptr;
+  hipError_t e = hipSuccess;
+  if (p->disparities == 128) {
+    e = hipMalloc((void **)&padded, (words + 128) * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(padded, 0, 128 * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(padded + 128, census_right, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
+  }
+  if (e == hipSuccess) {
+    launch_sgm_path(c->dc.W, c->dc.H, frames, p->disparities, p->p1, p->p2, direction, census_left, padded ? padded + 128 : census_right, path_cost,
+                    matching_cost, padded != nullptr, c->stream);
+    e = hipGetLastError();
+  }
+  if (padded) { (void)hipStreamSynchronize(c->stream); (void)hipFree(padded); }   // on every path, the failed ones included
+  HIP_TRY(c, e);
+  return MOD_OK;
+}
+
+int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, const uint8_t *right, const ModSgmParams *p, float *disparity) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!left || !right) return MOD_SKIP_NO_DISPARITY_NOW;     // no image pair: no disparity (estimateDisparity fails, :272-276)
+  if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity plane");
+  if ((rc = check_sgm_params(c, p))) return rc;
+  int group = 1;
+  if ((rc = ensure_sgm_scratch(c, p->disparities, frames, &group))) return rc;
+  const int W = c->dc.W, H = c->dc.H, D = p->disparities;
+  const size_t N = (size_t)W * H;
+  Buffers &b = c->b;
+  static const int order4[4] = {0, 1, 2, 3};
+  // Groups of frames go through two sets of census planes and cost volumes: while the winner-take-all of group k streams its
+  // volumes (HBM-bound, context stream), the aggregation paths of group k + 1 (instruction-bound, one side stream per path) already
+  // run.  Order on the context stream: census(0) fork(0) | census(1) fork(1) join(0) finish(0) | census(2) fork(2) join(1) finish(1) ...
+  // — set s is written again (census(k + 2), paths(k + 2) behind fork(k + 2)) only after finish(k) has been enqueued before it.
+  const int ngroups = (frames + group - 1) / group;
+  const size_t set_census = 2 * N * group, set_volumes = N * (size_t)D * group * kSgmPaths;
+  uint8_t *dl = b.sgm_maps, *dr = dl + N * group, *dlm = dr + N * group, *drm = dlm + N * group;
+  bool all_in_one[2] = {false, false};
+  auto start = [&](int k) -> int {
+    const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
+    uint32_t *cl = b.sgm_census + 128 + s * set_census, *cr = cl + N * g;
+    launch_sgm_census(W, H, g, left + (size_t)f0 * N, cl, c->stream);
+    launch_sgm_census(W, H, g, right + (size_t)f0 * N, cr, c->stream);
+    HIP_TRY(c, hipEventRecord(b.sgm_fork[s], c->stream));
+    const size_t path_stride = N * (size_t)D * g;        // one volume [g][H][W][D] per path
+    // the published configuration: all paths in ONE grid on one side stream (sgm.hip k_sgm_paths_all)
+    HIP_TRY(c, hipStreamWaitEvent(b.sgm_side[0], b.sgm_fork[s], 0));
+    if (launch_sgm_paths_all(W, H, g, D, p->p1, p->p2, p->paths, path_stride, cl, cr, b.sgm_S + s * set_volumes, b.sgm_side[0])) {
+      HIP_TRY(c, hipEventRecord(b.sgm_join[s][0], b.sgm_side[0]));
+      all_in_one[s] = true;
+      return MOD_OK;
+    }
+    all_in_one[s] = false;
+    for (int i = 0; i < p->paths; i++) {
+      HIP_TRY(c, hipStreamWaitEvent(b.sgm_side[i], b.sgm_fork[s], 0));   // a failed wait would let a path read census planes in flight
+      launch_sgm_path(W, H, g, D, p->p1, p->p2, p->paths == 4 ? order4[i] : i, cl, cr, b.sgm_S + s * set_volumes + (size_t)i * path_stride,
+                      nullptr, /*right_plane_padded=*/true, b.sgm_side[i]);   // cr follows cl inside the scratch allocation
+      HIP_TRY(c, hipEventRecord(b.sgm_join[s][i], b.sgm_side[i]));
+    }
+    return MOD_OK;
+  };
+  auto finish = [&](int k) -> int {
+    const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
+    // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
+    for (int i = 0; i < (all_in_one[s] ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, b.sgm_join[s][i], 0));
+    launch_sgm_finish(W, H, g, D, p->paths, N * (size_t)D * g, p->median, p->lr_check, b.sgm_S + s * set_volumes, dl, dr, dlm, drm,
+                      disparity + (size_t)f0 * N, c->stream);
+    return MOD_OK;
+  };
+  if ((rc = start(0))) return rc;
+  for (int k = 0; k < ngroups; k++) {
+    if (k + 1 < ngroups && (rc = start(k + 1))) return rc;
+    if ((rc = finish(k))) return rc;
+  }
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, const uint8_t *now, const ModFlowParams *p, float *flow) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!prev || !now) return MOD_SKIP_NO_FLOW;                  // no image pair: no flow (estimateOpticalFlow fails, :279-290)
+  if (!flow) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow plane");
+  if ((rc = check_flow_params(c, p, frames))) return rc;
+  if ((rc = ensure_flow_scratch(c))) return rc;
+  Buffers &b = c->b;
+  const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
+  int Wl[kFlowMaxLevels], Hl[kFlowMaxLevels];
+  Wl[0] = c->dc.W; Hl[0] = c->dc.H;
+  for (int l = 1; l < L; l++) { Wl[l] = Wl[l - 1] >> 1; Hl[l] = Hl[l - 1] >> 1; }
+  const size_t img0 = flow_level_offset(c, 1);
+  auto img = [&](int l) { return b.flow_img + (flow_level_offset(c, l) - img0); };     // level l >= 1: [2][F][Hl][Wl]
+  auto cen = [&](int l) { return b.flow_census + flow_level_offset(c, l); };           // level l: [2][F][Hl][Wl]
+  for (int l = 1; l < L; l++) {
+    const size_t Ns = (size_t)Wl[l - 1] * Hl[l - 1];
+    launch_flow_pyramid(Wl[l - 1], Hl[l - 1], Wl[l], Hl[l], F, l == 1 ? prev : img(l - 1), l == 1 ? now : img(l - 1) + F * Ns, img(l), c->stream);
+  }
+  const size_t N = (size_t)Wl[0] * Hl[0];
+  launch_sgm_census(Wl[0], Hl[0], F, prev, cen(0), c->stream);
+  launch_sgm_census(Wl[0], Hl[0], F, now, cen(0) + F * N, c->stream);
+  for (int l = 1; l < L; l++) launch_sgm_census(Wl[l], Hl[l], 2 * F, img(l), cen(l), c->stream);
+  // coarse to fine; level l writes integer plane set (l & 1) and reads set ((l + 1) & 1)
+  const size_t set = 2 * (size_t)c->cfg.max_frames * c->maxN;
+  short4 *const sub = p->subpixel ? b.flow_sub.get() : nullptr;
+  for (int l = L - 1; l >= 0; l--) {
+    const bool coarsest = l == L - 1;
+    launch_flow_match(Wl[l], Hl[l], coarsest ? 0 : Wl[l + 1], coarsest ? 0 : Hl[l + 1], F, dirs, p->window, p->radius, cen(l),
+                      coarsest ? nullptr : b.flow_int + ((l + 1) & 1) * set, b.flow_int + (l & 1) * set, l == 0 ? sub : nullptr, c->stream);
+  }
+  launch_flow_finish(Wl[0], Hl[0], F, b.flow_int, dirs == 2 ? b.flow_int + (size_t)F * N : nullptr, sub, p->fb_check, flow, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_egomotion_dev(ModContext *c, int32_t frames, const float *disparity_prev, const float *disparity_now, const float *flow,
+                      const ModEgoParams *p, ModTransform *transforms, ModEgoResult *results) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if ((rc = check_ego_params(c, p))) return rc;
+  if (!transforms) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null transforms");
+  if ((rc = construct_skip(flow, disparity_prev, true, disparity_now))) return rc;
+  return run_egomotion(c, frames, disparity_prev, disparity_now, flow, p, transforms, results, nullptr, 0.0);
+}
+
+}  // extern "C"

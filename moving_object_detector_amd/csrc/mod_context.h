@@ -1,0 +1,213 @@
+// mod_context.h — the context behind the C ABI and what its host-side files share (internal to libmod_sf.so, not installed):
+// mod_sf.hip (lifecycle, the batched scene-flow / cluster path), estimators.hip (SGM, flow, ego-motion), host_api.hip (*_host calls).
+#pragma once
+#include "../../include/mod_sf.h"
+#include "frame_const.h"
+#include "mod_launch.h"
+
+#include <string>
+#include <utility>
+#include <vector>
+
+constexpr int kRing = 4;        // pinned staging slots for the per-frame constants
+constexpr int kMaxChunks = 4;   // mod_process_dev cuts a large batch into at most this many chunks (ModConfig.batch_chunks)
+
+// One owner per GPU resource: a handle releases what it holds when it is reset or destroyed, and reads as the raw pointer / handle.
+// put() releases the old resource and hands the slot to the hip*Malloc / hip*Create call that fills it.
+template <class H, auto Release>
+class Owned {
+  H h_ = nullptr;
+
+ public:
+  Owned() = default;
+  Owned(Owned &&o) noexcept : h_(std::exchange(o.h_, nullptr)) {}
+  Owned &operator=(Owned &&o) noexcept { std::swap(h_, o.h_); return *this; }
+  ~Owned() { reset(); }
+  operator H() const { return h_; }
+  H get() const { return h_; }
+  H *put() { reset(); return &h_; }
+  void reset() { if (h_) (void)Release(h_); h_ = nullptr; }
+};
+template <class T> using DevPtr = Owned<T *, hipFree>;
+template <class T> using HostPtr = Owned<T *, hipHostFree>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+// allocates unless p already holds a buffer (lazily built buffer sets can be resumed after a failed attempt without leaking)
+template <class T>
+hipError_t dalloc(DevPtr<T> &p, size_t count) { return p ? hipSuccess : hipMalloc((void **)p.put(), count * sizeof(T)); }
+
+struct EventPair { Event a, b; };
+
+struct Buffers {
+  DevPtr<double> rayx, rayy;
+  DevPtr<FrameConst> fc;                    // [maxF]
+  DevPtr<uint64_t> mask, lroot;
+  DevPtr<float2> zrange;                    // [maxF][H][mask_words] depth range of the dynamic pixels of each mask word (fused path)
+  DevPtr<int32_t> parent;
+  DevPtr<int32_t> rsize, rkey;
+  DevPtr<ClusterBox> cbox;
+  DevPtr<int32_t> counters;
+  DevPtr<ClusterInfo> clusters;             // 2 x [maxF][max_objects]
+  DevPtr<uint32_t> mbits, mpix;
+  DevPtr<uint32_t> worklist;      // [2][F * max_objects]: all clusters of a launch, then the ambiguous ones
+  DevPtr<unsigned long long> dbg;
+  DevPtr<uint2> requests;
+  DevPtr<int32_t> tilehdr;
+  DevPtr<uint32_t> tilelist;
+  size_t req_alloc = 0;                     // entries currently allocated for `requests`
+  // one-frame staging for the *_host entry points (allocated on first use)
+  DevPtr<float> h_dnow, h_dprev, h_flow, h_planes;
+  DevPtr<void> h_aos;
+  DevPtr<int32_t> h_labels, h_nobj;
+  DevPtr<ModObject> h_objects;
+  // on-GPU disparity (allocated on first use)
+  DevPtr<uint32_t> sgm_census;
+  DevPtr<uint8_t> sgm_maps;
+  DevPtr<uint8_t> sgm_S;                    // [paths][group][H][W][D] path cost volumes
+  int sgm_D = 0, sgm_G = 0;                 // disparities / frames per group the scratch is sized for
+  // the aggregation paths are independent of each other: they run side by side on these streams (forked from / joined to the
+  // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
+  Stream sgm_side[8];
+  Event sgm_fork[2], sgm_join[2][8];
+  // on-GPU optical flow (allocated on first use, every level sized for max_width x max_height x max_frames; see flow_level_offset)
+  DevPtr<uint8_t> flow_img;                 // pyramid levels 1 .. kFlowMaxLevels - 1 of both images
+  DevPtr<uint32_t> flow_census;             // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
+  DevPtr<short2> flow_int;                  // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
+  DevPtr<short4> flow_sub;                  // [maxF][maxN] sub-pixel terms of level 0
+  // on-GPU ego-motion (allocated on first use; the correspondence buffers grow to the smallest stride seen: see ensure_ego_scratch)
+  DevPtr<double> ego_corr;                  // [maxF][9][ego_cap]
+  DevPtr<uint8_t> ego_flag;                 // [maxF][ego_cap]
+  DevPtr<int32_t> ego_blkcnt;               // [maxF][blocks of the grid at the smallest stride]
+  size_t ego_cap = 0;
+  DevPtr<int32_t> ego_ncorr;                // [maxF]
+  DevPtr<double> ego_hyp;                   // [maxF][MOD_EGO_MAX_HYPOTHESES][12]
+  DevPtr<int32_t> ego_hcnt;                 // [maxF][MOD_EGO_MAX_HYPOTHESES]
+  DevPtr<ModTransform> ego_tf;              // [maxF] mod_egomotion_host
+  DevPtr<ModEgoResult> ego_res;             // [maxF] mod_egomotion_host / a NULL `results` of mod_egomotion_dev
+};
+
+// Every resource is a member handle: mod_destroy synchronizes the streams below, and `delete` releases the rest.
+struct ModContext {
+  ModConfig cfg{};
+  ModCamera cam{};
+  ModParams prm{};
+  bool has_cam = false, has_prm = false;
+  Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
+  hipStream_t stream = nullptr;             // own_stream or the caller's
+  DevCam dc{};
+  Buffers b;
+  int max_objects = 0;
+  size_t maxN = 0;
+  int max_mask_words = 0;
+  // host streaming (mod_submit_frame_host): per-slot device buffers, a ring of MOD_PIPELINE_DEPTH + 1 disparity planes
+  // (frame t's plane is frame t+1's "previous"), two copy streams and the events that order them with the kernels
+  struct Pipe {
+    bool ready = false;
+    Stream h2d, d2h;
+    DevPtr<float> dnow[MOD_PIPELINE_DEPTH + 1], dprev[MOD_PIPELINE_DEPTH], flow[MOD_PIPELINE_DEPTH];
+    DevPtr<float> planes[MOD_PIPELINE_DEPTH];
+    DevPtr<void> aos[MOD_PIPELINE_DEPTH];
+    DevPtr<int32_t> labels[MOD_PIPELINE_DEPTH], nobj[MOD_PIPELINE_DEPTH];
+    DevPtr<ModObject> objects[MOD_PIPELINE_DEPTH];
+    HostPtr<int32_t> h_n[MOD_PIPELINE_DEPTH];        // pinned: object count of the slot's frame
+    HostPtr<ModObject> h_obj[MOD_PIPELINE_DEPTH];    // pinned: its objects (handed to the caller's array at collect time)
+    ModObject *user_obj[MOD_PIPELINE_DEPTH] = {};
+    int32_t user_cap[MOD_PIPELINE_DEPTH] = {};
+    Event ev_in[MOD_PIPELINE_DEPTH], ev_done[MOD_PIPELINE_DEPTH], ev_out[MOD_PIPELINE_DEPTH];
+    DevPtr<uint8_t> img[MOD_PIPELINE_DEPTH];         // mod_submit_stereo_host: the slot's two 8-bit images
+    Event ev_img[MOD_PIPELINE_DEPTH];                // ... the estimator has been enqueued behind them (context stream)
+    bool img_used[MOD_PIPELINE_DEPTH] = {};
+    Event ev_ring;                                   // last disparity plane written by kernels (stereo path)
+    // a ring plane may still be on its way to a caller's `disparity` buffer (result stream) when a frame that ended at a guard —
+    // it takes a plane but no ticket — has advanced the ring back to it: the plane's next writer waits for that copy
+    Event ev_plane_read[MOD_PIPELINE_DEPTH + 1];
+    bool plane_read_pending[MOD_PIPELINE_DEPTH + 1] = {};
+    bool ring_by_kernels = false;
+    // mod_submit_images_host: the left images, a ring indexed like the disparity planes (frame t's image is frame t+1's previous one;
+    // a frame that ends at a guard takes a plane but no ticket, so the ticket slots would not do)
+    DevPtr<uint8_t> limg[MOD_PIPELINE_DEPTH + 1];
+    Event ev_limg[MOD_PIPELINE_DEPTH + 1];           // the last kernel that reads the image has been enqueued (context stream)
+    bool limg_used[MOD_PIPELINE_DEPTH + 1] = {};
+    bool have_prev_img = false;                      // limg[(dring - 1) % (DEPTH + 1)] holds the previous submit's left image
+    // mod_submit_odometry_host: the slot's estimate on the device and its pinned host copy; collect reads the status
+    struct EgoSlot { ModTransform tf; ModEgoResult res; };
+    DevPtr<EgoSlot> ego;                             // device [DEPTH]
+    HostPtr<EgoSlot> h_ego[MOD_PIPELINE_DEPTH];      // pinned
+    bool odo[MOD_PIPELINE_DEPTH] = {};               // the slot's ticket came from the odometry stream
+    ModTransform *user_tf[MOD_PIPELINE_DEPTH] = {};
+    ModEgoResult *user_ego[MOD_PIPELINE_DEPTH] = {};
+    int64_t dring = 0;                               // disparity planes handed out so far: plane of the next frame = dring % (DEPTH + 1)
+    int64_t seq = 0;                                 // frames submitted so far
+    int in_flight = 0;
+    bool have_prev = false;                          // dnow[(seq - 1) % (DEPTH + 1)] holds the previous frame's disparity
+  } pipe;
+  HostPtr<FrameConst> pinned[kRing];
+  Event pinned_ev[kRing];
+  int ring_pos = 0;
+  // chunks of a large batch (process_chunked): chunk 0 runs on the context's stream, chunk k > 0 on chunk_stream[k - 1], forked from
+  // and joined to the context's stream with events, so the call keeps the stream semantics of every other entry point.  Made by
+  // mod_create when the context may chunk.
+  Stream chunk_stream[kMaxChunks - 1];
+  Event ev_fork, ev_join[kMaxChunks - 1];
+  // The tile headers (word 0) and the cluster counters are ZERO between calls: the context's first call clears them, and the cluster stage's
+  // last readers (k_final; k_median_ties' last workgroup) clear what a call has set — two memsets less in front of every call, which
+  // a small batch feels (a launch costs it ~8 us of GPU time whatever it does).  False while a call is being enqueued; a call that
+  // failed half-way leaves it false and the next one clears the scratch itself.
+  bool scratch_clean = false;
+  // the odometry stream's estimator has written the frame's FrameConst into b.fc on the stream: the scene-flow launch reads it there
+  bool fc_resident = false;
+  int profiling = 0;                          // stage mask of mod_set_profiling
+  std::vector<EventPair> pending[MOD_STAGE_COUNT];
+  std::vector<EventPair> free_events;
+  double stage_ms[MOD_STAGE_COUNT] = {};
+  int64_t stage_calls[MOD_STAGE_COUNT] = {};
+  std::string err;
+};
+
+inline int fail(ModContext *ctx, int code, const std::string &msg) {
+  if (ctx) ctx->err = msg;
+  return code;
+}
+
+#define HIP_TRY(ctx, expr)                                                                              \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess)                                                                               \
+      return fail(ctx, MOD_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));              \
+  } while (0)
+
+inline int check_ready(ModContext *c, int frames) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam || !c->has_prm) return fail(c, MOD_ERR_NOT_CONFIGURED, "camera and parameters must be set first");
+  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
+  return MOD_OK;
+}
+
+// construct()'s guards, in its order: nothing is published when an input is missing (scene_flow_constructor.cpp:104,110,122,127,133)
+inline int construct_skip(bool flow, bool prev, bool transform, bool now) {
+  if (!flow) return MOD_SKIP_NO_FLOW;
+  if (!prev) return MOD_SKIP_NO_DISPARITY_PREV;
+  if (!transform) return MOD_SKIP_NO_TRANSFORM;
+  if (!now) return MOD_SKIP_NO_DISPARITY_NOW;
+  return MOD_OK;
+}
+
+// mod_sf.hip
+void refresh_devcam(ModContext *c);
+int begin_cluster_scratch(ModContext *c);
+int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
+                const ModClusterOut *out);
+// the scene-flow stage of the host entry points: their SoA planes are internal staging that no caller sees (the cloud leaves as
+// 32-byte records straight from the kernel's registers), so the x and y planes are not written at all
+int scene_flow_staged(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *out);
+
+// estimators.hip
+int check_sgm_params(ModContext *c, const ModSgmParams *p);
+int check_flow_params(ModContext *c, const ModFlowParams *p, int frames);
+int check_ego_params(ModContext *c, const ModEgoParams *p);
+// the ego-motion estimator over `frames` frames; tf == null: into b.ego_tf, res == null: into b.ego_res; fc != null: also the frames'
+// scene-flow constants (with dt) into fc
+int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p,
+                  ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt);
