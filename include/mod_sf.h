@@ -303,6 +303,36 @@ int  mod_egomotion_dev(ModContext *ctx, int32_t frames, const float *disparity_p
 int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const float *disparity_now, const float *flow,
                         const ModEgoParams *params, ModTransform *transform, ModEgoResult *result);
 
+/* ---- camera images: encodings, windows, grey on the GPU --------------------------------------------------------------------- */
+/* The reference subscribes to image_rect_color (bgr8 / rgb8 / bgra8, rows possibly padded) and converts with
+ * cv_bridge::toCvCopy(..., MONO8) (scene_flow_constructor.cpp:220-221); its ZED launch crops a centred window first
+ * (image_crop.cpp:24-40).  A ModImageLayout describes such a message and the camera-sized window (the context's W x H) taken from
+ * it.  Grey = OpenCV's 8-bit BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14 (B = G = R = v gives v); alpha is ignored.
+ *   mod_set_image_layout   the layout of the HOST images every *_host image entry point reads (mod_sgm_compute_host,
+ *                          mod_flow_compute_host, mod_submit_stereo_host, mod_submit_images_host, mod_submit_odometry_host),
+ *                          read at call time like mod_set_params: a frame in flight completes with the layout of its own submit.
+ *                          NULL = mono8, packed, W x H, origin 0 (the layout of a context that never set one).  Only the window
+ *                          crosses PCIe; mono8 is copied straight into the estimator's buffer, colour is converted on the GPU.
+ *   mod_get_image_layout   the layout in force (the NULL layout spelled out)
+ *   mod_image_to_mono_dev  device frames stacked at step * height bytes -> grey planes [frames][H][W]; layout NULL = the context's.
+ *                          Ordered on the context's stream.  NULL src -> MOD_SKIP_NO_DISPARITY_NOW, like a NULL image elsewhere.
+ * MOD_ERR_INVALID_ARGUMENT: unknown encoding, step < width * channels, a window that does not fit inside the message;
+ * MOD_ERR_NOT_CONFIGURED: no camera yet (the window size is the camera's). */
+#define MOD_ENCODING_MONO8 0
+#define MOD_ENCODING_BGR8  1
+#define MOD_ENCODING_RGB8  2
+#define MOD_ENCODING_BGRA8 3
+#define MOD_ENCODING_RGBA8 4
+typedef struct ModImageLayout {   /* 24 bytes */
+  int32_t encoding;               /* MOD_ENCODING_* */
+  int32_t width, height;          /* of the message (sensor_msgs/Image width, height) */
+  int32_t step;                   /* bytes per row, >= width * channels */
+  int32_t x0, y0;                 /* top-left of the window taken; the window is the context's W x H */
+} ModImageLayout;
+int  mod_set_image_layout(ModContext *ctx, const ModImageLayout *layout);
+int  mod_get_image_layout(const ModContext *ctx, ModImageLayout *layout);
+int  mod_image_to_mono_dev(ModContext *ctx, int32_t frames, const uint8_t *src, const ModImageLayout *layout, uint8_t *mono);
+
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()
  * would publish nothing.  cloud_aos: W*H*32 bytes; labels: W*H int32; objects: capacity `max_objects`.
@@ -357,7 +387,8 @@ int  mod_collect_frame_host(ModContext *ctx, int32_t ticket, int32_t *n_objects)
  * estimator (mod_sgm_compute_dev) writes the disparity plane straight into the pipe's ring — where it serves as `now` of this frame
  * and as `previous` of the next — and scene flow + clustering follow on the context's stream: the disparity never crosses PCIe
  * (mod_sgm_compute_host + mod_submit_frame_host move it there and back: two trips of 4 bytes per pixel and frame).
- *   left / right    W*H bytes each, row-major (sensor_msgs/Image mono8); NULL = the estimator has nothing to work on:
+ *   left / right    W*H bytes each, row-major (sensor_msgs/Image mono8), or messages of the layout mod_set_image_layout set
+ *                   (colour, padded rows, a window; converted on the GPU); NULL = the estimator has nothing to work on:
  *                   MOD_SKIP_NO_DISPARITY_NOW, and the next frame has no previous disparity (disparity_now_.reset(), :272-276)
  *   sgm             estimator parameters; the camera's min / max_disparity must describe its output (0 and disparities - 1)
  *   flow, transform, dt, cloud_aos, labels, objects, max_objects, ticket: as mod_submit_frame_host.  A frame that ends at one

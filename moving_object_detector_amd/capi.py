@@ -32,6 +32,10 @@ MOD_PER_KERNEL_CLUSTER_STAGES = (1, 2, 3, 4, 5)
 MOD_PIPELINE_DEPTH = 3
 MOD_EGO_OK, MOD_EGO_FEW_POINTS, MOD_EGO_FEW_INLIERS, MOD_EGO_DIVERGED = 0, 1, 2, 3
 MOD_EGO_MAX_HYPOTHESES = 4096
+MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
+ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
+             "rgba8": MOD_ENCODING_RGBA8}
+CHANNELS = {MOD_ENCODING_MONO8: 1, MOD_ENCODING_BGR8: 3, MOD_ENCODING_RGB8: 3, MOD_ENCODING_BGRA8: 4, MOD_ENCODING_RGBA8: 4}
 STAGE_NAMES = ("k_scene_flow", "k_ccl_bits+k_ccl_tile_list", "k_ccl_link", "k_ccl_merge", "k_final", "k_median+k_median_ties",
                "cluster group (first launch to last)")
 
@@ -46,6 +50,7 @@ EXPORTS = [
     "mod_sgm_census_dev", "mod_sgm_path_dev", "mod_sgm_compute_dev", "mod_sgm_compute_host",
     "mod_flow_compute_dev", "mod_flow_compute_host", "mod_submit_images_host",
     "mod_egomotion_dev", "mod_egomotion_host", "mod_submit_odometry_host",
+    "mod_set_image_layout", "mod_get_image_layout", "mod_image_to_mono_dev",
 ]
 
 
@@ -121,6 +126,27 @@ def ego_params(stride: int = 4, hypotheses: int = 256, iterations: int = 10, min
                         int(seed) & 0xFFFFFFFF, 0)
 
 
+class ModImageLayout(C.Structure):
+    _fields_ = [("encoding", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("step", C.c_int32), ("x0", C.c_int32),
+                ("y0", C.c_int32)]
+
+
+def image_layout(encoding, width: int, height: int, step=None, x0: int = 0, y0: int = 0) -> ModImageLayout:
+    """ModImageLayout of a sensor_msgs/Image: `encoding` a MOD_ENCODING_* value or its ROS name ("bgr8", ...); step None = packed
+    rows (width * channels); (x0, y0) = top-left of the camera-sized window taken from it."""
+    enc = ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+    if step is None:
+        step = int(width) * CHANNELS.get(enc, 1)
+    return ModImageLayout(enc, int(width), int(height), int(step), int(x0), int(y0))
+
+
+def centred_window(msg_w: int, msg_h: int, W: int, H: int):
+    """Origin (x0, y0) of the centred W x H window of a msg_w x msg_h image: image_crop.cpp:24-40's integer (msg - size) / 2."""
+    if not (0 < W <= msg_w and 0 < H <= msg_h):
+        raise ValueError("the window must fit inside the image")
+    return (msg_w - W) // 2, (msg_h - H) // 2
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -178,6 +204,9 @@ def load(require_torch_first: bool = True):
     L.mod_egomotion_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.POINTER(ModEgoResult)]
     L.mod_submit_odometry_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.c_double,
                                            vp, vp, vp, i32, vp, vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(i32)]
+    L.mod_set_image_layout.argtypes = [vp, C.POINTER(ModImageLayout)]
+    L.mod_get_image_layout.argtypes = [vp, C.POINTER(ModImageLayout)]
+    L.mod_image_to_mono_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), vp]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

@@ -44,6 +44,32 @@ static int fetch_cluster_results(ModContext *c, int32_t *labels, ModObject *obje
   return MOD_OK;
 }
 
+// ---- host images (mod_set_image_layout) --------------------------------------------------------------------------------
+// The window of one host image to the device on stream s, as packed rows of W * channels bytes: one copy when the window's rows are
+// contiguous in the message (the default layout: the whole mono8 image), else a 2D copy.  Only the window crosses PCIe.
+static hipError_t copy_window(const ModImageLayout &l, int W, int H, const uint8_t *src, uint8_t *dst, hipStream_t s) {
+  const int C = image_channels(l.encoding);
+  const size_t row = (size_t)W * C;
+  const uint8_t *o = src + (size_t)l.y0 * l.step + (size_t)l.x0 * C;
+  if ((size_t)l.step == row) return hipMemcpyAsync(dst, o, row * H, hipMemcpyHostToDevice, s);
+  return hipMemcpy2DAsync(dst, row, o, (size_t)l.step, row, (size_t)H, hipMemcpyHostToDevice, s);
+}
+
+// The two images of a synchronous *_host call, grey on the device behind the context's stream: mono8 straight into the flow
+// staging slot (its 8 N bytes hold both), colour windows into that slot and k_to_mono from there into the cloud staging.
+static int upload_pair(ModContext *c, const ModImageLayout &l, const uint8_t *img0, const uint8_t *img1, uint8_t **grey) {
+  const int W = c->dc.W, H = c->dc.H;
+  uint8_t *slot = reinterpret_cast<uint8_t *>(c->b.h_flow.get());
+  const size_t P = (size_t)W * H * image_channels(l.encoding);
+  HIP_TRY(c, copy_window(l, W, H, img0, slot, c->stream));
+  HIP_TRY(c, copy_window(l, W, H, img1, slot + P, c->stream));
+  if (l.encoding == MOD_ENCODING_MONO8) { *grey = slot; return MOD_OK; }
+  *grey = static_cast<uint8_t *>(c->b.h_aos.get());
+  launch_to_mono(l.encoding, W, H, 2, slot, P, (int)(P / H), 0, 0, *grey, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
 // ---- host streaming: the pipe ------------------------------------------------------------------------------------------
 static int ensure_pipe(ModContext *c) {
   ModContext::Pipe &p = c->pipe;
@@ -129,28 +155,50 @@ static int submit_stereo(ModContext *c, const uint8_t *left, const uint8_t *righ
   if ((rc = check_sgm_params(c, sgm))) return rc;
   if (images && (rc = check_flow_params(c, fprm, 1))) return rc;
   if (odo && (rc = check_ego_params(c, eprm))) return rc;
+  ModImageLayout lay;
+  if ((rc = current_layout(c, &lay))) return rc;
+  const bool colour = lay.encoding != MOD_ENCODING_MONO8;
   if (p.in_flight >= MOD_PIPELINE_DEPTH) return fail(c, MOD_ERR_CAPACITY, "MOD_PIPELINE_DEPTH frames are already in flight");
   if ((rc = ensure_pipe(c))) return rc;
   constexpr int R = MOD_PIPELINE_DEPTH + 1;
   const int slot = (int)(p.seq % MOD_PIPELINE_DEPTH), nowi = (int)(p.dring % R), previ = (int)((p.dring + R - 1) % R);
-  const size_t N = (size_t)c->dc.W * c->dc.H;
+  const int W = c->dc.W, H = c->dc.H;
+  const size_t N = (size_t)W * H;
   if (!p.img[slot]) HIP_TRY(c, dalloc(p.img[slot], 2 * c->maxN));
   if (images && !p.limg[nowi]) HIP_TRY(c, dalloc(p.limg[nowi], c->maxN));
   if (images && !p.ev_limg[nowi]) HIP_TRY(c, hipEventCreateWithFlags(p.ev_limg[nowi].put(), hipEventDisableTiming));
+  if (colour && !p.stage[slot]) HIP_TRY(c, dalloc(p.stage[slot], 8 * c->maxN));
+  if (colour && !p.ev_stage[slot]) HIP_TRY(c, hipEventCreateWithFlags(p.ev_stage[slot].put(), hipEventDisableTiming));
   // images (and flow) on the copy stream; the slot's image buffer may still be read by the estimator of a frame that ended at a
   // guard (it took no ticket, so nobody waited for it): the copy queues behind that estimator.  A resident left image is replaced
-  // only after the last kernel that reads it (its own frame's and the next frame's estimators).
+  // only after the last kernel that reads it (its own frame's and the next frame's estimators).  Colour windows go to the slot's
+  // staging, which is replaced only after the kernels that read it; their grey is written on the context's stream, behind every
+  // older reader of img[slot] / limg[nowi].
   if (p.img_used[slot]) HIP_TRY(c, hipStreamWaitEvent(p.h2d, p.ev_img[slot], 0));
   uint8_t *dleft = p.img[slot];
   if (images) {
-    if (p.limg_used[nowi]) HIP_TRY(c, hipStreamWaitEvent(p.h2d, p.ev_limg[nowi], 0));
+    if (p.limg_used[nowi] && !colour) HIP_TRY(c, hipStreamWaitEvent(p.h2d, p.ev_limg[nowi], 0));
     dleft = p.limg[nowi];
   }
-  HIP_TRY(c, hipMemcpyAsync(dleft, left, N, hipMemcpyHostToDevice, p.h2d));
-  HIP_TRY(c, hipMemcpyAsync(p.img[slot] + N, right, N, hipMemcpyHostToDevice, p.h2d));
+  const size_t P = N * image_channels(lay.encoding);
+  if (colour) {
+    if (p.stage_used[slot]) HIP_TRY(c, hipStreamWaitEvent(p.h2d, p.ev_stage[slot], 0));
+    HIP_TRY(c, copy_window(lay, W, H, left, p.stage[slot], p.h2d));
+    HIP_TRY(c, copy_window(lay, W, H, right, p.stage[slot] + P, p.h2d));
+  } else {
+    HIP_TRY(c, copy_window(lay, W, H, left, dleft, p.h2d));
+    HIP_TRY(c, copy_window(lay, W, H, right, p.img[slot] + N, p.h2d));
+  }
   if (flow) HIP_TRY(c, hipMemcpyAsync(p.flow[slot], flow, 8 * N, hipMemcpyHostToDevice, p.h2d));
   HIP_TRY(c, hipEventRecord(p.ev_in[slot], p.h2d));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, p.ev_in[slot], 0));
+  if (colour) {                     // cv_bridge::toCvCopy(..., MONO8) (:220-221) on the GPU
+    launch_to_mono(lay.encoding, W, H, 1, p.stage[slot], P, (int)(P / H), 0, 0, dleft, c->stream);
+    launch_to_mono(lay.encoding, W, H, 1, p.stage[slot] + P, P, (int)(P / H), 0, 0, p.img[slot] + N, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(p.ev_stage[slot], c->stream));
+    p.stage_used[slot] = true;
+  }
   // estimateDisparity (:258-279) on the GPU, straight into the ring: this plane is `now` here and `previous` of the next frame.
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   if (p.plane_read_pending[nowi]) { HIP_TRY(c, hipStreamWaitEvent(c->stream, p.ev_plane_read[nowi], 0)); p.plane_read_pending[nowi] = false; }
@@ -207,9 +255,9 @@ int mod_flow_compute_host(ModContext *c, const uint8_t *prev, const uint8_t *now
   if ((rc = ensure_host_staging(c))) return rc;
   const size_t N = (size_t)c->dc.W * c->dc.H;
   Buffers &b = c->b;
-  uint8_t *dimg = reinterpret_cast<uint8_t *>(b.h_flow.get());    // staging: the 8 N bytes of the flow slot hold both images
-  HIP_TRY(c, hipMemcpyAsync(dimg, prev, N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dimg + N, now, N, hipMemcpyHostToDevice, c->stream));
+  ModImageLayout lay;
+  uint8_t *dimg = nullptr;
+  if ((rc = current_layout(c, &lay)) || (rc = upload_pair(c, lay, prev, now, &dimg))) return rc;
   if ((rc = mod_flow_compute_dev(c, 1, dimg, dimg + N, p, b.h_planes))) return rc;
   HIP_TRY(c, hipMemcpyAsync(flow, b.h_planes, 8 * N, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -246,9 +294,9 @@ int mod_sgm_compute_host(ModContext *c, const uint8_t *left, const uint8_t *righ
   if ((rc = ensure_host_staging(c))) return rc;
   const size_t N = (size_t)c->dc.W * c->dc.H;
   Buffers &b = c->b;
-  uint8_t *dimg = reinterpret_cast<uint8_t *>(b.h_flow.get());    // staging: the 8 N bytes of the flow slot hold both images
-  HIP_TRY(c, hipMemcpyAsync(dimg, left, N, hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipMemcpyAsync(dimg + N, right, N, hipMemcpyHostToDevice, c->stream));
+  ModImageLayout lay;
+  uint8_t *dimg = nullptr;
+  if ((rc = current_layout(c, &lay)) || (rc = upload_pair(c, lay, left, right, &dimg))) return rc;
   if ((rc = mod_sgm_compute_dev(c, 1, dimg, dimg + N, p, b.h_dnow))) return rc;
   HIP_TRY(c, hipMemcpyAsync(disparity, b.h_dnow, 4 * N, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));

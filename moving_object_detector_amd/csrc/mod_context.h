@@ -93,6 +93,8 @@ struct ModContext {
   ModCamera cam{};
   ModParams prm{};
   bool has_cam = false, has_prm = false;
+  ModImageLayout layout{};                  // of the host images (mod_set_image_layout) ...
+  bool has_layout = false;                  // ... or, while false, mono8 packed at the camera's size
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -130,6 +132,11 @@ struct ModContext {
     Event ev_limg[MOD_PIPELINE_DEPTH + 1];           // the last kernel that reads the image has been enqueued (context stream)
     bool limg_used[MOD_PIPELINE_DEPTH + 1] = {};
     bool have_prev_img = false;                      // limg[(dring - 1) % (DEPTH + 1)] holds the previous submit's left image
+    // colour images (mod_set_image_layout): the slot's two windows as they arrive, W * H * 4 bytes each (allocated on first use);
+    // k_to_mono turns them into grey in img[slot] / limg[nowi] on the context's stream
+    DevPtr<uint8_t> stage[MOD_PIPELINE_DEPTH];
+    Event ev_stage[MOD_PIPELINE_DEPTH];              // ... the kernels that read them have been enqueued (context stream)
+    bool stage_used[MOD_PIPELINE_DEPTH] = {};
     // mod_submit_odometry_host: the slot's estimate on the device and its pinned host copy; collect reads the status
     struct EgoSlot { ModTransform tf; ModEgoResult res; };
     DevPtr<EgoSlot> ego;                             // device [DEPTH]
@@ -196,6 +203,9 @@ inline int construct_skip(bool flow, bool prev, bool transform, bool now) {
 
 // mod_sf.hip
 void refresh_devcam(ModContext *c);
+// the layout the host image entry points read (the set one, or mono8 packed W x H), checked against the camera
+int current_layout(ModContext *c, ModImageLayout *out);
+int check_layout(ModContext *c, const ModImageLayout &l);
 int begin_cluster_scratch(ModContext *c);
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                 const ModClusterOut *out);

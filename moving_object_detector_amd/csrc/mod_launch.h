@@ -120,3 +120,9 @@ struct EgoArgs {
 };
 int ego_grid_blocks(int gw, int gh);   // blocks of the correspondence kernels per frame
 void launch_egomotion(const EgoArgs &a, hipStream_t s);
+
+// camera images to grey (ingest.hip).  Window W x H at (x0, y0) of each 8-bit frame (row pitch `step`, frames frame_bytes apart)
+// -> dst [frames][H][W]; encoding MOD_ENCODING_*
+int image_channels(int encoding);   // 0: unknown encoding
+void launch_to_mono(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int x0, int y0, uint8_t *dst,
+                    hipStream_t s);

@@ -249,6 +249,22 @@ int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPl
 
 }  // namespace
 
+int check_layout(ModContext *c, const ModImageLayout &l) {
+  const int C = image_channels(l.encoding);
+  if (!C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown image encoding");
+  if (l.width < 1 || l.height < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "image size must be positive");
+  if ((int64_t)l.step < (int64_t)l.width * C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "step is smaller than width * channels");
+  if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the image");
+  return MOD_OK;
+}
+
+int current_layout(ModContext *c, ModImageLayout *out) {
+  if (!c->has_layout) { *out = ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0}; return MOD_OK; }
+  *out = c->layout;
+  return check_layout(c, *out);   // the camera may have changed since the layout was set
+}
+
 void refresh_devcam(ModContext *c) {
   DevCam &d = c->dc;
   d.W = c->cam.width; d.H = c->cam.height;
@@ -447,6 +463,38 @@ int mod_get_camera(const ModContext *c, ModCamera *cam) {
 int mod_get_params(const ModContext *c, ModParams *p) {
   if (!c || !p || !c->has_prm) return MOD_ERR_NOT_CONFIGURED;
   *p = c->prm;
+  return MOD_OK;
+}
+
+int mod_set_image_layout(ModContext *c, const ModImageLayout *l) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
+  if (!l) { c->has_layout = false; return MOD_OK; }
+  int rc = check_layout(c, *l);
+  if (rc) return rc;
+  c->layout = *l; c->has_layout = true;
+  return MOD_OK;
+}
+
+int mod_get_image_layout(const ModContext *c, ModImageLayout *l) {
+  if (!c || !l) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return MOD_ERR_NOT_CONFIGURED;
+  *l = c->has_layout ? c->layout : ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};
+  return MOD_OK;
+}
+
+int mod_image_to_mono_dev(ModContext *c, int32_t frames, const uint8_t *src, const ModImageLayout *layout, uint8_t *mono) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
+  if (frames < 1 || frames > 65535) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be in 1..65535");
+  if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
+  ModImageLayout l;
+  int rc = layout ? check_layout(c, *layout) : current_layout(c, &l);
+  if (rc) return rc;
+  if (layout) l = *layout;
+  launch_to_mono(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.x0, l.y0, mono, c->stream);
+  HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
 

@@ -50,14 +50,85 @@ struct DisparityImage {
 // sensor_msgs/CameraInfo: only the projection matrix P is used (image_geometry::PinholeCameraModel::fromCameraInfo)
 struct CameraInfo { int width = 0, height = 0; double P[12] = {0}; };
 
-// sensor_msgs/Image, encoding mono8 (what the disparity estimator consumes): row-major, step == width
-struct Image { Header header; int width = 0, height = 0; const uint8_t *data = nullptr; };
+// image_crop.cpp:24-40: the camera of the centred w x h window of an info.width x info.height image — the window starts at the
+// integer ((W - w) / 2, (H - h) / 2) and the principal point moves by that offset (P[2], P[6]; K[2], K[5] alike in the reference)
+inline void centred_origin(int W, int H, int w, int h, int *x0, int *y0) { *x0 = (W - w) / 2; *y0 = (H - h) / 2; }
+inline CameraInfo crop_camera_info(const CameraInfo &info, int w, int h) {
+  int x0 = 0, y0 = 0;
+  centred_origin(info.width, info.height, w, h, &x0, &y0);
+  CameraInfo c = info;
+  c.P[2] = info.P[2] - x0;
+  c.P[6] = info.P[6] - y0;
+  c.width = w; c.height = h;
+  return c;
+}
+
+// sensor_msgs/Image: row-major 8-bit pixels, `step` bytes per row (0: width * channels).  mono8 is what the disparity estimator
+// consumes; bgr8 / rgb8 / bgra8 / rgba8 (image_rect_color) are converted on the GPU (mod_set_image_layout)
+struct Image {
+  Header header; int width = 0, height = 0; const uint8_t *data = nullptr;
+  std::string encoding = "mono8";
+  int step = 0;
+};
+
+// MOD_ENCODING_* of a sensor_msgs/Image encoding, -1 for one the library cannot take
+inline int image_encoding(const std::string &e) {
+  if (e == "mono8") return MOD_ENCODING_MONO8;
+  if (e == "bgr8") return MOD_ENCODING_BGR8;
+  if (e == "rgb8") return MOD_ENCODING_RGB8;
+  if (e == "bgra8") return MOD_ENCODING_BGRA8;
+  if (e == "rgba8") return MOD_ENCODING_RGBA8;
+  return -1;
+}
+inline int image_channels(int encoding) { return encoding == MOD_ENCODING_MONO8 ? 1 : encoding <= MOD_ENCODING_RGB8 ? 3 : 4; }
+
+// The layout of `image` with the camera-sized window at (x0, y0); false for an encoding the library cannot take
+inline bool image_layout(const Image &image, int x0, int y0, ModImageLayout *layout) {
+  const int enc = image_encoding(image.encoding);
+  if (enc < 0) return false;
+  layout->encoding = enc; layout->width = image.width; layout->height = image.height;
+  layout->step = image.step > 0 ? image.step : image.width * image_channels(enc);
+  layout->x0 = x0; layout->y0 = y0;
+  return true;
+}
 
 // cv_bridge::CvImage with encoding 32FC2: optical flow, x then y
 struct FlowImage { Header header; int width = 0, height = 0; const float *data = nullptr; };
 
 // geometry_msgs/Transform
 struct Transform { double translation[3] = {0, 0, 0}; double rotation[4] = {0, 0, 0, 1}; /* x y z w */ };
+
+// tf2::Transform in double: rotation matrix (row-major) and translation.  The pose arithmetic of integrateAndBroadcastTF
+// (scene_flow_constructor.cpp:320-348): products, inverses, and the quaternion <-> matrix conversions of tf2::Matrix3x3.
+struct Pose {
+  double R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+  double t[3] = {0, 0, 0};
+  static Pose fromTransform(const Transform &x) {          // tf2::Matrix3x3::setRotation
+    const double qx = x.rotation[0], qy = x.rotation[1], qz = x.rotation[2], qw = x.rotation[3];
+    const double d = qx * qx + qy * qy + qz * qz + qw * qw, s = 2.0 / d;
+    const double xs = qx * s, ys = qy * s, zs = qz * s, wx = qw * xs, wy = qw * ys, wz = qw * zs;
+    const double xx = qx * xs, xy = qx * ys, xz = qx * zs, yy = qy * ys, yz = qy * zs, zz = qz * zs;
+    Pose p;
+    const double m[3][3] = {{1.0 - (yy + zz), xy - wz, xz + wy}, {xy + wz, 1.0 - (xx + zz), yz - wx}, {xz - wy, yz + wx, 1.0 - (xx + yy)}};
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) p.R[i][j] = m[i][j]; p.t[i] = x.translation[i]; }
+    return p;
+  }
+  Pose operator*(const Pose &o) const {
+    Pose p;
+    for (int i = 0; i < 3; i++) {
+      for (int j = 0; j < 3; j++) p.R[i][j] = R[i][0] * o.R[0][j] + R[i][1] * o.R[1][j] + R[i][2] * o.R[2][j];
+      p.t[i] = R[i][0] * o.t[0] + R[i][1] * o.t[1] + R[i][2] * o.t[2] + t[i];
+    }
+    return p;
+  }
+  Pose inverse() const {
+    Pose p;
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) p.R[i][j] = R[j][i];
+    for (int i = 0; i < 3; i++) p.t[i] = -(p.R[i][0] * t[0] + p.R[i][1] * t[1] + p.R[i][2] * t[2]);
+    return p;
+  }
+  Transform toTransform() const;
+};
 
 // The libviso2 hand-off (scene_flow_constructor.cpp:232-249): VisualOdometryStereo::getMotion() returns the 4x4 motion of the
 // left camera from the previous to the current frame; the reference wraps it as tf2::Transform(Matrix3x3, Vector3) and stores
@@ -88,6 +159,13 @@ inline Transform transform_from_motion(const double m[4][4]) {
   }
   for (int i = 0; i < 4; i++) t.rotation[i] = q[i];     // x y z w
   return t;
+}
+
+inline Transform Pose::toTransform() const {   // tf2::Matrix3x3::getRotation, as transform_from_motion
+  double m[4][4] = {};
+  for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) m[i][j] = R[i][j]; m[i][3] = t[i]; }
+  m[3][3] = 1.0;
+  return transform_from_motion(m);
 }
 
 // sensor_msgs/PointCloud2 carrying pcl::PointXYZVelocity records (point_step 32; x@0 y@4 z@8 vx@16 vy@20 vz@24)

@@ -8,8 +8,15 @@
 //   disparity        on the GPU (libmod_sf's SGM), replacing sgm_gpu::SgmGpu::computeDisparity (:35,267)
 //   scene flow       on the GPU, overlapped with the next frame's estimators like construct_thread_ (:389-392): submitStereo() /
 //                    collect(); the disparity plane stays in HBM as the next frame's previous one (:397-398)
-//   optical flow     CALL-OUT estimateOpticalFlow(): the reference asks pwc_net (:281-291); not part of this package
-//   camera motion    CALL-OUT estimateCameraMotion(): the reference runs libviso2 and a TF lookup (:214-256); not part of this package
+//   optical flow     on the GPU (libmod_sf's census flow, not PWC-Net) when `~gpu_estimators` is true (default); with it false, the
+//                    CALL-OUT estimateOpticalFlow(): the reference asks pwc_net (:281-291); not part of this package
+//   camera motion    on the GPU (libmod_sf's stereo ego-motion, not libviso2) when `~gpu_estimators` is true: submitOdometry() /
+//                    collectOdometry() take the images as they arrive (encoding and step from the message, mod_set_image_layout), the
+//                    pose is integrated and odom -> base_link broadcast as integrateAndBroadcastTF does (:246,320-348; frame ids from
+//                    `~visual_odometry/{base_link,odom}_frame_id`, base -> camera from TF, identity when it is not available); with it
+//                    false, the CALL-OUT estimateCameraMotion(): the reference runs libviso2 and a TF lookup (:214-256)
+//   crop             `~crop_width` / `~crop_height` (0 = off) take the centred window of the images on the GPU and the camera of
+//                    crop_camera_info(), in place of the ZED launch's two image_crop nodes (image_crop.cpp:24-40)
 //   clustering       on the GPU, IN THIS PROCESS, when `~publish_moving_objects` is true (default): the node then advertises
 //                    `~moving_objects` itself (what the separate scene_flow_clusterer publishes, clusterer_nodelet.cpp:324-343) from the
 //                    planes that are still in HBM — one clustering per frame, no 29.5 MB PointCloud2 hand-off between two processes
@@ -35,7 +42,12 @@
 #include <sensor_msgs/CameraInfo.h>
 #include <sensor_msgs/Image.h>
 #include <sensor_msgs/PointCloud2.h>
+#include <geometry_msgs/TransformStamped.h>
+#include <tf2_ros/buffer.h>
+#include <tf2_ros/transform_broadcaster.h>
+#include <tf2_ros/transform_listener.h>
 
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -60,6 +72,15 @@ class SceneFlowConstructorNode {
     sgm.p2 = private_node_handle_.param("p2", 96); sgm.paths = private_node_handle_.param("paths", 8); sgm.lr_check = 1; sgm.median = 1;
     impl_->setDisparityParams(sgm);
     max_disparity_ = (float)(sgm.disparities - 1);
+
+    // every estimator on the GPU (default), or the two CALL-OUTs below; optional centred crop of the incoming images
+    gpu_estimators_ = private_node_handle_.param("gpu_estimators", true);
+    crop_width_ = private_node_handle_.param("crop_width", 0);
+    crop_height_ = private_node_handle_.param("crop_height", 0);
+    ros::NodeHandle visual_odometry_nh(private_node_handle_, "visual_odometry");   // the reference's frame parameters (:28-30)
+    base_link_frame_id_ = visual_odometry_nh.param("base_link_frame_id", std::string("base_link"));
+    odom_frame_id_ = visual_odometry_nh.param("odom_frame_id", std::string("odom"));
+    tf_listener_.reset(new tf2_ros::TransformListener(tf_buffer_));
 
     image_transport_.reset(new image_transport::ImageTransport(private_node_handle_));
 
@@ -123,6 +144,7 @@ class SceneFlowConstructorNode {
   // stereoCallback (:365-399)
   void stereoCallback(const sensor_msgs::ImageConstPtr &left_image, const sensor_msgs::ImageConstPtr &right_image,
                       const sensor_msgs::CameraInfoConstPtr &left_camera_info, const sensor_msgs::CameraInfoConstPtr &right_camera_info) {
+    if (gpu_estimators_) { gpuCallback(left_image, right_image, left_camera_info, right_camera_info); return; }
     const ros::WallTime start_process = ros::WallTime::now();
     if (!camera_set_) {               // first frame: camera model from the left CameraInfo (:368-375); disparity fields as the estimator reports them
       mod_host::CameraInfo info;
@@ -173,36 +195,137 @@ class SceneFlowConstructorNode {
     previous_left_image_ = left_image;
   }
 
+  static mod_host::Image image_of(const sensor_msgs::Image &m) {
+    mod_host::Image o;
+    o.header = header_of(m.header); o.width = m.width; o.height = m.height; o.data = m.data.data();
+    o.encoding = m.encoding; o.step = (int)m.step;
+    return o;
+  }
+
+  // stereoCallback with every estimator on the GPU: the images go in as they arrive (bgr8 / rgb8 / bgra8 / rgba8 / mono8, padded
+  // rows, the centred crop window), disparity, flow, camera motion, scene flow and clusters run there, the frame before is
+  // collected, its objects published and the pose broadcast
+  void gpuCallback(const sensor_msgs::ImageConstPtr &left_image, const sensor_msgs::ImageConstPtr &right_image,
+                   const sensor_msgs::CameraInfoConstPtr &left_camera_info, const sensor_msgs::CameraInfoConstPtr &right_camera_info) {
+    const ros::WallTime start_process = ros::WallTime::now();
+    const bool crop = crop_width_ > 0 && crop_height_ > 0;
+    if (!camera_set_) {               // first frame (:368-375); with the crop, the camera of the window (image_crop.cpp:31-39)
+      mod_host::CameraInfo info;
+      info.width = left_camera_info->width; info.height = left_camera_info->height;
+      for (int i = 0; i < 12; i++) info.P[i] = left_camera_info->P[i];
+      if (crop) info = mod_host::crop_camera_info(info, crop_width_, crop_height_);
+      mod_host::DisparityImage d;
+      d.f = (float)left_camera_info->P[0];
+      d.T = (float)(-right_camera_info->P[3] / right_camera_info->P[0]);
+      d.min_disparity = 0.0f; d.max_disparity = max_disparity_;
+      impl_->setCameraInfo(info, d);
+      camera_set_ = true;
+      camera_frame_id_ = left_image->header.frame_id;   // (:372)
+    }
+    publishPendingOdometry();
+    int x0 = 0, y0 = 0;
+    if (crop) mod_host::centred_origin((int)left_image->width, (int)left_image->height, crop_width_, crop_height_, &x0, &y0);
+    mod_host::Image l = image_of(*left_image), r = image_of(*right_image);
+    const bool usable = mod_host::image_encoding(left_image->encoding) >= 0;
+    if (!usable)                      // dropped like a failed estimateDisparity (:272-276): the next frame has no previous one
+      ROS_ERROR("image encoding '%s' is not one of mono8, bgr8, rgb8, bgra8, rgba8: frame dropped", left_image->encoding.c_str());
+    pending_objects_.reset(publish_moving_objects_ && moving_objects_pub_.getNumSubscribers() > 0 ? new mod_host::MovingObjectArray() : nullptr);
+    const bool want_flow = optflow_pub_.getNumSubscribers() > 0, want_depth = depth_pub_.getNumSubscribers() > 0;
+    pending_flow_.clear(); pending_disparity_.clear();
+    pending_cloud_.reset(pc_with_velocity_pub_.getNumSubscribers() > 0 ? new mod_host::PointCloud2() : nullptr);   // (:141-142)
+    pending_ticket_ = impl_->submitOdometry(usable ? &l : nullptr, usable ? &r : nullptr, pending_objects_.get(), want_flow ? &pending_flow_ : nullptr,
+                                            x0, y0, want_depth ? &pending_disparity_ : nullptr, pending_cloud_.get());
+    pending_header_ = left_image->header;
+    pending_keep_ = {left_image, right_image};        // the buffers stay alive until the frame is collected
+    ROS_INFO("process time: %f", (ros::WallTime::now() - start_process).toSec());
+  }
+
+  // the frame before: objects, ~optical_flow, ~depth, and integrateAndBroadcastTF (:320-348) when its estimate succeeded
+  void publishPendingOdometry() {
+    if (pending_ticket_ < 0) return;
+    const bool moved = impl_->collectOdometry(pending_ticket_);
+    pending_ticket_ = -1;
+    const size_t n = (size_t)impl_->imageWidth() * impl_->imageHeight();
+    if (moved) {
+      std::string error_msg;
+      mod_host::Transform base_to_camera;            // identity unless TF knows better
+      if (tf_buffer_.canTransform(base_link_frame_id_, camera_frame_id_, pending_header_.stamp, &error_msg)) {
+        const geometry_msgs::TransformStamped m = tf_buffer_.lookupTransform(base_link_frame_id_, camera_frame_id_, pending_header_.stamp);
+        base_to_camera.translation[0] = m.transform.translation.x; base_to_camera.translation[1] = m.transform.translation.y;
+        base_to_camera.translation[2] = m.transform.translation.z;
+        base_to_camera.rotation[0] = m.transform.rotation.x; base_to_camera.rotation[1] = m.transform.rotation.y;
+        base_to_camera.rotation[2] = m.transform.rotation.z; base_to_camera.rotation[3] = m.transform.rotation.w;
+      } else {
+        ROS_ERROR("The tf from '%s' to '%s' does not seem to be available, will assume it as identity! (%s)", base_link_frame_id_.c_str(),
+                  camera_frame_id_.c_str(), error_msg.c_str());
+      }
+      impl_->setBaseToCamera(base_to_camera);
+      const mod_host::Transform odom_to_base = impl_->odomToBase().toTransform();
+      geometry_msgs::TransformStamped msg;
+      msg.header.stamp = pending_header_.stamp; msg.header.frame_id = odom_frame_id_;
+      msg.child_frame_id = base_link_frame_id_;
+      msg.transform.translation.x = odom_to_base.translation[0]; msg.transform.translation.y = odom_to_base.translation[1];
+      msg.transform.translation.z = odom_to_base.translation[2];
+      msg.transform.rotation.x = odom_to_base.rotation[0]; msg.transform.rotation.y = odom_to_base.rotation[1];
+      msg.transform.rotation.z = odom_to_base.rotation[2]; msg.transform.rotation.w = odom_to_base.rotation[3];
+      tf_broadcaster_.sendTransform(msg);
+    }
+    if (!pending_flow_.empty() && optflow_pub_.getNumSubscribers() > 0) {      // (:99-100)
+      sensor_msgs::Image m;
+      m.header = pending_header_; m.width = impl_->imageWidth(); m.height = impl_->imageHeight(); m.encoding = "32FC2";
+      m.step = 8 * m.width; m.data.resize(8 * n);
+      std::memcpy(m.data.data(), pending_flow_.data(), 8 * n);
+      optflow_pub_.publish(m);
+    }
+    if (!pending_disparity_.empty() && depth_pub_.getNumSubscribers() > 0) {   // ~depth (toDepthImage, :114-121)
+      sensor_msgs::Image m;
+      m.header = pending_header_; m.width = impl_->imageWidth(); m.height = impl_->imageHeight(); m.encoding = "32FC1";
+      m.step = 4 * m.width; m.data.resize(4 * n);
+      if (mod_depth_image_host(ctx_, pending_disparity_.data(), reinterpret_cast<float *>(m.data.data())) == MOD_OK) depth_pub_.publish(m);
+    }
+    if (moved && pending_objects_) publishObjects();
+    if (moved && pending_cloud_) publishCloud();
+    pending_objects_.reset();
+    pending_cloud_.reset();
+    pending_keep_.clear();
+  }
+
+  void publishObjects() {                                             // publishMovingObjects (clusterer_nodelet.cpp:324-343)
+    moving_object_msgs::MovingObjectArray m;
+    m.header = pending_header_;
+    for (const auto &o : pending_objects_->moving_object_array) {
+      moving_object_msgs::MovingObject mo;
+      mo.id = o.id;
+      mo.center.position.x = o.center.position[0]; mo.center.position.y = o.center.position[1]; mo.center.position.z = o.center.position[2];
+      mo.center.orientation.x = 0; mo.center.orientation.y = 0; mo.center.orientation.z = 0; mo.center.orientation.w = 1;
+      mo.velocity.x = o.velocity[0]; mo.velocity.y = o.velocity[1]; mo.velocity.z = o.velocity[2];
+      mo.bounding_box.x = o.bounding_box[0]; mo.bounding_box.y = o.bounding_box[1]; mo.bounding_box.z = o.bounding_box[2];
+      m.moving_object_array.push_back(mo);
+    }
+    moving_objects_pub_.publish(m);
+  }
+
   void publishPending() {
     if (pending_ticket_ < 0) return;
     impl_->collect(pending_ticket_);
     pending_ticket_ = -1;
-    if (pending_objects_) {                                           // publishMovingObjects (clusterer_nodelet.cpp:324-343)
-      moving_object_msgs::MovingObjectArray m;
-      m.header = pending_header_;
-      for (const auto &o : pending_objects_->moving_object_array) {
-        moving_object_msgs::MovingObject mo;
-        mo.id = o.id;
-        mo.center.position.x = o.center.position[0]; mo.center.position.y = o.center.position[1]; mo.center.position.z = o.center.position[2];
-        mo.center.orientation.x = 0; mo.center.orientation.y = 0; mo.center.orientation.z = 0; mo.center.orientation.w = 1;
-        mo.velocity.x = o.velocity[0]; mo.velocity.y = o.velocity[1]; mo.velocity.z = o.velocity[2];
-        mo.bounding_box.x = o.bounding_box[0]; mo.bounding_box.y = o.bounding_box[1]; mo.bounding_box.z = o.bounding_box[2];
-        m.moving_object_array.push_back(mo);
-      }
-      moving_objects_pub_.publish(m);
+    if (pending_objects_) {
+      publishObjects();
       pending_objects_.reset();
     }
-    if (pending_cloud_) {                                             // publishPointcloud (:351-362); asked for because somebody subscribed (:144)
-      sensor_msgs::PointCloud2 msg;   // fields x, y, z, vx, vy, vz float32 at 0, 4, 8, 16, 20, 24 (pcl_point_xyz_velocity.h:27-34)
-      msg.header = pending_header_; msg.width = pending_cloud_->width; msg.height = pending_cloud_->height;
-      msg.point_step = 32; msg.row_step = pending_cloud_->row_step; msg.is_dense = true; msg.is_bigendian = false;
-      msg.data = std::move(pending_cloud_->data);
-      const char *names[6] = {"x", "y", "z", "vx", "vy", "vz"};
-      const uint32_t offs[6] = {0, 4, 8, 16, 20, 24};
-      for (int i = 0; i < 6; i++) { sensor_msgs::PointField pf; pf.name = names[i]; pf.offset = offs[i]; pf.datatype = sensor_msgs::PointField::FLOAT32; pf.count = 1; msg.fields.push_back(pf); }
-      pc_with_velocity_pub_.publish(msg);
-    }
+    if (pending_cloud_) publishCloud();   // asked for because somebody subscribed (:144)
     pending_keep_.clear();
+  }
+
+  void publishCloud() {                   // publishPointcloud (:351-362)
+    sensor_msgs::PointCloud2 msg;         // fields x, y, z, vx, vy, vz float32 at 0, 4, 8, 16, 20, 24 (pcl_point_xyz_velocity.h:27-34)
+    msg.header = pending_header_; msg.width = pending_cloud_->width; msg.height = pending_cloud_->height;
+    msg.point_step = 32; msg.row_step = pending_cloud_->row_step; msg.is_dense = true; msg.is_bigendian = false;
+    msg.data = std::move(pending_cloud_->data);
+    const char *names[6] = {"x", "y", "z", "vx", "vy", "vz"};
+    const uint32_t offs[6] = {0, 4, 8, 16, 20, 24};
+    for (int i = 0; i < 6; i++) { sensor_msgs::PointField pf; pf.name = names[i]; pf.offset = offs[i]; pf.datatype = sensor_msgs::PointField::FLOAT32; pf.count = 1; msg.fields.push_back(pf); }
+    pc_with_velocity_pub_.publish(msg);
   }
 
   // ~depth (toDepthImage, :114-121) and ~synthetic_optical_flow (:136-145): synchronous side path, only while somebody subscribes
@@ -252,6 +375,14 @@ class SceneFlowConstructorNode {
   std_msgs::Header pending_header_;
   std::vector<sensor_msgs::ImageConstPtr> pending_keep_;
   std::vector<float> view_prev_disparity_;
+  // ~gpu_estimators
+  bool gpu_estimators_ = true;
+  int crop_width_ = 0, crop_height_ = 0;
+  std::vector<float> pending_flow_, pending_disparity_;
+  std::string camera_frame_id_, base_link_frame_id_, odom_frame_id_;
+  tf2_ros::Buffer tf_buffer_;
+  std::unique_ptr<tf2_ros::TransformListener> tf_listener_;
+  tf2_ros::TransformBroadcaster tf_broadcaster_;
 };
 
 }  // namespace scene_flow_constructor

@@ -2,8 +2,9 @@
 // (scene_flow_constructor/include/scene_flow_constructor.h:33-275) for the part of the class that is on the hot path:
 // construct(), the previous-frame state of stereoCallback() and reconfigureCB().  Same member names, same argument
 // meaning, same "publish nothing when an input is missing" behaviour — the per-pixel work goes through the C ABI
-// (include/mod_sf.h) to the HIP kernels.  estimateDisparity() is here as well (the on-GPU SGM of SURVEY.md section 8(f) row 3); the
-// other estimators (PWC-Net / viso2), TF and ROS wiring are out of scope.
+// (include/mod_sf.h) to the HIP kernels.  estimateDisparity() is here as well (the on-GPU SGM of SURVEY.md section 8(f) row 3), and
+// submitOdometry() runs every estimator on the GPU (colour images in, camera motion and moving objects out) with the pose
+// integration of integrateAndBroadcastTF; the ROS wiring itself is in ros_adapter/.
 #pragma once
 #include <functional>
 #include <stdexcept>
@@ -69,6 +70,7 @@ class SceneFlowConstructor {
     // the library copies the CONTEXT's width x height bytes from each image: an image of another size than the configured camera
     // would be over-read (setCameraInfo() ran on the first frame, scene_flow_constructor.cpp:368-375)
     if (image_width_ > 0 && (left_image->width != image_width_ || left_image->height != image_height_)) return false;
+    if (!useLayout(*left_image, *right_image, 0, 0)) return false;   // the context reads the images as this message describes them
     pixels->resize((size_t)left_image->width * left_image->height);
     const int rc = mod_sgm_compute_host(ctx_, left_image->data, right_image->data, &sgm_, pixels->data());
     if (rc > 0) return false;
@@ -207,7 +209,8 @@ class SceneFlowConstructor {
                    const mod_host::Transform *transform_prev2now, mod_host::PointCloud2 *pc_with_velocity,
                    mod_host::MovingObjectArray *moving_objects = nullptr) {
     const bool images = left_image && right_image && left_image->data && right_image->data && left_image->width == image_width_ &&
-                        left_image->height == image_height_ && right_image->width == image_width_ && right_image->height == image_height_;
+                        left_image->height == image_height_ && right_image->width == image_width_ && right_image->height == image_height_ &&
+                        useLayout(*left_image, *right_image, 0, 0);
     ModTransform tf{};
     if (transform_prev2now) {
       for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
@@ -234,38 +237,127 @@ class SceneFlowConstructor {
     next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
     return ticket;
   }
+  // Pipelined stereoCallback() with every estimator on the GPU: images in (any encoding the library takes, rows as the message
+  // pads them, the camera-sized window at (x0, y0)), moving objects and the estimated camera motion out.  The layout is taken from
+  // the left message (left and right must agree in encoding, size and step, as the reference asserts, scene_flow_constructor.cpp:
+  // 224-226).  dt is the stamp difference of consecutive left images.  flow_out (optional, W * H * 2 floats): ~optical_flow;
+  // disparity_out (optional, W * H floats): the disparity image (32FC1, -1 where no match).  Both are valid after collectOdometry().
+  // Returns a ticket for collectOdometry(), or -1 where nothing will be published (first frame, missing or unusable images).
+  int submitOdometry(const mod_host::Image *left_image, const mod_host::Image *right_image, mod_host::MovingObjectArray *moving_objects,
+                     std::vector<float> *flow_out = nullptr, int x0 = 0, int y0 = 0, std::vector<float> *disparity_out = nullptr,
+                     mod_host::PointCloud2 *pc_with_velocity = nullptr) {
+    const bool images = left_image && right_image && left_image->data && right_image->data && useLayout(*left_image, *right_image, x0, y0);
+    const double dt = (images && have_stamp_) ? mod_host::duration_sec(left_image->header.stamp, previous_stamp_) : 0.0;
+    Pending &p = pending_[next_slot_];
+    p.objects.resize(max_objects_);
+    if (flow_out) flow_out->resize((size_t)image_width_ * image_height_ * 2);
+    if (disparity_out) disparity_out->resize((size_t)image_width_ * image_height_);
+    if (pc_with_velocity) pc_with_velocity->data.resize((size_t)image_width_ * image_height_ * 32);
+    int32_t ticket = -1;
+    ModFlowParams fp{4, 4, 5, 1, 1};
+    const int rc = mod_submit_odometry_host(ctx_, images ? left_image->data : nullptr, images ? right_image->data : nullptr, &sgm_, &fp,
+                                            &ego_, dt, pc_with_velocity ? pc_with_velocity->data.data() : nullptr, nullptr,
+                                            moving_objects ? p.objects.data() : nullptr,
+                                            moving_objects ? (int32_t)p.objects.size() : 0, disparity_out ? disparity_out->data() : nullptr,
+                                            flow_out ? flow_out->data() : nullptr,
+                                            &p.tf, &p.ego, &ticket);
+    have_parked_ = false;
+    if (images) { previous_stamp_ = left_image->header.stamp; have_stamp_ = true; }
+    else have_stamp_ = false;
+    if (rc > 0) return -1;
+    check(rc);
+    p.ticket = ticket; p.cloud = pc_with_velocity; p.objs = moving_objects; p.header = left_image->header;
+    next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
+    return ticket;
+  }
+  // collect() of an odometry ticket: fills the messages, integrates the pose (only when the estimate succeeded) and returns the
+  // estimated motion prev -> now; false when visual odometry failed (nothing is published, the pose is unchanged, :251-255).
+  bool collectOdometry(int ticket, mod_host::Transform *motion = nullptr) {
+    for (Pending &p : pending_) {
+      if (p.ticket != ticket) continue;
+      const int rc = finish(p, ticket);
+      if (motion) {
+        for (int i = 0; i < 3; i++) motion->translation[i] = p.tf.t[i];
+        for (int i = 0; i < 4; i++) motion->rotation[i] = p.tf.q[i];
+      }
+      return integrateEstimate(p.tf, rc == MOD_OK ? p.ego.status : MOD_EGO_DIVERGED);
+    }
+    throw std::runtime_error("collectOdometry(): unknown ticket");
+  }
+
+  // integrateAndBroadcastTF (scene_flow_constructor.cpp:246,320-348): integrated_pose_ *= motion.inverse().  base_to_camera: the
+  // base_link -> camera transform (the reference's TF lookup, identity when it is not available).
+  void integrate(const mod_host::Transform &motion) { integrated_pose_ = integrated_pose_ * mod_host::Pose::fromTransform(motion).inverse(); }
+  // an estimate of the library: integrated only when it succeeded (the reference integrates inside `if (viso_success)`, :231-246)
+  bool integrateEstimate(const ModTransform &tf, int ego_status) {
+    if (ego_status != MOD_EGO_OK) return false;
+    mod_host::Transform m;
+    for (int i = 0; i < 3; i++) m.translation[i] = tf.t[i];
+    for (int i = 0; i < 4; i++) m.rotation[i] = tf.q[i];
+    integrate(m);
+    return true;
+  }
+  void setBaseToCamera(const mod_host::Transform &base_to_camera) { base_to_camera_ = mod_host::Pose::fromTransform(base_to_camera); }
+  const mod_host::Pose &integratedPose() const { return integrated_pose_; }
+  // odom -> base_link, the transform the reference broadcasts: B * integrated * B^-1
+  mod_host::Pose odomToBase() const { return base_to_camera_ * integrated_pose_ * base_to_camera_.inverse(); }
+  // camera -> odom, B * integrated: what MovingObjectsTracker::movingObjectsCallback takes as to_odom
+  mod_host::Pose cameraToOdom() const { return base_to_camera_ * integrated_pose_; }
+  void setEgoParams(const ModEgoParams &p) { ego_ = p; }
+
   void collect(int ticket) {
     for (Pending &p : pending_) {
       if (p.ticket != ticket) continue;
-      int32_t n_obj = 0;
-      check(mod_collect_frame_host(ctx_, ticket, &n_obj));
-      if (p.cloud) {
-        p.cloud->header = p.header;
-        p.cloud->width = image_width_; p.cloud->height = image_height_;
-        p.cloud->point_step = 32; p.cloud->row_step = 32 * image_width_;
-        p.cloud->is_dense = true;
-      }
-      if (p.objs) {
-        p.objs->header = p.header;
-        p.objs->moving_object_array.clear();
-        for (int i = 0; i < n_obj && i < (int)p.objects.size(); i++) p.objs->moving_object_array.push_back(mod_host::to_message(p.objects[i]));
-      }
-      p.ticket = -1;
+      check(finish(p, ticket));
       return;
     }
     throw std::runtime_error("collect(): unknown ticket");
   }
 
   void setMaxObjects(int n) { max_objects_ = n; }
+  int imageWidth() const { return image_width_; }
+  int imageHeight() const { return image_height_; }
 
  private:
+
   struct Pending {
     int ticket = -1;
     mod_host::PointCloud2 *cloud = nullptr;
     mod_host::MovingObjectArray *objs = nullptr;
     mod_host::Header header;
     std::vector<ModObject> objects;
+    ModTransform tf{};
+    ModEgoResult ego{};
   };
+  // mod_set_image_layout from the left message, the camera-sized window at (x0, y0); false when the library cannot take the images
+  // (an unknown encoding, a window that does not fit) or left and right disagree in encoding, size or step (the reference asserts
+  // the same, scene_flow_constructor.cpp:224-226).  Every image entry point of this class sets it: the layout is the context's.
+  bool useLayout(const mod_host::Image &left, const mod_host::Image &right, int x0, int y0) {
+    ModImageLayout lay{};
+    if (!mod_host::image_layout(left, x0, y0, &lay) || right.encoding != left.encoding || right.width != left.width ||
+        right.height != left.height || right.step != left.step) return false;
+    return mod_set_image_layout(ctx_, &lay) == MOD_OK;
+  }
+
+  // collects a ticket and fills the messages handed to its submit; returns the collect status (< 0 thrown)
+  int finish(Pending &p, int ticket) {
+    int32_t n_obj = 0;
+    const int rc = mod_collect_frame_host(ctx_, ticket, &n_obj);
+    p.ticket = -1;
+    if (rc < 0) check(rc);
+    if (p.cloud) {
+      p.cloud->header = p.header;
+      p.cloud->width = image_width_; p.cloud->height = image_height_;
+      p.cloud->point_step = 32; p.cloud->row_step = 32 * image_width_;
+      p.cloud->is_dense = true;
+    }
+    if (p.objs) {
+      p.objs->header = p.header;
+      p.objs->moving_object_array.clear();
+      for (int i = 0; i < n_obj && i < (int)p.objects.size(); i++) p.objs->moving_object_array.push_back(mod_host::to_message(p.objects[i]));
+    }
+    return rc;
+  }
   Pending pending_[MOD_PIPELINE_DEPTH];
   int next_slot_ = 0;
   bool have_stamp_ = false, have_parked_ = false;
@@ -286,6 +378,8 @@ class SceneFlowConstructor {
   int image_width_ = 0, image_height_ = 0;
   int max_objects_ = 1024;
   bool have_previous_ = false;
+  ModEgoParams ego_{4, 256, 10, 50, 2.0f, 1.0f, 0u, 0};   // include/mod_sf.h defaults
+  mod_host::Pose integrated_pose_, base_to_camera_;
   mod_host::DisparityImage disparity_previous_;
   std::vector<float> previous_pixels_;
 };

@@ -85,6 +85,15 @@ class Context:
         self._check(self.lib.mod_get_params(self.h, C.byref(s)))
         return s
 
+    def set_image_layout(self, layout: Optional[capi.ModImageLayout]) -> None:
+        """Layout of the host images the *_host image entry points read (mod_set_image_layout); None = mono8 packed at the camera size."""
+        self._check(self.lib.mod_set_image_layout(self.h, C.byref(layout) if layout is not None else None))
+
+    def get_image_layout(self) -> capi.ModImageLayout:
+        s = capi.ModImageLayout()
+        self._check(self.lib.mod_get_image_layout(self.h, C.byref(s)))
+        return s
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.lib.mod_destroy(self.h)
@@ -184,6 +193,27 @@ class Context:
         if rc != 0:
             raise capi.ModError(rc, "mod_flow_compute_dev skipped")
         return out[0] if single and out.dim() == 4 else out
+
+    def image_to_mono(self, src: torch.Tensor, layout: Optional[capi.ModImageLayout] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Grey planes (F, H, W) uint8 at the camera size from device 8-bit frames (mod_image_to_mono_dev): `src` holds F frames of
+        layout.step * layout.height bytes each, back to back (any shape, contiguous uint8); layout None = the context's.  The camera-sized
+        window at (x0, y0) is converted with OpenCV's 8-bit BGR2GRAY formula.  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_image_layout()
+        if src.dtype != torch.uint8 or not src.is_contiguous() or src.device.type != "cuda":
+            raise ValueError("src must be a contiguous uint8 device tensor")
+        frame = lay.step * lay.height
+        if frame <= 0 or src.numel() % frame:
+            raise ValueError("src must hold whole frames of step * height bytes")
+        F = src.numel() // frame
+        if out is None:
+            out = torch.empty((F, self.height, self.width), dtype=torch.uint8, device=src.device)
+        elif out.shape != (F, self.height, self.width) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor (F, H, W)")
+        rc = self._check(self.lib.mod_image_to_mono_dev(self.h, F, src.data_ptr(), C.byref(lay), out.data_ptr()))
+        if rc != 0:
+            raise capi.ModError(rc, "mod_image_to_mono_dev skipped")
+        return out
 
     def estimate_egomotion(self, disp_prev: torch.Tensor, disp_now: torch.Tensor, flow: torch.Tensor,
                            params: Optional[capi.ModEgoParams] = None):

@@ -654,3 +654,44 @@ def make_ego_images(W: int, H: int, seed: int = 0, frames: int = 2, D: int = 128
     out["q"] = np.tile(np.array([[0.0, 0.0, 0.0, 1.0]]), (frames - 1, 1))
     out["boxes"] = boxes
     return out
+
+
+_ENCODINGS = {"mono8": (1, None), "bgr8": (3, (0, 1, 2)), "rgb8": (3, (2, 1, 0)), "bgra8": (4, (0, 1, 2)), "rgba8": (4, (2, 1, 0))}
+
+
+def to_colour(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=None):
+    """A grey image [H][W] uint8 as an 8-bit colour message (a sensor_msgs/Image payload), for the on-GPU conversion (csrc/ingest.hip).
+      seed None   B = G = R = the grey value: the conversion gives `mono` back exactly
+      seed int    channels that differ (each within a few levels of the grey value, so the texture survives), alpha random; the grey
+                  the conversion must give, (1868 B + 9617 G + 4899 R + 8192) >> 14, is returned with it
+      canvas      (msg_w, msg_h) >= (W, H): the image sits in the centred window (image_crop.cpp's (msg - size) / 2) of a larger
+                  message whose other pixels are random
+      pad         bytes at the end of every row (step = msg_w * channels + pad), random
+    Returns (payload uint8 [msg_h][step], layout dict (encoding, width, height, step, x0, y0), expected grey [H][W] uint8)."""
+    if encoding not in _ENCODINGS:
+        raise ValueError(f"unknown encoding {encoding!r}")
+    C, order = _ENCODINGS[encoding]
+    H, W = mono.shape
+    mw, mh = canvas if canvas is not None else (W, H)
+    if mw < W or mh < H or pad < 0:
+        raise ValueError("the canvas must hold the image")
+    x0, y0 = (mw - W) // 2, (mh - H) // 2
+    rng = np.random.Generator(np.random.PCG64([0xC010A, 0 if seed is None else int(seed) + 1]))
+    step = mw * C + pad
+    msg = rng.integers(0, 256, size=(mh, step), dtype=np.uint8)
+    v = mono.astype(np.int64)
+    if C == 1:
+        px = v[..., None]
+        expect = mono.copy()
+    else:
+        if seed is None:
+            bgr = np.stack([v, v, v], -1)
+        else:
+            bgr = np.clip(v[..., None] + rng.integers(-6, 7, size=(H, W, 3)), 0, 255)
+        expect = ((1868 * bgr[..., 0] + 9617 * bgr[..., 1] + 4899 * bgr[..., 2] + 8192) >> 14).astype(np.uint8)
+        px = rng.integers(0, 256, size=(H, W, C)).astype(np.int64)
+        for k, o in enumerate(order):
+            px[..., o] = bgr[..., k]
+    msg[y0:y0 + H, x0 * C:(x0 + W) * C] = px.reshape(H, W * C).astype(np.uint8)
+    layout = {"encoding": encoding, "width": mw, "height": mh, "step": step, "x0": x0, "y0": y0}
+    return msg, layout, expect

@@ -1,0 +1,116 @@
+"""HIP-event timing of the on-GPU image conversion (mod_image_to_mono_dev, csrc/ingest.hip) on 64 frames of 1920 x 1080 for every
+encoding (bytes in + out per second against the HBM's 8 TB/s), and the odometry stream (mod_submit_odometry_host) at 1280 x 720 fed
+mono8 and bgra8 images, from page-locked and from pageable host memory, in frames/s.  Prints one JSON line per measurement.
+Also an odd step and origin (every dword alignment of a run's source).  Run on the GPU: python tools/time_ingest.py [reps]"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_TBPS = 8.0
+
+
+def kernel(reps):
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    W, H, F = 1920, 1080, 64
+    ctx = Context(W, H, max_frames=1)
+    ctx.set_camera(synth.make_camera(W, H))
+    out = torch.empty((F, H, W), dtype=torch.uint8, device=ctx.device)
+    legs = [(enc, capi.image_layout(enc, W, H)) for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8")]
+    # the hard case for alignment: an odd step and an odd origin, so the runs of a row start at every byte offset of a dword
+    legs += [(enc + " odd step/x0", capi.image_layout(enc, W + 3, H + 1, step=(W + 3) * capi.CHANNELS[capi.ENCODINGS[enc]] + 1, x0=1, y0=1))
+             for enc in ("bgr8", "bgra8")]
+    for enc, lay in legs:
+        src = torch.randint(0, 256, (F * lay.step * lay.height,), dtype=torch.uint8, device=ctx.device)
+        call = lambda: ctx.lib.mod_image_to_mono_dev(ctx.h, F, src.data_ptr(), C.byref(lay), out.data_ptr())
+        for _ in range(3):
+            assert call() == 0
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            call()
+        b.record()
+        b.synchronize()
+        ms = a.elapsed_time(b) / reps
+        nbytes = F * W * H * (capi.CHANNELS[lay.encoding] + 1)
+        tbps = nbytes / (ms * 1e-3) / 1e12
+        print(json.dumps({"what": "k_to_mono", "encoding": enc, "W": W, "H": H, "frames": F, "step": lay.step, "x0": lay.x0,
+                          "MB_in": round(F * W * H * capi.CHANNELS[lay.encoding] / 1e6, 1), "reps": reps,
+                          "ms_per_call": round(ms, 4), "TB_per_s": round(tbps, 3), "of_hbm": round(tbps / HBM_TBPS, 3)}), flush=True)
+        del src
+    ctx.close()
+
+
+def stream_fps(W, H, reps, encoding, pinned):
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    m = synth.make_ego_images(W, H, seed=1, frames=2)
+    ctx = Context(W, H, max_frames=1)
+    cam = synth.make_camera(W, H)
+    cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
+    ctx.set_camera(cam)
+    ctx.set_params(synth.Params())
+    sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
+    imgs, pins, keep = [], [], []
+    for k in ("left0", "right0", "left1", "right1"):
+        msg, lay, _ = synth.to_colour(m[k], encoding, seed=None if encoding == "mono8" else 1)
+        if pinned:
+            p = C.c_void_p()
+            assert ctx.lib.mod_host_malloc(ctx.h, msg.nbytes, C.byref(p)) == 0
+            C.memmove(p.value, msg.ctypes.data, msg.nbytes)
+            pins.append(p)
+            imgs.append(p.value)
+        else:
+            keep.append(msg)
+            imgs.append(msg.ctypes.data)
+    ctx.set_image_layout(capi.image_layout(lay["encoding"], lay["width"], lay["height"], lay["step"]))
+    objs = [(capi.ModObject * 64)() for _ in range(3)]
+    t, n = C.c_int32(-1), C.c_int32(-1)
+    pending = []
+
+    def step(i):
+        l, r = (imgs[0], imgs[1]) if i % 2 == 0 else (imgs[2], imgs[3])
+        if len(pending) == 3:
+            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
+        rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
+                                              None, None, None, None, C.byref(t))
+        assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
+        if rc == 0:
+            pending.append(t.value)
+
+    for i in range(10):
+        step(i)
+    frames = max(20, reps)
+    t0 = time.perf_counter()
+    for i in range(10, 10 + frames):
+        step(i)
+    while pending:
+        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
+    dt = time.perf_counter() - t0
+    for p in pins:
+        ctx.lib.mod_host_free(ctx.h, p)
+    ctx.close()
+    return frames / dt
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
+    kernel(reps)
+    for pinned in (True, False):
+        for enc in ("mono8", "bgra8"):
+            fps = stream_fps(1280, 720, min(reps, 100), enc, pinned)
+            print(json.dumps({"what": "mod_submit_odometry_host", "encoding": enc, "host_memory": "pinned" if pinned else "pageable",
+                              "W": 1280, "H": 720, "frames_per_s": round(fps, 1)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
