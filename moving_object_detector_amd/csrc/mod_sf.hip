@@ -1,6 +1,6 @@
 // mod_sf.hip — C ABI (include/mod_sf.h) over the gfx950 kernels: context lifecycle and configuration, the batched scene-flow /
 // cluster / process path, parameter folding, stage timers, memory helpers.  Host-side only; the kernels live in sceneflow.hip and
-// cluster.hip, the estimators' entry points in estimators.hip, the host-pointer calls in host_api.hip.
+// the clusterer's ccl_*.hip / cluster_*.hip, the estimators' entry points in estimators.hip, the host-pointer calls in host_api.hip.
 #include "mod_context.h"
 #include "exact_div.h"
 #include "mod_sf_debug.h"

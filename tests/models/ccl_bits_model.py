@@ -1,4 +1,4 @@
-"""CPU model of the bit-plane tile kernel k_ccl_bits (moving_object_detector_amd/csrc/cluster.hip): the per-tile steps on
+"""CPU model of the bit-plane tile kernel k_ccl_bits (moving_object_detector_amd/csrc/ccl_bits.hip): the per-tile steps on
 Python integers, word for word what the kernel does on (h, a, b) register triples with lane = grid row.
 
 A tile whose dynamic cells all pass each other's depth gate has the connectivity of its MASK alone

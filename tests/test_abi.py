@@ -126,18 +126,25 @@ def test_only_k_final_touches_the_optional_labels_plane():
     other than k_final — the tie replay's image-scan fallback — still reading it.  Source-level pin: `a.labels` appears in
     k_final only, and every store there sits behind a test of the pointer."""
     import re
-    src = open(os.path.join(ROOT, "moving_object_detector_amd", "csrc", "cluster.hip")).read()
-    starts = [(m.start(), m.group(1)) for m in re.finditer(r"__global__[^\n]*\bvoid\s+(\w+)\s*\(", src)]
-    uses = [m.start() for m in re.finditer(r"\ba\.labels\b", src)]
-    assert uses, "k_final is expected to write the labels plane"
-    for u in uses:
-        owner = [name for pos, name in starts if pos < u][-1]
-        assert owner == "k_final", f"a.labels used in {owner}"
-    lines = src.splitlines()
-    for i, line in enumerate(lines):
-        if re.search(r"\ba\.labels\s*\[", line):                     # an access: guarded on this line or by the enclosing `if (a.labels)`
-            ctx = " ".join(lines[max(0, i - 2): i + 1])
-            assert re.search(r"if\s*\(\s*a\.labels\b", ctx), f"cluster.hip:{i + 1}: unguarded access to the labels plane"
+    csrc = os.path.join(ROOT, "moving_object_detector_amd", "csrc")
+    names = ["cluster_common.h", "ccl_tile.hip", "ccl_bits.hip", "ccl_merge.hip", "cluster_final.hip", "cluster_median.hip"]
+    found = sorted(n for n in os.listdir(csrc) if n.startswith(("cluster", "ccl_")))
+    assert found == sorted(names), f"the clusterer's sources are {found}"         # (one file for all stages is gone: nothing left unscanned)
+    total = 0
+    for name in names:
+        src = open(os.path.join(csrc, name)).read()
+        starts = [(m.start(), m.group(1)) for m in re.finditer(r"__global__[^\n]*\bvoid\s+(\w+)\s*\(", src)]
+        uses = [m.start() for m in re.finditer(r"\ba\.labels\b", src)]
+        total += len(uses)
+        for u in uses:
+            owner = ([k for pos, k in starts if pos < u] or ["no kernel"])[-1]
+            assert owner == "k_final", f"{name}: a.labels used in {owner}"
+        lines = src.splitlines()
+        for i, line in enumerate(lines):
+            if re.search(r"\ba\.labels\s*\[", line):                 # an access: guarded on this line or by the enclosing `if (a.labels)`
+                ctx = " ".join(lines[max(0, i - 2): i + 1])
+                assert re.search(r"if\s*\(\s*a\.labels\b", ctx), f"{name}:{i + 1}: unguarded access to the labels plane"
+    assert total, "k_final is expected to write the labels plane"
 
 
 def test_product_library_has_no_hidden_switches_or_experiment_kernels():

@@ -158,7 +158,7 @@ def test_scratch_is_left_clean_across_calls_of_different_shape(oracle):
 
 def test_size_filter_inside_the_merge_kernel_and_as_a_kernel_of_its_own_agree():
     """Batches of up to 16 frames run the size filter in k_ccl_merge's last workgroup per frame, larger ones as k_select behind it
-    (cluster.hip kFusedFilterFrames): 16 and 17 frames of one stream, the fused call and the clusterer alone, against one-frame calls."""
+    (ccl_merge.hip kFusedFilterFrames): 16 and 17 frames of one stream, the fused call and the clusterer alone, against one-frame calls."""
     from moving_object_detector_amd import synth
     W, H, F = 320, 240, 17
     cam, sq = _stream(W, H, F, seed=5)
