@@ -190,8 +190,9 @@ def score(cam, corr, hyps, prm: EgoParams):
     return np.array([-1 if hp is None else int(inliers(k, hp[0], hp[1], corr["P"], corr["O"], th).sum()) for hp in hyps], np.int64)
 
 
-def _terms(k, R, t, P, O):
-    """Per correspondence: the 21 upper entries of J^T J (row-major), the 6 of J^T r, r^T r — (n, 28)."""
+def jacobians(k, R, t, P, O):
+    """Per correspondence: the residuals ru, rv, rr and their derivatives Ju, Jv, Jr (6 arrays each) with respect to the left
+    perturbation (w, tau) of the motion, R <- exp([w]x) R, t <- exp([w]x) t + tau, at (w, tau) = 0."""
     X, Y, Z, a, b, ru, rv, rr = residuals(k, R, t, P, O)
     iz = 1.0 / Z
     ux = k["fx"] * iz
@@ -203,6 +204,12 @@ def _terms(k, R, t, P, O):
     Ju = [gu * Y, ux * Z - gu * X, -(ux * Y), ux, zero, gu]
     Jv = [gv * Y - vy * Z, -(gv * X), vy * X, zero, vy, gv]
     Jr = [gr * Y, ux * Z - gr * X, -(ux * Y), ux, zero, gr]
+    return ru, rv, rr, Ju, Jv, Jr
+
+
+def _terms(k, R, t, P, O):
+    """Per correspondence: the 21 upper entries of J^T J (row-major), the 6 of J^T r, r^T r — (n, 28)."""
+    ru, rv, rr, Ju, Jv, Jr = jacobians(k, R, t, P, O)
     cols = []
     for i in range(6):
         for j in range(i, 6):

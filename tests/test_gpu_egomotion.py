@@ -1,7 +1,8 @@
 """GPU: the on-GPU stereo ego-motion estimator (csrc/egomotion.hip) — bit for bit against the numpy restatement
-(tests/models/ego_model.py) on the correspondence list, every hypothesis's inlier count and the chosen hypothesis; batches against
-single frames, repeats and the host form; accuracy on synth.make_frame; the scene flow and clusters it feeds; the odometry stream
-(mod_submit_odometry_host) against the images stream fed its transforms; failure and argument codes."""
+(tests/models/ego_model.py) on the correspondence list, every hypothesis's inlier count, the chosen hypothesis, every ModEgoResult
+field (rms_px included) and the transform's bits; batches against single frames, repeats and the host form; accuracy on
+synth.make_frame; the scene flow and clusters it feeds; the odometry stream (mod_submit_odometry_host) against the images stream fed
+its transforms; failure and argument codes.  Edge cases: test_gpu_egomotion_edges.py."""
 import ctypes as C
 import os
 import sys
@@ -12,12 +13,10 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, os.path.join(HERE, "models"))
 sys.path.insert(0, HERE)
 import ego_model as em  # noqa: E402
-
-CHECKED = os.path.join(ROOT, "moving_object_detector_amd", "libmod_sf_checked.so")
+from util import CHECKED_LIB as CHECKED, EgoChecked, bits_equal64  # noqa: E402
 
 
 def _frames(W, H, F, seed):
@@ -45,48 +44,6 @@ def _dev(ctx, frs):
             torch.from_numpy(np.stack([f.flow for f in frs])).to(d))
 
 
-class _Checked:
-    """A context of the diagnostic build, which can read the estimator's scratch (mod_debug_read 5, 6, 7)."""
-
-    def __init__(self, W, H, F, cam):
-        from moving_object_detector_amd import capi, synth
-        import moving_object_detector_amd.pipeline  # noqa: F401  (torch first: one HIP runtime)
-        L = C.CDLL(CHECKED)
-        vp = C.c_void_p
-        L.mod_create.argtypes = [C.POINTER(capi.ModConfig), C.POINTER(vp)]
-        L.mod_destroy.argtypes = [vp]
-        L.mod_destroy.restype = None
-        L.mod_set_camera.argtypes = [vp, C.POINTER(capi.ModCamera)]
-        L.mod_set_params.argtypes = [vp, C.POINTER(capi.ModParams)]
-        L.mod_egomotion_dev.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.ModEgoParams), vp, vp]
-        L.mod_synchronize.argtypes = [vp]
-        L.mod_debug_read.argtypes = [vp, C.c_int, vp, C.c_ulonglong]
-        self.L, self.h = L, C.c_void_p()
-        assert L.mod_create(C.byref(capi.ModConfig(0, W, H, F, 0, 0, None)), C.byref(self.h)) == 0
-        assert L.mod_set_camera(self.h, C.byref(capi.camera_struct(cam))) == 0
-        assert L.mod_set_params(self.h, C.byref(capi.params_struct(synth.Params()))) == 0
-        self.W, self.H, self.F = W, H, F
-
-    def run(self, dp, dn, fl, prm):
-        F = dn.shape[0]
-        tf = torch.empty((F, 7), dtype=torch.float64, device=dn.device)
-        res = torch.empty((F, 24), dtype=torch.uint8, device=dn.device)
-        assert self.L.mod_egomotion_dev(self.h, F, dp.data_ptr(), dn.data_ptr(), fl.data_ptr(), C.byref(prm), tf.data_ptr(), res.data_ptr()) == 0
-        assert self.L.mod_synchronize(self.h) == 0
-        cap = -(-self.W // prm.stride) * -(-self.H // prm.stride)
-        n = np.zeros(self.F, np.int32)
-        corr = np.zeros((self.F, 9, cap), np.float64)
-        cnt = np.zeros(F * prm.hypotheses, np.int32)          # [frames][hypotheses] of this call
-        for which, a in ((5, n), (6, corr), (7, cnt)):
-            assert self.L.mod_debug_read(self.h, which, a.ctypes.data, a.nbytes) == 0
-        cnt = cnt.reshape(F, prm.hypotheses)
-        from moving_object_detector_amd.pipeline import EGO_RESULT_DTYPE
-        return tf.cpu().numpy(), np.frombuffer(res.cpu().numpy().tobytes(), dtype=EGO_RESULT_DTYPE), n, corr, cnt
-
-    def close(self):
-        self.L.mod_destroy(self.h)
-
-
 @pytest.mark.parametrize("W,H,F,strides,hyps", [(320, 240, 1, (8, 4, 2), (1, 64, 256)), (320, 240, 3, (8, 4, 2), (256, 1, 64)),
                                                  (1280, 720, 1, (8, 4), (64, 256)), (1280, 720, 3, (8, 4, 2), (256, 1, 64))])
 def test_gpu_matches_the_model_bit_for_bit(W, H, F, strides, hyps):
@@ -94,7 +51,7 @@ def test_gpu_matches_the_model_bit_for_bit(W, H, F, strides, hyps):
     if not os.path.exists(CHECKED):
         pytest.fail("the diagnostic build libmod_sf_checked.so is missing (build() makes it)")
     cam, frs = _frames(W, H, F, seed=11 * F + W)
-    ck = _Checked(W, H, F, cam)
+    ck = EgoChecked(W, H, F, cam)
     dp, dn, fl = _dev(None, frs)
     for s in strides:                                   # descending: the scratch grows on the way
         for hn in hyps:
@@ -111,9 +68,10 @@ def test_gpu_matches_the_model_bit_for_bit(W, H, F, strides, hyps):
                 best = int(np.argmax(cnt[f, :hn]))
                 assert best == m["best"] and cnt[f, best] == m["counts"][m["best"]]
                 assert res["status"][f] == m["status"] and res["inliers"][f] == m["inliers"] and res["iterations"][f] == m["iterations"], (s, hn, f)
-                if m["status"] == em.OK:
-                    assert np.abs(tf[f] - m["transform"]).max() <= 1e-6, (s, hn, f, tf[f], m["transform"])
-                else:
+                assert res["correspondences"][f] == m["correspondences"], (s, hn, f)
+                assert bits_equal64(tf[f], m["transform"]), (s, hn, f, tf[f].tolist(), m["transform"].tolist())
+                assert bits_equal64(res["rms_px"][f], m["rms"]), (s, hn, f, float(res["rms_px"][f]), m["rms"])
+                if m["status"] != em.OK:
                     assert np.isnan(tf[f]).all()
     ck.close()
 

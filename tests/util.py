@@ -1,7 +1,70 @@
 """Shared helpers for the parity tests."""
+import ctypes as C
+import os
+
 import numpy as np
 
 PLANES = ("x", "y", "z", "vx", "vy", "vz")
+CHECKED_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "moving_object_detector_amd", "libmod_sf_checked.so")
+
+
+class EgoChecked:
+    """A context of the diagnostic build, which can read the ego-motion estimator's scratch (mod_debug_read 5, 6, 7).  The library
+    lays the correspondences out as [max_frames][9][cap] with cap the grid size of the smallest stride this context has seen
+    (ensure_ego_scratch), so the reads use that stride, not the call's."""
+
+    def __init__(self, W, H, F, cam):
+        from moving_object_detector_amd import capi, synth
+        import moving_object_detector_amd.pipeline  # noqa: F401  (torch first: one HIP runtime)
+        L = C.CDLL(CHECKED_LIB)
+        vp = C.c_void_p
+        L.mod_create.argtypes = [C.POINTER(capi.ModConfig), C.POINTER(vp)]
+        L.mod_destroy.argtypes = [vp]
+        L.mod_destroy.restype = None
+        L.mod_set_camera.argtypes = [vp, C.POINTER(capi.ModCamera)]
+        L.mod_set_params.argtypes = [vp, C.POINTER(capi.ModParams)]
+        L.mod_egomotion_dev.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.ModEgoParams), vp, vp]
+        L.mod_egomotion_host.argtypes = [vp, vp, vp, vp, C.POINTER(capi.ModEgoParams), C.POINTER(capi.ModTransform), C.POINTER(capi.ModEgoResult)]
+        L.mod_synchronize.argtypes = [vp]
+        L.mod_debug_read.argtypes = [vp, C.c_int, vp, C.c_ulonglong]
+        self.L, self.h = L, C.c_void_p()
+        assert L.mod_create(C.byref(capi.ModConfig(0, W, H, F, 0, 0, None)), C.byref(self.h)) == 0
+        assert L.mod_set_camera(self.h, C.byref(capi.camera_struct(cam))) == 0
+        assert L.mod_set_params(self.h, C.byref(capi.params_struct(synth.Params()))) == 0
+        self.W, self.H, self.F = W, H, F
+        self.min_stride = None
+
+    def run(self, dp, dn, fl, prm):
+        """One mod_egomotion_dev call on device tensors -> transforms (F, 7), results (EGO_RESULT_DTYPE), correspondence counts
+        [max_frames], correspondences [max_frames][9][cap], hypothesis counts [F][hypotheses]."""
+        import torch
+        from moving_object_detector_amd.pipeline import EGO_RESULT_DTYPE
+        F = dn.shape[0]
+        tf = torch.empty((F, 7), dtype=torch.float64, device=dn.device)
+        res = torch.empty((F, 24), dtype=torch.uint8, device=dn.device)
+        assert self.L.mod_egomotion_dev(self.h, F, dp.data_ptr(), dn.data_ptr(), fl.data_ptr(), C.byref(prm), tf.data_ptr(), res.data_ptr()) == 0
+        assert self.L.mod_synchronize(self.h) == 0
+        self.min_stride = prm.stride if self.min_stride is None else min(self.min_stride, prm.stride)
+        s = self.min_stride
+        cap = -(-self.W // s) * -(-self.H // s)
+        n = np.zeros(self.F, np.int32)
+        corr = np.zeros((self.F, 9, cap), np.float64)
+        cnt = np.zeros(F * prm.hypotheses, np.int32)          # [frames][hypotheses] of this call
+        for which, a in ((5, n), (6, corr), (7, cnt)):
+            assert self.L.mod_debug_read(self.h, which, a.ctypes.data, a.nbytes) == 0
+        cnt = cnt.reshape(F, prm.hypotheses)
+        return tf.cpu().numpy(), np.frombuffer(res.cpu().numpy().tobytes(), dtype=EGO_RESULT_DTYPE), n, corr, cnt
+
+    def host(self, d_prev, d_now, flow, prm):
+        """mod_egomotion_host of one frame of host arrays -> return code, ModTransform bytes, ModEgoResult bytes."""
+        from moving_object_detector_amd import capi
+        ht, hr = capi.ModTransform(), capi.ModEgoResult()
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (d_prev, d_now, flow)]
+        rc = self.L.mod_egomotion_host(self.h, *[a.ctypes.data for a in arrs], C.byref(prm), C.byref(ht), C.byref(hr))
+        return rc, bytes(ht), bytes(hr)
+
+    def close(self):
+        self.L.mod_destroy(self.h)
 
 
 def bits_equal(a, b):
@@ -15,6 +78,31 @@ def bits_equal(a, b):
     if not np.array_equal(na, nb):
         return False
     return np.array_equal(a.view(np.uint32)[~na], b.view(np.uint32)[~nb])
+
+
+def bits_equal64(a, b):
+    """bits_equal for f64: the same bits everywhere, NaN == NaN by position."""
+    a = np.ascontiguousarray(a, np.float64)
+    b = np.ascontiguousarray(b, np.float64)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return np.array_equal(na, nb) and np.array_equal(a.view(np.uint64)[~na], b.view(np.uint64)[~nb])
+
+
+def assert_ego_frame(tf, res, n, corr, cnt, m, where):
+    """One frame of EgoChecked.run (transform (7,), result record, correspondence count, correspondences [9][cap], hypothesis counts)
+    against ego_model.estimate's dict m, bit for bit: the correspondence list, every hypothesis's inlier count, every ModEgoResult field
+    (rms_px included) and the transform."""
+    k = len(m["corr"]["pix"])
+    assert n == k == res["correspondences"], (where, n, k, res["correspondences"])
+    want = np.concatenate([m["corr"]["P"].T, m["corr"]["Q"].T, m["corr"]["O"].T])
+    assert bits_equal64(corr[:, :k], want), (where, "correspondences")
+    assert np.array_equal(cnt, m["counts"]), (where, "hypothesis counts", np.flatnonzero(cnt != m["counts"])[:8])
+    got = (int(res["status"]), int(res["inliers"]), int(res["iterations"]))
+    assert got == (m["status"], m["inliers"], m["iterations"]), (where, "status, inliers, iterations", got, m["status"], m["inliers"], m["iterations"])
+    assert bits_equal64(res["rms_px"], m["rms"]), (where, "rms", float(res["rms_px"]), m["rms"])
+    assert bits_equal64(tf, m["transform"]), (where, "transform", tf.tolist(), m["transform"].tolist())
 
 
 def first_mismatch(a, b):
