@@ -223,6 +223,17 @@ int  mod_sgm_compute_dev(ModContext *ctx, int32_t frames, const uint8_t *left, c
                          float *disparity);
 /* the same for one frame in host memory (what a ROS node holding sensor_msgs/Image buffers calls); synchronous */
 int  mod_sgm_compute_host(ModContext *ctx, const uint8_t *left, const uint8_t *right, const ModSgmParams *params, float *disparity);
+/* Sub-pixel disparity, opt-in: context state like the image layout, read when a call or a submit enqueues its estimator —
+ * mod_sgm_compute_dev / _host, mod_submit_stereo_host, mod_submit_images_host, mod_submit_odometry_host; a frame in flight
+ * completes with the setting of its own submit.  fraction_bits 0 (the default): whole disparities, as ever.  4: sixteenths of a
+ * pixel — with S the summed path costs and d their first minimum, q = floor((16 num + den) / (2 den)), num = S(d-1) - S(d+1),
+ * den = S(d-1) - 2 S(d) + S(d+1), for 1 <= d <= disparities - 2 (else 0; den >= 1 and |q| <= 8 because d is the FIRST minimum);
+ * v = 16 d + q; the median runs on v; the left-right check on the nearest integer (v + 8) >> 4 against the (integer) right map;
+ * the pixel is v / 16, exact in float, still inside [0, disparities - 1], or -1.  Integer arithmetic throughout:
+ * tests/models/sgm_subpixel_model.py restates it bit for bit.  Any other value: MOD_ERR_INVALID_ARGUMENT. */
+#define MOD_SGM_FRACTION_BITS 4
+int  mod_set_disparity_subpixel(ModContext *ctx, int32_t fraction_bits);
+int  mod_get_disparity_subpixel(const ModContext *ctx, int32_t *fraction_bits);
 /* stages, for tests and tracing: centre-symmetric census (31 bits per pixel, 0 where the window leaves the image) ... */
 int  mod_sgm_census_dev(ModContext *ctx, int32_t frames, const uint8_t *image, uint32_t *census);
 /* ... and one aggregation path L_r [frames][H][W][disparities] uint8 over the Hamming cost of the census words; direction 0..7 =

@@ -32,6 +32,7 @@ MOD_PER_KERNEL_CLUSTER_STAGES = (1, 2, 3, 4, 5)
 MOD_PIPELINE_DEPTH = 3
 MOD_EGO_OK, MOD_EGO_FEW_POINTS, MOD_EGO_FEW_INLIERS, MOD_EGO_DIVERGED = 0, 1, 2, 3
 MOD_EGO_MAX_HYPOTHESES = 4096
+MOD_SGM_FRACTION_BITS = 4
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
 ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
              "rgba8": MOD_ENCODING_RGBA8}
@@ -51,6 +52,7 @@ EXPORTS = [
     "mod_flow_compute_dev", "mod_flow_compute_host", "mod_submit_images_host",
     "mod_egomotion_dev", "mod_egomotion_host", "mod_submit_odometry_host",
     "mod_set_image_layout", "mod_get_image_layout", "mod_image_to_mono_dev",
+    "mod_set_disparity_subpixel", "mod_get_disparity_subpixel",
 ]
 
 
@@ -207,6 +209,8 @@ def load(require_torch_first: bool = True):
     L.mod_set_image_layout.argtypes = [vp, C.POINTER(ModImageLayout)]
     L.mod_get_image_layout.argtypes = [vp, C.POINTER(ModImageLayout)]
     L.mod_image_to_mono_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), vp]
+    L.mod_set_disparity_subpixel.argtypes = [vp, i32]
+    L.mod_get_disparity_subpixel.argtypes = [vp, C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

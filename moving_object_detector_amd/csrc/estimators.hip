@@ -24,7 +24,7 @@ constexpr int kSgmPaths = 8;
 constexpr int kSgmGroup = 8;                             // frames per group (4 .. 16 measured in round 3: 8 is the knee)
 constexpr size_t kSgmVolumeBudget = (size_t)24 << 30;    // bytes of cost volumes a context may hold
 
-static int ensure_sgm_scratch(ModContext *c, int D, int frames, int *group) {
+static int ensure_sgm_scratch(ModContext *c, int D, int frames, bool subpixel, int *group) {
   Buffers &b = c->b;
   const size_t N = c->maxN;
   const int even = (frames + kSgmGroup - 1) / kSgmGroup;          // groups of equal size: 11 frames go as 6 + 5, not 8 + 3
@@ -40,18 +40,27 @@ static int ensure_sgm_scratch(ModContext *c, int D, int frames, int *group) {
     // round 3 and changed nothing: plain non-blocking side streams)
     for (int i = 0; i < 8; i++) HIP_TRY(c, hipStreamCreateWithFlags(b.sgm_side[i].put(), hipStreamNonBlocking));
   }
-  if (b.sgm_S && b.sgm_D >= D && b.sgm_G >= g) return MOD_OK;
+  const bool volumes_fit = b.sgm_S && b.sgm_D >= D && b.sgm_G >= g;
+  if (volumes_fit && (b.sgm_maps16 || !subpixel)) return MOD_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (volumes_fit) {                                   // the first sub-pixel call of a context that has its volumes: only the maps grow
+    DevPtr<uint8_t> maps;                              // the old maps stay until the new ones exist: a failed allocation changes nothing
+    HIP_TRY(c, dalloc(maps, 6 * c->maxN * (size_t)b.sgm_G));
+    b.sgm_maps = std::move(maps);                      // (swaps: the old buffer is released with `maps`)
+    b.sgm_maps16 = true;
+    return MOD_OK;
+  }
   // grow-only in BOTH dimensions: calls that alternate between (few disparities, large group) and (many, small) settle on the
   // maxima after one reallocation each instead of freeing and allocating gigabytes on every call
   const int D2 = std::max(D, b.sgm_D), g2 = std::max(g, b.sgm_G);
-  b.sgm_S.reset(); b.sgm_census.reset(); b.sgm_maps.reset(); b.sgm_D = 0; b.sgm_G = 0;
+  const bool maps16 = subpixel || b.sgm_maps16;         // ... and in the width of the left maps (sub-pixel mode: 16-bit, 6 N bytes per frame)
+  b.sgm_S.reset(); b.sgm_census.reset(); b.sgm_maps.reset(); b.sgm_D = 0; b.sgm_G = 0; b.sgm_maps16 = false;
   // two sets (see mod_sgm_compute_dev) behind 128 words of lead: the D == 128 path kernels read up to 127 words to the left of a
   // right census plane unconditionally (discarded: disparities that do not exist) — inside the allocation even for tiny images
   HIP_TRY(c, dalloc(b.sgm_census, 2 * 2 * N * g2 + 128));
-  HIP_TRY(c, dalloc(b.sgm_maps, 4 * N * g2));
+  HIP_TRY(c, dalloc(b.sgm_maps, (maps16 ? 6 : 4) * N * g2));
   HIP_TRY(c, dalloc(b.sgm_S, 2 * N * (size_t)D2 * g2 * kSgmPaths));
-  b.sgm_D = D2; b.sgm_G = g2;
+  b.sgm_D = D2; b.sgm_G = g2; b.sgm_maps16 = maps16;
   return MOD_OK;
 }
 
@@ -194,7 +203,8 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity plane");
   if ((rc = check_sgm_params(c, p))) return rc;
   int group = 1;
-  if ((rc = ensure_sgm_scratch(c, p->disparities, frames, &group))) return rc;
+  const bool subpixel = c->sgm_fraction_bits != 0;       // the setting of THIS call: every kernel below is enqueued before it returns
+  if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
   const int W = c->dc.W, H = c->dc.H, D = p->disparities;
   const size_t N = (size_t)W * H;
   Buffers &b = c->b;
@@ -206,6 +216,11 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   const int ngroups = (frames + group - 1) / group;
   const size_t set_census = 2 * N * group, set_volumes = N * (size_t)D * group * kSgmPaths;
   uint8_t *dl = b.sgm_maps, *dr = dl + N * group, *dlm = dr + N * group, *drm = dlm + N * group;
+  uint16_t *dl16 = nullptr, *dlm16 = nullptr;
+  if (subpixel) {                                        // 16-bit left maps first (2 N bytes per frame each), then the two right maps
+    dl16 = reinterpret_cast<uint16_t *>(b.sgm_maps.get()); dlm16 = dl16 + N * group;
+    dr = b.sgm_maps + 4 * N * group; drm = dr + N * group;
+  }
   bool all_in_one[2] = {false, false};
   auto start = [&](int k) -> int {
     const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
@@ -235,7 +250,7 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
     // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
     for (int i = 0; i < (all_in_one[s] ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, b.sgm_join[s][i], 0));
     launch_sgm_finish(W, H, g, D, p->paths, N * (size_t)D * g, p->median, p->lr_check, b.sgm_S + s * set_volumes, dl, dr, dlm, drm,
-                      disparity + (size_t)f0 * N, c->stream);
+                      dl16, dlm16, disparity + (size_t)f0 * N, c->stream);
     return MOD_OK;
   };
   if ((rc = start(0))) return rc;
@@ -244,6 +259,20 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
     if ((rc = finish(k))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_set_disparity_subpixel(ModContext *c, int32_t fraction_bits) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (fraction_bits != 0 && fraction_bits != MOD_SGM_FRACTION_BITS)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fraction_bits must be 0 (off) or 4 (sixteenths of a pixel)");
+  c->sgm_fraction_bits = fraction_bits;
+  return MOD_OK;
+}
+
+int mod_get_disparity_subpixel(const ModContext *c, int32_t *fraction_bits) {
+  if (!c || !fraction_bits) return MOD_ERR_INVALID_ARGUMENT;
+  *fraction_bits = c->sgm_fraction_bits;
   return MOD_OK;
 }
 

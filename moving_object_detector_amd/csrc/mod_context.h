@@ -63,7 +63,8 @@ struct Buffers {
   DevPtr<ModObject> h_objects;
   // on-GPU disparity (allocated on first use)
   DevPtr<uint32_t> sgm_census;
-  DevPtr<uint8_t> sgm_maps;
+  DevPtr<uint8_t> sgm_maps;                 // winner-take-all maps of a group and their medians: left, right; 8-bit (4 N bytes per frame) ...
+  bool sgm_maps16 = false;                  // ... or sized for the sub-pixel mode's 16-bit left maps (6 N): grow-only, like the volumes
   DevPtr<uint8_t> sgm_S;                    // [paths][group][H][W][D] path cost volumes
   int sgm_D = 0, sgm_G = 0;                 // disparities / frames per group the scratch is sized for
   // the aggregation paths are independent of each other: they run side by side on these streams (forked from / joined to the
@@ -95,6 +96,7 @@ struct ModContext {
   bool has_cam = false, has_prm = false;
   ModImageLayout layout{};                  // of the host images (mod_set_image_layout) ...
   bool has_layout = false;                  // ... or, while false, mono8 packed at the camera's size
+  int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};

@@ -403,8 +403,25 @@ __global__ __launch_bounds__(64) void k_sgm_paths_all(int W, int H, int P1, int 
 //   right disparity of x': first minimum of S(x' + d, d), x' + d < W -> the pixel x contributes its S(x, d) to x' = x - d with an LDS
 //                          atomicMin on the same keys (one row of keys in LDS): the cost volume is read ONCE, coalesced, instead of
 //                          gathering a diagonal per pixel
+//
+// SUB (the sub-pixel mode, mod_set_disparity_subpixel): the left map holds v = 16 d + q, q the vertex of the parabola through
+// S(x, d - 1), S(x, d), S(x, d + 1) in sixteenths (sgm_fraction).  The keys, the reduction and the right map are those of the
+// integer kernel; the winner's neighbours may live in the adjacent lane, so every lane fetches its two outer neighbours with one DPP
+// shift each way while all 64 lanes are active, and the ONE lane that owns the winner computes the fraction — one division per
+// pixel, after the reduction — and stores the pixel.
+//
+// q = floor((16 num + den) / (2 den)), num = cm - cp, den = cm - 2 c0 + cp, for 1 <= d <= D - 2, else 0.  d is the FIRST minimum:
+// cm > c0 <= cp, hence den >= 1 and |num| <= den: -8 <= q <= 8, and 16 num + 17 den >= 1 — the truncating unsigned division of
+// that, minus 8, is the floor (the intermediate 16 * (cm - cp) may wrap; the sum does not).
+__device__ __forceinline__ uint32_t sgm_fraction(uint32_t cm, uint32_t c0, uint32_t cp, uint32_t d, int D) {
+  if (d < 1u || d + 2u > (uint32_t)D) return 16u * d;
+  const uint32_t den = cm - 2u * c0 + cp;
+  return 16u * d + (16u * (cm - cp) + 17u * den) / (2u * den) - 8u;
+}
+
+template <bool SUB, class TL>
 __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
-                                                 uint8_t *__restrict__ dl, uint8_t *__restrict__ dr) {
+                                                 TL *__restrict__ dl, uint8_t *__restrict__ dr) {
   extern __shared__ uint32_t rkey[];                 // [W]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, y = blockIdx.x, f = blockIdx.y;
   const size_t plane = (size_t)f * W * H;
@@ -424,7 +441,15 @@ __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths,
     }
     const uint32_t k0 = d0 < D ? ((s0 << 8) | (uint32_t)d0) : 0xffffffffu, k1 = d1 < D ? ((s1 << 8) | (uint32_t)d1) : 0xffffffffu;
     const uint32_t kl = wave_min_u32(min(k0, k1));
-    if (lane == 0) dl[(size_t)y * W + x] = (uint8_t)(kl & 255u);
+    if constexpr (!SUB) {
+      if (lane == 0) dl[(size_t)y * W + x] = (uint8_t)(kl & 255u);
+    } else {
+      // S(x, d0 - 1), S(x, d1 + 1): the neighbouring lanes' sums (all 64 lanes are active here)
+      const uint32_t below = MOD_DPP(s1, 0x138), above = MOD_DPP(s0, 0x130);   // wave_shr:1, wave_shl:1
+      const uint32_t d = kl & 255u;
+      if ((uint32_t)lane == (d >> 1))                // the lane that owns the winner
+        dl[(size_t)y * W + x] = (TL)((d & 1u) ? sgm_fraction(s0, kl >> 8, above, d, D) : sgm_fraction(below, kl >> 8, s1, d, D));
+    }
     if (d0 < D && x - d0 >= 0) atomicMin(&rkey[x - d0], k0);
     if (d1 < D && x - d1 >= 0) atomicMin(&rkey[x - d1], k1);
   }
@@ -435,8 +460,12 @@ __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths,
 // The same for disparity counts that are multiples of 16 (the default 128 is): lane = (pixel of the wave's group of 8, 16 consecutive
 // disparities) — one 16-byte load per path and lane, a wave reads 1 KB contiguous per path; the path costs are summed as packed pairs
 // of 16-bit numbers (sums stay below 8 x 128), the minimum over a pixel's 8 lanes is three DPP steps.
+// SUB: as above.  After the butterfly all 8 lanes of the pixel hold the winning key; lane d / 16 owns the winner and finds its two
+// neighbours among its own 16 sums or, for the first / last of them, in the sum the adjacent lane passed over (row_shr:1 /
+// row_shl:1 before the reduction; the lane across a pixel boundary is only ever asked for d = 0 or d = D - 1, which have no fraction).
+template <bool SUB, class TL>
 __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
-                                                   uint8_t *__restrict__ dl, uint8_t *__restrict__ dr) {
+                                                   TL *__restrict__ dl, uint8_t *__restrict__ dr) {
   extern __shared__ uint32_t rkey[];                 // [W]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, y = blockIdx.x, f = blockIdx.y;
   const size_t plane = (size_t)f * W * H;
@@ -461,6 +490,8 @@ __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int path
         e[3] += w.w & 0x00ff00ffu; o[3] += (w.w >> 8) & 0x00ff00ffu;
       }
     }
+    uint32_t edge_lo = 0, edge_hi = 0;               // S(x, dbase - 1), S(x, dbase + 16) (all 64 lanes active)
+    if constexpr (SUB) { edge_lo = MOD_DPP(o[3], 0x111) >> 16; edge_hi = MOD_DPP(e[0], 0x101) & 0xffffu; }   // row_shr:1, row_shl:1
     uint32_t best = 0xffffffffu;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -480,15 +511,31 @@ __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int path
     t = MOD_DPP(best, 0xB1); best = min(best, t);
     t = MOD_DPP(best, 0x4E); best = min(best, t);
     t = MOD_DPP(best, 0x141); best = min(best, t);
-    if (sub == 0 && x < W) dl[(size_t)y * W + x] = (uint8_t)(best & 255u);
+    if constexpr (!SUB) {
+      if (sub == 0 && x < W) dl[(size_t)y * W + x] = (uint8_t)(best & 255u);
+    } else {
+      const uint32_t d = best & 255u;
+      if ((d >> 4) == (uint32_t)sub && x < W) {      // the lane that owns the winner (a dead pixel's key names disparity 255: nobody)
+        // sum i = d % 16 sits in word j = i / 4 at place k = i % 4: e[j] low, o[j] low, e[j] high, o[j] high
+        const uint32_t j = (d >> 2) & 3u, k = d & 3u;
+        const uint32_t ej = j == 0 ? e[0] : j == 1 ? e[1] : j == 2 ? e[2] : e[3], oj = j == 0 ? o[0] : j == 1 ? o[1] : j == 2 ? o[2] : o[3];
+        const uint32_t before = j == 0 ? edge_lo : (j == 1 ? o[0] : j == 2 ? o[1] : o[2]) >> 16;         // the sum in front of word j
+        const uint32_t after = j == 3 ? edge_hi : (j == 0 ? e[1] : j == 1 ? e[2] : e[3]) & 0xffffu;      // the sum behind it
+        const uint32_t cm = k == 0 ? before : k == 1 ? (ej & 0xffffu) : k == 2 ? (oj & 0xffffu) : (ej >> 16);
+        const uint32_t cp = k == 0 ? (oj & 0xffffu) : k == 1 ? (ej >> 16) : k == 2 ? (oj >> 16) : after;
+        dl[(size_t)y * W + x] = (TL)sgm_fraction(cm, best >> 8, cp, d, D);
+      }
+    }
   }
   __syncthreads();
   for (int i = threadIdx.x; i < W; i += 256) dr[(size_t)y * W + i] = (uint8_t)(rkey[i] & 255u);
 }
 
-// 3 x 3 median of a uint8 map (border pixels keep their value): exact 9-element selection network
+// 3 x 3 median of a uint8 map, or of the sub-pixel mode's uint16 left map (border pixels keep their value): exact 9-element
+// selection network
 __device__ __forceinline__ void srt(int &a, int &b) { const int t = min(a, b); b = max(a, b); a = t; }
-__global__ __launch_bounds__(256) void k_sgm_median3(int W, int H, const uint8_t *__restrict__ in, uint8_t *__restrict__ out) {
+template <class T>
+__global__ __launch_bounds__(256) void k_sgm_median3(int W, int H, const T *__restrict__ in, T *__restrict__ out) {
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
   if (x >= W || y >= H) return;
   in += (size_t)blockIdx.z * W * H; out += (size_t)blockIdx.z * W * H;
@@ -497,7 +544,7 @@ __global__ __launch_bounds__(256) void k_sgm_median3(int W, int H, const uint8_t
   int v0 = in[p - W - 1], v1 = in[p - W], v2 = in[p - W + 1], v3 = in[p - 1], v4 = in[p], v5 = in[p + 1], v6 = in[p + W - 1], v7 = in[p + W], v8 = in[p + W + 1];
   srt(v1, v2); srt(v4, v5); srt(v7, v8); srt(v0, v1); srt(v3, v4); srt(v6, v7); srt(v1, v2); srt(v4, v5); srt(v7, v8);
   srt(v0, v3); srt(v5, v8); srt(v4, v7); srt(v3, v6); srt(v1, v4); srt(v2, v5); srt(v4, v7); srt(v4, v2); srt(v6, v4); srt(v4, v2);
-  out[p] = (uint8_t)v4;
+  out[p] = (T)v4;
 }
 
 // left-right consistency check -> DisparityImage pixels (float, -1 = invalid)
@@ -512,6 +559,19 @@ __global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, cons
   bool ok = true;
   if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
   disp[p] = ok ? (float)d : -1.0f;
+}
+// the same on the sub-pixel mode's left map v = 16 d + q: the check runs on the nearest integer, the pixel leaves as v / 16 (exact)
+__global__ __launch_bounds__(256) void k_sgm_lr_sub(int W, int H, int lr_check, const uint16_t *__restrict__ dl, const uint8_t *__restrict__ dr,
+                                                    float *__restrict__ disp) {
+  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+  if (x >= W || y >= H) return;
+  const size_t plane = (size_t)blockIdx.z * W * H;
+  dl += plane; dr += plane; disp += plane;
+  const size_t p = (size_t)y * W + x;
+  const int v = dl[p], d = (v + 8) >> 4;
+  bool ok = true;
+  if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
+  disp[p] = ok ? (float)v * 0.0625f : -1.0f;
 }
 
 }  // namespace
@@ -581,13 +641,23 @@ bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int p
 }
 
 void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, const uint8_t *Lv,
-                       uint8_t *dl, uint8_t *dr, uint8_t *dlm, uint8_t *drm, float *disparity, hipStream_t s) {
-  if (D % 16 == 0) hipLaunchKernelGGL(k_sgm_wta16, dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl, dr);
-  else hipLaunchKernelGGL(k_sgm_wta, dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl, dr);
+                       uint8_t *dl, uint8_t *dr, uint8_t *dlm, uint8_t *drm, uint16_t *dl16, uint16_t *dlm16, float *disparity, hipStream_t s) {
   const dim3 g((W + 63) / 64, (H + 3) / 4, frames), b(64, 4);
+  if (dl16) {                                          // sub-pixel mode: 16-bit left maps, the right maps as ever
+    if (D % 16 == 0) hipLaunchKernelGGL((k_sgm_wta16<true, uint16_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl16, dr);
+    else hipLaunchKernelGGL((k_sgm_wta<true, uint16_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl16, dr);
+    if (median) {
+      hipLaunchKernelGGL(k_sgm_median3<uint16_t>, g, b, 0, s, W, H, dl16, dlm16);
+      hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dr, drm);
+    }
+    hipLaunchKernelGGL(k_sgm_lr_sub, g, b, 0, s, W, H, lr_check, median ? dlm16 : dl16, median ? drm : dr, disparity);
+    return;
+  }
+  if (D % 16 == 0) hipLaunchKernelGGL((k_sgm_wta16<false, uint8_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl, dr);
+  else hipLaunchKernelGGL((k_sgm_wta<false, uint8_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl, dr);
   if (median) {
-    hipLaunchKernelGGL(k_sgm_median3, g, b, 0, s, W, H, dl, dlm);
-    hipLaunchKernelGGL(k_sgm_median3, g, b, 0, s, W, H, dr, drm);
+    hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dl, dlm);
+    hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dr, drm);
   }
   hipLaunchKernelGGL(k_sgm_lr, g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? drm : dr, disparity);
 }

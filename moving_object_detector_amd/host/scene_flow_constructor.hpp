@@ -62,6 +62,9 @@ class SceneFlowConstructor {
   // the message then points at.  Returns false (and leaves `disparity` alone) when an image is missing or of the wrong size: the
   // reference then resets disparity_now_, i.e. the caller passes a null disparity on.
   void setDisparityParams(const ModSgmParams &p) { sgm_ = p; }
+  // sub-pixel disparity (mod_set_disparity_subpixel: sixteenths of a pixel); off unless asked for.  Frames already submitted keep
+  // the setting of their submit.
+  void setDisparitySubpixel(bool on) { check(mod_set_disparity_subpixel(ctx_, on ? MOD_SGM_FRACTION_BITS : 0)); }
   bool estimateDisparity(const mod_host::Image *left_image, const mod_host::Image *right_image, const mod_host::CameraInfo &left_camera_info,
                          const mod_host::CameraInfo &right_camera_info, mod_host::DisparityImage *disparity, std::vector<float> *pixels) {
     if (!left_image || !right_image || !left_image->data || !right_image->data) return false;

@@ -94,6 +94,17 @@ class Context:
         self._check(self.lib.mod_get_image_layout(self.h, C.byref(s)))
         return s
 
+    def set_disparity_subpixel(self, on) -> None:
+        """Sub-pixel mode of the on-GPU disparity estimator (mod_set_disparity_subpixel): False / 0 = whole disparities (the default),
+        True / 4 = sixteenths of a pixel.  Read when a call or a submit enqueues its estimator."""
+        bits = (capi.MOD_SGM_FRACTION_BITS if on else 0) if isinstance(on, (bool, np.bool_)) else int(on)   # any other number: as given
+        self._check(self.lib.mod_set_disparity_subpixel(self.h, bits))
+
+    def get_disparity_subpixel(self) -> int:
+        bits = C.c_int32(-1)
+        self._check(self.lib.mod_get_disparity_subpixel(self.h, C.byref(bits)))
+        return bits.value
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.lib.mod_destroy(self.h)

@@ -460,6 +460,31 @@ def make_stereo_images(W: int, H: int, seed: int = 0, D: int = 128, n_boxes: int
     return left, right, truth
 
 
+def make_slanted_stereo(W: int, H: int, seed: int = 0, d_top: float = 6.0, d_bottom: float = 22.0):
+    """Stereo pair of ONE textured plane whose disparity runs linearly from d_top (first row) to d_bottom (last row), so every
+    fractional part occurs: left(y, x) = T[y, x], right(y, x) = T[y, x + d(y)] resampled linearly from a lightly smoothed random
+    texture T (the conventions of make_stereo_images).  The texture depends on the seed only: two calls with one seed and
+    different disparities share the left image.  Returns left, right (uint8) and the true left disparity map (float32)."""
+    pad = 130                                              # fixed: the texture must not depend on the disparities
+    if not (0.0 <= d_top <= pad - 2 and 0.0 <= d_bottom <= pad - 2):
+        raise ValueError("disparities must be in 0 .. 128")
+    rng = np.random.Generator(np.random.PCG64([0x51A0000 + seed]))
+    t = rng.integers(0, 256, size=(H, W + pad)).astype(np.float64)
+    k = np.array([1, 2, 1], np.float64) / 4
+    t = np.apply_along_axis(lambda r: np.convolve(r, k, mode="same"), 1, t)
+    t = np.apply_along_axis(lambda c: np.convolve(c, k, mode="same"), 0, t)
+    d = np.linspace(float(d_top), float(d_bottom), H) if H > 1 else np.array([float(d_top)])
+    pos = np.arange(W)[None, :] + d[:, None]
+    i0 = np.floor(pos).astype(np.int64)
+    w = pos - i0
+    rows = np.arange(H)[:, None]
+    right = (1.0 - w) * t[rows, i0] + w * t[rows, i0 + 1]
+    left = t[:, :W]
+    to8 = lambda a: np.clip(np.floor(a + 0.5), 0, 255).astype(np.uint8)
+    truth = np.broadcast_to(d[:, None], (H, W)).astype(np.float32)
+    return to8(left), to8(right), np.ascontiguousarray(truth)
+
+
 def make_box_flow(truth: np.ndarray, shift: float = 24.0) -> np.ndarray:
     """Optical flow (H, W, 2) for a stereo pair of make_stereo_images seen twice by a camera that stands still: zero on the
     background, (-shift, 0) on the boxes (every layer nearer than the background), i.e. a box pixel was `shift` pixels to the

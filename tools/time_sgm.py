@@ -1,16 +1,25 @@
-"""Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.  usage (GPU box): python tools/time_sgm.py [W H [D]]"""
-import ctypes as C, os, sys, time
+"""Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
+usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--reps N]     (--subpixel: mod_set_disparity_subpixel(4))"""
+import argparse, ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 from moving_object_detector_amd import capi, synth
 from moving_object_detector_amd.pipeline import Context
-W, H = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (1280, 720)
-D = int(sys.argv[3]) if len(sys.argv) > 3 else 128
+ap = argparse.ArgumentParser(description=__doc__)
+ap.add_argument("W", type=int, nargs="?", default=1280)
+ap.add_argument("H", type=int, nargs="?", default=720)
+ap.add_argument("D", type=int, nargs="?", default=128)
+ap.add_argument("--subpixel", action="store_true")
+ap.add_argument("--reps", type=int, default=3)
+a = ap.parse_args()
+W, H, D = a.W, a.H, a.D
 F = int(os.environ.get("SGM_F", "16"))
 pairs = [synth.make_stereo_images(W, H, 7 + f, D, n_boxes=5) for f in range(F)]
 ctx = Context(W, H, max_frames=F)
 ctx.set_camera(synth.make_camera(W, H)); ctx.set_params(synth.Params())
+if a.subpixel:
+    ctx.set_disparity_subpixel(True)
 dev = ctx.device
 tl = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev); tr = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
 out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
@@ -20,9 +29,9 @@ for paths in (8, 4):
         assert ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr()) == 0
     ctx.synchronize()
     t0 = time.perf_counter()
-    reps = 3
-    for _ in range(reps):
+    for _ in range(a.reps):
         ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
     ctx.synchronize()
-    ms = 1e3 * (time.perf_counter() - t0) / (reps * F)
-    print(f"{W}x{H} D={D} paths={paths}: {ms:.2f} ms per frame ({1e3 / ms:.0f} frames/s); valid {float((out >= 0).float().mean()):.2f}")
+    ms = 1e3 * (time.perf_counter() - t0) / (a.reps * F)
+    print(f"{W}x{H} D={D} paths={paths} frames={F} subpixel={'on' if a.subpixel else 'off'}: {ms:.3f} ms per frame ({1e3 / ms:.0f} frames/s); "
+          f"valid {float((out >= 0).float().mean()):.2f}")
