@@ -36,6 +36,21 @@ using Stream = Owned<hipStream_t, hipStreamDestroy>;
 // allocates unless p already holds a buffer (lazily built buffer sets can be resumed after a failed attempt without leaking)
 template <class T>
 hipError_t dalloc(DevPtr<T> &p, size_t count) { return p ? hipSuccess : hipMalloc((void **)p.put(), count * sizeof(T)); }
+inline hipError_t make_event(Event &e) { return e ? hipSuccess : hipEventCreateWithFlags(e.put(), hipEventDisableTiming); }
+
+// An event and whether it has been recorded yet: wait() on a fence that never was is no call at all.  A fence stays armed (every
+// later wait() waits again) unless its waiter takes it with wait_once().  record() makes the event where nobody has.
+struct Fence {
+  Event ev;
+  bool armed = false;
+  hipError_t record(hipStream_t s) {
+    hipError_t e = make_event(ev);
+    if (e == hipSuccess && (e = hipEventRecord(ev, s)) == hipSuccess) armed = true;
+    return e;
+  }
+  hipError_t wait(hipStream_t s) const { return armed ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+  hipError_t wait_once(hipStream_t s) { return std::exchange(armed, false) ? hipStreamWaitEvent(s, ev, 0) : hipSuccess; }
+};
 
 struct EventPair { Event a, b; };
 
@@ -56,11 +71,6 @@ struct Buffers {
   DevPtr<int32_t> tilehdr;
   DevPtr<uint32_t> tilelist;
   size_t req_alloc = 0;                     // entries currently allocated for `requests`
-  // one-frame staging for the *_host entry points (allocated on first use)
-  DevPtr<float> h_dnow, h_dprev, h_flow, h_planes;
-  DevPtr<void> h_aos;
-  DevPtr<int32_t> h_labels, h_nobj;
-  DevPtr<ModObject> h_objects;
   // on-GPU disparity (allocated on first use)
   DevPtr<uint32_t> sgm_census;
   DevPtr<uint8_t> sgm_maps;                 // winner-take-all maps of a group and their medians: left, right; 8-bit (4 N bytes per frame) ...
@@ -104,52 +114,69 @@ struct ModContext {
   int max_objects = 0;
   size_t maxN = 0;
   int max_mask_words = 0;
-  // host streaming (mod_submit_frame_host): per-slot device buffers, a ring of MOD_PIPELINE_DEPTH + 1 disparity planes
-  // (frame t's plane is frame t+1's "previous"), two copy streams and the events that order them with the kernels
+  // the device buffers of one host frame: the staging of the synchronous *_host entry points and each slot of the stream have a set
+  struct FrameBuffers {
+    DevPtr<float> dprev, flow, planes;
+    DevPtr<void> aos;
+    DevPtr<int32_t> labels, nobj;
+    DevPtr<ModObject> objects;
+  };
+  // one-frame staging of the synchronous entry points (allocated on first use; ready: the last allocation has succeeded)
+  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; } staging;
+  // host streaming (mod_submit_frame_host and the mod_submit_*_host image entries): a slot per ticket, a ring of MOD_PIPELINE_DEPTH + 1
+  // planes (frame t's plane is frame t+1's "previous"), two copy streams and the events and fences that order them with the kernels
   struct Pipe {
+    struct EgoSlot { ModTransform tf; ModEgoResult res; };
+    // What a ticket owns.  dprev: a caller's previous disparity; flow: copied in or estimated; planes: z, vx, vy, vz (see scene_flow_staged)
+    struct Slot : FrameBuffers {
+      HostPtr<int32_t> h_n;                          // pinned: object count of the slot's frame
+      // pinned: its objects (the count is not known at submit time, and a pageable destination would make the submit wait); collect hands them on
+      HostPtr<ModObject> h_obj;
+      ModObject *user_obj = nullptr;
+      int32_t user_cap = 0;
+      Event ev_in, ev_done, ev_out;                  // inputs on the device (copy stream) / kernels enqueued / results on the host
+      DevPtr<uint8_t> img;                           // image entries: the slot's two 8-bit images (the left one unless one is resident)
+      // ... the estimator has been enqueued behind them (context stream).  A frame that ended at a guard took no ticket, so nobody
+      // waited for its estimator: the next copy into img queues behind it
+      Fence img_read;
+      // colour images (mod_set_image_layout): the slot's two windows as they arrive, W * H * 4 bytes each (allocated on first use);
+      // k_to_mono turns them into grey in img / the plane's left image on the context's stream, behind every older reader of those
+      DevPtr<uint8_t> stage;
+      Fence stage_read;                              // ... the kernels that read them have been enqueued (context stream)
+      // mod_submit_odometry_host: the slot's estimate on the device (its element of Pipe::ego, last copied out before the slot's
+      // previous ticket was collected) and its pinned host copy; collect reads the status
+      EgoSlot *ego = nullptr;
+      HostPtr<EgoSlot> h_ego;
+      bool odo = false;                              // the slot's ticket came from the odometry stream
+      ModTransform *user_tf = nullptr;               // ... and where collect hands the estimate (either may be null)
+      ModEgoResult *user_ego = nullptr;
+    };
+    // What lives one frame longer than its ticket.  A frame that ends at a guard takes a plane but no ticket: the slots would not do.
+    struct RingPlane {
+      DevPtr<float> disparity;
+      // the plane may still be on its way to a caller's `disparity` buffer (result stream) when guard-skipped frames have advanced the
+      // ring back to it: the plane's next writer waits for that copy, once
+      Fence copied_out;
+      DevPtr<uint8_t> left;                          // mod_submit_images_host / _odometry_host: the frame's left image, grey
+      Fence left_read;                               // the last kernel that reads it (this frame's or the next one's) has been enqueued
+    };
+    struct Frame { Slot *s; RingPlane *now, *prev; };   // a frame's place in the pipe: its slot, the plane it fills, the plane before
     bool ready = false;
     Stream h2d, d2h;
-    DevPtr<float> dnow[MOD_PIPELINE_DEPTH + 1], dprev[MOD_PIPELINE_DEPTH], flow[MOD_PIPELINE_DEPTH];
-    DevPtr<float> planes[MOD_PIPELINE_DEPTH];
-    DevPtr<void> aos[MOD_PIPELINE_DEPTH];
-    DevPtr<int32_t> labels[MOD_PIPELINE_DEPTH], nobj[MOD_PIPELINE_DEPTH];
-    DevPtr<ModObject> objects[MOD_PIPELINE_DEPTH];
-    HostPtr<int32_t> h_n[MOD_PIPELINE_DEPTH];        // pinned: object count of the slot's frame
-    HostPtr<ModObject> h_obj[MOD_PIPELINE_DEPTH];    // pinned: its objects (handed to the caller's array at collect time)
-    ModObject *user_obj[MOD_PIPELINE_DEPTH] = {};
-    int32_t user_cap[MOD_PIPELINE_DEPTH] = {};
-    Event ev_in[MOD_PIPELINE_DEPTH], ev_done[MOD_PIPELINE_DEPTH], ev_out[MOD_PIPELINE_DEPTH];
-    DevPtr<uint8_t> img[MOD_PIPELINE_DEPTH];         // mod_submit_stereo_host: the slot's two 8-bit images
-    Event ev_img[MOD_PIPELINE_DEPTH];                // ... the estimator has been enqueued behind them (context stream)
-    bool img_used[MOD_PIPELINE_DEPTH] = {};
-    Event ev_ring;                                   // last disparity plane written by kernels (stereo path)
-    // a ring plane may still be on its way to a caller's `disparity` buffer (result stream) when a frame that ended at a guard —
-    // it takes a plane but no ticket — has advanced the ring back to it: the plane's next writer waits for that copy
-    Event ev_plane_read[MOD_PIPELINE_DEPTH + 1];
-    bool plane_read_pending[MOD_PIPELINE_DEPTH + 1] = {};
-    bool ring_by_kernels = false;
-    // mod_submit_images_host: the left images, a ring indexed like the disparity planes (frame t's image is frame t+1's previous one;
-    // a frame that ends at a guard takes a plane but no ticket, so the ticket slots would not do)
-    DevPtr<uint8_t> limg[MOD_PIPELINE_DEPTH + 1];
-    Event ev_limg[MOD_PIPELINE_DEPTH + 1];           // the last kernel that reads the image has been enqueued (context stream)
-    bool limg_used[MOD_PIPELINE_DEPTH + 1] = {};
-    bool have_prev_img = false;                      // limg[(dring - 1) % (DEPTH + 1)] holds the previous submit's left image
-    // colour images (mod_set_image_layout): the slot's two windows as they arrive, W * H * 4 bytes each (allocated on first use);
-    // k_to_mono turns them into grey in img[slot] / limg[nowi] on the context's stream
-    DevPtr<uint8_t> stage[MOD_PIPELINE_DEPTH];
-    Event ev_stage[MOD_PIPELINE_DEPTH];              // ... the kernels that read them have been enqueued (context stream)
-    bool stage_used[MOD_PIPELINE_DEPTH] = {};
-    // mod_submit_odometry_host: the slot's estimate on the device and its pinned host copy; collect reads the status
-    struct EgoSlot { ModTransform tf; ModEgoResult res; };
-    DevPtr<EgoSlot> ego;                             // device [DEPTH]
-    HostPtr<EgoSlot> h_ego[MOD_PIPELINE_DEPTH];      // pinned
-    bool odo[MOD_PIPELINE_DEPTH] = {};               // the slot's ticket came from the odometry stream
-    ModTransform *user_tf[MOD_PIPELINE_DEPTH] = {};
-    ModEgoResult *user_ego[MOD_PIPELINE_DEPTH] = {};
-    int64_t dring = 0;                               // disparity planes handed out so far: plane of the next frame = dring % (DEPTH + 1)
-    int64_t seq = 0;                                 // frames submitted so far
+    static constexpr int R = MOD_PIPELINE_DEPTH + 1;
+    Slot slot[MOD_PIPELINE_DEPTH];
+    RingPlane ring[R];
+    DevPtr<EgoSlot> ego;                             // device [DEPTH], one element per slot (Slot::ego)
+    // the last plane written by kernels (image entries; a frame they skipped took a plane without a ticket): mod_submit_frame_host's next copy waits
+    Fence ring_written;
+    int64_t dring = 0, seq = 0;                      // planes / tickets handed out so far
     int in_flight = 0;
-    bool have_prev = false;                          // dnow[(seq - 1) % (DEPTH + 1)] holds the previous frame's disparity
+    bool have_prev = false, have_prev_img = false;   // the plane before the next one holds the previous frame's disparity / left image
+    // The ring arithmetic, all of it: the slot of ticket number t, the plane the next frame fills and the one filled before it.
+    Frame frame(int64_t t) { return {&slot[t % MOD_PIPELINE_DEPTH], &ring[dring % R], &ring[(dring + R - 1) % R]}; }
+    // `now` becomes the next frame's previous plane (disparity_previous_ = disparity_now_, scene_flow_constructor.cpp:397-398).  An image frame
+    // takes its plane once its estimator is enqueued and keeps it when it then ends at a guard; a disparity frame takes one only with its ticket.
+    void advance_ring() { dring++; have_prev = true; }
   } pipe;
   HostPtr<FrameConst> pinned[kRing];
   Event pinned_ev[kRing];
