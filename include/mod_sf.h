@@ -234,6 +234,31 @@ int  mod_sgm_compute_host(ModContext *ctx, const uint8_t *left, const uint8_t *r
 #define MOD_SGM_FRACTION_BITS 4
 int  mod_set_disparity_subpixel(ModContext *ctx, int32_t fraction_bits);
 int  mod_get_disparity_subpixel(const ModContext *ctx, int32_t *fraction_bits);
+/* Rejection filters, opt-in: context state like the sub-pixel mode, read when a call or a submit enqueues its estimator (the same
+ * five entry points); a frame in flight completes with the settings of its own submit.  All zero (the default): off — the estimator
+ * enqueues the kernels it always did.  Integer arithmetic up to the final conversion: tests/models/sgm_filters_model.py restates
+ * both bit for bit.
+ *   uniqueness_ratio u (StereoSGBM's rule, left map only): with d the first minimum of the summed path costs S(x, .), m = S(x, d)
+ *     and s2 = min S(x, d') over |d' - d| >= 2, the pixel is rejected iff such a d' exists and s2 * (100 - u) < m * 100.  A rejected
+ *     pixel carries a marker (255; 65535 in the sub-pixel map) through the 3 x 3 median — as the largest value: an isolated rejection
+ *     is replaced by its neighbourhood's median, a rejected patch stays — and leaves the left-right check as -1.
+ *   speckle_size / speckle_range (the last stage, on the float plane): pixels that are finite and >= 0 take part; 4-neighbours that
+ *     both take part are linked iff fabsf(a - b) <= (float)speckle_range (pairwise, not against a seed); every pixel of a connected
+ *     region of at most speckle_size pixels becomes -1. */
+typedef struct ModDisparityFilters {   /* 16 bytes; all zero = off */
+  int32_t uniqueness_ratio;  /* 0..99 [%]; 0 = off */
+  int32_t speckle_size;      /* regions of at most this many pixels are invalidated; 0 = off; <= max_width * max_height */
+  int32_t speckle_range;     /* >= 0, whole disparities: neighbours link when they differ by at most this */
+  int32_t reserved;          /* must be 0 */
+} ModDisparityFilters;
+/* NULL = all off.  Out-of-range values and a non-zero `reserved`: MOD_ERR_INVALID_ARGUMENT, and the settings stay as they were. */
+int  mod_set_disparity_filters(ModContext *ctx, const ModDisparityFilters *filters);
+int  mod_get_disparity_filters(const ModContext *ctx, ModDisparityFilters *filters);
+/* The speckle stage alone, in place, on any 32FC1 disparity planes [frames][H][W] of the camera's size (a caller's own matcher):
+ * a pixel takes part iff it is finite and >= the camera's min_disparity; removed pixels become min_disparity - 1.  speckle_size 0:
+ * nothing to do.  Ordered on the context's stream; scratch (8 bytes per pixel of max_frames frames) is allocated on first use.
+ * NULL plane -> MOD_SKIP_NO_DISPARITY_NOW. */
+int  mod_disparity_speckle_dev(ModContext *ctx, int32_t frames, float *disparity, int32_t speckle_size, int32_t speckle_range);
 /* stages, for tests and tracing: centre-symmetric census (31 bits per pixel, 0 where the window leaves the image) ... */
 int  mod_sgm_census_dev(ModContext *ctx, int32_t frames, const uint8_t *image, uint32_t *census);
 /* ... and one aggregation path L_r [frames][H][W][disparities] uint8 over the Hamming cost of the census words; direction 0..7 =

@@ -53,6 +53,7 @@ EXPORTS = [
     "mod_egomotion_dev", "mod_egomotion_host", "mod_submit_odometry_host",
     "mod_set_image_layout", "mod_get_image_layout", "mod_image_to_mono_dev",
     "mod_set_disparity_subpixel", "mod_get_disparity_subpixel",
+    "mod_set_disparity_filters", "mod_get_disparity_filters", "mod_disparity_speckle_dev",
 ]
 
 
@@ -95,6 +96,10 @@ class ModSceneFlowPlanes(C.Structure):
 class ModSgmParams(C.Structure):
     _fields_ = [("disparities", C.c_int32), ("p1", C.c_int32), ("p2", C.c_int32), ("paths", C.c_int32), ("lr_check", C.c_int32),
                 ("median", C.c_int32)]
+
+
+class ModDisparityFilters(C.Structure):
+    _fields_ = [("uniqueness_ratio", C.c_int32), ("speckle_size", C.c_int32), ("speckle_range", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ModFlowParams(C.Structure):
@@ -211,6 +216,9 @@ def load(require_torch_first: bool = True):
     L.mod_image_to_mono_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), vp]
     L.mod_set_disparity_subpixel.argtypes = [vp, i32]
     L.mod_get_disparity_subpixel.argtypes = [vp, C.POINTER(i32)]
+    L.mod_set_disparity_filters.argtypes = [vp, C.POINTER(ModDisparityFilters)]
+    L.mod_get_disparity_filters.argtypes = [vp, C.POINTER(ModDisparityFilters)]
+    L.mod_disparity_speckle_dev.argtypes = [vp, i32, vp, i32, i32]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

@@ -64,6 +64,29 @@ static int ensure_sgm_scratch(ModContext *c, int D, int frames, bool subpixel, i
   return MOD_OK;
 }
 
+// ---- rejection filters of the disparity (sgm.hip: uniqueness; disparity_filter.hip: speckle) -------------------------------
+int check_disparity_filters(ModContext *c, const ModDisparityFilters *f) {
+  if (f->uniqueness_ratio < 0 || f->uniqueness_ratio > 99) return fail(c, MOD_ERR_INVALID_ARGUMENT, "uniqueness_ratio must be in 0..99");
+  if (f->speckle_size < 0 || (size_t)f->speckle_size > (size_t)c->cfg.max_width * (size_t)c->cfg.max_height)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "speckle_size must be in 0..max_width * max_height");
+  if (f->speckle_range < 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "speckle_range must be >= 0");
+  if (f->reserved != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "ModDisparityFilters.reserved must be 0");
+  return MOD_OK;
+}
+
+// parent and size planes for `frames` frames; grows, after a sync, when a larger count comes (the old planes stay if that fails)
+static int ensure_speckle_scratch(ModContext *c, int frames) {
+  Buffers &b = c->b;
+  if (b.spk_frames >= frames) return MOD_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevPtr<int32_t> parent, size;
+  HIP_TRY(c, dalloc(parent, (size_t)frames * c->maxN));
+  HIP_TRY(c, dalloc(size, (size_t)frames * c->maxN));
+  b.spk_parent = std::move(parent); b.spk_size = std::move(size);   // (swaps: the old planes are released with the locals)
+  b.spk_frames = frames;
+  return MOD_OK;
+}
+
 // ---- on-GPU optical flow (flow.hip) ---------------------------------------------------------------------------------------
 constexpr int kFlowMaxLevels = 6;
 constexpr int kFlowMinCoarse = 16;      // px on either side of the coarsest level
@@ -204,7 +227,9 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   if ((rc = check_sgm_params(c, p))) return rc;
   int group = 1;
   const bool subpixel = c->sgm_fraction_bits != 0;       // the setting of THIS call: every kernel below is enqueued before it returns
+  const ModDisparityFilters filters = c->sgm_filters;   // ... and so are the filters
   if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
+  if (filters.speckle_size > 0 && (rc = ensure_speckle_scratch(c, group))) return rc;
   const int W = c->dc.W, H = c->dc.H, D = p->disparities;
   const size_t N = (size_t)W * H;
   Buffers &b = c->b;
@@ -249,8 +274,12 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
     const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
     // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
     for (int i = 0; i < (all_in_one[s] ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, b.sgm_join[s][i], 0));
-    launch_sgm_finish(W, H, g, D, p->paths, N * (size_t)D * g, p->median, p->lr_check, b.sgm_S + s * set_volumes, dl, dr, dlm, drm,
-                      dl16, dlm16, disparity + (size_t)f0 * N, c->stream);
+    launch_sgm_finish(W, H, g, D, p->paths, N * (size_t)D * g, p->median, p->lr_check, filters.uniqueness_ratio, b.sgm_S + s * set_volumes,
+                      dl, dr, dlm, drm, dl16, dlm16, disparity + (size_t)f0 * N, c->stream);
+    // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever)
+    if (filters.speckle_size > 0)
+      launch_speckle(W, H, g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, disparity + (size_t)f0 * N, b.spk_parent, b.spk_size,
+                     b.dbg, c->stream);
     return MOD_OK;
   };
   if ((rc = start(0))) return rc;
@@ -273,6 +302,34 @@ int mod_set_disparity_subpixel(ModContext *c, int32_t fraction_bits) {
 int mod_get_disparity_subpixel(const ModContext *c, int32_t *fraction_bits) {
   if (!c || !fraction_bits) return MOD_ERR_INVALID_ARGUMENT;
   *fraction_bits = c->sgm_fraction_bits;
+  return MOD_OK;
+}
+
+int mod_set_disparity_filters(ModContext *c, const ModDisparityFilters *f) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!f) { c->sgm_filters = ModDisparityFilters{}; return MOD_OK; }
+  if (int rc = check_disparity_filters(c, f)) return rc;
+  c->sgm_filters = *f;
+  return MOD_OK;
+}
+
+int mod_get_disparity_filters(const ModContext *c, ModDisparityFilters *f) {
+  if (!c || !f) return MOD_ERR_INVALID_ARGUMENT;
+  *f = c->sgm_filters;
+  return MOD_OK;
+}
+
+int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, int32_t speckle_size, int32_t speckle_range) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!disparity) return MOD_SKIP_NO_DISPARITY_NOW;
+  const ModDisparityFilters f{0, speckle_size, speckle_range, 0};
+  if ((rc = check_disparity_filters(c, &f))) return rc;
+  if (speckle_size == 0) return MOD_OK;
+  if ((rc = ensure_speckle_scratch(c, c->cfg.max_frames))) return rc;
+  launch_speckle(c->dc.W, c->dc.H, frames, c->cam.min_disparity, c->cam.min_disparity - 1.0f, speckle_size, speckle_range, disparity,
+                 c->b.spk_parent, c->b.spk_size, c->b.dbg, c->stream);
+  HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
 

@@ -81,6 +81,10 @@ struct Buffers {
   // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
   Stream sgm_side[8];
   Event sgm_fork[2], sgm_join[2][8];
+  // speckle filter (disparity_filter.hip): union-find parents and region sizes of its own, [spk_frames][maxN] each — a group of the
+  // estimator or max_frames of mod_disparity_speckle_dev; allocated on first use with the filter on, grow-only (ensure_speckle_scratch)
+  DevPtr<int32_t> spk_parent, spk_size;
+  int spk_frames = 0;
   // on-GPU optical flow (allocated on first use, every level sized for max_width x max_height x max_frames; see flow_level_offset)
   DevPtr<uint8_t> flow_img;                 // pyramid levels 1 .. kFlowMaxLevels - 1 of both images
   DevPtr<uint32_t> flow_census;             // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
@@ -107,6 +111,7 @@ struct ModContext {
   ModImageLayout layout{};                  // of the host images (mod_set_image_layout) ...
   bool has_layout = false;                  // ... or, while false, mono8 packed at the camera's size
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
+  ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -246,6 +251,7 @@ int scene_flow_staged(ModContext *c, const ModFrameBatch *in, const ModSceneFlow
 int check_sgm_params(ModContext *c, const ModSgmParams *p);
 int check_flow_params(ModContext *c, const ModFlowParams *p, int frames);
 int check_ego_params(ModContext *c, const ModEgoParams *p);
+int check_disparity_filters(ModContext *c, const ModDisparityFilters *f);
 // the ego-motion estimator over `frames` frames; tf == null: into b.ego_tf, res == null: into b.ego_res; fc != null: also the frames'
 // scene-flow constants (with dt) into fc
 int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p,

@@ -21,7 +21,8 @@
 // A product build compiles the conditions away.  Codes: 0 link request pixel, 1 link roots, 2 merge root, 3 root list slot,
 // 4 select root, 5 final: parent entry, 6 final: tile-root cell, 7 final: label, 8 final: member slot, 9 median: segment,
 // 10 median: member pixel, 11 ties: member slot, 12 tile: link-request slot, 13 tile: root pixel, 14 ties: members placed != cluster size,
-// 15 select: more clusters than max_objects, 16 scene flow: a late kernarg load disagrees with the argument it stands for.
+// 15 select: more clusters than max_objects, 16 scene flow: a late kernarg load disagrees with the argument it stands for,
+// 17 speckle filter: a parent entry that is not a smaller pixel index of the frame.
 // dbg layout: [0, 64) cycle counters of the PHASE_COUNTERS build, [64, 96) one counter per code.
 constexpr int kDbgCheckBase = 64, kDbgWords = 96;
 #ifdef MOD_CHECKED

@@ -86,9 +86,14 @@ void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direct
 bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int paths, size_t path_stride, const uint32_t *cl, const uint32_t *cr,
                           uint8_t *L, hipStream_t s);
 // winner-take-all, median, left-right check.  dl16 / dlm16 non-null: the sub-pixel mode — the left maps are 16-bit (16 d + q) and
-// live there, dl / dlm are not used
-void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, const uint8_t *Lv,
+// live there, dl / dlm are not used.  uniqueness: 0 = off, else the ratio in percent (mod_set_disparity_filters)
+void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
                        uint8_t *dl, uint8_t *dr, uint8_t *dlm, uint8_t *drm, uint16_t *dl16, uint16_t *dlm16, float *disparity, hipStream_t s);
+
+// speckle filter (disparity_filter.hip), in place on `disparity` [frames][H][W]: regions (4-connected, neighbours within speckle_range,
+// pixels finite and >= lo) of at most speckle_size pixels become `invalid`.  parent / size: [frames][H][W] scratch of the filter's own
+void launch_speckle(int W, int H, int frames, float lo, float invalid, int speckle_size, int speckle_range, float *disparity,
+                    int32_t *parent, int32_t *size, unsigned long long *dbg, hipStream_t s);
 
 // on-GPU optical flow (flow.hip).  Pyramid level of both images: src0 / src1 [frames][Hs][Ws] -> dst [2][frames][H][W].
 void launch_flow_pyramid(int Ws, int Hs, int W, int H, int frames, const uint8_t *src0, const uint8_t *src1, uint8_t *dst, hipStream_t s);

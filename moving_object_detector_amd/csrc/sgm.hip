@@ -419,9 +419,24 @@ __device__ __forceinline__ uint32_t sgm_fraction(uint32_t cm, uint32_t c0, uint3
   return 16u * d + (16u * (cm - cp) + 17u * den) / (2u * den) - 8u;
 }
 
-template <bool SUB, class TL>
+//
+// UNIQ (the uniqueness test, mod_set_disparity_filters; StereoSGBM's rule, left map only): after the reduction that found the winner
+// d with m = S(x, d), a second reduction of the same shape over the keys whose disparity is at least 2 away gives s2 = min S(x, d'),
+// |d' - d| >= 2; the lane that stores the pixel rejects it iff such a d' exists and s2 * (100 - u) < m * 100 (S <= 8 * 255: no
+// overflow) and stores the marker kSgmRejected<TL> instead — the largest value of the map's type (real values reach 127 / 2040), an
+// ordinary value to the median, -1 behind the left-right kernels.  The right map is untouched.
+template <class TL> constexpr uint32_t kSgmRejected = sizeof(TL) == 1 ? 255u : 65535u;
+__device__ __forceinline__ uint32_t sgm_far_key(uint32_t key, uint32_t d) {   // the key, unless its disparity is the winner's or next to it
+  const uint32_t kd = key & 255u;
+  return kd + 1u >= d && kd <= d + 1u ? 0xffffffffu : key;
+}
+__device__ __forceinline__ bool sgm_ambiguous(uint32_t best, uint32_t second, int u) {
+  return second != 0xffffffffu && (second >> 8) * (uint32_t)(100 - u) < (best >> 8) * 100u;
+}
+
+template <bool SUB, class TL, bool UNIQ>
 __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
-                                                 TL *__restrict__ dl, uint8_t *__restrict__ dr) {
+                                                 TL *__restrict__ dl, uint8_t *__restrict__ dr, int u) {
   extern __shared__ uint32_t rkey[];                 // [W]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, y = blockIdx.x, f = blockIdx.y;
   const size_t plane = (size_t)f * W * H;
@@ -441,14 +456,16 @@ __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths,
     }
     const uint32_t k0 = d0 < D ? ((s0 << 8) | (uint32_t)d0) : 0xffffffffu, k1 = d1 < D ? ((s1 << 8) | (uint32_t)d1) : 0xffffffffu;
     const uint32_t kl = wave_min_u32(min(k0, k1));
+    bool rejected = false;
+    if constexpr (UNIQ) rejected = sgm_ambiguous(kl, wave_min_u32(min(sgm_far_key(k0, kl & 255u), sgm_far_key(k1, kl & 255u))), u);
     if constexpr (!SUB) {
-      if (lane == 0) dl[(size_t)y * W + x] = (uint8_t)(kl & 255u);
+      if (lane == 0) dl[(size_t)y * W + x] = (uint8_t)(rejected ? kSgmRejected<TL> : (kl & 255u));
     } else {
       // S(x, d0 - 1), S(x, d1 + 1): the neighbouring lanes' sums (all 64 lanes are active here)
       const uint32_t below = MOD_DPP(s1, 0x138), above = MOD_DPP(s0, 0x130);   // wave_shr:1, wave_shl:1
       const uint32_t d = kl & 255u;
       if ((uint32_t)lane == (d >> 1))                // the lane that owns the winner
-        dl[(size_t)y * W + x] = (TL)((d & 1u) ? sgm_fraction(s0, kl >> 8, above, d, D) : sgm_fraction(below, kl >> 8, s1, d, D));
+        dl[(size_t)y * W + x] = (TL)(rejected ? kSgmRejected<TL> : (d & 1u) ? sgm_fraction(s0, kl >> 8, above, d, D) : sgm_fraction(below, kl >> 8, s1, d, D));
     }
     if (d0 < D && x - d0 >= 0) atomicMin(&rkey[x - d0], k0);
     if (d1 < D && x - d1 >= 0) atomicMin(&rkey[x - d1], k1);
@@ -463,9 +480,11 @@ __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths,
 // SUB: as above.  After the butterfly all 8 lanes of the pixel hold the winning key; lane d / 16 owns the winner and finds its two
 // neighbours among its own 16 sums or, for the first / last of them, in the sum the adjacent lane passed over (row_shr:1 /
 // row_shl:1 before the reduction; the lane across a pixel boundary is only ever asked for d = 0 or d = D - 1, which have no fraction).
-template <bool SUB, class TL>
+// UNIQ: as above.  The second minimum runs over the lane's 16 keys again with those next to the winner masked, then through the same
+// three DPP steps; every lane of the pixel holds it, so whichever lane stores the pixel does the one compare.
+template <bool SUB, class TL, bool UNIQ>
 __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
-                                                   TL *__restrict__ dl, uint8_t *__restrict__ dr) {
+                                                   TL *__restrict__ dl, uint8_t *__restrict__ dr, int u) {
   extern __shared__ uint32_t rkey[];                 // [W]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, y = blockIdx.x, f = blockIdx.y;
   const size_t plane = (size_t)f * W * H;
@@ -511,8 +530,25 @@ __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int path
     t = MOD_DPP(best, 0xB1); best = min(best, t);
     t = MOD_DPP(best, 0x4E); best = min(best, t);
     t = MOD_DPP(best, 0x141); best = min(best, t);
+    bool rejected = false;
+    if constexpr (UNIQ) {
+      const uint32_t dw = best & 255u;
+      uint32_t second = 0xffffffffu;
+      if (live) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+          const uint32_t d = (uint32_t)(dbase + 4 * j);
+          const uint32_t k0 = ((e[j] & 0xffffu) << 8) | d, k1 = ((o[j] & 0xffffu) << 8) | (d + 1), k2 = ((e[j] >> 16) << 8) | (d + 2), k3 = ((o[j] >> 16) << 8) | (d + 3);
+          second = min(second, min(min(sgm_far_key(k0, dw), sgm_far_key(k1, dw)), min(sgm_far_key(k2, dw), sgm_far_key(k3, dw))));
+        }
+      }
+      t = MOD_DPP(second, 0xB1); second = min(second, t);
+      t = MOD_DPP(second, 0x4E); second = min(second, t);
+      t = MOD_DPP(second, 0x141); second = min(second, t);
+      rejected = sgm_ambiguous(best, second, u);
+    }
     if constexpr (!SUB) {
-      if (sub == 0 && x < W) dl[(size_t)y * W + x] = (uint8_t)(best & 255u);
+      if (sub == 0 && x < W) dl[(size_t)y * W + x] = (uint8_t)(rejected ? kSgmRejected<TL> : (best & 255u));
     } else {
       const uint32_t d = best & 255u;
       if ((d >> 4) == (uint32_t)sub && x < W) {      // the lane that owns the winner (a dead pixel's key names disparity 255: nobody)
@@ -523,7 +559,7 @@ __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int path
         const uint32_t after = j == 3 ? edge_hi : (j == 0 ? e[1] : j == 1 ? e[2] : e[3]) & 0xffffu;      // the sum behind it
         const uint32_t cm = k == 0 ? before : k == 1 ? (ej & 0xffffu) : k == 2 ? (oj & 0xffffu) : (ej >> 16);
         const uint32_t cp = k == 0 ? (oj & 0xffffu) : k == 1 ? (ej >> 16) : k == 2 ? (oj >> 16) : after;
-        dl[(size_t)y * W + x] = (TL)sgm_fraction(cm, best >> 8, cp, d, D);
+        dl[(size_t)y * W + x] = (TL)(rejected ? kSgmRejected<TL> : sgm_fraction(cm, best >> 8, cp, d, D));
       }
     }
   }
@@ -547,7 +583,9 @@ __global__ __launch_bounds__(256) void k_sgm_median3(int W, int H, const T *__re
   out[p] = (T)v4;
 }
 
-// left-right consistency check -> DisparityImage pixels (float, -1 = invalid)
+// left-right consistency check -> DisparityImage pixels (float, -1 = invalid).  UNIQ: the marker of a pixel the uniqueness test (or
+// the median of a rejected patch) left is -1 whatever the check says
+template <bool UNIQ>
 __global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, const uint8_t *__restrict__ dl, const uint8_t *__restrict__ dr,
                                                 float *__restrict__ disp) {
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
@@ -558,9 +596,11 @@ __global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, cons
   const int d = dl[p];
   bool ok = true;
   if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
+  if (UNIQ && d == (int)kSgmRejected<uint8_t>) ok = false;
   disp[p] = ok ? (float)d : -1.0f;
 }
 // the same on the sub-pixel mode's left map v = 16 d + q: the check runs on the nearest integer, the pixel leaves as v / 16 (exact)
+template <bool UNIQ>
 __global__ __launch_bounds__(256) void k_sgm_lr_sub(int W, int H, int lr_check, const uint16_t *__restrict__ dl, const uint8_t *__restrict__ dr,
                                                     float *__restrict__ disp) {
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
@@ -571,6 +611,7 @@ __global__ __launch_bounds__(256) void k_sgm_lr_sub(int W, int H, int lr_check, 
   const int v = dl[p], d = (v + 8) >> 4;
   bool ok = true;
   if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
+  if (UNIQ && v == (int)kSgmRejected<uint16_t>) ok = false;
   disp[p] = ok ? (float)v * 0.0625f : -1.0f;
 }
 
@@ -640,24 +681,35 @@ bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int p
   return true;
 }
 
-void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, const uint8_t *Lv,
+// uniqueness: 0 = off (the instantiations without the test), else the ratio u in percent
+void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
                        uint8_t *dl, uint8_t *dr, uint8_t *dlm, uint8_t *drm, uint16_t *dl16, uint16_t *dlm16, float *disparity, hipStream_t s) {
-  const dim3 g((W + 63) / 64, (H + 3) / 4, frames), b(64, 4);
+  const dim3 g((W + 63) / 64, (H + 3) / 4, frames), b(64, 4), gw(H, frames), bw(256);
+  const size_t lds = (size_t)W * sizeof(uint32_t);
+  const int u = uniqueness;
+#define SGM_WTA(KERNEL, SUB, TL, OUT)                                                                                                   \
+  do {                                                                                                                                  \
+    if (u) hipLaunchKernelGGL((KERNEL<SUB, TL, true>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, OUT, dr, u);                     \
+    else hipLaunchKernelGGL((KERNEL<SUB, TL, false>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, OUT, dr, u);                      \
+  } while (0)
   if (dl16) {                                          // sub-pixel mode: 16-bit left maps, the right maps as ever
-    if (D % 16 == 0) hipLaunchKernelGGL((k_sgm_wta16<true, uint16_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl16, dr);
-    else hipLaunchKernelGGL((k_sgm_wta<true, uint16_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl16, dr);
+    if (D % 16 == 0) SGM_WTA(k_sgm_wta16, true, uint16_t, dl16);
+    else SGM_WTA(k_sgm_wta, true, uint16_t, dl16);
     if (median) {
       hipLaunchKernelGGL(k_sgm_median3<uint16_t>, g, b, 0, s, W, H, dl16, dlm16);
       hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dr, drm);
     }
-    hipLaunchKernelGGL(k_sgm_lr_sub, g, b, 0, s, W, H, lr_check, median ? dlm16 : dl16, median ? drm : dr, disparity);
+    if (u) hipLaunchKernelGGL(k_sgm_lr_sub<true>, g, b, 0, s, W, H, lr_check, median ? dlm16 : dl16, median ? drm : dr, disparity);
+    else hipLaunchKernelGGL(k_sgm_lr_sub<false>, g, b, 0, s, W, H, lr_check, median ? dlm16 : dl16, median ? drm : dr, disparity);
     return;
   }
-  if (D % 16 == 0) hipLaunchKernelGGL((k_sgm_wta16<false, uint8_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl, dr);
-  else hipLaunchKernelGGL((k_sgm_wta<false, uint8_t>), dim3(H, frames), dim3(256), (size_t)W * sizeof(uint32_t), s, W, H, D, paths, path_stride, Lv, dl, dr);
+  if (D % 16 == 0) SGM_WTA(k_sgm_wta16, false, uint8_t, dl);
+  else SGM_WTA(k_sgm_wta, false, uint8_t, dl);
+#undef SGM_WTA
   if (median) {
     hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dl, dlm);
     hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dr, drm);
   }
-  hipLaunchKernelGGL(k_sgm_lr, g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? drm : dr, disparity);
+  if (u) hipLaunchKernelGGL(k_sgm_lr<true>, g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? drm : dr, disparity);
+  else hipLaunchKernelGGL(k_sgm_lr<false>, g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? drm : dr, disparity);
 }

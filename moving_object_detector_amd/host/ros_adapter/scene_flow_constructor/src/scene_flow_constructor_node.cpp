@@ -7,6 +7,8 @@
 // What runs where:
 //   disparity        on the GPU (libmod_sf's SGM), replacing sgm_gpu::SgmGpu::computeDisparity (:35,267)
 //                    `~disparity_subpixel` (default false): disparities in sixteenths of a pixel (mod_set_disparity_subpixel)
+//                    `~uniqueness_ratio`, `~speckle_size`, `~speckle_range` (stereo_image_proc's names; default 0 = off): the
+//                    estimator's rejection filters (mod_set_disparity_filters)
 //   scene flow       on the GPU, overlapped with the next frame's estimators like construct_thread_ (:389-392): submitStereo() /
 //                    collect(); the disparity plane stays in HBM as the next frame's previous one (:397-398)
 //   optical flow     on the GPU (libmod_sf's census flow, not PWC-Net) when `~gpu_estimators` is true (default); with it false, the
@@ -73,6 +75,8 @@ class SceneFlowConstructorNode {
     sgm.p2 = private_node_handle_.param("p2", 96); sgm.paths = private_node_handle_.param("paths", 8); sgm.lr_check = 1; sgm.median = 1;
     impl_->setDisparityParams(sgm);
     impl_->setDisparitySubpixel(private_node_handle_.param("disparity_subpixel", false));   // sixteenths of a pixel; the fields of ~depth's source stay
+    impl_->setDisparityFilters(private_node_handle_.param("uniqueness_ratio", 0), private_node_handle_.param("speckle_size", 0),
+                               private_node_handle_.param("speckle_range", 0));   // stereo_image_proc's names; 0 = off
     max_disparity_ = (float)(sgm.disparities - 1);
 
     // every estimator on the GPU (default), or the two CALL-OUTs below; optional centred crop of the incoming images

@@ -65,6 +65,13 @@ class SceneFlowConstructor {
   // sub-pixel disparity (mod_set_disparity_subpixel: sixteenths of a pixel); off unless asked for.  Frames already submitted keep
   // the setting of their submit.
   void setDisparitySubpixel(bool on) { check(mod_set_disparity_subpixel(ctx_, on ? MOD_SGM_FRACTION_BITS : 0)); }
+  // rejection filters of the disparity (mod_set_disparity_filters; stereo_image_proc's names): uniqueness ratio in percent, regions of at
+  // most speckle_size pixels whose neighbours differ by at most speckle_range disparities are invalidated; all 0 = off, the default.
+  // Frames already submitted keep the settings of their submit.
+  void setDisparityFilters(int uniqueness_ratio, int speckle_size, int speckle_range) {
+    const ModDisparityFilters f{uniqueness_ratio, speckle_size, speckle_range, 0};
+    check(mod_set_disparity_filters(ctx_, &f));
+  }
   bool estimateDisparity(const mod_host::Image *left_image, const mod_host::Image *right_image, const mod_host::CameraInfo &left_camera_info,
                          const mod_host::CameraInfo &right_camera_info, mod_host::DisparityImage *disparity, std::vector<float> *pixels) {
     if (!left_image || !right_image || !left_image->data || !right_image->data) return false;

@@ -105,6 +105,30 @@ class Context:
         self._check(self.lib.mod_get_disparity_subpixel(self.h, C.byref(bits)))
         return bits.value
 
+    def set_disparity_filters(self, uniqueness_ratio: int = 0, speckle_size: int = 0, speckle_range: int = 0) -> None:
+        """Rejection filters of the on-GPU disparity estimator (mod_set_disparity_filters), all off by default: uniqueness_ratio in
+        percent (StereoSGBM's rule), speckle_size / speckle_range as in stereo_image_proc (regions of at most speckle_size pixels whose
+        neighbours differ by at most speckle_range go).  Read when a call or a submit enqueues its estimator."""
+        f = capi.ModDisparityFilters(int(uniqueness_ratio), int(speckle_size), int(speckle_range), 0)
+        self._check(self.lib.mod_set_disparity_filters(self.h, C.byref(f)))
+
+    def get_disparity_filters(self) -> dict:
+        f = capi.ModDisparityFilters(-1, -1, -1, -1)
+        self._check(self.lib.mod_get_disparity_filters(self.h, C.byref(f)))
+        return {"uniqueness_ratio": f.uniqueness_ratio, "speckle_size": f.speckle_size, "speckle_range": f.speckle_range}
+
+    def speckle_filter(self, dev_planes: torch.Tensor, size: int, range: int) -> torch.Tensor:   # noqa: A002 (stereo_image_proc's name)
+        """The speckle stage alone, in place (mod_disparity_speckle_dev), on device float32 planes (F, H, W) or (H, W) of the camera's
+        size: pixels take part when finite and >= the camera's min_disparity, removed ones become min_disparity - 1.  Enqueued on the
+        context's stream; returns `dev_planes`."""
+        p = dev_planes[None] if dev_planes.dim() == 2 else dev_planes
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device.type != "cuda" or p.shape[1:] != (self.height, self.width):
+            raise ValueError("dev_planes must be a contiguous float32 device tensor (F, H, W) at the camera size")
+        rc = self._check(self.lib.mod_disparity_speckle_dev(self.h, p.shape[0], p.data_ptr(), int(size), int(range)))
+        if rc != 0:
+            raise capi.ModError(rc, "mod_disparity_speckle_dev skipped")
+        return dev_planes
+
     def close(self) -> None:
         if getattr(self, "h", None):
             self.lib.mod_destroy(self.h)

@@ -1,5 +1,6 @@
 """Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
-usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--reps N]     (--subpixel: mod_set_disparity_subpixel(4))"""
+usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--reps N]
+(--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given)"""
 import argparse, ctypes as C, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -11,6 +12,8 @@ ap.add_argument("W", type=int, nargs="?", default=1280)
 ap.add_argument("H", type=int, nargs="?", default=720)
 ap.add_argument("D", type=int, nargs="?", default=128)
 ap.add_argument("--subpixel", action="store_true")
+ap.add_argument("--uniqueness", type=int, default=0, metavar="U", help="uniqueness ratio in percent (0 = off)")
+ap.add_argument("--speckle", type=int, nargs=2, default=(0, 0), metavar=("SIZE", "RANGE"), help="speckle filter (size 0 = off)")
 ap.add_argument("--reps", type=int, default=3)
 a = ap.parse_args()
 W, H, D = a.W, a.H, a.D
@@ -20,6 +23,9 @@ ctx = Context(W, H, max_frames=F)
 ctx.set_camera(synth.make_camera(W, H)); ctx.set_params(synth.Params())
 if a.subpixel:
     ctx.set_disparity_subpixel(True)
+if a.uniqueness or a.speckle[0]:
+    ctx.set_disparity_filters(a.uniqueness, a.speckle[0], a.speckle[1])
+filters = f" uniqueness={a.uniqueness} speckle={a.speckle[0]}/{a.speckle[1]}" if a.uniqueness or a.speckle[0] else ""
 dev = ctx.device
 tl = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev); tr = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
 out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
@@ -33,5 +39,5 @@ for paths in (8, 4):
         ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
     ctx.synchronize()
     ms = 1e3 * (time.perf_counter() - t0) / (a.reps * F)
-    print(f"{W}x{H} D={D} paths={paths} frames={F} subpixel={'on' if a.subpixel else 'off'}: {ms:.3f} ms per frame ({1e3 / ms:.0f} frames/s); "
+    print(f"{W}x{H} D={D} paths={paths} frames={F} subpixel={'on' if a.subpixel else 'off'}{filters}: {ms:.3f} ms per frame ({1e3 / ms:.0f} frames/s); "
           f"valid {float((out >= 0).float().mean()):.2f}")

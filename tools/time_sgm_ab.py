@@ -1,12 +1,12 @@
 """A/B timing of the on-GPU disparity estimator across BUILDS of the library: one process = one library and one mode, one JSON line.
 
-usage (GPU box): python tools/time_sgm_ab.py TAG [--lib PATH] [--subpixel] [--sizes 1280x720,1920x1080] [--frames 16,64] [--seconds 1.5]
+usage (GPU box): python tools/time_sgm_ab.py TAG [--lib PATH] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--sizes 1280x720,1920x1080] [--frames 16,64] [--seconds 1.5]
 
 The loop is tools/time_sgm.py's (mod_sgm_compute_dev, D = 128, 8 paths, two warm-up calls), timed in three windows of --seconds / 3
 each.  The library is bound here with plain ctypes — only the entry points the loop calls — so that an older build, which lacks newer
 entry points, can be timed against the current one: run the processes alternately (parent, this, parent, this ...) on one box and
-compare the lines.  Line: {"tag", "subpixel", "<W>x<H>_F<frames>": [ms per frame of the three windows], "..._sum": sum of the output
-planes (equal sums: equal work)}.  profiles/sgm_subpixel_time.jsonl was written by it."""
+compare the lines.  Line: {"tag", "subpixel", "uniqueness", "speckle", "<W>x<H>_F<frames>": [ms per frame of the three windows], "..._sum": sum of the output
+planes (equal sums: equal work)}.  profiles/sgm_subpixel_time.jsonl and profiles/sgm_filters_time.jsonl were written by it."""
 import argparse, ctypes as C, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -17,6 +17,8 @@ ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDe
 ap.add_argument("tag")
 ap.add_argument("--lib", default=capi.LIB_PATH, help="the libmod_sf.so to time (default: this tree's)")
 ap.add_argument("--subpixel", action="store_true", help="mod_set_disparity_subpixel(4); needs a build that has it")
+ap.add_argument("--uniqueness", type=int, default=0, metavar="U", help="mod_set_disparity_filters: uniqueness ratio; needs a build that has it")
+ap.add_argument("--speckle", type=int, nargs=2, default=(0, 0), metavar=("SIZE", "RANGE"), help="... and the speckle filter (size 0 = off)")
 ap.add_argument("--sizes", default="1280x720,1920x1080")
 ap.add_argument("--frames", default="16,64")
 ap.add_argument("--seconds", type=float, default=1.5)
@@ -33,8 +35,11 @@ L.mod_synchronize.argtypes = [vp]
 L.mod_sgm_compute_dev.argtypes = [vp, i32, vp, vp, C.POINTER(capi.ModSgmParams), vp]
 if a.subpixel:
     L.mod_set_disparity_subpixel.argtypes = [vp, i32]
+filters = capi.ModDisparityFilters(a.uniqueness, a.speckle[0], a.speckle[1], 0)
+if a.uniqueness or a.speckle[0]:
+    L.mod_set_disparity_filters.argtypes = [vp, C.POINTER(capi.ModDisparityFilters)]
 dev = torch.device("cuda", 0)
-res = {"tag": a.tag, "subpixel": bool(a.subpixel)}
+res = {"tag": a.tag, "subpixel": bool(a.subpixel), "uniqueness": a.uniqueness, "speckle": list(a.speckle)}
 for size in a.sizes.split(","):
     W, H = (int(v) for v in size.split("x"))
     pairs = [synth.make_stereo_images(W, H, 7 + f, 128, n_boxes=5) for f in range(8)]     # eight distinct pairs, repeated
@@ -47,6 +52,8 @@ for size in a.sizes.split(","):
         assert L.mod_set_params(h, C.byref(capi.params_struct(synth.Params()))) == 0
         if a.subpixel:
             assert L.mod_set_disparity_subpixel(h, 4) == 0
+        if a.uniqueness or a.speckle[0]:
+            assert L.mod_set_disparity_filters(h, C.byref(filters)) == 0
         rep = -(-F // 8)
         tl, tr = torch.from_numpy(np.concatenate([Lh] * rep)[:F]).to(dev), torch.from_numpy(np.concatenate([Rh] * rep)[:F]).to(dev)
         out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
