@@ -291,6 +291,27 @@ int  mod_flow_compute_dev(ModContext *ctx, int32_t frames, const uint8_t *prev, 
                           float *flow);
 /* the same for one frame in host memory; synchronous */
 int  mod_flow_compute_host(ModContext *ctx, const uint8_t *prev, const uint8_t *now, const ModFlowParams *params, float *flow);
+/* Neighbour-seed propagation, opt-in: context state like mod_set_disparity_filters, read when a call or a submit enqueues the flow —
+ * mod_flow_compute_dev / _host, mod_submit_images_host, mod_submit_odometry_host; a frame in flight completes with the setting of
+ * its own submit.  seeds 1 (the default): as described above — the estimator enqueues the kernels it always did.  seeds 5: on
+ * every finer level a pixel also tries the winners of its parent's four neighbours, so a pixel near a motion boundary whose parent
+ * chose the other layer's motion can still find its own (tests/models/flow_prop_model.py restates it bit
+ * for bit).  The coarsest level is the same for either value.  On a finer level l (W x H; level l+1 is W1 x H1 with winners F_{l+1}),
+ * for pixel (x, y):
+ *   parent   (X, Y) = (min(x >> 1, W1 - 1), min(y >> 1, H1 - 1));
+ *   seeds    k = 0..4 with offset (ox, oy) = (0,0), (-1,0), (+1,0), (0,-1), (0,+1); seed k's parent is
+ *            (clamp(X + ox, 0, W1 - 1), clamp(Y + oy, 0, H1 - 1)) and its centre c_k = 2 F_{l+1}(that parent);
+ *   winner   each seed's nine candidates c_k + [-1, 1]^2 are scored as ever, and each seed picks its own winner by the usual key
+ *            (cost, then |ex| + |ey|, then raster index); the pixel's winner is the seed winner with the smallest COST, ties to the
+ *            lowest k (a seed whose centre equals that of a lower k can therefore never win);
+ *   sub-pixel (level 0): the terms come from the winning seed's own 3 x 3 costs; per axis both neighbours exist only when the
+ *            winner is that seed's centre candidate on that axis.
+ * Both directions use the rule, so the forward-backward check compares two propagated fields.  Largest displacement, pyramid,
+ * census, border costs and the finishing step are unchanged; ModFlowParams keeps its layout.  Any other value:
+ * MOD_ERR_INVALID_ARGUMENT, and the setting stays as it was. */
+#define MOD_FLOW_SEEDS 5
+int  mod_set_flow_propagation(ModContext *ctx, int32_t seeds);
+int  mod_get_flow_propagation(const ModContext *ctx, int32_t *seeds);
 
 /* ---- on-GPU stereo ego-motion ---------------------------------------------------------------------------------------------- */
 /* The reference obtains transform_prev2now_ from libviso2 (VisualOdometryStereo::process + getMotion(),

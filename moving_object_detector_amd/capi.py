@@ -33,6 +33,7 @@ MOD_PIPELINE_DEPTH = 3
 MOD_EGO_OK, MOD_EGO_FEW_POINTS, MOD_EGO_FEW_INLIERS, MOD_EGO_DIVERGED = 0, 1, 2, 3
 MOD_EGO_MAX_HYPOTHESES = 4096
 MOD_SGM_FRACTION_BITS = 4
+MOD_FLOW_SEEDS = 5
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
 ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
              "rgba8": MOD_ENCODING_RGBA8}
@@ -54,6 +55,7 @@ EXPORTS = [
     "mod_set_image_layout", "mod_get_image_layout", "mod_image_to_mono_dev",
     "mod_set_disparity_subpixel", "mod_get_disparity_subpixel",
     "mod_set_disparity_filters", "mod_get_disparity_filters", "mod_disparity_speckle_dev",
+    "mod_set_flow_propagation", "mod_get_flow_propagation",
 ]
 
 
@@ -219,6 +221,8 @@ def load(require_torch_first: bool = True):
     L.mod_set_disparity_filters.argtypes = [vp, C.POINTER(ModDisparityFilters)]
     L.mod_get_disparity_filters.argtypes = [vp, C.POINTER(ModDisparityFilters)]
     L.mod_disparity_speckle_dev.argtypes = [vp, i32, vp, i32, i32]
+    L.mod_set_flow_propagation.argtypes = [vp, i32]
+    L.mod_get_flow_propagation.argtypes = [vp, C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

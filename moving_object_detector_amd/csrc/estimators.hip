@@ -319,6 +319,19 @@ int mod_get_disparity_filters(const ModContext *c, ModDisparityFilters *f) {
   return MOD_OK;
 }
 
+int mod_set_flow_propagation(ModContext *c, int32_t seeds) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (seeds != 1 && seeds != MOD_FLOW_SEEDS) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow seeds must be 1 (off) or 5 (the parent and its four neighbours)");
+  c->flow_seeds = seeds;
+  return MOD_OK;
+}
+
+int mod_get_flow_propagation(const ModContext *c, int32_t *seeds) {
+  if (!c || !seeds) return MOD_ERR_INVALID_ARGUMENT;
+  *seeds = c->flow_seeds;
+  return MOD_OK;
+}
+
 int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, int32_t speckle_size, int32_t speckle_range) {
   int rc = check_ready(c, frames);
   if (rc) return rc;
@@ -342,6 +355,7 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   if ((rc = ensure_flow_scratch(c))) return rc;
   Buffers &b = c->b;
   const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
+  const int seeds = c->flow_seeds;                       // the setting of THIS call: every kernel below is enqueued before it returns
   int Wl[kFlowMaxLevels], Hl[kFlowMaxLevels];
   Wl[0] = c->dc.W; Hl[0] = c->dc.H;
   for (int l = 1; l < L; l++) { Wl[l] = Wl[l - 1] >> 1; Hl[l] = Hl[l - 1] >> 1; }
@@ -361,7 +375,7 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   short4 *const sub = p->subpixel ? b.flow_sub.get() : nullptr;
   for (int l = L - 1; l >= 0; l--) {
     const bool coarsest = l == L - 1;
-    launch_flow_match(Wl[l], Hl[l], coarsest ? 0 : Wl[l + 1], coarsest ? 0 : Hl[l + 1], F, dirs, p->window, p->radius, cen(l),
+    launch_flow_match(Wl[l], Hl[l], coarsest ? 0 : Wl[l + 1], coarsest ? 0 : Hl[l + 1], F, dirs, p->window, p->radius, seeds, cen(l),
                       coarsest ? nullptr : b.flow_int + ((l + 1) & 1) * set, b.flow_int + (l & 1) * set, l == 0 ? sub : nullptr, c->stream);
   }
   launch_flow_finish(Wl[0], Hl[0], F, b.flow_int, dirs == 2 ? b.flow_int + (size_t)F * N : nullptr, sub, p->fb_check, flow, c->stream);

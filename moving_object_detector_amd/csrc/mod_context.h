@@ -112,6 +112,7 @@ struct ModContext {
   bool has_layout = false;                  // ... or, while false, mono8 packed at the camera's size
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
+  int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};

@@ -98,8 +98,9 @@ void launch_speckle(int W, int H, int frames, float lo, float invalid, int speck
 // on-GPU optical flow (flow.hip).  Pyramid level of both images: src0 / src1 [frames][Hs][Ws] -> dst [2][frames][H][W].
 void launch_flow_pyramid(int Ws, int Hs, int W, int H, int frames, const uint8_t *src0, const uint8_t *src1, uint8_t *dst, hipStream_t s);
 // one level, `dirs` directions (1: forward, 2: + backward); coarse == nullptr: the coarsest level.  census [2][frames][H][W] (prev, now),
-// coarse [dirs][frames][H1][W1], out [dirs][frames][H][W], sub [frames][H][W] or null
-void launch_flow_match(int W, int H, int W1, int H1, int frames, int dirs, int window, int radius, const uint32_t *census,
+// coarse [dirs][frames][H1][W1], out [dirs][frames][H][W], sub [frames][H][W] or null.  seeds (finer levels): 1 = the parent's winner,
+// 5 = + the winners of the parent's four neighbours (mod_set_flow_propagation)
+void launch_flow_match(int W, int H, int W1, int H1, int frames, int dirs, int window, int radius, int seeds, const uint32_t *census,
                        const short2 *coarse, short2 *out, short4 *sub, hipStream_t s);
 // level 0 winners (+ backward field G when fb >= 0, + sub-pixel terms) -> flow [frames][H][W][2] f32
 void launch_flow_finish(int W, int H, int frames, const short2 *F, const short2 *G, const short4 *sub, int fb, float *flow, hipStream_t s);

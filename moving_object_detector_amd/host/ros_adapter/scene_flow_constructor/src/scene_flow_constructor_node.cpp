@@ -13,6 +13,7 @@
 //                    collect(); the disparity plane stays in HBM as the next frame's previous one (:397-398)
 //   optical flow     on the GPU (libmod_sf's census flow, not PWC-Net) when `~gpu_estimators` is true (default); with it false, the
 //                    CALL-OUT estimateOpticalFlow(): the reference asks pwc_net (:281-291); not part of this package
+//                    `~flow_seeds` (default 1 = off; 5): neighbour-seed propagation of that flow (mod_set_flow_propagation)
 //   camera motion    on the GPU (libmod_sf's stereo ego-motion, not libviso2) when `~gpu_estimators` is true: submitOdometry() /
 //                    collectOdometry() take the images as they arrive (encoding and step from the message, mod_set_image_layout), the
 //                    pose is integrated and odom -> base_link broadcast as integrateAndBroadcastTF does (:246,320-348; frame ids from
@@ -77,6 +78,7 @@ class SceneFlowConstructorNode {
     impl_->setDisparitySubpixel(private_node_handle_.param("disparity_subpixel", false));   // sixteenths of a pixel; the fields of ~depth's source stay
     impl_->setDisparityFilters(private_node_handle_.param("uniqueness_ratio", 0), private_node_handle_.param("speckle_size", 0),
                                private_node_handle_.param("speckle_range", 0));   // stereo_image_proc's names; 0 = off
+    impl_->setFlowPropagation(private_node_handle_.param("flow_seeds", 1));   // 1 = off; 5 = the parent's four neighbours seed the search too
     max_disparity_ = (float)(sgm.disparities - 1);
 
     // every estimator on the GPU (default), or the two CALL-OUTs below; optional centred crop of the incoming images

@@ -72,6 +72,9 @@ class SceneFlowConstructor {
     const ModDisparityFilters f{uniqueness_ratio, speckle_size, speckle_range, 0};
     check(mod_set_disparity_filters(ctx_, &f));
   }
+  // neighbour-seed propagation of the optical flow (mod_set_flow_propagation): 1 = off, the default; 5 = every finer level also tries the
+  // winners of the parent's four neighbours.  Frames already submitted keep the setting of their submit.
+  void setFlowPropagation(int seeds) { check(mod_set_flow_propagation(ctx_, seeds)); }
   bool estimateDisparity(const mod_host::Image *left_image, const mod_host::Image *right_image, const mod_host::CameraInfo &left_camera_info,
                          const mod_host::CameraInfo &right_camera_info, mod_host::DisparityImage *disparity, std::vector<float> *pixels) {
     if (!left_image || !right_image || !left_image->data || !right_image->data) return false;

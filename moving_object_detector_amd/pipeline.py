@@ -117,6 +117,16 @@ class Context:
         self._check(self.lib.mod_get_disparity_filters(self.h, C.byref(f)))
         return {"uniqueness_ratio": f.uniqueness_ratio, "speckle_size": f.speckle_size, "speckle_range": f.speckle_range}
 
+    def set_flow_propagation(self, seeds: int = 1) -> None:
+        """Neighbour-seed propagation of the on-GPU optical flow (mod_set_flow_propagation): 1 = off (the default), 5 = every finer
+        level also tries the winners of the parent's four neighbours.  Takes effect for calls and submits made after it."""
+        self._check(self.lib.mod_set_flow_propagation(self.h, int(seeds)))
+
+    def get_flow_propagation(self) -> int:
+        seeds = C.c_int32(-1)
+        self._check(self.lib.mod_get_flow_propagation(self.h, C.byref(seeds)))
+        return seeds.value
+
     def speckle_filter(self, dev_planes: torch.Tensor, size: int, range: int) -> torch.Tensor:   # noqa: A002 (stereo_image_proc's name)
         """The speckle stage alone, in place (mod_disparity_speckle_dev), on device float32 planes (F, H, W) or (H, W) of the camera's
         size: pixels take part when finite and >= the camera's min_disparity, removed ones become min_disparity - 1.  Enqueued on the

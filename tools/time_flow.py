@@ -1,6 +1,8 @@
 """HIP-event timing of the on-GPU optical flow: mod_flow_compute_dev (default parameters, forward-backward check on) at 1280 x 720 and
 1920 x 1080 for 1 and 8 frames, and the images stream (mod_submit_images_host: SGM disparity + flow + scene flow + clustering per
-frame, three frames in flight) in frames/s.  Prints one JSON line per measurement.  Run on the GPU: python tools/time_flow.py"""
+frame, three frames in flight) in frames/s.  Prints one JSON line per measurement.  Run on the GPU:
+    python tools/time_flow.py [REPS] [--seeds N]        (--seeds 5: mod_set_flow_propagation(5); 1, the default, never calls it)"""
+import argparse
 import ctypes as C
 import json
 import os
@@ -16,7 +18,11 @@ def main():
     import torch
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.pipeline import Context
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    ap = argparse.ArgumentParser()
+    ap.add_argument("reps", nargs="?", type=int, default=50)
+    ap.add_argument("--seeds", type=int, default=1, metavar="N", help="mod_set_flow_propagation: 1 (off) or 5")
+    args = ap.parse_args()
+    reps, seeds = args.reps, args.seeds
     prm = capi.flow_params()
     for W, H in ((1280, 720), (1920, 1080)):
         m = synth.make_moving_images(W, H, seed=1, n_boxes=4)
@@ -24,6 +30,8 @@ def main():
             ctx = Context(W, H, max_frames=F)
             ctx.set_camera(synth.make_camera(W, H))
             ctx.set_params(synth.Params())
+            if seeds != 1:
+                ctx.set_flow_propagation(seeds)
             dev = ctx.device
             tp = torch.from_numpy(np.stack([m["left0"]] * F)).to(dev)
             tn = torch.from_numpy(np.stack([m["left1"]] * F)).to(dev)
@@ -39,7 +47,7 @@ def main():
             b.record()
             b.synchronize()
             ms = a.elapsed_time(b) / reps
-            print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "ms_per_call": round(ms, 4),
+            print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "seeds": seeds, "ms_per_call": round(ms, 4),
                               "ms_per_frame": round(ms / F, 4)}), flush=True)
             ctx.close()
         # the images stream
@@ -48,6 +56,8 @@ def main():
         cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
         ctx.set_camera(cam)
         ctx.set_params(synth.Params())
+        if seeds != 1:
+            ctx.set_flow_propagation(seeds)
         sp = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
         tf = capi.transforms_array(np.zeros((1, 3)), np.array([[0.0, 0.0, 0.0, 1.0]]))
         pins = []
@@ -80,7 +90,7 @@ def main():
         while pending:
             assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) == 0
         dt = time.perf_counter() - t0
-        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "frames_per_s": round(frames / dt, 1),
+        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "frames_per_s": round(frames / dt, 1),
                           "ms_per_frame": round(1e3 * dt / frames, 3)}), flush=True)
         for p in pins:
             ctx.lib.mod_host_free(ctx.h, p)
