@@ -390,6 +390,60 @@ int  mod_set_image_layout(ModContext *ctx, const ModImageLayout *layout);
 int  mod_get_image_layout(const ModContext *ctx, ModImageLayout *layout);
 int  mod_image_to_mono_dev(ModContext *ctx, int32_t frames, const uint8_t *src, const ModImageLayout *layout, uint8_t *mono);
 
+/* ---- raw camera images: rectification on the GPU ---------------------------------------------------------------------------- */
+/* The reference's launch files subscribe to image_rect_color: something upstream (image_proc, the ZED SDK) has rectified.  With a
+ * rectification set, the library does that step itself, so the *_host image entry points take RAW, distorted messages.  Opt-in,
+ * context state like the image layout; off by default, and while off every call enqueues exactly what it did before.
+ * A ModRectifyCamera is what the sensor_msgs/CameraInfo of the raw image carries: width, height (the raw message's size, which is also
+ * the rectified image's, as image_proc makes it); K (fx = K[0], fy = K[4], cx = K[2], cy = K[5]; the skew K[1] must be 0);
+ * D = k1 k2 p1 p2 k3 k4 k5 k6 (plumb_bob: the first five, the rest 0; rational_polynomial: all eight); R, the rectifying rotation;
+ * P (fx' = P[0], fy' = P[5], cx' = P[2], cy' = P[6]).  The context's W x H window at the layout's (x0, y0) is a window of the
+ * RECTIFIED image (image_crop runs behind the rectifier); the P given to mod_set_camera stays the cropped one.
+ * Map (f64 on the host, operations in this order, no contraction; tests/models/rectify_model.py restates it bit for bit), for window
+ * pixel (u, v) with U = u + x0, V = v + y0:
+ *   x = (U - cx') / fx';  y = (V - cy') / fy'
+ *   X = R[0]*x + R[3]*y + R[6];  Y = R[1]*x + R[4]*y + R[7];  Wd = R[2]*x + R[5]*y + R[8];  x = X / Wd;  y = Y / Wd
+ *   x2 = x*x; y2 = y*y; r2 = x2 + y2; xy2 = 2.0*x*y
+ *   kr = (1.0 + ((k3*r2 + k2)*r2 + k1)*r2) / (1.0 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *   xd = x*kr + p1*xy2 + p2*(r2 + 2.0*x2);  yd = y*kr + p1*(r2 + 2.0*y2) + p2*xy2
+ *   mx = fx*xd + cx;  my = fy*yd + cy;  qx = rint(mx * 32.0), qy = rint(my * 32.0)   (half to even)
+ * clamped to [-2^24, 2^24], a non-finite value becomes -2^24: cv::initUndistortRectifyMap on cv::remap's 1/32-pixel grid (parity
+ * with a particular OpenCV build is not claimed).  Sampling, all integers: ix = qx >> 5, ax = qx & 31 (the same for y); taps
+ * p00 = (ix, iy), p01 = (ix+1, iy), p10 = (ix, iy+1), p11 = (ix+1, iy+1) of the raw message, a tap outside it reads 0 in every
+ * channel; per channel top = (32-ax) p00 + ax p01, bot = (32-ax) p10 + ax p11, val = ((32-ay) top + ay bot + 512) >> 10; colour is
+ * interpolated per channel and then converted to grey as above (image_proc rectifies the colour image, cv_bridge converts).
+ *   mod_set_rectification  both NULL = off; one NULL = error.  While set, mod_sgm_compute_host, mod_submit_stereo_host,
+ *                          mod_submit_images_host and mod_submit_odometry_host rectify `left` with the left map and `right` with the
+ *                          right one, mod_flow_compute_host both images with the left one; the WHOLE message (height * step bytes)
+ *                          crosses PCIe.  The _dev estimator calls take grey planes and are untouched.
+ *   mod_get_rectification  *enabled and, when set, the calibrations (left / right may be NULL)
+ *   mod_rectify_dev        as mod_image_to_mono_dev, rectified with the map of `eye`; layout NULL = the context's
+ *   mod_rectify_map_host   the map of `eye` for the window of `layout` (NULL = the context's): host int32 [H][W][2] (qx, qy)
+ *                          Each eye holds ONE map.  Either of these two calls with a layout whose window differs from the one the
+ *                          *_host calls and submits use replaces that eye's map: the next of those rebuilds it (a stream
+ *                          synchronise, the f64 map on the host, one copy), and while tickets are outstanding such a call is
+ *                          refused.  Trace maps with the layout in force, or on a context of their own.
+ * A map is built for the window in force (message size, x0, y0, W, H), cached, and rebuilt at the next use after any of those or the
+ * calibration changed.  A map that a frame in flight reads is never overwritten: mod_set_rectification, and any call that would
+ * rebuild a map, is refused (MOD_ERR_INVALID_ARGUMENT) while tickets are outstanding; otherwise they wait for the context's stream.
+ * MOD_ERR_INVALID_ARGUMENT: non-finite entries; fx, fy, fx', fy' <= 0; K[1] != 0; width or height < 1 or > MOD_MAX_WIDTH; R with an
+ * entry of R R^T - I above 1e-6 in magnitude (the setting stays as it was); an invalid eye; at call time a layout whose width /
+ * height differ from the calibration's.  MOD_ERR_NOT_CONFIGURED: no camera, or (mod_rectify_dev, mod_rectify_map_host) no
+ * rectification set. */
+typedef struct ModRectifyCamera {   /* 312 bytes */
+  int32_t width, height;
+  double  K[9];
+  double  D[8];
+  double  R[9];
+  double  P[12];
+} ModRectifyCamera;
+#define MOD_EYE_LEFT  0
+#define MOD_EYE_RIGHT 1
+int  mod_set_rectification(ModContext *ctx, const ModRectifyCamera *left, const ModRectifyCamera *right);
+int  mod_get_rectification(const ModContext *ctx, ModRectifyCamera *left, ModRectifyCamera *right, int32_t *enabled);
+int  mod_rectify_dev(ModContext *ctx, int32_t frames, const uint8_t *src, const ModImageLayout *layout, int32_t eye, uint8_t *mono);
+int  mod_rectify_map_host(ModContext *ctx, int32_t eye, const ModImageLayout *layout, int32_t *map_qxqy);
+
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()
  * would publish nothing.  cloud_aos: W*H*32 bytes; labels: W*H int32; objects: capacity `max_objects`.

@@ -34,6 +34,8 @@ MOD_EGO_OK, MOD_EGO_FEW_POINTS, MOD_EGO_FEW_INLIERS, MOD_EGO_DIVERGED = 0, 1, 2,
 MOD_EGO_MAX_HYPOTHESES = 4096
 MOD_SGM_FRACTION_BITS = 4
 MOD_FLOW_SEEDS = 5
+MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
+MOD_MAX_WIDTH = 16384
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
 ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
              "rgba8": MOD_ENCODING_RGBA8}
@@ -56,6 +58,7 @@ EXPORTS = [
     "mod_set_disparity_subpixel", "mod_get_disparity_subpixel",
     "mod_set_disparity_filters", "mod_get_disparity_filters", "mod_disparity_speckle_dev",
     "mod_set_flow_propagation", "mod_get_flow_propagation",
+    "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
 ]
 
 
@@ -156,12 +159,34 @@ def centred_window(msg_w: int, msg_h: int, W: int, H: int):
     return (msg_w - W) // 2, (msg_h - H) // 2
 
 
+class ModRectifyCamera(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("K", C.c_double * 9), ("D", C.c_double * 8), ("R", C.c_double * 9),
+                ("P", C.c_double * 12)]
+
+
+def rectify_camera(width: int, height: int, K, D, R, P) -> ModRectifyCamera:
+    """ModRectifyCamera from the fields of the raw image's sensor_msgs/CameraInfo: K (9), R (9), P (12) row-major (flat or nested),
+    D = k1 k2 p1 p2 [k3 [k4 k5 k6]] (plumb_bob: five, rational_polynomial: eight; shorter ones are padded with zeros)."""
+    def flat(v, n, name):
+        out = [float(x) for row in v for x in (row if hasattr(row, "__len__") else [row])]
+        if len(out) != n:
+            raise ValueError(f"{name} must have {n} entries")
+        return out
+    d = [float(x) for x in D]
+    if len(d) > 8:
+        raise ValueError("D has at most 8 coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+    d += [0.0] * (8 - len(d))
+    return ModRectifyCamera(int(width), int(height), (C.c_double * 9)(*flat(K, 9, "K")), (C.c_double * 8)(*d),
+                            (C.c_double * 9)(*flat(R, 9, "R")), (C.c_double * 12)(*flat(P, 12, "P")))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
 
 MOD_OBJECT_BYTES = C.sizeof(ModObject)
 assert MOD_OBJECT_BYTES == 112
+assert C.sizeof(ModRectifyCamera) == 312
 
 
 class ModError(RuntimeError):
@@ -223,6 +248,10 @@ def load(require_torch_first: bool = True):
     L.mod_disparity_speckle_dev.argtypes = [vp, i32, vp, i32, i32]
     L.mod_set_flow_propagation.argtypes = [vp, i32]
     L.mod_get_flow_propagation.argtypes = [vp, C.POINTER(i32)]
+    L.mod_set_rectification.argtypes = [vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)]
+    L.mod_get_rectification.argtypes = [vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(i32)]
+    L.mod_rectify_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), i32, vp]
+    L.mod_rectify_map_host.argtypes = [vp, i32, C.POINTER(ModImageLayout), vp]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

@@ -113,6 +113,19 @@ struct ModContext {
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
   int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
+  // mod_set_rectification: the calibrations and, per eye, the map in HBM with the window it was built for (ensure_rectify_map builds
+  // it at the next use after the window or the calibration changed, never under a frame in flight)
+  struct Rectify {
+    bool on = false;
+    ModRectifyCamera cam[2]{};
+    struct Map {
+      DevPtr<int32_t> q;                      // [H][W][2], allocated on first use for maxN pixels
+      bool valid = false;
+      int32_t width = 0, height = 0, x0 = 0, y0 = 0, W = 0, H = 0;
+    } map[2];
+  } rect;
+  // whole raw messages on their way to k_rectify: two of the layout in force (allocated on first use, grow-only)
+  struct RawStage { DevPtr<uint8_t> buf; size_t bytes = 0; };
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -128,7 +141,7 @@ struct ModContext {
     DevPtr<ModObject> objects;
   };
   // one-frame staging of the synchronous entry points (allocated on first use; ready: the last allocation has succeeded)
-  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; } staging;
+  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; RawStage raw; } staging;
   // host streaming (mod_submit_frame_host and the mod_submit_*_host image entries): a slot per ticket, a ring of MOD_PIPELINE_DEPTH + 1
   // planes (frame t's plane is frame t+1's "previous"), two copy streams and the events and fences that order them with the kernels
   struct Pipe {
@@ -149,6 +162,7 @@ struct ModContext {
       // k_to_mono turns them into grey in img / the plane's left image on the context's stream, behind every older reader of those
       DevPtr<uint8_t> stage;
       Fence stage_read;                              // ... the kernels that read them have been enqueued (context stream)
+      RawStage raw;                                  // with a rectification set: the slot's two raw messages instead, behind the same fence
       // mod_submit_odometry_host: the slot's estimate on the device (its element of Pipe::ego, last copied out before the slot's
       // previous ticket was collected) and its pinned host copy; collect reads the status
       EgoSlot *ego = nullptr;
@@ -241,6 +255,11 @@ void refresh_devcam(ModContext *c);
 // the layout the host image entry points read (the set one, or mono8 packed W x H), checked against the camera
 int current_layout(ModContext *c, ModImageLayout *out);
 int check_layout(ModContext *c, const ModImageLayout &l);
+// with a rectification set (the caller has checked that, and eye): the map of `eye` for the window of `l` is in c->rect.map[eye].q when this returns MOD_OK (built, behind
+// the context's stream, unless it is the cached one; refused while tickets are outstanding)
+int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l);
+// room for two raw messages of `l` in r; a buffer that has to grow is replaced once the context's streams have drained
+int ensure_raw_stage(ModContext *c, ModContext::RawStage &r, const ModImageLayout &l);
 int begin_cluster_scratch(ModContext *c);
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                 const ModClusterOut *out);

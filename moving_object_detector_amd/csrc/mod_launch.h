@@ -134,3 +134,10 @@ void launch_egomotion(const EgoArgs &a, hipStream_t s);
 int image_channels(int encoding);   // 0: unknown encoding
 void launch_to_mono(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int x0, int y0, uint8_t *dst,
                     hipStream_t s);
+
+// raw camera images to rectified grey (rectify.hip).  map: device int32 [H][W][2], where each pixel of the W x H window lies in the
+// width x height message (1/32 pixel; build_rectify_map fills a host copy for the window at (x0, y0)) -> dst [frames][H][W]
+void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int width, int height,
+                    const int32_t *map, uint8_t *dst, hipStream_t s);
+void build_rectify_map(const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map);
+const char *check_rectify_camera(const ModRectifyCamera &cam);   // null: valid, else what is wrong with it

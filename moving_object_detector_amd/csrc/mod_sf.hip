@@ -265,6 +265,38 @@ int current_layout(ModContext *c, ModImageLayout *out) {
   return check_layout(c, *out);   // the camera may have changed since the layout was set
 }
 
+// (callers have checked that a rectification is set and that eye is one of the two)
+int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l) {
+  const ModRectifyCamera &cam = c->rect.cam[eye];
+  if (l.width != cam.width || l.height != cam.height)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the image layout's width / height differ from the rectification's");
+  ModContext::Rectify::Map &m = c->rect.map[eye];
+  const int W = c->dc.W, H = c->dc.H;
+  if (m.valid && m.width == l.width && m.height == l.height && m.x0 == l.x0 && m.y0 == l.y0 && m.W == W && m.H == H) return MOD_OK;
+  if (c->pipe.in_flight > 0)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the rectification map must be rebuilt while frames are in flight: collect every ticket first");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // kernels of calls and of frames that ended at a guard may still read the old map
+  HIP_TRY(c, dalloc(m.q, 2 * c->maxN));
+  m.valid = false;
+  std::vector<int32_t> host(2 * (size_t)W * H);
+  build_rectify_map(cam, l.x0, l.y0, W, H, host.data());
+  HIP_TRY(c, hipMemcpyAsync(m.q, host.data(), sizeof(int32_t) * host.size(), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));   // `host` is stack-owned
+  m.width = l.width; m.height = l.height; m.x0 = l.x0; m.y0 = l.y0; m.W = W; m.H = H;
+  m.valid = true;
+  return MOD_OK;
+}
+
+int ensure_raw_stage(ModContext *c, ModContext::RawStage &r, const ModImageLayout &l) {
+  const size_t need = 2 * (size_t)l.step * l.height;
+  if (r.bytes >= need) return MOD_OK;
+  for (hipStream_t q : {c->stream, (hipStream_t)c->pipe.h2d}) if (q) HIP_TRY(c, hipStreamSynchronize(q));
+  r.buf.reset(); r.bytes = 0;
+  HIP_TRY(c, dalloc(r.buf, need));
+  r.bytes = need;
+  return MOD_OK;
+}
+
 void refresh_devcam(ModContext *c) {
   DevCam &d = c->dc;
   d.W = c->cam.width; d.H = c->cam.height;
@@ -495,6 +527,61 @@ int mod_image_to_mono_dev(ModContext *c, int32_t frames, const uint8_t *src, con
   if (layout) l = *layout;
   launch_to_mono(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.x0, l.y0, mono, c->stream);
   HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_set_rectification(ModContext *c, const ModRectifyCamera *left, const ModRectifyCamera *right) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!left != !right) return fail(c, MOD_ERR_INVALID_ARGUMENT, "rectification: both eyes or neither");
+  for (const ModRectifyCamera *cam : {left, right})
+    if (const char *what = cam ? check_rectify_camera(*cam) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, what);
+  if (c->pipe.in_flight > 0)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the rectification cannot change while frames are in flight: collect every ticket first");
+  c->rect.on = left != nullptr;
+  if (left) { c->rect.cam[MOD_EYE_LEFT] = *left; c->rect.cam[MOD_EYE_RIGHT] = *right; }
+  for (ModContext::Rectify::Map &m : c->rect.map) m.valid = false;   // rebuilt at the next use, behind the context's stream
+  return MOD_OK;
+}
+
+int mod_get_rectification(const ModContext *c, ModRectifyCamera *left, ModRectifyCamera *right, int32_t *enabled) {
+  if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
+  *enabled = c->rect.on;
+  if (c->rect.on && left) *left = c->rect.cam[MOD_EYE_LEFT];
+  if (c->rect.on && right) *right = c->rect.cam[MOD_EYE_RIGHT];
+  return MOD_OK;
+}
+
+// the layout a rectifying call works on (the given one, or the context's) and the map of `eye` for its window
+static int rectify_setup(ModContext *c, const ModImageLayout *layout, int32_t eye, ModImageLayout *l) {
+  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
+  if (eye != MOD_EYE_LEFT && eye != MOD_EYE_RIGHT) return fail(c, MOD_ERR_INVALID_ARGUMENT, "eye must be MOD_EYE_LEFT or MOD_EYE_RIGHT");
+  if (!c->rect.on) return fail(c, MOD_ERR_NOT_CONFIGURED, "no rectification is set");
+  int rc = layout ? check_layout(c, *layout) : current_layout(c, l);
+  if (rc) return rc;
+  if (layout) *l = *layout;
+  return ensure_rectify_map(c, eye, *l);
+}
+
+int mod_rectify_dev(ModContext *c, int32_t frames, const uint8_t *src, const ModImageLayout *layout, int32_t eye, uint8_t *mono) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (frames < 1 || frames > 65535) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be in 1..65535");
+  ModImageLayout l;
+  if (int rc = rectify_setup(c, layout, eye, &l)) return rc;
+  if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
+  launch_rectify(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.width, l.height, c->rect.map[eye].q, mono,
+                 c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_rectify_map_host(ModContext *c, int32_t eye, const ModImageLayout *layout, int32_t *map_qxqy) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!map_qxqy) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null map");
+  ModImageLayout l;
+  if (int rc = rectify_setup(c, layout, eye, &l)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(map_qxqy, c->rect.map[eye].q, sizeof(int32_t) * 2 * (size_t)c->dc.W * c->dc.H, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MOD_OK;
 }
 

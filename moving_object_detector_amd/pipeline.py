@@ -127,6 +127,19 @@ class Context:
         self._check(self.lib.mod_get_flow_propagation(self.h, C.byref(seeds)))
         return seeds.value
 
+    def set_rectification(self, left: Optional[capi.ModRectifyCamera] = None, right: Optional[capi.ModRectifyCamera] = None) -> None:
+        """Rectification of raw camera images on the GPU (mod_set_rectification): the calibrations of the two eyes
+        (capi.rectify_camera), or neither = off (the default).  While set, the *_host image entry points take raw messages.  Refused
+        while tickets are outstanding."""
+        self._check(self.lib.mod_set_rectification(self.h, C.byref(left) if left is not None else None,
+                                                   C.byref(right) if right is not None else None))
+
+    def get_rectification(self):
+        """(left, right) ModRectifyCamera of the rectification in force, or None while it is off."""
+        l, r, on = capi.ModRectifyCamera(), capi.ModRectifyCamera(), C.c_int32(-1)
+        self._check(self.lib.mod_get_rectification(self.h, C.byref(l), C.byref(r), C.byref(on)))
+        return (l, r) if on.value else None
+
     def speckle_filter(self, dev_planes: torch.Tensor, size: int, range: int) -> torch.Tensor:   # noqa: A002 (stereo_image_proc's name)
         """The speckle stage alone, in place (mod_disparity_speckle_dev), on device float32 planes (F, H, W) or (H, W) of the camera's
         size: pixels take part when finite and >= the camera's min_disparity, removed ones become min_disparity - 1.  Enqueued on the
@@ -258,6 +271,33 @@ class Context:
         rc = self._check(self.lib.mod_image_to_mono_dev(self.h, F, src.data_ptr(), C.byref(lay), out.data_ptr()))
         if rc != 0:
             raise capi.ModError(rc, "mod_image_to_mono_dev skipped")
+        return out
+
+    def rectify(self, src: torch.Tensor, layout: Optional[capi.ModImageLayout] = None, eye: int = capi.MOD_EYE_LEFT,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Rectified grey planes (F, H, W) uint8 at the camera size from raw device 8-bit frames (mod_rectify_dev): `src` as for
+        image_to_mono, `eye` selects the map (capi.MOD_EYE_LEFT / MOD_EYE_RIGHT).  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_image_layout()
+        if src.dtype != torch.uint8 or not src.is_contiguous() or src.device.type != "cuda":
+            raise ValueError("src must be a contiguous uint8 device tensor")
+        frame = lay.step * lay.height
+        if frame <= 0 or src.numel() % frame:
+            raise ValueError("src must hold whole frames of step * height bytes")
+        F = src.numel() // frame
+        if out is None:
+            out = torch.empty((F, self.height, self.width), dtype=torch.uint8, device=src.device)
+        elif out.shape != (F, self.height, self.width) or out.dtype != torch.uint8 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 tensor (F, H, W)")
+        rc = self._check(self.lib.mod_rectify_dev(self.h, F, src.data_ptr(), C.byref(lay), int(eye), out.data_ptr()))
+        if rc != 0:
+            raise capi.ModError(rc, "mod_rectify_dev skipped")
+        return out
+
+    def rectification_map(self, eye: int = capi.MOD_EYE_LEFT, layout: Optional[capi.ModImageLayout] = None) -> np.ndarray:
+        """The map k_rectify reads for `eye` and the window of `layout` (None = the context's), from the device
+        (mod_rectify_map_host): (H, W, 2) int32, (qx, qy) in 1/32 pixel of the raw message."""
+        out = np.empty((self.height, self.width, 2), dtype=np.int32)
+        self._check(self.lib.mod_rectify_map_host(self.h, int(eye), C.byref(layout) if layout is not None else None, out.ctypes.data))
         return out
 
     def estimate_egomotion(self, disp_prev: torch.Tensor, disp_now: torch.Tensor, flow: torch.Tensor,

@@ -1,0 +1,179 @@
+"""HIP-event timing of the on-GPU rectification (mod_rectify_dev, csrc/rectify.hip) on 64 frames of 1920 x 1080 for every encoding,
+beside the plain conversion (mod_image_to_mono_dev, csrc/ingest.hip) of the same frames in the same run (it moves the same image
+bytes without the map), in bytes in + map + out per second against the HBM's 8 TB/s; and the odometry stream
+(mod_submit_odometry_host) at 1280 x 720 fed bgra8 messages from page-locked memory without a rectification and with the identity
+calibration (the same grey planes reach the estimators, so the two legs differ by the rectification stage alone), in frames/s.
+k_rectify has two paths, a source box staged in LDS and direct gathers from global memory; the product picks one
+(csrc/rectify.hip kStagedDefault).  The measurement builds that pin each path are timed as further legs in the same rounds, and
+their grey planes are compared with the product's bit for bit:
+  make -C moving_object_detector_amd/csrc EXTRA=-DMOD_RECTIFY_DIRECT OUT=../libmod_sf_rectify_direct.so lib
+  make -C moving_object_detector_amd/csrc EXTRA=-DMOD_RECTIFY_STAGED OUT=../libmod_sf_rectify_staged.so lib
+A build that is missing is recorded as missing.  Prints one JSON line per measurement and appends them to profiles/rectify_time.jsonl.
+Run on the GPU: python tools/time_rectify.py [reps] [kernel]   (kernel: the kernel legs only, for a rocprofv3 --kernel-trace run)"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_TBPS = 8.0
+OUT = os.path.join(ROOT, "profiles", "rectify_time.jsonl")
+
+
+def emit(rec):
+    line = json.dumps(rec)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "a") as f:
+        f.write(line + "\n")
+
+
+def zed_like(capi, w, h, eye):
+    """k1 about -0.17, a small rectifying rotation, P's focal a little below K's (a ZED's 1080p calibration in round numbers)."""
+    s = 1.0 if eye == 0 else -1.0
+    a, b, c = 0.003 * s, -0.004, 0.002 * s
+    ca, sa, cb, sb, cc, sc = np.cos(a), np.sin(a), np.cos(b), np.sin(b), np.cos(c), np.sin(c)
+    R = np.array([[cc, -sc, 0], [sc, cc, 0], [0, 0, 1]]) @ np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]]) @ np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]])
+    f = 1400.0 * w / 1920.0
+    K = [f + 0.3, 0, 0.5 * w + 11.2 * s, 0, f - 0.9, 0.5 * h - 7.9, 0, 0, 1]
+    P = [0.964 * f, 0, 0.5 * w, -0.12 * 0.964 * f * (eye != 0), 0, 0.964 * f, 0.5 * h, 0, 0, 0, 1, 0]
+    return capi.rectify_camera(w, h, K, [-0.172 + 0.003 * s, 0.026, 0.0004 * s, -0.0003, 0.0012], R.ravel(), P)
+
+
+def timed(torch, call, reps):
+    for _ in range(3):
+        assert call() == 0
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        call()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def kernel(reps):
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    W, H, F = 1920, 1080, 64
+
+    def context():
+        c = Context(W, H, max_frames=1)
+        c.set_camera(synth.make_camera(W, H))
+        c.set_rectification(zed_like(capi, W, H, 0), zed_like(capi, W, H, 1))
+        return c
+
+    ctx = context()
+    legs = [("k_to_mono", ctx, False), ("k_rectify", ctx, True)]
+    for path_name in ("direct", "staged"):         # second copies of the library in this process, with contexts of their own
+        build = os.path.join(os.path.dirname(capi.LIB_PATH), f"libmod_sf_rectify_{path_name}.so")
+        what = f"k_rectify ({path_name} path, measurement build)"
+        if os.path.exists(build):
+            product = (capi.LIB_PATH, capi._lib)
+            capi.LIB_PATH, capi._lib = build, None
+            legs.append((what, context(), True))
+            capi.LIB_PATH, capi._lib = product
+        else:
+            emit({"what": what, "missing": os.path.relpath(build, ROOT), "note": "not built: this run has no such leg"})
+    out = torch.empty((F, H, W), dtype=torch.uint8, device=ctx.device)
+    for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8"):
+        lay = capi.image_layout(enc, W, H)
+        Cn = capi.CHANNELS[lay.encoding]
+        src = torch.randint(0, 256, (F * lay.step * lay.height,), dtype=torch.uint8, device=ctx.device)
+        ms, same, first = {}, {}, None
+        for rnd in range(2):                       # the kernels alternate, twice: the spread is part of the record
+            for what, c, rect in legs:
+                call = ((lambda c=c: c.lib.mod_rectify_dev(c.h, F, src.data_ptr(), C.byref(lay), 0, out.data_ptr())) if rect else
+                        (lambda c=c: c.lib.mod_image_to_mono_dev(c.h, F, src.data_ptr(), C.byref(lay), out.data_ptr())))
+                ms.setdefault(what, []).append(timed(torch, call, reps))
+                if rect and rnd == 0:              # every path computes the same planes
+                    torch.cuda.synchronize()
+                    planes = out.clone()
+                    same[what] = True if first is None else bool(torch.equal(planes, first))
+                    first = planes if first is None else first
+        for what, _, rect in legs:
+            per_px = Cn + 8 + 1 if rect else Cn + 1
+            best = min(ms[what])
+            tbps = F * W * H * per_px / (best * 1e-3) / 1e12
+            emit({"what": what, "encoding": enc, "W": W, "H": H, "frames": F, "reps": reps, "bytes_per_px": per_px,
+                  "ms_per_call": [round(v, 4) for v in ms[what]], "TB_per_s": round(tbps, 3), "of_hbm": round(tbps / HBM_TBPS, 3),
+                  "vs_k_to_mono": round(best / min(ms["k_to_mono"]), 2), **({"same_planes_as_product": same[what]} if rect else {})})
+        del src
+    for c in {id(c): c for _, c, _ in legs}.values():
+        c.close()
+
+
+def stream_fps(W, H, reps, rectify):
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    m = synth.make_ego_images(W, H, seed=1, frames=2)
+    ctx = Context(W, H, max_frames=1)
+    cam = synth.make_camera(W, H)
+    cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
+    ctx.set_camera(cam)
+    ctx.set_params(synth.Params())
+    if rectify:
+        f = 0.55 * W + 0.5
+        ident = capi.rectify_camera(W, H, [f, 0, 0.5 * W + 0.3, 0, f, 0.5 * H - 0.3, 0, 0, 1], [], [1, 0, 0, 0, 1, 0, 0, 0, 1],
+                                    [f, 0, 0.5 * W + 0.3, 0, 0, f, 0.5 * H - 0.3, 0, 0, 0, 1, 0])
+        ctx.set_rectification(ident, ident)
+    sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
+    imgs, pins = [], []
+    for k in ("left0", "right0", "left1", "right1"):
+        msg, lay, _ = synth.to_colour(m[k], "bgra8", seed=1)
+        p = C.c_void_p()
+        assert ctx.lib.mod_host_malloc(ctx.h, msg.nbytes, C.byref(p)) == 0
+        C.memmove(p.value, msg.ctypes.data, msg.nbytes)
+        pins.append(p)
+        imgs.append(p.value)
+    ctx.set_image_layout(capi.image_layout(lay["encoding"], lay["width"], lay["height"], lay["step"]))
+    objs = [(capi.ModObject * 64)() for _ in range(3)]
+    t, n = C.c_int32(-1), C.c_int32(-1)
+    pending = []
+
+    def step(i):
+        l, r = (imgs[0], imgs[1]) if i % 2 == 0 else (imgs[2], imgs[3])
+        if len(pending) == 3:
+            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
+        rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
+                                              None, None, None, None, C.byref(t))
+        assert rc in (0, capi.MOD_SKIP_NO_FLOW), (rc, ctx.lib.mod_last_error(ctx.h))
+        if rc == 0:
+            pending.append(t.value)
+
+    for i in range(10):
+        step(i)
+    frames = max(20, reps)
+    t0 = time.perf_counter()
+    for i in range(10, 10 + frames):
+        step(i)
+    while pending:
+        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
+    dt = time.perf_counter() - t0
+    for p in pins:
+        ctx.lib.mod_host_free(ctx.h, p)
+    ctx.close()
+    return frames / dt
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    kernel(reps)
+    if "kernel" in sys.argv[2:]:
+        return
+    for rnd in range(2):
+        for rectify in (False, True):
+            fps = stream_fps(1280, 720, min(reps, 100), rectify)
+            emit({"what": "mod_submit_odometry_host", "encoding": "bgra8", "host_memory": "pinned", "rectification": "identity" if rectify else "off", "round": rnd,
+                  "W": 1280, "H": 720, "frames_per_s": round(fps, 1)})
+
+
+if __name__ == "__main__":
+    main()
