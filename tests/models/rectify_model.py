@@ -123,3 +123,50 @@ def rectify(buf, layout, qmap, frames: int = 1) -> np.ndarray:
         return val[..., 0].astype(np.uint8)
     b, g, r = im.ORDER[enc]
     return im.grey(val[..., b], val[..., g], val[..., r])
+
+
+# ---- which tap path k_rectify<Enc, Staged = true> takes, tile by tile ----------------------------------------------------------------
+RUN, TILE_RUNS, TILE_ROWS, TILE_DWORDS = 4, 16, 16, 4096
+Tile = namedtuple("Tile", "box rows pitch outcome")     # box (x0, x1, y0, y1) of message pixels, or None; outcome border / staged / fallback
+
+
+def tile_of(x, y, W, dst_off):
+    """(by, bx) of the workgroup that makes frame 0's output pixel (x, y): run r of row y covers x in [head + 4 (r - 1), head + 4 r),
+    head = (-(base + dst_off + y W)) & 3 with the planes' allocation (base) 4-aligned; a workgroup is 16 runs x 16 rows."""
+    x, y = np.asarray(x, np.int64), np.asarray(y, np.int64)
+    head = (-(dst_off + y * W)) & (RUN - 1)
+    r = (x - head) // RUN + 1                               # (floor: the pixels in front of the first dword boundary are run 0)
+    return y // TILE_ROWS, r // TILE_RUNS
+
+
+def staged_plan(qmap, layout, dst_off=0):
+    """{(by, bx): Tile} for every workgroup of frame 0, restating the kernel's box arithmetic: the box is the hull of the taps
+    max(ix, 0) .. min(ix + 1, width - 1) x max(iy, 0) .. min(iy + 1, height - 1) of the tile's pixels (a pixel with an empty range in
+    either axis has no tap inside the message); rows = y1 - y0 + 1, nd = (row_bytes + 3) // 4 + 1, pitch = nd + 2; staged if and only
+    if rows * pitch <= 4096 dwords (16 KiB of LDS), else the tile falls back to direct gathers; no tap inside: border."""
+    H, W = qmap.shape[:2]
+    C = im.CHANNELS[im.encoding_of(layout.encoding)]
+    qx, qy = qmap[..., 0].astype(np.int64), qmap[..., 1].astype(np.int64)
+    ix, iy = qx >> 5, qy >> 5
+    xa, xb = np.maximum(ix, 0), np.minimum(ix + 1, layout.width - 1)
+    ya, yb = np.maximum(iy, 0), np.minimum(iy + 1, layout.height - 1)
+    has = (xa <= xb) & (ya <= yb)
+    by, bx = tile_of(np.arange(W)[None, :] + np.zeros((H, 1), np.int64), np.arange(H)[:, None] + np.zeros((1, W), np.int64), W, dst_off)
+    runs = (W + RUN - 1) // RUN + 1
+    ny, nx = (H + TILE_ROWS - 1) // TILE_ROWS, (runs + TILE_RUNS - 1) // TILE_RUNS
+    far = np.iinfo(np.int64).max
+    lo = np.full((4, ny * nx), far)                         # minima of x0, -x1, y0, -y1 per tile, as the kernel keeps them
+    t = (by * nx + bx)[has]
+    for k, v in enumerate((xa, -xb, ya, -yb)):
+        np.minimum.at(lo[k], t, v[has])
+    plan = {}
+    for j in range(ny):
+        for i in range(nx):
+            x0, x1, y0, y1 = (int(v) for v in lo[:, j * nx + i] * (1, -1, 1, -1))
+            if x0 == far:
+                plan[(j, i)] = Tile(None, 0, 0, "border")
+                continue
+            rows, row_bytes = y1 - y0 + 1, (x1 - x0 + 1) * C
+            pitch = (row_bytes + 3) // 4 + 1 + 2
+            plan[(j, i)] = Tile((x0, x1, y0, y1), rows, pitch, "staged" if rows * pitch <= TILE_DWORDS else "fallback")
+    return plan

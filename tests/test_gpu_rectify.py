@@ -1,7 +1,7 @@
 """GPU: the rectification stage (csrc/rectify.hip) bit for bit against tests/models/rectify_model.py — the f64 map through
 mod_rectify_map_host, k_rectify through mod_rectify_dev (every encoding, widths around the 4-pixel runs and the 64 x 16 workgroup tile,
-odd steps, origins and addresses, bytes of the row padding never matter), the identity calibration against mod_image_to_mono_dev,
-1080p, and the *_host image entry points fed raw messages."""
+odd steps, origins and addresses, bytes of the row padding never matter), the cases of tests/rectify_cases.py (the ones the staged
+build runs in tests/test_gpu_rectify_staged.py), the identity calibration against mod_image_to_mono_dev, 1080p, and the *_host image entry points fed raw messages."""
 import ctypes as C
 import os
 import sys
@@ -15,6 +15,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "models"))
 import ingest_model as im  # noqa: E402
 import rectify_model as rm  # noqa: E402
+sys.path.insert(0, HERE)
+import rectify_cases  # noqa: E402
 
 ENCODINGS = ("mono8", "bgr8", "rgb8", "bgra8", "rgba8")
 
@@ -96,6 +98,14 @@ def test_kernel_matches_the_model(W, H):
             b[:, :, mw * Cn:] = fill
             assert np.array_equal(_rectify(ctx, b.ravel(), lay, F, eye, src_off, dst_off), want), (enc, fill)
     ctx.close()
+
+
+@pytest.mark.parametrize("name", rectify_cases.NAMES)
+def test_kernel_cases_on_the_product_build(name):
+    """Every case of tests/rectify_cases.py (the grid with rows around the tile's 16, the identity over the whole message, boxes
+    around 16 KiB, the 9x map, a whole tile of border, the clamps, messages one and two pixels wide or high) through the library the
+    product loads: the direct tap path.  tests/test_gpu_rectify_staged.py runs the same list through the staged path."""
+    rectify_cases.run(rectify_cases.CASES[rectify_cases.NAMES.index(name)], _ctx, _cams)
 
 
 @pytest.mark.parametrize("enc", ENCODINGS)

@@ -1,6 +1,7 @@
 """CPU: tests/models/rectify_model.py, the numpy restatement of the rectification stage (include/mod_sf.h), checked
 against what can be worked out by hand: the identity calibration, a pure half-pixel shift, the clamps, grey in colour, and a plain
-per-pixel loop; the distorted fixture the GPU tests use is shown to reach the message's borders and most of the 1/32 grid."""
+per-pixel loop; the distorted fixture the GPU tests use is shown to reach the message's borders and most of the 1/32 grid; staged_plan
+(which tap path the staged build takes, tile by tile) against a brute force, and the properties the GPU cases rely on."""
 import os
 import sys
 
@@ -176,3 +177,92 @@ def test_remap_parity_with_cv2():
     ref = cv2.remap(img, m1, m2, cv2.INTER_LINEAR, borderMode=cv2.BORDER_CONSTANT)[f["y0"]:f["y0"] + f["H"], f["x0"]:f["x0"] + f["W"]]
     got = rm.rectify(img, _layout("mono8", f["mw"], f["mh"], f["x0"], f["y0"]), rm.build_map(cal, f["x0"], f["y0"], f["W"], f["H"]))[0]
     assert np.abs(got.astype(int) - ref.astype(int)).max() <= 1
+
+
+# ---- staged_plan: which tap path k_rectify's staged build takes, tile by tile -----------------------------------------------------------
+def _brute_plan(qmap, lay, dst_off):
+    """One output pixel and one tap at a time, from taps()'s inside flags: the hull of the taps inside the message per workgroup tile
+    (run r of row y covers x in [head + 4 (r - 1), head + 4 r), 16 runs x 16 rows per tile)."""
+    H, W = qmap.shape[:2]
+    C = im.CHANNELS[im.NAMES[lay.encoding]]
+    ix, iy, _, _, inside = rm.taps(qmap, lay.width, lay.height)
+    runs = (W + 3) // 4 + 1
+    boxes = {(j, i): None for j in range((H + 15) // 16) for i in range((runs + 15) // 16)}
+    for y in range(H):
+        head = (4 - (dst_off + y * W) % 4) % 4
+        for r in range(runs):
+            for x in range(max(0, head + 4 * (r - 1)), min(W, head + 4 * r)):
+                for (dy, dx), ok in zip(((0, 0), (0, 1), (1, 0), (1, 1)), inside):
+                    if ok[y, x]:
+                        tx, ty, b = int(ix[y, x]) + dx, int(iy[y, x]) + dy, boxes[(y // 16, r // 16)]
+                        boxes[(y // 16, r // 16)] = (tx, tx, ty, ty) if b is None else (min(b[0], tx), max(b[1], tx), min(b[2], ty), max(b[3], ty))
+    plan = {}
+    for k, b in boxes.items():
+        if b is None:
+            plan[k] = rm.Tile(None, 0, 0, "border")
+            continue
+        rows, row_bytes = b[3] - b[2] + 1, (b[1] - b[0] + 1) * C
+        dwords = -(-row_bytes // 4) + 1 + 2
+        plan[k] = rm.Tile(b, rows, dwords, "staged" if rows * dwords * 4 <= 16384 else "fallback")
+    return plan
+
+
+def _plan_maps():
+    import rectify_cases as rc
+    nine = rc.CASES[rc.NAMES.index("9x map that is not smooth")]
+    return {"identity": (rm.build_map(rm.identity(67, 19, 70.5, 69.25, 33.3, 9.7), 0, 0, 67, 19), 67, 19),
+            "distorted": (_fixture_maps()[1], FIX["mw"], FIX["mh"]),
+            "nine": (rm.build_map(nine.cals[1], nine.x0, nine.y0, nine.W, nine.H), nine.mw, nine.mh)}
+
+
+@pytest.mark.parametrize("which", ("identity", "distorted", "nine"))
+def test_staged_plan_is_the_brute_force(which):
+    m, mw, mh = _plan_maps()[which]
+    seen = set()
+    for enc, dst_off in (("mono8", 0), ("bgr8", 1), ("rgba8", 3), ("mono8", 2)):
+        lay = _layout(enc, mw, mh, 0, 0, pad=1)
+        plan = rm.staged_plan(m, lay, dst_off)
+        assert plan == _brute_plan(m, lay, dst_off), (enc, dst_off)
+        seen |= {t.outcome for t in plan.values()}
+    assert seen == {"identity": {"staged"}, "distorted": {"staged"}, "nine": {"staged", "fallback"}}[which]
+
+
+def test_tile_of_follows_the_output_address():
+    """head = the pixels of a row in front of the output's first dword boundary: with W = 5 and dst_off = 3, row 0 starts at byte 3
+    (head 1), row 1 at byte 8 (head 0), row 2 at byte 13 (head 3)."""
+    by, bx = rm.tile_of(np.array([0, 1, 0, 2, 3]), np.array([0, 0, 1, 2, 2]), 5, 3)
+    assert by.tolist() == [0] * 5 and bx.tolist() == [0] * 5
+    # run 16 (the second tile column) starts at x = head + 60
+    assert rm.tile_of(60, 0, 130, 3)[1] == 0 and rm.tile_of(61, 0, 130, 3)[1] == 1 and rm.tile_of(60, 0, 130, 4)[1] == 1
+    assert rm.tile_of(0, 15, 130, 0)[0] == 0 and rm.tile_of(0, 16, 130, 0)[0] == 1
+
+
+def test_every_kernel_case_exercises_its_branch():
+    """What the GPU tests rely on (tests/rectify_cases.py): each case's plan shows the outcomes the case is there for, in every
+    encoding; the identity case is k_to_mono's output; all three outcomes and both sides of the 16 KiB limit occur in the list."""
+    import rectify_cases as rc
+    assert len(set(rc.NAMES)) == len(rc.NAMES)
+    seen, offs = set(), set()
+    for case in rc.CASES:
+        assert case.W <= 160 and case.H <= 48
+        for k in range(len(case.encodings)):
+            lay, payload, qmap, want, src_off, dst_off, eye, plan = rc.prepare(case, k)
+            seen |= {t.outcome for t in plan.values()}
+            offs.add((src_off, dst_off))
+            assert 1 <= src_off <= 3 and 1 <= dst_off <= 3 and lay[3] >= case.mw * rc.channels(lay[0])
+            assert want.shape == (rc.F, case.H, case.W) and rc.F == 3
+    assert seen == {"border", "staged", "fallback"}
+    assert {s for s, _ in offs} == {1, 2, 3} and {d for _, d in offs} == {1, 2, 3}
+    grid = [c for c in rc.CASES if c.name.startswith("grid")]
+    assert {(c.W, c.H) for c in grid} >= {(W, H) for W in (2, 3, 15, 17, 63, 64, 65, 130) for H in (1, 7)} | {(W, H) for W in (63, 65) for H in (16, 17, 33)}
+    assert all(rc.layout(c, e)[3] % 2 == 1 for c in grid for e in c.encodings)          # odd, padded steps
+    thin = {(c.mw, c.mh) for c in rc.CASES if c.name.startswith("message")}
+    assert {w for w, _ in thin} >= {1, 2} and {h for _, h in thin} >= {1, 2}
+
+
+def test_the_large_shape_never_falls_back():
+    """the 1080p call of the staged worker: its plan check holds (rectify_cases.large asserts it), and the tiles counted by hand:
+    (1920 / 4 + 1) runs = 31 tile columns x 68 tile rows"""
+    import rectify_cases as rc
+    plan = rc.large()[-1]
+    assert len(plan) == 31 * 68 and {t.outcome for t in plan.values()} <= {"staged", "border"}
