@@ -365,6 +365,12 @@ int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const floa
  * cv_bridge::toCvCopy(..., MONO8) (scene_flow_constructor.cpp:220-221); its ZED launch crops a centred window first
  * (image_crop.cpp:24-40).  A ModImageLayout describes such a message and the camera-sized window (the context's W x H) taken from
  * it.  Grey = OpenCV's 8-bit BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14 (B = G = R = v gives v); alpha is ignored.
+ * Packed YUV 4:2:2, what a UVC camera delivers without a vendor SDK, is taken as it arrives: two bytes per pixel, step >= 2 * width;
+ * MOD_ENCODING_YUV422 (ROS "yuv422") is UYVY, bytes U0 Y0 V0 Y1, the luma of pixel x is byte 2x + 1 of its row;
+ * MOD_ENCODING_YUV422_YUY2 ("yuv422_yuy2") is YUYV, bytes Y0 U0 Y1 V0, the luma of pixel x is byte 2x.  Grey = Y, unchanged (what
+ * cv_bridge's COLOR_YUV2GRAY_UYVY / _YUY2 and image_proc's image_mono do); chroma is never read, and any width and x0 is legal, odd
+ * ones included.  Under rectification Y is interpolated as one channel, like mono8: parity with "convert to BGR, rectify, convert to
+ * grey" is not claimed.
  *   mod_set_image_layout   the layout of the HOST images every *_host image entry point reads (mod_sgm_compute_host,
  *                          mod_flow_compute_host, mod_submit_stereo_host, mod_submit_images_host, mod_submit_odometry_host),
  *                          read at call time like mod_set_params: a frame in flight completes with the layout of its own submit.
@@ -373,6 +379,7 @@ int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const floa
  *   mod_get_image_layout   the layout in force (the NULL layout spelled out)
  *   mod_image_to_mono_dev  device frames stacked at step * height bytes -> grey planes [frames][H][W]; layout NULL = the context's.
  *                          Ordered on the context's stream.  NULL src -> MOD_SKIP_NO_DISPARITY_NOW, like a NULL image elsewhere.
+ *                          It has no eye: for the right pane of side-by-side frames (below) the caller passes src + width * channels.
  * MOD_ERR_INVALID_ARGUMENT: unknown encoding, step < width * channels, a window that does not fit inside the message;
  * MOD_ERR_NOT_CONFIGURED: no camera yet (the window size is the camera's). */
 #define MOD_ENCODING_MONO8 0
@@ -380,15 +387,41 @@ int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const floa
 #define MOD_ENCODING_RGB8  2
 #define MOD_ENCODING_BGRA8 3
 #define MOD_ENCODING_RGBA8 4
+#define MOD_ENCODING_YUV422 5        /* UYVY */
+#define MOD_ENCODING_YUV422_YUY2 6   /* YUYV */
 typedef struct ModImageLayout {   /* 24 bytes */
   int32_t encoding;               /* MOD_ENCODING_* */
-  int32_t width, height;          /* of the message (sensor_msgs/Image width, height) */
-  int32_t step;                   /* bytes per row, >= width * channels */
+  int32_t width, height;          /* of the message (sensor_msgs/Image width, height); side by side: of one eye's pane */
+  int32_t step;                   /* bytes per row, >= width * channels (side by side: of the whole row, >= 2 * width * channels) */
   int32_t x0, y0;                 /* top-left of the window taken; the window is the context's W x H */
 } ModImageLayout;
 int  mod_set_image_layout(ModContext *ctx, const ModImageLayout *layout);
 int  mod_get_image_layout(const ModContext *ctx, ModImageLayout *layout);
 int  mod_image_to_mono_dev(ModContext *ctx, int32_t frames, const uint8_t *src, const ModImageLayout *layout, uint8_t *mono);
+
+/* ---- side-by-side stereo messages ------------------------------------------------------------------------------------------- */
+/* A stereo head used as a plain UVC device delivers both eyes in ONE frame, the left half and the right half of every row.  Opt-in
+ * context state like mod_set_disparity_subpixel: read at submit time, a frame in flight keeps the setting of its submit, and it may
+ * change while tickets are outstanding.  on: 0 = off (the default; every call enqueues exactly what it did before), 1 = on.
+ * While on, one message holds both eyes:
+ *   - the layout's width and height describe ONE eye's image (what that eye's CameraInfo and, with a rectification, its
+ *     calibration state); step is the pitch of the WHOLE row and must be >= 2 * width * channels;
+ *   - the left eye's pane starts at byte 0 of each row, the right eye's at byte width * channels; (x0, y0) is the window inside a
+ *     pane, the same for both eyes;
+ *   - mod_sgm_compute_host, mod_submit_stereo_host, mod_submit_images_host and mod_submit_odometry_host take the message in `left`;
+ *     `right` must be NULL or equal to `left` (anything else: MOD_ERR_INVALID_ARGUMENT); a NULL `left` skips as it always did;
+ *   - mod_flow_compute_host reads the left pane of both of its messages (this follows from the layout);
+ *   - without a rectification the two windows are copied, one from each pane: only the windows cross PCIe.  With one, the message
+ *     crosses PCIe ONCE (height * step bytes) and is rectified twice, the left pane with the left map and the right pane with the
+ *     right one; a tap outside a pane reads 0, never the other eye's pixel;
+ *   - mod_rectify_dev: `eye` also selects the pane; frames > 1 are whole messages stacked at height * step bytes.
+ * mod_set_side_by_side(1) under a layout whose step < 2 * width * channels (the default layout, mono8 packed at the camera's size, is
+ * one), and such a layout (mod_set_image_layout, or one handed to mod_rectify_dev / mod_image_to_mono_dev) while on:
+ * MOD_ERR_INVALID_ARGUMENT, the state stays
+ * as it was.  Before a camera is set there is no layout to check: the check is then made at call time.  The rectification maps are
+ * per eye and do not depend on this setting. */
+int  mod_set_side_by_side(ModContext *ctx, int32_t on);
+int  mod_get_side_by_side(const ModContext *ctx, int32_t *on);
 
 /* ---- raw camera images: rectification on the GPU ---------------------------------------------------------------------------- */
 /* The reference's launch files subscribe to image_rect_color: something upstream (image_proc, the ZED SDK) has rectified.  With a

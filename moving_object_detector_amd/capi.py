@@ -37,9 +37,12 @@ MOD_FLOW_SEEDS = 5
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
 MOD_MAX_WIDTH = 16384
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
+MOD_ENCODING_YUV422, MOD_ENCODING_YUV422_YUY2 = 5, 6   # packed 4:2:2: UYVY, YUYV (grey = Y)
 ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
-             "rgba8": MOD_ENCODING_RGBA8}
-CHANNELS = {MOD_ENCODING_MONO8: 1, MOD_ENCODING_BGR8: 3, MOD_ENCODING_RGB8: 3, MOD_ENCODING_BGRA8: 4, MOD_ENCODING_RGBA8: 4}
+             "rgba8": MOD_ENCODING_RGBA8, "yuv422": MOD_ENCODING_YUV422, "yuv422_yuy2": MOD_ENCODING_YUV422_YUY2}
+# bytes per pixel
+CHANNELS = {MOD_ENCODING_MONO8: 1, MOD_ENCODING_BGR8: 3, MOD_ENCODING_RGB8: 3, MOD_ENCODING_BGRA8: 4, MOD_ENCODING_RGBA8: 4,
+            MOD_ENCODING_YUV422: 2, MOD_ENCODING_YUV422_YUY2: 2}
 STAGE_NAMES = ("k_scene_flow", "k_ccl_bits+k_ccl_tile_list", "k_ccl_link", "k_ccl_merge", "k_final", "k_median+k_median_ties",
                "cluster group (first launch to last)")
 
@@ -59,6 +62,7 @@ EXPORTS = [
     "mod_set_disparity_filters", "mod_get_disparity_filters", "mod_disparity_speckle_dev",
     "mod_set_flow_propagation", "mod_get_flow_propagation",
     "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
+    "mod_set_side_by_side", "mod_get_side_by_side",
 ]
 
 
@@ -145,7 +149,8 @@ class ModImageLayout(C.Structure):
 
 def image_layout(encoding, width: int, height: int, step=None, x0: int = 0, y0: int = 0) -> ModImageLayout:
     """ModImageLayout of a sensor_msgs/Image: `encoding` a MOD_ENCODING_* value or its ROS name ("bgr8", ...); step None = packed
-    rows (width * channels); (x0, y0) = top-left of the camera-sized window taken from it."""
+    rows (width * channels); (x0, y0) = top-left of the camera-sized window taken from it.  For a side-by-side message (width = one
+    eye's) pass the step of the whole row."""
     enc = ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
     if step is None:
         step = int(width) * CHANNELS.get(enc, 1)
@@ -252,6 +257,8 @@ def load(require_torch_first: bool = True):
     L.mod_get_rectification.argtypes = [vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(i32)]
     L.mod_rectify_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), i32, vp]
     L.mod_rectify_map_host.argtypes = [vp, i32, C.POINTER(ModImageLayout), vp]
+    L.mod_set_side_by_side.argtypes = [vp, i32]
+    L.mod_get_side_by_side.argtypes = [vp, C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

@@ -71,18 +71,27 @@ static hipError_t copy_window(const ModImageLayout &l, int W, int H, const uint8
   return hipMemcpy2DAsync(dst, row, o, (size_t)l.step, row, (size_t)H, hipMemcpyHostToDevice, s);
 }
 
+// side by side (mod_set_side_by_side): `right` of a call that takes one message for both eyes must be NULL or that message
+static int check_one_message(ModContext *c, const uint8_t *left, const uint8_t *right) {
+  return right && right != left ? fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side: right must be NULL or equal to left") : MOD_OK;
+}
+
 // Two whole raw messages to `raw` on stream s, one after the other: a rectified window needs source pixels outside the window.
-static int copy_messages(ModContext *c, const ModImageLayout &l, const uint8_t *img0, const uint8_t *img1, uint8_t *raw, hipStream_t s) {
+// panes: img0 is ONE message that holds both eyes side by side; it crosses once.
+static int copy_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *img0, const uint8_t *img1, uint8_t *raw,
+                         hipStream_t s) {
   const size_t M = (size_t)l.step * l.height;
   HIP_TRY(c, hipMemcpyAsync(raw, img0, M, hipMemcpyHostToDevice, s));
-  HIP_TRY(c, hipMemcpyAsync(raw + M, img1, M, hipMemcpyHostToDevice, s));
+  if (!panes) HIP_TRY(c, hipMemcpyAsync(raw + M, img1, M, hipMemcpyHostToDevice, s));
   return MOD_OK;
 }
-// ... and k_rectify from there on the context's stream, each message with the map of its eye
-static int rectify_messages(ModContext *c, const ModImageLayout &l, const uint8_t *raw, int eye1, uint8_t *grey0, uint8_t *grey1) {
-  const size_t M = (size_t)l.step * l.height;
-  launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw, M, l.step, l.width, l.height, c->rect.map[MOD_EYE_LEFT].q, grey0, c->stream);
-  launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw + M, M, l.step, l.width, l.height, c->rect.map[eye1].q, grey1, c->stream);
+// ... and k_rectify from there on the context's stream, each message (or each pane of the one message) with the map of its eye.  A
+// pane is a message of the pane's width that starts width * channels bytes into the row and ends with the message's last byte.
+static int rectify_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *raw, int eye1, uint8_t *grey0, uint8_t *grey1) {
+  const size_t M = (size_t)l.step * l.height, at1 = panes ? pane_offset(l, MOD_EYE_RIGHT) : M;
+  launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw, M, M, l.step, l.width, l.height, c->rect.map[MOD_EYE_LEFT].q, grey0, c->stream);
+  launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw + at1, M, panes ? M - at1 : M, l.step, l.width, l.height, c->rect.map[eye1].q, grey1,
+                 c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
@@ -90,18 +99,19 @@ static int rectify_messages(ModContext *c, const ModImageLayout &l, const uint8_
 // The two images of a synchronous *_host call, grey on the device behind the context's stream: mono8 straight into the flow
 // staging slot (its 8 N bytes hold both), colour windows into that slot and k_to_mono from there into the cloud staging.  With a
 // rectification set: the whole messages into the raw staging, and k_rectify from there into the cloud staging (img0 with the left
-// map, img1 with the map of eye1).
-static int upload_pair(ModContext *c, const uint8_t *img0, const uint8_t *img1, int eye1, uint8_t **grey) {
+// map, img1 with the map of eye1).  panes: img0 holds both eyes side by side and img1 is not read.
+static int upload_pair(ModContext *c, const uint8_t *img0, const uint8_t *img1, int eye1, bool panes, uint8_t **grey) {
   ModImageLayout l;
   if (int rc = current_layout(c, &l)) return rc;
   if (c->rect.on) {
     int rc;
     if ((rc = ensure_rectify_map(c, MOD_EYE_LEFT, l)) || (rc = ensure_rectify_map(c, eye1, l)) || (rc = ensure_raw_stage(c, c->staging.raw, l)) ||
-        (rc = copy_messages(c, l, img0, img1, c->staging.raw.buf, c->stream)))
+        (rc = copy_messages(c, l, panes, img0, img1, c->staging.raw.buf, c->stream)))
       return rc;
     *grey = static_cast<uint8_t *>(c->staging.aos.get());
-    return rectify_messages(c, l, c->staging.raw.buf, eye1, *grey, *grey + pixels(c));
+    return rectify_messages(c, l, panes, c->staging.raw.buf, eye1, *grey, *grey + pixels(c));
   }
+  if (panes) img1 = img0 + pane_offset(l, MOD_EYE_RIGHT);   // one window from each pane
   const int W = c->dc.W, H = c->dc.H;
   uint8_t *slot = reinterpret_cast<uint8_t *>(c->staging.flow.get());
   const size_t P = pixels(c) * image_channels(l.encoding);
@@ -207,11 +217,13 @@ struct StereoFrame {
   ModImageLayout lay;
   uint8_t *left, *right;
   bool rectify;                      // the images are raw messages: whole into the slot's raw staging, k_rectify from there
+  bool panes;                        // side by side at this submit: rq.left holds both eyes
   bool colour() const { return lay.encoding != MOD_ENCODING_MONO8; }
 };
 
 static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay) {
-  if (!rq.left || !rq.right) {      // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276)
+  // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276); side by side, left holds both eyes
+  if (!rq.left || (!rq.right && !c->side_by_side)) {
     c->pipe.have_prev = false;      // ... which becomes the next frame's (missing) previous disparity (:397-398)
     c->pipe.have_prev_img = false;  // ... and the next frame has no previous image to estimate the flow from
     return MOD_SKIP_NO_DISPARITY_NOW;
@@ -219,6 +231,7 @@ static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout 
   if (int rc = check_sgm_params(c, rq.sgm)) return rc;
   if (int rc = rq.estimates_flow() ? check_flow_params(c, rq.flow_prm, 1) : MOD_OK) return rc;
   if (int rc = rq.odometry() ? check_ego_params(c, rq.ego_prm) : MOD_OK) return rc;
+  if (int rc = c->side_by_side ? check_one_message(c, rq.left, rq.right) : MOD_OK) return rc;
   if (int rc = current_layout(c, lay)) return rc;
   if (!c->rect.on) return MOD_OK;
   if (int rc = ensure_rectify_map(c, MOD_EYE_LEFT, *lay)) return rc;
@@ -241,12 +254,12 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
   const size_t P = pixels(c) * image_channels(f.lay.encoding);
   if (f.rectify) {                  // image_proc's rectifier and cv_bridge's conversion on the GPU
     HIP_TRY(c, f.s.stage_read.wait(p.h2d));
-    if (int rc = copy_messages(c, f.lay, rq.left, rq.right, f.s.raw.buf, p.h2d)) return rc;
+    if (int rc = copy_messages(c, f.lay, f.panes, rq.left, rq.right, f.s.raw.buf, p.h2d)) return rc;
     if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
     HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
     // the grey images are written on the context's stream, which is behind every older reader of them already
-    if (int rc = rectify_messages(c, f.lay, f.s.raw.buf, MOD_EYE_RIGHT, f.left, f.right)) return rc;
+    if (int rc = rectify_messages(c, f.lay, f.panes, f.s.raw.buf, MOD_EYE_RIGHT, f.left, f.right)) return rc;
     HIP_TRY(c, f.s.stage_read.record(c->stream));
     return MOD_OK;
   }
@@ -254,8 +267,9 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
   // colour grey is written on the context's stream, which is behind every older reader already: only a copy waits for left_read
   if (rq.estimates_flow() && !f.colour()) HIP_TRY(c, f.now.left_read.wait(p.h2d));
   if (f.colour()) HIP_TRY(c, f.s.stage_read.wait(p.h2d));
+  const uint8_t *right = f.panes ? rq.left + pane_offset(f.lay, MOD_EYE_RIGHT) : rq.right;   // one window from each pane
   HIP_TRY(c, copy_window(f.lay, W, H, rq.left, f.colour() ? f.s.stage.get() : f.left, p.h2d));
-  HIP_TRY(c, copy_window(f.lay, W, H, rq.right, f.colour() ? f.s.stage.get() + P : f.right, p.h2d));
+  HIP_TRY(c, copy_window(f.lay, W, H, right, f.colour() ? f.s.stage.get() + P : f.right, p.h2d));
   if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
   HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
@@ -301,7 +315,7 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   ModImageLayout lay;
   int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on};
+  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on, c->side_by_side};
   if ((rc = grow_for(c, rq, f)) || (rc = upload_images(c, rq, f)) || (rc = estimate(c, rq, f))) return rc;
   static const ModTransform kUnused = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};   // stands for the transform in HBM (never read)
   const ModFrameBatch in{1, 0, f.now.disparity, f.prev.disparity, f.s.flow, rq.odometry() ? &kUnused : rq.transform, &rq.dt};
@@ -320,7 +334,7 @@ int mod_flow_compute_host(ModContext *c, const uint8_t *prev, const uint8_t *now
   if (!prev || !now) return MOD_SKIP_NO_FLOW;
   if (!flow) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow image");
   uint8_t *dimg = nullptr;
-  if ((rc = check_flow_params(c, p, 1)) || (rc = ensure_host_staging(c)) || (rc = upload_pair(c, prev, now, MOD_EYE_LEFT, &dimg))) return rc;
+  if ((rc = check_flow_params(c, p, 1)) || (rc = ensure_host_staging(c)) || (rc = upload_pair(c, prev, now, MOD_EYE_LEFT, false, &dimg))) return rc;
   if ((rc = mod_flow_compute_dev(c, 1, dimg, dimg + pixels(c), p, c->staging.planes))) return rc;
   return download_sync(c, flow, c->staging.planes, 8 * pixels(c));
 }
@@ -347,10 +361,12 @@ int mod_egomotion_host(ModContext *c, const float *disparity_prev, const float *
 int mod_sgm_compute_host(ModContext *c, const uint8_t *left, const uint8_t *right, const ModSgmParams *p, float *disparity) {
   int rc = check_ready(c, 1);
   if (rc) return rc;
-  if (!left || !right) return MOD_SKIP_NO_DISPARITY_NOW;
+  const bool panes = c->side_by_side;   // one message holds both eyes
+  if (!left || (!right && !panes)) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity image");
+  if ((rc = panes ? check_one_message(c, left, right) : MOD_OK)) return rc;
   uint8_t *dimg = nullptr;
-  if ((rc = ensure_host_staging(c)) || (rc = upload_pair(c, left, right, MOD_EYE_RIGHT, &dimg))) return rc;
+  if ((rc = ensure_host_staging(c)) || (rc = upload_pair(c, left, right, MOD_EYE_RIGHT, panes, &dimg))) return rc;
   if ((rc = mod_sgm_compute_dev(c, 1, dimg, dimg + pixels(c), p, c->staging.dnow))) return rc;
   return download_sync(c, disparity, c->staging.dnow, 4 * pixels(c));
 }

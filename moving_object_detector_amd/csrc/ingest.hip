@@ -5,7 +5,8 @@
 // on bytes already in HBM: it reads the camera-sized window (W x H) at (x0, y0) of each 8-bit frame of a batch (row pitch `step`,
 // frames stacked at step * message height bytes) and writes packed grey planes [frames][H][W].
 //
-// Memory-bound: C + 1 bytes per pixel (C = 1, 3 or 4 channels).  Each lane makes one run of 16 consecutive output pixels of one row.
+// Memory-bound: C + 1 bytes per pixel (C = 1, 2, 3 or 4 bytes of a source pixel; packed YUV 4:2:2 is C = 2, grey = its Y byte).
+// Each lane makes one run of 16 consecutive output pixels of one row.
 // Runs are placed on the OUTPUT's 16-byte grid, so a row interior is one aligned 16-byte store; the source of a run starts at any byte
 // (neither step nor x0 * C need be a multiple of 4): the run loads the dwords that cover it from the dword below its first byte and
 // shifts them into place with v_alignbyte.  A run whose loads would leave the window's bytes of its row (the row ends), or whose
@@ -20,7 +21,7 @@ constexpr int kBlock = 256;
 template <int Enc>
 __device__ __forceinline__ uint32_t pixel_grey(const uint8_t *p) {
   using F = Fmt<Enc>;
-  if constexpr (F::C == 1) return p[0];
+  if constexpr (F::mono) return p[F::y];
   else return grey(p[F::b], p[F::g], p[F::r]);
 }
 
@@ -33,13 +34,22 @@ __device__ __forceinline__ uint32_t byte_of(const uint32_t (&d)[N]) {
 template <int Enc, int P, int N>
 __device__ __forceinline__ uint32_t run_grey(const uint32_t (&d)[N]) {
   using F = Fmt<Enc>;
-  if constexpr (F::C == 1) return byte_of<P, N>(d);
+  if constexpr (F::mono) return byte_of<P * F::C + F::y, N>(d);
   else return grey(byte_of<P * F::C + F::b, N>(d), byte_of<P * F::C + F::g, N>(d), byte_of<P * F::C + F::r, N>(d));
 }
 
 template <int Enc, int... P>
 __device__ __forceinline__ void pack_run(const uint32_t (&d)[kRun * Fmt<Enc>::C / 4], uint32_t (&o)[4], std::integer_sequence<int, P...>) {
-  ((o[P >> 2] |= run_grey<Enc, P>(d) << ((P & 3) * 8)), ...);
+  using F = Fmt<Enc>;
+  if constexpr (F::mono && F::C == 2) {
+    // the four luma bytes of an output dword lie in two source dwords, every other byte from F::y on: one v_perm_b32 gathers them
+    // (selector byte k = the index, within the eight bytes {d[2 j + 1], d[2 j]}, of output byte k)
+    constexpr uint32_t sel = 0x06040200u + 0x01010101u * F::y;
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = __builtin_amdgcn_perm(d[2 * j + 1], d[2 * j], sel);
+  } else {
+    ((o[P >> 2] |= run_grey<Enc, P>(d) << ((P & 3) * 8)), ...);
+  }
 }
 
 //   runs         runs per row: (W + 15) / 16 + 1 (run r covers x in [head + 16 (r - 1), head + 16 r), head = pixels of the row in
@@ -95,6 +105,7 @@ int image_channels(int encoding) {
     case MOD_ENCODING_MONO8: return 1;
     case MOD_ENCODING_BGR8: case MOD_ENCODING_RGB8: return 3;
     case MOD_ENCODING_BGRA8: case MOD_ENCODING_RGBA8: return 4;
+    case MOD_ENCODING_YUV422: case MOD_ENCODING_YUV422_YUY2: return 2;   // bytes per pixel; one of them is the grey
     default: return 0;
   }
 }
@@ -107,6 +118,8 @@ void launch_to_mono(int encoding, int W, int H, int frames, const uint8_t *src, 
     case MOD_ENCODING_RGB8:  launch<MOD_ENCODING_RGB8>(W, H, frames, src, frame_bytes, step, x0, y0, dst, s); break;
     case MOD_ENCODING_BGRA8: launch<MOD_ENCODING_BGRA8>(W, H, frames, src, frame_bytes, step, x0, y0, dst, s); break;
     case MOD_ENCODING_RGBA8: launch<MOD_ENCODING_RGBA8>(W, H, frames, src, frame_bytes, step, x0, y0, dst, s); break;
+    case MOD_ENCODING_YUV422: launch<MOD_ENCODING_YUV422>(W, H, frames, src, frame_bytes, step, x0, y0, dst, s); break;
+    case MOD_ENCODING_YUV422_YUY2: launch<MOD_ENCODING_YUV422_YUY2>(W, H, frames, src, frame_bytes, step, x0, y0, dst, s); break;
     default: break;
   }
 }

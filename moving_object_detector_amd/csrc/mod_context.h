@@ -110,6 +110,7 @@ struct ModContext {
   bool has_cam = false, has_prm = false;
   ModImageLayout layout{};                  // of the host images (mod_set_image_layout) ...
   bool has_layout = false;                  // ... or, while false, mono8 packed at the camera's size
+  bool side_by_side = false;                // mod_set_side_by_side: one message holds both eyes; read when a call / submit is made
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
   int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
@@ -124,7 +125,8 @@ struct ModContext {
       int32_t width = 0, height = 0, x0 = 0, y0 = 0, W = 0, H = 0;
     } map[2];
   } rect;
-  // whole raw messages on their way to k_rectify: two of the layout in force (allocated on first use, grow-only)
+  // whole raw messages on their way to k_rectify: room for two of the layout in force (allocated on first use, grow-only); a
+  // side-by-side message is one, and uses the first half
   struct RawStage { DevPtr<uint8_t> buf; size_t bytes = 0; };
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
@@ -254,7 +256,10 @@ inline int construct_skip(bool flow, bool prev, bool transform, bool now) {
 void refresh_devcam(ModContext *c);
 // the layout the host image entry points read (the set one, or mono8 packed W x H), checked against the camera
 int current_layout(ModContext *c, ModImageLayout *out);
-int check_layout(ModContext *c, const ModImageLayout &l);
+// panes: the message holds both eyes side by side (width is a pane's, step the whole row's)
+int check_layout(ModContext *c, const ModImageLayout &l, bool panes);
+// where the pane of `eye` starts in a row of a side-by-side message
+inline size_t pane_offset(const ModImageLayout &l, int eye) { return eye == MOD_EYE_RIGHT ? (size_t)l.width * image_channels(l.encoding) : 0; }
 // with a rectification set (the caller has checked that, and eye): the map of `eye` for the window of `l` is in c->rect.map[eye].q when this returns MOD_OK (built, behind
 // the context's stream, unless it is the cached one; refused while tickets are outstanding)
 int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l);

@@ -131,13 +131,15 @@ void launch_egomotion(const EgoArgs &a, hipStream_t s);
 
 // camera images to grey (ingest.hip).  Window W x H at (x0, y0) of each 8-bit frame (row pitch `step`, frames frame_bytes apart)
 // -> dst [frames][H][W]; encoding MOD_ENCODING_*
-int image_channels(int encoding);   // 0: unknown encoding
+int image_channels(int encoding);   // bytes per pixel; 0: unknown encoding
 void launch_to_mono(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int x0, int y0, uint8_t *dst,
                     hipStream_t s);
 
 // raw camera images to rectified grey (rectify.hip).  map: device int32 [H][W][2], where each pixel of the W x H window lies in the
-// width x height message (1/32 pixel; build_rectify_map fills a host copy for the window at (x0, y0)) -> dst [frames][H][W]
-void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int width, int height,
-                    const int32_t *map, uint8_t *dst, hipStream_t s);
+// width x height message (1/32 pixel; build_rectify_map fills a host copy for the window at (x0, y0)) -> dst [frames][H][W].
+// Frames lie frame_bytes apart; `extent` bytes from a frame's first one may be loaded (step * height, or less for a pane of a
+// side-by-side message: src then points at the pane and width is the pane's)
+void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, size_t extent, int step, int width,
+                    int height, const int32_t *map, uint8_t *dst, hipStream_t s);
 void build_rectify_map(const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map);
 const char *check_rectify_camera(const ModRectifyCamera &cam);   // null: valid, else what is wrong with it

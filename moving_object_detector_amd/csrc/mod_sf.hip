@@ -249,20 +249,22 @@ int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPl
 
 }  // namespace
 
-int check_layout(ModContext *c, const ModImageLayout &l) {
+int check_layout(ModContext *c, const ModImageLayout &l, bool panes) {
   const int C = image_channels(l.encoding);
   if (!C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown image encoding");
   if (l.width < 1 || l.height < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "image size must be positive");
   if ((int64_t)l.step < (int64_t)l.width * C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "step is smaller than width * channels");
+  if (panes && (int64_t)l.step < 2 * (int64_t)l.width * C)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side: step is smaller than 2 * width * channels (width is one eye's)");
   if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the image");
   return MOD_OK;
 }
 
 int current_layout(ModContext *c, ModImageLayout *out) {
-  if (!c->has_layout) { *out = ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0}; return MOD_OK; }
-  *out = c->layout;
-  return check_layout(c, *out);   // the camera may have changed since the layout was set
+  *out = c->has_layout ? c->layout : ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};
+  if (!c->has_layout && !c->side_by_side) return MOD_OK;
+  return check_layout(c, *out, c->side_by_side);   // the camera may have changed since the layout was set
 }
 
 // (callers have checked that a rectification is set and that eye is one of the two)
@@ -501,10 +503,28 @@ int mod_get_params(const ModContext *c, ModParams *p) {
 int mod_set_image_layout(ModContext *c, const ModImageLayout *l) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
-  if (!l) { c->has_layout = false; return MOD_OK; }
-  int rc = check_layout(c, *l);
+  const ModImageLayout packed{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};   // (holds no two panes: refused while side by side)
+  int rc = check_layout(c, l ? *l : packed, c->side_by_side);
   if (rc) return rc;
-  c->layout = *l; c->has_layout = true;
+  if (l) c->layout = *l;
+  c->has_layout = l != nullptr;
+  return MOD_OK;
+}
+
+int mod_set_side_by_side(ModContext *c, int32_t on) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (on != 0 && on != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side must be 0 or 1");
+  if (on && c->has_cam) {           // the layout in force must hold two panes (without a camera there is none yet: checked at call time)
+    const ModImageLayout l = c->has_layout ? c->layout : ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};
+    if (int rc = check_layout(c, l, true)) return rc;
+  }
+  c->side_by_side = on != 0;
+  return MOD_OK;
+}
+
+int mod_get_side_by_side(const ModContext *c, int32_t *on) {
+  if (!c || !on) return MOD_ERR_INVALID_ARGUMENT;
+  *on = c->side_by_side;
   return MOD_OK;
 }
 
@@ -522,7 +542,7 @@ int mod_image_to_mono_dev(ModContext *c, int32_t frames, const uint8_t *src, con
   if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
   ModImageLayout l;
-  int rc = layout ? check_layout(c, *layout) : current_layout(c, &l);
+  int rc = layout ? check_layout(c, *layout, c->side_by_side) : current_layout(c, &l);
   if (rc) return rc;
   if (layout) l = *layout;
   launch_to_mono(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.x0, l.y0, mono, c->stream);
@@ -556,7 +576,7 @@ static int rectify_setup(ModContext *c, const ModImageLayout *layout, int32_t ey
   if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
   if (eye != MOD_EYE_LEFT && eye != MOD_EYE_RIGHT) return fail(c, MOD_ERR_INVALID_ARGUMENT, "eye must be MOD_EYE_LEFT or MOD_EYE_RIGHT");
   if (!c->rect.on) return fail(c, MOD_ERR_NOT_CONFIGURED, "no rectification is set");
-  int rc = layout ? check_layout(c, *layout) : current_layout(c, l);
+  int rc = layout ? check_layout(c, *layout, c->side_by_side) : current_layout(c, l);
   if (rc) return rc;
   if (layout) *l = *layout;
   return ensure_rectify_map(c, eye, *l);
@@ -569,8 +589,8 @@ int mod_rectify_dev(ModContext *c, int32_t frames, const uint8_t *src, const Mod
   if (int rc = rectify_setup(c, layout, eye, &l)) return rc;
   if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
-  launch_rectify(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.width, l.height, c->rect.map[eye].q, mono,
-                 c->stream);
+  const size_t M = (size_t)l.step * l.height, pane = c->side_by_side ? pane_offset(l, eye) : 0;   // side by side: eye selects the pane too
+  launch_rectify(l.encoding, c->dc.W, c->dc.H, frames, src + pane, M, M - pane, l.step, l.width, l.height, c->rect.map[eye].q, mono, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

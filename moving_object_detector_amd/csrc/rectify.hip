@@ -14,7 +14,8 @@
 //           box from its map entries (wave shuffles, one LDS exchange), copies it into LDS with coalesced aligned dword loads
 //           (bytes singly only where a dword lies astride the message's first or last byte) and takes every tap from there; a box
 //           that does not fit 16 KiB is gathered directly.  Compiled out of the product until it has been timed (kStagedDefault).
-// Nothing outside height * step bytes of a message is loaded.  C source bytes + 8 map bytes + 1 per pixel; no atomics; frames in
+// Nothing outside the `extent` bytes of a message is loaded (height * step; for the right pane of a side-by-side message, which
+// starts width * C bytes into it, that much less).  C source bytes + 8 map bytes + 1 per pixel; no atomics; frames in
 // blockIdx.z.
 #include "image_fmt.h"
 
@@ -34,10 +35,15 @@ constexpr double kQMax = 16777216.0;   // 2^24: the map's clamp, so that ix + 1 
 template <int Enc, int NC>
 __device__ __forceinline__ void load_pair(const uint8_t *p, uint32_t (&t0)[NC], uint32_t (&t1)[NC]) {
   using F = Fmt<Enc>;
-  if constexpr (F::C == 1) {
+  if constexpr (F::mono && F::C == 1) {
     uint16_t w;
     __builtin_memcpy(&w, p, 2);
     t0[0] = w & 0xffu; t1[0] = w >> 8;
+  } else if constexpr (F::mono) {                  // pitch 2: the grey bytes of the pair are bytes y and 2 + y of its four
+    static_assert(F::C == 2, "one grey channel at pitch 1 or 2");
+    uint32_t w;
+    __builtin_memcpy(&w, p, 4);
+    t0[0] = (w >> (8 * F::y)) & 0xffu; t1[0] = (w >> (8 * (F::C + F::y))) & 0xffu;
   } else {
     uint64_t w = 0;
     if constexpr (F::C == 4) __builtin_memcpy(&w, p, 8);
@@ -51,7 +57,7 @@ __device__ __forceinline__ void load_pair(const uint8_t *p, uint32_t (&t0)[NC], 
 template <int Enc, int NC>
 __device__ __forceinline__ void load_one(const uint8_t *p, uint32_t (&t)[NC]) {
   using F = Fmt<Enc>;
-  if constexpr (F::C == 1) t[0] = p[0];
+  if constexpr (F::mono) t[0] = p[F::y];
   else { t[0] = p[F::b]; t[1] = p[F::g]; t[2] = p[F::r]; }
 }
 
@@ -73,7 +79,7 @@ __device__ __forceinline__ uint32_t interpolate(const uint32_t (&t)[2][2][NC], u
 template <int Enc>
 __device__ __forceinline__ uint32_t rect_pixel(const uint8_t *__restrict__ msg, int step, int width, int height, int qx, int qy) {
   using F = Fmt<Enc>;
-  constexpr int C = F::C, NC = C == 1 ? 1 : 3;
+  constexpr int C = F::C, NC = F::mono ? 1 : 3;
   const int ix = qx >> 5, iy = qy >> 5;
   const bool in0 = (unsigned)ix < (unsigned)width, in1 = (unsigned)(ix + 1) < (unsigned)width;
   uint32_t t[2][2][NC] = {};
@@ -107,7 +113,7 @@ __device__ __forceinline__ int wave_min(int v) {
 template <int Enc, int NC>
 __device__ __forceinline__ void unpack(uint64_t w, int at, uint32_t (&t)[NC]) {
   using F = Fmt<Enc>;
-  if constexpr (F::C == 1) t[0] = (uint32_t)(w >> (8 * at)) & 0xffu;
+  if constexpr (F::mono) t[0] = (uint32_t)(w >> (8 * (at + F::y))) & 0xffu;
   else {
     t[0] = (uint32_t)(w >> (8 * (at + F::b))) & 0xffu; t[1] = (uint32_t)(w >> (8 * (at + F::g))) & 0xffu;
     t[2] = (uint32_t)(w >> (8 * (at + F::r))) & 0xffu;
@@ -120,7 +126,7 @@ template <int Enc>
 __device__ __forceinline__ uint32_t rect_pixel_lds(const uint32_t *tile, int pitch, uint32_t phase0, int step, const Box &box, int width,
                                                    int height, int qx, int qy) {
   using F = Fmt<Enc>;
-  constexpr int C = F::C, NC = C == 1 ? 1 : 3;
+  constexpr int C = F::C, NC = F::mono ? 1 : 3;
   const int ix = qx >> 5, iy = qy >> 5;
   const bool in0 = (unsigned)ix < (unsigned)width, in1 = (unsigned)(ix + 1) < (unsigned)width;
   uint32_t t[2][2][NC] = {};
@@ -135,7 +141,7 @@ __device__ __forceinline__ uint32_t rect_pixel_lds(const uint32_t *tile, int pit
       const uint32_t *d = tile + br * pitch + (at >> 2);
       const uint32_t sh = at & 3u;
       const uint32_t lo = __builtin_amdgcn_alignbyte(d[1], d[0], sh);
-      const uint32_t hi = C == 1 ? 0u : __builtin_amdgcn_alignbyte(d[2], d[1], sh);   // (bytes past the row's are shifted in, never used)
+      const uint32_t hi = 2 * C <= 4 ? 0u : __builtin_amdgcn_alignbyte(d[2], d[1], sh);   // (bytes past the row's are shifted in, never used)
       const uint64_t w = lo | ((uint64_t)hi << 32);
       if (in0) unpack<Enc, NC>(w, 0, t[r][0]);
       if (in1) unpack<Enc, NC>(w, in0 ? C : 0, t[r][1]);
@@ -146,12 +152,13 @@ __device__ __forceinline__ uint32_t rect_pixel_lds(const uint32_t *tile, int pit
 
 //   runs         runs per row: (W + 3) / 4 + 1 (run r covers x in [head + 4 (r - 1), head + 4 r), head = pixels of the row in front
 //                of the output's first dword boundary)
-//   frame_bytes  step * height;  width, height: of the message;  map [H][W] (qx, qy)
+//   frame_bytes  step * height, the distance between two frames;  extent: the bytes that may be loaded from a frame's first one (the
+//                same, or less for a pane that starts inside the message);  width, height: of the message (pane);  map [H][W] (qx, qy)
 //   Staged       the workgroup first copies the box of message bytes its taps touch into LDS with coalesced aligned dword loads
 //                and samples from there; a box that does not fit kTileDwords (a map that is far from smooth) is gathered directly
 template <int Enc, bool Staged>
-__global__ __launch_bounds__(kBlock) void k_rectify(int W, int H, int runs, const uint8_t *__restrict__ src, size_t frame_bytes, int step,
-                                                    int width, int height, const int2 *__restrict__ map, uint8_t *__restrict__ dst) {
+__global__ __launch_bounds__(kBlock) void k_rectify(int W, int H, int runs, const uint8_t *__restrict__ src, size_t frame_bytes, size_t extent,
+                                                    int step, int width, int height, const int2 *__restrict__ map, uint8_t *__restrict__ dst) {
   constexpr int C = Fmt<Enc>::C;
   const int r = blockIdx.x * kTileRuns + threadIdx.x % kTileRuns;
   const int y = blockIdx.y * kTileRows + threadIdx.x / kTileRuns;
@@ -201,7 +208,7 @@ __global__ __launch_bounds__(kBlock) void k_rectify(int W, int H, int runs, cons
       const uint32_t phase0 = (uint32_t)(uintptr_t)first & 3u;
       staged = (long long)rows * pitch <= kTileDwords;   // (uniform: the box is the workgroup's)
       if (staged) {
-        const uint8_t *end = msg + frame_bytes;
+        const uint8_t *end = msg + extent;
         for (int i = threadIdx.x; i < rows * nd; i += kBlock) {
           const int br = i / nd, d = i - br * nd;
           const uint8_t *a0 = first + (size_t)br * step;                     // the row's first byte
@@ -240,7 +247,7 @@ __global__ __launch_bounds__(kBlock) void k_rectify(int W, int H, int runs, cons
 
 // measurement builds (tools/time_rectify.py, `make EXTRA=-DMOD_RECTIFY_DIRECT OUT=...` / `EXTRA=-DMOD_RECTIFY_STAGED OUT=...`) pin the
 // path; the product takes kStagedDefault
-[[maybe_unused]] constexpr bool kStagedDefault = false;   // the staged path has not been timed against the direct one yet
+[[maybe_unused]] constexpr bool kStagedDefault = false;   // one timing so far, and it is mixed: the direct path stays
 #if defined(MOD_RECTIFY_DIRECT)
 constexpr bool kStaged = false;
 #elif defined(MOD_RECTIFY_STAGED)
@@ -250,11 +257,11 @@ constexpr bool kStaged = kStagedDefault;
 #endif
 
 template <int Enc>
-void launch(int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int width, int height, const int32_t *map,
-            uint8_t *dst, hipStream_t s) {
+void launch(int W, int H, int frames, const uint8_t *src, size_t frame_bytes, size_t extent, int step, int width, int height,
+            const int32_t *map, uint8_t *dst, hipStream_t s) {
   const int runs = (W + kRun - 1) / kRun + 1;
   const dim3 grid((unsigned)((runs + kTileRuns - 1) / kTileRuns), (unsigned)((H + kTileRows - 1) / kTileRows), (unsigned)frames);
-  hipLaunchKernelGGL((k_rectify<Enc, kStaged>), grid, dim3(kBlock), 0, s, W, H, runs, src, frame_bytes, step, width, height,
+  hipLaunchKernelGGL((k_rectify<Enc, kStaged>), grid, dim3(kBlock), 0, s, W, H, runs, src, frame_bytes, extent, step, width, height,
                      reinterpret_cast<const int2 *>(map), dst);
 }
 
@@ -266,14 +273,16 @@ int32_t quantise(double m) {
 
 }  // namespace
 
-void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int width, int height,
-                    const int32_t *map, uint8_t *dst, hipStream_t s) {
+void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, size_t extent, int step, int width,
+                    int height, const int32_t *map, uint8_t *dst, hipStream_t s) {
   switch (encoding) {
-    case MOD_ENCODING_MONO8: launch<MOD_ENCODING_MONO8>(W, H, frames, src, frame_bytes, step, width, height, map, dst, s); break;
-    case MOD_ENCODING_BGR8:  launch<MOD_ENCODING_BGR8>(W, H, frames, src, frame_bytes, step, width, height, map, dst, s); break;
-    case MOD_ENCODING_RGB8:  launch<MOD_ENCODING_RGB8>(W, H, frames, src, frame_bytes, step, width, height, map, dst, s); break;
-    case MOD_ENCODING_BGRA8: launch<MOD_ENCODING_BGRA8>(W, H, frames, src, frame_bytes, step, width, height, map, dst, s); break;
-    case MOD_ENCODING_RGBA8: launch<MOD_ENCODING_RGBA8>(W, H, frames, src, frame_bytes, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_MONO8: launch<MOD_ENCODING_MONO8>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_BGR8:  launch<MOD_ENCODING_BGR8>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_RGB8:  launch<MOD_ENCODING_RGB8>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_BGRA8: launch<MOD_ENCODING_BGRA8>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_RGBA8: launch<MOD_ENCODING_RGBA8>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_YUV422: launch<MOD_ENCODING_YUV422>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
+    case MOD_ENCODING_YUV422_YUY2: launch<MOD_ENCODING_YUV422_YUY2>(W, H, frames, src, frame_bytes, extent, step, width, height, map, dst, s); break;
     default: break;
   }
 }

@@ -75,6 +75,14 @@ class SceneFlowConstructor {
   // neighbour-seed propagation of the optical flow (mod_set_flow_propagation): 1 = off, the default; 5 = every finer level also tries the
   // winners of the parent's four neighbours.  Frames already submitted keep the setting of their submit.
   void setFlowPropagation(int seeds) { check(mod_set_flow_propagation(ctx_, seeds)); }
+  // side-by-side stereo messages (mod_set_side_by_side; what a stereo head used as a plain UVC camera delivers): while set,
+  // submitStereo() and submitOdometry() take ONE message of twice the camera's width in left_image, its left half the left eye's
+  // image, and right_image must be null or that message.  Off by default.  The layout is set with the next message: until then the
+  // library refuses a layout that cannot hold two panes, so the setting is kept here and handed on with the layout.
+  // While set, NO entry point takes two distinct images: estimateDisparity() returns false for them (it has no one-message form:
+  // use submitStereo() or submitOdometry()), and the two submits treat them as missing images and return -1.  Switch it off before
+  // handing two messages in again; frames already submitted keep the setting of their submit.
+  void setSideBySide(bool on) { side_by_side_ = on; }
   bool estimateDisparity(const mod_host::Image *left_image, const mod_host::Image *right_image, const mod_host::CameraInfo &left_camera_info,
                          const mod_host::CameraInfo &right_camera_info, mod_host::DisparityImage *disparity, std::vector<float> *pixels) {
     if (!left_image || !right_image || !left_image->data || !right_image->data) return false;
@@ -221,9 +229,11 @@ class SceneFlowConstructor {
   int submitStereo(const mod_host::Image *left_image, const mod_host::Image *right_image, const mod_host::FlowImage *left_flow,
                    const mod_host::Transform *transform_prev2now, mod_host::PointCloud2 *pc_with_velocity,
                    mod_host::MovingObjectArray *moving_objects = nullptr) {
-    const bool images = left_image && right_image && left_image->data && right_image->data && left_image->width == image_width_ &&
-                        left_image->height == image_height_ && right_image->width == image_width_ && right_image->height == image_height_ &&
-                        useLayout(*left_image, *right_image, 0, 0);
+    if (side_by_side_ && !right_image) right_image = left_image;   // one message holds both eyes
+    const int panes = side_by_side_ ? 2 : 1;
+    const bool images = left_image && right_image && left_image->data && right_image->data && left_image->width == panes * image_width_ &&
+                        left_image->height == image_height_ && right_image->width == panes * image_width_ &&
+                        right_image->height == image_height_ && useLayout(*left_image, *right_image, 0, 0);
     ModTransform tf{};
     if (transform_prev2now) {
       for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
@@ -259,6 +269,7 @@ class SceneFlowConstructor {
   int submitOdometry(const mod_host::Image *left_image, const mod_host::Image *right_image, mod_host::MovingObjectArray *moving_objects,
                      std::vector<float> *flow_out = nullptr, int x0 = 0, int y0 = 0, std::vector<float> *disparity_out = nullptr,
                      mod_host::PointCloud2 *pc_with_velocity = nullptr) {
+    if (side_by_side_ && !right_image) right_image = left_image;   // one message holds both eyes
     const bool images = left_image && right_image && left_image->data && right_image->data && useLayout(*left_image, *right_image, x0, y0);
     const double dt = (images && have_stamp_) ? mod_host::duration_sec(left_image->header.stamp, previous_stamp_) : 0.0;
     Pending &p = pending_[next_slot_];
@@ -347,9 +358,14 @@ class SceneFlowConstructor {
   // the same, scene_flow_constructor.cpp:224-226).  Every image entry point of this class sets it: the layout is the context's.
   bool useLayout(const mod_host::Image &left, const mod_host::Image &right, int x0, int y0) {
     ModImageLayout lay{};
-    if (!mod_host::image_layout(left, x0, y0, &lay) || right.encoding != left.encoding || right.width != left.width ||
+    if (!mod_host::image_layout(left, x0, y0, &lay, side_by_side_) || right.encoding != left.encoding || right.width != left.width ||
         right.height != left.height || right.step != left.step) return false;
-    return mod_set_image_layout(ctx_, &lay) == MOD_OK;
+    if (side_by_side_ && right.data != left.data) return false;
+    // the library checks a layout against the side-by-side state in force and the state against the layout: set each while the
+    // other allows it (off accepts every layout, and a two-pane layout accepts both states)
+    if (!side_by_side_) check(mod_set_side_by_side(ctx_, 0));
+    if (mod_set_image_layout(ctx_, &lay) != MOD_OK) return false;
+    return !side_by_side_ || mod_set_side_by_side(ctx_, 1) == MOD_OK;
   }
 
   // collects a ticket and fills the messages handed to its submit; returns the collect status (< 0 thrown)
@@ -374,6 +390,7 @@ class SceneFlowConstructor {
   Pending pending_[MOD_PIPELINE_DEPTH];
   int next_slot_ = 0;
   bool have_stamp_ = false, have_parked_ = false;
+  bool side_by_side_ = false;
   mod_host::Time previous_stamp_;
   std::vector<float> parked_;
 

@@ -140,6 +140,17 @@ class Context:
         self._check(self.lib.mod_get_rectification(self.h, C.byref(l), C.byref(r), C.byref(on)))
         return (l, r) if on.value else None
 
+    def set_side_by_side(self, on) -> None:
+        """Side-by-side stereo messages (mod_set_side_by_side): while on, one message holds both eyes, the layout's width is one eye's
+        and its step the whole row's (>= 2 * width * channels); the stereo *_host entry points take it in `left`.  Off by default; read
+        when a call or a submit is made."""
+        self._check(self.lib.mod_set_side_by_side(self.h, int(bool(on)) if isinstance(on, (bool, np.bool_)) else int(on)))
+
+    def get_side_by_side(self) -> bool:
+        on = C.c_int32(-1)
+        self._check(self.lib.mod_get_side_by_side(self.h, C.byref(on)))
+        return bool(on.value)
+
     def speckle_filter(self, dev_planes: torch.Tensor, size: int, range: int) -> torch.Tensor:   # noqa: A002 (stereo_image_proc's name)
         """The speckle stage alone, in place (mod_disparity_speckle_dev), on device float32 planes (F, H, W) or (H, W) of the camera's
         size: pixels take part when finite and >= the camera's min_disparity, removed ones become min_disparity - 1.  Enqueued on the
@@ -256,7 +267,8 @@ class Context:
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Grey planes (F, H, W) uint8 at the camera size from device 8-bit frames (mod_image_to_mono_dev): `src` holds F frames of
         layout.step * layout.height bytes each, back to back (any shape, contiguous uint8); layout None = the context's.  The camera-sized
-        window at (x0, y0) is converted with OpenCV's 8-bit BGR2GRAY formula.  Enqueued on the context's stream."""
+        window at (x0, y0) is converted with OpenCV's 8-bit BGR2GRAY formula (packed YUV 4:2:2: grey = Y).  Enqueued on the context's
+        stream."""
         lay = layout if layout is not None else self.get_image_layout()
         if src.dtype != torch.uint8 or not src.is_contiguous() or src.device.type != "cuda":
             raise ValueError("src must be a contiguous uint8 device tensor")
@@ -276,7 +288,8 @@ class Context:
     def rectify(self, src: torch.Tensor, layout: Optional[capi.ModImageLayout] = None, eye: int = capi.MOD_EYE_LEFT,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Rectified grey planes (F, H, W) uint8 at the camera size from raw device 8-bit frames (mod_rectify_dev): `src` as for
-        image_to_mono, `eye` selects the map (capi.MOD_EYE_LEFT / MOD_EYE_RIGHT).  Enqueued on the context's stream."""
+        image_to_mono, `eye` selects the map (capi.MOD_EYE_LEFT / MOD_EYE_RIGHT) and, while side by side, the pane.  Enqueued on the
+        context's stream."""
         lay = layout if layout is not None else self.get_image_layout()
         if src.dtype != torch.uint8 or not src.is_contiguous() or src.device.type != "cuda":
             raise ValueError("src must be a contiguous uint8 device tensor")

@@ -681,7 +681,9 @@ def make_ego_images(W: int, H: int, seed: int = 0, frames: int = 2, D: int = 128
     return out
 
 
-_ENCODINGS = {"mono8": (1, None), "bgr8": (3, (0, 1, 2)), "rgb8": (3, (2, 1, 0)), "bgra8": (4, (0, 1, 2)), "rgba8": (4, (2, 1, 0))}
+_ENCODINGS = {"mono8": (1, None), "bgr8": (3, (0, 1, 2)), "rgb8": (3, (2, 1, 0)), "bgra8": (4, (0, 1, 2)), "rgba8": (4, (2, 1, 0)),
+              "yuv422": (2, None), "yuv422_yuy2": (2, None)}
+_LUMA_AT = {"yuv422": 1, "yuv422_yuy2": 0}     # packed 4:2:2: the byte of a pixel that holds its Y (UYVY, YUYV)
 
 
 def to_colour(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=None):
@@ -692,6 +694,7 @@ def to_colour(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=N
       canvas      (msg_w, msg_h) >= (W, H): the image sits in the centred window (image_crop.cpp's (msg - size) / 2) of a larger
                   message whose other pixels are random
       pad         bytes at the end of every row (step = msg_w * channels + pad), random
+    yuv422 / yuv422_yuy2: Y = the grey value, chroma random (it is never read); seed only seeds the chroma.
     Returns (payload uint8 [msg_h][step], layout dict (encoding, width, height, step, x0, y0), expected grey [H][W] uint8)."""
     if encoding not in _ENCODINGS:
         raise ValueError(f"unknown encoding {encoding!r}")
@@ -708,6 +711,10 @@ def to_colour(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=N
     if C == 1:
         px = v[..., None]
         expect = mono.copy()
+    elif order is None:
+        px = rng.integers(0, 256, size=(H, W, C)).astype(np.int64)
+        px[..., _LUMA_AT[encoding]] = v
+        expect = mono.copy()
     else:
         if seed is None:
             bgr = np.stack([v, v, v], -1)
@@ -720,3 +727,18 @@ def to_colour(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=N
     msg[y0:y0 + H, x0 * C:(x0 + W) * C] = px.reshape(H, W * C).astype(np.uint8)
     layout = {"encoding": encoding, "width": mw, "height": mh, "step": step, "x0": x0, "y0": y0}
     return msg, layout, expect
+
+
+def side_by_side(left: np.ndarray, right: np.ndarray, layout: dict, pad: int = 0, seed: int = 0):
+    """Two messages of one layout (to_colour's payloads [msg_h][step]) as ONE side-by-side message (mod_set_side_by_side): the left
+    message's pixel bytes in the left half of every row, the right one's in the right half, `pad` random bytes behind them.  Returns
+    (payload uint8 [msg_h][2 * width * channels + pad], layout dict: width, height, x0, y0 of ONE eye, step of the whole row)."""
+    C = _ENCODINGS[layout["encoding"]][0]
+    row = layout["width"] * C
+    if left.shape != right.shape or left.shape[1] < row or pad < 0:
+        raise ValueError("left and right must be messages of `layout`")
+    rng = np.random.Generator(np.random.PCG64([0x5B5, int(seed)]))
+    msg = rng.integers(0, 256, size=(left.shape[0], 2 * row + pad), dtype=np.uint8)
+    msg[:, :row] = left[:, :row]
+    msg[:, row:2 * row] = right[:, :row]
+    return msg, dict(layout, step=2 * row + pad)

@@ -1,6 +1,7 @@
 """HIP-event timing of the on-GPU image conversion (mod_image_to_mono_dev, csrc/ingest.hip) on 64 frames of 1920 x 1080 for every
 encoding (bytes in + out per second against the HBM's 8 TB/s), and the odometry stream (mod_submit_odometry_host) at 1280 x 720 fed
-mono8 and bgra8 images, from page-locked and from pageable host memory, in frames/s.  Prints one JSON line per measurement.
+mono8 and bgra8 images and ONE side-by-side yuv422_yuy2 message per frame (mod_set_side_by_side), from page-locked and from pageable
+host memory, in frames/s.  Prints one JSON line per measurement.
 Also an odd step and origin (every dword alignment of a run's source).  Run on the GPU: python tools/time_ingest.py [reps]"""
 import ctypes as C
 import json
@@ -24,10 +25,10 @@ def kernel(reps):
     ctx = Context(W, H, max_frames=1)
     ctx.set_camera(synth.make_camera(W, H))
     out = torch.empty((F, H, W), dtype=torch.uint8, device=ctx.device)
-    legs = [(enc, capi.image_layout(enc, W, H)) for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8")]
+    legs = [(enc, capi.image_layout(enc, W, H)) for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422", "yuv422_yuy2")]
     # the hard case for alignment: an odd step and an odd origin, so the runs of a row start at every byte offset of a dword
     legs += [(enc + " odd step/x0", capi.image_layout(enc, W + 3, H + 1, step=(W + 3) * capi.CHANNELS[capi.ENCODINGS[enc]] + 1, x0=1, y0=1))
-             for enc in ("bgr8", "bgra8")]
+             for enc in ("bgr8", "bgra8", "yuv422_yuy2")]
     for enc, lay in legs:
         src = torch.randint(0, 256, (F * lay.step * lay.height,), dtype=torch.uint8, device=ctx.device)
         call = lambda: ctx.lib.mod_image_to_mono_dev(ctx.h, F, src.data_ptr(), C.byref(lay), out.data_ptr())
@@ -50,7 +51,7 @@ def kernel(reps):
     ctx.close()
 
 
-def stream_fps(W, H, reps, encoding, pinned):
+def stream_fps(W, H, reps, encoding, pinned, side_by_side=False):
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.pipeline import Context
     m = synth.make_ego_images(W, H, seed=1, frames=2)
@@ -61,8 +62,13 @@ def stream_fps(W, H, reps, encoding, pinned):
     ctx.set_params(synth.Params())
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
     imgs, pins, keep = [], [], []
-    for k in ("left0", "right0", "left1", "right1"):
-        msg, lay, _ = synth.to_colour(m[k], encoding, seed=None if encoding == "mono8" else 1)
+    msgs = [synth.to_colour(m[k], encoding, seed=None if encoding == "mono8" else 1) for k in ("left0", "right0", "left1", "right1")]
+    lay = msgs[0][1]
+    msgs = [msg for msg, _, _ in msgs]
+    if side_by_side:                  # one message per frame: two messages in all, and no right pointer
+        (a, lay), (b, _) = (synth.side_by_side(msgs[i], msgs[i + 1], lay) for i in (0, 2))
+        msgs = [a, b]
+    for msg in msgs:
         if pinned:
             p = C.c_void_p()
             assert ctx.lib.mod_host_malloc(ctx.h, msg.nbytes, C.byref(p)) == 0
@@ -73,12 +79,13 @@ def stream_fps(W, H, reps, encoding, pinned):
             keep.append(msg)
             imgs.append(msg.ctypes.data)
     ctx.set_image_layout(capi.image_layout(lay["encoding"], lay["width"], lay["height"], lay["step"]))
+    ctx.set_side_by_side(side_by_side)
     objs = [(capi.ModObject * 64)() for _ in range(3)]
     t, n = C.c_int32(-1), C.c_int32(-1)
     pending = []
 
     def step(i):
-        l, r = (imgs[0], imgs[1]) if i % 2 == 0 else (imgs[2], imgs[3])
+        l, r = (imgs[i % 2], None) if side_by_side else (imgs[2 * (i % 2)], imgs[2 * (i % 2) + 1])
         if len(pending) == 3:
             assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
         rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
@@ -106,10 +113,10 @@ def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     kernel(reps)
     for pinned in (True, False):
-        for enc in ("mono8", "bgra8"):
-            fps = stream_fps(1280, 720, min(reps, 100), enc, pinned)
-            print(json.dumps({"what": "mod_submit_odometry_host", "encoding": enc, "host_memory": "pinned" if pinned else "pageable",
-                              "W": 1280, "H": 720, "frames_per_s": round(fps, 1)}), flush=True)
+        for enc, sbs in (("mono8", False), ("bgra8", False), ("yuv422_yuy2", False), ("yuv422_yuy2", True)):
+            fps = stream_fps(1280, 720, min(reps, 100), enc, pinned, sbs)
+            print(json.dumps({"what": "mod_submit_odometry_host", "encoding": enc, "side_by_side": sbs,
+                              "host_memory": "pinned" if pinned else "pageable", "W": 1280, "H": 720, "frames_per_s": round(fps, 1)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -2,7 +2,9 @@
 beside the plain conversion (mod_image_to_mono_dev, csrc/ingest.hip) of the same frames in the same run (it moves the same image
 bytes without the map), in bytes in + map + out per second against the HBM's 8 TB/s; and the odometry stream
 (mod_submit_odometry_host) at 1280 x 720 fed bgra8 messages from page-locked memory without a rectification and with the identity
-calibration (the same grey planes reach the estimators, so the two legs differ by the rectification stage alone), in frames/s.
+calibration (the same grey planes reach the estimators, so the two legs differ by the rectification stage alone), in frames/s; and
+the rectified stream fed yuv422_yuy2 as two messages per frame and as ONE side-by-side message of the same content
+(mod_set_side_by_side: the same bytes cross PCIe, in one copy instead of two; passing the whole frame for each eye would move twice that).
 k_rectify has two paths, a source box staged in LDS and direct gathers from global memory; the product picks one
 (csrc/rectify.hip kStagedDefault).  The measurement builds that pin each path are timed as further legs in the same rounds, and
 their grey planes are compared with the product's bit for bit:
@@ -83,7 +85,7 @@ def kernel(reps):
         else:
             emit({"what": what, "missing": os.path.relpath(build, ROOT), "note": "not built: this run has no such leg"})
     out = torch.empty((F, H, W), dtype=torch.uint8, device=ctx.device)
-    for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8"):
+    for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422", "yuv422_yuy2"):
         lay = capi.image_layout(enc, W, H)
         Cn = capi.CHANNELS[lay.encoding]
         src = torch.randint(0, 256, (F * lay.step * lay.height,), dtype=torch.uint8, device=ctx.device)
@@ -110,7 +112,7 @@ def kernel(reps):
         c.close()
 
 
-def stream_fps(W, H, reps, rectify):
+def stream_fps(W, H, reps, rectify, encoding="bgra8", side_by_side=False):
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.pipeline import Context
     m = synth.make_ego_images(W, H, seed=1, frames=2)
@@ -126,20 +128,26 @@ def stream_fps(W, H, reps, rectify):
         ctx.set_rectification(ident, ident)
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
     imgs, pins = [], []
-    for k in ("left0", "right0", "left1", "right1"):
-        msg, lay, _ = synth.to_colour(m[k], "bgra8", seed=1)
+    msgs = [synth.to_colour(m[k], encoding, seed=1) for k in ("left0", "right0", "left1", "right1")]
+    lay = msgs[0][1]
+    msgs = [msg for msg, _, _ in msgs]
+    if side_by_side:                  # one message per frame: two messages in all, and no right pointer
+        (a, lay), (b, _) = (synth.side_by_side(msgs[i], msgs[i + 1], lay) for i in (0, 2))
+        msgs = [a, b]
+    for msg in msgs:
         p = C.c_void_p()
         assert ctx.lib.mod_host_malloc(ctx.h, msg.nbytes, C.byref(p)) == 0
         C.memmove(p.value, msg.ctypes.data, msg.nbytes)
         pins.append(p)
         imgs.append(p.value)
     ctx.set_image_layout(capi.image_layout(lay["encoding"], lay["width"], lay["height"], lay["step"]))
+    ctx.set_side_by_side(side_by_side)
     objs = [(capi.ModObject * 64)() for _ in range(3)]
     t, n = C.c_int32(-1), C.c_int32(-1)
     pending = []
 
     def step(i):
-        l, r = (imgs[0], imgs[1]) if i % 2 == 0 else (imgs[2], imgs[3])
+        l, r = (imgs[i % 2], None) if side_by_side else (imgs[2 * (i % 2)], imgs[2 * (i % 2) + 1])
         if len(pending) == 3:
             assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
         rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
@@ -160,7 +168,7 @@ def stream_fps(W, H, reps, rectify):
     for p in pins:
         ctx.lib.mod_host_free(ctx.h, p)
     ctx.close()
-    return frames / dt
+    return frames / dt, lay["step"] * lay["height"] * (1 if side_by_side else 2)
 
 
 def main():
@@ -170,8 +178,13 @@ def main():
         return
     for rnd in range(2):
         for rectify in (False, True):
-            fps = stream_fps(1280, 720, min(reps, 100), rectify)
+            fps, _ = stream_fps(1280, 720, min(reps, 100), rectify)
             emit({"what": "mod_submit_odometry_host", "encoding": "bgra8", "host_memory": "pinned", "rectification": "identity" if rectify else "off", "round": rnd,
+                  "W": 1280, "H": 720, "frames_per_s": round(fps, 1)})
+        for sbs in (False, True):
+            fps, h2d = stream_fps(1280, 720, min(reps, 100), True, "yuv422_yuy2", sbs)
+            emit({"what": "mod_submit_odometry_host", "encoding": "yuv422_yuy2", "host_memory": "pinned", "rectification": "identity", "round": rnd,
+                  "messages_per_frame": 1 if sbs else 2, "h2d_bytes_per_frame": h2d, "h2d_copies_per_frame": 1 if sbs else 2,
                   "W": 1280, "H": 720, "frames_per_s": round(fps, 1)})
 
 
