@@ -371,16 +371,37 @@ int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const floa
  * cv_bridge's COLOR_YUV2GRAY_UYVY / _YUY2 and image_proc's image_mono do); chroma is never read, and any width and x0 is legal, odd
  * ones included.  Under rectification Y is interpolated as one channel, like mono8: parity with "convert to BGR, rectify, convert to
  * grey" is not claimed.
+ * 8-bit Bayer mosaics, what an industrial or MIPI sensor delivers, are demosaiced straight to grey: MOD_ENCODING_BAYER_RGGB8 /
+ * _BGGR8 / _GBRG8 / _GRBG8 (ROS "bayer_rggb8", ...), one byte per pixel, step >= width, width >= 3 and height >= 3.  For
+ * bayer_ABCD8, pixel (x, y) of the MESSAGE carries the colour ABCD[2 (y & 1) + (x & 1)].  With p(x, y) the message byte and
+ * kR = 4899, kG = 9617, kB = 1868 (the grey weights above), an interior pixel (1 <= x <= width - 2, 1 <= y <= height - 2) is, in
+ * uint32 arithmetic,
+ *   at an R or B site (own weight kc, the opposite colour's ko):
+ *       v = (4 p(x,y) kc + (the four edge neighbours' sum) kG + (the four diagonal neighbours' sum) ko + 32768) >> 16
+ *   at a G site (kh: the weight of the colour that shares its row, kv: of the one that shares its column):
+ *       v = (2 p(x,y) kG + (p(x-1,y) + p(x+1,y)) kh + (p(x,y-1) + p(x,y+1)) kv + 16384) >> 15
+ * which is bilinear demosaicing and the grey above with a single rounding; a pixel of the message's one-pixel frame copies the
+ * nearest interior result, v(clamp(x, 1, width - 2), clamp(y, 1, height - 2)).  The window is the message's demosaic, cropped
+ * (debayer, then crop): a pixel at the window's edge uses the message's pixels outside the window, x0 and y0 of either parity are
+ * legal, and only the message's own edge is a border.  Side by side (below), each pane is a message of its own: the colour at the
+ * right pane's (0, 0) is the message's colour at column `width` (an odd width shifts the pattern by one column), the frame rule
+ * applies at the pane's edges, and no output pixel of one eye depends on a byte of the other.  Under rectification the whole
+ * message (or pane) is demosaiced to grey by this rule and then rectified as mono8 of step `width`.  This is the arithmetic of this
+ * library; bit parity with OpenCV's Bayer conversions is not claimed.
  *   mod_set_image_layout   the layout of the HOST images every *_host image entry point reads (mod_sgm_compute_host,
  *                          mod_flow_compute_host, mod_submit_stereo_host, mod_submit_images_host, mod_submit_odometry_host),
  *                          read at call time like mod_set_params: a frame in flight completes with the layout of its own submit.
  *                          NULL = mono8, packed, W x H, origin 0 (the layout of a context that never set one).  Only the window
- *                          crosses PCIe; mono8 is copied straight into the estimator's buffer, colour is converted on the GPU.
+ *                          crosses PCIe (a Bayer window with its one-pixel apron, clamped to the message or pane); mono8 is copied
+ *                          straight into the estimator's buffer, colour and Bayer are converted on the GPU.
  *   mod_get_image_layout   the layout in force (the NULL layout spelled out)
  *   mod_image_to_mono_dev  device frames stacked at step * height bytes -> grey planes [frames][H][W]; layout NULL = the context's.
  *                          Ordered on the context's stream.  NULL src -> MOD_SKIP_NO_DISPARITY_NOW, like a NULL image elsewhere.
- *                          It has no eye: for the right pane of side-by-side frames (below) the caller passes src + width * channels.
- * MOD_ERR_INVALID_ARGUMENT: unknown encoding, step < width * channels, a window that does not fit inside the message;
+ *                          It has no eye: for the right pane of side-by-side frames (below) the caller passes src + width * channels
+ *                          (Bayer: and, for an odd width, the encoding as it lies there: rggb <-> grbg, bggr <-> gbrg); the
+ *                          Bayer region is width x height at src, so the pane's edges are borders.
+ * MOD_ERR_INVALID_ARGUMENT: unknown encoding, step < width * channels, a window that does not fit inside the message, a Bayer
+ * layout with width < 3 or height < 3;
  * MOD_ERR_NOT_CONFIGURED: no camera yet (the window size is the camera's). */
 #define MOD_ENCODING_MONO8 0
 #define MOD_ENCODING_BGR8  1
@@ -389,6 +410,10 @@ int  mod_egomotion_host(ModContext *ctx, const float *disparity_prev, const floa
 #define MOD_ENCODING_RGBA8 4
 #define MOD_ENCODING_YUV422 5        /* UYVY */
 #define MOD_ENCODING_YUV422_YUY2 6   /* YUYV */
+#define MOD_ENCODING_BAYER_RGGB8 16  /* 8-bit Bayer mosaics, one byte per pixel; 7..15 and anything above 19 are unknown */
+#define MOD_ENCODING_BAYER_BGGR8 17
+#define MOD_ENCODING_BAYER_GBRG8 18
+#define MOD_ENCODING_BAYER_GRBG8 19
 typedef struct ModImageLayout {   /* 24 bytes */
   int32_t encoding;               /* MOD_ENCODING_* */
   int32_t width, height;          /* of the message (sensor_msgs/Image width, height); side by side: of one eye's pane */

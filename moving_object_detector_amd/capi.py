@@ -40,6 +40,11 @@ MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MO
 MOD_ENCODING_YUV422, MOD_ENCODING_YUV422_YUY2 = 5, 6   # packed 4:2:2: UYVY, YUYV (grey = Y)
 ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
              "rgba8": MOD_ENCODING_RGBA8, "yuv422": MOD_ENCODING_YUV422, "yuv422_yuy2": MOD_ENCODING_YUV422_YUY2}
+# 8-bit Bayer mosaics, demosaiced straight to grey on the GPU (one byte per pixel; width, height >= 3)
+MOD_ENCODING_BAYER_RGGB8, MOD_ENCODING_BAYER_BGGR8, MOD_ENCODING_BAYER_GBRG8, MOD_ENCODING_BAYER_GRBG8 = 16, 17, 18, 19
+BAYER_ENCODINGS = {"bayer_rggb8": MOD_ENCODING_BAYER_RGGB8, "bayer_bggr8": MOD_ENCODING_BAYER_BGGR8,
+                   "bayer_gbrg8": MOD_ENCODING_BAYER_GBRG8, "bayer_grbg8": MOD_ENCODING_BAYER_GRBG8}
+BAYER_CHANNELS = {e: 1 for e in BAYER_ENCODINGS.values()}    # bytes per pixel (a dict of its own: CHANNELS' keys are ENCODINGS' values)
 # bytes per pixel
 CHANNELS = {MOD_ENCODING_MONO8: 1, MOD_ENCODING_BGR8: 3, MOD_ENCODING_RGB8: 3, MOD_ENCODING_BGRA8: 4, MOD_ENCODING_RGBA8: 4,
             MOD_ENCODING_YUV422: 2, MOD_ENCODING_YUV422_YUY2: 2}
@@ -148,12 +153,15 @@ class ModImageLayout(C.Structure):
 
 
 def image_layout(encoding, width: int, height: int, step=None, x0: int = 0, y0: int = 0) -> ModImageLayout:
-    """ModImageLayout of a sensor_msgs/Image: `encoding` a MOD_ENCODING_* value or its ROS name ("bgr8", ...); step None = packed
+    """ModImageLayout of a sensor_msgs/Image: `encoding` a MOD_ENCODING_* value or its ROS name ("bgr8", "bayer_rggb8", ...); step None = packed
     rows (width * channels); (x0, y0) = top-left of the camera-sized window taken from it.  For a side-by-side message (width = one
     eye's) pass the step of the whole row."""
-    enc = ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+    if isinstance(encoding, str):
+        enc = ENCODINGS[encoding] if encoding in ENCODINGS else BAYER_ENCODINGS[encoding]
+    else:
+        enc = int(encoding)
     if step is None:
-        step = int(width) * CHANNELS.get(enc, 1)
+        step = int(width) * CHANNELS.get(enc, BAYER_CHANNELS.get(enc, 1))
     return ModImageLayout(enc, int(width), int(height), int(step), int(x0), int(y0))
 
 

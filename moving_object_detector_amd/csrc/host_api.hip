@@ -1,6 +1,7 @@
 // host_api.hip — the C ABI's host-pointer entry points: the single-frame *_host calls, which stage one frame through device buffers
 // of the context, and the submit / collect stream with its pipe of slots, copy streams and ring of planes.  Host-side only.
 #include "mod_context.h"
+#include "bayer_region.h"
 
 #include <algorithm>
 #include <cstring>
@@ -11,7 +12,9 @@ static size_t pixels(const ModContext *c) { return (size_t)c->dc.W * c->dc.H; }
 static int alloc_frame_buffers(ModContext *c, ModContext::FrameBuffers &b, int planes) {
   const size_t N = c->maxN;
   HIP_TRY(c, dalloc(b.dprev, N));
-  HIP_TRY(c, dalloc(b.flow, 2 * N));
+  // + 16 bytes: the synchronous calls stage their two windows in the staging's flow buffer, which must hold window_stage_bytes()
+  // (two Bayer regions of a camera one pixel high outgrow 8 N); the pipe's slots share this allocator and do not need the extra
+  HIP_TRY(c, dalloc(b.flow, 2 * N + 4));
   HIP_TRY(c, dalloc(b.planes, planes * N));
   if (!b.aos) HIP_TRY(c, hipMalloc(b.aos.put(), 32 * N));
   HIP_TRY(c, dalloc(b.labels, N));
@@ -71,6 +74,18 @@ static hipError_t copy_window(const ModImageLayout &l, int W, int H, const uint8
   return hipMemcpy2DAsync(dst, row, o, (size_t)l.step, row, (size_t)H, hipMemcpyHostToDevice, s);
 }
 
+// bytes that hold two staged windows of any encoding: 4 bytes a pixel, or two Bayer regions (bayer_region.h: <= 6 N + 12 bytes while W H <= N)
+static size_t window_stage_bytes(const ModContext *c) { return 8 * c->maxN + 16; }
+// the region of one host message (src: the message, or its pane) to dst on stream s, rows packed
+static hipError_t copy_bayer_region(const ModImageLayout &l, const BayerRegion &g, const uint8_t *src, uint8_t *dst, hipStream_t s) {
+  return hipMemcpy2DAsync(dst, (size_t)g.rw, src + (size_t)g.ay * l.step + g.ax, (size_t)l.step, (size_t)g.rw, (size_t)g.rh, hipMemcpyHostToDevice, s);
+}
+// ... and the window's grey from it on the context's stream; right_pane: the message the region came from is a right pane
+static void bayer_region_to_mono(ModContext *c, const ModImageLayout &l, const BayerRegion &g, bool right_pane, const uint8_t *staged, uint8_t *grey) {
+  launch_bayer_to_mono(c->dc.W, c->dc.H, 1, staged, 0, g.rw, g.rw, g.rh, l.x0 - g.ax, l.y0 - g.ay,
+                       bayer_phase(l.encoding, g.ax + (right_pane ? l.width : 0), g.ay), grey, c->stream);
+}
+
 // side by side (mod_set_side_by_side): `right` of a call that takes one message for both eyes must be NULL or that message
 static int check_one_message(ModContext *c, const uint8_t *left, const uint8_t *right) {
   return right && right != left ? fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side: right must be NULL or equal to left") : MOD_OK;
@@ -87,8 +102,14 @@ static int copy_messages(ModContext *c, const ModImageLayout &l, bool panes, con
 }
 // ... and k_rectify from there on the context's stream, each message (or each pane of the one message) with the map of its eye.  A
 // pane is a message of the pane's width that starts width * channels bytes into the row and ends with the message's last byte.
-static int rectify_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *raw, int eye1, uint8_t *grey0, uint8_t *grey1) {
+// Bayer messages are demosaiced whole into `bayer` first (room for two grey planes of the message's, or pane's, size).
+static int rectify_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *raw, int eye1, uint8_t *bayer, uint8_t *grey0,
+                            uint8_t *grey1) {
   const size_t M = (size_t)l.step * l.height, at1 = panes ? pane_offset(l, MOD_EYE_RIGHT) : M;
+  if (is_bayer(l.encoding)) {
+    if (int rc = rectify_bayer(c, l, 1, raw, MOD_EYE_LEFT, bayer, c->rect.map[MOD_EYE_LEFT].q, grey0)) return rc;
+    return rectify_bayer(c, l, 1, raw + at1, panes ? MOD_EYE_RIGHT : MOD_EYE_LEFT, bayer + (size_t)l.width * l.height, c->rect.map[eye1].q, grey1);
+  }
   launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw, M, M, l.step, l.width, l.height, c->rect.map[MOD_EYE_LEFT].q, grey0, c->stream);
   launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw + at1, M, panes ? M - at1 : M, l.step, l.width, l.height, c->rect.map[eye1].q, grey1,
                  c->stream);
@@ -106,14 +127,26 @@ static int upload_pair(ModContext *c, const uint8_t *img0, const uint8_t *img1, 
   if (c->rect.on) {
     int rc;
     if ((rc = ensure_rectify_map(c, MOD_EYE_LEFT, l)) || (rc = ensure_rectify_map(c, eye1, l)) || (rc = ensure_raw_stage(c, c->staging.raw, l)) ||
+        (rc = is_bayer(l.encoding) ? ensure_stage_bytes(c, c->staging.bayer_grey, 2 * (size_t)l.width * l.height) : MOD_OK) ||
         (rc = copy_messages(c, l, panes, img0, img1, c->staging.raw.buf, c->stream)))
       return rc;
     *grey = static_cast<uint8_t *>(c->staging.aos.get());
-    return rectify_messages(c, l, panes, c->staging.raw.buf, eye1, *grey, *grey + pixels(c));
+    return rectify_messages(c, l, panes, c->staging.raw.buf, eye1, c->staging.bayer_grey.buf, *grey, *grey + pixels(c));
   }
   if (panes) img1 = img0 + pane_offset(l, MOD_EYE_RIGHT);   // one window from each pane
   const int W = c->dc.W, H = c->dc.H;
   uint8_t *slot = reinterpret_cast<uint8_t *>(c->staging.flow.get());
+  if (is_bayer(l.encoding)) {      // the two regions into the slot, their windows' grey into the cloud staging
+    const BayerRegion g = bayer_region(l.width, l.height, l.x0, l.y0, W, H);
+    uint8_t *slot1 = slot + (size_t)g.rw * g.rh;
+    HIP_TRY(c, copy_bayer_region(l, g, img0, slot, c->stream));
+    HIP_TRY(c, copy_bayer_region(l, g, img1, slot1, c->stream));
+    *grey = static_cast<uint8_t *>(c->staging.aos.get());
+    bayer_region_to_mono(c, l, g, false, slot, *grey);
+    bayer_region_to_mono(c, l, g, panes, slot1, *grey + pixels(c));
+    HIP_TRY(c, hipGetLastError());
+    return MOD_OK;
+  }
   const size_t P = pixels(c) * image_channels(l.encoding);
   HIP_TRY(c, copy_window(l, W, H, img0, slot, c->stream));
   HIP_TRY(c, copy_window(l, W, H, img1, slot + P, c->stream));
@@ -241,8 +274,10 @@ static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout 
 static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   HIP_TRY(c, dalloc(f.s.img, 2 * c->maxN));
   if (rq.estimates_flow()) HIP_TRY(c, dalloc(f.now.left, c->maxN));
-  if (f.rectify) { if (int rc = ensure_raw_stage(c, f.s.raw, f.lay)) return rc; }
-  else if (f.colour()) HIP_TRY(c, dalloc(f.s.stage, 8 * c->maxN));
+  if (f.rectify) {
+    if (int rc = ensure_raw_stage(c, f.s.raw, f.lay)) return rc;
+    if (int rc = is_bayer(f.lay.encoding) ? ensure_stage_bytes(c, f.s.bayer_grey, 2 * (size_t)f.lay.width * f.lay.height) : MOD_OK) return rc;
+  } else if (f.colour()) HIP_TRY(c, dalloc(f.s.stage, window_stage_bytes(c)));
   f.left = rq.estimates_flow() ? f.now.left.get() : f.s.img.get();
   f.right = f.s.img.get() + pixels(c);
   return MOD_OK;
@@ -259,7 +294,7 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
     HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
     // the grey images are written on the context's stream, which is behind every older reader of them already
-    if (int rc = rectify_messages(c, f.lay, f.panes, f.s.raw.buf, MOD_EYE_RIGHT, f.left, f.right)) return rc;
+    if (int rc = rectify_messages(c, f.lay, f.panes, f.s.raw.buf, MOD_EYE_RIGHT, f.s.bayer_grey.buf, f.left, f.right)) return rc;
     HIP_TRY(c, f.s.stage_read.record(c->stream));
     return MOD_OK;
   }
@@ -268,12 +303,25 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
   if (rq.estimates_flow() && !f.colour()) HIP_TRY(c, f.now.left_read.wait(p.h2d));
   if (f.colour()) HIP_TRY(c, f.s.stage_read.wait(p.h2d));
   const uint8_t *right = f.panes ? rq.left + pane_offset(f.lay, MOD_EYE_RIGHT) : rq.right;   // one window from each pane
-  HIP_TRY(c, copy_window(f.lay, W, H, rq.left, f.colour() ? f.s.stage.get() : f.left, p.h2d));
-  HIP_TRY(c, copy_window(f.lay, W, H, right, f.colour() ? f.s.stage.get() + P : f.right, p.h2d));
+  const bool bayer = is_bayer(f.lay.encoding);
+  const BayerRegion g = bayer ? bayer_region(f.lay.width, f.lay.height, f.lay.x0, f.lay.y0, W, H) : BayerRegion{};
+  uint8_t *stage1 = f.colour() ? f.s.stage.get() + (bayer ? (size_t)g.rw * g.rh : P) : nullptr;
+  if (bayer) {
+    HIP_TRY(c, copy_bayer_region(f.lay, g, rq.left, f.s.stage, p.h2d));
+    HIP_TRY(c, copy_bayer_region(f.lay, g, right, stage1, p.h2d));
+  } else {
+    HIP_TRY(c, copy_window(f.lay, W, H, rq.left, f.colour() ? f.s.stage.get() : f.left, p.h2d));
+    HIP_TRY(c, copy_window(f.lay, W, H, right, f.colour() ? stage1 : f.right, p.h2d));
+  }
   if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
   HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
-  if (f.colour()) {                 // cv_bridge::toCvCopy(..., MONO8) (:220-221) on the GPU
+  if (bayer) {                      // image_proc's debayer and cv_bridge's conversion on the GPU
+    bayer_region_to_mono(c, f.lay, g, false, f.s.stage, f.left);
+    bayer_region_to_mono(c, f.lay, g, f.panes, stage1, f.right);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, f.s.stage_read.record(c->stream));
+  } else if (f.colour()) {          // cv_bridge::toCvCopy(..., MONO8) (:220-221) on the GPU
     launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage, P, (int)(P / H), 0, 0, f.left, c->stream);
     launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage + P, P, (int)(P / H), 0, 0, f.right, c->stream);
     HIP_TRY(c, hipGetLastError());

@@ -106,6 +106,8 @@ int image_channels(int encoding) {
     case MOD_ENCODING_BGR8: case MOD_ENCODING_RGB8: return 3;
     case MOD_ENCODING_BGRA8: case MOD_ENCODING_RGBA8: return 4;
     case MOD_ENCODING_YUV422: case MOD_ENCODING_YUV422_YUY2: return 2;   // bytes per pixel; one of them is the grey
+    case MOD_ENCODING_BAYER_RGGB8: case MOD_ENCODING_BAYER_BGGR8: case MOD_ENCODING_BAYER_GBRG8: case MOD_ENCODING_BAYER_GRBG8:
+      return 1;                                                           // one colour sample per pixel (bayer.hip converts these)
     default: return 0;
   }
 }

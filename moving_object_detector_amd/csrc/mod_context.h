@@ -128,6 +128,9 @@ struct ModContext {
   // whole raw messages on their way to k_rectify: room for two of the layout in force (allocated on first use, grow-only); a
   // side-by-side message is one, and uses the first half
   struct RawStage { DevPtr<uint8_t> buf; size_t bytes = 0; };
+  // Bayer messages under a rectification are demosaiced whole (debayer, then rectify): the grey planes k_rectify then samples, one
+  // per frame of mod_rectify_dev (the host paths have their own, beside their raw stages); allocated on first use, grow-only
+  RawStage bayer_grey;
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -143,7 +146,7 @@ struct ModContext {
     DevPtr<ModObject> objects;
   };
   // one-frame staging of the synchronous entry points (allocated on first use; ready: the last allocation has succeeded)
-  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; RawStage raw; } staging;
+  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; RawStage raw, bayer_grey; } staging;
   // host streaming (mod_submit_frame_host and the mod_submit_*_host image entries): a slot per ticket, a ring of MOD_PIPELINE_DEPTH + 1
   // planes (frame t's plane is frame t+1's "previous"), two copy streams and the events and fences that order them with the kernels
   struct Pipe {
@@ -165,6 +168,7 @@ struct ModContext {
       DevPtr<uint8_t> stage;
       Fence stage_read;                              // ... the kernels that read them have been enqueued (context stream)
       RawStage raw;                                  // with a rectification set: the slot's two raw messages instead, behind the same fence
+      RawStage bayer_grey;                           // ... and, for Bayer messages, their two demosaiced grey planes (k_rectify samples these)
       // mod_submit_odometry_host: the slot's estimate on the device (its element of Pipe::ego, last copied out before the slot's
       // previous ticket was collected) and its pinned host copy; collect reads the status
       EgoSlot *ego = nullptr;
@@ -265,6 +269,11 @@ inline size_t pane_offset(const ModImageLayout &l, int eye) { return eye == MOD_
 int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l);
 // room for two raw messages of `l` in r; a buffer that has to grow is replaced once the context's streams have drained
 int ensure_raw_stage(ModContext *c, ModContext::RawStage &r, const ModImageLayout &l);
+int ensure_stage_bytes(ModContext *c, ModContext::RawStage &r, size_t need);   // ... for `need` bytes
+// Bayer under a rectification: `frames` whole messages at src (or their panes: src points at the pane, `pane` says which eye's) to
+// the grey planes `grey` [frames][height][width], then k_rectify from those as mono8 through `map` into mono; context's stream
+int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint8_t *src, int pane, uint8_t *grey, const int32_t *map,
+                  uint8_t *mono);
 int begin_cluster_scratch(ModContext *c);
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                 const ModClusterOut *out);

@@ -135,6 +135,15 @@ int image_channels(int encoding);   // bytes per pixel; 0: unknown encoding
 void launch_to_mono(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int x0, int y0, uint8_t *dst,
                     hipStream_t s);
 
+// 8-bit Bayer mosaics to grey (bayer.hip).  Region rw x rh bytes (row pitch `step`, frames frame_bytes apart; rw, rh >= 3) whose
+// byte (0, 0) lies `phase` into the RGGB tile; the window W x H at (x0, y0) of it -> dst [frames][H][W].  Pixels of the region's
+// one-pixel frame copy the nearest interior result
+void launch_bayer_to_mono(int W, int H, int frames, const uint8_t *src, size_t frame_bytes, int step, int rw, int rh, int x0, int y0, int phase,
+                          uint8_t *dst, hipStream_t s);
+// the phase of a region whose (0, 0) is pixel (x, y) of a MOD_ENCODING_BAYER_* message; -1: not a Bayer encoding
+int bayer_phase(int encoding, int x, int y);
+inline bool is_bayer(int encoding) { return bayer_phase(encoding, 0, 0) >= 0; }
+
 // raw camera images to rectified grey (rectify.hip).  map: device int32 [H][W][2], where each pixel of the W x H window lies in the
 // width x height message (1/32 pixel; build_rectify_map fills a host copy for the window at (x0, y0)) -> dst [frames][H][W].
 // Frames lie frame_bytes apart; `extent` bytes from a frame's first one may be loaded (step * height, or less for a pane of a

@@ -253,6 +253,8 @@ int check_layout(ModContext *c, const ModImageLayout &l, bool panes) {
   const int C = image_channels(l.encoding);
   if (!C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown image encoding");
   if (l.width < 1 || l.height < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "image size must be positive");
+  if (is_bayer(l.encoding) && (l.width < 3 || l.height < 3))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "a Bayer image must be at least 3 x 3 (a pixel of its frame copies an interior one)");
   if ((int64_t)l.step < (int64_t)l.width * C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "step is smaller than width * channels");
   if (panes && (int64_t)l.step < 2 * (int64_t)l.width * C)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side: step is smaller than 2 * width * channels (width is one eye's)");
@@ -290,12 +292,25 @@ int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l) {
 }
 
 int ensure_raw_stage(ModContext *c, ModContext::RawStage &r, const ModImageLayout &l) {
-  const size_t need = 2 * (size_t)l.step * l.height;
+  return ensure_stage_bytes(c, r, 2 * (size_t)l.step * l.height);
+}
+
+int ensure_stage_bytes(ModContext *c, ModContext::RawStage &r, size_t need) {
   if (r.bytes >= need) return MOD_OK;
   for (hipStream_t q : {c->stream, (hipStream_t)c->pipe.h2d}) if (q) HIP_TRY(c, hipStreamSynchronize(q));
   r.buf.reset(); r.bytes = 0;
   HIP_TRY(c, dalloc(r.buf, need));
   r.bytes = need;
+  return MOD_OK;
+}
+
+int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint8_t *src, int pane, uint8_t *grey, const int32_t *map,
+                  uint8_t *mono) {
+  const size_t G = (size_t)l.width * l.height;
+  launch_bayer_to_mono(l.width, l.height, frames, src, (size_t)l.step * l.height, l.step, l.width, l.height, 0, 0,
+                       bayer_phase(l.encoding, pane == MOD_EYE_RIGHT ? l.width : 0, 0), grey, c->stream);
+  launch_rectify(MOD_ENCODING_MONO8, c->dc.W, c->dc.H, frames, grey, G, G, l.width, l.width, l.height, map, mono, c->stream);
+  HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
 
@@ -545,7 +560,11 @@ int mod_image_to_mono_dev(ModContext *c, int32_t frames, const uint8_t *src, con
   int rc = layout ? check_layout(c, *layout, c->side_by_side) : current_layout(c, &l);
   if (rc) return rc;
   if (layout) l = *layout;
-  launch_to_mono(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.x0, l.y0, mono, c->stream);
+  if (is_bayer(l.encoding))        // the region is the message (side by side: the pane src points at, with the pattern as it lies there)
+    launch_bayer_to_mono(c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.width, l.height, l.x0, l.y0,
+                         bayer_phase(l.encoding, 0, 0), mono, c->stream);
+  else
+    launch_to_mono(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.x0, l.y0, mono, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
@@ -590,6 +609,10 @@ int mod_rectify_dev(ModContext *c, int32_t frames, const uint8_t *src, const Mod
   if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
   const size_t M = (size_t)l.step * l.height, pane = c->side_by_side ? pane_offset(l, eye) : 0;   // side by side: eye selects the pane too
+  if (is_bayer(l.encoding)) {      // debayer, then rectify: the whole messages (or panes) to grey planes of the context's, k_rectify from those
+    if (int rc = ensure_stage_bytes(c, c->bayer_grey, (size_t)frames * l.width * l.height)) return rc;
+    return rectify_bayer(c, l, frames, src + pane, c->side_by_side ? eye : MOD_EYE_LEFT, c->bayer_grey.buf, c->rect.map[eye].q, mono);
+  }
   launch_rectify(l.encoding, c->dc.W, c->dc.H, frames, src + pane, M, M - pane, l.step, l.width, l.height, c->rect.map[eye].q, mono, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;

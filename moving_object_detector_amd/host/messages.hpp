@@ -65,7 +65,7 @@ inline CameraInfo crop_camera_info(const CameraInfo &info, int w, int h) {
 
 // sensor_msgs/Image: row-major 8-bit pixels, `step` bytes per row (0: width * channels).  mono8 is what the disparity estimator
 // consumes; bgr8 / rgb8 / bgra8 / rgba8 (image_rect_color) and packed yuv422 / yuv422_yuy2 (a UVC camera's own format) are
-// converted on the GPU (mod_set_image_layout)
+// converted on the GPU (mod_set_image_layout), and so are the 8-bit Bayer mosaics bayer_rggb8 / _bggr8 / _gbrg8 / _grbg8
 struct Image {
   Header header; int width = 0, height = 0; const uint8_t *data = nullptr;
   std::string encoding = "mono8";
@@ -83,10 +83,19 @@ inline int image_encoding(const std::string &e) {
   if (e == "yuv422_yuy2") return MOD_ENCODING_YUV422_YUY2;   // YUYV
   return -1;
 }
-// bytes per pixel of an encoding image_encoding() returned
+// MOD_ENCODING_BAYER_* of an 8-bit Bayer encoding ("bayer_rggb8", ...: demosaiced straight to grey on the GPU), -1 for any other
+inline int bayer_encoding(const std::string &e) {
+  if (e == "bayer_rggb8") return MOD_ENCODING_BAYER_RGGB8;
+  if (e == "bayer_bggr8") return MOD_ENCODING_BAYER_BGGR8;
+  if (e == "bayer_gbrg8") return MOD_ENCODING_BAYER_GBRG8;
+  if (e == "bayer_grbg8") return MOD_ENCODING_BAYER_GRBG8;
+  return -1;
+}
+// bytes per pixel of an encoding image_encoding() or bayer_encoding() returned
 inline int image_channels(int encoding) {
   switch (encoding) {
     case MOD_ENCODING_MONO8: return 1;
+    case MOD_ENCODING_BAYER_RGGB8: case MOD_ENCODING_BAYER_BGGR8: case MOD_ENCODING_BAYER_GBRG8: case MOD_ENCODING_BAYER_GRBG8: return 1;
     case MOD_ENCODING_YUV422: case MOD_ENCODING_YUV422_YUY2: return 2;
     case MOD_ENCODING_BGR8: case MOD_ENCODING_RGB8: return 3;
     default: return 4;
@@ -96,7 +105,7 @@ inline int image_channels(int encoding) {
 // The layout of `image` with the camera-sized window at (x0, y0); false for an encoding the library cannot take.  side_by_side: the
 // message holds both eyes, each in one half of every row (mod_set_side_by_side): the layout's width is a pane's, its step the row's
 inline bool image_layout(const Image &image, int x0, int y0, ModImageLayout *layout, bool side_by_side = false) {
-  const int enc = image_encoding(image.encoding);
+  const int known = image_encoding(image.encoding), enc = known >= 0 ? known : bayer_encoding(image.encoding);
   if (enc < 0 || (side_by_side && image.width % 2)) return false;
   layout->encoding = enc; layout->width = side_by_side ? image.width / 2 : image.width; layout->height = image.height;
   layout->step = image.step > 0 ? image.step : image.width * image_channels(enc);

@@ -211,7 +211,7 @@ class SceneFlowConstructorNode {
   }
 
   // stereoCallback with every estimator on the GPU: the images go in as they arrive (bgr8 / rgb8 / bgra8 / rgba8 / mono8 / yuv422 /
-  // yuv422_yuy2, padded rows, the centred crop window), disparity, flow, camera motion, scene flow and clusters run there, the frame
+  // yuv422_yuy2 / the 8-bit Bayer mosaics, padded rows, the centred crop window), disparity, flow, camera motion, scene flow and clusters run there, the frame
   // before is collected, its objects published and the pose broadcast
   void gpuCallback(const sensor_msgs::ImageConstPtr &left_image, const sensor_msgs::ImageConstPtr &right_image,
                    const sensor_msgs::CameraInfoConstPtr &left_camera_info, const sensor_msgs::CameraInfoConstPtr &right_camera_info) {
@@ -234,9 +234,9 @@ class SceneFlowConstructorNode {
     int x0 = 0, y0 = 0;
     if (crop) mod_host::centred_origin((int)left_image->width, (int)left_image->height, crop_width_, crop_height_, &x0, &y0);
     mod_host::Image l = image_of(*left_image), r = image_of(*right_image);
-    const bool usable = mod_host::image_encoding(left_image->encoding) >= 0;
+    const bool usable = mod_host::image_encoding(left_image->encoding) >= 0 || mod_host::bayer_encoding(left_image->encoding) >= 0;
     if (!usable)                      // dropped like a failed estimateDisparity (:272-276): the next frame has no previous one
-      ROS_ERROR("image encoding '%s' is not one of mono8, bgr8, rgb8, bgra8, rgba8, yuv422, yuv422_yuy2: frame dropped",
+      ROS_ERROR("image encoding '%s' is not one of mono8, bgr8, rgb8, bgra8, rgba8, yuv422, yuv422_yuy2, bayer_{rggb,bggr,gbrg,grbg}8: frame dropped",
                 left_image->encoding.c_str());
     pending_objects_.reset(publish_moving_objects_ && moving_objects_pub_.getNumSubscribers() > 0 ? new mod_host::MovingObjectArray() : nullptr);
     const bool want_flow = optflow_pub_.getNumSubscribers() > 0, want_depth = depth_pub_.getNumSubscribers() > 0;

@@ -729,11 +729,53 @@ def to_colour(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=N
     return msg, layout, expect
 
 
+BAYER_PATTERNS = ("rggb", "bggr", "gbrg", "grbg")
+
+
+def mosaic(bgr: np.ndarray, pattern: str) -> np.ndarray:
+    """A (..., H, W, 3) uint8 B, G, R image sampled into the 8-bit Bayer mosaic (..., H, W) of `pattern` ("rggb", "bggr", "gbrg",
+    "grbg", or the ROS name "bayer_rggb8", ...): pixel (x, y) keeps the channel pattern[2 * (y & 1) + (x & 1)]."""
+    name = pattern[6:-1] if pattern.startswith("bayer_") and pattern.endswith("8") else pattern
+    if name not in BAYER_PATTERNS:
+        raise ValueError(f"unknown Bayer pattern {pattern!r}")
+    bgr = np.asarray(bgr)
+    if bgr.dtype != np.uint8 or bgr.ndim < 3 or bgr.shape[-1] != 3:
+        raise ValueError("bgr must be (..., H, W, 3) uint8")
+    out = np.empty(bgr.shape[:-1], np.uint8)
+    for k, colour in enumerate(name):
+        out[..., k >> 1::2, k & 1::2] = bgr[..., k >> 1::2, k & 1::2, "bgr".index(colour)]
+    return out
+
+
+def to_bayer(mono: np.ndarray, encoding: str, seed=None, pad: int = 0, canvas=None):
+    """to_colour for the Bayer encodings ("bayer_rggb8", ...): the grey image as a mosaic inside a larger message.  seed None: a
+    flat B = G = R = grey mosaic (its demosaic differs from `mono` where the image has texture: bilinear interpolation smooths);
+    seed int: the three channels differ by a few levels.  The message outside the centred window is a mosaic of the image continued
+    by reflection, so the window's edges see texture, not noise.  Returns (payload uint8 [msg_h][step], layout dict); the grey the
+    conversion gives is the model's to state (tests/models/bayer_model.py), not this function's."""
+    H, W = mono.shape
+    mw, mh = canvas if canvas is not None else (W, H)
+    if mw < W or mh < H or mw < 3 or mh < 3 or pad < 0:
+        raise ValueError("the canvas must hold the image and be at least 3 x 3")
+    x0, y0 = (mw - W) // 2, (mh - H) // 2
+    rng = np.random.Generator(np.random.PCG64([0xBA7E2, 0 if seed is None else int(seed) + 1]))
+    big = np.pad(mono, ((y0, mh - H - y0), (x0, mw - W - x0)), mode="symmetric").astype(np.int64)
+    bgr = np.stack([big, big, big], -1)
+    if seed is not None:
+        bgr = np.clip(bgr + rng.integers(-6, 7, size=bgr.shape), 0, 255)
+    msg = rng.integers(0, 256, size=(mh, mw + pad), dtype=np.uint8)
+    msg[:, :mw] = mosaic(bgr.astype(np.uint8), encoding)
+    return msg, {"encoding": encoding, "width": mw, "height": mh, "step": mw + pad, "x0": x0, "y0": y0}
+
+
 def side_by_side(left: np.ndarray, right: np.ndarray, layout: dict, pad: int = 0, seed: int = 0):
     """Two messages of one layout (to_colour's payloads [msg_h][step]) as ONE side-by-side message (mod_set_side_by_side): the left
     message's pixel bytes in the left half of every row, the right one's in the right half, `pad` random bytes behind them.  Returns
-    (payload uint8 [msg_h][2 * width * channels + pad], layout dict: width, height, x0, y0 of ONE eye, step of the whole row)."""
-    C = _ENCODINGS[layout["encoding"]][0]
+    (payload uint8 [msg_h][2 * width * channels + pad], layout dict: width, height, x0, y0 of ONE eye, step of the whole row).
+    Bayer layouts: the pattern of a side-by-side message runs on across the seam, so for an ODD width the right message must have been
+    mosaiced with the pattern shifted by one column (rggb <-> grbg, bggr <-> gbrg); the bytes are copied as they are, and the returned
+    layout names the LEFT pane's pattern."""
+    C = 1 if layout["encoding"].startswith("bayer_") else _ENCODINGS[layout["encoding"]][0]
     row = layout["width"] * C
     if left.shape != right.shape or left.shape[1] < row or pad < 0:
         raise ValueError("left and right must be messages of `layout`")

@@ -11,7 +11,10 @@ their grey planes are compared with the product's bit for bit:
   make -C moving_object_detector_amd/csrc EXTRA=-DMOD_RECTIFY_DIRECT OUT=../libmod_sf_rectify_direct.so lib
   make -C moving_object_detector_amd/csrc EXTRA=-DMOD_RECTIFY_STAGED OUT=../libmod_sf_rectify_staged.so lib
 A build that is missing is recorded as missing.  Prints one JSON line per measurement and appends them to profiles/rectify_time.jsonl.
-Run on the GPU: python tools/time_rectify.py [reps] [kernel]   (kernel: the kernel legs only, for a rocprofv3 --kernel-trace run)"""
+Bayer messages are demosaiced whole and then rectified as mono8 (k_bayer_to_mono + k_rectify): the bayer_rggb8 row beside the mono8
+row is the cost of the two passes.
+Run on the GPU: python tools/time_rectify.py [reps] [kernel] [bayer]   (kernel: the kernel legs only, for a rocprofv3 --kernel-trace
+run; bayer: only the mono8 and bayer_rggb8 rows)"""
 import ctypes as C
 import json
 import os
@@ -60,7 +63,7 @@ def timed(torch, call, reps):
     return a.elapsed_time(b) / reps
 
 
-def kernel(reps):
+def kernel(reps, encodings=("mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422", "yuv422_yuy2", "bayer_rggb8")):
     import torch
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.pipeline import Context
@@ -85,9 +88,9 @@ def kernel(reps):
         else:
             emit({"what": what, "missing": os.path.relpath(build, ROOT), "note": "not built: this run has no such leg"})
     out = torch.empty((F, H, W), dtype=torch.uint8, device=ctx.device)
-    for enc in ("mono8", "bgr8", "rgb8", "bgra8", "rgba8", "yuv422", "yuv422_yuy2"):
+    for enc in encodings:
         lay = capi.image_layout(enc, W, H)
-        Cn = capi.CHANNELS[lay.encoding]
+        Cn = capi.CHANNELS.get(lay.encoding, capi.BAYER_CHANNELS.get(lay.encoding))
         src = torch.randint(0, 256, (F * lay.step * lay.height,), dtype=torch.uint8, device=ctx.device)
         ms, same, first = {}, {}, None
         for rnd in range(2):                       # the kernels alternate, twice: the spread is part of the record
@@ -104,7 +107,8 @@ def kernel(reps):
             per_px = Cn + 8 + 1 if rect else Cn + 1
             best = min(ms[what])
             tbps = F * W * H * per_px / (best * 1e-3) / 1e12
-            emit({"what": what, "encoding": enc, "W": W, "H": H, "frames": F, "reps": reps, "bytes_per_px": per_px,
+            bayer_leg = what == "k_to_mono" and lay.encoding in capi.BAYER_CHANNELS      # the conversion of a Bayer frame is k_bayer_to_mono
+            emit({"what": "k_bayer_to_mono" if bayer_leg else what, "encoding": enc, "W": W, "H": H, "frames": F, "reps": reps, "bytes_per_px": per_px,
                   "ms_per_call": [round(v, 4) for v in ms[what]], "TB_per_s": round(tbps, 3), "of_hbm": round(tbps / HBM_TBPS, 3),
                   "vs_k_to_mono": round(best / min(ms["k_to_mono"]), 2), **({"same_planes_as_product": same[what]} if rect else {})})
         del src
@@ -173,6 +177,9 @@ def stream_fps(W, H, reps, rectify, encoding="bgra8", side_by_side=False):
 
 def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
+    if "bayer" in sys.argv[2:]:
+        kernel(reps, ("mono8", "bayer_rggb8"))
+        return
     kernel(reps)
     if "kernel" in sys.argv[2:]:
         return
