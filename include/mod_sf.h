@@ -502,6 +502,66 @@ int  mod_get_rectification(const ModContext *ctx, ModRectifyCamera *left, ModRec
 int  mod_rectify_dev(ModContext *ctx, int32_t frames, const uint8_t *src, const ModImageLayout *layout, int32_t eye, uint8_t *mono);
 int  mod_rectify_map_host(ModContext *ctx, int32_t eye, const ModImageLayout *layout, int32_t *map_qxqy);
 
+/* ---- RGB-D cameras: depth images to disparity on the GPU --------------------------------------------------------------------- */
+/* A RealSense, an Azure Kinect or a structured-light head delivers one image and one depth image (REP 118: 16UC1 millimetres with
+ * 0 = no reading, 32FC1 metres with NaN = no reading), no stereo pair.  Everything behind the disparity ring works from disparity
+ * alone, so for such a camera the estimator stage is a conversion, d = fT / z with fT the F32 product disp_f * disp_T of the camera
+ * (any positive virtual baseline works; INTEGRATION.md says how to choose it).  Context state like the image layout: the depth layout
+ * and the registration are read when a call or a submit is made, and a frame in flight keeps what its submit read.
+ * A ModDepthLayout describes the depth message as a ModImageLayout describes an image: window pixel (u, v) reads message pixel
+ * (u + x0, v + y0); frames of a batch are stacked at step * height bytes; samples are little-endian.
+ * The plain path (no registration: the depth image is aligned to the image camera), all F32, -ffp-contract=off:
+ *   16UC1: r = the uint16; z = (float)r * unit (one F32 multiply)          32FC1: z = value * unit
+ *   unit == 0 selects the encoding's REP 118 default: 0.001f for 16UC1, 1.0f for 32FC1
+ *   valid iff z > 0.0f and z is finite (0, -0.0, negatives, NaN and +-inf are not)
+ *   valid: d = fT / z (the correctly rounded F32 division); invalid: d = min_disparity - 1.0f (the estimator's -1 at min_disparity 0,
+ *   the convention of mod_disparity_speckle_dev).  Nothing is clipped to max_disparity: getDisparity rejects out-of-range values
+ *   downstream (disparity_image_processor.cpp:25-28), and a d that underflows to 0 is rejected at :38.
+ * The registered path (mod_set_depth_registration, opt-in: the depth camera has intrinsics and a pose of its own, what
+ * depth_image_proc/register does on the CPU): the WHOLE depth message is scattered into a z-buffer of the context's W x H, and the
+ * layout's x0, y0 must be 0.  For every message pixel (U, V) whose z is valid by the rule above, in F64, the operations in exactly
+ * this order, no contraction (fx_d .. t: the registration; fx, fy, cx, cy, Tx, Ty: the context camera's, the cropped P given to
+ * mod_set_camera, so results land in window coordinates; tests/models/depth_model.py restates both paths bit for bit):
+ *   Z0 = (double)z;  X0 = ((U - cx_d) * Z0) / fx_d;  Y0 = ((V - cy_d) * Z0) / fy_d
+ *   X = ((R[0]*X0 + R[1]*Y0) + R[2]*Z0) + t[0]      (R row-major, P_img = R P_depth + t)
+ *   Y = ((R[3]*X0 + R[4]*Y0) + R[5]*Z0) + t[1];  Z = ((R[6]*X0 + R[7]*Y0) + R[8]*Z0) + t[2]
+ *   drop unless Z > 0 and finite
+ *   a = ((fx*X + Tx) / Z + cx) + 0.5;  b = ((fy*Y + Ty) / Z + cy) + 0.5
+ *   drop unless 0 <= a < W and 0 <= b < H   (compared as doubles, before any conversion)
+ *   ui = (int)floor(a); vi = (int)floor(b); zf = (float)Z (round to nearest even);  zbuf[vi][ui] = min(zbuf[vi][ui], zf)
+ * The minimum is a 32-bit atomic minimum on the bit pattern of zf: positive floats order like their unsigned patterns and the
+ * all-ones word stands for "empty", so the result does not depend on the order of the atomics.  Then d = fT / zbuf where a sample
+ * landed and min_disparity - 1.0f where none did.  Holes are left as holes (no splatting, no fill: depth_image_proc/register's
+ * default; parity with a particular depth_image_proc build is not claimed).  The z-buffer is scratch of the context's, allocated on
+ * first use.
+ *   mod_set_depth_layout        NULL = 16UC1, packed, W x H, origin 0, unit 0 (the default)
+ *   mod_set_depth_registration  NULL = off (the default).  Set the registration BEFORE a layout whose message is not the camera's
+ *                               size: without one the W x H window must fit the message, with one x0 and y0 must be 0 and the
+ *                               message may have any size.  Both rules are checked again when a call or a submit is made.
+ *   mod_get_depth_registration  *enabled and, when set, the registration (may be NULL)
+ *   mod_depth_to_disparity_dev  `frames` device depth messages -> disparity [frames][H][W] on the context's stream; layout NULL = the
+ *                               context's; depth NULL: MOD_SKIP_NO_DISPARITY_NOW; `depth` must be aligned to its element size and
+ *                               `disparity` to 4 bytes; frames <= ModConfig.max_frames
+ * MOD_ERR_INVALID_ARGUMENT (the state stays as it was): an unknown encoding; width or height < 1 or > MOD_MAX_WIDTH; step < width *
+ * 2 (or 4), not a multiple of 2 (or 4), or step * height >= 2^31; unit not finite or < 0; a window that does not fit the message;
+ * non-finite registration entries, fx_d or fy_d <= 0, an entry of R R^T - I above 1e-6 in magnitude (the rectifier's rule); a
+ * registration together with x0 or y0 != 0.  MOD_ERR_NOT_CONFIGURED: no camera set. */
+#define MOD_DEPTH_16UC1 0
+#define MOD_DEPTH_32FC1 1
+typedef struct ModDepthLayout {   /* 28 bytes */
+  int32_t encoding, width, height, step, x0, y0;
+  float   unit;
+} ModDepthLayout;
+typedef struct ModDepthRegistration {   /* 128 bytes */
+  double fx, fy, cx, cy;   /* the depth camera, of the full depth message; fx, fy > 0 */
+  double R[9], t[3];       /* depth optical frame -> image optical frame */
+} ModDepthRegistration;
+int  mod_set_depth_layout(ModContext *ctx, const ModDepthLayout *layout);
+int  mod_get_depth_layout(const ModContext *ctx, ModDepthLayout *layout);
+int  mod_set_depth_registration(ModContext *ctx, const ModDepthRegistration *registration);
+int  mod_get_depth_registration(const ModContext *ctx, ModDepthRegistration *registration, int32_t *enabled);
+int  mod_depth_to_disparity_dev(ModContext *ctx, int32_t frames, const void *depth, const ModDepthLayout *layout, float *disparity);
+
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()
  * would publish nothing.  cloud_aos: W*H*32 bytes; labels: W*H int32; objects: capacity `max_objects`.
@@ -595,6 +655,22 @@ int  mod_submit_odometry_host(ModContext *ctx, const uint8_t *left, const uint8_
                               const ModFlowParams *flow_prm, const ModEgoParams *ego_prm, double dt, void *cloud_aos, int32_t *labels,
                               ModObject *objects, int32_t max_objects, float *disparity, float *flow_out, ModTransform *transform_out,
                               ModEgoResult *ego_out, int32_t *ticket);
+/* One image and one depth image in, moving objects out: mod_submit_images_host (transform non-NULL) or mod_submit_odometry_host
+ * (transform NULL; ego_prm is then required) with the disparity estimator replaced by the depth conversion above.  On the copy
+ * stream, without a registration only the depth window crosses PCIe (W * H * 2 or 4 bytes); with one the whole message crosses.  On
+ * the context's stream the conversion writes straight into the ring plane, `now` of this frame and `previous` of the next.
+ *   image   a message of the context's image layout, in every encoding the library takes
+ *   depth   a message of the context's depth layout
+ * The left-image ring, the skip codes, a first frame, mod_forget_previous, "a submit of another kind", a NULL image or NULL depth
+ * (MOD_SKIP_NO_DISPARITY_NOW, and the next frame has no previous), disparity / flow_out / transform_out / ego_out and collection:
+ * as the two submits above.  MOD_ERR_INVALID_ARGUMENT (the state stays as it was): side by side is on; a rectification is set but
+ * no registration (a depth image aligned to a raw image cannot be aligned to the rectified one; with a registration the image is
+ * rectified with the left map and the registration's target is the rectified camera); transform and ego_prm both NULL; a NULL
+ * flow_prm; what mod_depth_to_disparity_dev refuses of the depth layout in force. */
+int  mod_submit_depth_host(ModContext *ctx, const uint8_t *image, const void *depth, const ModFlowParams *flow_prm,
+                           const ModEgoParams *ego_prm, const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels,
+                           ModObject *objects, int32_t max_objects, float *disparity, float *flow_out, ModTransform *transform_out,
+                           ModEgoResult *ego_out, int32_t *ticket);
 /* disparity_now_.reset() of a failed estimateDisparity (scene_flow_constructor.cpp:272-276): the next submit without an
  * explicit disparity_prev reports MOD_SKIP_NO_DISPARITY_PREV instead of pairing with a stale frame. */
 int  mod_forget_previous(ModContext *ctx);

@@ -36,6 +36,9 @@ MOD_SGM_FRACTION_BITS = 4
 MOD_FLOW_SEEDS = 5
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
 MOD_MAX_WIDTH = 16384
+MOD_DEPTH_16UC1, MOD_DEPTH_32FC1 = 0, 1                  # REP 118 depth images: uint16 millimetres / float32 metres
+DEPTH_ENCODINGS = {"16UC1": MOD_DEPTH_16UC1, "32FC1": MOD_DEPTH_32FC1}
+DEPTH_BYTES = {MOD_DEPTH_16UC1: 2, MOD_DEPTH_32FC1: 4}   # bytes per sample
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
 MOD_ENCODING_YUV422, MOD_ENCODING_YUV422_YUY2 = 5, 6   # packed 4:2:2: UYVY, YUYV (grey = Y)
 ENCODINGS = {"mono8": MOD_ENCODING_MONO8, "bgr8": MOD_ENCODING_BGR8, "rgb8": MOD_ENCODING_RGB8, "bgra8": MOD_ENCODING_BGRA8,
@@ -68,6 +71,8 @@ EXPORTS = [
     "mod_set_flow_propagation", "mod_get_flow_propagation",
     "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
     "mod_set_side_by_side", "mod_get_side_by_side",
+    "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
+    "mod_depth_to_disparity_dev", "mod_submit_depth_host",
 ]
 
 
@@ -193,6 +198,36 @@ def rectify_camera(width: int, height: int, K, D, R, P) -> ModRectifyCamera:
                             (C.c_double * 9)(*flat(R, 9, "R")), (C.c_double * 12)(*flat(P, 12, "P")))
 
 
+class ModDepthLayout(C.Structure):
+    _fields_ = [("encoding", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("step", C.c_int32), ("x0", C.c_int32),
+                ("y0", C.c_int32), ("unit", C.c_float)]
+
+
+def depth_layout(encoding, width: int, height: int, step=None, x0: int = 0, y0: int = 0, unit: float = 0.0) -> ModDepthLayout:
+    """ModDepthLayout of a depth sensor_msgs/Image: `encoding` a MOD_DEPTH_* value or its ROS name ("16UC1", "32FC1"); step None =
+    packed rows; (x0, y0) = top-left of the camera-sized window taken from it (0, 0 with a registration); unit = metres per count,
+    0 = the REP 118 default (0.001 for 16UC1, 1 for 32FC1)."""
+    enc = DEPTH_ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+    if step is None:
+        step = int(width) * DEPTH_BYTES.get(enc, 2)
+    return ModDepthLayout(enc, int(width), int(height), int(step), int(x0), int(y0), float(unit))
+
+
+class ModDepthRegistration(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("R", C.c_double * 9),
+                ("t", C.c_double * 3)]
+
+
+def depth_registration(fx: float, fy: float, cx: float, cy: float, R=(1, 0, 0, 0, 1, 0, 0, 0, 1), t=(0, 0, 0)) -> ModDepthRegistration:
+    """ModDepthRegistration: the depth camera's intrinsics (of the full depth message) and the transform depth optical frame -> image
+    optical frame, P_img = R P_depth + t (R row-major, flat or nested)."""
+    r = [float(x) for row in R for x in (row if hasattr(row, "__len__") else [row])]
+    tt = [float(x) for x in t]
+    if len(r) != 9 or len(tt) != 3:
+        raise ValueError("R must have 9 entries and t 3")
+    return ModDepthRegistration(float(fx), float(fy), float(cx), float(cy), (C.c_double * 9)(*r), (C.c_double * 3)(*tt))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -200,6 +235,7 @@ class ModClusterOut(C.Structure):
 MOD_OBJECT_BYTES = C.sizeof(ModObject)
 assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
+assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 
 
 class ModError(RuntimeError):
@@ -267,6 +303,13 @@ def load(require_torch_first: bool = True):
     L.mod_rectify_map_host.argtypes = [vp, i32, C.POINTER(ModImageLayout), vp]
     L.mod_set_side_by_side.argtypes = [vp, i32]
     L.mod_get_side_by_side.argtypes = [vp, C.POINTER(i32)]
+    L.mod_set_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]
+    L.mod_get_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]
+    L.mod_set_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration)]
+    L.mod_get_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration), C.POINTER(i32)]
+    L.mod_depth_to_disparity_dev.argtypes = [vp, i32, vp, C.POINTER(ModDepthLayout), vp]
+    L.mod_submit_depth_host.argtypes = [vp, vp, vp, C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.c_double,
+                                        vp, vp, vp, i32, vp, vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]

@@ -1,0 +1,180 @@
+// depth.hip — depth images to the disparity planes everything downstream reads.
+//
+// An RGB-D camera delivers one image and one depth image (REP 118: 16UC1 millimetres with 0 = no reading, 32FC1 metres with NaN = no
+// reading).  The scene-flow, ego-motion and cluster kernels work from disparity alone, so the estimator stage of such a camera is a
+// conversion: d = fT / z, with fT the F32 product disp_f * disp_T the scene-flow kernel divides by (DevCam.fT).
+//
+// k_depth_to_disparity (the plain path: the depth image is aligned to the image camera) reads the camera-sized window (W x H) at
+// (x0, y0) of each depth message of a batch (row pitch `step`, frames stacked at step * message height bytes) and writes packed planes
+// [frames][H][W] f32.  Memory-bound: 2 or 4 bytes in, 4 out per pixel.  Each lane makes one run of 8 consecutive pixels of one row,
+// placed on the OUTPUT's 32-byte grid (two aligned 16-byte stores); the source of a run is loaded as 16-byte words where its address
+// allows, as dwords where it is 4-byte aligned, and — a 16UC1 run that starts half-way into a dword (odd x0 + head) — as the dwords
+// around it shifted into place with v_alignbyte.  Runs cut by a row end, and the half-way runs next to one, take the scalar path.
+//
+// k_depth_register + k_zbuffer_to_disparity (the registered path: the depth camera has its own intrinsics and pose) scatter every
+// valid sample of the WHOLE message into a z-buffer of the camera's size, f64 in the operation order include/mod_sf.h states, and
+// keep the nearest sample of every target with a 32-bit atomicMin on the bit pattern of (float)Z: positive floats order like their
+// unsigned patterns and the all-ones word (no float a sample can produce) stands for "empty", so the minimum does not depend on the
+// order the atomics arrive in.  Holes stay holes.  No LDS; frames in blockIdx.z.
+#include "mod_launch.h"
+
+namespace {
+
+constexpr int kRun = 8;       // output pixels per lane
+constexpr int kBlock = 256;
+constexpr uint32_t kEmpty = 0xffffffffu;
+
+template <int Enc> constexpr int kBytes = Enc == MOD_DEPTH_16UC1 ? 2 : 4;
+
+// valid iff z > 0 and finite (0, -0.0, negatives, NaN, +-inf are not): d = fT / z, else `invalid` (min_disparity - 1)
+__device__ __forceinline__ float to_disparity(float z, float fT, float invalid) {
+  const bool ok = z > 0.0f && z < __builtin_inff();
+  return ok ? fT / z : invalid;
+}
+
+template <int Enc>
+__device__ __forceinline__ float sample_z(const uint8_t *p, float unit) {
+  if constexpr (Enc == MOD_DEPTH_16UC1) return (float)*reinterpret_cast<const uint16_t *>(p) * unit;
+  else return *reinterpret_cast<const float *>(p) * unit;
+}
+
+// sample k of a run held in dwords d[] (little-endian)
+template <int Enc, int N>
+__device__ __forceinline__ float run_z(const uint32_t (&d)[N], int k, float unit) {
+  if constexpr (Enc == MOD_DEPTH_16UC1) return (float)((d[k >> 1] >> ((k & 1) * 16)) & 0xffffu) * unit;
+  else return __uint_as_float(d[k]) * unit;
+}
+
+//   runs         runs per row: (W + 7) / 8 + 1 (run r covers x in [head + 8 (r - 1), head + 8 r), head = pixels of the row in front of
+//                the output's first 32-byte boundary)
+//   frame_bytes  step * message height
+template <int Enc>
+__global__ __launch_bounds__(kBlock) void k_depth_to_disparity(int W, int H, int runs, const uint8_t *__restrict__ src, size_t frame_bytes,
+                                                               int step, int x0, int y0, float unit, float fT, float invalid,
+                                                               float *__restrict__ dst) {
+  constexpr int B = kBytes<Enc>, NW = kRun * B / 4;   // dwords of a run
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= runs * H) return;
+  const int y = i / runs, r = i - y * runs;
+  const int f = blockIdx.z;
+  const uint8_t *row = src + (size_t)f * frame_bytes + (size_t)(y0 + y) * step + (size_t)x0 * B;   // the window's row
+  float *out = dst + ((size_t)f * H + y) * W;
+  const int head = (int)(((0u - (uint32_t)(uintptr_t)out) & 31u) >> 2);
+  const int xs = head + (r - 1) * kRun;
+  if (xs >= 0 && xs + kRun <= W) {
+    const uint8_t *s = row + (ptrdiff_t)xs * B;
+    const uint32_t a = (uint32_t)(uintptr_t)s;
+    uint32_t d[NW];
+    bool loaded = true;
+    if ((a & 15u) == 0) {
+      const uint4 *p = reinterpret_cast<const uint4 *>(s);
+#pragma unroll
+      for (int k = 0; k < NW / 4; k++) {
+        const uint4 q = p[k];
+        d[4 * k] = q.x; d[4 * k + 1] = q.y; d[4 * k + 2] = q.z; d[4 * k + 3] = q.w;
+      }
+    } else if ((a & 3u) == 0) {
+      const uint32_t *p = reinterpret_cast<const uint32_t *>(s);
+#pragma unroll
+      for (int k = 0; k < NW; k++) d[k] = p[k];
+    } else if (B == 2 && xs >= 1 && xs + kRun + 1 <= W) {   // half-way into a dword: the sample on either side is the window's too
+      const uint32_t *p = reinterpret_cast<const uint32_t *>(s - 2);
+      uint32_t w[NW + 1];
+#pragma unroll
+      for (int k = 0; k < NW + 1; k++) w[k] = p[k];
+#pragma unroll
+      for (int k = 0; k < NW; k++) d[k] = __builtin_amdgcn_alignbyte(w[k + 1], w[k], 2);
+    } else {
+      loaded = false;
+    }
+    if (loaded) {
+      float o[kRun];
+#pragma unroll
+      for (int k = 0; k < kRun; k++) o[k] = to_disparity(run_z<Enc>(d, k, unit), fT, invalid);
+      float4 *q = reinterpret_cast<float4 *>(__builtin_assume_aligned(out + xs, 16));
+      q[0] = make_float4(o[0], o[1], o[2], o[3]);
+      q[1] = make_float4(o[4], o[5], o[6], o[7]);
+      return;
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < kRun; k++) {
+    const int x = xs + k;
+    if (x >= 0 && x < W) out[x] = to_disparity(sample_z<Enc>(row + (size_t)x * B, unit), fT, invalid);
+  }
+}
+
+// One lane per sample (U, V) of the whole width x height message; zbuf [frames][H][W] holds kEmpty on entry.
+template <int Enc>
+__global__ __launch_bounds__(kBlock) void k_depth_register(int width, const uint8_t *__restrict__ src, size_t frame_bytes, int step, float unit,
+                                                           DepthRegArgs g, int W, int H, uint32_t *__restrict__ zbuf) {
+  const int U = blockIdx.x * kBlock + threadIdx.x, V = blockIdx.y, f = blockIdx.z;
+  if (U >= width) return;
+  const float z = sample_z<Enc>(src + (size_t)f * frame_bytes + (size_t)V * step + (size_t)U * kBytes<Enc>, unit);
+  if (!(z > 0.0f && z < __builtin_inff())) return;
+  const double Z0 = (double)z;
+  const double X0 = (((double)U - g.cxd) * Z0) / g.fxd, Y0 = (((double)V - g.cyd) * Z0) / g.fyd;
+  const double X = ((g.R[0] * X0 + g.R[1] * Y0) + g.R[2] * Z0) + g.t[0];
+  const double Y = ((g.R[3] * X0 + g.R[4] * Y0) + g.R[5] * Z0) + g.t[1];
+  const double Z = ((g.R[6] * X0 + g.R[7] * Y0) + g.R[8] * Z0) + g.t[2];
+  if (!(Z > 0.0 && Z < __builtin_inf())) return;
+  const double a = ((g.fx * X + g.Tx) / Z + g.cx) + 0.5, b = ((g.fy * Y + g.Ty) / Z + g.cy) + 0.5;
+  if (!(a >= 0.0 && a < (double)W && b >= 0.0 && b < (double)H)) return;   // as doubles, before any conversion (NaN fails)
+  const int ui = (int)floor(a), vi = (int)floor(b);                        // 0 <= ui < W, 0 <= vi < H by the test above
+  atomicMin(zbuf + ((size_t)f * H + vi) * W + ui, __float_as_uint((float)Z));
+}
+
+// n words of z-buffer -> n disparities, four per lane (16-byte accesses when dst allows; zbuf is the context's own allocation)
+__global__ __launch_bounds__(kBlock) void k_zbuffer_to_disparity(size_t n, const uint32_t *__restrict__ zbuf, float fT, float invalid,
+                                                                 float *__restrict__ dst) {
+  const size_t i = 4 * ((size_t)blockIdx.x * kBlock + threadIdx.x);
+  if (i >= n) return;
+  if (i + 4 <= n && ((uintptr_t)dst & 15u) == 0) {
+    const uint4 q = *reinterpret_cast<const uint4 *>(zbuf + i);
+    *reinterpret_cast<float4 *>(dst + i) = make_float4(q.x == kEmpty ? invalid : fT / __uint_as_float(q.x), q.y == kEmpty ? invalid : fT / __uint_as_float(q.y),
+                                                       q.z == kEmpty ? invalid : fT / __uint_as_float(q.z), q.w == kEmpty ? invalid : fT / __uint_as_float(q.w));
+    return;
+  }
+  for (size_t k = i; k < n && k < i + 4; k++) {
+    const uint32_t q = zbuf[k];
+    dst[k] = q == kEmpty ? invalid : fT / __uint_as_float(q);
+  }
+}
+
+template <int Enc>
+void launch_plain(int W, int H, int frames, const void *src, size_t frame_bytes, int step, int x0, int y0, float unit, float fT, float invalid,
+                  float *dst, hipStream_t s) {
+  const int runs = (W + kRun - 1) / kRun + 1;
+  const dim3 grid((unsigned)(((size_t)runs * H + kBlock - 1) / kBlock), 1, (unsigned)frames);
+  hipLaunchKernelGGL(k_depth_to_disparity<Enc>, grid, dim3(kBlock), 0, s, W, H, runs, static_cast<const uint8_t *>(src), frame_bytes, step, x0, y0,
+                     unit, fT, invalid, dst);
+}
+
+template <int Enc>
+void launch_register(int W, int H, int frames, const void *src, int width, int height, int step, float unit, const DepthRegArgs &g, uint32_t *zbuf,
+                     hipStream_t s) {
+  const dim3 grid((unsigned)((width + kBlock - 1) / kBlock), (unsigned)height, (unsigned)frames);
+  hipLaunchKernelGGL(k_depth_register<Enc>, grid, dim3(kBlock), 0, s, width, static_cast<const uint8_t *>(src), (size_t)step * height, step, unit, g,
+                     W, H, zbuf);
+}
+
+}  // namespace
+
+int depth_bytes(int encoding) { return encoding == MOD_DEPTH_16UC1 ? 2 : encoding == MOD_DEPTH_32FC1 ? 4 : 0; }
+
+void launch_depth_to_disparity(int encoding, int W, int H, int frames, const void *src, size_t frame_bytes, int step, int x0, int y0, float unit,
+                               float fT, float invalid, float *dst, hipStream_t s) {
+  if (encoding == MOD_DEPTH_16UC1) launch_plain<MOD_DEPTH_16UC1>(W, H, frames, src, frame_bytes, step, x0, y0, unit, fT, invalid, dst, s);
+  else if (encoding == MOD_DEPTH_32FC1) launch_plain<MOD_DEPTH_32FC1>(W, H, frames, src, frame_bytes, step, x0, y0, unit, fT, invalid, dst, s);
+}
+
+hipError_t launch_depth_register(int encoding, int W, int H, int frames, const void *src, int width, int height, int step, float unit,
+                                 const DepthRegArgs &g, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s) {
+  const size_t n = (size_t)frames * W * H;
+  const hipError_t e = hipMemsetAsync(zbuf, 0xff, 4 * n, s);
+  if (e != hipSuccess) return e;
+  if (encoding == MOD_DEPTH_16UC1) launch_register<MOD_DEPTH_16UC1>(W, H, frames, src, width, height, step, unit, g, zbuf, s);
+  else if (encoding == MOD_DEPTH_32FC1) launch_register<MOD_DEPTH_32FC1>(W, H, frames, src, width, height, step, unit, g, zbuf, s);
+  hipLaunchKernelGGL(k_zbuffer_to_disparity, dim3((unsigned)((n + 4 * kBlock - 1) / (4 * kBlock))), dim3(kBlock), 0, s, n, zbuf, fT, invalid, dst);
+  return hipSuccess;
+}

@@ -92,27 +92,28 @@ static int check_one_message(ModContext *c, const uint8_t *left, const uint8_t *
 }
 
 // Two whole raw messages to `raw` on stream s, one after the other: a rectified window needs source pixels outside the window.
-// panes: img0 is ONE message that holds both eyes side by side; it crosses once.
+// panes: img0 is ONE message that holds both eyes side by side; it crosses once.  img1 null (an RGB-D frame): one message, one eye.
 static int copy_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *img0, const uint8_t *img1, uint8_t *raw,
                          hipStream_t s) {
   const size_t M = (size_t)l.step * l.height;
   HIP_TRY(c, hipMemcpyAsync(raw, img0, M, hipMemcpyHostToDevice, s));
-  if (!panes) HIP_TRY(c, hipMemcpyAsync(raw + M, img1, M, hipMemcpyHostToDevice, s));
+  if (!panes && img1) HIP_TRY(c, hipMemcpyAsync(raw + M, img1, M, hipMemcpyHostToDevice, s));
   return MOD_OK;
 }
 // ... and k_rectify from there on the context's stream, each message (or each pane of the one message) with the map of its eye.  A
 // pane is a message of the pane's width that starts width * channels bytes into the row and ends with the message's last byte.
-// Bayer messages are demosaiced whole into `bayer` first (room for two grey planes of the message's, or pane's, size).
+// Bayer messages are demosaiced whole into `bayer` first (room for two grey planes of the message's, or pane's, size).  grey1 null:
+// the first message alone.
 static int rectify_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *raw, int eye1, uint8_t *bayer, uint8_t *grey0,
                             uint8_t *grey1) {
   const size_t M = (size_t)l.step * l.height, at1 = panes ? pane_offset(l, MOD_EYE_RIGHT) : M;
   if (is_bayer(l.encoding)) {
     if (int rc = rectify_bayer(c, l, 1, raw, MOD_EYE_LEFT, bayer, c->rect.map[MOD_EYE_LEFT].q, grey0)) return rc;
-    return rectify_bayer(c, l, 1, raw + at1, panes ? MOD_EYE_RIGHT : MOD_EYE_LEFT, bayer + (size_t)l.width * l.height, c->rect.map[eye1].q, grey1);
+    return !grey1 ? MOD_OK : rectify_bayer(c, l, 1, raw + at1, panes ? MOD_EYE_RIGHT : MOD_EYE_LEFT, bayer + (size_t)l.width * l.height, c->rect.map[eye1].q, grey1);
   }
   launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw, M, M, l.step, l.width, l.height, c->rect.map[MOD_EYE_LEFT].q, grey0, c->stream);
-  launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw + at1, M, panes ? M - at1 : M, l.step, l.width, l.height, c->rect.map[eye1].q, grey1,
-                 c->stream);
+  if (grey1) launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw + at1, M, panes ? M - at1 : M, l.step, l.width, l.height, c->rect.map[eye1].q, grey1,
+                            c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
@@ -227,7 +228,8 @@ static int finish_frame(ModContext *c, Pipe::Slot &s, Pipe::RingPlane &now, cons
 }
 
 // ---- host streaming: the image entries ---------------------------------------------------------------------------------
-// mod_submit_stereo_host: flow and transform from the caller; _images_host: flow from the previous left image; _odometry_host: both estimated
+// mod_submit_stereo_host: flow and transform from the caller; _images_host: flow from the previous left image; _odometry_host: both estimated;
+// mod_submit_depth_host: EstimatedFlow or Odometry with `rgbd` set: no right image, the disparity converted from `depth` instead of estimated
 enum class StereoKind { CallerFlow, EstimatedFlow, Odometry };
 struct StereoRequest {
   StereoKind kind;
@@ -241,6 +243,8 @@ struct StereoRequest {
   const ModEgoParams *ego_prm;
   ModTransform *transform_out;      // Odometry; may be null, like ...
   ModEgoResult *ego_out;
+  bool rgbd;                        // left is the image of an RGB-D camera (right and sgm are null), and ...
+  const void *depth;                // ... its depth message
   bool estimates_flow() const { return kind != StereoKind::CallerFlow; }
   bool odometry() const { return kind == StereoKind::Odometry; }
 };
@@ -251,35 +255,73 @@ struct StereoFrame {
   uint8_t *left, *right;
   bool rectify;                      // the images are raw messages: whole into the slot's raw staging, k_rectify from there
   bool panes;                        // side by side at this submit: rq.left holds both eyes
+  ModDepthLayout dlay;               // RGB-D: the depth message's layout at this submit, and then the staged copy's
   bool colour() const { return lay.encoding != MOD_ENCODING_MONO8; }
 };
 
-static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay) {
+// what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
+static int rgbd_checks(ModContext *c, ModDepthLayout *dlay) {
+  if (c->side_by_side) return fail(c, MOD_ERR_INVALID_ARGUMENT, "mod_submit_depth_host takes one image: side by side must be off");
+  if (c->rect.on && !c->has_depth_reg)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "a depth image aligned to the raw image cannot be aligned to the rectified one: set a depth registration");
+  return current_depth_layout(c, dlay);
+}
+
+static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay, ModDepthLayout *dlay) {
+  if (int rc = rq.rgbd ? rgbd_checks(c, dlay) : MOD_OK) return rc;
   // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276); side by side, left holds both eyes
-  if (!rq.left || (!rq.right && !c->side_by_side)) {
+  if (!rq.left || (rq.rgbd ? !rq.depth : !rq.right && !c->side_by_side)) {
     c->pipe.have_prev = false;      // ... which becomes the next frame's (missing) previous disparity (:397-398)
     c->pipe.have_prev_img = false;  // ... and the next frame has no previous image to estimate the flow from
     return MOD_SKIP_NO_DISPARITY_NOW;
   }
-  if (int rc = check_sgm_params(c, rq.sgm)) return rc;
+  if (int rc = rq.rgbd ? MOD_OK : check_sgm_params(c, rq.sgm)) return rc;
   if (int rc = rq.estimates_flow() ? check_flow_params(c, rq.flow_prm, 1) : MOD_OK) return rc;
   if (int rc = rq.odometry() ? check_ego_params(c, rq.ego_prm) : MOD_OK) return rc;
   if (int rc = c->side_by_side ? check_one_message(c, rq.left, rq.right) : MOD_OK) return rc;
   if (int rc = current_layout(c, lay)) return rc;
   if (!c->rect.on) return MOD_OK;
   if (int rc = ensure_rectify_map(c, MOD_EYE_LEFT, *lay)) return rc;
-  return ensure_rectify_map(c, MOD_EYE_RIGHT, *lay);
+  return rq.rgbd ? MOD_OK : ensure_rectify_map(c, MOD_EYE_RIGHT, *lay);
+}
+
+// RGB-D: bytes of the depth message that cross PCIe (the window, packed; with a registration the whole message)
+static size_t depth_stage_bytes(const ModContext *c, const ModDepthLayout &l) {
+  return c->has_depth_reg ? (size_t)l.step * l.height : pixels(c) * depth_bytes(l.encoding);
 }
 
 static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
-  HIP_TRY(c, dalloc(f.s.img, 2 * c->maxN));
+  if (!rq.rgbd) HIP_TRY(c, dalloc(f.s.img, 2 * c->maxN));
   if (rq.estimates_flow()) HIP_TRY(c, dalloc(f.now.left, c->maxN));
+  if (rq.rgbd) {
+    if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage_bytes(c, f.dlay))) return rc;
+    if (c->has_depth_reg) HIP_TRY(c, dalloc(f.s.zbuf, c->maxN));
+  }
   if (f.rectify) {
     if (int rc = ensure_raw_stage(c, f.s.raw, f.lay)) return rc;
     if (int rc = is_bayer(f.lay.encoding) ? ensure_stage_bytes(c, f.s.bayer_grey, 2 * (size_t)f.lay.width * f.lay.height) : MOD_OK) return rc;
   } else if (f.colour()) HIP_TRY(c, dalloc(f.s.stage, window_stage_bytes(c)));
   f.left = rq.estimates_flow() ? f.now.left.get() : f.s.img.get();
-  f.right = f.s.img.get() + pixels(c);
+  f.right = rq.rgbd ? nullptr : f.s.img.get() + pixels(c);
+  return MOD_OK;
+}
+
+// RGB-D: the depth window (with a registration: the whole message) to the slot's stage on the copy stream, rows packed like
+// copy_window's; f.dlay becomes the layout of the staged copy
+static int upload_depth(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
+  Pipe &p = c->pipe;
+  ModDepthLayout &l = f.dlay;
+  HIP_TRY(c, f.s.depth_read.wait(p.h2d));
+  if (c->has_depth_reg) {
+    HIP_TRY(c, hipMemcpyAsync(f.s.depth.buf, rq.depth, (size_t)l.step * l.height, hipMemcpyHostToDevice, p.h2d));
+    return MOD_OK;
+  }
+  const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H;
+  const size_t row = (size_t)W * B;
+  const uint8_t *o = static_cast<const uint8_t *>(rq.depth) + (size_t)l.y0 * l.step + (size_t)l.x0 * B;
+  if ((size_t)l.step == row) HIP_TRY(c, hipMemcpyAsync(f.s.depth.buf, o, row * H, hipMemcpyHostToDevice, p.h2d));
+  else HIP_TRY(c, hipMemcpy2DAsync(f.s.depth.buf, row, o, (size_t)l.step, row, (size_t)H, hipMemcpyHostToDevice, p.h2d));
+  l.width = W; l.height = H; l.step = (int32_t)row; l.x0 = l.y0 = 0;
   return MOD_OK;
 }
 
@@ -291,6 +333,7 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
     HIP_TRY(c, f.s.stage_read.wait(p.h2d));
     if (int rc = copy_messages(c, f.lay, f.panes, rq.left, rq.right, f.s.raw.buf, p.h2d)) return rc;
     if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
+    if (int rc = rq.rgbd ? upload_depth(c, rq, f) : MOD_OK) return rc;
     HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
     HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
     // the grey images are written on the context's stream, which is behind every older reader of them already
@@ -298,7 +341,7 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
     HIP_TRY(c, f.s.stage_read.record(c->stream));
     return MOD_OK;
   }
-  HIP_TRY(c, f.s.img_read.wait(p.h2d));
+  if (!rq.rgbd) HIP_TRY(c, f.s.img_read.wait(p.h2d));
   // colour grey is written on the context's stream, which is behind every older reader already: only a copy waits for left_read
   if (rq.estimates_flow() && !f.colour()) HIP_TRY(c, f.now.left_read.wait(p.h2d));
   if (f.colour()) HIP_TRY(c, f.s.stage_read.wait(p.h2d));
@@ -308,22 +351,23 @@ static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f)
   uint8_t *stage1 = f.colour() ? f.s.stage.get() + (bayer ? (size_t)g.rw * g.rh : P) : nullptr;
   if (bayer) {
     HIP_TRY(c, copy_bayer_region(f.lay, g, rq.left, f.s.stage, p.h2d));
-    HIP_TRY(c, copy_bayer_region(f.lay, g, right, stage1, p.h2d));
+    if (right) HIP_TRY(c, copy_bayer_region(f.lay, g, right, stage1, p.h2d));
   } else {
     HIP_TRY(c, copy_window(f.lay, W, H, rq.left, f.colour() ? f.s.stage.get() : f.left, p.h2d));
-    HIP_TRY(c, copy_window(f.lay, W, H, right, f.colour() ? stage1 : f.right, p.h2d));
+    if (right) HIP_TRY(c, copy_window(f.lay, W, H, right, f.colour() ? stage1 : f.right, p.h2d));
   }
   if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
+  if (int rc = rq.rgbd ? upload_depth(c, rq, f) : MOD_OK) return rc;
   HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
   if (bayer) {                      // image_proc's debayer and cv_bridge's conversion on the GPU
     bayer_region_to_mono(c, f.lay, g, false, f.s.stage, f.left);
-    bayer_region_to_mono(c, f.lay, g, f.panes, stage1, f.right);
+    if (f.right) bayer_region_to_mono(c, f.lay, g, f.panes, stage1, f.right);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, f.s.stage_read.record(c->stream));
   } else if (f.colour()) {          // cv_bridge::toCvCopy(..., MONO8) (:220-221) on the GPU
     launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage, P, (int)(P / H), 0, 0, f.left, c->stream);
-    launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage + P, P, (int)(P / H), 0, 0, f.right, c->stream);
+    if (f.right) launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage + P, P, (int)(P / H), 0, 0, f.right, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, f.s.stage_read.record(c->stream));
   }
@@ -335,13 +379,20 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   // estimateDisparity (:258-279) on the GPU, straight into the ring: this plane is `now` here and `previous` of the next frame.
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   HIP_TRY(c, f.now.copied_out.wait_once(c->stream));
-  if (int rc = mod_sgm_compute_dev(c, 1, f.left, f.right, rq.sgm, f.now.disparity)) return rc;
-  HIP_TRY(c, f.s.img_read.record(c->stream));
+  if (rq.rgbd) {                    // the depth conversion (depth.hip) in the estimator's place
+    if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.s.zbuf, f.now.disparity)) return rc;
+    HIP_TRY(c, f.s.depth_read.record(c->stream));
+  } else {
+    if (int rc = mod_sgm_compute_dev(c, 1, f.left, f.right, rq.sgm, f.now.disparity)) return rc;
+    HIP_TRY(c, f.s.img_read.record(c->stream));
+  }
   HIP_TRY(c, p.ring_written.record(c->stream));
   if (rq.estimates_flow()) HIP_TRY(c, f.now.left_read.record(c->stream));
-  const bool had_prev = p.have_prev, has_flow = rq.estimates_flow() ? p.have_prev_img : rq.flow != nullptr;
+  // an RGB-D image pairs with an RGB-D image only, a stereo head's left image with one of its own: the other is "a submit of another kind"
+  const bool had_prev = p.have_prev, has_flow = rq.estimates_flow() ? p.have_prev_img && p.prev_img_rgbd == rq.rgbd : rq.flow != nullptr;
   p.advance_ring();                 // whatever construct() does with the frame: it keeps its plane when it ends at a guard below
   p.have_prev_img = rq.estimates_flow();   // previous_left = left (:279-290)
+  p.prev_img_rgbd = rq.rgbd;
   // disparity_now exists by now
   if (int rc = construct_skip(has_flow, had_prev, rq.transform || rq.odometry(), true)) return rc;
   if (rq.estimates_flow()) {        // estimateOpticalFlow (:279-290) on the GPU, straight into the frame's flow buffer
@@ -361,9 +412,10 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
 static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq) {
   Pipe::Frame at;
   ModImageLayout lay;
-  int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay); });
+  ModDepthLayout dlay{};
+  int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on, c->side_by_side};
+  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on, c->side_by_side, dlay};
   if ((rc = grow_for(c, rq, f)) || (rc = upload_images(c, rq, f)) || (rc = estimate(c, rq, f))) return rc;
   static const ModTransform kUnused = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};   // stands for the transform in HBM (never read)
   const ModFrameBatch in{1, 0, f.now.disparity, f.prev.disparity, f.s.flow, rq.odometry() ? &kUnused : rq.transform, &rq.dt};
@@ -569,6 +621,18 @@ int mod_submit_odometry_host(ModContext *c, const uint8_t *left, const uint8_t *
   if (c && !ego_prm) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null ego-motion parameters");
   StereoRequest rq{StereoKind::Odometry, left, right, sgm, dt, {cloud_aos, labels, objects, max_objects, disparity, flow_out}};
   rq.flow_prm = flow_prm; rq.ego_prm = ego_prm; rq.transform_out = transform_out; rq.ego_out = ego_out;
+  return submit_stereo(c, ticket, rq);
+}
+
+int mod_submit_depth_host(ModContext *c, const uint8_t *image, const void *depth, const ModFlowParams *flow_prm, const ModEgoParams *ego_prm,
+                          const ModTransform *transform, double dt, void *cloud_aos, int32_t *labels, ModObject *objects, int32_t max_objects,
+                          float *disparity, float *flow_out, ModTransform *transform_out, ModEgoResult *ego_out, int32_t *ticket) {
+  if (c && !flow_prm) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow parameters");
+  if (c && !transform && !ego_prm) return fail(c, MOD_ERR_INVALID_ARGUMENT, "a transform or ego-motion parameters: both are null");
+  StereoRequest rq{transform ? StereoKind::EstimatedFlow : StereoKind::Odometry, image, nullptr, nullptr, dt,
+                   {cloud_aos, labels, objects, max_objects, disparity, flow_out}};
+  rq.flow_prm = flow_prm; rq.transform = transform; rq.rgbd = true; rq.depth = depth;
+  if (rq.odometry()) { rq.ego_prm = ego_prm; rq.transform_out = transform_out; rq.ego_out = ego_out; }
   return submit_stereo(c, ticket, rq);
 }
 

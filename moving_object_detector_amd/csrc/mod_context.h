@@ -131,6 +131,13 @@ struct ModContext {
   // Bayer messages under a rectification are demosaiced whole (debayer, then rectify): the grey planes k_rectify then samples, one
   // per frame of mod_rectify_dev (the host paths have their own, beside their raw stages); allocated on first use, grow-only
   RawStage bayer_grey;
+  // RGB-D cameras (depth.hip): the depth messages' layout (mod_set_depth_layout; while has_depth_layout is false: 16UC1 packed at the
+  // camera's size) and the opt-in registration to the image camera; both read when a call / submit is made
+  ModDepthLayout depth_layout{};
+  bool has_depth_layout = false;
+  ModDepthRegistration depth_reg{};
+  bool has_depth_reg = false;
+  DevPtr<uint32_t> depth_zbuf;              // mod_depth_to_disparity_dev's z-buffer, [max_frames][maxN], allocated on first registered call
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -169,6 +176,11 @@ struct ModContext {
       Fence stage_read;                              // ... the kernels that read them have been enqueued (context stream)
       RawStage raw;                                  // with a rectification set: the slot's two raw messages instead, behind the same fence
       RawStage bayer_grey;                           // ... and, for Bayer messages, their two demosaiced grey planes (k_rectify samples these)
+      // mod_submit_depth_host: the slot's depth window (with a registration: whole message) as it arrives, and the kernels that read
+      // it have been enqueued (context stream); the slot's z-buffer [maxN], written and read on the context's stream only
+      RawStage depth;
+      Fence depth_read;
+      DevPtr<uint32_t> zbuf;
       // mod_submit_odometry_host: the slot's estimate on the device (its element of Pipe::ego, last copied out before the slot's
       // previous ticket was collected) and its pinned host copy; collect reads the status
       EgoSlot *ego = nullptr;
@@ -198,6 +210,7 @@ struct ModContext {
     int64_t dring = 0, seq = 0;                      // planes / tickets handed out so far
     int in_flight = 0;
     bool have_prev = false, have_prev_img = false;   // the plane before the next one holds the previous frame's disparity / left image
+    bool prev_img_rgbd = false;                      // ... and that left image came from mod_submit_depth_host (it pairs with its own kind only)
     // The ring arithmetic, all of it: the slot of ticket number t, the plane the next frame fills and the one filled before it.
     Frame frame(int64_t t) { return {&slot[t % MOD_PIPELINE_DEPTH], &ring[dring % R], &ring[(dring + R - 1) % R]}; }
     // `now` becomes the next frame's previous plane (disparity_previous_ = disparity_now_, scene_flow_constructor.cpp:397-398).  An image frame
@@ -274,6 +287,11 @@ int ensure_stage_bytes(ModContext *c, ModContext::RawStage &r, size_t need);   /
 // the grey planes `grey` [frames][height][width], then k_rectify from those as mono8 through `map` into mono; context's stream
 int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint8_t *src, int pane, uint8_t *grey, const int32_t *map,
                   uint8_t *mono);
+// the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
+int current_depth_layout(ModContext *c, ModDepthLayout *out);
+// `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,
+// or with a registration in force the scatter through zbuf [frames][W H]
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, uint32_t *zbuf, float *disparity);
 int begin_cluster_scratch(ModContext *c);
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                 const ModClusterOut *out);

@@ -152,3 +152,15 @@ void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, 
                     int height, const int32_t *map, uint8_t *dst, hipStream_t s);
 void build_rectify_map(const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map);
 const char *check_rectify_camera(const ModRectifyCamera &cam);   // null: valid, else what is wrong with it
+
+// depth images to disparity (depth.hip).  Window W x H at (x0, y0) of each depth frame (MOD_DEPTH_*, row pitch `step`, frames
+// frame_bytes apart) -> dst [frames][H][W]: fT / (sample * unit) where that is positive and finite, else `invalid`
+int depth_bytes(int encoding);      // bytes per sample; 0: unknown encoding
+void launch_depth_to_disparity(int encoding, int W, int H, int frames, const void *src, size_t frame_bytes, int step, int x0, int y0, float unit,
+                               float fT, float invalid, float *dst, hipStream_t s);
+// the depth camera (of the whole message) and its pose, then the image camera whose W x H window the samples land in
+struct DepthRegArgs { double fxd, fyd, cxd, cyd, R[9], t[3], fx, fy, cx, cy, Tx, Ty; };
+// the registered path: every sample of the whole width x height messages (frames step * height bytes apart) through g into the
+// z-buffer zbuf [frames][H][W] (cleared here), the nearest sample of every target -> dst as above, targets nothing hit -> `invalid`
+hipError_t launch_depth_register(int encoding, int W, int H, int frames, const void *src, int width, int height, int step, float unit,
+                                 const DepthRegArgs &g, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s);

@@ -314,6 +314,50 @@ int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint
   return MOD_OK;
 }
 
+// registered: a registration is in force (the whole message is scattered: no window, any message size)
+static int check_depth_layout(ModContext *c, const ModDepthLayout &l, bool registered) {
+  const int B = depth_bytes(l.encoding);
+  if (!B) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown depth encoding");
+  if (l.width < 1 || l.height < 1 || l.width > MOD_MAX_WIDTH || l.height > MOD_MAX_WIDTH)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: width and height must be in 1..MOD_MAX_WIDTH");
+  if ((int64_t)l.step < (int64_t)l.width * B || l.step % B) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: step must be a multiple of the sample size and >= width * sample size");
+  if ((int64_t)l.step * l.height > INT32_MAX) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: step * height must be below 2^31");
+  if (!std::isfinite(l.unit) || l.unit < 0.0f) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: unit must be 0 (the REP 118 default) or finite and positive");
+  if (registered) {
+    if (l.x0 || l.y0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: x0 and y0 must be 0 while a depth registration is set (the whole message is registered)");
+  } else if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height) {
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the depth image");
+  }
+  return MOD_OK;
+}
+
+static ModDepthLayout default_depth_layout(const ModContext *c) { return ModDepthLayout{MOD_DEPTH_16UC1, c->dc.W, c->dc.H, 2 * c->dc.W, 0, 0, 0.0f}; }
+
+int current_depth_layout(ModContext *c, ModDepthLayout *out) {
+  *out = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  return check_depth_layout(c, *out, c->has_depth_reg);   // the camera or the registration may have changed since the layout was set
+}
+
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, uint32_t *zbuf, float *disparity) {
+  const float unit = l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f;
+  const float invalid = c->dc.dmin - 1.0f;
+  if (c->has_depth_reg) {
+    const ModDepthRegistration &r = c->depth_reg;
+    DepthRegArgs g{};
+    g.fxd = r.fx; g.fyd = r.fy; g.cxd = r.cx; g.cyd = r.cy;
+    for (int i = 0; i < 9; i++) g.R[i] = r.R[i];
+    for (int i = 0; i < 3; i++) g.t[i] = r.t[i];
+    g.fx = c->cam.fx; g.fy = c->cam.fy; g.cx = c->cam.cx; g.cy = c->cam.cy; g.Tx = c->cam.Tx; g.Ty = c->cam.Ty;
+    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, unit, g, c->dc.fT, invalid, zbuf, disparity,
+                                     c->stream));
+  } else {
+    launch_depth_to_disparity(l.encoding, c->dc.W, c->dc.H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, unit, c->dc.fT, invalid,
+                              disparity, c->stream);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
 void refresh_devcam(ModContext *c) {
   DevCam &d = c->dc;
   d.W = c->cam.width; d.H = c->cam.height;
@@ -626,6 +670,65 @@ int mod_rectify_map_host(ModContext *c, int32_t eye, const ModImageLayout *layou
   HIP_TRY(c, hipMemcpyAsync(map_qxqy, c->rect.map[eye].q, sizeof(int32_t) * 2 * (size_t)c->dc.W * c->dc.H, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MOD_OK;
+}
+
+int mod_set_depth_layout(ModContext *c, const ModDepthLayout *l) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
+  if (int rc = check_depth_layout(c, l ? *l : default_depth_layout(c), c->has_depth_reg)) return rc;
+  if (l) c->depth_layout = *l;
+  c->has_depth_layout = l != nullptr;
+  return MOD_OK;
+}
+
+int mod_get_depth_layout(const ModContext *c, ModDepthLayout *l) {
+  if (!c || !l) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return MOD_ERR_NOT_CONFIGURED;
+  *l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  return MOD_OK;
+}
+
+int mod_set_depth_registration(ModContext *c, const ModDepthRegistration *r) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (r) {
+    for (const double v : {r->fx, r->fy, r->cx, r->cy}) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite intrinsics");
+    for (const double v : r->R) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite entry in R");
+    for (const double v : r->t) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite entry in t");
+    if (r->fx <= 0.0 || r->fy <= 0.0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: the focal lengths must be positive");
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        const double d = r->R[3 * i] * r->R[3 * j] + r->R[3 * i + 1] * r->R[3 * j + 1] + r->R[3 * i + 2] * r->R[3 * j + 2];
+        if (std::fabs(d - (i == j ? 1.0 : 0.0)) > 1e-6)
+          return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: R is not a rotation (R R^T differs from I by more than 1e-6)");
+      }
+    c->depth_reg = *r;
+  }
+  c->has_depth_reg = r != nullptr;
+  return MOD_OK;
+}
+
+int mod_get_depth_registration(const ModContext *c, ModDepthRegistration *r, int32_t *enabled) {
+  if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
+  *enabled = c->has_depth_reg;
+  if (c->has_depth_reg && r) *r = c->depth_reg;
+  return MOD_OK;
+}
+
+int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth, const ModDepthLayout *layout, float *disparity) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
+  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
+  ModDepthLayout l;
+  int rc = layout ? check_depth_layout(c, *layout, c->has_depth_reg) : current_depth_layout(c, &l);
+  if (rc) return rc;
+  if (layout) l = *layout;
+  if (!depth) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity planes");
+  if ((uintptr_t)depth % depth_bytes(l.encoding) || (uintptr_t)disparity % 4)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth must be aligned to its sample size and disparity to 4 bytes");
+  if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
+  return run_depth_to_disparity(c, frames, depth, l, c->depth_zbuf, disparity);
 }
 
 int mod_synchronize(ModContext *c) {

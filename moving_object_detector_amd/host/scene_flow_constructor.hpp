@@ -294,6 +294,53 @@ class SceneFlowConstructor {
     next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
     return ticket;
   }
+  // RGB-D cameras (mod_submit_depth_host): the layout of the depth messages — `depth` is a sensor_msgs/Image with encoding "16UC1"
+  // (millimetres) or "32FC1" (metres), little-endian; unit 0 = the REP 118 default — with the camera-sized window at (x0, y0), and the
+  // optional registration of a depth camera with intrinsics and a pose of its own (null = off; set it before a layout of another size
+  // than the camera's, with x0 = y0 = 0).  false / an exception where the library refuses the values.
+  bool setDepthLayout(const mod_host::Image &depth, int x0 = 0, int y0 = 0, float unit = 0.0f) {
+    const int enc = depth.encoding == "16UC1" ? MOD_DEPTH_16UC1 : depth.encoding == "32FC1" ? MOD_DEPTH_32FC1 : -1;
+    if (enc < 0) return false;
+    const ModDepthLayout lay{enc, depth.width, depth.height, depth.step > 0 ? depth.step : depth.width * (enc == MOD_DEPTH_16UC1 ? 2 : 4), x0, y0, unit};
+    return mod_set_depth_layout(ctx_, &lay) == MOD_OK;
+  }
+  void setDepthRegistration(const ModDepthRegistration *registration) { check(mod_set_depth_registration(ctx_, registration)); }
+  // submitOdometry() for an RGB-D camera: one image (any encoding the library takes, the window at (x0, y0)) and one depth image of the
+  // layout setDepthLayout() set, in the disparity estimator's place the conversion fT / depth on the GPU.  transform_prev2now null: the
+  // camera motion is estimated on the GPU (collectOdometry() joins the ticket and integrates it); else the caller's (collect()).
+  // dt is the stamp difference of consecutive images.  Returns a ticket, or -1 where nothing will be published (first frame, a
+  // missing image, setSideBySide() on).
+  int submitDepth(const mod_host::Image *image, const mod_host::Image *depth, mod_host::MovingObjectArray *moving_objects,
+                  const mod_host::Transform *transform_prev2now = nullptr, std::vector<float> *flow_out = nullptr, int x0 = 0, int y0 = 0,
+                  std::vector<float> *disparity_out = nullptr, mod_host::PointCloud2 *pc_with_velocity = nullptr) {
+    // while setSideBySide() is on an image is two panes: an RGB-D frame is then a missing image, like two distinct images elsewhere
+    const bool images = !side_by_side_ && image && depth && image->data && depth->data && useLayout(*image, *image, x0, y0);
+    ModTransform tf{};
+    if (transform_prev2now) {
+      for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
+      for (int i = 0; i < 4; i++) tf.q[i] = transform_prev2now->rotation[i];
+    }
+    const double dt = (images && have_stamp_) ? mod_host::duration_sec(image->header.stamp, previous_stamp_) : 0.0;
+    Pending &p = pending_[next_slot_];
+    p.objects.resize(max_objects_);
+    if (flow_out) flow_out->resize((size_t)image_width_ * image_height_ * 2);
+    if (disparity_out) disparity_out->resize((size_t)image_width_ * image_height_);
+    if (pc_with_velocity) pc_with_velocity->data.resize((size_t)image_width_ * image_height_ * 32);
+    int32_t ticket = -1;
+    ModFlowParams fp{4, 4, 5, 1, 1};
+    const int rc = mod_submit_depth_host(ctx_, images ? image->data : nullptr, images ? depth->data : nullptr, &fp, &ego_, transform_prev2now ? &tf : nullptr,
+                                         dt, pc_with_velocity ? pc_with_velocity->data.data() : nullptr, nullptr, moving_objects ? p.objects.data() : nullptr,
+                                         moving_objects ? (int32_t)p.objects.size() : 0, disparity_out ? disparity_out->data() : nullptr,
+                                         flow_out ? flow_out->data() : nullptr, &p.tf, &p.ego, &ticket);
+    have_parked_ = false;
+    if (images) { previous_stamp_ = image->header.stamp; have_stamp_ = true; }
+    else have_stamp_ = false;
+    if (rc > 0) return -1;
+    check(rc);
+    p.ticket = ticket; p.cloud = pc_with_velocity; p.objs = moving_objects; p.header = image->header;
+    next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
+    return ticket;
+  }
   // collect() of an odometry ticket: fills the messages, integrates the pose (only when the estimate succeeded) and returns the
   // estimated motion prev -> now; false when visual odometry failed (nothing is published, the pose is unchanged, :251-255).
   bool collectOdometry(int ticket, mod_host::Transform *motion = nullptr) {

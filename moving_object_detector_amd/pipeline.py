@@ -151,6 +151,49 @@ class Context:
         self._check(self.lib.mod_get_side_by_side(self.h, C.byref(on)))
         return bool(on.value)
 
+    def set_depth_layout(self, layout: Optional[capi.ModDepthLayout]) -> None:
+        """Layout of the depth messages of an RGB-D camera (mod_set_depth_layout, capi.depth_layout); None = 16UC1 packed at the camera
+        size.  Read when a call or a submit is made."""
+        self._check(self.lib.mod_set_depth_layout(self.h, C.byref(layout) if layout is not None else None))
+
+    def get_depth_layout(self) -> capi.ModDepthLayout:
+        s = capi.ModDepthLayout()
+        self._check(self.lib.mod_get_depth_layout(self.h, C.byref(s)))
+        return s
+
+    def set_depth_registration(self, registration: Optional[capi.ModDepthRegistration] = None) -> None:
+        """Registration of the depth camera to the image camera on the GPU (mod_set_depth_registration, capi.depth_registration); None =
+        off (the default: the depth image is aligned to the image already).  Set it before a depth layout of another size than the
+        camera's."""
+        self._check(self.lib.mod_set_depth_registration(self.h, C.byref(registration) if registration is not None else None))
+
+    def get_depth_registration(self):
+        """The ModDepthRegistration in force, or None while it is off."""
+        r, on = capi.ModDepthRegistration(), C.c_int32(-1)
+        self._check(self.lib.mod_get_depth_registration(self.h, C.byref(r), C.byref(on)))
+        return r if on.value else None
+
+    def depth_to_disparity(self, dev: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Disparity planes (F, H, W) float32 at the camera size from device depth messages (mod_depth_to_disparity_dev): `dev` holds F
+        messages of layout.step * layout.height bytes each, back to back (any dtype and shape, contiguous); layout None = the context's.
+        fT / depth where the depth is positive and finite, min_disparity - 1 elsewhere; with a registration set the messages are
+        registered to the image camera first.  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_depth_layout()
+        if not dev.is_contiguous() or dev.device.type != "cuda":
+            raise ValueError("dev must be a contiguous device tensor")
+        frame, nbytes = lay.step * lay.height, dev.numel() * dev.element_size()
+        if frame <= 0 or nbytes % frame:
+            raise ValueError("dev must hold whole messages of step * height bytes")
+        F = nbytes // frame
+        if out is None:
+            out = torch.empty((F, self.height, self.width), dtype=torch.float32, device=dev.device)
+        elif out.shape != (F, self.height, self.width) or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor (F, H, W)")
+        rc = self._check(self.lib.mod_depth_to_disparity_dev(self.h, F, dev.data_ptr(), C.byref(lay), out.data_ptr()))
+        if rc != 0:
+            raise capi.ModError(rc, "mod_depth_to_disparity_dev skipped")
+        return out
+
     def speckle_filter(self, dev_planes: torch.Tensor, size: int, range: int) -> torch.Tensor:   # noqa: A002 (stereo_image_proc's name)
         """The speckle stage alone, in place (mod_disparity_speckle_dev), on device float32 planes (F, H, W) or (H, W) of the camera's
         size: pixels take part when finite and >= the camera's min_disparity, removed ones become min_disparity - 1.  Enqueued on the

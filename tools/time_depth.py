@@ -1,0 +1,127 @@
+"""HIP-event timing of the depth-image path (csrc/depth.hip) at 1280 x 720: k_depth_to_disparity (mod_depth_to_disparity_dev, both
+encodings) and the registered path (k_depth_register + k_zbuffer_to_disparity, 16UC1) on 64 frames per call in ms and TB/s of the
+bytes each must move, k_to_mono (bgr8) on the same box for comparison, and the depth stream (mod_submit_depth_host: 16UC1 depth, bgr8
+image, odometry kind, three frames in flight) in frames/s.  Prints one JSON line per measurement.
+Run on the GPU: python tools/time_depth.py [reps]"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+W, H, F = 1280, 720, 64
+
+
+def timed(torch, call, reps):
+    for _ in range(3):
+        assert call() == 0
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(reps):
+        call()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / reps
+
+
+def kernels(reps):
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F)
+    cam = synth.make_camera(W, H)
+    ctx.set_camera(cam)
+    dev = ctx.device
+    out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
+    rng = np.random.default_rng(0)
+    mm = torch.from_numpy(rng.integers(0, 8000, size=(F, H, W)).astype(np.uint16).view(np.int16)).to(dev)
+    metres = torch.from_numpy(rng.uniform(0.0, 8.0, size=(F, H, W)).astype(np.float32)).to(dev)
+    for name, src, B in (("16UC1", mm, 2), ("32FC1", metres, 4)):
+        lay = capi.depth_layout(name, W, H)
+        ms = timed(torch, lambda: ctx.lib.mod_depth_to_disparity_dev(ctx.h, F, src.data_ptr(), C.byref(lay), out.data_ptr()), reps)
+        print(json.dumps({"what": "k_depth_to_disparity", "encoding": name, "W": W, "H": H, "frames": F, "ms_per_call": round(ms, 4),
+                          "TB_per_s": round(F * W * H * (B + 4) / ms / 1e9, 3)}), flush=True)
+    # registered: a depth camera of the same size beside the image camera, turned by half a degree
+    a = np.radians(0.5)
+    ctx.set_depth_registration(capi.depth_registration(cam.fx * 1.05, cam.fy * 1.05, cam.cx, cam.cy,
+                                                       [np.cos(a), 0, np.sin(a), 0, 1, 0, -np.sin(a), 0, np.cos(a)], (0.02, 0.0, 0.0)))
+    lay = capi.depth_layout("16UC1", W, H)
+    ms = timed(torch, lambda: ctx.lib.mod_depth_to_disparity_dev(ctx.h, F, mm.data_ptr(), C.byref(lay), out.data_ptr()), reps)
+    # memset 4 + sample 2 + one atomic (4 read + 4 written) + finish 4 + 4 bytes per pixel
+    print(json.dumps({"what": "k_depth_register + k_zbuffer_to_disparity", "encoding": "16UC1", "W": W, "H": H, "frames": F,
+                      "ms_per_call": round(ms, 4), "TB_per_s": round(F * W * H * 22 / ms / 1e9, 3)}), flush=True)
+    ctx.set_depth_registration(None)
+    # the ingest kernel on the same box: bgr8 frames to grey
+    bgr = torch.from_numpy(rng.integers(0, 256, size=(F, H, W * 3), dtype=np.uint8)).to(dev)
+    grey = torch.empty((F, H, W), dtype=torch.uint8, device=dev)
+    il = capi.image_layout("bgr8", W, H)
+    ms = timed(torch, lambda: ctx.lib.mod_image_to_mono_dev(ctx.h, F, bgr.data_ptr(), C.byref(il), grey.data_ptr()), reps)
+    print(json.dumps({"what": "k_to_mono", "encoding": "bgr8", "W": W, "H": H, "frames": F, "ms_per_call": round(ms, 4),
+                      "TB_per_s": round(F * W * H * 4 / ms / 1e9, 3)}), flush=True)
+    ctx.close()
+
+
+def stream_fps(reps):
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    m = synth.make_ego_images(W, H, seed=1, frames=2)
+    ctx = Context(W, H, max_frames=1)
+    cam = synth.make_camera(W, H)
+    cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
+    ctx.set_camera(cam)
+    ctx.set_params(synth.Params())
+    ctx.set_image_layout(capi.image_layout("bgr8", W, H))
+    fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
+    fp, ep = capi.flow_params(), capi.ego_params()
+    pins = []
+    for k in (0, 1):
+        bgr = np.ascontiguousarray(np.repeat(m[f"left{k}"][..., None], 3, axis=2))
+        mm = np.rint(1000.0 * fT / m[f"disparity{k}"].astype(np.float64)).astype(np.uint16)
+        for a in (bgr, mm):
+            p = C.c_void_p()
+            assert ctx.lib.mod_host_malloc(ctx.h, a.nbytes, C.byref(p)) == 0
+            C.memmove(p.value, a.ctypes.data, a.nbytes)
+            pins.append(p)
+    objs = [(capi.ModObject * 64)() for _ in range(3)]
+    t, n = C.c_int32(-1), C.c_int32(-1)
+    pending = []
+
+    def step(i):
+        img, dep = (pins[0], pins[1]) if i % 2 == 0 else (pins[2], pins[3])
+        if len(pending) == 3:
+            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
+        rc = ctx.lib.mod_submit_depth_host(ctx.h, img, dep, C.byref(fp), C.byref(ep), None, 1.0 / 15.0, None, None, objs[i % 3], 64, None, None,
+                                           None, None, C.byref(t))
+        assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
+        if rc == 0:
+            pending.append(t.value)
+
+    for i in range(10):
+        step(i)
+    frames = max(20, reps)
+    t0 = time.perf_counter()
+    for i in range(10, 10 + frames):
+        step(i)
+    while pending:
+        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
+    dt = time.perf_counter() - t0
+    for p in pins:
+        ctx.lib.mod_host_free(ctx.h, p)
+    ctx.close()
+    return frames / dt
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    kernels(reps)
+    print(json.dumps({"what": "mod_submit_depth_host", "image": "bgr8", "depth": "16UC1", "kind": "odometry", "W": W, "H": H,
+                      "frames_per_s": round(stream_fps(reps), 1)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
