@@ -534,6 +534,30 @@ int  mod_rectify_map_host(ModContext *ctx, int32_t eye, const ModImageLayout *la
  * landed and min_disparity - 1.0f where none did.  Holes are left as holes (no splatting, no fill: depth_image_proc/register's
  * default; parity with a particular depth_image_proc build is not claimed).  The z-buffer is scratch of the context's, allocated on
  * first use.
+ * The footprint (mod_set_depth_splat, opt-in, off by default; depth_image_proc/register's fill_upsampling_holes): a depth camera of
+ * fewer pixels than the image camera leaves a lattice of targets no sample lands on.  With the mode on, every message pixel (U, V)
+ * whose z is valid and whose own Z passes "drop unless Z > 0 and finite" (a) does the above unchanged, the same drop tests and the same
+ * zf, and (b) paints the target pixels whose centres lie inside the bounding box of its four projected corners, a fronto-parallel patch
+ * at the sample's own Z0.  F64, no contraction, in this order:
+ *   for the corners (U - 0.5, V - 0.5), (U - 0.5, V + 0.5), (U + 0.5, V - 0.5), (U + 0.5, V + 0.5), k = 0 .. 3: the chain X0 .. Z above
+ *     with the corner in the place of (U, V) and the sample's Z0;  drop the footprint unless all four Z are > 0 and finite
+ *   p_k = (fx*X + Tx) / Z + cx;  q_k = (fy*Y + Ty) / Z + cy                    (no + 0.5: a target is covered when its centre is inside)
+ *   ulo = ceil(min(min(p0, p1), min(p2, p3)));  uhi = ceil(max(max(p0, p1), max(p2, p3))) - 1;  vlo, vhi likewise from q
+ *   drop the footprint if one of the four bounds is not finite (a NaN propagates through min and max)
+ *   drop it if (uhi - ulo) + 1 > MOD_DEPTH_SPLAT_MAX or (vhi - vlo) + 1 > MOD_DEPTH_SPLAT_MAX   (as doubles, BEFORE clipping: a sample
+ *     that would paint more than 8 x 8 targets keeps its point alone)
+ *   ulo = max(ulo, 0); uhi = min(uhi, W - 1); vlo = max(vlo, 0); vhi = min(vhi, H - 1)  (as doubles); drop it if ulo > uhi or vlo > vhi
+ *   for every (u, v) of the closed rectangle [ulo, uhi] x [vlo, vhi]: zbuf[v][u] = min(zbuf[v][u], zf), the atomic minimum and the zf of (a)
+ * A dropped footprint never drops the point, and a point outside the window does not drop its footprint.  The rectangle is half-open
+ * in the image: at equal size and identity pose it is the sample's own pixel, at a ratio of 2 neighbouring samples tile the image.
+ * Every target the point rule hits is still hit, and the result still does not depend on the order of the atomics.  Occlusion shadows
+ * and pixels without a reading stay holes.  depth_image_proc's own rule paints floor(a1) .. floor(a2) inclusive and drops footprints
+ * that cross the border: parity with it is not claimed.  tests/models/depth_splat_model.py restates the mode bit for bit.
+ *   mod_set_depth_splat         on = 0 (the default) or 1; anything else: MOD_ERR_INVALID_ARGUMENT, the state stays as it was.  May be set
+ *                               at any time; it has an effect only while a registration is in force (the plain path ignores it).  Context
+ *                               state like the depth layout: read when mod_depth_to_disparity_dev is called and at the submit of
+ *                               mod_submit_depth_host; a ticket in flight keeps the setting of its submit.
+ *   mod_get_depth_splat         *on
  *   mod_set_depth_layout        NULL = 16UC1, packed, W x H, origin 0, unit 0 (the default)
  *   mod_set_depth_registration  NULL = off (the default).  Set the registration BEFORE a layout whose message is not the camera's
  *                               size: without one the W x H window must fit the message, with one x0 and y0 must be 0 and the
@@ -561,6 +585,9 @@ int  mod_get_depth_layout(const ModContext *ctx, ModDepthLayout *layout);
 int  mod_set_depth_registration(ModContext *ctx, const ModDepthRegistration *registration);
 int  mod_get_depth_registration(const ModContext *ctx, ModDepthRegistration *registration, int32_t *enabled);
 int  mod_depth_to_disparity_dev(ModContext *ctx, int32_t frames, const void *depth, const ModDepthLayout *layout, float *disparity);
+#define MOD_DEPTH_SPLAT_MAX 8   /* targets per axis a footprint may paint */
+int  mod_set_depth_splat(ModContext *ctx, int32_t on);
+int  mod_get_depth_splat(const ModContext *ctx, int32_t *on);
 
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()

@@ -37,6 +37,7 @@ MOD_FLOW_SEEDS = 5
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
 MOD_MAX_WIDTH = 16384
 MOD_DEPTH_16UC1, MOD_DEPTH_32FC1 = 0, 1                  # REP 118 depth images: uint16 millimetres / float32 metres
+MOD_DEPTH_SPLAT_MAX = 8                                  # targets per axis a footprint of mod_set_depth_splat may paint
 DEPTH_ENCODINGS = {"16UC1": MOD_DEPTH_16UC1, "32FC1": MOD_DEPTH_32FC1}
 DEPTH_BYTES = {MOD_DEPTH_16UC1: 2, MOD_DEPTH_32FC1: 4}   # bytes per sample
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
@@ -72,7 +73,7 @@ EXPORTS = [
     "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
     "mod_set_side_by_side", "mod_get_side_by_side",
     "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
-    "mod_depth_to_disparity_dev", "mod_submit_depth_host",
+    "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
 ]
 
 
@@ -308,6 +309,8 @@ def load(require_torch_first: bool = True):
     L.mod_set_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration)]
     L.mod_get_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration), C.POINTER(i32)]
     L.mod_depth_to_disparity_dev.argtypes = [vp, i32, vp, C.POINTER(ModDepthLayout), vp]
+    L.mod_set_depth_splat.argtypes = [vp, i32]
+    L.mod_get_depth_splat.argtypes = [vp, C.POINTER(i32)]
     L.mod_submit_depth_host.argtypes = [vp, vp, vp, C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.c_double,
                                         vp, vp, vp, i32, vp, vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(i32)]
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]

@@ -16,6 +16,11 @@
 // keep the nearest sample of every target with a 32-bit atomicMin on the bit pattern of (float)Z: positive floats order like their
 // unsigned patterns and the all-ones word (no float a sample can produce) stands for "empty", so the minimum does not depend on the
 // order the atomics arrive in.  Holes stay holes.  No LDS; frames in blockIdx.z.
+//
+// k_depth_register_splat (mod_set_depth_splat, opt-in) is k_depth_register for a depth camera of fewer pixels than the image camera:
+// besides its point every sample paints its footprint, the target centres inside the bounding box of its four projected corners
+// (at most MOD_DEPTH_SPLAT_MAX per axis), with the same atomicMin and the same (float)Z.  One lane per sample; the off path's kernel
+// is untouched.
 #include "mod_launch.h"
 
 namespace {
@@ -124,6 +129,63 @@ __global__ __launch_bounds__(kBlock) void k_depth_register(int width, const uint
   atomicMin(zbuf + ((size_t)f * H + vi) * W + ui, __float_as_uint((float)Z));
 }
 
+// the header's chain for message position (u, v) at depth Z0: the point in the image camera's frame
+__device__ __forceinline__ void to_image_frame(const DepthRegArgs &g, double u, double v, double Z0, double &X, double &Y, double &Z) {
+  const double X0 = ((u - g.cxd) * Z0) / g.fxd, Y0 = ((v - g.cyd) * Z0) / g.fyd;
+  X = ((g.R[0] * X0 + g.R[1] * Y0) + g.R[2] * Z0) + g.t[0];
+  Y = ((g.R[3] * X0 + g.R[4] * Y0) + g.R[5] * Z0) + g.t[1];
+  Z = ((g.R[6] * X0 + g.R[7] * Y0) + g.R[8] * Z0) + g.t[2];
+}
+
+__device__ __forceinline__ bool positive_finite(double v) { return v > 0.0 && v < __builtin_inf(); }
+__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < __builtin_inf(); }   // NaN fails
+
+// k_depth_register with the footprint of every sample (include/mod_sf.h, "the footprint").  One lane per sample: the four corners
+// share the sample's Z0 and two values each of X0 and Y0, so the compiler keeps one copy of every product the corners have in common,
+// and the lane then walks its own rectangle of at most kSplatMax x kSplatMax targets.  Neighbouring lanes paint neighbouring
+// rectangles of the same rows, so iteration (dv, du) of a wave is one atomic instruction over one or two stretches of z-buffer rows.
+constexpr int kSplatMax = MOD_DEPTH_SPLAT_MAX;
+
+template <int Enc>
+__global__ __launch_bounds__(kBlock) void k_depth_register_splat(int width, const uint8_t *__restrict__ src, size_t frame_bytes, int step, float unit,
+                                                                 DepthRegArgs g, int W, int H, uint32_t *__restrict__ zbuf) {
+  const int U = blockIdx.x * kBlock + threadIdx.x, V = blockIdx.y, f = blockIdx.z;
+  if (U >= width) return;
+  const float z = sample_z<Enc>(src + (size_t)f * frame_bytes + (size_t)V * step + (size_t)U * kBytes<Enc>, unit);
+  if (!(z > 0.0f && z < __builtin_inff())) return;
+  const double Z0 = (double)z;
+  double X, Y, Z;
+  to_image_frame(g, (double)U, (double)V, Z0, X, Y, Z);
+  if (!positive_finite(Z)) return;                                          // no zf: neither point nor footprint
+  const uint32_t zf = __float_as_uint((float)Z);
+  uint32_t *const plane = zbuf + (size_t)f * H * W;
+  // a. the point, as k_depth_register
+  const double a = ((g.fx * X + g.Tx) / Z + g.cx) + 0.5, b = ((g.fy * Y + g.Ty) / Z + g.cy) + 0.5;
+  if (a >= 0.0 && a < (double)W && b >= 0.0 && b < (double)H) atomicMin(plane + (size_t)(int)floor(b) * W + (int)floor(a), zf);
+  // b. the footprint: corners (-,-), (-,+), (+,-), (+,+) of (U, V), all at Z0
+  double p[4], q[4];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    double Xc, Yc, Zc;
+    to_image_frame(g, (double)U + (k & 2 ? 0.5 : -0.5), (double)V + (k & 1 ? 0.5 : -0.5), Z0, Xc, Yc, Zc);
+    ok &= positive_finite(Zc);
+    p[k] = (g.fx * Xc + g.Tx) / Zc + g.cx;
+    q[k] = (g.fy * Yc + g.Ty) / Zc + g.cy;
+    ok &= is_finite(p[k]) & is_finite(q[k]);                                      // a non-finite corner makes a non-finite bound (NaN propagates)
+  }
+  if (!ok) return;
+  double ulo = ceil(fmin(fmin(p[0], p[1]), fmin(p[2], p[3]))), uhi = ceil(fmax(fmax(p[0], p[1]), fmax(p[2], p[3]))) - 1.0;
+  double vlo = ceil(fmin(fmin(q[0], q[1]), fmin(q[2], q[3]))), vhi = ceil(fmax(fmax(q[0], q[1]), fmax(q[2], q[3]))) - 1.0;
+  if ((uhi - ulo) + 1.0 > (double)kSplatMax || (vhi - vlo) + 1.0 > (double)kSplatMax) return;   // before clipping: the point alone
+  ulo = fmax(ulo, 0.0); uhi = fmin(uhi, (double)(W - 1));
+  vlo = fmax(vlo, 0.0); vhi = fmin(vhi, (double)(H - 1));
+  if (ulo > uhi || vlo > vhi) return;
+  const int u0 = (int)ulo, u1 = (int)uhi, v0 = (int)vlo, v1 = (int)vhi;       // 0 <= u0 <= u1 < W, 0 <= v0 <= v1 < H, at most kSplatMax apart
+  for (int v = v0; v <= v1; v++)
+    for (int u = u0; u <= u1; u++) atomicMin(plane + (size_t)v * W + u, zf);
+}
+
 // n words of z-buffer -> n disparities, four per lane (16-byte accesses when dst allows; zbuf is the context's own allocation)
 __global__ __launch_bounds__(kBlock) void k_zbuffer_to_disparity(size_t n, const uint32_t *__restrict__ zbuf, float fT, float invalid,
                                                                  float *__restrict__ dst) {
@@ -151,11 +213,11 @@ void launch_plain(int W, int H, int frames, const void *src, size_t frame_bytes,
 }
 
 template <int Enc>
-void launch_register(int W, int H, int frames, const void *src, int width, int height, int step, float unit, const DepthRegArgs &g, uint32_t *zbuf,
-                     hipStream_t s) {
+void launch_register(int W, int H, int frames, const void *src, int width, int height, int step, float unit, const DepthRegArgs &g, bool splat,
+                     uint32_t *zbuf, hipStream_t s) {
   const dim3 grid((unsigned)((width + kBlock - 1) / kBlock), (unsigned)height, (unsigned)frames);
-  hipLaunchKernelGGL(k_depth_register<Enc>, grid, dim3(kBlock), 0, s, width, static_cast<const uint8_t *>(src), (size_t)step * height, step, unit, g,
-                     W, H, zbuf);
+  const auto kernel = splat ? k_depth_register_splat<Enc> : k_depth_register<Enc>;
+  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, width, static_cast<const uint8_t *>(src), (size_t)step * height, step, unit, g, W, H, zbuf);
 }
 
 }  // namespace
@@ -169,12 +231,12 @@ void launch_depth_to_disparity(int encoding, int W, int H, int frames, const voi
 }
 
 hipError_t launch_depth_register(int encoding, int W, int H, int frames, const void *src, int width, int height, int step, float unit,
-                                 const DepthRegArgs &g, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s) {
+                                 const DepthRegArgs &g, bool splat, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s) {
   const size_t n = (size_t)frames * W * H;
   const hipError_t e = hipMemsetAsync(zbuf, 0xff, 4 * n, s);
   if (e != hipSuccess) return e;
-  if (encoding == MOD_DEPTH_16UC1) launch_register<MOD_DEPTH_16UC1>(W, H, frames, src, width, height, step, unit, g, zbuf, s);
-  else if (encoding == MOD_DEPTH_32FC1) launch_register<MOD_DEPTH_32FC1>(W, H, frames, src, width, height, step, unit, g, zbuf, s);
+  if (encoding == MOD_DEPTH_16UC1) launch_register<MOD_DEPTH_16UC1>(W, H, frames, src, width, height, step, unit, g, splat, zbuf, s);
+  else if (encoding == MOD_DEPTH_32FC1) launch_register<MOD_DEPTH_32FC1>(W, H, frames, src, width, height, step, unit, g, splat, zbuf, s);
   hipLaunchKernelGGL(k_zbuffer_to_disparity, dim3((unsigned)((n + 4 * kBlock - 1) / (4 * kBlock))), dim3(kBlock), 0, s, n, zbuf, fT, invalid, dst);
   return hipSuccess;
 }

@@ -256,6 +256,7 @@ struct StereoFrame {
   bool rectify;                      // the images are raw messages: whole into the slot's raw staging, k_rectify from there
   bool panes;                        // side by side at this submit: rq.left holds both eyes
   ModDepthLayout dlay;               // RGB-D: the depth message's layout at this submit, and then the staged copy's
+  bool splat;                        // ... and mod_set_depth_splat's setting at this submit
   bool colour() const { return lay.encoding != MOD_ENCODING_MONO8; }
 };
 
@@ -380,7 +381,7 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   HIP_TRY(c, f.now.copied_out.wait_once(c->stream));
   if (rq.rgbd) {                    // the depth conversion (depth.hip) in the estimator's place
-    if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.s.zbuf, f.now.disparity)) return rc;
+    if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.splat, f.s.zbuf, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.depth_read.record(c->stream));
   } else {
     if (int rc = mod_sgm_compute_dev(c, 1, f.left, f.right, rq.sgm, f.now.disparity)) return rc;
@@ -415,7 +416,7 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   ModDepthLayout dlay{};
   int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on, c->side_by_side, dlay};
+  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on, c->side_by_side, dlay, c->depth_splat};
   if ((rc = grow_for(c, rq, f)) || (rc = upload_images(c, rq, f)) || (rc = estimate(c, rq, f))) return rc;
   static const ModTransform kUnused = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};   // stands for the transform in HBM (never read)
   const ModFrameBatch in{1, 0, f.now.disparity, f.prev.disparity, f.s.flow, rq.odometry() ? &kUnused : rq.transform, &rq.dt};

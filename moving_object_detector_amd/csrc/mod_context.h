@@ -137,6 +137,7 @@ struct ModContext {
   bool has_depth_layout = false;
   ModDepthRegistration depth_reg{};
   bool has_depth_reg = false;
+  bool depth_splat = false;                 // mod_set_depth_splat: the registered path paints footprints (k_depth_register_splat)
   DevPtr<uint32_t> depth_zbuf;              // mod_depth_to_disparity_dev's z-buffer, [max_frames][maxN], allocated on first registered call
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
@@ -291,7 +292,7 @@ int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint
 int current_depth_layout(ModContext *c, ModDepthLayout *out);
 // `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,
 // or with a registration in force the scatter through zbuf [frames][W H]
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, uint32_t *zbuf, float *disparity);
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, uint32_t *zbuf, float *disparity);
 int begin_cluster_scratch(ModContext *c);
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                 const ModClusterOut *out);

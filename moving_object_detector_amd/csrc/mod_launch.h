@@ -161,6 +161,7 @@ void launch_depth_to_disparity(int encoding, int W, int H, int frames, const voi
 // the depth camera (of the whole message) and its pose, then the image camera whose W x H window the samples land in
 struct DepthRegArgs { double fxd, fyd, cxd, cyd, R[9], t[3], fx, fy, cx, cy, Tx, Ty; };
 // the registered path: every sample of the whole width x height messages (frames step * height bytes apart) through g into the
-// z-buffer zbuf [frames][H][W] (cleared here), the nearest sample of every target -> dst as above, targets nothing hit -> `invalid`
+// z-buffer zbuf [frames][H][W] (cleared here), the nearest sample of every target -> dst as above, targets nothing hit -> `invalid`;
+// splat: every sample paints its footprint too (k_depth_register_splat, mod_set_depth_splat)
 hipError_t launch_depth_register(int encoding, int W, int H, int frames, const void *src, int width, int height, int step, float unit,
-                                 const DepthRegArgs &g, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s);
+                                 const DepthRegArgs &g, bool splat, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s);

@@ -338,7 +338,7 @@ int current_depth_layout(ModContext *c, ModDepthLayout *out) {
   return check_depth_layout(c, *out, c->has_depth_reg);   // the camera or the registration may have changed since the layout was set
 }
 
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, uint32_t *zbuf, float *disparity) {
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, uint32_t *zbuf, float *disparity) {
   const float unit = l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f;
   const float invalid = c->dc.dmin - 1.0f;
   if (c->has_depth_reg) {
@@ -348,8 +348,8 @@ int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const M
     for (int i = 0; i < 9; i++) g.R[i] = r.R[i];
     for (int i = 0; i < 3; i++) g.t[i] = r.t[i];
     g.fx = c->cam.fx; g.fy = c->cam.fy; g.cx = c->cam.cx; g.cy = c->cam.cy; g.Tx = c->cam.Tx; g.Ty = c->cam.Ty;
-    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, unit, g, c->dc.fT, invalid, zbuf, disparity,
-                                     c->stream));
+    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, unit, g, splat, c->dc.fT, invalid, zbuf,
+                                     disparity, c->stream));
   } else {
     launch_depth_to_disparity(l.encoding, c->dc.W, c->dc.H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, unit, c->dc.fT, invalid,
                               disparity, c->stream);
@@ -728,7 +728,20 @@ int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth,
   if ((uintptr_t)depth % depth_bytes(l.encoding) || (uintptr_t)disparity % 4)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth must be aligned to its sample size and disparity to 4 bytes");
   if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
-  return run_depth_to_disparity(c, frames, depth, l, c->depth_zbuf, disparity);
+  return run_depth_to_disparity(c, frames, depth, l, c->depth_splat, c->depth_zbuf, disparity);
+}
+
+int mod_set_depth_splat(ModContext *c, int32_t on) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (on != 0 && on != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth splat: on must be 0 or 1");
+  c->depth_splat = on != 0;
+  return MOD_OK;
+}
+
+int mod_get_depth_splat(const ModContext *c, int32_t *on) {
+  if (!c || !on) return MOD_ERR_INVALID_ARGUMENT;
+  *on = c->depth_splat;
+  return MOD_OK;
 }
 
 int mod_synchronize(ModContext *c) {

@@ -305,6 +305,9 @@ class SceneFlowConstructor {
     return mod_set_depth_layout(ctx_, &lay) == MOD_OK;
   }
   void setDepthRegistration(const ModDepthRegistration *registration) { check(mod_set_depth_registration(ctx_, registration)); }
+  // a depth camera of fewer pixels than the image camera (a registration is set): every depth sample fills the image pixels inside its
+  // projected footprint instead of one, depth_image_proc/register's fill_upsampling_holes; off by default, read at each submitDepth()
+  void setDepthSplat(bool on) { check(mod_set_depth_splat(ctx_, on ? 1 : 0)); }
   // submitOdometry() for an RGB-D camera: one image (any encoding the library takes, the window at (x0, y0)) and one depth image of the
   // layout setDepthLayout() set, in the disparity estimator's place the conversion fT / depth on the GPU.  transform_prev2now null: the
   // camera motion is estimated on the GPU (collectOdometry() joins the ticket and integrates it); else the caller's (collect()).

@@ -173,11 +173,22 @@ class Context:
         self._check(self.lib.mod_get_depth_registration(self.h, C.byref(r), C.byref(on)))
         return r if on.value else None
 
+    def set_depth_splat(self, on: bool = True) -> None:
+        """Fill the holes a depth camera of fewer pixels than the image camera leaves in the registered path (mod_set_depth_splat):
+        every depth sample paints the image pixels inside its projected footprint, at most capi.MOD_DEPTH_SPLAT_MAX per axis, not its
+        centre alone.  Off by default; without a registration it has no effect.  Read when a call or a submit is made."""
+        self._check(self.lib.mod_set_depth_splat(self.h, int(on)))
+
+    def get_depth_splat(self) -> bool:
+        on = C.c_int32(-1)
+        self._check(self.lib.mod_get_depth_splat(self.h, C.byref(on)))
+        return bool(on.value)
+
     def depth_to_disparity(self, dev: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Disparity planes (F, H, W) float32 at the camera size from device depth messages (mod_depth_to_disparity_dev): `dev` holds F
         messages of layout.step * layout.height bytes each, back to back (any dtype and shape, contiguous); layout None = the context's.
         fT / depth where the depth is positive and finite, min_disparity - 1 elsewhere; with a registration set the messages are
-        registered to the image camera first.  Enqueued on the context's stream."""
+        registered to the image camera first (set_depth_splat: with their footprints).  Enqueued on the context's stream."""
         lay = layout if layout is not None else self.get_depth_layout()
         if not dev.is_contiguous() or dev.device.type != "cuda":
             raise ValueError("dev must be a contiguous device tensor")

@@ -2,8 +2,12 @@
 encodings) and the registered path (k_depth_register + k_zbuffer_to_disparity, 16UC1) on 64 frames per call in ms and TB/s of the
 bytes each must move, k_to_mono (bgr8) on the same box for comparison, and the depth stream (mod_submit_depth_host: 16UC1 depth, bgr8
 image, odometry kind, three frames in flight) in frames/s.  Prints one JSON line per measurement.
-Run on the GPU: python tools/time_depth.py [reps]"""
+--splat: the registered path and the depth stream on a depth message of HALF the camera's width and height (the case
+mod_set_depth_splat exists for) with the mode off and on, the two alternating in one process for ROUNDS rounds: every round's figure,
+the median and the spread (largest - smallest) of each.
+Run on the GPU: python tools/time_depth.py [reps] [--splat]"""
 import ctypes as C
+import functools
 import json
 import os
 import sys
@@ -14,6 +18,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 W, H, F = 1280, 720, 64
+ROUNDS = 5
 
 
 def timed(torch, call, reps):
@@ -66,22 +71,78 @@ def kernels(reps):
     ctx.close()
 
 
-def stream_fps(reps):
+def half_size_registration(capi, cam):
+    """a depth camera of half the resolution beside the image camera, turned by half a degree: message pixel (U, V) looks along image
+    pixel (2 U, 2 V)"""
+    a = np.radians(0.5)
+    return capi.depth_registration(cam.fx / 2, cam.fy / 2, cam.cx / 2 + 0.1, cam.cy / 2 - 0.15,
+                                   [np.cos(a), 0, np.sin(a), 0, 1, 0, -np.sin(a), 0, np.cos(a)], (0.02, 0.0, 0.0))
+
+
+def spread(values):
+    return {"rounds": [round(v, 4) for v in values], "median": round(float(np.median(values)), 4), "spread": round(max(values) - min(values), 4)}
+
+
+def kernels_splat(reps):
+    """memset + k_depth_register (off) or k_depth_register_splat (on) + k_zbuffer_to_disparity on F half-size 16UC1 messages"""
+    import torch
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.pipeline import Context
-    m = synth.make_ego_images(W, H, seed=1, frames=2)
+    ctx = Context(W, H, max_frames=F)
+    cam = synth.make_camera(W, H)
+    ctx.set_camera(cam)
+    ctx.set_depth_registration(half_size_registration(capi, cam))
+    out = torch.empty((F, H, W), dtype=torch.float32, device=ctx.device)
+    rng = np.random.default_rng(0)
+    mm = torch.from_numpy(rng.integers(0, 8000, size=(F, H // 2, W // 2)).astype(np.uint16).view(np.int16)).to(ctx.device)
+    lay = capi.depth_layout("16UC1", W // 2, H // 2)
+    ms = {0: [], 1: []}
+    for _ in range(ROUNDS):
+        for on in (0, 1):
+            ctx.set_depth_splat(on)
+            ms[on].append(timed(torch, lambda: ctx.lib.mod_depth_to_disparity_dev(ctx.h, F, mm.data_ptr(), C.byref(lay), out.data_ptr()), reps))
+    valid = {}
+    for on in (0, 1):
+        ctx.set_depth_splat(on)
+        assert ctx.lib.mod_depth_to_disparity_dev(ctx.h, 1, mm.data_ptr(), C.byref(lay), out.data_ptr()) == 0
+        ctx.synchronize()
+        valid[on] = round(float((out[0] >= 0).float().mean().item()), 4)
+    for on in (0, 1):
+        print(json.dumps({"what": "registered path, half-size depth message", "splat": on, "encoding": "16UC1", "W": W, "H": H, "frames": F,
+                          "ms_per_call": spread(ms[on]), "ms_per_frame_median": round(float(np.median(ms[on])) / F, 5),
+                          "valid_share_of_frame_0": valid[on]}), flush=True)
+    ctx.close()
+
+
+@functools.lru_cache(maxsize=None)
+def ego_images():
+    from moving_object_detector_amd import synth
+    return synth.make_ego_images(W, H, seed=1, frames=2)
+
+
+def stream_fps(reps, splat=None):
+    """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on"""
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    m = ego_images()
     ctx = Context(W, H, max_frames=1)
     cam = synth.make_camera(W, H)
     cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
     ctx.set_camera(cam)
     ctx.set_params(synth.Params())
     ctx.set_image_layout(capi.image_layout("bgr8", W, H))
+    if splat is not None:
+        ctx.set_depth_registration(half_size_registration(capi, cam))
+        ctx.set_depth_layout(capi.depth_layout("16UC1", W // 2, H // 2))
+        ctx.set_depth_splat(splat)
     fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
     fp, ep = capi.flow_params(), capi.ego_params()
     pins = []
     for k in (0, 1):
         bgr = np.ascontiguousarray(np.repeat(m[f"left{k}"][..., None], 3, axis=2))
         mm = np.rint(1000.0 * fT / m[f"disparity{k}"].astype(np.float64)).astype(np.uint16)
+        if splat is not None:
+            mm = np.ascontiguousarray(mm[::2, ::2])
         for a in (bgr, mm):
             p = C.c_void_p()
             assert ctx.lib.mod_host_malloc(ctx.h, a.nbytes, C.byref(p)) == 0
@@ -103,7 +164,7 @@ def stream_fps(reps):
 
     for i in range(10):
         step(i)
-    frames = max(20, reps)
+    frames = max(20, reps) if splat is None else max(300, reps)   # the alternating rounds want a window of a good half second
     t0 = time.perf_counter()
     for i in range(10, 10 + frames):
         step(i)
@@ -117,7 +178,18 @@ def stream_fps(reps):
 
 
 def main():
-    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 50
+    args = [a for a in sys.argv[1:] if a != "--splat"]
+    reps = int(args[0]) if args else 50
+    if "--splat" in sys.argv[1:]:
+        kernels_splat(reps)
+        fps = {0: [], 1: []}
+        for _ in range(ROUNDS):
+            for on in (0, 1):
+                fps[on].append(stream_fps(reps, on))
+        for on in (0, 1):
+            print(json.dumps({"what": "mod_submit_depth_host, half-size registered depth message", "splat": on, "image": "bgr8", "depth": "16UC1",
+                              "kind": "odometry", "W": W, "H": H, "frames_per_s": spread(fps[on])}), flush=True)
+        return
     kernels(reps)
     print(json.dumps({"what": "mod_submit_depth_host", "image": "bgr8", "depth": "16UC1", "kind": "odometry", "W": W, "H": H,
                       "frames_per_s": round(stream_fps(reps), 1)}), flush=True)
