@@ -1,6 +1,11 @@
 """GPU: scene-flow stage against the oracle on hostile inputs — random cameras with non-zero Tx/Ty, unnormalised
 quaternions, negative / tiny dt, disparities spanning denormals..inf, flows spanning 0..1e30, NaN everywhere; also
-transforms with huge entries that defeat the "certainly finite" shortcut of the second rigid transform."""
+transforms with huge entries.
+
+The flows here are random and unrelated to the static flow, so under the random poses no pixel that gets a velocity is static: this test
+does not exercise the "certainly finite" shortcut of stage 2a (FrameConst.pad[0]) — neither its firing at hostile coordinates nor its
+declining beyond the bound — and its batches are single frames of the inline kernels.  tests/test_gpu_sceneflow_variants.py covers both: static and threshold-tied pixels at tame and
+extreme coordinates, batches of differing frames, every kernel variant."""
 import numpy as np
 import pytest
 
@@ -41,7 +46,7 @@ def test_hostile_inputs(oracle, seed):
     t = rng.standard_normal(3) * rng.choice([0.1, 10.0])
     dt = float(rng.choice([0.1, 1.0 / 15.0, 1e-9, -0.1, 3.0]))
     if seed == 4:
-        q = q * 1e18                                                  # rotation entries ~1e36: the finite-bound shortcut must decline
+        q = q * 1e18                                                  # rotation entries ~1e36 (no pixel is static here: see the docstring)
     if seed == 5:
         t = np.array([np.inf, 0.0, np.nan])
     # the kernel's division shortcuts (csrc/exact_div.h) and their fall-backs
