@@ -1,7 +1,7 @@
 // host_api.hip — the C ABI's host-pointer entry points: the single-frame *_host calls, which stage one frame through device buffers
-// of the context, and the submit / collect stream with its pipe of slots, copy streams and ring of planes.  Host-side only.
+// of the context, and the submit / collect stream with its pipe of slots, copy streams and ring of planes.  Host-side only; how a
+// host image becomes grey on the device is host_images.hip's (ImageIngest).
 #include "mod_context.h"
-#include "bayer_region.h"
 
 #include <algorithm>
 #include <cstring>
@@ -63,99 +63,21 @@ static int fetch_cluster_results(ModContext *c, int32_t *labels, ModObject *obje
   return objects && ncopy > 0 ? download_sync(c, objects, h.objects, sizeof(ModObject) * ncopy) : MOD_OK;
 }
 
-// ---- host images (mod_set_image_layout) --------------------------------------------------------------------------------
-// The window of one host image to the device on stream s, as packed rows of W * channels bytes: one copy when the window's rows are
-// contiguous in the message (the default layout: the whole mono8 image), else a 2D copy.  Only the window crosses PCIe.
-static hipError_t copy_window(const ModImageLayout &l, int W, int H, const uint8_t *src, uint8_t *dst, hipStream_t s) {
-  const int C = image_channels(l.encoding);
-  const size_t row = (size_t)W * C;
-  const uint8_t *o = src + (size_t)l.y0 * l.step + (size_t)l.x0 * C;
-  if ((size_t)l.step == row) return hipMemcpyAsync(dst, o, row * H, hipMemcpyHostToDevice, s);
-  return hipMemcpy2DAsync(dst, row, o, (size_t)l.step, row, (size_t)H, hipMemcpyHostToDevice, s);
-}
-
-// bytes that hold two staged windows of any encoding: 4 bytes a pixel, or two Bayer regions (bayer_region.h: <= 6 N + 12 bytes while W H <= N)
-static size_t window_stage_bytes(const ModContext *c) { return 8 * c->maxN + 16; }
-// the region of one host message (src: the message, or its pane) to dst on stream s, rows packed
-static hipError_t copy_bayer_region(const ModImageLayout &l, const BayerRegion &g, const uint8_t *src, uint8_t *dst, hipStream_t s) {
-  return hipMemcpy2DAsync(dst, (size_t)g.rw, src + (size_t)g.ay * l.step + g.ax, (size_t)l.step, (size_t)g.rw, (size_t)g.rh, hipMemcpyHostToDevice, s);
-}
-// ... and the window's grey from it on the context's stream; right_pane: the message the region came from is a right pane
-static void bayer_region_to_mono(ModContext *c, const ModImageLayout &l, const BayerRegion &g, bool right_pane, const uint8_t *staged, uint8_t *grey) {
-  launch_bayer_to_mono(c->dc.W, c->dc.H, 1, staged, 0, g.rw, g.rw, g.rh, l.x0 - g.ax, l.y0 - g.ay,
-                       bayer_phase(l.encoding, g.ax + (right_pane ? l.width : 0), g.ay), grey, c->stream);
-}
-
-// side by side (mod_set_side_by_side): `right` of a call that takes one message for both eyes must be NULL or that message
-static int check_one_message(ModContext *c, const uint8_t *left, const uint8_t *right) {
-  return right && right != left ? fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side: right must be NULL or equal to left") : MOD_OK;
-}
-
-// Two whole raw messages to `raw` on stream s, one after the other: a rectified window needs source pixels outside the window.
-// panes: img0 is ONE message that holds both eyes side by side; it crosses once.  img1 null (an RGB-D frame): one message, one eye.
-static int copy_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *img0, const uint8_t *img1, uint8_t *raw,
-                         hipStream_t s) {
-  const size_t M = (size_t)l.step * l.height;
-  HIP_TRY(c, hipMemcpyAsync(raw, img0, M, hipMemcpyHostToDevice, s));
-  if (!panes && img1) HIP_TRY(c, hipMemcpyAsync(raw + M, img1, M, hipMemcpyHostToDevice, s));
-  return MOD_OK;
-}
-// ... and k_rectify from there on the context's stream, each message (or each pane of the one message) with the map of its eye.  A
-// pane is a message of the pane's width that starts width * channels bytes into the row and ends with the message's last byte.
-// Bayer messages are demosaiced whole into `bayer` first (room for two grey planes of the message's, or pane's, size).  grey1 null:
-// the first message alone.
-static int rectify_messages(ModContext *c, const ModImageLayout &l, bool panes, const uint8_t *raw, int eye1, uint8_t *bayer, uint8_t *grey0,
-                            uint8_t *grey1) {
-  const size_t M = (size_t)l.step * l.height, at1 = panes ? pane_offset(l, MOD_EYE_RIGHT) : M;
-  if (is_bayer(l.encoding)) {
-    if (int rc = rectify_bayer(c, l, 1, raw, MOD_EYE_LEFT, bayer, c->rect.map[MOD_EYE_LEFT].q, grey0)) return rc;
-    return !grey1 ? MOD_OK : rectify_bayer(c, l, 1, raw + at1, panes ? MOD_EYE_RIGHT : MOD_EYE_LEFT, bayer + (size_t)l.width * l.height, c->rect.map[eye1].q, grey1);
-  }
-  launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw, M, M, l.step, l.width, l.height, c->rect.map[MOD_EYE_LEFT].q, grey0, c->stream);
-  if (grey1) launch_rectify(l.encoding, c->dc.W, c->dc.H, 1, raw + at1, M, panes ? M - at1 : M, l.step, l.width, l.height, c->rect.map[eye1].q, grey1,
-                            c->stream);
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
-}
-
-// The two images of a synchronous *_host call, grey on the device behind the context's stream: mono8 straight into the flow
-// staging slot (its 8 N bytes hold both), colour windows into that slot and k_to_mono from there into the cloud staging.  With a
-// rectification set: the whole messages into the raw staging, and k_rectify from there into the cloud staging (img0 with the left
-// map, img1 with the map of eye1).  panes: img0 holds both eyes side by side and img1 is not read.
+// The two images of a synchronous *_host call, grey on the device behind the context's stream (ingest_copy, ingest_to_grey): mono8
+// straight into the flow staging slot (its 8 N bytes hold both), else staged in that slot, or with a rectification set in the raw
+// staging, and grey in the cloud staging (img0 with the left map, img1 with the map of eye1).  panes: img0 holds both eyes.
 static int upload_pair(ModContext *c, const uint8_t *img0, const uint8_t *img1, int eye1, bool panes, uint8_t **grey) {
-  ModImageLayout l;
-  if (int rc = current_layout(c, &l)) return rc;
-  if (c->rect.on) {
-    int rc;
-    if ((rc = ensure_rectify_map(c, MOD_EYE_LEFT, l)) || (rc = ensure_rectify_map(c, eye1, l)) || (rc = ensure_raw_stage(c, c->staging.raw, l)) ||
-        (rc = is_bayer(l.encoding) ? ensure_stage_bytes(c, c->staging.bayer_grey, 2 * (size_t)l.width * l.height) : MOD_OK) ||
-        (rc = copy_messages(c, l, panes, img0, img1, c->staging.raw.buf, c->stream)))
-      return rc;
-    *grey = static_cast<uint8_t *>(c->staging.aos.get());
-    return rectify_messages(c, l, panes, c->staging.raw.buf, eye1, c->staging.bayer_grey.buf, *grey, *grey + pixels(c));
-  }
-  if (panes) img1 = img0 + pane_offset(l, MOD_EYE_RIGHT);   // one window from each pane
-  const int W = c->dc.W, H = c->dc.H;
-  uint8_t *slot = reinterpret_cast<uint8_t *>(c->staging.flow.get());
-  if (is_bayer(l.encoding)) {      // the two regions into the slot, their windows' grey into the cloud staging
-    const BayerRegion g = bayer_region(l.width, l.height, l.x0, l.y0, W, H);
-    uint8_t *slot1 = slot + (size_t)g.rw * g.rh;
-    HIP_TRY(c, copy_bayer_region(l, g, img0, slot, c->stream));
-    HIP_TRY(c, copy_bayer_region(l, g, img1, slot1, c->stream));
-    *grey = static_cast<uint8_t *>(c->staging.aos.get());
-    bayer_region_to_mono(c, l, g, false, slot, *grey);
-    bayer_region_to_mono(c, l, g, panes, slot1, *grey + pixels(c));
-    HIP_TRY(c, hipGetLastError());
-    return MOD_OK;
-  }
-  const size_t P = pixels(c) * image_channels(l.encoding);
-  HIP_TRY(c, copy_window(l, W, H, img0, slot, c->stream));
-  HIP_TRY(c, copy_window(l, W, H, img1, slot + P, c->stream));
-  if (l.encoding == MOD_ENCODING_MONO8) { *grey = slot; return MOD_OK; }
-  *grey = static_cast<uint8_t *>(c->staging.aos.get());
-  launch_to_mono(l.encoding, W, H, 2, slot, P, (int)(P / H), 0, 0, *grey, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
+  ModContext::HostStaging &h = c->staging;
+  ImageIngest in{};
+  in.rectify = c->rect.on; in.panes = panes; in.eye1 = eye1; in.batch2 = true;
+  in.stage = reinterpret_cast<uint8_t *>(h.flow.get()); in.raw = &h.raw; in.bayer_grey = &h.bayer_grey;
+  if (int rc = current_layout(c, &in.lay)) return rc;
+  for (int eye : {(int)MOD_EYE_LEFT, eye1}) if (int rc = in.rectify ? ensure_rectify_map(c, eye, in.lay) : MOD_OK) return rc;
+  if (int rc = in.rectify ? ensure_raw_stages(c, in) : MOD_OK) return rc;
+  in.grey0 = *grey = in.staged() ? static_cast<uint8_t *>(h.aos.get()) : in.stage;
+  in.grey1 = in.grey0 + pixels(c);
+  if (int rc = ingest_copy(c, in, img0, img1, c->stream)) return rc;
+  return ingest_to_grey(c, in);
 }
 
 // ---- host streaming: the pipe ------------------------------------------------------------------------------------------
@@ -251,13 +173,9 @@ struct StereoRequest {
 struct StereoFrame {
   Pipe::Slot &s;
   Pipe::RingPlane &now, &prev;
-  ModImageLayout lay;
-  uint8_t *left, *right;
-  bool rectify;                      // the images are raw messages: whole into the slot's raw staging, k_rectify from there
-  bool panes;                        // side by side at this submit: rq.left holds both eyes
+  ImageIngest img;                   // layout, rectification and side by side as they are at this submit; the slot's stages; grow_for: the grey images
   ModDepthLayout dlay;               // RGB-D: the depth message's layout at this submit, and then the staged copy's
   bool splat;                        // ... and mod_set_depth_splat's setting at this submit
-  bool colour() const { return lay.encoding != MOD_ENCODING_MONO8; }
 };
 
 // what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
@@ -298,12 +216,12 @@ static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
     if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage_bytes(c, f.dlay))) return rc;
     if (c->has_depth_reg) HIP_TRY(c, dalloc(f.s.zbuf, c->maxN));
   }
-  if (f.rectify) {
-    if (int rc = ensure_raw_stage(c, f.s.raw, f.lay)) return rc;
-    if (int rc = is_bayer(f.lay.encoding) ? ensure_stage_bytes(c, f.s.bayer_grey, 2 * (size_t)f.lay.width * f.lay.height) : MOD_OK) return rc;
-  } else if (f.colour()) HIP_TRY(c, dalloc(f.s.stage, window_stage_bytes(c)));
-  f.left = rq.estimates_flow() ? f.now.left.get() : f.s.img.get();
-  f.right = rq.rgbd ? nullptr : f.s.img.get() + pixels(c);
+  if (f.img.rectify) {
+    if (int rc = ensure_raw_stages(c, f.img)) return rc;
+  } else if (f.img.staged()) HIP_TRY(c, dalloc(f.s.stage, window_stage_bytes(c)));
+  f.img.stage = f.s.stage;
+  f.img.grey0 = rq.estimates_flow() ? f.now.left.get() : f.s.img.get();
+  f.img.grey1 = rq.rgbd ? nullptr : f.s.img.get() + pixels(c);
   return MOD_OK;
 }
 
@@ -318,60 +236,26 @@ static int upload_depth(ModContext *c, const StereoRequest &rq, StereoFrame &f) 
     return MOD_OK;
   }
   const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H;
-  const size_t row = (size_t)W * B;
-  const uint8_t *o = static_cast<const uint8_t *>(rq.depth) + (size_t)l.y0 * l.step + (size_t)l.x0 * B;
-  if ((size_t)l.step == row) HIP_TRY(c, hipMemcpyAsync(f.s.depth.buf, o, row * H, hipMemcpyHostToDevice, p.h2d));
-  else HIP_TRY(c, hipMemcpy2DAsync(f.s.depth.buf, row, o, (size_t)l.step, row, (size_t)H, hipMemcpyHostToDevice, p.h2d));
-  l.width = W; l.height = H; l.step = (int32_t)row; l.x0 = l.y0 = 0;
+  HIP_TRY(c, copy_window(rq.depth, l.step, l.x0, l.y0, B, W, H, f.s.depth.buf, p.h2d));
+  l.width = W; l.height = H; l.step = W * B; l.x0 = l.y0 = 0;
   return MOD_OK;
 }
 
+// The frame's images, grey on the device: the shared copies on the copy stream behind the fences of what they overwrite, with the
+// frame's other inputs; the shared kernels on the context's stream, which is behind every older reader of the grey images already
 static int upload_images(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   Pipe &p = c->pipe;
-  const int W = c->dc.W, H = c->dc.H;
-  const size_t P = pixels(c) * image_channels(f.lay.encoding);
-  if (f.rectify) {                  // image_proc's rectifier and cv_bridge's conversion on the GPU
-    HIP_TRY(c, f.s.stage_read.wait(p.h2d));
-    if (int rc = copy_messages(c, f.lay, f.panes, rq.left, rq.right, f.s.raw.buf, p.h2d)) return rc;
-    if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
-    if (int rc = rq.rgbd ? upload_depth(c, rq, f) : MOD_OK) return rc;
-    HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
-    HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
-    // the grey images are written on the context's stream, which is behind every older reader of them already
-    if (int rc = rectify_messages(c, f.lay, f.panes, f.s.raw.buf, MOD_EYE_RIGHT, f.s.bayer_grey.buf, f.left, f.right)) return rc;
-    HIP_TRY(c, f.s.stage_read.record(c->stream));
-    return MOD_OK;
-  }
-  if (!rq.rgbd) HIP_TRY(c, f.s.img_read.wait(p.h2d));
-  // colour grey is written on the context's stream, which is behind every older reader already: only a copy waits for left_read
-  if (rq.estimates_flow() && !f.colour()) HIP_TRY(c, f.now.left_read.wait(p.h2d));
-  if (f.colour()) HIP_TRY(c, f.s.stage_read.wait(p.h2d));
-  const uint8_t *right = f.panes ? rq.left + pane_offset(f.lay, MOD_EYE_RIGHT) : rq.right;   // one window from each pane
-  const bool bayer = is_bayer(f.lay.encoding);
-  const BayerRegion g = bayer ? bayer_region(f.lay.width, f.lay.height, f.lay.x0, f.lay.y0, W, H) : BayerRegion{};
-  uint8_t *stage1 = f.colour() ? f.s.stage.get() + (bayer ? (size_t)g.rw * g.rh : P) : nullptr;
-  if (bayer) {
-    HIP_TRY(c, copy_bayer_region(f.lay, g, rq.left, f.s.stage, p.h2d));
-    if (right) HIP_TRY(c, copy_bayer_region(f.lay, g, right, stage1, p.h2d));
-  } else {
-    HIP_TRY(c, copy_window(f.lay, W, H, rq.left, f.colour() ? f.s.stage.get() : f.left, p.h2d));
-    if (right) HIP_TRY(c, copy_window(f.lay, W, H, right, f.colour() ? stage1 : f.right, p.h2d));
-  }
+  const ImageIngest &in = f.img;
+  if (!in.rectify && !rq.rgbd) HIP_TRY(c, f.s.img_read.wait(p.h2d));
+  if (!in.staged() && rq.estimates_flow()) HIP_TRY(c, f.now.left_read.wait(p.h2d));   // only a copy into the left image waits for its readers
+  if (in.staged()) HIP_TRY(c, f.s.stage_read.wait(p.h2d));   // the copies land in the slot's stage (raw messages, windows, regions)
+  if (int rc = ingest_copy(c, in, rq.left, rq.right, p.h2d)) return rc;
   if (rq.flow) HIP_TRY(c, hipMemcpyAsync(f.s.flow, rq.flow, 8 * pixels(c), hipMemcpyHostToDevice, p.h2d));
   if (int rc = rq.rgbd ? upload_depth(c, rq, f) : MOD_OK) return rc;
   HIP_TRY(c, hipEventRecord(f.s.ev_in, p.h2d));
   HIP_TRY(c, hipStreamWaitEvent(c->stream, f.s.ev_in, 0));
-  if (bayer) {                      // image_proc's debayer and cv_bridge's conversion on the GPU
-    bayer_region_to_mono(c, f.lay, g, false, f.s.stage, f.left);
-    if (f.right) bayer_region_to_mono(c, f.lay, g, f.panes, stage1, f.right);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, f.s.stage_read.record(c->stream));
-  } else if (f.colour()) {          // cv_bridge::toCvCopy(..., MONO8) (:220-221) on the GPU
-    launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage, P, (int)(P / H), 0, 0, f.left, c->stream);
-    if (f.right) launch_to_mono(f.lay.encoding, W, H, 1, f.s.stage + P, P, (int)(P / H), 0, 0, f.right, c->stream);
-    HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, f.s.stage_read.record(c->stream));
-  }
+  if (int rc = ingest_to_grey(c, in)) return rc;
+  if (in.staged()) HIP_TRY(c, f.s.stage_read.record(c->stream));   // ... and kernels have read it
   return MOD_OK;
 }
 
@@ -384,7 +268,7 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
     if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.splat, f.s.zbuf, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.depth_read.record(c->stream));
   } else {
-    if (int rc = mod_sgm_compute_dev(c, 1, f.left, f.right, rq.sgm, f.now.disparity)) return rc;
+    if (int rc = mod_sgm_compute_dev(c, 1, f.img.grey0, f.img.grey1, rq.sgm, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.img_read.record(c->stream));
   }
   HIP_TRY(c, p.ring_written.record(c->stream));
@@ -416,7 +300,9 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   ModDepthLayout dlay{};
   int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, lay, nullptr, nullptr, c->rect.on, c->side_by_side, dlay, c->depth_splat};
+  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat};
+  f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
+  f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
   if ((rc = grow_for(c, rq, f)) || (rc = upload_images(c, rq, f)) || (rc = estimate(c, rq, f))) return rc;
   static const ModTransform kUnused = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};   // stands for the transform in HBM (never read)
   const ModFrameBatch in{1, 0, f.now.disparity, f.prev.disparity, f.s.flow, rq.odometry() ? &kUnused : rq.transform, &rq.dt};

@@ -1,5 +1,6 @@
 // mod_context.h — the context behind the C ABI and what its host-side files share (internal to libmod_sf.so, not installed):
-// mod_sf.hip (lifecycle, the batched scene-flow / cluster path), estimators.hip (SGM, flow, ego-motion), host_api.hip (*_host calls).
+// mod_sf.hip (lifecycle, the batched scene-flow / cluster path), estimators.hip (SGM, flow, ego-motion), host_images.hip (image and
+// depth layouts, rectification, the host images' way to grey), host_api.hip (*_host calls).
 #pragma once
 #include "../../include/mod_sf.h"
 #include "frame_const.h"
@@ -272,33 +273,53 @@ inline int construct_skip(bool flow, bool prev, bool transform, bool now) {
 
 // mod_sf.hip
 void refresh_devcam(ModContext *c);
-// the layout the host image entry points read (the set one, or mono8 packed W x H), checked against the camera
-int current_layout(ModContext *c, ModImageLayout *out);
-// panes: the message holds both eyes side by side (width is a pane's, step the whole row's)
-int check_layout(ModContext *c, const ModImageLayout &l, bool panes);
-// where the pane of `eye` starts in a row of a side-by-side message
-inline size_t pane_offset(const ModImageLayout &l, int eye) { return eye == MOD_EYE_RIGHT ? (size_t)l.width * image_channels(l.encoding) : 0; }
-// with a rectification set (the caller has checked that, and eye): the map of `eye` for the window of `l` is in c->rect.map[eye].q when this returns MOD_OK (built, behind
-// the context's stream, unless it is the cached one; refused while tickets are outstanding)
-int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l);
-// room for two raw messages of `l` in r; a buffer that has to grow is replaced once the context's streams have drained
-int ensure_raw_stage(ModContext *c, ModContext::RawStage &r, const ModImageLayout &l);
-int ensure_stage_bytes(ModContext *c, ModContext::RawStage &r, size_t need);   // ... for `need` bytes
-// Bayer under a rectification: `frames` whole messages at src (or their panes: src points at the pane, `pane` says which eye's) to
-// the grey planes `grey` [frames][height][width], then k_rectify from those as mono8 through `map` into mono; context's stream
-int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint8_t *src, int pane, uint8_t *grey, const int32_t *map,
-                  uint8_t *mono);
-// the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
-int current_depth_layout(ModContext *c, ModDepthLayout *out);
-// `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,
-// or with a registration in force the scatter through zbuf [frames][W H]
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, uint32_t *zbuf, float *disparity);
 int begin_cluster_scratch(ModContext *c);
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                 const ModClusterOut *out);
 // the scene-flow stage of the host entry points: their SoA planes are internal staging that no caller sees (the cloud leaves as
 // 32-byte records straight from the kernel's registers), so the x and y planes are not written at all
 int scene_flow_staged(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *out);
+
+// host_images.hip
+// the layout the host image entry points read (the set one, or mono8 packed W x H), checked against the camera
+int current_layout(ModContext *c, ModImageLayout *out);
+// where the pane of `eye` starts in a row of a side-by-side message
+inline size_t pane_offset(const ModImageLayout &l, int eye) { return eye == MOD_EYE_RIGHT ? (size_t)l.width * image_channels(l.encoding) : 0; }
+// side by side (mod_set_side_by_side): `right` of a call that takes one message for both eyes must be NULL or that message
+int check_one_message(ModContext *c, const uint8_t *left, const uint8_t *right);
+// with a rectification set (the caller has checked that, and eye): the map of `eye` for the window of `l` is in c->rect.map[eye].q when this returns MOD_OK (built, behind
+// the context's stream, unless it is the cached one; refused while tickets are outstanding)
+int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l);
+// room for `need` bytes in r; a buffer that has to grow is replaced once the context's streams have drained
+int ensure_stage_bytes(ModContext *c, ModContext::RawStage &r, size_t need);
+// the W x H window at (x0, y0) of a host image of bpp bytes a pixel to dst on stream s, as packed rows of W * bpp bytes: only the window crosses PCIe
+hipError_t copy_window(const void *src, int32_t step, int32_t x0, int32_t y0, int bpp, int W, int H, void *dst, hipStream_t s);
+size_t window_stage_bytes(const ModContext *c);   // what ImageIngest::stage must hold
+// The one way of host images to grey, in two halves that a caller runs in order.  Where one call's / one frame's images go:
+struct ImageIngest {
+  ModImageLayout lay;
+  bool rectify, panes;              // a rectification is set; img0 holds both eyes side by side (img1 is not read)
+  int eye1;                         // rectifying: the map of the second image
+  uint8_t *stage;                   // colour windows / Bayer regions as they arrive (unused for mono8 and when rectifying)
+  ModContext::RawStage *raw, *bayer_grey;   // rectifying: the whole messages, and the demosaiced planes of Bayer ones (ensure_raw_stages)
+  uint8_t *grey0, *grey1;           // the results; mono8 windows are copied straight into them.  grey1 null: one image (RGB-D)
+  // the caller's choice: the two colour windows become grey in ONE k_to_mono launch of two frames, not two launches of one.  It needs
+  // grey1 == grey0 + W H (the staged windows are a window's bytes apart anyway); the synchronous calls ask for it, the stream never does
+  bool batch2;
+  // the images pass through a stage and kernels make the grey images (false: mono8 windows, copied straight into grey0 / grey1)
+  bool staged() const { return rectify || lay.encoding != MOD_ENCODING_MONO8; }
+};
+// rectifying: room for two raw messages of in.lay in *in.raw and, when they are Bayer mosaics, for their two grey planes in *in.bayer_grey
+int ensure_raw_stages(ModContext *c, const ImageIngest &in);
+// the copies, on copy_stream: whole messages when rectifying, else Bayer regions / mono8 windows / colour windows
+int ingest_copy(ModContext *c, const ImageIngest &in, const uint8_t *img0, const uint8_t *img1, hipStream_t copy_stream);
+// the kernels, on the context's stream: k_rectify (behind k_bayer_to_mono), k_bayer_to_mono, k_to_mono; none unless in.staged()
+int ingest_to_grey(ModContext *c, const ImageIngest &in);
+// the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
+int current_depth_layout(ModContext *c, ModDepthLayout *out);
+// `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,
+// or with a registration in force the scatter through zbuf [frames][W H]
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, uint32_t *zbuf, float *disparity);
 
 // estimators.hip
 int check_sgm_params(ModContext *c, const ModSgmParams *p);

@@ -1,6 +1,6 @@
-// mod_sf.hip — C ABI (include/mod_sf.h) over the gfx950 kernels: context lifecycle and configuration, the batched scene-flow /
+// mod_sf.hip — C ABI (include/mod_sf.h) over the gfx950 kernels: context lifecycle, camera and parameters, the batched scene-flow /
 // cluster / process path, parameter folding, stage timers, memory helpers.  Host-side only; the kernels live in sceneflow.hip and
-// the clusterer's ccl_*.hip / cluster_*.hip, the estimators' entry points in estimators.hip, the host-pointer calls in host_api.hip.
+// the clusterer's ccl_*.hip / cluster_*.hip, the estimators in estimators.hip, image input in host_images.hip, the *_host calls in host_api.hip.
 #include "mod_context.h"
 #include "exact_div.h"
 #include "mod_sf_debug.h"
@@ -249,115 +249,6 @@ int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPl
 
 }  // namespace
 
-int check_layout(ModContext *c, const ModImageLayout &l, bool panes) {
-  const int C = image_channels(l.encoding);
-  if (!C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown image encoding");
-  if (l.width < 1 || l.height < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "image size must be positive");
-  if (is_bayer(l.encoding) && (l.width < 3 || l.height < 3))
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "a Bayer image must be at least 3 x 3 (a pixel of its frame copies an interior one)");
-  if ((int64_t)l.step < (int64_t)l.width * C) return fail(c, MOD_ERR_INVALID_ARGUMENT, "step is smaller than width * channels");
-  if (panes && (int64_t)l.step < 2 * (int64_t)l.width * C)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side: step is smaller than 2 * width * channels (width is one eye's)");
-  if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the image");
-  return MOD_OK;
-}
-
-int current_layout(ModContext *c, ModImageLayout *out) {
-  *out = c->has_layout ? c->layout : ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};
-  if (!c->has_layout && !c->side_by_side) return MOD_OK;
-  return check_layout(c, *out, c->side_by_side);   // the camera may have changed since the layout was set
-}
-
-// (callers have checked that a rectification is set and that eye is one of the two)
-int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l) {
-  const ModRectifyCamera &cam = c->rect.cam[eye];
-  if (l.width != cam.width || l.height != cam.height)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the image layout's width / height differ from the rectification's");
-  ModContext::Rectify::Map &m = c->rect.map[eye];
-  const int W = c->dc.W, H = c->dc.H;
-  if (m.valid && m.width == l.width && m.height == l.height && m.x0 == l.x0 && m.y0 == l.y0 && m.W == W && m.H == H) return MOD_OK;
-  if (c->pipe.in_flight > 0)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the rectification map must be rebuilt while frames are in flight: collect every ticket first");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // kernels of calls and of frames that ended at a guard may still read the old map
-  HIP_TRY(c, dalloc(m.q, 2 * c->maxN));
-  m.valid = false;
-  std::vector<int32_t> host(2 * (size_t)W * H);
-  build_rectify_map(cam, l.x0, l.y0, W, H, host.data());
-  HIP_TRY(c, hipMemcpyAsync(m.q, host.data(), sizeof(int32_t) * host.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // `host` is stack-owned
-  m.width = l.width; m.height = l.height; m.x0 = l.x0; m.y0 = l.y0; m.W = W; m.H = H;
-  m.valid = true;
-  return MOD_OK;
-}
-
-int ensure_raw_stage(ModContext *c, ModContext::RawStage &r, const ModImageLayout &l) {
-  return ensure_stage_bytes(c, r, 2 * (size_t)l.step * l.height);
-}
-
-int ensure_stage_bytes(ModContext *c, ModContext::RawStage &r, size_t need) {
-  if (r.bytes >= need) return MOD_OK;
-  for (hipStream_t q : {c->stream, (hipStream_t)c->pipe.h2d}) if (q) HIP_TRY(c, hipStreamSynchronize(q));
-  r.buf.reset(); r.bytes = 0;
-  HIP_TRY(c, dalloc(r.buf, need));
-  r.bytes = need;
-  return MOD_OK;
-}
-
-int rectify_bayer(ModContext *c, const ModImageLayout &l, int frames, const uint8_t *src, int pane, uint8_t *grey, const int32_t *map,
-                  uint8_t *mono) {
-  const size_t G = (size_t)l.width * l.height;
-  launch_bayer_to_mono(l.width, l.height, frames, src, (size_t)l.step * l.height, l.step, l.width, l.height, 0, 0,
-                       bayer_phase(l.encoding, pane == MOD_EYE_RIGHT ? l.width : 0, 0), grey, c->stream);
-  launch_rectify(MOD_ENCODING_MONO8, c->dc.W, c->dc.H, frames, grey, G, G, l.width, l.width, l.height, map, mono, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
-}
-
-// registered: a registration is in force (the whole message is scattered: no window, any message size)
-static int check_depth_layout(ModContext *c, const ModDepthLayout &l, bool registered) {
-  const int B = depth_bytes(l.encoding);
-  if (!B) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown depth encoding");
-  if (l.width < 1 || l.height < 1 || l.width > MOD_MAX_WIDTH || l.height > MOD_MAX_WIDTH)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: width and height must be in 1..MOD_MAX_WIDTH");
-  if ((int64_t)l.step < (int64_t)l.width * B || l.step % B) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: step must be a multiple of the sample size and >= width * sample size");
-  if ((int64_t)l.step * l.height > INT32_MAX) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: step * height must be below 2^31");
-  if (!std::isfinite(l.unit) || l.unit < 0.0f) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: unit must be 0 (the REP 118 default) or finite and positive");
-  if (registered) {
-    if (l.x0 || l.y0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: x0 and y0 must be 0 while a depth registration is set (the whole message is registered)");
-  } else if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height) {
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the depth image");
-  }
-  return MOD_OK;
-}
-
-static ModDepthLayout default_depth_layout(const ModContext *c) { return ModDepthLayout{MOD_DEPTH_16UC1, c->dc.W, c->dc.H, 2 * c->dc.W, 0, 0, 0.0f}; }
-
-int current_depth_layout(ModContext *c, ModDepthLayout *out) {
-  *out = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
-  return check_depth_layout(c, *out, c->has_depth_reg);   // the camera or the registration may have changed since the layout was set
-}
-
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, uint32_t *zbuf, float *disparity) {
-  const float unit = l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f;
-  const float invalid = c->dc.dmin - 1.0f;
-  if (c->has_depth_reg) {
-    const ModDepthRegistration &r = c->depth_reg;
-    DepthRegArgs g{};
-    g.fxd = r.fx; g.fyd = r.fy; g.cxd = r.cx; g.cyd = r.cy;
-    for (int i = 0; i < 9; i++) g.R[i] = r.R[i];
-    for (int i = 0; i < 3; i++) g.t[i] = r.t[i];
-    g.fx = c->cam.fx; g.fy = c->cam.fy; g.cx = c->cam.cx; g.cy = c->cam.cy; g.Tx = c->cam.Tx; g.Ty = c->cam.Ty;
-    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, unit, g, splat, c->dc.fT, invalid, zbuf,
-                                     disparity, c->stream));
-  } else {
-    launch_depth_to_disparity(l.encoding, c->dc.W, c->dc.H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, unit, c->dc.fT, invalid,
-                              disparity, c->stream);
-  }
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
-}
-
 void refresh_devcam(ModContext *c) {
   DevCam &d = c->dc;
   d.W = c->cam.width; d.H = c->cam.height;
@@ -556,191 +447,6 @@ int mod_get_camera(const ModContext *c, ModCamera *cam) {
 int mod_get_params(const ModContext *c, ModParams *p) {
   if (!c || !p || !c->has_prm) return MOD_ERR_NOT_CONFIGURED;
   *p = c->prm;
-  return MOD_OK;
-}
-
-int mod_set_image_layout(ModContext *c, const ModImageLayout *l) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
-  const ModImageLayout packed{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};   // (holds no two panes: refused while side by side)
-  int rc = check_layout(c, l ? *l : packed, c->side_by_side);
-  if (rc) return rc;
-  if (l) c->layout = *l;
-  c->has_layout = l != nullptr;
-  return MOD_OK;
-}
-
-int mod_set_side_by_side(ModContext *c, int32_t on) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (on != 0 && on != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "side by side must be 0 or 1");
-  if (on && c->has_cam) {           // the layout in force must hold two panes (without a camera there is none yet: checked at call time)
-    const ModImageLayout l = c->has_layout ? c->layout : ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};
-    if (int rc = check_layout(c, l, true)) return rc;
-  }
-  c->side_by_side = on != 0;
-  return MOD_OK;
-}
-
-int mod_get_side_by_side(const ModContext *c, int32_t *on) {
-  if (!c || !on) return MOD_ERR_INVALID_ARGUMENT;
-  *on = c->side_by_side;
-  return MOD_OK;
-}
-
-int mod_get_image_layout(const ModContext *c, ModImageLayout *l) {
-  if (!c || !l) return MOD_ERR_INVALID_ARGUMENT;
-  if (!c->has_cam) return MOD_ERR_NOT_CONFIGURED;
-  *l = c->has_layout ? c->layout : ModImageLayout{MOD_ENCODING_MONO8, c->dc.W, c->dc.H, c->dc.W, 0, 0};
-  return MOD_OK;
-}
-
-int mod_image_to_mono_dev(ModContext *c, int32_t frames, const uint8_t *src, const ModImageLayout *layout, uint8_t *mono) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
-  if (frames < 1 || frames > 65535) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be in 1..65535");
-  if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
-  if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
-  ModImageLayout l;
-  int rc = layout ? check_layout(c, *layout, c->side_by_side) : current_layout(c, &l);
-  if (rc) return rc;
-  if (layout) l = *layout;
-  if (is_bayer(l.encoding))        // the region is the message (side by side: the pane src points at, with the pattern as it lies there)
-    launch_bayer_to_mono(c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.width, l.height, l.x0, l.y0,
-                         bayer_phase(l.encoding, 0, 0), mono, c->stream);
-  else
-    launch_to_mono(l.encoding, c->dc.W, c->dc.H, frames, src, (size_t)l.step * l.height, l.step, l.x0, l.y0, mono, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
-}
-
-int mod_set_rectification(ModContext *c, const ModRectifyCamera *left, const ModRectifyCamera *right) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (!left != !right) return fail(c, MOD_ERR_INVALID_ARGUMENT, "rectification: both eyes or neither");
-  for (const ModRectifyCamera *cam : {left, right})
-    if (const char *what = cam ? check_rectify_camera(*cam) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, what);
-  if (c->pipe.in_flight > 0)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the rectification cannot change while frames are in flight: collect every ticket first");
-  c->rect.on = left != nullptr;
-  if (left) { c->rect.cam[MOD_EYE_LEFT] = *left; c->rect.cam[MOD_EYE_RIGHT] = *right; }
-  for (ModContext::Rectify::Map &m : c->rect.map) m.valid = false;   // rebuilt at the next use, behind the context's stream
-  return MOD_OK;
-}
-
-int mod_get_rectification(const ModContext *c, ModRectifyCamera *left, ModRectifyCamera *right, int32_t *enabled) {
-  if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
-  *enabled = c->rect.on;
-  if (c->rect.on && left) *left = c->rect.cam[MOD_EYE_LEFT];
-  if (c->rect.on && right) *right = c->rect.cam[MOD_EYE_RIGHT];
-  return MOD_OK;
-}
-
-// the layout a rectifying call works on (the given one, or the context's) and the map of `eye` for its window
-static int rectify_setup(ModContext *c, const ModImageLayout *layout, int32_t eye, ModImageLayout *l) {
-  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
-  if (eye != MOD_EYE_LEFT && eye != MOD_EYE_RIGHT) return fail(c, MOD_ERR_INVALID_ARGUMENT, "eye must be MOD_EYE_LEFT or MOD_EYE_RIGHT");
-  if (!c->rect.on) return fail(c, MOD_ERR_NOT_CONFIGURED, "no rectification is set");
-  int rc = layout ? check_layout(c, *layout, c->side_by_side) : current_layout(c, l);
-  if (rc) return rc;
-  if (layout) *l = *layout;
-  return ensure_rectify_map(c, eye, *l);
-}
-
-int mod_rectify_dev(ModContext *c, int32_t frames, const uint8_t *src, const ModImageLayout *layout, int32_t eye, uint8_t *mono) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (frames < 1 || frames > 65535) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be in 1..65535");
-  ModImageLayout l;
-  if (int rc = rectify_setup(c, layout, eye, &l)) return rc;
-  if (!src) return MOD_SKIP_NO_DISPARITY_NOW;
-  if (!mono) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey planes");
-  const size_t M = (size_t)l.step * l.height, pane = c->side_by_side ? pane_offset(l, eye) : 0;   // side by side: eye selects the pane too
-  if (is_bayer(l.encoding)) {      // debayer, then rectify: the whole messages (or panes) to grey planes of the context's, k_rectify from those
-    if (int rc = ensure_stage_bytes(c, c->bayer_grey, (size_t)frames * l.width * l.height)) return rc;
-    return rectify_bayer(c, l, frames, src + pane, c->side_by_side ? eye : MOD_EYE_LEFT, c->bayer_grey.buf, c->rect.map[eye].q, mono);
-  }
-  launch_rectify(l.encoding, c->dc.W, c->dc.H, frames, src + pane, M, M - pane, l.step, l.width, l.height, c->rect.map[eye].q, mono, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
-}
-
-int mod_rectify_map_host(ModContext *c, int32_t eye, const ModImageLayout *layout, int32_t *map_qxqy) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (!map_qxqy) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null map");
-  ModImageLayout l;
-  if (int rc = rectify_setup(c, layout, eye, &l)) return rc;
-  HIP_TRY(c, hipMemcpyAsync(map_qxqy, c->rect.map[eye].q, sizeof(int32_t) * 2 * (size_t)c->dc.W * c->dc.H, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  return MOD_OK;
-}
-
-int mod_set_depth_layout(ModContext *c, const ModDepthLayout *l) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
-  if (int rc = check_depth_layout(c, l ? *l : default_depth_layout(c), c->has_depth_reg)) return rc;
-  if (l) c->depth_layout = *l;
-  c->has_depth_layout = l != nullptr;
-  return MOD_OK;
-}
-
-int mod_get_depth_layout(const ModContext *c, ModDepthLayout *l) {
-  if (!c || !l) return MOD_ERR_INVALID_ARGUMENT;
-  if (!c->has_cam) return MOD_ERR_NOT_CONFIGURED;
-  *l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
-  return MOD_OK;
-}
-
-int mod_set_depth_registration(ModContext *c, const ModDepthRegistration *r) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (r) {
-    for (const double v : {r->fx, r->fy, r->cx, r->cy}) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite intrinsics");
-    for (const double v : r->R) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite entry in R");
-    for (const double v : r->t) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite entry in t");
-    if (r->fx <= 0.0 || r->fy <= 0.0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: the focal lengths must be positive");
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
-        const double d = r->R[3 * i] * r->R[3 * j] + r->R[3 * i + 1] * r->R[3 * j + 1] + r->R[3 * i + 2] * r->R[3 * j + 2];
-        if (std::fabs(d - (i == j ? 1.0 : 0.0)) > 1e-6)
-          return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: R is not a rotation (R R^T differs from I by more than 1e-6)");
-      }
-    c->depth_reg = *r;
-  }
-  c->has_depth_reg = r != nullptr;
-  return MOD_OK;
-}
-
-int mod_get_depth_registration(const ModContext *c, ModDepthRegistration *r, int32_t *enabled) {
-  if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
-  *enabled = c->has_depth_reg;
-  if (c->has_depth_reg && r) *r = c->depth_reg;
-  return MOD_OK;
-}
-
-int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth, const ModDepthLayout *layout, float *disparity) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (!c->has_cam) return fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
-  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
-  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
-  ModDepthLayout l;
-  int rc = layout ? check_depth_layout(c, *layout, c->has_depth_reg) : current_depth_layout(c, &l);
-  if (rc) return rc;
-  if (layout) l = *layout;
-  if (!depth) return MOD_SKIP_NO_DISPARITY_NOW;
-  if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity planes");
-  if ((uintptr_t)depth % depth_bytes(l.encoding) || (uintptr_t)disparity % 4)
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth must be aligned to its sample size and disparity to 4 bytes");
-  if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
-  return run_depth_to_disparity(c, frames, depth, l, c->depth_splat, c->depth_zbuf, disparity);
-}
-
-int mod_set_depth_splat(ModContext *c, int32_t on) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (on != 0 && on != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth splat: on must be 0 or 1");
-  c->depth_splat = on != 0;
-  return MOD_OK;
-}
-
-int mod_get_depth_splat(const ModContext *c, int32_t *on) {
-  if (!c || !on) return MOD_ERR_INVALID_ARGUMENT;
-  *on = c->depth_splat;
   return MOD_OK;
 }
 
