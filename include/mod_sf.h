@@ -454,11 +454,13 @@ int  mod_get_side_by_side(const ModContext *ctx, int32_t *on);
  * context state like the image layout; off by default, and while off every call enqueues exactly what it did before.
  * A ModRectifyCamera is what the sensor_msgs/CameraInfo of the raw image carries: width, height (the raw message's size, which is also
  * the rectified image's, as image_proc makes it); K (fx = K[0], fy = K[4], cx = K[2], cy = K[5]; the skew K[1] must be 0);
- * D = k1 k2 p1 p2 k3 k4 k5 k6 (plumb_bob: the first five, the rest 0; rational_polynomial: all eight); R, the rectifying rotation;
+ * D = k1 k2 p1 p2 k3 k4 k5 k6 (plumb_bob: the first five, the rest 0; rational_polynomial: all eight; under
+ * MOD_DISTORTION_EQUIDISTANT, below: k1 k2 k3 k4, the rest 0); R, the rectifying rotation;
  * P (fx' = P[0], fy' = P[5], cx' = P[2], cy' = P[6]).  The context's W x H window at the layout's (x0, y0) is a window of the
  * RECTIFIED image (image_crop runs behind the rectifier); the P given to mod_set_camera stays the cropped one.
- * Map (f64 on the host, operations in this order, no contraction; tests/models/rectify_model.py restates it bit for bit), for window
- * pixel (u, v) with U = u + x0, V = v + y0:
+ * Map (f64, built on the GPU by k_rectify_map, one lane per entry, from IEEE + - * / sqrt and rint alone; operations in this order,
+ * no contraction; csrc/rectify_map.h is the one definition, for device and host, and tests/models/rectify_model.py restates it bit
+ * for bit), for window pixel (u, v) with U = u + x0, V = v + y0:
  *   x = (U - cx') / fx';  y = (V - cy') / fy'
  *   X = R[0]*x + R[3]*y + R[6];  Y = R[1]*x + R[4]*y + R[7];  Wd = R[2]*x + R[5]*y + R[8];  x = X / Wd;  y = Y / Wd
  *   x2 = x*x; y2 = y*y; r2 = x2 + y2; xy2 = 2.0*x*y
@@ -466,7 +468,20 @@ int  mod_get_side_by_side(const ModContext *ctx, int32_t *on);
  *   xd = x*kr + p1*xy2 + p2*(r2 + 2.0*x2);  yd = y*kr + p1*(r2 + 2.0*y2) + p2*xy2
  *   mx = fx*xd + cx;  my = fy*yd + cy;  qx = rint(mx * 32.0), qy = rint(my * 32.0)   (half to even)
  * clamped to [-2^24, 2^24], a non-finite value becomes -2^24: cv::initUndistortRectifyMap on cv::remap's 1/32-pixel grid (parity
- * with a particular OpenCV build is not claimed).  Sampling, all integers: ix = qx >> 5, ax = qx & 31 (the same for y); taps
+ * with a particular OpenCV build is not claimed).
+ * Under MOD_DISTORTION_EQUIDISTANT (mod_set_distortion_model; fisheye lenses, Kannala-Brandt, cv::fisheye, D = k1 k2 k3 k4) the lines
+ * from x2 to yd are replaced by (tests/models/fisheye_model.py restates it bit for bit):
+ *   if !(Wd > 0.0): qx = qy = -2^24                    (the ray is at or behind 90 degrees; cv::fisheye writes -inf there)
+ *   r = sqrt(x*x + y*y);  if !(r <= 1048576.0): qx = qy = -2^24                    (also NaN; never inside a real image)
+ *   th = atan_m(r);  t2 = th*th;  td = th * (1.0 + (((k4*t2 + k3)*t2 + k2)*t2 + k1)*t2)
+ *   sc = (r == 0.0) ? 1.0 : td / r;  mx = fx*(x*sc) + cx;  my = fy*(y*sc) + cy
+ * and quantised as above.  atan_m is the library's own arctangent, built from correctly rounded operations only, so that numpy, a host
+ * compiler and the GPU agree in every bit (libm's and the device library's atan are not correctly rounded):
+ *   t = r;  four times: t = t / (1.0 + sqrt(1.0 + t*t))                            (atan r = 16 atan t, t <= tan(pi/32))
+ *   u = t*t;  s = c11;  for k = 10 .. 0: s = s*u + ck,  ck = (k even ? 1.0 : -1.0) / (double)(2k + 1);  atan_m = 16.0 * (t*s)
+ * within 1.2e-15 absolute of the arctangent on [0, 2^20].  This is cv::fisheye::initUndistortRectifyMap's model on the same grid; bit
+ * parity with a particular OpenCV build is not claimed here either.  The Wd and r guards apply to the equidistant model only; the
+ * rational model's arithmetic is as it always was.  Sampling, all integers: ix = qx >> 5, ax = qx & 31 (the same for y); taps
  * p00 = (ix, iy), p01 = (ix+1, iy), p10 = (ix, iy+1), p11 = (ix+1, iy+1) of the raw message, a tap outside it reads 0 in every
  * channel; per channel top = (32-ax) p00 + ax p01, bot = (32-ax) p10 + ax p11, val = ((32-ay) top + ay bot + 512) >> 10; colour is
  * interpolated per channel and then converted to grey as above (image_proc rectifies the colour image, cv_bridge converts).
@@ -478,12 +493,20 @@ int  mod_get_side_by_side(const ModContext *ctx, int32_t *on);
  *   mod_rectify_dev        as mod_image_to_mono_dev, rectified with the map of `eye`; layout NULL = the context's
  *   mod_rectify_map_host   the map of `eye` for the window of `layout` (NULL = the context's): host int32 [H][W][2] (qx, qy)
  *                          Each eye holds ONE map.  Either of these two calls with a layout whose window differs from the one the
- *                          *_host calls and submits use replaces that eye's map: the next of those rebuilds it (a stream
- *                          synchronise, the f64 map on the host, one copy), and while tickets are outstanding such a call is
+ *                          *_host calls and submits use replaces that eye's map: the next of those rebuilds it (one short
+ *                          kernel on the context's stream, no wait), and while tickets are outstanding such a call is
  *                          refused.  Trace maps with the layout in force, or on a context of their own.
- * A map is built for the window in force (message size, x0, y0, W, H), cached, and rebuilt at the next use after any of those or the
- * calibration changed.  A map that a frame in flight reads is never overwritten: mod_set_rectification, and any call that would
- * rebuild a map, is refused (MOD_ERR_INVALID_ARGUMENT) while tickets are outstanding; otherwise they wait for the context's stream.
+ *   mod_set_distortion_model  MOD_DISTORTION_RATIONAL (the default) or MOD_DISTORTION_EQUIDISTANT: how D is read.  Context state
+ *                          like mod_set_side_by_side; it holds for both eyes (a stereo head has one lens type) and is read when a
+ *                          map is built.  It may be set before or after mod_set_rectification; whichever of the two calls comes
+ *                          second checks the pair: equidistant with a non-zero D[4..7] in either eye is
+ *                          MOD_ERR_INVALID_ARGUMENT, and so is any other value of `model`; the state stays as it was.  Changing
+ *                          it invalidates both cached maps, so it is refused while tickets are outstanding.
+ *   mod_get_distortion_model  the model in force
+ * A map is built for the window in force (message size, x0, y0, W, H) and the distortion model, cached, and rebuilt at the next use
+ * after any of those or the calibration changed.  A map that a frame in flight reads is never overwritten: mod_set_rectification,
+ * mod_set_distortion_model, and any call that would rebuild a map, are refused (MOD_ERR_INVALID_ARGUMENT) while tickets are
+ * outstanding; otherwise the rebuild is ordered on the context's stream behind every reader of the old map.
  * MOD_ERR_INVALID_ARGUMENT: non-finite entries; fx, fy, fx', fy' <= 0; K[1] != 0; width or height < 1 or > MOD_MAX_WIDTH; R with an
  * entry of R R^T - I above 1e-6 in magnitude (the setting stays as it was); an invalid eye; at call time a layout whose width /
  * height differ from the calibration's.  MOD_ERR_NOT_CONFIGURED: no camera, or (mod_rectify_dev, mod_rectify_map_host) no
@@ -501,6 +524,10 @@ int  mod_set_rectification(ModContext *ctx, const ModRectifyCamera *left, const 
 int  mod_get_rectification(const ModContext *ctx, ModRectifyCamera *left, ModRectifyCamera *right, int32_t *enabled);
 int  mod_rectify_dev(ModContext *ctx, int32_t frames, const uint8_t *src, const ModImageLayout *layout, int32_t eye, uint8_t *mono);
 int  mod_rectify_map_host(ModContext *ctx, int32_t eye, const ModImageLayout *layout, int32_t *map_qxqy);
+#define MOD_DISTORTION_RATIONAL    0   /* plumb_bob / rational_polynomial: D = k1 k2 p1 p2 k3 k4 k5 k6 (the default; as ever) */
+#define MOD_DISTORTION_EQUIDISTANT 1   /* fisheye (Kannala-Brandt, cv::fisheye): D = k1 k2 k3 k4, D[4..7] must be 0 */
+int  mod_set_distortion_model(ModContext *ctx, int32_t model);
+int  mod_get_distortion_model(const ModContext *ctx, int32_t *model);
 
 /* ---- RGB-D cameras: depth images to disparity on the GPU --------------------------------------------------------------------- */
 /* A RealSense, an Azure Kinect or a structured-light head delivers one image and one depth image (REP 118: 16UC1 millimetres with

@@ -35,6 +35,9 @@ MOD_EGO_MAX_HYPOTHESES = 4096
 MOD_SGM_FRACTION_BITS = 4
 MOD_FLOW_SEEDS = 5
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
+MOD_DISTORTION_RATIONAL, MOD_DISTORTION_EQUIDISTANT = 0, 1   # how ModRectifyCamera.D is read (mod_set_distortion_model)
+DISTORTION_MODELS = {"plumb_bob": MOD_DISTORTION_RATIONAL, "rational_polynomial": MOD_DISTORTION_RATIONAL,
+                     "equidistant": MOD_DISTORTION_EQUIDISTANT}   # sensor_msgs/CameraInfo.distortion_model
 MOD_MAX_WIDTH = 16384
 MOD_DEPTH_16UC1, MOD_DEPTH_32FC1 = 0, 1                  # REP 118 depth images: uint16 millimetres / float32 metres
 MOD_DEPTH_SPLAT_MAX = 8                                  # targets per axis a footprint of mod_set_depth_splat may paint
@@ -71,6 +74,7 @@ EXPORTS = [
     "mod_set_disparity_filters", "mod_get_disparity_filters", "mod_disparity_speckle_dev",
     "mod_set_flow_propagation", "mod_get_flow_propagation",
     "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
+    "mod_set_distortion_model", "mod_get_distortion_model",
     "mod_set_side_by_side", "mod_get_side_by_side",
     "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
     "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
@@ -239,6 +243,16 @@ assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 
 
+def distortion_model(model) -> int:
+    """MOD_DISTORTION_* from the integer or from a CameraInfo's distortion_model string ("plumb_bob", "rational_polynomial",
+    "equidistant").  An unknown string raises ValueError; an integer is passed on for the library to judge."""
+    if isinstance(model, str):
+        if model not in DISTORTION_MODELS:
+            raise ValueError(f"unknown distortion model {model!r} (known: {', '.join(DISTORTION_MODELS)})")
+        return DISTORTION_MODELS[model]
+    return int(model)
+
+
 class ModError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libmod_sf error {code}: {msg}")
@@ -302,6 +316,8 @@ def load(require_torch_first: bool = True):
     L.mod_get_rectification.argtypes = [vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(i32)]
     L.mod_rectify_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), i32, vp]
     L.mod_rectify_map_host.argtypes = [vp, i32, C.POINTER(ModImageLayout), vp]
+    L.mod_set_distortion_model.argtypes = [vp, i32]
+    L.mod_get_distortion_model.argtypes = [vp, C.POINTER(i32)]
     L.mod_set_side_by_side.argtypes = [vp, i32]
     L.mod_get_side_by_side.argtypes = [vp, C.POINTER(i32)]
     L.mod_set_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]

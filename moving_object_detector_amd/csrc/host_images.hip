@@ -47,17 +47,16 @@ int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l) {
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "the image layout's width / height differ from the rectification's");
   ModContext::Rectify::Map &m = c->rect.map[eye];
   const int W = c->dc.W, H = c->dc.H;
-  if (m.valid && m.width == l.width && m.height == l.height && m.x0 == l.x0 && m.y0 == l.y0 && m.W == W && m.H == H) return MOD_OK;
+  const int32_t model = c->rect.model;
+  if (m.valid && m.width == l.width && m.height == l.height && m.x0 == l.x0 && m.y0 == l.y0 && m.W == W && m.H == H && m.model == model) return MOD_OK;
   if (c->pipe.in_flight > 0)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "the rectification map must be rebuilt while frames are in flight: collect every ticket first");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // kernels of calls and of frames that ended at a guard may still read the old map
   HIP_TRY(c, dalloc(m.q, 2 * c->maxN));
   m.valid = false;
-  std::vector<int32_t> host(2 * (size_t)W * H);
-  build_rectify_map(cam, l.x0, l.y0, W, H, host.data());
-  HIP_TRY(c, hipMemcpyAsync(m.q, host.data(), sizeof(int32_t) * host.size(), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));   // `host` is stack-owned
-  m.width = l.width; m.height = l.height; m.x0 = l.x0; m.y0 = l.y0; m.W = W; m.H = H;
+  // No wait: every reader of the old map (k_rectify, mod_rectify_map_host's copy) and k_rectify_map are enqueued on the context's
+  // stream, in program order; kernels of calls and of frames that ended at a guard read the old map in front of this launch.
+  HIP_TRY(c, launch_rectify_map(model, cam, l.x0, l.y0, W, H, m.q, c->stream));
+  m.width = l.width; m.height = l.height; m.x0 = l.x0; m.y0 = l.y0; m.W = W; m.H = H; m.model = model;
   m.valid = true;
   return MOD_OK;
 }
@@ -281,6 +280,8 @@ int mod_set_rectification(ModContext *c, const ModRectifyCamera *left, const Mod
   if (!left != !right) return fail(c, MOD_ERR_INVALID_ARGUMENT, "rectification: both eyes or neither");
   for (const ModRectifyCamera *cam : {left, right})
     if (const char *what = cam ? check_rectify_camera(*cam) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, what);
+  for (const ModRectifyCamera *cam : {left, right})   // (the call that comes second checks the pair: model and coefficients)
+    if (const char *what = cam ? check_distortion(c->rect.model, *cam) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, what);
   if (c->pipe.in_flight > 0)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "the rectification cannot change while frames are in flight: collect every ticket first");
   c->rect.on = left != nullptr;
@@ -294,6 +295,25 @@ int mod_get_rectification(const ModContext *c, ModRectifyCamera *left, ModRectif
   *enabled = c->rect.on;
   if (c->rect.on && left) *left = c->rect.cam[MOD_EYE_LEFT];
   if (c->rect.on && right) *right = c->rect.cam[MOD_EYE_RIGHT];
+  return MOD_OK;
+}
+
+int mod_set_distortion_model(ModContext *c, int32_t model) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (model != MOD_DISTORTION_RATIONAL && model != MOD_DISTORTION_EQUIDISTANT)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "distortion model must be MOD_DISTORTION_RATIONAL or MOD_DISTORTION_EQUIDISTANT");
+  if (c->rect.on)
+    for (const ModRectifyCamera &cam : c->rect.cam)
+      if (const char *what = check_distortion(model, cam)) return fail(c, MOD_ERR_INVALID_ARGUMENT, what);
+  if (c->pipe.in_flight > 0)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the distortion model cannot change while frames are in flight: collect every ticket first");
+  c->rect.model = model;   // part of each map's key: both are rebuilt at the next use, behind the context's stream
+  return MOD_OK;
+}
+
+int mod_get_distortion_model(const ModContext *c, int32_t *model) {
+  if (!c || !model) return MOD_ERR_INVALID_ARGUMENT;
+  *model = c->rect.model;
   return MOD_OK;
 }
 

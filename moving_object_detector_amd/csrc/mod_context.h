@@ -115,15 +115,16 @@ struct ModContext {
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
   int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
-  // mod_set_rectification: the calibrations and, per eye, the map in HBM with the window it was built for (ensure_rectify_map builds
-  // it at the next use after the window or the calibration changed, never under a frame in flight)
+  // mod_set_rectification: the calibrations and, per eye, the map in HBM with the window and the distortion model it was built for
+  // (ensure_rectify_map builds it at the next use after the window, the calibration or the model changed, never under a frame in flight)
   struct Rectify {
     bool on = false;
     ModRectifyCamera cam[2]{};
+    int32_t model = MOD_DISTORTION_RATIONAL;  // mod_set_distortion_model: both eyes'; read when a map is built
     struct Map {
       DevPtr<int32_t> q;                      // [H][W][2], allocated on first use for maxN pixels
       bool valid = false;
-      int32_t width = 0, height = 0, x0 = 0, y0 = 0, W = 0, H = 0;
+      int32_t width = 0, height = 0, x0 = 0, y0 = 0, W = 0, H = 0, model = 0;
     } map[2];
   } rect;
   // whole raw messages on their way to k_rectify: room for two of the layout in force (allocated on first use, grow-only); a

@@ -145,12 +145,14 @@ int bayer_phase(int encoding, int x, int y);
 inline bool is_bayer(int encoding) { return bayer_phase(encoding, 0, 0) >= 0; }
 
 // raw camera images to rectified grey (rectify.hip).  map: device int32 [H][W][2], where each pixel of the W x H window lies in the
-// width x height message (1/32 pixel; build_rectify_map fills a host copy for the window at (x0, y0)) -> dst [frames][H][W].
+// width x height message (1/32 pixel; launch_rectify_map fills it for the window at (x0, y0)) -> dst [frames][H][W].
 // Frames lie frame_bytes apart; `extent` bytes from a frame's first one may be loaded (step * height, or less for a pane of a
 // side-by-side message: src then points at the pane and width is the pane's)
 void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, size_t frame_bytes, size_t extent, int step, int width,
                     int height, const int32_t *map, uint8_t *dst, hipStream_t s);
-void build_rectify_map(const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map);
+// k_rectify_map on s: the map of `cam` under distortion model `model` (MOD_DISTORTION_*) for the W x H window at (x0, y0)
+hipError_t launch_rectify_map(int model, const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map, hipStream_t s);
+const char *check_distortion(int model, const ModRectifyCamera &cam);   // null: cam's D fits the model, else what is wrong with it
 const char *check_rectify_camera(const ModRectifyCamera &cam);   // null: valid, else what is wrong with it
 
 // depth images to disparity (depth.hip).  Window W x H at (x0, y0) of each depth frame (MOD_DEPTH_*, row pitch `step`, frames

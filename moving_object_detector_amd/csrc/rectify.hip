@@ -2,8 +2,8 @@
 // cv::remap, INTER_LINEAR on the 1/32-pixel grid, BORDER_CONSTANT) and cv_bridge's MONO8 conversion do on the CPU ahead of the
 // reference's constructor node.  include/mod_sf.h states the formula; tests/models/rectify_model.py restates it bit for bit.
 //
-// build_rectify_map (host, f64): for every pixel of the context's W x H window of the RECTIFIED image, where it lies in the raw
-// message, in 1/32 pixel: int32 [H][W][2], 8 B/px in HBM.
+// k_rectify_map (f64, the arithmetic of rectify_map.h, either distortion model): for every pixel of the context's W x H window of
+// the RECTIFIED image, where it lies in the raw message, in 1/32 pixel: int32 [H][W][2], 8 B/px in HBM.
 // k_rectify: one lane makes a run of 4 consecutive output pixels of one row.  Runs are placed on the OUTPUT's dword grid, so a
 // row interior is one aligned dword store per lane; a run cut by a row end stores bytes.  A workgroup covers 16 runs x 16 rows
 // (64 pixels x 16 rows; a wave stores 4 rows of 64 contiguous bytes).  Per pixel: the map entry, four taps of the raw message (a
@@ -18,6 +18,7 @@
 // starts width * C bytes into it, that much less).  C source bytes + 8 map bytes + 1 per pixel; no atomics; frames in
 // blockIdx.z.
 #include "image_fmt.h"
+#include "rectify_map.h"
 
 #include <climits>
 #include <cmath>
@@ -29,7 +30,6 @@ constexpr int kRun = 4;        // output pixels per lane
 constexpr int kTileRuns = 16;  // runs (lanes) of a workgroup along x ...
 constexpr int kTileRows = 16;  // ... and rows
 constexpr int kBlock = kTileRuns * kTileRows;
-constexpr double kQMax = 16777216.0;   // 2^24: the map's clamp, so that ix + 1 and iy * step stay far from overflow
 
 // the 2 C bytes of two neighbouring pixels at p (any byte alignment), B, G, R (or the one grey channel) of each into t0 / t1
 template <int Enc, int NC>
@@ -265,10 +265,18 @@ void launch(int W, int H, int frames, const uint8_t *src, size_t frame_bytes, si
                      reinterpret_cast<const int2 *>(map), dst);
 }
 
-int32_t quantise(double m) {
-  double q = std::nearbyint(m * 32.0);   // half to even (the default rounding mode)
-  if (!std::isfinite(q)) return (int32_t)-kQMax;
-  return (int32_t)(q < -kQMax ? -kQMax : q > kQMax ? kQMax : q);
+// ---- the map itself: rectify_map.h's arithmetic, one lane per entry ----------------------------------------------------------------
+// A workgroup is 64 x 4 entries: the lanes of a wave run along a row, so a wave's 8-byte (qx, qy) stores are one contiguous run of
+// 512 bytes.  The calibration comes by value in the kernel arguments; pure f64 VALU work, no LDS, no atomics, nothing is loaded.
+constexpr int kMapCols = 64, kMapRows = 4;
+
+template <int Model>
+__global__ __launch_bounds__(kMapCols * kMapRows) void k_rectify_map(ModRectifyCamera cam, int x0, int y0, int W, int H, int2 *__restrict__ map) {
+  const int u = blockIdx.x * kMapCols + threadIdx.x, v = blockIdx.y * kMapRows + threadIdx.y;
+  if (u >= W || v >= H) return;
+  int32_t qx, qy;
+  rectify_map::entry<Model>(cam, (double)(u + x0), (double)(v + y0), qx, qy);
+  map[(size_t)v * W + u] = make_int2(qx, qy);
 }
 
 }  // namespace
@@ -287,29 +295,25 @@ void launch_rectify(int encoding, int W, int H, int frames, const uint8_t *src, 
   }
 }
 
-// cv::initUndistortRectifyMap for the W x H window at (x0, y0) of the rectified image, on cv::remap's 1/32-pixel grid.  Every
-// operation in the order include/mod_sf.h states (the Makefile's -ffp-contract=off keeps products and sums apart), so that numpy
-// reproduces every bit.
-void build_rectify_map(const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map) {
-  const double fx = cam.K[0], fy = cam.K[4], cx = cam.K[2], cy = cam.K[5];
-  const double fxp = cam.P[0], fyp = cam.P[5], cxp = cam.P[2], cyp = cam.P[6];
-  const double k1 = cam.D[0], k2 = cam.D[1], p1 = cam.D[2], p2 = cam.D[3], k3 = cam.D[4], k4 = cam.D[5], k5 = cam.D[6], k6 = cam.D[7];
-  const double *R = cam.R;
-  for (int v = 0; v < H; v++) {
-    const double V = (double)(v + y0);
-    for (int u = 0; u < W; u++) {
-      const double U = (double)(u + x0);
-      double x = (U - cxp) / fxp, y = (V - cyp) / fyp;
-      const double X = R[0] * x + R[3] * y + R[6], Y = R[1] * x + R[4] * y + R[7], Wd = R[2] * x + R[5] * y + R[8];   // R transposed
-      x = X / Wd; y = Y / Wd;
-      const double x2 = x * x, y2 = y * y, r2 = x2 + y2, xy2 = 2.0 * x * y;
-      const double kr = (1.0 + ((k3 * r2 + k2) * r2 + k1) * r2) / (1.0 + ((k6 * r2 + k5) * r2 + k4) * r2);
-      const double xd = x * kr + p1 * xy2 + p2 * (r2 + 2.0 * x2), yd = y * kr + p1 * (r2 + 2.0 * y2) + p2 * xy2;
-      const double mx = fx * xd + cx, my = fy * yd + cy;
-      int32_t *q = map + 2 * ((size_t)v * W + u);
-      q[0] = quantise(mx); q[1] = quantise(my);
-    }
+// cv::initUndistortRectifyMap (model 0) / cv::fisheye::initUndistortRectifyMap (model 1) for the W x H window at (x0, y0) of the
+// rectified image, on cv::remap's 1/32-pixel grid: map [H][W] (qx, qy) on the device, enqueued on s.  Every operation in the order
+// include/mod_sf.h states (the Makefile's -ffp-contract=off keeps products and sums apart), so that numpy reproduces every bit.
+hipError_t launch_rectify_map(int model, const ModRectifyCamera &cam, int x0, int y0, int W, int H, int32_t *map, hipStream_t s) {
+  const dim3 grid((unsigned)((W + kMapCols - 1) / kMapCols), (unsigned)((H + kMapRows - 1) / kMapRows)), block(kMapCols, kMapRows);
+  int2 *q = reinterpret_cast<int2 *>(map);
+  switch (model) {
+    case MOD_DISTORTION_RATIONAL: hipLaunchKernelGGL(k_rectify_map<MOD_DISTORTION_RATIONAL>, grid, block, 0, s, cam, x0, y0, W, H, q); break;
+    case MOD_DISTORTION_EQUIDISTANT: hipLaunchKernelGGL(k_rectify_map<MOD_DISTORTION_EQUIDISTANT>, grid, block, 0, s, cam, x0, y0, W, H, q); break;
+    default: return hipErrorInvalidValue;
   }
+  return hipGetLastError();
+}
+
+const char *check_distortion(int model, const ModRectifyCamera &cam) {
+  if (model == MOD_DISTORTION_EQUIDISTANT)
+    for (int i = 4; i < 8; i++)
+      if (cam.D[i] != 0.0) return "rectification: the equidistant model takes D = k1 k2 k3 k4, D[4..7] must be 0";
+  return nullptr;
 }
 
 const char *check_rectify_camera(const ModRectifyCamera &cam) {

@@ -140,6 +140,17 @@ class Context:
         self._check(self.lib.mod_get_rectification(self.h, C.byref(l), C.byref(r), C.byref(on)))
         return (l, r) if on.value else None
 
+    def set_distortion_model(self, model) -> None:
+        """How the rectification reads D (mod_set_distortion_model): capi.MOD_DISTORTION_RATIONAL (the default) or
+        capi.MOD_DISTORTION_EQUIDISTANT, or a CameraInfo's string ("plumb_bob", "rational_polynomial", "equidistant").  Both eyes';
+        refused while tickets are outstanding."""
+        self._check(self.lib.mod_set_distortion_model(self.h, capi.distortion_model(model)))
+
+    def get_distortion_model(self) -> int:
+        model = C.c_int32(-1)
+        self._check(self.lib.mod_get_distortion_model(self.h, C.byref(model)))
+        return model.value
+
     def set_side_by_side(self, on) -> None:
         """Side-by-side stereo messages (mod_set_side_by_side): while on, one message holds both eyes, the layout's width is one eye's
         and its step the whole row's (>= 2 * width * channels); the stereo *_host entry points take it in `left`.  Off by default; read

@@ -14,7 +14,12 @@ A build that is missing is recorded as missing.  Prints one JSON line per measur
 Bayer messages are demosaiced whole and then rectified as mono8 (k_bayer_to_mono + k_rectify): the bayer_rggb8 row beside the mono8
 row is the cost of the two passes.
 Run on the GPU: python tools/time_rectify.py [reps] [kernel] [bayer]   (kernel: the kernel legs only, for a rocprofv3 --kernel-trace
-run; bayer: only the mono8 and bayer_rggb8 rows)"""
+run; bayer: only the mono8 and bayer_rggb8 rows)
+--map [reps]: the REBUILD of the rectification maps instead (a window change that forces ensure_rectify_map to work: k_rectify_map; in
+a library from before it, the f64 loop on the host, one copy and two stream synchronisations), both eyes at 1280 x 720 and
+1920 x 1080, for each distortion model the library has; wall clock with the wait for the context's stream included, 3 warm-up
+rebuilds, `reps` timed ones (default 20), median, extremes and every repetition recorded.  Appends to profiles/rectify_map_time.jsonl.
+The script only needs the library's old calls, so a copy of it times an older checkout the same way."""
 import ctypes as C
 import json
 import os
@@ -175,7 +180,57 @@ def stream_fps(W, H, reps, rectify, encoding="bgra8", side_by_side=False):
     return frames / dt, lay["step"] * lay["height"] * (1 if side_by_side else 2)
 
 
+def fisheye_like(capi, w, h, eye):
+    """An equidistant head of about 150 degrees: f = 0.382 w, k1 .. k4 of a few 1e-2, zed_like's rotation, P's focal 0.3 w."""
+    z = zed_like(capi, w, h, eye)
+    f, s = 0.382 * w, 1.0 if eye == 0 else -1.0
+    K = [f + 0.3, 0, 0.5 * w + 11.2 * s, 0, f - 0.9, 0.5 * h - 7.9, 0, 0, 1]
+    P = [0.3 * w, 0, 0.5 * w, -0.12 * 0.3 * w * (eye != 0), 0, 0.3 * w, 0.5 * h, 0, 0, 0, 1, 0]
+    return capi.rectify_camera(w, h, K, [0.021 + 0.002 * s, -0.034, 0.027, -0.012], list(z.R), P)
+
+
+def map_rebuild(reps):
+    """One record per size and model: the time of rebuilding BOTH eyes' maps.  mod_rectify_dev with a NULL source does the map's
+    work and nothing else (it then skips), for a window that alternates between x0 = 0 and x0 = 1, so every call rebuilds."""
+    global OUT
+    OUT = os.path.join(ROOT, "profiles", "rectify_map_time.jsonl")
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    on_gpu = "mod_set_distortion_model" in capi.EXPORTS
+    models = [("rational", 0, zed_like)] + ([("equidistant", 1, fisheye_like)] if on_gpu else [])
+    for W, H in ((1280, 720), (1920, 1080)):
+        for name, model, make in models:
+            ctx = Context(W, H, max_frames=1)
+            ctx.set_camera(synth.make_camera(W, H))
+            if on_gpu:
+                ctx.set_distortion_model(model)
+            ctx.set_rectification(make(capi, W + 1, H, 0), make(capi, W + 1, H, 1))
+            lays = [capi.image_layout("mono8", W + 1, H, x0=x0) for x0 in (0, 1)]
+
+            def rebuild(i):
+                t0 = time.perf_counter()
+                for eye in (0, 1):
+                    rc = ctx.lib.mod_rectify_dev(ctx.h, 1, None, C.byref(lays[i % 2]), eye, None)
+                    assert rc == capi.MOD_SKIP_NO_DISPARITY_NOW, (rc, ctx.lib.mod_last_error(ctx.h))
+                ctx.synchronize()
+                return (time.perf_counter() - t0) * 1e3
+
+            for i in range(3):
+                rebuild(i)
+            ms = [rebuild(3 + i) for i in range(reps)]
+            m = np.empty((H, W, 2), np.int32)                      # a checksum: runs of two checkouts can be compared
+            assert ctx.lib.mod_rectify_map_host(ctx.h, 0, C.byref(lays[0]), m.ctypes.data) == 0
+            emit({"what": "rectify map rebuild, both eyes", "built_on": "gpu (k_rectify_map)" if on_gpu else "host (f64 loop + copy)",
+                  "model": name, "W": W, "H": H, "reps": reps, "ms_median": round(float(np.median(ms)), 4), "ms_min": round(min(ms), 4),
+                  "ms_max": round(max(ms), 4), "ms": [round(v, 4) for v in ms], "map_sum": int(m.astype(np.int64).sum())})
+            ctx.close()
+
+
 def main():
+    if "--map" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--map"]
+        map_rebuild(int(rest[0]) if rest else 20)
+        return
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 100
     if "bayer" in sys.argv[2:]:
         kernel(reps, ("mono8", "bayer_rggb8"))
