@@ -211,7 +211,7 @@ int mod_sgm_path_dev(ModContext *c, int32_t frames, const uint32_t *census_left,
   }
   if (e == hipSuccess) {
     launch_sgm_path(c->dc.W, c->dc.H, frames, p->disparities, p->p1, p->p2, direction, census_left, padded ? padded + 128 : census_right, path_cost,
-                    matching_cost, padded != nullptr, c->stream);
+                    matching_cost, c->stream);
     e = hipGetLastError();
   }
   if (padded) { (void)hipStreamSynchronize(c->stream); (void)hipFree(padded); }   // on every path, the failed ones included
@@ -265,7 +265,7 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
     for (int i = 0; i < p->paths; i++) {
       HIP_TRY(c, hipStreamWaitEvent(b.sgm_side[i], b.sgm_fork[s], 0));   // a failed wait would let a path read census planes in flight
       launch_sgm_path(W, H, g, D, p->p1, p->p2, p->paths == 4 ? order4[i] : i, cl, cr, b.sgm_S + s * set_volumes + (size_t)i * path_stride,
-                      nullptr, /*right_plane_padded=*/true, b.sgm_side[i]);   // cr follows cl inside the scratch allocation
+                      nullptr, b.sgm_side[i]);                                // cr follows cl inside the scratch allocation: padded
       HIP_TRY(c, hipEventRecord(b.sgm_join[s][i], b.sgm_side[i]));
     }
     return MOD_OK;

@@ -110,12 +110,10 @@ __device__ __forceinline__ SgmLane sgm_lane(int lane, int D) {
   s.none = (s.has0 ? 0u : kSgmNone) | (s.has1 ? 0u : (kSgmNone << 16));
   return s;
 }
-// FULL: D == 128, every lane owns two disparities: one unconditional 2-byte store at (wave-uniform pixel base) + 2 * lane
-template <bool FULL>
 __device__ __forceinline__ void sgm_emit(const SgmOut &o, const SgmLane &ln, size_t at, uint32_t lane, uint32_t l, uint32_t c, bool even_d, uint32_t sel) {
   SGM_GLOBAL uint8_t *pl = sgm_uniform(o.L + at), *pc = o.C ? sgm_uniform(o.C + at) : nullptr;
   const uint32_t q = 2 * lane;
-  if (FULL || (ln.has1 && even_d)) {                                  // both disparities exist and the pair is 2-byte aligned
+  if (ln.has1 && even_d) {                                          // both disparities exist and the pair is 2-byte aligned
     *(SGM_GLOBAL uint16_t *)(pl + q) = (uint16_t)__builtin_amdgcn_perm(0u, l, sel);
     if (pc) *(SGM_GLOBAL uint16_t *)(pc + q) = (uint16_t)__builtin_amdgcn_perm(0u, c, sel);
   } else {
@@ -131,7 +129,8 @@ struct SgmPair { uint32_t a, b; };
 // matching costs of the lane's two disparities at column x (31 where the disparity leaves the right image); dlast = D - 1
 __device__ __forceinline__ uint32_t sgm_cost_pk(uint32_t wl, SgmPair r, int x, int d0, int dlast) {
   uint32_t c = (uint32_t)__popc(wl ^ r.b) + ((uint32_t)__popc(wl ^ r.a) << 16);
-  if (x < dlast) {                                                    // wave-uniform: only the first D - 1 columns
+  if (x <= dlast) {                                                   // wave-uniform: only the first D columns (x == D - 1: an odd D's last
+                                                                      // lane owns d0 = x alone, its pair was read at word 0 as well)
     asm volatile("" ::: "memory");                                    // keep this a branch: the other columns skip it
     const uint32_t c0 = x > d0 ? (c & 0xffffu) : x == d0 ? (c >> 16) : 31u;
     const uint32_t c1 = x > d0 ? (c >> 16) : 31u;
@@ -140,7 +139,7 @@ __device__ __forceinline__ uint32_t sgm_cost_pk(uint32_t wl, SgmPair r, int x, i
   return c;
 }
 
-template <bool RTL, bool FULL>
+template <bool RTL>
 __global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, int P2, const uint32_t *__restrict__ cl,
                                                    const uint32_t *__restrict__ cr, SgmOut out) {
   extern __shared__ uint32_t srow[];                 // [W + 1] right census row, [W] left census row
@@ -173,8 +172,8 @@ __global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, 
     const SgmPair rn = pair(xn);
     const uint32_t c = sgm_cost_pk(wl, r, x, d0, dlast);
     uint32_t l = step > 0 ? sgm_step(lp, c, p1pk, (uint32_t)P2, sh) : c;
-    if (!FULL) l = (l & ln.keep) | ln.none;
-    sgm_emit<FULL>(out, ln, ((size_t)y * W + x) * D, lane, l, c, even_d, sel);
+    l = (l & ln.keep) | ln.none;
+    sgm_emit(out, ln, ((size_t)y * W + x) * D, lane, l, c, even_d, sel);
     lp = l;
     x = RTL ? x - 1 : x + 1;
     wl = wln; r = rn;
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, 
 // L2 / HBM (one 8-byte load per lane, see SgmPair), kPF steps ahead of their use: the recurrence is a dependent chain per step, a
 // memory round trip per step would dominate it.
 constexpr int kSgmPF = 4;
-template <int RX, int RY, bool FULL>
+template <int RX, int RY>
 __global__ __launch_bounds__(64) void k_sgm_path_line(int W, int H, int D, int P1, int P2, const uint32_t *__restrict__ cl,
                                                       const uint32_t *__restrict__ cr, SgmOut out) {
   const int lane = threadIdx.x, line = blockIdx.x, f = blockIdx.y;
@@ -229,8 +228,8 @@ __global__ __launch_bounds__(64) void k_sgm_path_line(int W, int H, int D, int P
       const uint32_t c = sgm_cost_pk(wl[u], r[u], xx, d0, dlast);
       fetch(i + kSgmPF, wl[u], r[u]);                // slot u is free again: the words of pixel i + kPF
       uint32_t l = i > 0 ? sgm_step(lp, c, p1pk, (uint32_t)P2, sh) : c;
-      if (!FULL) l = (l & ln.keep) | ln.none;
-      sgm_emit<FULL>(out, ln, ((size_t)yy * W + xx) * D, lane, l, c, even_d, sel);
+      l = (l & ln.keep) | ln.none;
+      sgm_emit(out, ln, ((size_t)yy * W + xx) * D, lane, l, c, even_d, sel);
       lp = l;
     }
   }
@@ -622,24 +621,11 @@ void launch_sgm_census(int W, int H, int frames, const uint8_t *img, uint32_t *o
 }
 
 void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
-                     uint8_t *L, uint8_t *cost, bool right_plane_padded, hipStream_t s) {
+                     uint8_t *L, uint8_t *cost, hipStream_t s) {
   SgmOut o{L, cost};
-  const size_t lds = ((size_t)2 * W + 1) * sizeof(uint32_t);
   const dim3 b(64);
-  const dim3 gh(H, frames), gv(W, frames), gd(W + H - 1, frames);
-#define SGM_PATH(FULL)                                                                                                              \
-  switch (direction) { /* numbering of oracle/sgm_ref.cpp: 0 (+1,0) 1 (-1,0) 2 (0,+1) 3 (0,-1) 4 (+1,+1) 5 (-1,-1) 6 (-1,+1) 7 (+1,-1) */ \
-    case 0: hipLaunchKernelGGL((k_sgm_path_h<false, FULL>), gh, b, lds, s, W, H, D, P1, P2, cl, cr, o); break;                      \
-    case 1: hipLaunchKernelGGL((k_sgm_path_h<true, FULL>), gh, b, lds, s, W, H, D, P1, P2, cl, cr, o); break;                       \
-    case 2: hipLaunchKernelGGL((k_sgm_path_line<0, 1, FULL>), gv, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;                      \
-    case 3: hipLaunchKernelGGL((k_sgm_path_line<0, -1, FULL>), gv, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;                     \
-    case 4: hipLaunchKernelGGL((k_sgm_path_line<1, 1, FULL>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;                      \
-    case 5: hipLaunchKernelGGL((k_sgm_path_line<-1, -1, FULL>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;                    \
-    case 6: hipLaunchKernelGGL((k_sgm_path_line<-1, 1, FULL>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;                     \
-    default: hipLaunchKernelGGL((k_sgm_path_line<1, -1, FULL>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;                    \
-  }
   // D == 128 (the published configuration): four lines per wave; the one-line kernels serve every other disparity count
-  if (D == 128 && right_plane_padded) {
+  if (D == 128) {
     const dim3 qh((H + 3) / 4, frames), qv((W + 3) / 4, frames), qd((W + H - 1 + 3) / 4, frames);
     const bool uh = (H & 3) == 0, uv = (W & 3) == 0;
 #define SGM_Q(RX, RY, UNI, GRID)                                                                                            \
@@ -662,8 +648,18 @@ void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direct
 #undef SGM_Q
     return;
   }
-  if (D == 128) { SGM_PATH(true) } else { SGM_PATH(false) }
-#undef SGM_PATH
+  const size_t lds = ((size_t)2 * W + 1) * sizeof(uint32_t);
+  const dim3 gh(H, frames), gv(W, frames), gd(W + H - 1, frames);
+  switch (direction) { /* numbering of oracle/sgm_ref.cpp: 0 (+1,0) 1 (-1,0) 2 (0,+1) 3 (0,-1) 4 (+1,+1) 5 (-1,-1) 6 (-1,+1) 7 (+1,-1) */
+    case 0: hipLaunchKernelGGL(k_sgm_path_h<false>, gh, b, lds, s, W, H, D, P1, P2, cl, cr, o); break;
+    case 1: hipLaunchKernelGGL(k_sgm_path_h<true>, gh, b, lds, s, W, H, D, P1, P2, cl, cr, o); break;
+    case 2: hipLaunchKernelGGL((k_sgm_path_line<0, 1>), gv, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
+    case 3: hipLaunchKernelGGL((k_sgm_path_line<0, -1>), gv, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
+    case 4: hipLaunchKernelGGL((k_sgm_path_line<1, 1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
+    case 5: hipLaunchKernelGGL((k_sgm_path_line<-1, -1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
+    case 6: hipLaunchKernelGGL((k_sgm_path_line<-1, 1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
+    default: hipLaunchKernelGGL((k_sgm_path_line<1, -1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
+  }
 }
 
 // every path of the published configuration (D == 128) in one grid; returns false when the combination is not covered (other D,

@@ -1,6 +1,7 @@
 """CPU: the two restatements of the SGM disparity estimator (oracle/sgm_ref.cpp, oracle/sgm_numpy.py) against each other, stage
 by stage, and against the committed fixture.  Integer arithmetic: everything is compared exactly."""
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -23,6 +24,45 @@ def test_restatements_agree_stage_by_stage(W, H, D, seed):
     assert np.array_equal(S, st["S"]) and np.array_equal(disp, st["disparity"])
     for kw in (dict(paths=4), dict(lr_check=False), dict(median=False), dict(P1=3, P2=40)):
         assert np.array_equal(pysgm.compute(left, right, D, **kw), sn.compute(left, right, D, **kw)), kw
+
+
+def _agree(left, right, D, P1, P2):
+    from oracle import pysgm
+    from oracle import sgm_numpy as sn
+    st = sn.compute(left, right, D, P1, P2, stages=True)
+    assert np.array_equal(pysgm.census(left), st["census_left"]) and np.array_equal(pysgm.census(right), st["census_right"])
+    C = pysgm.cost(st["census_left"], st["census_right"], D)
+    assert np.array_equal(C, st["cost"])
+    for i in range(8):
+        assert np.array_equal(pysgm.aggregate(C, P1, P2, i), st["paths"][i]), i
+    disp, S = pysgm.compute(left, right, D, P1, P2, want_S=True)
+    assert np.array_equal(S, st["S"]) and np.array_equal(disp, st["disparity"])
+    for kw in (dict(paths=4), dict(lr_check=False, median=False)):
+        assert np.array_equal(pysgm.compute(left, right, D, P1, P2, **kw), sn.compute(left, right, D, P1, P2, **kw)), kw
+    return st
+
+
+@pytest.mark.parametrize("family", ["tie_rich", "saturating_shift", "last_disparity", "lane_edges", "flat", "identical", "binary"])
+def test_restatements_agree_on_the_hostile_families(family):
+    """The families of tests/sgm_cases.py at the smallest shape that keeps their character (D > 32 for the ties, a census interior of
+    3 rows), under every penalty set of tests/test_gpu_sgm_edges.py."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import sgm_cases as sc
+    W, H, D = 44, 9, 36
+    left, right = sc.make(family, W, H, D, 7)
+    top = 0
+    for P1, P2 in sc.PENALTY_EDGES + ((1, 1), (40, 40)):
+        st = _agree(left, right, D, P1, P2)
+        top = max(top, max(int(L.max()) for L in st["paths"]))
+    assert top == 255                                               # P2 = 224 reaches the top of uint8 in both
+
+
+@pytest.mark.parametrize("W,H,D", [(2, 1, 1), (2, 2, 2), (3, 1, 3), (5, 3, 17), (8, 6, 128), (9, 7, 127), (3, 8, 15), (12, 2, 16)])
+def test_restatements_agree_on_tiny_images_and_edge_disparity_counts(W, H, D):
+    rng = np.random.default_rng(W * 1000 + H * 100 + D)
+    left, right = rng.integers(0, 256, (H, W), dtype=np.uint8), rng.integers(0, 256, (H, W), dtype=np.uint8)
+    for P1, P2 in ((0, 0), (0, 224), (6, 96)):
+        _agree(left, right, D, P1, P2)
 
 
 def test_census_known_answers():
