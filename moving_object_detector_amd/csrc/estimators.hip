@@ -19,8 +19,7 @@ int check_sgm_params(ModContext *c, const ModSgmParams *p) {
 // scratch of the complete estimator for a GROUP of frames (one wave walks a path line, so a single frame cannot fill the GPU; the
 // frames of a group run side by side): per frame two census planes, one uint8 cost volume PER PATH (written once, never read
 // back by the path kernels: a running sum would put its load latency into every step of a path), four disparity maps.  Census
-// planes and volumes exist twice: consecutive groups overlap (mod_sgm_compute_dev).
-constexpr int kSgmPaths = 8;
+// planes and volumes exist twice, as two sets: consecutive groups overlap (mod_sgm_compute_dev).
 constexpr int kSgmGroup = 8;                             // frames per group (4 .. 16 measured in round 3: 8 is the knee)
 constexpr size_t kSgmVolumeBudget = (size_t)24 << 30;    // bytes of cost volumes a context may hold
 
@@ -34,18 +33,18 @@ static int ensure_sgm_scratch(ModContext *c, int D, int frames, bool subpixel, i
   if (!b.sgm_fork[0]) {
     for (int k = 0; k < 2; k++) {
       HIP_TRY(c, hipEventCreateWithFlags(b.sgm_fork[k].put(), hipEventDisableTiming));
-      for (int i = 0; i < 8; i++) HIP_TRY(c, hipEventCreateWithFlags(b.sgm_join[k][i].put(), hipEventDisableTiming));
+      for (int i = 0; i < kSgmPaths; i++) HIP_TRY(c, hipEventCreateWithFlags(b.sgm_join[k][i].put(), hipEventDisableTiming));
     }
     // (a CU-masked path stream that kept one CU in 8 / 4 / 3 free for the winner-take-all of the group before was measured in
     // round 3 and changed nothing: plain non-blocking side streams)
-    for (int i = 0; i < 8; i++) HIP_TRY(c, hipStreamCreateWithFlags(b.sgm_side[i].put(), hipStreamNonBlocking));
+    for (int i = 0; i < kSgmPaths; i++) HIP_TRY(c, hipStreamCreateWithFlags(b.sgm_side[i].put(), hipStreamNonBlocking));
   }
   const bool volumes_fit = b.sgm_S && b.sgm_D >= D && b.sgm_G >= g;
   if (volumes_fit && (b.sgm_maps16 || !subpixel)) return MOD_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (volumes_fit) {                                   // the first sub-pixel call of a context that has its volumes: only the maps grow
     DevPtr<uint8_t> maps;                              // the old maps stay until the new ones exist: a failed allocation changes nothing
-    HIP_TRY(c, dalloc(maps, 6 * c->maxN * (size_t)b.sgm_G));
+    HIP_TRY(c, dalloc(maps, sgm_maps_bytes(true) * N * b.sgm_G));
     b.sgm_maps = std::move(maps);                      // (swaps: the old buffer is released with `maps`)
     b.sgm_maps16 = true;
     return MOD_OK;
@@ -53,14 +52,65 @@ static int ensure_sgm_scratch(ModContext *c, int D, int frames, bool subpixel, i
   // grow-only in BOTH dimensions: calls that alternate between (few disparities, large group) and (many, small) settle on the
   // maxima after one reallocation each instead of freeing and allocating gigabytes on every call
   const int D2 = std::max(D, b.sgm_D), g2 = std::max(g, b.sgm_G);
-  const bool maps16 = subpixel || b.sgm_maps16;         // ... and in the width of the left maps (sub-pixel mode: 16-bit, 6 N bytes per frame)
+  const bool maps16 = subpixel || b.sgm_maps16;         // ... and in the width of the left maps (sub-pixel mode: 16-bit)
   b.sgm_S.reset(); b.sgm_census.reset(); b.sgm_maps.reset(); b.sgm_D = 0; b.sgm_G = 0; b.sgm_maps16 = false;
-  // two sets (see mod_sgm_compute_dev) behind 128 words of lead: the D == 128 path kernels read up to 127 words to the left of a
-  // right census plane unconditionally (discarded: disparities that do not exist) — inside the allocation even for tiny images
-  HIP_TRY(c, dalloc(b.sgm_census, 2 * 2 * N * g2 + 128));
-  HIP_TRY(c, dalloc(b.sgm_maps, (maps16 ? 6 : 4) * N * g2));
+  // two sets (sgm_set) behind the lead the D == 128 path kernels need (mod_launch.h) — inside the allocation even for tiny images
+  HIP_TRY(c, dalloc(b.sgm_census, kSgmCensusLead + 2 * 2 * N * g2));
+  HIP_TRY(c, dalloc(b.sgm_maps, sgm_maps_bytes(maps16) * N * g2));
   HIP_TRY(c, dalloc(b.sgm_S, 2 * N * (size_t)D2 * g2 * kSgmPaths));
   b.sgm_D = D2; b.sgm_G = g2; b.sgm_maps16 = maps16;
+  return MOD_OK;
+}
+
+// What set k & 1 holds for group k of a call: `g` frames from frame `f0` on
+struct SgmSet {
+  int f0, g;
+  uint32_t *cl, *cr;            // census planes [g][N]; cr follows cl inside the scratch allocation: it has its lead
+  uint8_t *S;                   // one cost volume [g][H][W][D] per path, path_stride bytes apart
+  size_t path_stride;
+  hipEvent_t fork;              // recorded on the context's stream behind the census kernels
+  const Event *join;            // [kSgmPaths], recorded on the side streams behind the path kernels
+  bool all_in_one;              // the paths went as ONE grid on side stream 0 (sgm_start): only join[0] was recorded
+};
+
+static SgmSet sgm_set(const Buffers &b, int k, int group, int frames, size_t N, int D) {
+  const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
+  uint32_t *cl = b.sgm_census + kSgmCensusLead + s * (2 * N * group);
+  return {f0, g, cl, cl + N * g, b.sgm_S + s * (N * D * group * kSgmPaths), N * D * g, b.sgm_fork[s], b.sgm_join[s], false};
+}
+
+// census of the group on the context's stream, then its aggregation paths on the side streams
+static int sgm_start(ModContext *c, const ModSgmParams *p, const uint8_t *left, const uint8_t *right, SgmSet &s) {
+  const int W = c->dc.W, H = c->dc.H, D = p->disparities;
+  const size_t N = (size_t)W * H;
+  const Stream *side = c->b.sgm_side;
+  launch_sgm_census(W, H, s.g, left + s.f0 * N, s.cl, c->stream);
+  launch_sgm_census(W, H, s.g, right + s.f0 * N, s.cr, c->stream);
+  HIP_TRY(c, hipEventRecord(s.fork, c->stream));
+  // the published configuration: all paths in ONE grid on one side stream (sgm.hip k_sgm_paths_all)
+  HIP_TRY(c, hipStreamWaitEvent(side[0], s.fork, 0));
+  if ((s.all_in_one = launch_sgm_paths_all(W, H, s.g, D, p->p1, p->p2, p->paths, s.path_stride, s.cl, s.cr, s.S, side[0]))) {
+    HIP_TRY(c, hipEventRecord(s.join[0], side[0]));
+    return MOD_OK;
+  }
+  for (int i = 0; i < p->paths; i++) {   // 4 paths: directions 0 .. 3
+    HIP_TRY(c, hipStreamWaitEvent(side[i], s.fork, 0));   // a failed wait would let a path read census planes in flight
+    launch_sgm_path(W, H, s.g, D, p->p1, p->p2, i, s.cl, s.cr, s.S + i * s.path_stride, nullptr, side[i]);
+    HIP_TRY(c, hipEventRecord(s.join[i], side[i]));
+  }
+  return MOD_OK;
+}
+
+// winner-take-all .. left-right check of the group (and the speckle filter) on the context's stream, behind its paths
+static int sgm_finish(ModContext *c, const ModSgmParams *p, const ModDisparityFilters &filters, const SgmSet &s, const SgmMaps &maps, float *disparity) {
+  const int W = c->dc.W, H = c->dc.H;
+  float *out = disparity + s.f0 * ((size_t)W * H);
+  // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
+  for (int i = 0; i < (s.all_in_one ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, s.join[i], 0));
+  launch_sgm_finish(W, H, s.g, p->disparities, p->paths, s.path_stride, p->median, p->lr_check, filters.uniqueness_ratio, s.S, maps, out, c->stream);
+  // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever)
+  if (filters.speckle_size > 0)
+    launch_speckle(W, H, s.g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, out, c->b.spk_parent, c->b.spk_size, c->b.dbg, c->stream);
   return MOD_OK;
 }
 
@@ -200,21 +250,21 @@ int mod_sgm_path_dev(ModContext *c, int32_t frames, const uint32_t *census_left,
   if (!census_left || !census_right || !path_cost) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null plane");
   if ((rc = check_sgm_params(c, p))) return rc;
   if (direction < 0 || direction > 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "direction must be 0..7");
-  // (stage entry point, tests and tracing) the D == 128 kernels read up to 127 words before the right plane: give them a padded copy
+  // (stage entry point, tests and tracing) D == 128: the right plane behind the lead those kernels need (mod_launch.h), in a copy
   const size_t words = (size_t)frames * c->dc.W * c->dc.H;
-  uint32_t *padded = nullptr;
+  DevPtr<uint32_t> padded;
   hipError_t e = hipSuccess;
   if (p->disparities == 128) {
-    e = hipMalloc((void **)&padded, (words + 128) * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(padded, 0, 128 * sizeof(uint32_t), c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(padded + 128, census_right, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
+    e = dalloc(padded, words + kSgmCensusLead);
+    if (e == hipSuccess) e = hipMemsetAsync(padded, 0, kSgmCensusLead * sizeof(uint32_t), c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(padded + kSgmCensusLead, census_right, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
   }
   if (e == hipSuccess) {
-    launch_sgm_path(c->dc.W, c->dc.H, frames, p->disparities, p->p1, p->p2, direction, census_left, padded ? padded + 128 : census_right, path_cost,
-                    matching_cost, c->stream);
+    launch_sgm_path(c->dc.W, c->dc.H, frames, p->disparities, p->p1, p->p2, direction, census_left, padded ? padded + kSgmCensusLead : census_right,
+                    path_cost, matching_cost, c->stream);
     e = hipGetLastError();
   }
-  if (padded) { (void)hipStreamSynchronize(c->stream); (void)hipFree(padded); }   // on every path, the failed ones included
+  if (padded) (void)hipStreamSynchronize(c->stream);   // before the copy is released: on every path, the failed ones included
   HIP_TRY(c, e);
   return MOD_OK;
 }
@@ -230,62 +280,20 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   const ModDisparityFilters filters = c->sgm_filters;   // ... and so are the filters
   if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
   if (filters.speckle_size > 0 && (rc = ensure_speckle_scratch(c, group))) return rc;
-  const int W = c->dc.W, H = c->dc.H, D = p->disparities;
-  const size_t N = (size_t)W * H;
+  const size_t N = (size_t)c->dc.W * c->dc.H;
   Buffers &b = c->b;
-  static const int order4[4] = {0, 1, 2, 3};
   // Groups of frames go through two sets of census planes and cost volumes: while the winner-take-all of group k streams its
   // volumes (HBM-bound, context stream), the aggregation paths of group k + 1 (instruction-bound, one side stream per path) already
   // run.  Order on the context stream: census(0) fork(0) | census(1) fork(1) join(0) finish(0) | census(2) fork(2) join(1) finish(1) ...
   // — set s is written again (census(k + 2), paths(k + 2) behind fork(k + 2)) only after finish(k) has been enqueued before it.
   const int ngroups = (frames + group - 1) / group;
-  const size_t set_census = 2 * N * group, set_volumes = N * (size_t)D * group * kSgmPaths;
-  uint8_t *dl = b.sgm_maps, *dr = dl + N * group, *dlm = dr + N * group, *drm = dlm + N * group;
-  uint16_t *dl16 = nullptr, *dlm16 = nullptr;
-  if (subpixel) {                                        // 16-bit left maps first (2 N bytes per frame each), then the two right maps
-    dl16 = reinterpret_cast<uint16_t *>(b.sgm_maps.get()); dlm16 = dl16 + N * group;
-    dr = b.sgm_maps + 4 * N * group; drm = dr + N * group;
-  }
-  bool all_in_one[2] = {false, false};
-  auto start = [&](int k) -> int {
-    const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
-    uint32_t *cl = b.sgm_census + 128 + s * set_census, *cr = cl + N * g;
-    launch_sgm_census(W, H, g, left + (size_t)f0 * N, cl, c->stream);
-    launch_sgm_census(W, H, g, right + (size_t)f0 * N, cr, c->stream);
-    HIP_TRY(c, hipEventRecord(b.sgm_fork[s], c->stream));
-    const size_t path_stride = N * (size_t)D * g;        // one volume [g][H][W][D] per path
-    // the published configuration: all paths in ONE grid on one side stream (sgm.hip k_sgm_paths_all)
-    HIP_TRY(c, hipStreamWaitEvent(b.sgm_side[0], b.sgm_fork[s], 0));
-    if (launch_sgm_paths_all(W, H, g, D, p->p1, p->p2, p->paths, path_stride, cl, cr, b.sgm_S + s * set_volumes, b.sgm_side[0])) {
-      HIP_TRY(c, hipEventRecord(b.sgm_join[s][0], b.sgm_side[0]));
-      all_in_one[s] = true;
-      return MOD_OK;
-    }
-    all_in_one[s] = false;
-    for (int i = 0; i < p->paths; i++) {
-      HIP_TRY(c, hipStreamWaitEvent(b.sgm_side[i], b.sgm_fork[s], 0));   // a failed wait would let a path read census planes in flight
-      launch_sgm_path(W, H, g, D, p->p1, p->p2, p->paths == 4 ? order4[i] : i, cl, cr, b.sgm_S + s * set_volumes + (size_t)i * path_stride,
-                      nullptr, b.sgm_side[i]);                                // cr follows cl inside the scratch allocation: padded
-      HIP_TRY(c, hipEventRecord(b.sgm_join[s][i], b.sgm_side[i]));
-    }
-    return MOD_OK;
-  };
-  auto finish = [&](int k) -> int {
-    const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
-    // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
-    for (int i = 0; i < (all_in_one[s] ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, b.sgm_join[s][i], 0));
-    launch_sgm_finish(W, H, g, D, p->paths, N * (size_t)D * g, p->median, p->lr_check, filters.uniqueness_ratio, b.sgm_S + s * set_volumes,
-                      dl, dr, dlm, drm, dl16, dlm16, disparity + (size_t)f0 * N, c->stream);
-    // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever)
-    if (filters.speckle_size > 0)
-      launch_speckle(W, H, g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, disparity + (size_t)f0 * N, b.spk_parent, b.spk_size,
-                     b.dbg, c->stream);
-    return MOD_OK;
-  };
+  const SgmMaps maps = sgm_carve_maps(b.sgm_maps, N, group, subpixel);
+  SgmSet set[2];
+  const auto start = [&](int k) { return sgm_start(c, p, left, right, set[k & 1] = sgm_set(b, k, group, frames, N, p->disparities)); };
   if ((rc = start(0))) return rc;
   for (int k = 0; k < ngroups; k++) {
     if (k + 1 < ngroups && (rc = start(k + 1))) return rc;
-    if ((rc = finish(k))) return rc;
+    if ((rc = sgm_finish(c, p, filters, set[k & 1], maps, disparity))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;

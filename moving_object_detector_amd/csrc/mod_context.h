@@ -73,15 +73,15 @@ struct Buffers {
   DevPtr<uint32_t> tilelist;
   size_t req_alloc = 0;                     // entries currently allocated for `requests`
   // on-GPU disparity (allocated on first use)
-  DevPtr<uint32_t> sgm_census;
-  DevPtr<uint8_t> sgm_maps;                 // winner-take-all maps of a group and their medians: left, right; 8-bit (4 N bytes per frame) ...
-  bool sgm_maps16 = false;                  // ... or sized for the sub-pixel mode's 16-bit left maps (6 N): grow-only, like the volumes
-  DevPtr<uint8_t> sgm_S;                    // [paths][group][H][W][D] path cost volumes
+  DevPtr<uint32_t> sgm_census;              // kSgmCensusLead words, then two sets of [left, right][group][N] census planes
+  DevPtr<uint8_t> sgm_maps;                 // SgmMaps of a group (mod_launch.h): sgm_maps_bytes(sgm_maps16) * N bytes per frame
+  bool sgm_maps16 = false;                  // sized for the sub-pixel mode's 16-bit left maps: grow-only, like the volumes
+  DevPtr<uint8_t> sgm_S;                    // two sets of [kSgmPaths][group][H][W][D] path cost volumes
   int sgm_D = 0, sgm_G = 0;                 // disparities / frames per group the scratch is sized for
   // the aggregation paths are independent of each other: they run side by side on these streams (forked from / joined to the
   // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
-  Stream sgm_side[8];
-  Event sgm_fork[2], sgm_join[2][8];
+  Stream sgm_side[kSgmPaths];
+  Event sgm_fork[2], sgm_join[2][kSgmPaths];   // per set (estimators.hip SgmSet)
   // speckle filter (disparity_filter.hip): union-find parents and region sizes of its own, [spk_frames][maxN] each — a group of the
   // estimator or max_frames of mod_disparity_speckle_dev; allocated on first use with the filter on, grow-only (ensure_speckle_scratch)
   DevPtr<int32_t> spk_parent, spk_size;

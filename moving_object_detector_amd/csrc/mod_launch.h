@@ -77,18 +77,36 @@ void launch_median(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);
 int ccl_tile_rows();                 // tile height of k_ccl_tile
 int ccl_request_capacity(int n);     // link requests one tile can emit at neighbor_distance n
 
-// on-GPU disparity, first stages (sgm.hip)
+// on-GPU disparity (sgm.hip)
+constexpr int kSgmPaths = 8;          // aggregation paths at most: the side streams, the join events and the volumes of a set count them
+// words that must be readable in front of a right census plane `cr` when D == 128: the four-lines-per-wave kernels (the only ones for
+// that count) read their census windows unconditionally, up to kSgmCensusLead - 1 words to the left of a row; those words belong to
+// disparities that do not exist and are never used
+constexpr int kSgmCensusLead = 128;
 void launch_sgm_census(int W, int H, int frames, const uint8_t *img, uint32_t *out, hipStream_t s);
-// D == 128: the 127 words before `cr` must be readable (the four-lines-per-wave kernels, the only ones for that count, read their
-// census windows unconditionally; words left of a row belong to disparities that do not exist and are never used)
+// direction: the reference's numbering (sgm.hip kSgmDir)
 void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
                      uint8_t *L, uint8_t *cost, hipStream_t s);
 bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int paths, size_t path_stride, const uint32_t *cl, const uint32_t *cr,
                           uint8_t *L, hipStream_t s);
-// winner-take-all, median, left-right check.  dl16 / dlm16 non-null: the sub-pixel mode — the left maps are 16-bit (16 d + q) and
-// live there, dl / dlm are not used.  uniqueness: 0 = off, else the ratio in percent (mod_set_disparity_filters)
+
+// The winner-take-all maps of a group and their 3 x 3 medians, [group][N] each, inside one allocation.  The left maps hold d in 8 bits
+// or, in the sub-pixel mode, 16 d + q in 16 bits; the right maps are 8-bit in both.
+struct SgmMaps {
+  void *left, *left_median;           // uint8_t (left_bytes 1) or uint16_t (2)
+  uint8_t *right, *right_median;
+  int left_bytes;
+};
+constexpr size_t sgm_maps_bytes(bool subpixel) { return 2 * (subpixel ? 2 : 1) + 2; }   // per pixel of a frame: two left, two right maps
+// 8-bit: left, right, left median, right median; sub-pixel: the two 16-bit left maps, then the two right maps
+inline SgmMaps sgm_carve_maps(uint8_t *base, size_t N, int group, bool subpixel) {
+  const size_t n = N * group;
+  if (subpixel) return {base, base + 2 * n, base + 4 * n, base + 5 * n, 2};
+  return {base, base + 2 * n, base + n, base + 3 * n, 1};
+}
+// winner-take-all, median, left-right check.  uniqueness: 0 = off, else the ratio in percent (mod_set_disparity_filters)
 void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
-                       uint8_t *dl, uint8_t *dr, uint8_t *dlm, uint8_t *drm, uint16_t *dl16, uint16_t *dlm16, float *disparity, hipStream_t s);
+                       const SgmMaps &m, float *disparity, hipStream_t s);
 
 // speckle filter (disparity_filter.hip), in place on `disparity` [frames][H][W]: regions (4-connected, neighbours within speckle_range,
 // pixels finite and >= lo) of at most speckle_size pixels become `invalid`.  parent / size: [frames][H][W] scratch of the filter's own

@@ -10,6 +10,7 @@
 #include "mod_launch.h"
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 namespace {
 
@@ -582,36 +583,22 @@ __global__ __launch_bounds__(256) void k_sgm_median3(int W, int H, const T *__re
   out[p] = (T)v4;
 }
 
-// left-right consistency check -> DisparityImage pixels (float, -1 = invalid).  UNIQ: the marker of a pixel the uniqueness test (or
-// the median of a rejected patch) left is -1 whatever the check says
-template <bool UNIQ>
-__global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, const uint8_t *__restrict__ dl, const uint8_t *__restrict__ dr,
+// left-right consistency check -> DisparityImage pixels (float, -1 = invalid).  A uint8 left map stores d itself; the sub-pixel mode's
+// uint16 map stores v = 16 d + q: the check runs on the nearest integer, the pixel leaves as v / 16 (exact).  UNIQ: the marker of a
+// pixel the uniqueness test (or the median of a rejected patch) left is -1 whatever the check says
+template <class TL, bool UNIQ>
+__global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, const TL *__restrict__ dl, const uint8_t *__restrict__ dr,
                                                 float *__restrict__ disp) {
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
   if (x >= W || y >= H) return;
   const size_t plane = (size_t)blockIdx.z * W * H;
   dl += plane; dr += plane; disp += plane;
   const size_t p = (size_t)y * W + x;
-  const int d = dl[p];
+  const int v = dl[p], d = sizeof(TL) == 1 ? v : (v + 8) >> 4;
   bool ok = true;
   if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
-  if (UNIQ && d == (int)kSgmRejected<uint8_t>) ok = false;
-  disp[p] = ok ? (float)d : -1.0f;
-}
-// the same on the sub-pixel mode's left map v = 16 d + q: the check runs on the nearest integer, the pixel leaves as v / 16 (exact)
-template <bool UNIQ>
-__global__ __launch_bounds__(256) void k_sgm_lr_sub(int W, int H, int lr_check, const uint16_t *__restrict__ dl, const uint8_t *__restrict__ dr,
-                                                    float *__restrict__ disp) {
-  const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
-  if (x >= W || y >= H) return;
-  const size_t plane = (size_t)blockIdx.z * W * H;
-  dl += plane; dr += plane; disp += plane;
-  const size_t p = (size_t)y * W + x;
-  const int v = dl[p], d = (v + 8) >> 4;
-  bool ok = true;
-  if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
-  if (UNIQ && v == (int)kSgmRejected<uint16_t>) ok = false;
-  disp[p] = ok ? (float)v * 0.0625f : -1.0f;
+  if (UNIQ && v == (int)kSgmRejected<TL>) ok = false;
+  disp[p] = ok ? (sizeof(TL) == 1 ? (float)d : (float)v * 0.0625f) : -1.0f;
 }
 
 }  // namespace
@@ -620,46 +607,41 @@ void launch_sgm_census(int W, int H, int frames, const uint8_t *img, uint32_t *o
   hipLaunchKernelGGL(k_sgm_census, dim3((W + 63) / 64, (H + 3) / 4, frames), dim3(64, 4, 1), 0, s, W, H, img, out);
 }
 
+// The reference's numbering of the aggregation directions (oracle/sgm_ref.cpp): direction -> (RX, RY), the step along a path
+constexpr int kSgmDir[kSgmPaths][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, -1}, {-1, 1}, {1, -1}};
+
+// f(std::integral_constant<int, direction>) (a number outside the table goes as the last direction), and f(std::bool_constant<flags>...):
+// where run-time choices become template arguments
+template <int I = 0, class F>
+static void with_direction(int direction, F &&f) {
+  if constexpr (I + 1 < kSgmPaths) { if (direction != I) return with_direction<I + 1>(direction, f); }
+  f(std::integral_constant<int, I>{});
+}
+template <class F>
+static void with_flags(F &&f) { f(); }
+template <class F, class... B>
+static void with_flags(F &&f, bool flag, B... rest) {
+  if (flag) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
                      uint8_t *L, uint8_t *cost, hipStream_t s) {
   SgmOut o{L, cost};
-  const dim3 b(64);
-  // D == 128 (the published configuration): four lines per wave; the one-line kernels serve every other disparity count
-  if (D == 128) {
-    const dim3 qh((H + 3) / 4, frames), qv((W + 3) / 4, frames), qd((W + H - 1 + 3) / 4, frames);
-    const bool uh = (H & 3) == 0, uv = (W & 3) == 0;
-#define SGM_Q(RX, RY, UNI, GRID)                                                                                            \
-    do {                                                                                                                    \
-      if (cost) { if (UNI) hipLaunchKernelGGL((k_sgm_path_q<RX, RY, true, true>), GRID, b, 0, s, W, H, P1, P2, cl, cr, o);   \
-                  else hipLaunchKernelGGL((k_sgm_path_q<RX, RY, false, true>), GRID, b, 0, s, W, H, P1, P2, cl, cr, o); }     \
-      else { if (UNI) hipLaunchKernelGGL((k_sgm_path_q<RX, RY, true, false>), GRID, b, 0, s, W, H, P1, P2, cl, cr, o);        \
-             else hipLaunchKernelGGL((k_sgm_path_q<RX, RY, false, false>), GRID, b, 0, s, W, H, P1, P2, cl, cr, o); }         \
-    } while (0)
-    switch (direction) {
-      case 0: SGM_Q(1, 0, uh, qh); break;
-      case 1: SGM_Q(-1, 0, uh, qh); break;
-      case 2: SGM_Q(0, 1, uv, qv); break;
-      case 3: SGM_Q(0, -1, uv, qv); break;
-      case 4: SGM_Q(1, 1, false, qd); break;
-      case 5: SGM_Q(-1, -1, false, qd); break;
-      case 6: SGM_Q(-1, 1, false, qd); break;
-      default: SGM_Q(1, -1, false, qd); break;
-    }
-#undef SGM_Q
-    return;
-  }
-  const size_t lds = ((size_t)2 * W + 1) * sizeof(uint32_t);
-  const dim3 gh(H, frames), gv(W, frames), gd(W + H - 1, frames);
-  switch (direction) { /* numbering of oracle/sgm_ref.cpp: 0 (+1,0) 1 (-1,0) 2 (0,+1) 3 (0,-1) 4 (+1,+1) 5 (-1,-1) 6 (-1,+1) 7 (+1,-1) */
-    case 0: hipLaunchKernelGGL(k_sgm_path_h<false>, gh, b, lds, s, W, H, D, P1, P2, cl, cr, o); break;
-    case 1: hipLaunchKernelGGL(k_sgm_path_h<true>, gh, b, lds, s, W, H, D, P1, P2, cl, cr, o); break;
-    case 2: hipLaunchKernelGGL((k_sgm_path_line<0, 1>), gv, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
-    case 3: hipLaunchKernelGGL((k_sgm_path_line<0, -1>), gv, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
-    case 4: hipLaunchKernelGGL((k_sgm_path_line<1, 1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
-    case 5: hipLaunchKernelGGL((k_sgm_path_line<-1, -1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
-    case 6: hipLaunchKernelGGL((k_sgm_path_line<-1, 1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
-    default: hipLaunchKernelGGL((k_sgm_path_line<1, -1>), gd, b, 0, s, W, H, D, P1, P2, cl, cr, o); break;
-  }
+  with_direction(direction, [&](auto dir) {
+    constexpr int RX = kSgmDir[dir.value][0], RY = kSgmDir[dir.value][1];
+    const int lines = RY == 0 ? H : RX == 0 ? W : W + H - 1;     // rows, columns, diagonals
+    // D == 128 (the published configuration): four lines per wave (UNIFORM: no partial quad of rows / columns); the one-line kernels
+    // serve every other disparity count
+    if (D == 128)
+      with_flags([&](auto uniform, auto costs) {
+        hipLaunchKernelGGL((k_sgm_path_q<RX, RY, uniform.value, costs.value>), dim3((lines + 3) / 4, frames), dim3(64), 0, s, W, H, P1, P2, cl, cr, o);
+      }, (RX == 0 || RY == 0) && (lines & 3) == 0, cost != nullptr);
+    else if constexpr (RY == 0)
+      hipLaunchKernelGGL(k_sgm_path_h<(RX < 0)>, dim3(lines, frames), dim3(64), ((size_t)2 * W + 1) * sizeof(uint32_t), s, W, H, D, P1, P2, cl, cr, o);
+    else
+      hipLaunchKernelGGL((k_sgm_path_line<RX, RY>), dim3(lines, frames), dim3(64), 0, s, W, H, D, P1, P2, cl, cr, o);
+  });
 }
 
 // every path of the published configuration (D == 128) in one grid; returns false when the combination is not covered (other D,
@@ -669,43 +651,27 @@ bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int p
   if (D != 128 || (paths != 8 && paths != 4)) return false;
   const int nh = (H + 3) / 4, nv = (W + 3) / 4, nd = (W + H - 1 + 3) / 4;
   const dim3 g(2 * nh + 2 * nv + (paths == 8 ? 4 * nd : 0), frames), b(64);
-  const bool uh = (H & 3) == 0, uv = (W & 3) == 0;
-  if (uh && uv) hipLaunchKernelGGL((k_sgm_paths_all<true, true>), g, b, 0, s, W, H, P1, P2, paths, path_stride, cl, cr, L);
-  else if (uh) hipLaunchKernelGGL((k_sgm_paths_all<true, false>), g, b, 0, s, W, H, P1, P2, paths, path_stride, cl, cr, L);
-  else if (uv) hipLaunchKernelGGL((k_sgm_paths_all<false, true>), g, b, 0, s, W, H, P1, P2, paths, path_stride, cl, cr, L);
-  else hipLaunchKernelGGL((k_sgm_paths_all<false, false>), g, b, 0, s, W, H, P1, P2, paths, path_stride, cl, cr, L);
+  with_flags([&](auto uh, auto uv) {
+    hipLaunchKernelGGL((k_sgm_paths_all<uh.value, uv.value>), g, b, 0, s, W, H, P1, P2, paths, path_stride, cl, cr, L);
+  }, (H & 3) == 0, (W & 3) == 0);
   return true;
 }
 
 // uniqueness: 0 = off (the instantiations without the test), else the ratio u in percent
 void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
-                       uint8_t *dl, uint8_t *dr, uint8_t *dlm, uint8_t *drm, uint16_t *dl16, uint16_t *dlm16, float *disparity, hipStream_t s) {
+                       const SgmMaps &m, float *disparity, hipStream_t s) {
   const dim3 g((W + 63) / 64, (H + 3) / 4, frames), b(64, 4), gw(H, frames), bw(256);
   const size_t lds = (size_t)W * sizeof(uint32_t);
   const int u = uniqueness;
-#define SGM_WTA(KERNEL, SUB, TL, OUT)                                                                                                   \
-  do {                                                                                                                                  \
-    if (u) hipLaunchKernelGGL((KERNEL<SUB, TL, true>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, OUT, dr, u);                     \
-    else hipLaunchKernelGGL((KERNEL<SUB, TL, false>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, OUT, dr, u);                      \
-  } while (0)
-  if (dl16) {                                          // sub-pixel mode: 16-bit left maps, the right maps as ever
-    if (D % 16 == 0) SGM_WTA(k_sgm_wta16, true, uint16_t, dl16);
-    else SGM_WTA(k_sgm_wta, true, uint16_t, dl16);
+  with_flags([&](auto sub, auto uniq, auto by16) {     // sub-pixel mode: 16-bit left maps, the right maps as ever
+    using TL = std::conditional_t<sub.value, uint16_t, uint8_t>;
+    TL *dl = static_cast<TL *>(m.left), *dlm = static_cast<TL *>(m.left_median);
+    if constexpr (by16.value) hipLaunchKernelGGL((k_sgm_wta16<sub.value, TL, uniq.value>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, dl, m.right, u);
+    else hipLaunchKernelGGL((k_sgm_wta<sub.value, TL, uniq.value>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, dl, m.right, u);
     if (median) {
-      hipLaunchKernelGGL(k_sgm_median3<uint16_t>, g, b, 0, s, W, H, dl16, dlm16);
-      hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dr, drm);
+      hipLaunchKernelGGL(k_sgm_median3<TL>, g, b, 0, s, W, H, dl, dlm);
+      hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, m.right, m.right_median);
     }
-    if (u) hipLaunchKernelGGL(k_sgm_lr_sub<true>, g, b, 0, s, W, H, lr_check, median ? dlm16 : dl16, median ? drm : dr, disparity);
-    else hipLaunchKernelGGL(k_sgm_lr_sub<false>, g, b, 0, s, W, H, lr_check, median ? dlm16 : dl16, median ? drm : dr, disparity);
-    return;
-  }
-  if (D % 16 == 0) SGM_WTA(k_sgm_wta16, false, uint8_t, dl);
-  else SGM_WTA(k_sgm_wta, false, uint8_t, dl);
-#undef SGM_WTA
-  if (median) {
-    hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dl, dlm);
-    hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, dr, drm);
-  }
-  if (u) hipLaunchKernelGGL(k_sgm_lr<true>, g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? drm : dr, disparity);
-  else hipLaunchKernelGGL(k_sgm_lr<false>, g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? drm : dr, disparity);
+    hipLaunchKernelGGL((k_sgm_lr<TL, uniq.value>), g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? m.right_median : m.right, disparity);
+  }, m.left_bytes == 2, u != 0, D % 16 == 0);
 }

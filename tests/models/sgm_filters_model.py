@@ -1,5 +1,5 @@
 """Numpy restatement of the SGM estimator's rejection filters (mod_set_disparity_filters; csrc/sgm.hip k_sgm_wta / k_sgm_wta16 <.., UNIQ>,
-k_sgm_lr<UNIQ>, k_sgm_lr_sub<UNIQ>; csrc/disparity_filter.hip) on top of sgm_subpixel_model.  TEST INFRASTRUCTURE ONLY.
+k_sgm_lr<TL, UNIQ>; csrc/disparity_filter.hip) on top of sgm_subpixel_model.  TEST INFRASTRUCTURE ONLY.
 
 Input: S [H][W][D], the sum of the path costs (oracle/pysgm.compute(..., want_S=True)).  Integers up to the final conversion.
 

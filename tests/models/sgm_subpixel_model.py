@@ -1,5 +1,5 @@
 """Numpy restatement of the SGM estimator's winner-take-all, median and left-right check with the optional sub-pixel fraction
-(csrc/sgm.hip: k_sgm_wta16<true, uint16_t>, k_sgm_wta<true, uint16_t>, k_sgm_median3<uint16_t>, k_sgm_lr_sub).  TEST INFRASTRUCTURE ONLY.
+(csrc/sgm.hip: k_sgm_wta16<true, uint16_t>, k_sgm_wta<true, uint16_t>, k_sgm_median3<uint16_t>, k_sgm_lr<uint16_t>).  TEST INFRASTRUCTURE ONLY.
 
 Input: S [H][W][D], the sum of the path costs (oracle/sgm_numpy.compute(..., stages=True)["S"]).  Integer arithmetic up to the
 final conversion, so the GPU agrees bit for bit.

@@ -8,8 +8,8 @@ odd D and the last lane of D = 15, 17, 127 with byte stores); k_sgm_path_q<RX, R
 rows and columns and the ragged diagonals, partly filled waves included.  Complete estimator: k_sgm_paths_all<UH, UV> (D = 128, 4 and
 8 paths: <true, true> 140 x 12 and 8 x 8, <true, false> 38 x 12, <false, true> 36 x 10, <false, false> the other tiny images), the
 one-line kernels on their side streams otherwise;
-k_sgm_wta16 / k_sgm_wta <SUB, TL, UNIQ> in all four SUB x UNIQ variants each; k_sgm_median3<uint8_t / uint16_t>; k_sgm_lr<UNIQ>,
-k_sgm_lr_sub<UNIQ>."""
+k_sgm_wta16 / k_sgm_wta <SUB, TL, UNIQ> in all four SUB x UNIQ variants each; k_sgm_median3<uint8_t / uint16_t>; k_sgm_lr<TL, UNIQ>
+for both left-map types."""
 import ctypes as C
 import os
 import sys

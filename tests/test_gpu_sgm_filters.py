@@ -1,5 +1,5 @@
 """GPU: the rejection filters of the on-GPU disparity estimator (mod_set_disparity_filters, mod_disparity_speckle_dev; csrc/sgm.hip
-k_sgm_wta / k_sgm_wta16 <.., UNIQ>, k_sgm_lr<UNIQ>, k_sgm_lr_sub<UNIQ>; csrc/disparity_filter.hip) bit for bit against
+k_sgm_wta / k_sgm_wta16 <.., UNIQ>, k_sgm_lr<TL, UNIQ>; csrc/disparity_filter.hip) bit for bit against
 their numpy restatement (tests/models/sgm_filters_model.py): the sizes and flag sets of tests/test_gpu_sgm_subpixel.py, integer and
 sub-pixel maps, both winner-take-all kernels, several groups of frames, each filter alone and both together; argument checks; off is
 off; the host form; the scratch across growing frame counts; the standalone speckle call on constructed planes; the settings travel

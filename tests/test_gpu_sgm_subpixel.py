@@ -1,5 +1,5 @@
 """GPU: the sub-pixel mode of the on-GPU disparity estimator (mod_set_disparity_subpixel; csrc/sgm.hip k_sgm_wta16<true, uint16_t>,
-k_sgm_wta<true, uint16_t>, k_sgm_median3<uint16_t>, k_sgm_lr_sub) bit for bit against its numpy restatement
+k_sgm_wta<true, uint16_t>, k_sgm_median3<uint16_t>, k_sgm_lr<uint16_t>) bit for bit against its numpy restatement
 (tests/models/sgm_subpixel_model.py): both winner-take-all kernels, ragged widths, D = 8 .. 128, several groups of frames, the flag
 combinations of tests/test_gpu_sgm.py, the committed slanted pair; off is off; the setting travels with the submit through the
 three frame streams that take images."""
