@@ -99,7 +99,9 @@ __global__ __launch_bounds__(NW * 64) void k_final(DevCam c, ClArgs a) {
   for (int j = 0; j < RPW; j++) {
     const int y = y0 + r0 + j;
     const bool dyn = (mw[j] >> lane) & 1ull;
-    // tile-local coordinates of the tile root: d = ly * W + lx with lx < 64, ly < TH, so (d + 0.5) / W truncates to ly exactly
+    // tile-local coordinates of the tile root: d = ly * W + lx with lx < 64, ly < TH <= 16, i.e. d < 16 W + 64.  For such d the F32
+    // product (d + 0.5) * (1 / W) truncates to ly exactly for every W an image can have: tests/test_row_model.py checks every W up to
+    // 70000; the formula first fails near W = 4.19 M.  It is NOT exact for whole-image pixel indices (k_median_ties divides)
     const int d = par[j] - tile0;
     const int ly = (int)(((float)d + 0.5f) * invW);
     // a tile root's own entry was redirected to the final root (possibly in another tile) by k_ccl_merge: it is its own cell

@@ -407,6 +407,17 @@ __device__ __forceinline__ void finalize_frame(const DevCam &c, const ClArgs &a,
   a.n_objects[f] = n;
 }
 
+// Row of pixel index p (the return value) and its column, by an integer divide.  (Images below 2^24 pixels used to take the row as
+// (uint32_t)(((float)p + 0.5f) * (1.0f / W)).  That is NOT exact: the rounding of 1.0f / W and of the product outgrows the 0.5 / W
+// margin from about p = 2^22 on.  At 3840 x 2160 the 834 last-column pixels from row 1326 down came out as row + 1 with column
+// 0xffffffff, fell out of the column-major layout, and the replay sorted a list with stale entries.  tests/models/row_model.py keeps
+// that formula and tests/test_row_model.py its failures.  Both passes that call this wait on memory, not on the divide.)
+__device__ __forceinline__ uint32_t tie_row_col(uint32_t p, uint32_t W, uint32_t &x) {
+  const uint32_t y = p / W;
+  x = p - y * W;
+  return y;
+}
+
 __global__ __launch_bounds__(kTieThreads) void k_median_ties(DevCam c, ClArgs a, int frames) {
   using namespace introsort_emul;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -437,15 +448,14 @@ __global__ __launch_bounds__(kTieThreads) void k_median_ties(DevCam c, ClArgs a,
     __syncthreads();
     {
       uint32_t x0 = 0xffffffffu, x1 = 0, y0 = 0xffffffffu, y1 = 0;
-      const float invW = 1.0f / (float)c.W;          // p < 2^24: (p + 0.5) / W truncates to the row exactly (else: divide)
-      const bool small_image = N < (1u << 24);
       for (int i0 = tid; i0 < size; i0 += kTieThreads * 4) {
         uint32_t p4[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) p4[u] = Bpos[min(i0 + u * kTieThreads, size - 1)];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-          const uint32_t y = small_image ? (uint32_t)(((float)p4[u] + 0.5f) * invW) : p4[u] / (uint32_t)c.W, x = p4[u] - y * (uint32_t)c.W;
+          uint32_t x;
+          const uint32_t y = tie_row_col(p4[u], (uint32_t)c.W, x);
           x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1; y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
         }
       }
@@ -466,9 +476,9 @@ __global__ __launch_bounds__(kTieThreads) void k_median_ties(DevCam c, ClArgs a,
       // per run of kTieLds cells in column-major order; `base` carries the members of the runs before.  (Round 1 scanned the
       // labels plane for such boxes; the member list needs neither that plane nor the velocities again.)
       const int ncell = ncols * nseg64;              // < 2^21 + W: W * H < 2^27
-      const float invWf = 1.0f / (float)c.W;
       auto cell_of = [&](uint32_t p, int &bit) {
-        const uint32_t y = (N < (1u << 24)) ? (uint32_t)(((float)p + 0.5f) * invWf) : p / (uint32_t)c.W, x = p - y * (uint32_t)c.W;
+        uint32_t x;
+        const uint32_t y = tie_row_col(p, (uint32_t)c.W, x);
         const int ry = (int)y - ymin;
         bit = ry & 63;
         return ((int)x - xmin) * nseg64 + (ry >> 6);

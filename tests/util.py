@@ -147,3 +147,15 @@ def compare_objects(gpu_objs, orc_objs, strict_velocity=True):
             assert ng == no
         else:
             assert np.array_equal(g["velocity"], np.asarray(o["velocity"])), (g["velocity"], o["velocity"], o.get("ambiguous"))
+
+
+def compare_objects_bits(gpu_objs, orc_objs):
+    """compare_objects for records that may hold NaN or inf: id and n_points as integers, center, bounding_box and velocity as F64 bit
+    patterns, a NaN matching a NaN at the same position (bits_equal64).  Velocities are always strict: the oracle's std::sort decides."""
+    assert len(gpu_objs) == len(orc_objs), (len(gpu_objs), len(orc_objs))
+    for g, o in zip(gpu_objs, orc_objs):
+        assert int(g["id"]) == int(o["id"]), (int(g["id"]), int(o["id"]))
+        assert int(g["n_points"]) == int(o["n_points"]), (int(o["id"]), int(g["n_points"]), int(o["n_points"]))
+        for k in ("center", "bounding_box", "velocity"):
+            assert bits_equal64(g[k], np.asarray(o[k], np.float64)), (int(o["id"]), k, g[k].tolist(), np.asarray(o[k]).tolist(), o.get("ambiguous"))
+        assert np.array_equal(g["orientation"], np.array([0.0, 0.0, 0.0, 1.0]))
