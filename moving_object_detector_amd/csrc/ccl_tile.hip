@@ -591,4 +591,5 @@ void launch_ccl_tile(const DevCam &c, const ClArgs &a, int frames, hipStream_t s
 }
 
 int ccl_tile_rows() { return kTileH; }
+int ccl_tiles(int mask_words, int H) { return mask_words * ((H + kTileH - 1) / kTileH); }
 int ccl_request_capacity(int n) { return n * (64 + n) + kTileH * n; }

@@ -70,7 +70,7 @@ __device__ __forceinline__ int uf_unite(int *parent, int a, int b) {
 }
 
 constexpr int kTileH = 16, kTileWaves = 4;   // tile = 64 x 16 px, 4 rows per wave (measured best of 8x4, 16x4, 16x8, 32x8)
-static inline dim3 tile_grid(const DevCam &c, int frames) { return dim3(c.mask_words, (c.H + kTileH - 1) / kTileH, frames); }
+static inline dim3 tile_grid(const DevCam &c, int frames) { return dim3(c.mask_words, ccl_tiles(1, c.H), frames); }   // (1 word: the tile rows)
 void launch_ccl_bits(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);   // k_ccl_bits<c.n>, c.n = 1 .. 10 (ccl_bits.hip)
 
 // Block-level phase stamps of the diagnostic build (make PHASE_COUNTERS=1): PHASE_CLOCK starts the clock of a work item, PHASE_STAMP(i)

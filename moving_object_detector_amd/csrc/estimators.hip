@@ -24,41 +24,41 @@ constexpr int kSgmGroup = 8;                             // frames per group (4 
 constexpr size_t kSgmVolumeBudget = (size_t)24 << 30;    // bytes of cost volumes a context may hold
 
 static int ensure_sgm_scratch(ModContext *c, int D, int frames, bool subpixel, int *group) {
-  Buffers &b = c->b;
+  Buffers::Sgm &b = c->b.sgm;
   const size_t N = c->maxN;
   const int even = (frames + kSgmGroup - 1) / kSgmGroup;          // groups of equal size: 11 frames go as 6 + 5, not 8 + 3
   int g = (frames + even - 1) / even;
   while (g > 1 && 2 * (size_t)g * N * D * kSgmPaths > kSgmVolumeBudget) g--;
   *group = g;
-  if (!b.sgm_fork[0]) {
+  if (!b.fork[0]) {
     for (int k = 0; k < 2; k++) {
-      HIP_TRY(c, hipEventCreateWithFlags(b.sgm_fork[k].put(), hipEventDisableTiming));
-      for (int i = 0; i < kSgmPaths; i++) HIP_TRY(c, hipEventCreateWithFlags(b.sgm_join[k][i].put(), hipEventDisableTiming));
+      HIP_TRY(c, hipEventCreateWithFlags(b.fork[k].put(), hipEventDisableTiming));
+      for (int i = 0; i < kSgmPaths; i++) HIP_TRY(c, hipEventCreateWithFlags(b.join[k][i].put(), hipEventDisableTiming));
     }
     // (a CU-masked path stream that kept one CU in 8 / 4 / 3 free for the winner-take-all of the group before was measured in
     // round 3 and changed nothing: plain non-blocking side streams)
-    for (int i = 0; i < kSgmPaths; i++) HIP_TRY(c, hipStreamCreateWithFlags(b.sgm_side[i].put(), hipStreamNonBlocking));
+    for (int i = 0; i < kSgmPaths; i++) HIP_TRY(c, hipStreamCreateWithFlags(b.side[i].put(), hipStreamNonBlocking));
   }
-  const bool volumes_fit = b.sgm_S && b.sgm_D >= D && b.sgm_G >= g;
-  if (volumes_fit && (b.sgm_maps16 || !subpixel)) return MOD_OK;
+  const bool volumes_fit = b.S && b.D >= D && b.G >= g;
+  if (volumes_fit && (b.maps16 || !subpixel)) return MOD_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   if (volumes_fit) {                                   // the first sub-pixel call of a context that has its volumes: only the maps grow
     DevPtr<uint8_t> maps;                              // the old maps stay until the new ones exist: a failed allocation changes nothing
-    HIP_TRY(c, dalloc(maps, sgm_maps_bytes(true) * N * b.sgm_G));
-    b.sgm_maps = std::move(maps);                      // (swaps: the old buffer is released with `maps`)
-    b.sgm_maps16 = true;
+    HIP_TRY(c, dalloc(maps, sgm_maps_bytes(true) * N * b.G));
+    b.maps = std::move(maps);                      // (swaps: the old buffer is released with `maps`)
+    b.maps16 = true;
     return MOD_OK;
   }
   // grow-only in BOTH dimensions: calls that alternate between (few disparities, large group) and (many, small) settle on the
   // maxima after one reallocation each instead of freeing and allocating gigabytes on every call
-  const int D2 = std::max(D, b.sgm_D), g2 = std::max(g, b.sgm_G);
-  const bool maps16 = subpixel || b.sgm_maps16;         // ... and in the width of the left maps (sub-pixel mode: 16-bit)
-  b.sgm_S.reset(); b.sgm_census.reset(); b.sgm_maps.reset(); b.sgm_D = 0; b.sgm_G = 0; b.sgm_maps16 = false;
+  const int D2 = std::max(D, b.D), g2 = std::max(g, b.G);
+  const bool maps16 = subpixel || b.maps16;         // ... and in the width of the left maps (sub-pixel mode: 16-bit)
+  b.S.reset(); b.census.reset(); b.maps.reset(); b.D = 0; b.G = 0; b.maps16 = false;
   // two sets (sgm_set) behind the lead the D == 128 path kernels need (mod_launch.h) — inside the allocation even for tiny images
-  HIP_TRY(c, dalloc(b.sgm_census, kSgmCensusLead + 2 * 2 * N * g2));
-  HIP_TRY(c, dalloc(b.sgm_maps, sgm_maps_bytes(maps16) * N * g2));
-  HIP_TRY(c, dalloc(b.sgm_S, 2 * N * (size_t)D2 * g2 * kSgmPaths));
-  b.sgm_D = D2; b.sgm_G = g2; b.sgm_maps16 = maps16;
+  HIP_TRY(c, dalloc(b.census, kSgmCensusLead + 2 * 2 * N * g2));
+  HIP_TRY(c, dalloc(b.maps, sgm_maps_bytes(maps16) * N * g2));
+  HIP_TRY(c, dalloc(b.S, 2 * N * (size_t)D2 * g2 * kSgmPaths));
+  b.D = D2; b.G = g2; b.maps16 = maps16;
   return MOD_OK;
 }
 
@@ -73,17 +73,17 @@ struct SgmSet {
   bool all_in_one;              // the paths went as ONE grid on side stream 0 (sgm_start): only join[0] was recorded
 };
 
-static SgmSet sgm_set(const Buffers &b, int k, int group, int frames, size_t N, int D) {
+static SgmSet sgm_set(const Buffers::Sgm &b, int k, int group, int frames, size_t N, int D) {
   const int f0 = k * group, g = std::min(group, frames - f0), s = k & 1;
-  uint32_t *cl = b.sgm_census + kSgmCensusLead + s * (2 * N * group);
-  return {f0, g, cl, cl + N * g, b.sgm_S + s * (N * D * group * kSgmPaths), N * D * g, b.sgm_fork[s], b.sgm_join[s], false};
+  uint32_t *cl = b.census + kSgmCensusLead + s * (2 * N * group);
+  return {f0, g, cl, cl + N * g, b.S + s * (N * D * group * kSgmPaths), N * D * g, b.fork[s], b.join[s], false};
 }
 
 // census of the group on the context's stream, then its aggregation paths on the side streams
 static int sgm_start(ModContext *c, const ModSgmParams *p, const uint8_t *left, const uint8_t *right, SgmSet &s) {
   const int W = c->dc.W, H = c->dc.H, D = p->disparities;
   const size_t N = (size_t)W * H;
-  const Stream *side = c->b.sgm_side;
+  const Stream *side = c->b.sgm.side;
   launch_sgm_census(W, H, s.g, left + s.f0 * N, s.cl, c->stream);
   launch_sgm_census(W, H, s.g, right + s.f0 * N, s.cr, c->stream);
   HIP_TRY(c, hipEventRecord(s.fork, c->stream));
@@ -110,7 +110,7 @@ static int sgm_finish(ModContext *c, const ModSgmParams *p, const ModDisparityFi
   launch_sgm_finish(W, H, s.g, p->disparities, p->paths, s.path_stride, p->median, p->lr_check, filters.uniqueness_ratio, s.S, maps, out, c->stream);
   // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever)
   if (filters.speckle_size > 0)
-    launch_speckle(W, H, s.g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, out, c->b.spk_parent, c->b.spk_size, c->b.dbg, c->stream);
+    launch_speckle(W, H, s.g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, out, c->b.spk.parent, c->b.spk.size, c->b.dbg, c->stream);
   return MOD_OK;
 }
 
@@ -126,14 +126,14 @@ int check_disparity_filters(ModContext *c, const ModDisparityFilters *f) {
 
 // parent and size planes for `frames` frames; grows, after a sync, when a larger count comes (the old planes stay if that fails)
 static int ensure_speckle_scratch(ModContext *c, int frames) {
-  Buffers &b = c->b;
-  if (b.spk_frames >= frames) return MOD_OK;
+  Buffers::Speckle &b = c->b.spk;
+  if (b.frames >= frames) return MOD_OK;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   DevPtr<int32_t> parent, size;
   HIP_TRY(c, dalloc(parent, (size_t)frames * c->maxN));
   HIP_TRY(c, dalloc(size, (size_t)frames * c->maxN));
-  b.spk_parent = std::move(parent); b.spk_size = std::move(size);   // (swaps: the old planes are released with the locals)
-  b.spk_frames = frames;
+  b.parent = std::move(parent); b.size = std::move(size);   // (swaps: the old planes are released with the locals)
+  b.frames = frames;
   return MOD_OK;
 }
 
@@ -141,11 +141,17 @@ static int ensure_speckle_scratch(ModContext *c, int frames) {
 constexpr int kFlowMaxLevels = 6;
 constexpr int kFlowMinCoarse = 16;      // px on either side of the coarsest level
 
-// elements before level l in the per-level scratch regions: level k holds [2][maxF][(max_width >> k) * (max_height >> k)]
-static size_t flow_level_offset(const ModContext *c, int l) {
-  size_t off = 0;
-  for (int k = 0; k < l; k++) off += (size_t)2 * c->cfg.max_frames * (size_t)(c->cfg.max_width >> k) * (size_t)(c->cfg.max_height >> k);
-  return off;
+// The pyramid of a call: level l is W[l] x H[l] pixels (level 0: the camera's); its region [2][maxF][(max_width >> l) * (max_height >> l)] of the per-level
+// scratch, sized for the capacity, starts img[l] / cen[l] elements into Buffers::Flow::img (l >= 1) / ::census; entry kFlowMaxLevels: the buffer's length
+struct FlowPlan { int W[kFlowMaxLevels], H[kFlowMaxLevels]; size_t img[kFlowMaxLevels + 1], cen[kFlowMaxLevels + 1]; };
+
+static FlowPlan flow_plan(const ModContext *c) {
+  FlowPlan p{};
+  for (int l = 0; l < kFlowMaxLevels; l++) {
+    p.W[l] = c->dc.W >> l; p.H[l] = c->dc.H >> l;
+    p.cen[l + 1] = p.cen[l] + (size_t)2 * c->cfg.max_frames * (size_t)(c->cfg.max_width >> l) * (size_t)(c->cfg.max_height >> l); p.img[l + 1] = p.cen[l + 1] - p.cen[1];
+  }
+  return p;
 }
 
 int check_flow_params(ModContext *c, const ModFlowParams *p, int frames) {
@@ -160,14 +166,13 @@ int check_flow_params(ModContext *c, const ModFlowParams *p, int frames) {
   return MOD_OK;
 }
 
-static int ensure_flow_scratch(ModContext *c) {
-  Buffers &b = c->b;
-  if (b.flow_sub) return MOD_OK;                     // the last buffer of the set exists: all do
-  const size_t N = c->maxN, F = (size_t)c->cfg.max_frames;
-  HIP_TRY(c, dalloc(b.flow_img, flow_level_offset(c, kFlowMaxLevels) - flow_level_offset(c, 1)));
-  HIP_TRY(c, dalloc(b.flow_census, flow_level_offset(c, kFlowMaxLevels)));
-  HIP_TRY(c, dalloc(b.flow_int, 2 * 2 * F * N));
-  HIP_TRY(c, dalloc(b.flow_sub, F * N));
+static int ensure_flow_scratch(ModContext *c, const FlowPlan &lv) {
+  Buffers::Flow &b = c->b.flow;
+  if (b.sub) return MOD_OK;                          // the last buffer of the set exists: all do
+  HIP_TRY(c, dalloc(b.img, lv.img[kFlowMaxLevels]));
+  HIP_TRY(c, dalloc(b.census, lv.cen[kFlowMaxLevels]));
+  HIP_TRY(c, dalloc(b.winners, 2 * 2 * (size_t)c->cfg.max_frames * c->maxN));
+  HIP_TRY(c, dalloc(b.sub, (size_t)c->cfg.max_frames * c->maxN));
   return MOD_OK;
 }
 
@@ -187,24 +192,24 @@ int check_ego_params(ModContext *c, const ModEgoParams *p) {
 
 // Correspondence scratch for `stride` (max_width x max_height x max_frames / stride^2); grows, after a sync, when a smaller stride comes.
 static int ensure_ego_scratch(ModContext *c, int stride) {
-  Buffers &b = c->b;
+  Buffers::Ego &b = c->b.ego;
   const size_t F = (size_t)c->cfg.max_frames;
   const int gw = (c->cfg.max_width + stride - 1) / stride, gh = (c->cfg.max_height + stride - 1) / stride;
   const size_t cap = (size_t)gw * gh;
-  if (cap > b.ego_cap) {
+  if (cap > b.cap) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    b.ego_corr.reset(); b.ego_flag.reset(); b.ego_blkcnt.reset(); b.ego_cap = 0;
-    HIP_TRY(c, dalloc(b.ego_corr, F * 9 * cap));
-    HIP_TRY(c, dalloc(b.ego_flag, F * cap));
-    HIP_TRY(c, dalloc(b.ego_blkcnt, F * (size_t)ego_grid_blocks(gw, gh)));
-    b.ego_cap = cap;
+    b.corr.reset(); b.flag.reset(); b.blkcnt.reset(); b.cap = 0;
+    HIP_TRY(c, dalloc(b.corr, F * 9 * cap));
+    HIP_TRY(c, dalloc(b.flag, F * cap));
+    HIP_TRY(c, dalloc(b.blkcnt, F * (size_t)ego_grid_blocks(gw, gh)));
+    b.cap = cap;
   }
-  if (!b.ego_res) {
-    HIP_TRY(c, dalloc(b.ego_ncorr, F));
-    HIP_TRY(c, dalloc(b.ego_hyp, F * MOD_EGO_MAX_HYPOTHESES * 12));
-    HIP_TRY(c, dalloc(b.ego_hcnt, F * MOD_EGO_MAX_HYPOTHESES));
-    HIP_TRY(c, dalloc(b.ego_tf, F));
-    HIP_TRY(c, dalloc(b.ego_res, F));
+  if (!b.res) {
+    HIP_TRY(c, dalloc(b.ncorr, F));
+    HIP_TRY(c, dalloc(b.hyp, F * MOD_EGO_MAX_HYPOTHESES * 12));
+    HIP_TRY(c, dalloc(b.hcnt, F * MOD_EGO_MAX_HYPOTHESES));
+    HIP_TRY(c, dalloc(b.tf, F));
+    HIP_TRY(c, dalloc(b.res, F));
   }
   return MOD_OK;
 }
@@ -213,18 +218,18 @@ int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dn
                   ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt) {
   int rc = ensure_ego_scratch(c, p->stride);
   if (rc) return rc;
-  Buffers &b = c->b;
+  Buffers::Ego &b = c->b.ego;
   EgoArgs a;
   a.W = c->dc.W; a.H = c->dc.H; a.frames = frames; a.stride = p->stride;
   a.gw = (a.W + p->stride - 1) / p->stride; a.gh = (a.H + p->stride - 1) / p->stride;
-  a.cap = (int)b.ego_cap;
+  a.cap = (int)b.cap;
   a.hyps = p->hypotheses; a.iterations = p->iterations; a.min_inliers = p->min_inliers; a.seed = p->seed;
   a.dlo = std::max(c->cam.min_disparity, p->min_disparity); a.dhi = c->cam.max_disparity;
   a.th = (double)p->inlier_threshold;
   a.fx = c->cam.fx; a.fy = c->cam.fy; a.cx = c->cam.cx; a.cy = c->cam.cy; a.Tx = c->cam.Tx; a.Ty = c->cam.Ty; a.fT = (double)c->dc.fT;
   a.dprev = dprev; a.dnow = dnow; a.flow = flow;
-  a.corr = b.ego_corr; a.blkcnt = b.ego_blkcnt; a.ncorr = b.ego_ncorr; a.hyp = b.ego_hyp; a.hcnt = b.ego_hcnt; a.flag = b.ego_flag;
-  a.tf = reinterpret_cast<double *>(tf ? tf : b.ego_tf.get()); a.res = res ? res : b.ego_res.get(); a.fc = fc; a.dt = dt;
+  a.corr = b.corr; a.blkcnt = b.blkcnt; a.ncorr = b.ncorr; a.hyp = b.hyp; a.hcnt = b.hcnt; a.flag = b.flag;
+  a.tf = reinterpret_cast<double *>(tf ? tf : b.tf.get()); a.res = res ? res : b.res.get(); a.fc = fc; a.dt = dt;
   static_assert(sizeof(ModTransform) == 7 * sizeof(double), "ModTransform is 7 doubles");
   launch_egomotion(a, c->stream);
   HIP_TRY(c, hipGetLastError());
@@ -281,13 +286,13 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
   if (filters.speckle_size > 0 && (rc = ensure_speckle_scratch(c, group))) return rc;
   const size_t N = (size_t)c->dc.W * c->dc.H;
-  Buffers &b = c->b;
+  const Buffers::Sgm &b = c->b.sgm;
   // Groups of frames go through two sets of census planes and cost volumes: while the winner-take-all of group k streams its
   // volumes (HBM-bound, context stream), the aggregation paths of group k + 1 (instruction-bound, one side stream per path) already
   // run.  Order on the context stream: census(0) fork(0) | census(1) fork(1) join(0) finish(0) | census(2) fork(2) join(1) finish(1) ...
   // — set s is written again (census(k + 2), paths(k + 2) behind fork(k + 2)) only after finish(k) has been enqueued before it.
   const int ngroups = (frames + group - 1) / group;
-  const SgmMaps maps = sgm_carve_maps(b.sgm_maps, N, group, subpixel);
+  const SgmMaps maps = sgm_carve_maps(b.maps, N, group, subpixel);
   SgmSet set[2];
   const auto start = [&](int k) { return sgm_start(c, p, left, right, set[k & 1] = sgm_set(b, k, group, frames, N, p->disparities)); };
   if ((rc = start(0))) return rc;
@@ -349,7 +354,7 @@ int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, i
   if (speckle_size == 0) return MOD_OK;
   if ((rc = ensure_speckle_scratch(c, c->cfg.max_frames))) return rc;
   launch_speckle(c->dc.W, c->dc.H, frames, c->cam.min_disparity, c->cam.min_disparity - 1.0f, speckle_size, speckle_range, disparity,
-                 c->b.spk_parent, c->b.spk_size, c->b.dbg, c->stream);
+                 c->b.spk.parent, c->b.spk.size, c->b.dbg, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
@@ -360,33 +365,29 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   if (!prev || !now) return MOD_SKIP_NO_FLOW;                  // no image pair: no flow (estimateOpticalFlow fails, :279-290)
   if (!flow) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow plane");
   if ((rc = check_flow_params(c, p, frames))) return rc;
-  if ((rc = ensure_flow_scratch(c))) return rc;
-  Buffers &b = c->b;
+  const FlowPlan lv = flow_plan(c);
+  if ((rc = ensure_flow_scratch(c, lv))) return rc;
+  const Buffers::Flow &b = c->b.flow;
   const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
   const int seeds = c->flow_seeds;                       // the setting of THIS call: every kernel below is enqueued before it returns
-  int Wl[kFlowMaxLevels], Hl[kFlowMaxLevels];
-  Wl[0] = c->dc.W; Hl[0] = c->dc.H;
-  for (int l = 1; l < L; l++) { Wl[l] = Wl[l - 1] >> 1; Hl[l] = Hl[l - 1] >> 1; }
-  const size_t img0 = flow_level_offset(c, 1);
-  auto img = [&](int l) { return b.flow_img + (flow_level_offset(c, l) - img0); };     // level l >= 1: [2][F][Hl][Wl]
-  auto cen = [&](int l) { return b.flow_census + flow_level_offset(c, l); };           // level l: [2][F][Hl][Wl]
+  const int *const W = lv.W, *const H = lv.H; uint8_t *const img = b.img; uint32_t *const cen = b.census;   // level l >= 1 at img + lv.img[l], level l of the census planes at cen + lv.cen[l]: [2][F][H[l]][W[l]]
+  const size_t N = (size_t)W[0] * H[0];
   for (int l = 1; l < L; l++) {
-    const size_t Ns = (size_t)Wl[l - 1] * Hl[l - 1];
-    launch_flow_pyramid(Wl[l - 1], Hl[l - 1], Wl[l], Hl[l], F, l == 1 ? prev : img(l - 1), l == 1 ? now : img(l - 1) + F * Ns, img(l), c->stream);
+    uint8_t *const src = img + lv.img[l - 1];            // (level 0 is the caller's two images)
+    launch_flow_pyramid(W[l - 1], H[l - 1], W[l], H[l], F, l == 1 ? prev : src, l == 1 ? now : src + F * ((size_t)W[l - 1] * H[l - 1]), img + lv.img[l], c->stream);
   }
-  const size_t N = (size_t)Wl[0] * Hl[0];
-  launch_sgm_census(Wl[0], Hl[0], F, prev, cen(0), c->stream);
-  launch_sgm_census(Wl[0], Hl[0], F, now, cen(0) + F * N, c->stream);
-  for (int l = 1; l < L; l++) launch_sgm_census(Wl[l], Hl[l], 2 * F, img(l), cen(l), c->stream);
+  launch_sgm_census(W[0], H[0], F, prev, cen, c->stream);
+  launch_sgm_census(W[0], H[0], F, now, cen + F * N, c->stream);
+  for (int l = 1; l < L; l++) launch_sgm_census(W[l], H[l], 2 * F, img + lv.img[l], cen + lv.cen[l], c->stream);
   // coarse to fine; level l writes integer plane set (l & 1) and reads set ((l + 1) & 1)
   const size_t set = 2 * (size_t)c->cfg.max_frames * c->maxN;
-  short4 *const sub = p->subpixel ? b.flow_sub.get() : nullptr;
+  short4 *const sub = p->subpixel ? b.sub.get() : nullptr;
   for (int l = L - 1; l >= 0; l--) {
     const bool coarsest = l == L - 1;
-    launch_flow_match(Wl[l], Hl[l], coarsest ? 0 : Wl[l + 1], coarsest ? 0 : Hl[l + 1], F, dirs, p->window, p->radius, seeds, cen(l),
-                      coarsest ? nullptr : b.flow_int + ((l + 1) & 1) * set, b.flow_int + (l & 1) * set, l == 0 ? sub : nullptr, c->stream);
+    launch_flow_match(W[l], H[l], coarsest ? 0 : W[l + 1], coarsest ? 0 : H[l + 1], F, dirs, p->window, p->radius, seeds, cen + lv.cen[l],
+                      coarsest ? nullptr : b.winners + ((l + 1) & 1) * set, b.winners + (l & 1) * set, l == 0 ? sub : nullptr, c->stream);
   }
-  launch_flow_finish(Wl[0], Hl[0], F, b.flow_int, dirs == 2 ? b.flow_int + (size_t)F * N : nullptr, sub, p->fb_check, flow, c->stream);
+  launch_flow_finish(W[0], H[0], F, b.winners, dirs == 2 ? b.winners + (size_t)F * N : nullptr, sub, p->fb_check, flow, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -337,10 +337,10 @@ int mod_egomotion_host(ModContext *c, const float *disparity_prev, const float *
   HIP_TRY(c, plane_in(c, h.dprev, disparity_prev, 1, c->stream));
   HIP_TRY(c, plane_in(c, h.dnow, disparity_now, 1, c->stream));
   HIP_TRY(c, plane_in(c, h.flow, flow, 2, c->stream));
-  if ((rc = run_egomotion(c, 1, h.dprev, h.dnow, h.flow, p, nullptr, nullptr, nullptr, 0.0))) return rc;   // into b.ego_tf, b.ego_res
+  if ((rc = run_egomotion(c, 1, h.dprev, h.dnow, h.flow, p, nullptr, nullptr, nullptr, 0.0))) return rc;   // into b.ego.tf, b.ego.res
   ModEgoResult r{};
-  HIP_TRY(c, hipMemcpyAsync(transform, c->b.ego_tf, sizeof(ModTransform), hipMemcpyDeviceToHost, c->stream));
-  if ((rc = download_sync(c, &r, c->b.ego_res, sizeof(ModEgoResult)))) return rc;
+  HIP_TRY(c, hipMemcpyAsync(transform, c->b.ego.tf, sizeof(ModTransform), hipMemcpyDeviceToHost, c->stream));
+  if ((rc = download_sync(c, &r, c->b.ego.res, sizeof(ModEgoResult)))) return rc;
   if (result) *result = r;
   return r.status == MOD_EGO_OK ? MOD_OK : MOD_SKIP_NO_TRANSFORM;   // visual odometry failed: construct() publishes nothing (:251-255)
 }
@@ -449,7 +449,7 @@ int mod_cluster_cloud_host(ModContext *c, const void *cloud, int32_t width, int3
   launch_unpack(N, h.aos, pl.x, pl.y, pl.z, pl.vx, pl.vy, pl.vz, c->stream);
   HIP_TRY(c, hipGetLastError());
   const ModClusterOut out = cluster_out(h, labels);
-  if ((rc = begin_cluster_scratch(c)) || (rc = run_cluster(c, 1, &pl, c->b.mask, false, false, &out))) return rc;
+  if ((rc = begin_cluster_scratch(c)) || (rc = run_cluster(c, 1, &pl, c->b.cluster.mask, false, false, &out))) return rc;
   c->scratch_clean = true;
   return fetch_cluster_results(c, labels, objects, max_objects, n_objects);
 }

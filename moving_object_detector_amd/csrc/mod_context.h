@@ -38,6 +38,7 @@ using Stream = Owned<hipStream_t, hipStreamDestroy>;
 template <class T>
 hipError_t dalloc(DevPtr<T> &p, size_t count) { return p ? hipSuccess : hipMalloc((void **)p.put(), count * sizeof(T)); }
 inline hipError_t make_event(Event &e) { return e ? hipSuccess : hipEventCreateWithFlags(e.put(), hipEventDisableTiming); }
+#define HIP_OK(expr) do { if (hipError_t e_ = (expr); e_ != hipSuccess) return e_; } while (0)   // in functions that return a hipError_t (entry points: HIP_TRY)
 
 // An event and whether it has been recorded yet: wait() on a fence that never was is no call at all.  A fence stays armed (every
 // later wait() waits again) unless its waiter takes it with wait_once().  record() makes the event where nobody has.
@@ -55,52 +56,53 @@ struct Fence {
 
 struct EventPair { Event a, b; };
 
+// Scratch of the cluster stage and of the scene-flow epilogue that feeds it (what each buffer holds: mod_launch.h ClArgs).  Sized once, for the capacities
+// below; a call's frames lie the CAMERA's strides apart inside it.  Its operations are in mod_sf.hip: cluster_alloc, cluster_grow_requests, cluster_carve.
+struct ClusterScratch {
+  size_t frames = 0, pixels = 0, mask_rows = 0, tiles = 0, max_objects = 0;   // capacities: frames; per frame pixels, mask words x rows, tiles, objects
+  DevPtr<uint64_t> mask, lroot;             // [frames][mask_rows]
+  DevPtr<float2> zrange;                    // [frames][mask_rows] depth range of the dynamic pixels of each mask word (fused path)
+  DevPtr<int32_t> parent, rsize, rkey;      // [frames][pixels]; rsize, rkey: 4 + 4 B per pixel of address space, touched only at roots
+  DevPtr<uint32_t> mbits, mpix;             // [frames][pixels]
+  DevPtr<ClusterBox> cbox;                  // [frames][max_objects]
+  DevPtr<ClusterInfo> clusters;             // [2][frames][max_objects]: the clusters, then (rank_scratch) what k_ccl_merge ranks them in
+  DevPtr<uint32_t> worklist;                // [2][frames * max_objects]: all clusters of a launch, then (tielist) the ambiguous ones
+  ClusterInfo *rank_scratch = nullptr; uint32_t *tielist = nullptr;   // the second halves of the two, set where they are allocated
+  DevPtr<int32_t> counters, tilehdr;        // [frames][kClusterCounters], [frames][tiles][kTileHdrWords]
+  DevPtr<uint32_t> tilelist;                // [frames * tiles]
+  DevPtr<uint2> requests; size_t req_alloc = 0;   // [frames][tiles][ccl_request_capacity(neighbor_distance)], grown by mod_set_params; entries allocated
+};
+
 struct Buffers {
   DevPtr<double> rayx, rayy;
   DevPtr<FrameConst> fc;                    // [maxF]
-  DevPtr<uint64_t> mask, lroot;
-  DevPtr<float2> zrange;                    // [maxF][H][mask_words] depth range of the dynamic pixels of each mask word (fused path)
-  DevPtr<int32_t> parent;
-  DevPtr<int32_t> rsize, rkey;
-  DevPtr<ClusterBox> cbox;
-  DevPtr<int32_t> counters;
-  DevPtr<ClusterInfo> clusters;             // 2 x [maxF][max_objects]
-  DevPtr<uint32_t> mbits, mpix;
-  DevPtr<uint32_t> worklist;      // [2][F * max_objects]: all clusters of a launch, then the ambiguous ones
-  DevPtr<unsigned long long> dbg;
-  DevPtr<uint2> requests;
-  DevPtr<int32_t> tilehdr;
-  DevPtr<uint32_t> tilelist;
-  size_t req_alloc = 0;                     // entries currently allocated for `requests`
-  // on-GPU disparity (allocated on first use)
-  DevPtr<uint32_t> sgm_census;              // kSgmCensusLead words, then two sets of [left, right][group][N] census planes
-  DevPtr<uint8_t> sgm_maps;                 // SgmMaps of a group (mod_launch.h): sgm_maps_bytes(sgm_maps16) * N bytes per frame
-  bool sgm_maps16 = false;                  // sized for the sub-pixel mode's 16-bit left maps: grow-only, like the volumes
-  DevPtr<uint8_t> sgm_S;                    // two sets of [kSgmPaths][group][H][W][D] path cost volumes
-  int sgm_D = 0, sgm_G = 0;                 // disparities / frames per group the scratch is sized for
-  // the aggregation paths are independent of each other: they run side by side on these streams (forked from / joined to the
-  // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
-  Stream sgm_side[kSgmPaths];
-  Event sgm_fork[2], sgm_join[2][kSgmPaths];   // per set (estimators.hip SgmSet)
-  // speckle filter (disparity_filter.hip): union-find parents and region sizes of its own, [spk_frames][maxN] each — a group of the
+  DevPtr<unsigned long long> dbg;           // [kDbgWords] diagnostic counters (mod_device.h)
+  ClusterScratch cluster;
+  struct Sgm {                              // on-GPU disparity (allocated on first use)
+    DevPtr<uint32_t> census;                // kSgmCensusLead words, then two sets of [left, right][group][N] census planes
+    DevPtr<uint8_t> maps;                   // SgmMaps of a group (mod_launch.h): sgm_maps_bytes(maps16) * N bytes per frame
+    DevPtr<uint8_t> S;                      // two sets of [kSgmPaths][group][H][W][D] path cost volumes
+    int D = 0, G = 0; bool maps16 = false;  // disparities / frames per group the scratch is sized for; the sub-pixel mode's 16-bit left maps: grow-only, all three
+    // the aggregation paths are independent of each other: they run side by side on these streams (forked from / joined to the
+    // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
+    Stream side[kSgmPaths];
+    Event fork[2], join[2][kSgmPaths];      // per set (estimators.hip SgmSet)
+  } sgm;
+  // speckle filter (disparity_filter.hip): union-find parents and region sizes of its own, [frames][maxN] each — a group of the
   // estimator or max_frames of mod_disparity_speckle_dev; allocated on first use with the filter on, grow-only (ensure_speckle_scratch)
-  DevPtr<int32_t> spk_parent, spk_size;
-  int spk_frames = 0;
-  // on-GPU optical flow (allocated on first use, every level sized for max_width x max_height x max_frames; see flow_level_offset)
-  DevPtr<uint8_t> flow_img;                 // pyramid levels 1 .. kFlowMaxLevels - 1 of both images
-  DevPtr<uint32_t> flow_census;             // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
-  DevPtr<short2> flow_int;                  // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
-  DevPtr<short4> flow_sub;                  // [maxF][maxN] sub-pixel terms of level 0
-  // on-GPU ego-motion (allocated on first use; the correspondence buffers grow to the smallest stride seen: see ensure_ego_scratch)
-  DevPtr<double> ego_corr;                  // [maxF][9][ego_cap]
-  DevPtr<uint8_t> ego_flag;                 // [maxF][ego_cap]
-  DevPtr<int32_t> ego_blkcnt;               // [maxF][blocks of the grid at the smallest stride]
-  size_t ego_cap = 0;
-  DevPtr<int32_t> ego_ncorr;                // [maxF]
-  DevPtr<double> ego_hyp;                   // [maxF][MOD_EGO_MAX_HYPOTHESES][12]
-  DevPtr<int32_t> ego_hcnt;                 // [maxF][MOD_EGO_MAX_HYPOTHESES]
-  DevPtr<ModTransform> ego_tf;              // [maxF] mod_egomotion_host
-  DevPtr<ModEgoResult> ego_res;             // [maxF] mod_egomotion_host / a NULL `results` of mod_egomotion_dev
+  struct Speckle { DevPtr<int32_t> parent, size; int frames = 0; } spk;
+  struct Flow {                             // on-GPU optical flow (allocated on first use, every level sized for max_width x max_height x max_frames: FlowPlan)
+    DevPtr<uint8_t> img;                    // pyramid levels 1 .. kFlowMaxLevels - 1 of both images
+    DevPtr<uint32_t> census;                // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
+    DevPtr<short2> winners;                 // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
+    DevPtr<short4> sub;                     // [maxF][maxN] sub-pixel terms of level 0
+  } flow;
+  struct Ego {                              // on-GPU ego-motion (allocated on first use; the correspondence buffers grow to the smallest stride seen: ensure_ego_scratch)
+    DevPtr<double> corr, hyp;               // [maxF][9][cap], [maxF][MOD_EGO_MAX_HYPOTHESES][12]
+    DevPtr<uint8_t> flag; size_t cap = 0;   // [maxF][cap]
+    DevPtr<int32_t> blkcnt, ncorr, hcnt;    // [maxF][blocks of the grid at the smallest stride], [maxF], [maxF][MOD_EGO_MAX_HYPOTHESES]
+    DevPtr<ModTransform> tf; DevPtr<ModEgoResult> res;   // [maxF] each: mod_egomotion_host / (res) a NULL `results` of mod_egomotion_dev
+  } ego;
 };
 
 // Every resource is a member handle: mod_destroy synchronizes the streams below, and `delete` releases the rest.
@@ -147,7 +149,6 @@ struct ModContext {
   Buffers b;
   int max_objects = 0;
   size_t maxN = 0;
-  int max_mask_words = 0;
   // the device buffers of one host frame: the staging of the synchronous *_host entry points and each slot of the stream have a set
   struct FrameBuffers {
     DevPtr<float> dprev, flow, planes;
@@ -327,7 +328,7 @@ int check_sgm_params(ModContext *c, const ModSgmParams *p);
 int check_flow_params(ModContext *c, const ModFlowParams *p, int frames);
 int check_ego_params(ModContext *c, const ModEgoParams *p);
 int check_disparity_filters(ModContext *c, const ModDisparityFilters *f);
-// the ego-motion estimator over `frames` frames; tf == null: into b.ego_tf, res == null: into b.ego_res; fc != null: also the frames'
+// the ego-motion estimator over `frames` frames; tf == null: into b.ego.tf, res == null: into b.ego.res; fc != null: also the frames'
 // scene-flow constants (with dt) into fc
 int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p,
                   ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt);

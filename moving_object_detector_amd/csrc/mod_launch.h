@@ -18,6 +18,9 @@ struct SfArgs {
   unsigned long long *dbg;            // the context's diagnostic counters (checked build: index assertion 16), unused by a product build
 };
 
+constexpr int kClusterCounters = 8;   // words per frame of ClArgs::counters
+constexpr int kTileHdrWords = 2;      // words per tile of ClArgs::tilehdr / SfArgs::tilehdr
+
 // Scratch the clustering kernels work in; all device pointers, sized by the context.
 struct ClArgs {
   const float *x, *y, *z, *vx, *vy, *vz;  // input planes [F][H][W]
@@ -75,6 +78,7 @@ void launch_ccl_merge(const DevCam &c, const ClArgs &a, int frames, ClusterInfo 
 void launch_final(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);
 void launch_median(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);
 int ccl_tile_rows();                 // tile height of k_ccl_tile
+int ccl_tiles(int mask_words, int H); // cluster tiles of a frame of H rows of mask_words words (a tile is one word wide)
 int ccl_request_capacity(int n);     // link requests one tile can emit at neighbor_distance n
 
 // on-GPU disparity (sgm.hip)

@@ -108,6 +108,54 @@ int check_batch(ModContext *c, const ModFrameBatch *in) {
 // launch" — where the clustering kernels keep their launch-wide counters and lists — is the chunk's own
 struct Chunk { int f0, n; };
 
+// frame f0 of a plane whose frames lie `stride` elements apart; a plane the caller did not pass stays null
+template <class T> T *at(T *p, size_t f0, size_t stride) { return p ? p + f0 * stride : nullptr; }
+
+// The cluster scratch (mod_context.h ClusterScratch): allocate, grow requests, carve; begin_cluster_scratch clears.
+hipError_t cluster_alloc(ClusterScratch &s, const ModConfig &cfg, int max_objects) {
+  s.frames = (size_t)cfg.max_frames; s.pixels = (size_t)cfg.max_width * cfg.max_height; s.max_objects = (size_t)max_objects;
+  s.mask_rows = (size_t)mod_mask_words(cfg.max_width) * cfg.max_height; s.tiles = (size_t)ccl_tiles(mod_mask_words(cfg.max_width), cfg.max_height);
+  const size_t F = s.frames, FN = F * s.pixels, FM = F * s.mask_rows, FO = F * s.max_objects, FT = F * s.tiles;
+  HIP_OK(dalloc(s.mask, FM)); HIP_OK(dalloc(s.lroot, FM)); HIP_OK(dalloc(s.zrange, FM));
+  HIP_OK(dalloc(s.parent, FN)); HIP_OK(dalloc(s.rsize, FN)); HIP_OK(dalloc(s.rkey, FN));
+  HIP_OK(dalloc(s.cbox, FO)); HIP_OK(dalloc(s.counters, F * kClusterCounters));
+  HIP_OK(dalloc(s.clusters, 2 * FO)); s.rank_scratch = s.clusters + FO;   // the second halves: stated here, and nowhere else
+  HIP_OK(dalloc(s.mbits, FN)); HIP_OK(dalloc(s.mpix, FN));
+  HIP_OK(dalloc(s.worklist, 2 * FO)); s.tielist = s.worklist + FO;
+  HIP_OK(dalloc(s.tilehdr, FT * kTileHdrWords));
+  return dalloc(s.tilelist, FT);
+}
+
+// room in `requests` for what every tile can emit at neighbor_distance n: grow-only, replaced once `stream` has drained
+hipError_t cluster_grow_requests(ClusterScratch &s, int n, hipStream_t stream) {
+  const size_t need = s.frames * s.tiles * ccl_request_capacity(n);
+  if (need <= s.req_alloc) return hipSuccess;
+  HIP_OK(hipStreamSynchronize(stream));
+  s.requests.reset(); s.req_alloc = 0;
+  HIP_OK(dalloc(s.requests, need));
+  s.req_alloc = need; return hipSuccess;
+}
+
+// A chunk's part of the scratch, of the planes, the mask and the outputs (out == null: the scene-flow launch, which reads only what
+// follows `a`).  The frames of a call lie the camera's strides apart, whatever the capacity.
+struct Carved { ClArgs a; ClusterInfo *rank_scratch; float2 *zrange; int tiles; };   // zrange: a.zrange for its writer (a.zrange is null unless flags_ready); tiles: of a frame
+
+Carved cluster_carve(const Buffers &b, const DevCam &dc, Chunk ch, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool flags_ready, const ModClusterOut *out) {
+  const ClusterScratch &s = b.cluster;
+  const size_t N = (size_t)dc.W * dc.H, f0 = (size_t)ch.f0, MWH = (size_t)dc.mask_words * dc.H, MO = s.max_objects, tiles = (size_t)ccl_tiles(dc.mask_words, dc.H);
+  static const ModClusterOut no_out{}; if (!out) out = &no_out;
+  Carved v{{}, s.rank_scratch + f0 * MO, s.zrange + f0 * MWH, (int)tiles}; ClArgs &a = v.a;
+  a.x = at(pl->x, f0, N); a.y = at(pl->y, f0, N); a.z = at(pl->z, f0, N); a.vx = at(pl->vx, f0, N); a.vy = at(pl->vy, f0, N); a.vz = at(pl->vz, f0, N);
+  a.mask = at(mask, f0, MWH); a.zrange = flags_ready ? v.zrange : nullptr; a.lroot = s.lroot + f0 * MWH;
+  a.parent = s.parent + f0 * N; a.rootlist = (int32_t *)s.mpix.get() + f0 * N; a.rsize = s.rsize + f0 * N; a.rkey = s.rkey + f0 * N;
+  a.cbox = s.cbox + f0 * MO; a.counters = s.counters + f0 * kClusterCounters; a.clusters = s.clusters + f0 * MO;
+  a.mbits = s.mbits + f0 * N; a.mpix = s.mpix + f0 * N; a.worklist = s.worklist + f0 * MO; a.tielist = s.tielist + f0 * MO;
+  a.labels = at(out->labels, f0, N); a.objects = at(out->objects, f0, MO); a.n_objects = at(out->n_objects, f0, 1); a.n_clusters = at(out->n_clusters, f0, 1);
+  a.max_objects = (int32_t)MO; a.req_cap = ccl_request_capacity(dc.n); a.dbg = b.dbg; a.xy_from_z = flags_ready ? 1 : 0;   // only mod_process_dev's fused path hands over its own scene-flow planes
+  a.requests = s.requests + f0 * tiles * (size_t)a.req_cap; a.tilehdr = s.tilehdr + f0 * tiles * kTileHdrWords; a.tilelist = s.tilelist + f0 * tiles;
+  return v;
+}
+
 int check_scene_flow_out(ModContext *c, const ModSceneFlowPlanes *out, bool xy_optional) {
   if (!out || !out->z || !out->vx || !out->vy || !out->vz)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "scene-flow output planes z,vx,vy,vz are required");
@@ -120,23 +168,18 @@ int check_scene_flow_out(ModContext *c, const ModSceneFlowPlanes *out, bool xy_o
 // the scene-flow kernel over one chunk of the batch (the per-frame constants of the WHOLE batch are in c->b.fc by now)
 void enqueue_scene_flow(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *out, uint64_t *mask, bool tile_flags, Chunk ch,
                         hipStream_t s, const InlineConsts *inl = nullptr) {
-  const size_t N = (size_t)c->dc.W * c->dc.H, f0 = (size_t)ch.f0, MWH = (size_t)c->dc.mask_words * c->dc.H;
+  const size_t N = (size_t)c->dc.W * c->dc.H, f0 = (size_t)ch.f0;
+  const bool marks = tile_flags && mask;   // the clustering follows: the kernel's epilogue also marks the cluster tiles that hold a dynamic pixel
+  const Carved cv = cluster_carve(c->b, c->dc, ch, out, mask, marks, nullptr);
   SfArgs a;
   a.dnow = in->disparity_now + f0 * N; a.dprev = in->disparity_prev + f0 * N; a.flow = in->flow + f0 * N * 2;
-  a.x = out->x ? out->x + f0 * N : nullptr; a.y = out->y ? out->y + f0 * N : nullptr;
-  a.z = out->z + f0 * N; a.vx = out->vx + f0 * N; a.vy = out->vy + f0 * N; a.vz = out->vz + f0 * N;
-  a.mask = mask ? mask + f0 * MWH : nullptr;
-  a.aos = out->cloud_aos ? (float4 *)out->cloud_aos + f0 * N * 2 : nullptr;
-  a.depth = out->depth ? out->depth + f0 * N : nullptr;
-  a.sflow = out->static_flow ? out->static_flow + f0 * N * 2 : nullptr;
-  a.fc = c->b.fc + f0;
-  a.tilehdr = nullptr; a.zrange = nullptr; a.tile_rows = ccl_tile_rows(); a.tiles_x = c->dc.mask_words;
-  a.tiles_per_frame = c->dc.mask_words * ((c->dc.H + ccl_tile_rows() - 1) / ccl_tile_rows());
-  a.dbg = c->b.dbg;
-  if (tile_flags && mask) {      // the clustering follows: the kernel's epilogue also marks the cluster tiles that hold a dynamic pixel
-    a.tilehdr = c->b.tilehdr + f0 * 2 * (size_t)a.tiles_per_frame;   // (all zero: ModContext::scratch_clean)
-    a.zrange = c->b.zrange + f0 * MWH; // ... and leaves the depth range of every non-zero mask word's dynamic pixels for the tile stage
-  }
+  a.x = at(out->x, f0, N); a.y = at(out->y, f0, N); a.z = out->z + f0 * N; a.vx = out->vx + f0 * N; a.vy = out->vy + f0 * N; a.vz = out->vz + f0 * N;
+  a.mask = at(mask, f0, (size_t)c->dc.mask_words * c->dc.H);
+  a.aos = at((float4 *)out->cloud_aos, f0, N * 2); a.depth = at(out->depth, f0, N); a.sflow = at(out->static_flow, f0, N * 2);
+  a.fc = c->b.fc + f0; a.dbg = c->b.dbg;
+  a.tilehdr = marks ? cv.a.tilehdr : nullptr;   // (all zero: ModContext::scratch_clean)
+  a.zrange = marks ? cv.zrange : nullptr;       // ... and leaves the depth range of every non-zero mask word's dynamic pixels for the tile stage
+  a.tile_rows = ccl_tile_rows(); a.tiles_x = c->dc.mask_words; a.tiles_per_frame = cv.tiles;
   StageTimer t(c, MOD_STAGE_SCENE_FLOW, s);
   launch_scene_flow(c->dc, a, ch.n, (inl && inl->used) ? inl->v : nullptr, s);
 }
@@ -163,25 +206,9 @@ int check_cluster_io(ModContext *c, const ModSceneFlowPlanes *pl, bool flags_rea
 // The clustering of one chunk on stream s.
 void enqueue_cluster(ModContext *c, Chunk ch, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
                     const ModClusterOut *out, hipStream_t s) {
-  const size_t N = (size_t)c->dc.W * c->dc.H, f0 = (size_t)ch.f0, MWH = (size_t)c->dc.mask_words * c->dc.H, MO = (size_t)c->max_objects;
-  const size_t tiles = (size_t)c->dc.mask_words * ((c->dc.H + ccl_tile_rows() - 1) / ccl_tile_rows());
+  const Carved cv = cluster_carve(c->b, c->dc, ch, pl, mask, flags_ready, out);
+  const ClArgs &a = cv.a;
   const int frames = ch.n;
-  ClArgs a;
-  a.x = pl->x ? pl->x + f0 * N : nullptr; a.y = pl->y ? pl->y + f0 * N : nullptr;
-  a.z = pl->z + f0 * N; a.vx = pl->vx + f0 * N; a.vy = pl->vy + f0 * N; a.vz = pl->vz + f0 * N;
-  a.mask = mask + f0 * MWH; a.zrange = flags_ready ? c->b.zrange + f0 * MWH : nullptr; a.lroot = c->b.lroot + f0 * MWH;
-  a.parent = c->b.parent + f0 * N; a.rootlist = (int32_t *)c->b.mpix.get() + f0 * N;
-  a.labels = out->labels ? out->labels + f0 * N : nullptr; a.rsize = c->b.rsize + f0 * N; a.rkey = c->b.rkey + f0 * N;
-  a.cbox = c->b.cbox + f0 * MO; a.counters = c->b.counters + f0 * 8; a.clusters = c->b.clusters + f0 * MO;
-  a.mbits = c->b.mbits + f0 * N; a.mpix = c->b.mpix + f0 * N;
-  a.worklist = c->b.worklist + f0 * MO; a.tielist = c->b.worklist + (size_t)c->cfg.max_frames * MO + f0 * MO;
-  a.objects = (ModObject *)out->objects + f0 * MO; a.n_objects = out->n_objects + f0;
-  a.n_clusters = out->n_clusters ? out->n_clusters + f0 : nullptr; a.max_objects = c->max_objects; a.dbg = c->b.dbg;
-  a.xy_from_z = flags_ready ? 1 : 0;                  // only mod_process_dev's fused path hands over its own scene-flow planes
-  const int req_cap = ccl_request_capacity(c->prm.neighbor_distance);
-  a.requests = c->b.requests + f0 * tiles * (size_t)req_cap; a.tilehdr = c->b.tilehdr + f0 * tiles * 2; a.tilelist = c->b.tilelist + f0 * tiles;
-  a.req_cap = req_cap;
-  ClusterInfo *const rank_scratch = c->b.clusters + (size_t)c->cfg.max_frames * MO + f0 * MO;   // second half of the allocation
   {
     StageTimer t(c, MOD_STAGE_CCL_TILE, s);
     if (!mask_ready) launch_dynamic_mask(c->dc, frames, a.vx, a.vy, a.vz, (uint64_t *)a.mask, s);
@@ -189,7 +216,7 @@ void enqueue_cluster(ModContext *c, Chunk ch, const ModSceneFlowPlanes *pl, cons
     launch_ccl_tile(c->dc, a, frames, s);                 // (the counters are zero: ModContext::scratch_clean)
   }
   { StageTimer t(c, MOD_STAGE_CCL_LINK, s); launch_ccl_link(c->dc, a, frames, s); }
-  { StageTimer t(c, MOD_STAGE_CCL_MERGE, s); launch_ccl_merge(c->dc, a, frames, rank_scratch, s); }
+  { StageTimer t(c, MOD_STAGE_CCL_MERGE, s); launch_ccl_merge(c->dc, a, frames, cv.rank_scratch, s); }
   { StageTimer t(c, MOD_STAGE_FINAL, s); launch_final(c->dc, a, frames, s); }
   { StageTimer t(c, MOD_STAGE_MEDIAN, s); launch_median(c->dc, a, frames, s); }
 }
@@ -247,6 +274,37 @@ int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPl
   return MOD_OK;
 }
 
+hipError_t reset_dbg(unsigned long long *dbg) {   // the diagnostic counters as a context starts with them: zero, slot 42 (a minimum) all ones
+  HIP_OK(hipMemset(dbg, 0, kDbgWords * sizeof(*dbg))); return hipMemset(dbg + 42, 0xFF, sizeof(*dbg));
+}
+
+// the chunk streams of process_chunked, on cfg->device; a few fork / join rounds, once: the runtime builds the cross-stream
+// signalling of the new streams here, not inside the first call
+hipError_t create_chunk_streams(ModContext *c) {
+  for (int k = 0; k < kMaxChunks - 1; k++) { HIP_OK(hipStreamCreateWithFlags(c->chunk_stream[k].put(), hipStreamNonBlocking)); HIP_OK(hipEventCreateWithFlags(c->ev_join[k].put(), hipEventDisableTiming)); }
+  HIP_OK(hipEventCreateWithFlags(c->ev_fork.put(), hipEventDisableTiming));
+  for (int i = 0; i < 16; i++) {
+    HIP_OK(hipEventRecord(c->ev_fork, c->stream));
+    for (int k = 0; k < kMaxChunks - 1; k++) {
+      HIP_OK(hipStreamWaitEvent(c->chunk_stream[k], c->ev_fork, 0)); HIP_OK(hipEventRecord(c->ev_join[k], c->chunk_stream[k]));
+      HIP_OK(hipStreamWaitEvent(c->stream, c->ev_join[k], 0));
+    }
+  }
+  return hipSuccess;
+}
+
+// what mod_create gives a context whose configuration, capacities and stream are set
+hipError_t create_resources(ModContext *c, const ModConfig &cfg) {
+  HIP_OK(dalloc(c->b.rayx, cfg.max_width + 4)); HIP_OK(dalloc(c->b.rayy, cfg.max_height + 4)); HIP_OK(dalloc(c->b.fc, cfg.max_frames));
+  HIP_OK(cluster_alloc(c->b.cluster, cfg, c->max_objects));   // (tile headers and counters are cleared by the first call: scratch_clean starts false)
+  HIP_OK(dalloc(c->b.dbg, kDbgWords)); HIP_OK(reset_dbg(c->b.dbg));
+  for (int i = 0; i < kRing; i++) {
+    HIP_OK(hipHostMalloc((void **)c->pinned[i].put(), sizeof(FrameConst) * cfg.max_frames, hipHostMallocDefault));
+    HIP_OK(hipEventCreateWithFlags(c->pinned_ev[i].put(), hipEventDisableTiming)); HIP_OK(hipEventRecord(c->pinned_ev[i], c->stream));
+  }
+  return (cfg.batch_chunks ? cfg.batch_chunks : kAutoChunks) >= 2 ? create_chunk_streams(c) : hipSuccess;
+}
+
 }  // namespace
 
 void refresh_devcam(ModContext *c) {
@@ -271,10 +329,9 @@ void refresh_devcam(ModContext *c) {
 }
 
 int begin_cluster_scratch(ModContext *c) {
-  if (!c->scratch_clean) {
-    const size_t tiles = (size_t)c->max_mask_words * ((c->cfg.max_height + ccl_tile_rows() - 1) / ccl_tile_rows());
-    HIP_TRY(c, hipMemsetAsync(c->b.tilehdr, 0, sizeof(int32_t) * 2 * tiles * c->cfg.max_frames, c->stream));
-    HIP_TRY(c, hipMemsetAsync(c->b.counters, 0, sizeof(int32_t) * 8 * c->cfg.max_frames, c->stream));
+  if (const ClusterScratch &s = c->b.cluster; !c->scratch_clean) {   // the clear of the scratch: word 0 of the tile headers, the counters (whole capacity)
+    HIP_TRY(c, hipMemsetAsync(s.tilehdr, 0, sizeof(int32_t) * kTileHdrWords * s.tiles * s.frames, c->stream));
+    HIP_TRY(c, hipMemsetAsync(s.counters, 0, sizeof(int32_t) * kClusterCounters * s.frames, c->stream));
   }
   c->scratch_clean = false;
   return MOD_OK;
@@ -326,60 +383,11 @@ int mod_create(const ModConfig *cfg, ModContext **out_ctx) {
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= cfg->device || cfg->device < 0) return MOD_ERR_NO_DEVICE;
   if (hipSetDevice(cfg->device) != hipSuccess) return MOD_ERR_NO_DEVICE;
   ModContext *c = new ModContext();
-  c->cfg = *cfg;
-  const size_t N = (size_t)cfg->max_width * cfg->max_height;
-  const int F = cfg->max_frames;
-  c->maxN = N;
-  c->max_mask_words = mod_mask_words(cfg->max_width);
-  c->max_objects = cfg->max_objects > 0 ? cfg->max_objects : (int)std::max<size_t>(1, N / 100);
+  c->cfg = *cfg; c->maxN = (size_t)cfg->max_width * cfg->max_height;
+  c->max_objects = cfg->max_objects > 0 ? cfg->max_objects : (int)std::max<size_t>(1, c->maxN / 100);
   if (cfg->stream) c->stream = (hipStream_t)cfg->stream;
   else { if (hipStreamCreate(c->own_stream.put()) != hipSuccess) { delete c; return MOD_ERR_DEVICE; } c->stream = c->own_stream; }
-  const size_t mw = (size_t)F * cfg->max_height * c->max_mask_words;
-  bool ok = true;
-  ok &= dalloc(c->b.rayx, cfg->max_width + 4) == hipSuccess;
-  ok &= dalloc(c->b.rayy, cfg->max_height + 4) == hipSuccess;
-  ok &= dalloc(c->b.fc, F) == hipSuccess;
-  ok &= dalloc(c->b.mask, mw) == hipSuccess;
-  ok &= dalloc(c->b.lroot, mw) == hipSuccess;
-  ok &= dalloc(c->b.zrange, mw) == hipSuccess;
-  ok &= dalloc(c->b.parent, (size_t)F * N) == hipSuccess;
-  ok &= dalloc(c->b.rsize, (size_t)F * N) == hipSuccess;   // 4 + 4 B per pixel of address space, touched only at roots
-  ok &= dalloc(c->b.rkey, (size_t)F * N) == hipSuccess;
-  ok &= dalloc(c->b.cbox, (size_t)F * c->max_objects) == hipSuccess;
-  ok &= dalloc(c->b.counters, (size_t)F * 8) == hipSuccess;
-  ok &= dalloc(c->b.clusters, (size_t)2 * F * c->max_objects) == hipSuccess;
-  ok &= dalloc(c->b.mbits, (size_t)F * N) == hipSuccess;
-  ok &= dalloc(c->b.mpix, (size_t)F * N) == hipSuccess;
-  ok &= dalloc(c->b.worklist, (size_t)2 * F * c->max_objects) == hipSuccess;
-  {
-    const size_t tiles = (size_t)c->max_mask_words * ((cfg->max_height + ccl_tile_rows() - 1) / ccl_tile_rows());
-    ok &= dalloc(c->b.tilehdr, (size_t)F * tiles * 2) == hipSuccess;
-    ok &= dalloc(c->b.tilelist, (size_t)F * tiles) == hipSuccess;
-  }
-  ok &= dalloc(c->b.dbg, kDbgWords) == hipSuccess;
-  if (ok) ok &= hipMemset(c->b.dbg, 0, kDbgWords * 8) == hipSuccess;
-  // (tile headers and counters are cleared by the first call: scratch_clean starts false)
-  if (ok) ok &= hipMemset((char *)c->b.dbg.get() + 42 * 8, 0xFF, 8) == hipSuccess;   // slot 42 is a minimum
-  for (int i = 0; i < kRing && ok; i++) {
-    ok &= hipHostMalloc((void **)c->pinned[i].put(), sizeof(FrameConst) * F, hipHostMallocDefault) == hipSuccess;
-    ok &= hipEventCreateWithFlags(c->pinned_ev[i].put(), hipEventDisableTiming) == hipSuccess;
-    if (ok) ok &= hipEventRecord(c->pinned_ev[i], c->stream) == hipSuccess;
-  }
-  // the chunk streams of process_chunked, on cfg->device; a few fork / join rounds, once: the runtime builds the cross-stream
-  // signalling of the new streams here, not inside the first call
-  if (ok && (cfg->batch_chunks ? cfg->batch_chunks : kAutoChunks) >= 2) {
-    for (int k = 0; k < kMaxChunks - 1 && ok; k++)
-      ok = hipStreamCreateWithFlags(c->chunk_stream[k].put(), hipStreamNonBlocking) == hipSuccess &&
-           hipEventCreateWithFlags(c->ev_join[k].put(), hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(c->ev_fork.put(), hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < 16 && ok; i++) {
-      ok = hipEventRecord(c->ev_fork, c->stream) == hipSuccess;
-      for (int k = 0; k < kMaxChunks - 1 && ok; k++)
-        ok = hipStreamWaitEvent(c->chunk_stream[k], c->ev_fork, 0) == hipSuccess &&
-             hipEventRecord(c->ev_join[k], c->chunk_stream[k]) == hipSuccess && hipStreamWaitEvent(c->stream, c->ev_join[k], 0) == hipSuccess;
-    }
-  }
-  if (!ok) { mod_destroy(c); return MOD_ERR_DEVICE; }
+  if (create_resources(c, c->cfg) != hipSuccess) { mod_destroy(c); return MOD_ERR_DEVICE; }
   *out_ctx = c;
   return MOD_OK;
 }
@@ -388,7 +396,7 @@ void mod_destroy(ModContext *c) {
   if (!c) return;
   // every stream the context uses drains first; then the members' handles release everything (mod_context.h)
   for (hipStream_t q : {c->stream, (hipStream_t)c->pipe.h2d, (hipStream_t)c->pipe.d2h}) if (q) (void)hipStreamSynchronize(q);
-  for (hipStream_t q : c->b.sgm_side) if (q) (void)hipStreamSynchronize(q);
+  for (hipStream_t q : c->b.sgm.side) if (q) (void)hipStreamSynchronize(q);
   for (hipStream_t q : c->chunk_stream) if (q) (void)hipStreamSynchronize(q);
   delete c;
 }
@@ -423,16 +431,7 @@ int mod_set_params(ModContext *c, const ModParams *p) {
   // cluster is ever dropped (the default capacity N/100 covers the reference's whole range cluster_size >= 100)
   if (c->maxN / (size_t)p->cluster_size > (size_t)c->max_objects)
     return fail(c, MOD_ERR_CAPACITY, "ModConfig.max_objects is smaller than max_width*max_height / cluster_size");
-  {   // link-request scratch grows with neighbor_distance
-    const size_t tiles = (size_t)c->max_mask_words * ((c->cfg.max_height + ccl_tile_rows() - 1) / ccl_tile_rows());
-    const size_t need = (size_t)c->cfg.max_frames * tiles * ccl_request_capacity(p->neighbor_distance);
-    if (need > c->b.req_alloc) {
-      HIP_TRY(c, hipStreamSynchronize(c->stream));
-      c->b.requests.reset(); c->b.req_alloc = 0;
-      HIP_TRY(c, dalloc(c->b.requests, need));
-      c->b.req_alloc = need;
-    }
-  }
+  HIP_TRY(c, cluster_grow_requests(c->b.cluster, p->neighbor_distance, c->stream));   // link-request scratch grows with neighbor_distance
   c->prm = *p;
   c->has_prm = true;
   refresh_devcam(c);
@@ -482,7 +481,7 @@ int mod_cluster_dev(ModContext *c, int32_t frames, const ModSceneFlowPlanes *pl,
   if (rc) return rc;
   const bool have = pl && pl->dynamic_mask;
   if ((rc = check_cluster_io(c, pl, false, out)) || (rc = begin_cluster_scratch(c))) return rc;
-  if ((rc = run_cluster(c, frames, pl, have ? pl->dynamic_mask : c->b.mask.get(), have, false, out))) return rc;
+  if ((rc = run_cluster(c, frames, pl, have ? pl->dynamic_mask : c->b.cluster.mask.get(), have, false, out))) return rc;
   c->scratch_clean = true;
   return MOD_OK;
 }
@@ -490,7 +489,7 @@ int mod_cluster_dev(ModContext *c, int32_t frames, const ModSceneFlowPlanes *pl,
 int mod_process_dev(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, const ModClusterOut *out) {
   int rc = check_batch(c, in);
   if (rc) return depth_on_skip(c, rc, in, pl);
-  uint64_t *mask = (pl && pl->dynamic_mask) ? pl->dynamic_mask : c->b.mask.get();
+  uint64_t *mask = (pl && pl->dynamic_mask) ? pl->dynamic_mask : c->b.cluster.mask.get();
   const int chunks = chunk_count(c, in->frames);
   if ((rc = check_scene_flow_out(c, pl, true)) || (rc = check_cluster_io(c, pl, true, out)) || (rc = begin_cluster_scratch(c))) return rc;
   if (chunks > 1) rc = process_chunked(c, in, pl, mask, out, chunks);
@@ -558,9 +557,9 @@ int mod_memcpy_d2h(ModContext *c, void *h, const void *d, uint64_t bytes) {
 // 6 correspondences, 7 hypothesis inlier counts)
 int mod_debug_read(ModContext *c, int which, void *dst, unsigned long long bytes) {
   if (!c || !dst) return MOD_ERR_INVALID_ARGUMENT;
-  const void *src = which == 0 ? (const void *)c->b.mbits : which == 4 ? (const void *)c->b.mpix : which == 1 ? (const void *)c->b.clusters
-                  : which == 5 ? (const void *)c->b.ego_ncorr : which == 6 ? (const void *)c->b.ego_corr : which == 7 ? (const void *)c->b.ego_hcnt
-                  : (const void *)c->b.counters;
+  const void *src = which == 0 ? (const void *)c->b.cluster.mbits : which == 4 ? (const void *)c->b.cluster.mpix : which == 1 ? (const void *)c->b.cluster.clusters
+                  : which == 5 ? (const void *)c->b.ego.ncorr : which == 6 ? (const void *)c->b.ego.corr : which == 7 ? (const void *)c->b.ego.hcnt
+                  : (const void *)c->b.cluster.counters;
   if (!src) return MOD_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
@@ -571,8 +570,7 @@ int mod_debug_counters(ModContext *c, unsigned long long *out32) {
   if (!c || !out32) return MOD_ERR_INVALID_ARGUMENT;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(out32, c->b.dbg, kDbgWords * 8, hipMemcpyDeviceToHost));
-  HIP_TRY(c, hipMemset(c->b.dbg, 0, kDbgWords * 8));
-  HIP_TRY(c, hipMemset((char *)c->b.dbg.get() + 42 * 8, 0xFF, 8));
+  HIP_TRY(c, reset_dbg(c->b.dbg));
   return MOD_OK;
 }
 #endif
