@@ -194,6 +194,38 @@ int  mod_cluster_dev(ModContext *ctx, int32_t frames, const ModSceneFlowPlanes *
  * planes->x and planes->y may both be NULL (objects-only: see ModSceneFlowPlanes). */
 int  mod_process_dev(ModContext *ctx, const ModFrameBatch *in, const ModSceneFlowPlanes *planes, const ModClusterOut *out);
 
+/* Per-cluster member lists, opt-in: what clustering() returns as pcl::IndicesClusters (clusterMap2IndicesCluster,
+ * clusterer_nodelet.cpp:97-117) and what cluster2Marker reads for the ~clusters markers (:119-145).  Context state like
+ * mod_set_disparity_filters.  NULL = off (the default): every call enqueues exactly what it did without this setting — no launch, no
+ * memset, no allocation.
+ *   Which calls write the lists: every later mod_cluster_dev and mod_process_dev, chunked (ModConfig.batch_chunks) or not, for all
+ *     their frames; the synchronous host calls that run the cluster stage, mod_process_frame_host and mod_cluster_cloud_host, as
+ *     frame 0.  Ordered on the context's stream like the other outputs.  The pipelined mod_submit_*_host calls never write the lists
+ *     (several tickets in flight would share one buffer): submits enqueue exactly what they enqueue without the setting.
+ *   offsets: for frame f with K = n_clusters[f] surviving clusters, offsets[f][0] = 0 and offsets[f][k+1] - offsets[f][k] is the size
+ *     of cluster k, k being the label the labels plane carries (the reference's numbering by first_edge_key).  All K clusters are
+ *     listed, accepted as objects or not.  offsets[f][k] = offsets[f][K] for K < k <= max_objects (the context's capacity:
+ *     ModConfig.max_objects, or max_width * max_height / 100 when that was 0).
+ *   indices: indices[f][offsets[f][k] .. offsets[f][k+1]) are cluster k's pixel indices v * W + u in the reference's order: u
+ *     ascending, then v ascending (column-major, :104-114).  Entries of indices and points at and beyond offsets[f][K] are not written.
+ *   points (optional): points[f][i] is the (x, y, z) of pixel indices[f][i], bit for bit what the x, y, z planes hold — NaN
+ *     coordinates of a caller's cloud included.  In an objects-only call (planes->x == planes->y == NULL) x and y are recomputed
+ *     from z and the ray tables with the scene-flow kernel's own two operations, as the cluster stage does for its boxes: identical
+ *     to a six-plane call.
+ *   MOD_ERR_INVALID_ARGUMENT (the setting stays as it was): offsets or indices NULL, reserved != 0.  Every context has a cluster
+ *     stage (max_objects 0 selects the default capacity), so there is no context that refuses the setting as such.
+ * Frames lie max_objects + 1 (offsets), H * W (indices) and 3 * H * W (points) elements apart, H * W being the camera's size at the
+ * call, like the labels plane.  The launches are timed inside MOD_STAGE_FINAL. */
+typedef struct ModClusterMembers {   /* 32 bytes; device pointers; the caller owns them */
+  int32_t *offsets;   /* [frames][max_objects + 1] */
+  int32_t *indices;   /* [frames][H * W] */
+  float   *points;    /* optional [frames][H * W][3]: x, y, z of indices[i], F32 as in the planes */
+  int64_t  reserved;  /* must be 0 */
+} ModClusterMembers;
+int  mod_set_cluster_members(ModContext *ctx, const ModClusterMembers *out);   /* NULL = off (the default) */
+/* *out: the setting in force (zeroed while off); *enabled: 0 / 1.  Either may be NULL. */
+int  mod_get_cluster_members(const ModContext *ctx, ModClusterMembers *out, int32_t *enabled);
+
 /* pcl::toROSMsg / pcl::fromROSMsg payload conversion (scene_flow_constructor.cpp:358-361, clusterer_nodelet.cpp:226). */
 int  mod_pack_cloud_dev(ModContext *ctx, int32_t frames, const ModSceneFlowPlanes *planes, void *cloud_aos);
 int  mod_unpack_cloud_dev(ModContext *ctx, int32_t frames, const void *cloud_aos, const ModSceneFlowPlanes *planes);
@@ -749,7 +781,8 @@ int  mod_memcpy_d2h(ModContext *ctx, void *host_dst, const void *dev_src, uint64
                                      reference numbering: in k_ccl_merge's last workgroup per frame for batches of up
                                      to 16 frames, as k_select behind it for larger ones (a stage of its own, "select",
                                      until ABI version 1)                                                        */
-#define MOD_STAGE_FINAL       4   /* k_final: labels plane + member compaction + cluster boxes                  */
+#define MOD_STAGE_FINAL       4   /* k_final: labels plane + member compaction + cluster boxes; with
+                                     mod_set_cluster_members on, k_cluster_members: the ordered member lists     */
 #define MOD_STAGE_MEDIAN      5   /* k_median + k_median_ties: median-velocity member; object ids               */
 #define MOD_STAGE_CLUSTER_GROUP 6 /* the whole cluster stage of a call, first launch to last (stages 1..5 and, in a chunked
                                      mod_process_dev, the overlap of its chunks: see ModConfig.batch_chunks).  While a timer

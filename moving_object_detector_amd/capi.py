@@ -78,6 +78,7 @@ EXPORTS = [
     "mod_set_side_by_side", "mod_get_side_by_side",
     "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
     "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
+    "mod_set_cluster_members", "mod_get_cluster_members",
 ]
 
 
@@ -237,7 +238,12 @@ class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
 
+class ModClusterMembers(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("indices", C.c_void_p), ("points", C.c_void_p), ("reserved", C.c_int64)]
+
+
 MOD_OBJECT_BYTES = C.sizeof(ModObject)
+assert C.sizeof(ModClusterMembers) == 32
 assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
@@ -332,6 +338,8 @@ def load(require_torch_first: bool = True):
     L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
+    L.mod_set_cluster_members.argtypes = [vp, C.POINTER(ModClusterMembers)]
+    L.mod_get_cluster_members.argtypes = [vp, C.POINTER(ModClusterMembers), C.POINTER(i32)]
     L.mod_pack_cloud_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), vp]
     L.mod_unpack_cloud_dev.argtypes = [vp, i32, vp, C.POINTER(ModSceneFlowPlanes)]
     L.mod_process_frame_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModTransform), C.c_double, vp, vp, vp, i32,

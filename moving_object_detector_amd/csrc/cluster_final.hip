@@ -1,5 +1,7 @@
-// cluster_final.hip — MOD_STAGE_FINAL: k_final, labels plane and member lists (overview: cluster_common.h)
+// cluster_final.hip — MOD_STAGE_FINAL: k_final, labels plane and member lists; k_cluster_members, the lists in the reference's order
+// for the caller (overview: cluster_common.h)
 #include "cluster_common.h"
+#include <algorithm>
 #pragma clang fp contract(off)
 namespace {
 
@@ -189,6 +191,98 @@ __global__ __launch_bounds__(NW * 64) void k_final(DevCam c, ClArgs a) {
     }
   }
 }
+
+// ---- k_cluster_members, opt-in (mod_set_cluster_members): the clusters' member lists in the reference's order (pcl::IndicesClusters of
+// clusterMap2IndicesCluster, clusterer_nodelet.cpp:97-117) ----
+// k_final has compacted every surviving cluster's pixels into mpix[offset .. offset + size), in tile order; k_select laid the
+// segments out in label order (ClusterInfo.offset is the exclusive prefix of the sizes), so offsets[k] IS ClusterInfo.offset and
+// the ordered segment goes to indices + offset — same place, other array.  The kernel runs between k_final and k_median:
+// k_median_ties turns mpix / mbits of a tied cluster into swap lists.
+//
+// Work: the launch's work list, static stride (all eight counter words of frame 0 are taken: no cursor).  A cluster is a chain of
+// three passes over its list (box, pass A, pass B: cluster_common.h, member layout), each a memory round trip per NT * 8 members, with the LDS mask
+// clear and the prefix in between.
+//   * clusters of more than kMemWaveMax members: the whole workgroup, kMemCells cells per run — one round trip per pass up to
+//     8192 members, ~10 workgroup barriers a cluster;
+//   * the others: ONE WAVE each, sixteen clusters per workgroup side by side, kMemWaveCells = kMemCells / 16 cells of the same LDS
+//     arrays per wave and no barrier at all.  A wave needs ceil(size / 512) round trips a pass where the workgroup needs one, so at
+//     kMemWaveMax = 1024 members a wave's chain is at most twice as long as the workgroup's would be — and sixteen of them run in
+//     the time, with none of the 1024-thread barriers that 15 idle waves would sit in.  Street-scene clusters are mostly a few
+//     hundred members in a box of 20 - 60 columns x 1 - 2 row cells, far inside 512 cells; a sparse small cluster whose box has more
+//     cells (a one-row stripe 600 px wide) takes further runs like any other box.  Reasoned from the code, not measured.
+// The large clusters go first: theirs is the longest chain of the launch.
+constexpr int kMemThreads = 1024, kMemCells = 8192, kMemWaveCells = kMemCells / (kMemThreads / 64), kMemWaveMax = 1024;
+
+template <int NT, int CELLS, bool XY_FROM_Z, bool POINTS>
+__device__ __forceinline__ void members_of(const DevCam &c, const ClArgs &a, const ClusterMemberOut &m, uint32_t item, int size, int off,
+                                           uint64_t *cmask, uint32_t *cstart, int *s_box, int *s_sum, int tid) {
+  const size_t N = (size_t)c.W * c.H;
+  const int f = (int)(item / (uint32_t)a.max_objects);
+  const size_t fN = (size_t)f * N;
+  const uint32_t *pix = a.mpix + fN + off;
+  int32_t *dst = m.indices + fN + off;
+  float *pts = POINTS ? m.points + (fN + off) * 3 : nullptr;
+  const float *px = XY_FROM_Z ? nullptr : a.x + fN, *py = XY_FROM_Z ? nullptr : a.y + fN, *pz = a.z + fN;   // (objects-only calls pass no x, y)
+  const MemberBox bx = member_box<NT>(pix, size, (uint32_t)c.W, s_box, tid);
+  [[maybe_unused]] const int placed = member_layout<NT, CELLS>(
+      pix, size, (uint32_t)c.W, bx, cmask, cstart, s_sum, tid, [](int) { return 0u; },
+      [&](int slot, uint32_t p, uint32_t, uint32_t x, uint32_t y) {
+        if (!MOD_CHECK(a, slot >= 0 && slot < size && (size_t)p < N, 11)) return;
+        dst[slot] = (int32_t)p;
+        if (POINTS) {
+          // x, y, z as the planes hold them; in a fused call x, y are the scene-flow kernel's two operations on z again (k_final)
+          const float z = pz[p];
+          float X, Y;
+          if (XY_FROM_Z) { const double zd = (double)z; X = (float)(c.rayx[x] * zd); Y = (float)(c.rayy[y] * zd); }
+          else { X = px[p]; Y = py[p]; }
+          float *o = pts + (size_t)slot * 3;
+          o[0] = X; o[1] = Y; o[2] = z;
+        }
+      },
+      [](int) {});
+  (void)MOD_CHECK(a, placed == size, 14);
+}
+
+template <bool XY_FROM_Z, bool POINTS>
+__global__ __launch_bounds__(kMemThreads) void k_cluster_members(DevCam c, ClArgs a, ClusterMemberOut m, int frames) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const size_t N = (size_t)c.W * c.H;
+  const int nwork = a.counters[6];
+  __shared__ uint64_t lraw[kMemCells + kMemCells / 2];               // 96 KB: the cell masks, then the cells' first slots
+  uint64_t *cmask = &lraw[0];
+  uint32_t *cstart = reinterpret_cast<uint32_t *>(&lraw[kMemCells]);
+  __shared__ int s_box[4], s_sum[kMemThreads / 64 + 1];
+  // ---- offsets: ClusterInfo.offset of the K clusters, the total from K on ----
+  for (int f = blockIdx.x; f < frames; f += gridDim.x) {
+    const ClusterInfo *C = a.clusters + (size_t)f * a.max_objects;
+    const int K = min(a.counters[f * kClusterCounters + 1], a.max_objects);
+    const int total = K > 0 ? C[K - 1].offset + C[K - 1].size : 0;
+    int32_t *o = m.offsets + (size_t)f * (a.max_objects + 1);
+    for (int k = tid; k <= a.max_objects; k += kMemThreads) o[k] = k < K ? C[k].offset : total;
+  }
+  // every segment is checked against the frame before anything is written through it
+  auto segment = [&](uint32_t item, int &size, int &off) {
+    const ClusterInfo *ci = a.clusters + item;       // item = frame * max_objects + cluster
+    size = ci->size; off = ci->offset;
+    return size >= 1 && off >= 0 && (size_t)off + (size_t)size <= N;
+  };
+  // ---- the large clusters: one per turn of the workgroup ----
+  for (int wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
+    const uint32_t item = a.worklist[wi];
+    int size, off;
+    if (!segment(item, size, off) || size <= kMemWaveMax) continue;  // block-uniform
+    members_of<kMemThreads, kMemCells, XY_FROM_Z, POINTS>(c, a, m, item, size, off, cmask, cstart, s_box, s_sum, tid);
+  }
+  __syncthreads();                                   // the LDS arrays change hands
+  // ---- the small ones: one per turn of a wave, in the wave's sixteenth of the arrays ----
+  for (int wi = blockIdx.x * (kMemThreads / 64) + wv; wi < nwork; wi += gridDim.x * (kMemThreads / 64)) {
+    const uint32_t item = a.worklist[wi];
+    int size, off;
+    if (!segment(item, size, off) || size > kMemWaveMax) continue;   // wave-uniform
+    members_of<64, kMemWaveCells, XY_FROM_Z, POINTS>(c, a, m, item, size, off, cmask + wv * kMemWaveCells, cstart + wv * kMemWaveCells, nullptr,
+                                                     nullptr, lane);
+  }
+}
 }  // namespace
 
 void launch_final(const DevCam &c, const ClArgs &a, int frames, hipStream_t s) {
@@ -197,4 +291,18 @@ void launch_final(const DevCam &c, const ClArgs &a, int frames, hipStream_t s) {
   constexpr int kFinalWaves = 2;
   if (a.xy_from_z) hipLaunchKernelGGL((k_final<kTileH, kFinalWaves, true>), tile_grid(c, frames), dim3(64, kFinalWaves, 1), 0, s, c, a);
   else hipLaunchKernelGGL((k_final<kTileH, kFinalWaves, false>), tile_grid(c, frames), dim3(64, kFinalWaves, 1), 0, s, c, a);
+}
+
+void launch_cluster_members(const DevCam &c, const ClArgs &a, const ClusterMemberOut &m, int frames, hipStream_t s) {
+  // a workgroup takes 96 KB of LDS: one per CU at most, fewer for small batches (a frame has tens of clusters, sixteen small ones
+  // go side by side in a workgroup)
+  const dim3 grid(std::min(256, frames * 4)), block(kMemThreads);
+  const bool pts = m.points != nullptr;
+  if (a.xy_from_z) {
+    if (pts) hipLaunchKernelGGL((k_cluster_members<true, true>), grid, block, 0, s, c, a, m, frames);
+    else hipLaunchKernelGGL((k_cluster_members<true, false>), grid, block, 0, s, c, a, m, frames);
+  } else {
+    if (pts) hipLaunchKernelGGL((k_cluster_members<false, true>), grid, block, 0, s, c, a, m, frames);
+    else hipLaunchKernelGGL((k_cluster_members<false, false>), grid, block, 0, s, c, a, m, frames);
+  }
 }

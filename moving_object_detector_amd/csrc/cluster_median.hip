@@ -407,20 +407,9 @@ __device__ __forceinline__ void finalize_frame(const DevCam &c, const ClArgs &a,
   a.n_objects[f] = n;
 }
 
-// Row of pixel index p (the return value) and its column, by an integer divide.  (Images below 2^24 pixels used to take the row as
-// (uint32_t)(((float)p + 0.5f) * (1.0f / W)).  That is NOT exact: the rounding of 1.0f / W and of the product outgrows the 0.5 / W
-// margin from about p = 2^22 on.  At 3840 x 2160 the 834 last-column pixels from row 1326 down came out as row + 1 with column
-// 0xffffffff, fell out of the column-major layout, and the replay sorted a list with stale entries.  tests/models/row_model.py keeps
-// that formula and tests/test_row_model.py its failures.  Both passes that call this wait on memory, not on the divide.)
-__device__ __forceinline__ uint32_t tie_row_col(uint32_t p, uint32_t W, uint32_t &x) {
-  const uint32_t y = p / W;
-  x = p - y * W;
-  return y;
-}
-
 __global__ __launch_bounds__(kTieThreads) void k_median_ties(DevCam c, ClArgs a, int frames) {
   using namespace introsort_emul;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const size_t N = (size_t)c.W * c.H;
   const int nwork = a.counters[7];
   // 96 KB of LDS, used twice: while the members are laid out, as kTieLds 64-bit cell masks + kTieLds cell offsets; during the
@@ -430,7 +419,7 @@ __global__ __launch_bounds__(kTieThreads) void k_median_ties(DevCam c, ClArgs a,
   uint16_t *lA = reinterpret_cast<uint16_t *>(lval + kTieLds), *lB = lA + kTieLds;
   uint64_t *cmask = &lraw[0];
   uint32_t *cstart = reinterpret_cast<uint32_t *>(&lraw[kTieLds]);
-  __shared__ int s_box[4];
+  __shared__ int s_box[4], s_lay[kTieThreads / 64 + 1];
   __shared__ TieShared sh;
   for (int wi = blockIdx.x; wi < nwork; wi += gridDim.x) {
     const uint32_t item = a.tielist[wi];
@@ -444,104 +433,18 @@ __global__ __launch_bounds__(kTieThreads) void k_median_ties(DevCam c, ClArgs a,
     uint32_t *val = (uint32_t *)(a.rsize + fN) + off;
     uint32_t *Apos = a.mbits + fN + off, *Bpos = a.mpix + fN + off;
     // ---- image-space bounding box of the cluster (from its member list, before that list becomes scratch) ----
-    if (tid == 0) { s_box[0] = 0x7fffffff; s_box[1] = 0; s_box[2] = 0x7fffffff; s_box[3] = 0; }
-    __syncthreads();
-    {
-      uint32_t x0 = 0xffffffffu, x1 = 0, y0 = 0xffffffffu, y1 = 0;
-      for (int i0 = tid; i0 < size; i0 += kTieThreads * 4) {
-        uint32_t p4[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) p4[u] = Bpos[min(i0 + u * kTieThreads, size - 1)];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          uint32_t x;
-          const uint32_t y = tie_row_col(p4[u], (uint32_t)c.W, x);
-          x0 = x < x0 ? x : x0; x1 = x > x1 ? x : x1; y0 = y < y0 ? y : y0; y1 = y > y1 ? y : y1;
-        }
-      }
-      x0 = wave_min_u32(x0); x1 = wave_max_u32(x1); y0 = wave_min_u32(y0); y1 = wave_max_u32(y1);
-      if (lane == 0 && x0 != 0xffffffffu) { atomicMin(&s_box[0], (int)x0); atomicMax(&s_box[1], (int)x1); atomicMin(&s_box[2], (int)y0); atomicMax(&s_box[3], (int)y1); }
-    }
-    __syncthreads();
+    const MemberBox bx = member_box<kTieThreads>(Bpos, size, (uint32_t)c.W, s_box, tid);
     PHASE_STAMP(20)
     if (MOD_ABLATE(c, 1 << 20)) continue;
-    const int xmin = s_box[0], ymin = s_box[2], ymax = s_box[3], ncols = s_box[1] - xmin + 1;
-    // ---- members in column-major order (clusterMap2IndicesCluster's order, :97-117) ----
-    // Fast path, straight from the member list (two coalesced passes, no image reads): the bounding box is cut into cells of
-    // one column x 64 rows; pass A sets bit (row & 63) of a member's cell, a prefix over the cells in column-major order gives
-    // every cell its first slot, pass B puts member (column, row) at slot = start[cell] + popcount(mask[cell] below its bit).
-    const int nseg64 = (ymax - ymin + 64) / 64;
+    // ---- members in column-major order (clusterMap2IndicesCluster's order, :97-117): cluster_common.h member_layout, kTieLds cells per run.
+    // (Round 1 scanned the labels plane for boxes with more cells; the member list needs neither that plane nor the velocities again.)
+    // The keys are the ||v|| bits as k_final computed them (norm3_f32) ----
     {
-      // Boxes with more than kTieLds cells (one tied cluster across most of a large image) go through the same two passes once
-      // per run of kTieLds cells in column-major order; `base` carries the members of the runs before.  (Round 1 scanned the
-      // labels plane for such boxes; the member list needs neither that plane nor the velocities again.)
-      const int ncell = ncols * nseg64;              // < 2^21 + W: W * H < 2^27
-      auto cell_of = [&](uint32_t p, int &bit) {
-        uint32_t x;
-        const uint32_t y = tie_row_col(p, (uint32_t)c.W, x);
-        const int ry = (int)y - ymin;
-        bit = ry & 63;
-        return ((int)x - xmin) * nseg64 + (ry >> 6);
-      };
-      int base = 0;
-      for (int g0 = 0; g0 < ncell; g0 += kTieLds) {  // block-uniform
-        const int ncl = min(kTieLds, ncell - g0);
-        for (int i = tid; i < kTieLds; i += kTieThreads) cmask[i] = 0ull;
-        __syncthreads();
-        for (int i0 = tid; i0 < size; i0 += kTieThreads * 8) {
-          uint32_t p8[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) p8[u] = Bpos[min(i0 + u * kTieThreads, size - 1)];
-#pragma unroll
-          for (int u = 0; u < 8; u++)
-            if (i0 + u * kTieThreads < size) {
-              int bit;
-              const int cl = cell_of(p8[u], bit) - g0;
-              if (cl >= 0 && cl < ncl) atomicOr((unsigned long long *)&cmask[cl], 1ull << bit);
-            }
-        }
-        __syncthreads();
-        PHASE_STAMP(21)
-        {   // exclusive prefix of the cell populations; thread t owns cells CPT t .. CPT t + CPT - 1
-          constexpr int CPT = kTieLds / kTieThreads;
-          static_assert(CPT * kTieThreads == kTieLds, "every thread owns the same number of cells");
-          int cnt[CPT], tot = 0;
-#pragma unroll
-          for (int u = 0; u < CPT; u++) { const int ci2 = tid * CPT + u; cnt[u] = ci2 < ncl ? __popcll((unsigned long long)cmask[ci2]) : 0; tot += cnt[u]; }
-          int incl = tot;
-          for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-          if (lane == 63) sh.cntA[wv] = incl;
-          __syncthreads();
-          if (tid == 0) { int run = base; for (int t = 0; t < kTieThreads / 64; t++) { const int x = sh.cntA[t]; sh.cntA[t] = run; run += x; } sh.cntB[0] = run; }
-          __syncthreads();
-          int run = sh.cntA[wv] + incl - tot;
-#pragma unroll
-          for (int u = 0; u < CPT; u++) { cstart[tid * CPT + u] = (uint32_t)run; run += cnt[u]; }
-          base = sh.cntB[0];
-        }
-        __syncthreads();
-        for (int i0 = tid; i0 < size; i0 += kTieThreads * 8) {
-          uint32_t p8[8], k8[8];
-#pragma unroll
-          for (int u = 0; u < 8; u++) { const int i = min(i0 + u * kTieThreads, size - 1); p8[u] = Bpos[i]; k8[u] = Apos[i]; }
-#pragma unroll
-          for (int u = 0; u < 8; u++)
-            if (i0 + u * kTieThreads < size) {
-              int bit;
-              const int cl = cell_of(p8[u], bit) - g0;
-              if (cl >= 0 && cl < ncl) {
-                const int slot = (int)cstart[cl] + __popcll((unsigned long long)(cmask[cl] & ((1ull << bit) - 1ull)));
-                if (MOD_CHECK(a, slot >= 0 && slot < size, 11)) {
-                  key[slot] = k8[u];                    // ||v|| bits as k_final computed them (norm3_f32)
-                  val[slot] = p8[u];
-                }
-              }
-            }
-        }
-        __syncthreads();
-        PHASE_STAMP(22)
-      }
-      (void)MOD_CHECK(a, base == size, 14);          // every member lies in exactly one cell
+      [[maybe_unused]] const int placed = member_layout<kTieThreads, kTieLds>(
+          Bpos, size, (uint32_t)c.W, bx, cmask, cstart, s_lay, tid, [&](int i) { return Apos[i]; },
+          [&](int slot, uint32_t p, uint32_t k2, uint32_t, uint32_t) { if (MOD_CHECK(a, slot >= 0 && slot < size, 11)) { key[slot] = k2; val[slot] = p; } },
+          [&](int i) { PHASE_STAMP(21 + i) });
+      (void)MOD_CHECK(a, placed == size, 14);        // every member lies in exactly one cell
     }
     PHASE_STAMP(23)
     if (MOD_ABLATE(c, 1 << 22)) continue;

@@ -124,7 +124,7 @@ static int finish_frame(ModContext *c, Pipe::Slot &s, Pipe::RingPlane &now, cons
   const ModSceneFlowPlanes pl = planes_at(s.planes, N, o.cloud_aos ? s.aos.get() : nullptr);
   const ModClusterOut out = cluster_out(s, o.labels);
   const bool cluster = o.labels || o.objects;     // neither asked for: the scene-flow stage alone (see mod_process_frame_host)
-  int rc = cluster ? mod_process_dev(c, &in, &pl, &out) : scene_flow_staged(c, &in, &pl);
+  int rc = cluster ? process_dev(c, &in, &pl, &out, nullptr) : scene_flow_staged(c, &in, &pl);   // (a ticketed frame never writes the member lists)
   if (rc) return rc;
   HIP_TRY(c, hipEventRecord(s.ev_done, c->stream));
   // results: their own stream
@@ -449,7 +449,7 @@ int mod_cluster_cloud_host(ModContext *c, const void *cloud, int32_t width, int3
   launch_unpack(N, h.aos, pl.x, pl.y, pl.z, pl.vx, pl.vy, pl.vz, c->stream);
   HIP_TRY(c, hipGetLastError());
   const ModClusterOut out = cluster_out(h, labels);
-  if ((rc = begin_cluster_scratch(c)) || (rc = run_cluster(c, 1, &pl, c->b.cluster.mask, false, false, &out))) return rc;
+  if ((rc = begin_cluster_scratch(c)) || (rc = run_cluster(c, 1, &pl, c->b.cluster.mask, false, false, &out, cluster_members(c)))) return rc;
   c->scratch_clean = true;
   return fetch_cluster_results(c, labels, objects, max_objects, n_objects);
 }

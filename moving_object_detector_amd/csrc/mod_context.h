@@ -116,6 +116,9 @@ struct ModContext {
   bool side_by_side = false;                // mod_set_side_by_side: one message holds both eyes; read when a call / submit is made
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
+  // mod_set_cluster_members: read by the calls that write the lists when they enqueue the cluster stage (members_on false: off)
+  ModClusterMembers members{};
+  bool members_on = false;
   int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
   // mod_set_rectification: the calibrations and, per eye, the map in HBM with the window and the distortion model it was built for
   // (ensure_rectify_map builds it at the next use after the window, the calibration or the model changed, never under a frame in flight)
@@ -276,8 +279,13 @@ inline int construct_skip(bool flow, bool prev, bool transform, bool now) {
 // mod_sf.hip
 void refresh_devcam(ModContext *c);
 int begin_cluster_scratch(ModContext *c);
+// mem: where the member lists of the call's frames go, or null (none are written)
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
-                const ModClusterOut *out);
+                const ModClusterOut *out, const ModClusterMembers *mem);
+// mod_process_dev with the member lists stated by the caller: the setting in force for the calls that write them (cluster_members),
+// null for the pipelined submits — several tickets in flight would share one buffer
+int process_dev(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, const ModClusterOut *out, const ModClusterMembers *mem);
+inline const ModClusterMembers *cluster_members(const ModContext *c) { return c->members_on ? &c->members : nullptr; }
 // the scene-flow stage of the host entry points: their SoA planes are internal staging that no caller sees (the cloud leaves as
 // 32-byte records straight from the kernel's registers), so the x and y planes are not written at all
 int scene_flow_staged(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *out);

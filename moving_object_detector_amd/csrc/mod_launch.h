@@ -77,6 +77,10 @@ void launch_ccl_link(const DevCam &c, const ClArgs &a, int frames, hipStream_t s
 void launch_ccl_merge(const DevCam &c, const ClArgs &a, int frames, ClusterInfo *rank_scratch, hipStream_t s);   // + size filter
 void launch_final(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);
 void launch_median(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);
+// The member lists of the launch's clusters (ModClusterMembers, moved to the launch's first frame): offsets [F][max_objects + 1],
+// indices [F][N], points [F][N][3] or null.  Between launch_final and launch_median: k_median_ties reuses the arrays it reads
+struct ClusterMemberOut { int32_t *offsets, *indices; float *points; };
+void launch_cluster_members(const DevCam &c, const ClArgs &a, const ClusterMemberOut &m, int frames, hipStream_t s);
 int ccl_tile_rows();                 // tile height of k_ccl_tile
 int ccl_tiles(int mask_words, int H); // cluster tiles of a frame of H rows of mask_words words (a tile is one word wide)
 int ccl_request_capacity(int n);     // link requests one tile can emit at neighbor_distance n

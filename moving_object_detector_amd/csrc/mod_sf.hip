@@ -138,13 +138,15 @@ hipError_t cluster_grow_requests(ClusterScratch &s, int n, hipStream_t stream) {
 
 // A chunk's part of the scratch, of the planes, the mask and the outputs (out == null: the scene-flow launch, which reads only what
 // follows `a`).  The frames of a call lie the camera's strides apart, whatever the capacity.
-struct Carved { ClArgs a; ClusterInfo *rank_scratch; float2 *zrange; int tiles; };   // zrange: a.zrange for its writer (a.zrange is null unless flags_ready); tiles: of a frame
+struct Carved { ClArgs a; ClusterInfo *rank_scratch; float2 *zrange; int tiles; ClusterMemberOut members; };   // zrange: a.zrange for its writer (a.zrange is null unless flags_ready); tiles: of a frame; members: all null unless the call writes the lists
 
-Carved cluster_carve(const Buffers &b, const DevCam &dc, Chunk ch, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool flags_ready, const ModClusterOut *out) {
+Carved cluster_carve(const Buffers &b, const DevCam &dc, Chunk ch, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool flags_ready, const ModClusterOut *out,
+                     const ModClusterMembers *mem) {
   const ClusterScratch &s = b.cluster;
   const size_t N = (size_t)dc.W * dc.H, f0 = (size_t)ch.f0, MWH = (size_t)dc.mask_words * dc.H, MO = s.max_objects, tiles = (size_t)ccl_tiles(dc.mask_words, dc.H);
   static const ModClusterOut no_out{}; if (!out) out = &no_out;
-  Carved v{{}, s.rank_scratch + f0 * MO, s.zrange + f0 * MWH, (int)tiles}; ClArgs &a = v.a;
+  Carved v{{}, s.rank_scratch + f0 * MO, s.zrange + f0 * MWH, (int)tiles, {}}; ClArgs &a = v.a;
+  if (mem) v.members = {at(mem->offsets, f0, MO + 1), at(mem->indices, f0, N), at(mem->points, f0, 3 * N)};
   a.x = at(pl->x, f0, N); a.y = at(pl->y, f0, N); a.z = at(pl->z, f0, N); a.vx = at(pl->vx, f0, N); a.vy = at(pl->vy, f0, N); a.vz = at(pl->vz, f0, N);
   a.mask = at(mask, f0, MWH); a.zrange = flags_ready ? v.zrange : nullptr; a.lroot = s.lroot + f0 * MWH;
   a.parent = s.parent + f0 * N; a.rootlist = (int32_t *)s.mpix.get() + f0 * N; a.rsize = s.rsize + f0 * N; a.rkey = s.rkey + f0 * N;
@@ -170,7 +172,7 @@ void enqueue_scene_flow(ModContext *c, const ModFrameBatch *in, const ModSceneFl
                         hipStream_t s, const InlineConsts *inl = nullptr) {
   const size_t N = (size_t)c->dc.W * c->dc.H, f0 = (size_t)ch.f0;
   const bool marks = tile_flags && mask;   // the clustering follows: the kernel's epilogue also marks the cluster tiles that hold a dynamic pixel
-  const Carved cv = cluster_carve(c->b, c->dc, ch, out, mask, marks, nullptr);
+  const Carved cv = cluster_carve(c->b, c->dc, ch, out, mask, marks, nullptr, nullptr);
   SfArgs a;
   a.dnow = in->disparity_now + f0 * N; a.dprev = in->disparity_prev + f0 * N; a.flow = in->flow + f0 * N * 2;
   a.x = at(out->x, f0, N); a.y = at(out->y, f0, N); a.z = out->z + f0 * N; a.vx = out->vx + f0 * N; a.vy = out->vy + f0 * N; a.vz = out->vz + f0 * N;
@@ -203,10 +205,10 @@ int check_cluster_io(ModContext *c, const ModSceneFlowPlanes *pl, bool flags_rea
   return MOD_OK;
 }
 
-// The clustering of one chunk on stream s.
+// The clustering of one chunk on stream s.  mem: where the member lists go (mod_set_cluster_members), or null: none are written
 void enqueue_cluster(ModContext *c, Chunk ch, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
-                    const ModClusterOut *out, hipStream_t s) {
-  const Carved cv = cluster_carve(c->b, c->dc, ch, pl, mask, flags_ready, out);
+                    const ModClusterOut *out, const ModClusterMembers *mem, hipStream_t s) {
+  const Carved cv = cluster_carve(c->b, c->dc, ch, pl, mask, flags_ready, out, mem);
   const ClArgs &a = cv.a;
   const int frames = ch.n;
   {
@@ -217,7 +219,11 @@ void enqueue_cluster(ModContext *c, Chunk ch, const ModSceneFlowPlanes *pl, cons
   }
   { StageTimer t(c, MOD_STAGE_CCL_LINK, s); launch_ccl_link(c->dc, a, frames, s); }
   { StageTimer t(c, MOD_STAGE_CCL_MERGE, s); launch_ccl_merge(c->dc, a, frames, cv.rank_scratch, s); }
-  { StageTimer t(c, MOD_STAGE_FINAL, s); launch_final(c->dc, a, frames, s); }
+  {
+    StageTimer t(c, MOD_STAGE_FINAL, s);
+    launch_final(c->dc, a, frames, s);
+    if (mem) launch_cluster_members(c->dc, a, cv.members, frames, s);   // before launch_median: the tie replay reuses the member arrays
+  }
   { StageTimer t(c, MOD_STAGE_MEDIAN, s); launch_median(c->dc, a, frames, s); }
 }
 
@@ -247,7 +253,8 @@ int chunk_count(const ModContext *c, int frames) {
 // code again (commit d9702f0 of round 5 has them: ModConfig.batch_chunks bits 8 and 9): chains held one kernel apart by events — no better than free-running ones; 3 or
 // 4 chunks like 2; the scene-flow kernel cut into the chunks too — +0.5 ... +3 % (it is bandwidth-bound throughout and gains
 // nothing from company), so it stays ONE launch over the whole batch ahead of the chunks.
-int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, uint64_t *mask, const ModClusterOut *out, int C) {
+int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, uint64_t *mask, const ModClusterOut *out,
+                    const ModClusterMembers *mem, int C) {
   int rc = upload_frame_consts(c, in, nullptr);
   if (rc) return rc;
   enqueue_scene_flow(c, in, pl, mask, true, Chunk{0, in->frames}, c->stream);
@@ -260,7 +267,7 @@ int process_chunked(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPl
     hipStream_t s = k ? c->chunk_stream[k - 1] : c->stream;
     if (k && (e = hipStreamWaitEvent(s, c->ev_fork, 0)) != hipSuccess) break;
     started = k + 1;
-    enqueue_cluster(c, ch, pl, mask, true, true, out, s);
+    enqueue_cluster(c, ch, pl, mask, true, true, out, mem, s);
   }
   // join every chunk stream that has started, after a failure too: the next call's scratch memsets (begin_cluster_scratch) must
   // queue behind the cluster kernels already enqueued
@@ -338,11 +345,11 @@ int begin_cluster_scratch(ModContext *c) {
 }
 
 int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const uint64_t *mask, bool mask_ready, bool flags_ready,
-                const ModClusterOut *out) {
+                const ModClusterOut *out, const ModClusterMembers *mem) {
   int rc = check_cluster_io(c, pl, flags_ready, out);
   if (rc) return rc;
   StageTimer t(c, MOD_STAGE_CLUSTER_GROUP, c->stream);
-  enqueue_cluster(c, Chunk{0, frames}, pl, mask, mask_ready, flags_ready, out, c->stream);
+  enqueue_cluster(c, Chunk{0, frames}, pl, mask, mask_ready, flags_ready, out, mem, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
@@ -481,23 +488,46 @@ int mod_cluster_dev(ModContext *c, int32_t frames, const ModSceneFlowPlanes *pl,
   if (rc) return rc;
   const bool have = pl && pl->dynamic_mask;
   if ((rc = check_cluster_io(c, pl, false, out)) || (rc = begin_cluster_scratch(c))) return rc;
-  if ((rc = run_cluster(c, frames, pl, have ? pl->dynamic_mask : c->b.cluster.mask.get(), have, false, out))) return rc;
+  if ((rc = run_cluster(c, frames, pl, have ? pl->dynamic_mask : c->b.cluster.mask.get(), have, false, out, cluster_members(c)))) return rc;
   c->scratch_clean = true;
   return MOD_OK;
 }
 
 int mod_process_dev(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, const ModClusterOut *out) {
+  return process_dev(c, in, pl, out, c ? cluster_members(c) : nullptr);
+}
+
+int mod_set_cluster_members(ModContext *c, const ModClusterMembers *m) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (m && (!m->offsets || !m->indices)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster members: offsets and indices are required");
+  if (m && m->reserved != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster members: reserved must be 0");
+  c->members_on = m != nullptr;
+  c->members = m ? *m : ModClusterMembers{};
+  return MOD_OK;
+}
+int mod_get_cluster_members(const ModContext *c, ModClusterMembers *m, int32_t *enabled) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (m) *m = c->members;
+  if (enabled) *enabled = c->members_on ? 1 : 0;
+  return MOD_OK;
+}
+
+}  // extern "C"
+
+int process_dev(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, const ModClusterOut *out, const ModClusterMembers *mem) {
   int rc = check_batch(c, in);
   if (rc) return depth_on_skip(c, rc, in, pl);
   uint64_t *mask = (pl && pl->dynamic_mask) ? pl->dynamic_mask : c->b.cluster.mask.get();
   const int chunks = chunk_count(c, in->frames);
   if ((rc = check_scene_flow_out(c, pl, true)) || (rc = check_cluster_io(c, pl, true, out)) || (rc = begin_cluster_scratch(c))) return rc;
-  if (chunks > 1) rc = process_chunked(c, in, pl, mask, out, chunks);
-  else if (!(rc = run_scene_flow(c, in, pl, mask, true, true))) rc = run_cluster(c, in->frames, pl, mask, true, true, out);
+  if (chunks > 1) rc = process_chunked(c, in, pl, mask, out, mem, chunks);
+  else if (!(rc = run_scene_flow(c, in, pl, mask, true, true))) rc = run_cluster(c, in->frames, pl, mask, true, true, out, mem);
   if (rc) return rc;
   c->scratch_clean = true;
   return MOD_OK;
 }
+
+extern "C" {
 
 int mod_pack_cloud_dev(ModContext *c, int32_t frames, const ModSceneFlowPlanes *pl, void *aos) {
   int rc = check_ready(c, frames);

@@ -1,10 +1,13 @@
 // clusterer_nodelet.hpp — host-side mirror of scene_flow_clusterer::ClustererNodelet
 // (scene_flow_clusterer/include/clusterer_nodelet.h:37-108): dataCB() on a PointCloud2 of pcl::PointXYZVelocity,
 // reconfigureCB(), and the MovingObjectArray it publishes.  clustering() and cluster2MovingObject() run on the GPU
-// through the C ABI (include/mod_sf.h).  Markers / colour image (debug visualisation) are out of scope; the labels
-// plane returned here is what they are drawn from.
+// through the C ABI (include/mod_sf.h).  clustering() also returns the pcl::IndicesClusters and the points cluster2Marker puts
+// into the ~clusters markers (mod_set_cluster_members); the markers' colours (ColorSet) and the colour image (debug
+// visualisation) are out of scope; the labels plane returned here is what the image is drawn from.
 #pragma once
+#include <array>
 #include <stdexcept>
+#include <vector>
 
 #include "messages.hpp"
 
@@ -52,8 +55,56 @@ class ClustererNodelet {
 
   void setMaxObjects(int n) { max_objects_ = n; }
 
+  // clustering() (clusterer_nodelet.cpp:85-95) asked for its result: dataCB, and with it `clusters` = the pcl::IndicesClusters
+  // content (clusterMap2IndicesCluster, :97-117: per surviving cluster its pixel indices, column-major) and, when `marker_points`
+  // is not null, per cluster the (x, y, z) cluster2Marker pushes into marker.points (:119-145; F32 coordinates widened to F64).
+  // context_max_objects: the capacity the context was created with (ModConfig.max_objects, or max_width * max_height / 100 when
+  // that was 0) — the stride of the offsets.  Only the offsets and the used prefix of the lists come back from the device.
+  typedef std::vector<std::vector<int>> IndicesClusters;
+  typedef std::vector<std::vector<std::array<double, 3>>> MarkerPoints;
+  void clustering(const mod_host::PointCloud2 &input_pc_msg, int context_max_objects, IndicesClusters *clusters, MarkerPoints *marker_points,
+                  mod_host::MovingObjectArray *moving_objects = nullptr, std::vector<int32_t> *cluster_map = nullptr) {
+    const size_t n = (size_t)input_pc_msg.width * input_pc_msg.height;
+    DeviceLists dev(ctx_, (size_t)context_max_objects + 1, n, marker_points != nullptr);
+    ModClusterMembers m{dev.offsets, dev.indices, dev.points, 0};
+    check(mod_set_cluster_members(ctx_, &m));
+    struct Off { ModContext *c; ~Off() { (void)mod_set_cluster_members(c, nullptr); } } off{ctx_};   // the setting does not outlive the buffers
+    dataCB(input_pc_msg, moving_objects, cluster_map);
+    std::vector<int32_t> offsets((size_t)context_max_objects + 1);
+    check(mod_memcpy_d2h(ctx_, offsets.data(), dev.offsets, sizeof(int32_t) * offsets.size()));
+    size_t K = 0;                        // every surviving cluster has members: the offsets rise up to K, then stay
+    while (K + 1 < offsets.size() && offsets[K + 1] > offsets[K]) K++;
+    const size_t used = (size_t)offsets[K];
+    std::vector<int32_t> idx(used);
+    std::vector<float> pts(marker_points ? 3 * used : 0);
+    if (used) check(mod_memcpy_d2h(ctx_, idx.data(), dev.indices, sizeof(int32_t) * used));
+    if (used && marker_points) check(mod_memcpy_d2h(ctx_, pts.data(), dev.points, sizeof(float) * 3 * used));
+    if (clusters) clusters->assign(K, std::vector<int>());
+    if (marker_points) marker_points->assign(K, std::vector<std::array<double, 3>>());
+    for (size_t k = 0; k < K; k++)
+      for (int32_t i = offsets[k]; i < offsets[k + 1]; i++) {
+        if (clusters) (*clusters)[k].push_back(idx[i]);
+        if (marker_points) (*marker_points)[k].push_back({(double)pts[3 * i], (double)pts[3 * i + 1], (double)pts[3 * i + 2]});
+      }
+  }
+
  private:
   void check(int rc) { if (rc < 0) throw std::runtime_error(std::string("libmod_sf: ") + mod_last_error(ctx_)); }
+  // the device buffers of one clustering() call
+  struct DeviceLists {
+    ModContext *c; int32_t *offsets = nullptr, *indices = nullptr; float *points = nullptr;
+    DeviceLists(ModContext *ctx, size_t n_off, size_t n, bool pts) : c(ctx) {
+      void *p = nullptr;
+      bool ok = mod_malloc(c, sizeof(int32_t) * n_off, &p) == MOD_OK; offsets = (int32_t *)p; p = nullptr;
+      ok = ok && mod_malloc(c, sizeof(int32_t) * n, &p) == MOD_OK; indices = (int32_t *)p; p = nullptr;
+      if (pts) { ok = ok && mod_malloc(c, sizeof(float) * 3 * n, &p) == MOD_OK; points = (float *)p; }
+      if (!ok) { release(); throw std::runtime_error("libmod_sf: no device memory for the cluster lists"); }
+    }
+    ~DeviceLists() { release(); }
+    void release() { for (void *p : {(void *)offsets, (void *)indices, (void *)points}) if (p) (void)mod_free(c, p); offsets = indices = nullptr; points = nullptr; }
+    DeviceLists(const DeviceLists &) = delete;
+    DeviceLists &operator=(const DeviceLists &) = delete;
+  };
   ModContext *ctx_;
   int max_objects_ = 1024;
 };

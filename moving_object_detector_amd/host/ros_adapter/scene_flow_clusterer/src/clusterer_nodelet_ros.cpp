@@ -2,7 +2,9 @@
 // base nodelet::Nodelet: nodelet_plugins.xml:3-4, clusterer_nodelet.cpp:5) with clustering() on an MI355X.  Same subscription
 // (`scene_flow`, queue 10, on the nodelet's single-threaded callback queue, clusterer_nodelet.cpp:25,35), same `~moving_objects`
 // topic gated on getNumSubscribers() (:237-238), same dynamic_reconfigure server (:27-29).  `~clusters` (MarkerArray) and
-// `~clusters_image` are debugging views drawn from the label plane this call can return; they are not rendered here.
+// `~clusters_image` are debugging views and are not published by this shell: `~clusters_image` is drawn from the label plane this
+// call can return, `~clusters` from ClustererNodelet::clustering() of the host mirror (host/clusterer_nodelet.hpp), which returns the
+// pcl::IndicesClusters and each marker's points (mod_set_cluster_members); only the markers' colours (ColorSet) are not provided.
 // Not buildable in the image this was written in (no ROS): tests/test_ros_adapter_syntax.py compiles it against declaration-only
 // stand-ins; behaviour lives in the host mirror (moving_object_detector_amd/host/clusterer_nodelet.hpp) and the C ABI, which are tested.
 #include <dynamic_reconfigure/server.h>

@@ -58,6 +58,7 @@ class Context:
         self.max_objects = max_objects if max_objects > 0 else max(1, (width * height) // 100)
         self.mask_words = (width + 63) // 64
         self._ws = None
+        self._members_ws = None
 
     # ---- configuration ----------------------------------------------------------------------------------------
     def _check(self, rc: int) -> int:
@@ -116,6 +117,27 @@ class Context:
         f = capi.ModDisparityFilters(-1, -1, -1, -1)
         self._check(self.lib.mod_get_disparity_filters(self.h, C.byref(f)))
         return {"uniqueness_ratio": f.uniqueness_ratio, "speckle_size": f.speckle_size, "speckle_range": f.speckle_range}
+
+    def set_cluster_members(self, ws: Optional[dict]) -> None:
+        """Per-cluster member lists (mod_set_cluster_members), off by default: every later cluster() / process() and the synchronous
+        host calls write offsets, indices (and points) into the tensors of `ws` (workspace(..., members=True)); None turns them off.
+        The pipelined submits never write them.  The tensors must stay alive while the setting is on (the context keeps `ws`)."""
+        if ws is None:
+            self._check(self.lib.mod_set_cluster_members(self.h, None))
+            self._members_ws = None
+            return
+        if ws.get("member_offsets") is None:
+            raise ValueError("workspace(..., members=True) allocates the member-list tensors")
+        pts = ws.get("member_points")
+        m = capi.ModClusterMembers(ws["member_offsets"].data_ptr(), ws["member_indices"].data_ptr(), pts.data_ptr() if pts is not None else None, 0)
+        self._check(self.lib.mod_set_cluster_members(self.h, C.byref(m)))
+        self._members_ws = ws
+
+    def get_cluster_members(self):
+        """(ModClusterMembers in force, enabled)."""
+        m, on = capi.ModClusterMembers(), C.c_int32(-1)
+        self._check(self.lib.mod_get_cluster_members(self.h, C.byref(m), C.byref(on)))
+        return m, bool(on.value)
 
     def set_flow_propagation(self, seeds: int = 1) -> None:
         """Neighbour-seed propagation of the on-GPU optical flow (mod_set_flow_propagation): 1 = off (the default), 5 = every finer
@@ -240,11 +262,14 @@ class Context:
             pass
 
     # ---- buffers ----------------------------------------------------------------------------------------------
-    def workspace(self, frames: int, aos: bool = False, extras: bool = False, labels: bool = True, xy: bool = True) -> dict:
+    def workspace(self, frames: int, aos: bool = False, extras: bool = False, labels: bool = True, xy: bool = True, members: bool = False,
+                  points: bool = False) -> dict:
         """Output buffers for `frames` frames, allocated once and reused.  labels=False: no cluster-label plane (the reference
         renders its cluster image only for subscribers, clusterer_nodelet.cpp:235-236).  xy=False: process() hands the library no x / y
-        planes (nobody takes the cloud, scene_flow_constructor.cpp:141-142): the rows 0 and 1 of `planes` are then never written."""
-        key = (frames, self.height, self.width, aos, extras, labels, xy)
+        planes (nobody takes the cloud, scene_flow_constructor.cpp:141-142): the rows 0 and 1 of `planes` are then never written.
+        members=True: the tensors of the per-cluster member lists (set_cluster_members(ws) turns them on), points=True: their x, y, z too."""
+        members = members or points
+        key = (frames, self.height, self.width, aos, extras, labels, xy, members, points)
         if self._ws is not None and self._ws["key"] == key:
             return self._ws
         H, W, dev = self.height, self.width, self.device
@@ -260,6 +285,9 @@ class Context:
         ws["aos"] = torch.empty((frames, H, W, 8), dtype=torch.float32, device=dev) if aos else None
         ws["depth"] = torch.empty((frames, H, W), dtype=torch.float32, device=dev) if extras else None
         ws["static_flow"] = torch.empty((frames, H, W, 2), dtype=torch.float32, device=dev) if extras else None
+        ws["member_offsets"] = torch.zeros((frames, self.max_objects + 1), dtype=torch.int32, device=dev) if members else None
+        ws["member_indices"] = torch.empty((frames, H * W), dtype=torch.int32, device=dev) if members else None
+        ws["member_points"] = torch.empty((frames, H * W, 3), dtype=torch.float32, device=dev) if points else None
         self._ws = ws
         return ws
 
@@ -430,3 +458,21 @@ class Context:
             k = min(int(n[f]), raw.shape[1])
             out.append(np.frombuffer(raw[f, :k].tobytes(), dtype=OBJECT_DTYPE).copy())
         return out
+
+    def clusters_to_host(self, ws, frames: Optional[int] = None):
+        """The member lists a call wrote (set_cluster_members).  Per frame a list of int32 arrays, cluster k's pixel indices v * W + u in
+        the reference's order (u ascending, then v); with points also, second, per frame the list of (n, 3) float32 arrays of their
+        x, y, z.  Copies the offsets first, then only the used prefix of indices / points."""
+        off = ws["member_offsets"].cpu().numpy()
+        K = ws["n_clusters"].cpu().numpy()
+        pts_t = ws.get("member_points")
+        F = off.shape[0] if frames is None else int(frames)
+        lists, points = [], []
+        for f in range(F):
+            k, used = int(K[f]), int(off[f, int(K[f])])
+            idx = ws["member_indices"][f, :used].cpu().numpy()
+            lists.append([idx[off[f, j]:off[f, j + 1]].copy() for j in range(k)])
+            if pts_t is not None:
+                p = pts_t[f, :used].cpu().numpy()
+                points.append([p[off[f, j]:off[f, j + 1]].copy() for j in range(k)])
+        return (lists, points) if pts_t is not None else lists

@@ -1,0 +1,411 @@
+"""GPU: the per-cluster member lists (mod_set_cluster_members, k_cluster_members).  The expected lists never come from the code under
+test: they are derived in numpy from the ORACLE's labels for the same cloud — for cluster k the pixels with label k ordered by
+(u, v), index v * W + u (clusterMap2IndicesCluster, clusterer_nodelet.cpp:104-114); points are the input planes at those indices."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from util import PLANES, bits_equal, compare_objects
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SENT_I, SENT_F = -7, -1234.5
+
+
+def _want(labels, K):
+    """Column-major member lists from a labels plane."""
+    H, W = labels.shape
+    lt = labels.T.ravel()                                   # u-major, v inside
+    pos = np.arange(W * H)
+    p = (pos % H) * W + pos // H
+    return [p[lt == k].astype(np.int32) for k in range(K)]
+
+
+def _prefill(ws):
+    ws["member_offsets"].fill_(SENT_I); ws["member_indices"].fill_(SENT_I)
+    if ws["member_points"] is not None:
+        ws["member_points"].fill_(SENT_F)
+
+
+def _check_frame(ws, f, labels, K, planes=None, max_objects=None, count=True):
+    """Frame f of ws against the oracle's labels: offsets, lists, untouched tails, and the points against `planes` (x, y, z).
+    count=False: a host call, whose cluster count stays in the library's own staging."""
+    want = _want(labels, K)
+    off = ws["member_offsets"][f].cpu().numpy()
+    idx = ws["member_indices"][f].cpu().numpy()
+    assert not count or int(ws["n_clusters"][f]) == K
+    sizes = [len(w) for w in want]
+    assert off[0] == 0 and np.array_equal(off[:K + 1], np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32))
+    assert np.all(off[K:] == off[K]) and len(off) == (max_objects if max_objects is not None else len(off) - 1) + 1
+    used = int(off[K])
+    for k in range(K):
+        assert np.array_equal(idx[off[k]:off[k + 1]], want[k]), f"frame {f} cluster {k}"
+    assert np.all(idx[used:] == SENT_I), "entries beyond offsets[K] were written"
+    if ws["member_points"] is not None:
+        pts = ws["member_points"][f].cpu().numpy()
+        assert np.all(pts[used:] == np.float32(SENT_F))
+        if planes is not None and used:
+            allp = np.concatenate(want)
+            for d, k in enumerate(("x", "y", "z")):
+                assert bits_equal(pts[:used, d], np.asarray(planes[k], np.float32).ravel()[allp]), k
+    return want
+
+
+def _cloud(W, H, dyn, z):
+    """Constant speed above the threshold where the mask is; coordinates distinct per pixel."""
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float32)
+    v = np.where(dyn, np.float32(1.0), np.float32(0.0)).astype(np.float32)
+    zero = np.zeros((H, W), np.float32)
+    return {"x": xs * np.float32(0.01), "y": ys * np.float32(0.01), "z": np.asarray(z, np.float32), "vx": v, "vy": zero, "vz": zero}
+
+
+def _cluster_ctx(W, H, prm, F=1):
+    from moving_object_detector_amd import synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F, max_objects=W * H // prm.cluster_size + 1)
+    ctx.set_camera(synth.make_camera(W, H)); ctx.set_params(prm)
+    return ctx
+
+
+def _run_clouds(oracle, clouds, prm, W, H, check_objects=True):
+    """mod_cluster_dev on the clouds (one frame each) with lists and points on, every frame checked against the oracle."""
+    F = len(clouds)
+    ctx = _cluster_ctx(W, H, prm, F)
+    ws = ctx.workspace(F, members=True, points=True)
+    for f, cl in enumerate(clouds):
+        for i, k in enumerate(PLANES):
+            ws["planes"][i, f].copy_(torch.from_numpy(cl[k]))
+    _prefill(ws)
+    ctx.set_cluster_members(ws)
+    assert ctx.cluster(F, ws, mask_ready=False) == 0
+    ctx.synchronize()
+    objs = ctx.objects_to_host(ws)
+    out = []
+    for f, cl in enumerate(clouds):
+        rl, ro, rK = oracle.cluster(cl, prm, "tidy", max_objects=W * H)
+        assert np.array_equal(ws["labels"][f].cpu().numpy(), rl)
+        if check_objects:
+            compare_objects(objs[f], ro, strict_velocity=True)
+        out.append((_check_frame(ws, f, rl, rK, cl, ctx.max_objects), rl, ro))
+    ctx.close()
+    return out
+
+
+# ---- 1. fused path ------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fused_case(oracle):
+    from moving_object_detector_amd import synth
+    W, H, F = 160, 120, 3
+    cam, sq = synth.make_sequence(W, H, F, seed=4)
+    prm = synth.Params(dynamic_flow_diff=1, cluster_size=30)
+    refs = []
+    for f in range(F):
+        ref = oracle.construct(cam, prm, sq["disparity"][f + 1], sq["disparity"][f], sq["flow"][f], sq["t"][f], sq["q"][f], float(sq["dt"][f]), "tidy")
+        rl, ro, rK = oracle.cluster(ref, prm, "tidy", max_objects=W * H)
+        refs.append((ref, rl, ro, rK))
+    return W, H, F, cam, sq, prm, refs
+
+
+def _fused_ctx(W, H, F, cam, prm, chunks=0):
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F, max_objects=W * H // prm.cluster_size + 1, batch_chunks=chunks)
+    ctx.set_camera(cam); ctx.set_params(prm)
+    return ctx
+
+
+def _batch(ctx, sq, F):
+    d = torch.from_numpy(sq["disparity"]).to(ctx.device)
+    return ctx.make_batch(d[1:1 + F].contiguous(), d[0:F].contiguous(), torch.from_numpy(sq["flow"][:F]).to(ctx.device), sq["t"][:F], sq["q"][:F], sq["dt"][:F])
+
+
+def _lists_bytes(ws, F):
+    off = ws["member_offsets"].cpu().numpy()
+    K = ws["n_clusters"].cpu().numpy()
+    used = [int(off[f, K[f]]) for f in range(F)]
+    pts = ws["member_points"]
+    return (off.tobytes(), [ws["member_indices"][f, :used[f]].cpu().numpy().tobytes() for f in range(F)],
+            [pts[f, :used[f]].cpu().numpy().tobytes() for f in range(F)] if pts is not None else None)
+
+
+def test_fused_path_lists_offsets_and_points(fused_case):
+    W, H, F, cam, sq, prm, refs = fused_case
+    ctx = _fused_ctx(W, H, F, cam, prm)
+    batch = _batch(ctx, sq, F)
+    ws = ctx.workspace(F, members=True, points=True)
+    _prefill(ws)
+    ctx.set_cluster_members(ws)
+    assert ctx.get_cluster_members()[1] is True
+    assert ctx.process(batch, ws) == 0
+    ctx.synchronize()
+    objs = ctx.objects_to_host(ws)
+    assert sum(r[3] for r in refs) >= F
+    for f, (ref, rl, ro, rK) in enumerate(refs):
+        want = _check_frame(ws, f, rl, rK, ref, ctx.max_objects)
+        compare_objects(objs[f], ro, strict_velocity=True)
+        if len(objs[f]) == rK:                                  # every cluster accepted: object k is cluster k
+            assert [int(o["n_points"]) for o in objs[f]] == [len(w) for w in want]
+    lists, points = ctx.clusters_to_host(ws)
+    for f, (ref, rl, ro, rK) in enumerate(refs):
+        want = _want(rl, rK)
+        assert len(lists[f]) == rK and all(np.array_equal(a, b) for a, b in zip(lists[f], want))
+        assert all(p.shape == (len(w), 3) for p, w in zip(points[f], want))
+    six = _lists_bytes(ws, F)
+    # the same call without a labels plane, then objects-only (x = y = NULL): identical lists, points identical bit for bit
+    for kw in ({"labels": False}, {"xy": False}):
+        ws2 = ctx.workspace(F, members=True, points=True, **kw)
+        _prefill(ws2)
+        ctx.set_cluster_members(ws2)
+        assert ctx.process(batch, ws2) == 0
+        ctx.synchronize()
+        assert _lists_bytes(ws2, F) == six, kw
+        assert np.all(ws2["member_indices"][0, int(ws2["member_offsets"][0, -1]):].cpu().numpy() == SENT_I)
+    ctx.close()
+
+
+# ---- 2. hand-built clouds -----------------------------------------------------------------------------------------------------
+def test_interleaved_clusters(oracle):
+    from moving_object_detector_amd import synth
+    W, H = 130, 70
+    ys, xs = np.mgrid[0:H, 0:W]
+    blk = (xs >= 3) & (xs < 43) & (ys >= 5) & (ys < 35)
+    z = np.where((xs - 3) % 2 == 0, 5.0, 9.0)
+    (want, rl, ro), = _run_clouds(oracle, [_cloud(W, H, blk, z)], synth.Params(cluster_size=10, neighbor_distance=4, depth_diff=0.15, dynamic_speed=0.3), W, H)
+    assert len(want) == 2 and len(want[0]) == len(want[1]) == 600 and not set(want[0]) & set(want[1])
+
+
+def test_tall_cluster_spans_four_row_cells(oracle):
+    from moving_object_detector_amd import synth
+    W, H = 64, 208
+    ys, xs = np.mgrid[0:H, 0:W]
+    dyn = (xs >= 20) & (xs < 26) & (ys >= 3) & (ys <= 199)
+    (want, rl, ro), = _run_clouds(oracle, [_cloud(W, H, dyn, np.full((H, W), 5.0))], synth.Params(cluster_size=10, neighbor_distance=4), W, H)
+    assert [len(w) for w in want] == [6 * 197]
+
+
+def test_cluster_with_holes(oracle):
+    """Every third pixel along the diagonals of a 30 x 30 block: every column holds every third row, so a member's rank inside its
+    cell is the popcount below its bit, not its row."""
+    from moving_object_detector_amd import synth
+    W, H = 100, 50
+    ys, xs = np.mgrid[0:H, 0:W]
+    dyn = (xs >= 7) & (xs < 37) & (ys >= 11) & (ys < 41) & ((xs + ys) % 3 == 0)
+    (want, rl, ro), = _run_clouds(oracle, [_cloud(W, H, dyn, np.full((H, W), 5.0))], synth.Params(cluster_size=10, neighbor_distance=4), W, H)
+    assert [len(w) for w in want] == [300]
+
+
+def test_size_filter_boundary(oracle):
+    from moving_object_detector_amd import synth
+    W, H = 96, 40
+    ys, xs = np.mgrid[0:H, 0:W]
+    a = (xs >= 5) & (xs < 15) & (ys >= 5) & (ys < 10)            # 50 members
+    b = (xs >= 60) & (xs < 67) & (ys >= 20) & (ys < 27)          # 49
+    (want, rl, ro), = _run_clouds(oracle, [_cloud(W, H, a | b, np.full((H, W), 5.0))], synth.Params(cluster_size=50, neighbor_distance=2), W, H)
+    assert [len(w) for w in want] == [50]
+    assert not set(want[0]) & set((ys[b] * W + xs[b]).tolist())
+
+
+def test_wide_stripes_take_several_runs_of_cells(oracle):
+    """A one-row stripe 8250 columns wide (8250 one-column cells: more than the workgroup's run of 8192) and, ten rows below, one of 600
+    members (a wave's cluster whose box has more cells than the wave's run of 512)."""
+    from moving_object_detector_amd import synth
+    W, H = 8256, 16
+    ys, xs = np.mgrid[0:H, 0:W]
+    dyn = ((ys == 2) & (xs >= 3) & (xs < 8253)) | ((ys == 12) & (xs >= 100) & (xs < 700))
+    (want, rl, ro), = _run_clouds(oracle, [_cloud(W, H, dyn, np.full((H, W), 5.0))], synth.Params(cluster_size=100, neighbor_distance=1), W, H)
+    assert sorted(len(w) for w in want) == [600, 8250]
+
+
+def test_sizes_at_the_wave_and_workgroup_split(oracle):
+    """1024 members (the largest cluster a single wave lays out, here in two runs of cells) beside 1025 (the smallest the workgroup takes)."""
+    from moving_object_detector_amd import synth
+    W, H = 1100, 12
+    ys, xs = np.mgrid[0:H, 0:W]
+    dyn = ((ys == 2) & (xs >= 9) & (xs < 9 + 1024)) | ((ys == 8) & (xs >= 30) & (xs < 30 + 1025))
+    (want, rl, ro), = _run_clouds(oracle, [_cloud(W, H, dyn, np.full((H, W), 5.0))], synth.Params(cluster_size=100, neighbor_distance=1), W, H)
+    assert [len(w) for w in want] == [1024, 1025]
+
+
+def test_empty_frame_between_two_others(oracle):
+    from moving_object_detector_amd import synth
+    W, H = 96, 40
+    ys, xs = np.mgrid[0:H, 0:W]
+    a = (xs >= 5) & (xs < 25) & (ys >= 5) & (ys < 25)
+    z = np.full((H, W), 5.0)
+    out = _run_clouds(oracle, [_cloud(W, H, a, z), _cloud(W, H, np.zeros((H, W), bool), z), _cloud(W, H, a[::-1].copy(), z)],
+                      synth.Params(cluster_size=50, neighbor_distance=2), W, H)
+    assert [len(o[0]) for o in out] == [1, 0, 1]                # (_check_frame: frame 1's offsets are all 0, its indices keep the sentinel)
+
+
+# ---- 3. tied medians: the lists are taken before the tie replay reuses the member arrays ------------------------------------------
+@pytest.mark.parametrize("case", ["big", "blobs"])
+def test_lists_of_tied_clusters(oracle, case):
+    from moving_object_detector_amd import synth
+    from test_gpu_median_ties import _tie_cloud
+    W, H = 160, 100
+    rng = np.random.default_rng(21 if case == "big" else 22)
+    ys, xs = np.mgrid[0:H, 0:W]
+    if case == "big":                                           # one cluster of ~11000 members: the workgroup's path
+        dyn = (xs > 10) & (xs < 150) & (ys > 5) & (ys < 95) & (rng.random((H, W)) < 0.95)
+        prm, nb = synth.Params(cluster_size=1000, neighbor_distance=4), 3
+    else:                                                       # clusters of ~800: a wave each
+        dyn = (xs % 40 < 30) & (ys % 40 < 30) & (xs < 120) & (ys < 80) & (rng.random((H, W)) < 0.9)
+        prm, nb = synth.Params(cluster_size=200, neighbor_distance=2), 5
+    planes = {k: np.ascontiguousarray(v, np.float32) for k, v in _tie_cloud(W, H, rng, dyn, nb).items()}
+    (want, rl, ro), = _run_clouds(oracle, [planes], prm, W, H)
+    assert any(o["ambiguous"] for o in ro), "the case is meant to produce ties between different vectors"
+    assert all((len(w) > 1024) == (case == "big") for w in want)
+
+
+# ---- 4. a caller's cloud with NaN x in two members ------------------------------------------------------------------------------
+def test_nan_coordinates_reach_the_points(oracle):
+    from moving_object_detector_amd import synth
+    W, H = 96, 40
+    ys, xs = np.mgrid[0:H, 0:W]
+    a = (xs >= 5) & (xs < 25) & (ys >= 5) & (ys < 25)
+    cl = _cloud(W, H, a, np.full((H, W), 5.0))
+    cl["x"][7, 9] = np.nan; cl["x"][20, 24] = np.nan
+    (want, rl, ro), = _run_clouds(oracle, [cl], synth.Params(cluster_size=50, neighbor_distance=2), W, H, check_objects=False)
+    assert len(want) == 1 and {7 * W + 9, 20 * W + 24} <= set(want[0].tolist())   # (_check_frame compared the NaN positions of the points)
+
+
+# ---- 5. chunked ---------------------------------------------------------------------------------------------------------------
+def test_chunked_call_gives_the_unchunked_lists():
+    from moving_object_detector_amd import synth
+    W, H, F = 160, 120, 64                                       # two chunks of 32 frames: the smallest batch that is cut
+    cam, sq = synth.make_sequence(W, H, F, seed=4)
+    prm = synth.Params(dynamic_flow_diff=1, cluster_size=30)
+    got = []
+    for chunks in (1, 2):
+        ctx = _fused_ctx(W, H, F, cam, prm, chunks)
+        ws = ctx.workspace(F, members=True, points=True)
+        _prefill(ws)
+        ctx.set_cluster_members(ws)
+        assert ctx.process(_batch(ctx, sq, F), ws) == 0
+        ctx.synchronize()
+        got.append((_lists_bytes(ws, F), ws["n_clusters"].cpu().numpy().copy(), ws["labels"].cpu().numpy().copy()))
+        ctx.close()
+    assert np.array_equal(got[0][1], got[1][1]) and got[0][1].sum() > F and np.array_equal(got[0][2], got[1][2])
+    assert got[0][0][0] == got[1][0][0], "offsets differ"
+    for f in range(F):                                          # the first and last frame of each chunk included
+        assert got[0][0][1][f] == got[1][0][1][f] and got[0][0][2][f] == got[1][0][2][f], f
+    for f in (0, 31, 32, 63):                                   # and they are the labels' lists
+        K = int(got[0][1][f])
+        assert got[0][0][1][f] == np.concatenate(_want(got[0][2][f], K) + [np.zeros(0, np.int32)]).astype(np.int32).tobytes()
+
+
+# ---- 6. off and untouched -----------------------------------------------------------------------------------------------------
+def _stage_calls(ctx):
+    from moving_object_detector_amd import capi
+    return [ctx.stage_time(s)[1] for s in range(capi.MOD_STAGE_COUNT)]
+
+
+def test_off_state_touches_nothing(fused_case):
+    from moving_object_detector_amd import capi
+    W, H, F, cam, sq, prm, refs = fused_case
+    runs = []
+    for mode in ("fresh", "never_set", "set_then_off"):
+        ctx = _fused_ctx(W, H, F, cam, prm)
+        ws = ctx.workspace(F, members=True, points=True)
+        _prefill(ws)
+        if mode == "set_then_off":
+            ctx.set_cluster_members(ws)
+            ctx.set_cluster_members(None)
+            assert ctx.get_cluster_members()[1] is False
+        ctx.set_profiling(True)
+        assert ctx.process(_batch(ctx, sq, F), ws) == 0
+        ctx.synchronize()
+        for k, s in (("member_offsets", SENT_I), ("member_indices", SENT_I), ("member_points", SENT_F)):
+            assert bool((ws[k] == s).all()), (mode, k)
+        n = ws["n_objects"].cpu().numpy()
+        runs.append((ws["labels"].cpu().numpy().copy(), n.copy(), [ws["objects"][f, :n[f]].cpu().numpy().tobytes() for f in range(F)], _stage_calls(ctx)))
+        ctx.close()
+    for r in runs[1:]:
+        assert np.array_equal(r[0], runs[0][0]) and np.array_equal(r[1], runs[0][1]) and r[2] == runs[0][2] and r[3] == runs[0][3]
+    assert runs[0][3][capi.MOD_STAGE_FINAL] == 1
+
+
+def test_submits_never_write_the_lists(fused_case):
+    from moving_object_detector_amd import capi
+    W, H, F, cam, sq, prm, refs = fused_case
+    ctx = _fused_ctx(W, H, 1, cam, prm)
+    ws = ctx.workspace(1, members=True, points=True)
+    CAP = ctx.max_objects
+    tf = capi.transforms_array(sq["t"][:1], sq["q"][:1])
+    flow0 = np.ascontiguousarray(sq["flow"][0])
+    args = (sq["disparity"][1].ctypes.data, sq["disparity"][0].ctypes.data, flow0.ctypes.data, C.byref(tf[0]), float(sq["dt"][0]))
+    got = []
+    for on in (False, True):
+        _prefill(ws)
+        ctx.set_cluster_members(ws if on else None)
+        objs, t, n = (capi.ModObject * CAP)(), C.c_int32(-1), C.c_int32(-1)
+        assert ctx.lib.mod_submit_frame_host(ctx.h, *args, None, None, objs, CAP, C.byref(t)) == 0, ctx.lib.mod_last_error(ctx.h)
+        assert ctx.lib.mod_collect_frame_host(ctx.h, t.value, C.byref(n)) == 0
+        ctx.synchronize()
+        assert bool((ws["member_offsets"] == SENT_I).all()) and bool((ws["member_indices"] == SENT_I).all()) and bool((ws["member_points"] == SENT_F).all())
+        got.append((n.value, bytes(objs)[:n.value * C.sizeof(capi.ModObject)]))
+    assert got[0] == got[1] and got[0][0] == len(refs[0][2])
+    # the synchronous host call with the setting on fills frame 0
+    _prefill(ws)
+    objs, n = (capi.ModObject * CAP)(), C.c_int32(-1)
+    assert ctx.lib.mod_process_frame_host(ctx.h, *args, None, None, objs, CAP, C.byref(n)) == 0
+    ctx.synchronize()
+    _check_frame(ws, 0, refs[0][1], refs[0][3], refs[0][0], ctx.max_objects, count=False)
+    ctx.close()
+
+
+# ---- 7. validation ------------------------------------------------------------------------------------------------------------
+def test_validation_and_cluster_cloud_host(oracle):
+    from moving_object_detector_amd import capi, synth
+    W, H = 96, 40
+    prm = synth.Params(cluster_size=50, neighbor_distance=2)
+    ctx = _cluster_ctx(W, H, prm)
+    ws = ctx.workspace(1, members=True, points=True)
+    ctx.set_cluster_members(ws)
+    before, on = ctx.get_cluster_members()
+    o, i, p = ws["member_offsets"].data_ptr(), ws["member_indices"].data_ptr(), ws["member_points"].data_ptr()
+    for bad in (capi.ModClusterMembers(None, i, p, 0), capi.ModClusterMembers(o, None, p, 0), capi.ModClusterMembers(o, i, p, 1)):
+        assert ctx.lib.mod_set_cluster_members(ctx.h, C.byref(bad)) == capi.MOD_ERR_INVALID_ARGUMENT
+        now, on = ctx.get_cluster_members()
+        assert on and bytes(now) == bytes(before)
+    # mod_cluster_cloud_host with the setting on fills frame 0
+    ys, xs = np.mgrid[0:H, 0:W]
+    cl = _cloud(W, H, (xs >= 5) & (xs < 25) & (ys >= 5) & (ys < 25), np.full((H, W), 5.0))
+    rec = np.zeros((H, W, 8), np.float32)
+    for j, k in zip((0, 1, 2, 4, 5, 6), PLANES):
+        rec[..., j] = cl[k]
+    _prefill(ws)
+    CAP = ctx.max_objects
+    objs, n = (capi.ModObject * CAP)(), C.c_int32(-1)
+    assert ctx.lib.mod_cluster_cloud_host(ctx.h, rec.ctypes.data, W, H, 32, 32 * W, None, objs, CAP, C.byref(n)) == 0, ctx.lib.mod_last_error(ctx.h)
+    ctx.synchronize()
+    rl, ro, rK = oracle.cluster(cl, prm, "tidy", max_objects=W * H)
+    assert n.value == len(ro) == 1
+    _check_frame(ws, 0, rl, rK, cl, ctx.max_objects, count=False)
+    ctx.close()
+
+
+# ---- 8. the C++ host mirror ---------------------------------------------------------------------------------------------------
+def test_mirror_clusters_and_marker_points(tmp_path):
+    """tests/cpp/cluster_members_test.cpp on the 160 x 120 golden cloud: the mirror's pcl::IndicesClusters content and marker points
+    equal the lists the program computes from the mirror's own labels with the reference's double loop."""
+    from test_oracle_golden import load_case
+    exe = os.path.join(ROOT, "tests", "cpp", "cluster_members_test")
+    if not os.path.exists(exe):
+        pytest.fail("tests/cpp/cluster_members_test is not built (run __graft_entry__.build())")
+    g, cam, prm = load_case(os.path.join(ROOT, "tests", "golden", "synth_160x120.npz"))
+    H, W = g["d_now"].shape
+    cloud = np.zeros((H, W, 8), np.float32)
+    for j, k in zip((0, 1, 2, 4, 5, 6), PLANES):
+        cloud[..., j] = g[k]
+    d = str(tmp_path)
+    np.asarray([W, H], np.float64).tofile(d + "/dims.f64")
+    np.asarray(g["prm"], np.float64).tofile(d + "/prm.f64")
+    cloud.tofile(d + "/cloud.f32")
+    r = subprocess.run([exe, d], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    K = int(g["labels"].max()) + 1
+    assert K >= 1 and r.stdout.startswith(f"ok: {K} clusters, {int((g['labels'] >= 0).sum())} members"), r.stdout
