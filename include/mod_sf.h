@@ -480,6 +480,48 @@ int  mod_image_to_mono_dev(ModContext *ctx, int32_t frames, const uint8_t *src, 
 int  mod_set_side_by_side(ModContext *ctx, int32_t on);
 int  mod_get_side_by_side(const ModContext *ctx, int32_t *on);
 
+/* ---- binning: camera images reduced by an integer factor ---------------------------------------------------------------------- */
+/* image_proc/crop_decimate's step on the GPU: a 1080p or 2K stereo head runs the estimators at half resolution, so that
+ * MOD_SGM_MAX_DISPARITIES spans twice as many full-resolution pixels and every per-pixel stage costs a quarter, without giving up
+ * field of view as a crop does.  Opt-in context state like mod_set_side_by_side: read when a call or a submit is made, a frame in
+ * flight completes with the binning of its own submit, and while off (the default) every call enqueues exactly what it did before.
+ * One definition for every input path.  Let G be the full-resolution grey window that the path without binning would produce for a
+ * camera of (bx W) x (by H) at the layout's (x0, y0): mono8, colour and YUV through the grey conversion above; Bayer through the
+ * demosaic above (debayer, then crop, then bin: the rule for the window's edge applies to the FULL window); under a rectification,
+ * the rectifier with a map of (bx W) x (by H) entries for that window.  The context's W x H image is then, in integers,
+ *   MOD_BIN_MEAN     out(X, Y) = (sum over j < by, i < bx of G(bx X + i, by Y + j) + ((bx by) >> 1)) / (bx by)
+ *                    (2 x 2: (a + b + c + d + 2) >> 2; half-way sums round up; cv::INTER_AREA at an integer factor)
+ *   MOD_BIN_NEAREST  out(X, Y) = G(bx X, by Y)      (the block's top-left pixel: crop_decimate's default, interpolation NN)
+ * tests/models/binning_model.py restates both.
+ *   - Layouts: the layout's width, height, step, x0 and y0 keep describing the MESSAGE; the window taken from it is (bx W) x (by H),
+ *     and that window must fit.  The default layout while binning is on is mono8 packed at (bx W) x (by H).
+ *   - Side by side: each pane is binned on its own; no output pixel of one eye depends on a byte of the other.
+ *   - Rectification: mod_rectify_map_host returns the full-window map [by H][bx W][2]; the cached map is keyed by the full window's
+ *     size, so a change of binning that changes it forces a rebuild, which is refused while tickets are outstanding (the rule of the
+ *     rectifier).  Without a rectification the binning may change between submits, like the layout.
+ *   - Every *_host image call and every stereo, images, odometry and depth submit reads it; so do mod_image_to_mono_dev and
+ *     mod_rectify_dev, whose output stays [frames][H][W].  The _dev estimator calls take grey planes and are untouched.
+ *   - The camera given to mod_set_camera is the BINNED one (what image_geometry does with binning_x / binning_y): with the
+ *     full-resolution P, fx_b = fx / bx, fy_b = fy / by, Tx_b = Tx / bx, Ty_b = Ty / by, disp_f_b = disp_f / bx;
+ *     MOD_BIN_NEAREST: cx_b = (cx - x0) / bx, cy_b = (cy - y0) / by; MOD_BIN_MEAN: cx_b = (cx - x0 - (bx - 1) / 2) / bx,
+ *     cy_b = (cy - y0 - (by - 1) / 2) / by (the block's centre).
+ *   - Depth images are NOT binned: mod_submit_depth_host bins the image, and the depth message must match the binned camera (or go
+ *     through mod_set_depth_registration, whose scatter lands in whatever size the image camera has).
+ *   - Capacity: bx W <= ModConfig.max_width and by H <= ModConfig.max_height, else MOD_ERR_CAPACITY; checked when the binning is
+ *     set if a camera is known, and again at call time (the camera may have changed).
+ *   mod_set_image_binning  NULL, or bx = by = 1 with either mode: off.  A factor outside 1..4, an unknown mode or a non-zero
+ *                          `reserved`: MOD_ERR_INVALID_ARGUMENT, and the setting stays as it was.
+ *   mod_get_image_binning  the binning in force (as it was set; never set, or set to NULL: bx = by = 1, MOD_BIN_MEAN) */
+#define MOD_BIN_MEAN    0   /* rounded box mean (cv::INTER_AREA at an integer factor) */
+#define MOD_BIN_NEAREST 1   /* the block's top-left pixel (crop_decimate's default, interpolation NN) */
+typedef struct ModImageBinning {  /* 16 bytes; NULL or bx = by = 1: off (the default) */
+  int32_t bx, by;                 /* 1..4 each */
+  int32_t mode;                   /* MOD_BIN_* */
+  int32_t reserved;               /* must be 0 */
+} ModImageBinning;
+int  mod_set_image_binning(ModContext *ctx, const ModImageBinning *binning);
+int  mod_get_image_binning(const ModContext *ctx, ModImageBinning *binning);
+
 /* ---- raw camera images: rectification on the GPU ---------------------------------------------------------------------------- */
 /* The reference's launch files subscribe to image_rect_color: something upstream (image_proc, the ZED SDK) has rectified.  With a
  * rectification set, the library does that step itself, so the *_host image entry points take RAW, distorted messages.  Opt-in,

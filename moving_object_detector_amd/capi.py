@@ -39,6 +39,8 @@ MOD_DISTORTION_RATIONAL, MOD_DISTORTION_EQUIDISTANT = 0, 1   # how ModRectifyCam
 DISTORTION_MODELS = {"plumb_bob": MOD_DISTORTION_RATIONAL, "rational_polynomial": MOD_DISTORTION_RATIONAL,
                      "equidistant": MOD_DISTORTION_EQUIDISTANT}   # sensor_msgs/CameraInfo.distortion_model
 MOD_MAX_WIDTH = 16384
+MOD_BIN_MEAN, MOD_BIN_NEAREST = 0, 1                     # mod_set_image_binning: rounded box mean / the block's top-left pixel
+BIN_MODES = {"mean": MOD_BIN_MEAN, "nearest": MOD_BIN_NEAREST}
 MOD_DEPTH_16UC1, MOD_DEPTH_32FC1 = 0, 1                  # REP 118 depth images: uint16 millimetres / float32 metres
 MOD_DEPTH_SPLAT_MAX = 8                                  # targets per axis a footprint of mod_set_depth_splat may paint
 DEPTH_ENCODINGS = {"16UC1": MOD_DEPTH_16UC1, "32FC1": MOD_DEPTH_32FC1}
@@ -76,6 +78,7 @@ EXPORTS = [
     "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
     "mod_set_distortion_model", "mod_get_distortion_model",
     "mod_set_side_by_side", "mod_get_side_by_side",
+    "mod_set_image_binning", "mod_get_image_binning",
     "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
     "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
     "mod_set_cluster_members", "mod_get_cluster_members",
@@ -176,6 +179,32 @@ def image_layout(encoding, width: int, height: int, step=None, x0: int = 0, y0: 
     return ModImageLayout(enc, int(width), int(height), int(step), int(x0), int(y0))
 
 
+class ModImageBinning(C.Structure):
+    _fields_ = [("bx", C.c_int32), ("by", C.c_int32), ("mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+def image_binning(bx: int = 1, by: int = 1, mode=MOD_BIN_MEAN) -> ModImageBinning:
+    """ModImageBinning (mod_set_image_binning): factors 1..4 and `mode` a MOD_BIN_* value or "mean" / "nearest"; bx = by = 1 is off."""
+    return ModImageBinning(int(bx), int(by), BIN_MODES[mode] if isinstance(mode, str) else int(mode), 0)
+
+
+def binned_camera(cam, binning: ModImageBinning, x0: int = 0, y0: int = 0):
+    """The camera to give set_camera while `binning` is on, from the FULL-resolution camera `cam` (its P) and the layout's window
+    origin: what image_geometry does with binning_x / binning_y, in float64.  fx, Tx and disp_f are divided by bx, fy and Ty by by; the
+    principal point moves to the window and is divided likewise, MOD_BIN_MEAN taking the block's centre ((bx - 1) / 2 earlier), MOD_BIN_NEAREST
+    its top-left pixel.  width and height become cam.width // bx, cam.height // by: state the window's size yourself when it is a crop.
+    Returns a copy of the same type (dataclasses.replace)."""
+    import dataclasses
+    bx, by = int(binning.bx), int(binning.by)
+    if bx < 1 or by < 1:
+        raise ValueError("binning factors must be >= 1")
+    ox, oy = ((bx - 1) / 2.0, (by - 1) / 2.0) if binning.mode == MOD_BIN_MEAN else (0.0, 0.0)
+    return dataclasses.replace(cam, width=int(cam.width) // bx, height=int(cam.height) // by,
+                               fx=float(cam.fx) / bx, fy=float(cam.fy) / by,
+                               cx=(float(cam.cx) - x0 - ox) / bx, cy=(float(cam.cy) - y0 - oy) / by,
+                               Tx=float(cam.Tx) / bx, Ty=float(cam.Ty) / by, disp_f=float(cam.disp_f) / bx)
+
+
 def centred_window(msg_w: int, msg_h: int, W: int, H: int):
     """Origin (x0, y0) of the centred W x H window of a msg_w x msg_h image: image_crop.cpp:24-40's integer (msg - size) / 2."""
     if not (0 < W <= msg_w and 0 < H <= msg_h):
@@ -247,6 +276,7 @@ assert C.sizeof(ModClusterMembers) == 32
 assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
+assert C.sizeof(ModImageBinning) == 16
 
 
 def distortion_model(model) -> int:
@@ -326,6 +356,8 @@ def load(require_torch_first: bool = True):
     L.mod_get_distortion_model.argtypes = [vp, C.POINTER(i32)]
     L.mod_set_side_by_side.argtypes = [vp, i32]
     L.mod_get_side_by_side.argtypes = [vp, C.POINTER(i32)]
+    L.mod_set_image_binning.argtypes = [vp, C.POINTER(ModImageBinning)]
+    L.mod_get_image_binning.argtypes = [vp, C.POINTER(ModImageBinning)]
     L.mod_set_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]
     L.mod_get_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]
     L.mod_set_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration)]

@@ -71,9 +71,11 @@ static int upload_pair(ModContext *c, const uint8_t *img0, const uint8_t *img1, 
   ImageIngest in{};
   in.rectify = c->rect.on; in.panes = panes; in.eye1 = eye1; in.batch2 = true;
   in.stage = reinterpret_cast<uint8_t *>(h.flow.get()); in.raw = &h.raw; in.bayer_grey = &h.bayer_grey;
+  in.bin = c->binning; in.bin_grey = &h.bin_grey;
   if (int rc = current_layout(c, &in.lay)) return rc;
   for (int eye : {(int)MOD_EYE_LEFT, eye1}) if (int rc = in.rectify ? ensure_rectify_map(c, eye, in.lay) : MOD_OK) return rc;
   if (int rc = in.rectify ? ensure_raw_stages(c, in) : MOD_OK) return rc;
+  if (int rc = ensure_bin_stage(c, in)) return rc;
   in.grey0 = *grey = in.staged() ? static_cast<uint8_t *>(h.aos.get()) : in.stage;
   in.grey1 = in.grey0 + pixels(c);
   if (int rc = ingest_copy(c, in, img0, img1, c->stream)) return rc;
@@ -218,7 +220,8 @@ static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   }
   if (f.img.rectify) {
     if (int rc = ensure_raw_stages(c, f.img)) return rc;
-  } else if (f.img.staged()) HIP_TRY(c, dalloc(f.s.stage, window_stage_bytes(c)));
+  } else if (f.img.windows_staged()) HIP_TRY(c, dalloc(f.s.stage, window_stage_bytes(c)));
+  if (int rc = ensure_bin_stage(c, f.img)) return rc;
   f.img.stage = f.s.stage;
   f.img.grey0 = rq.estimates_flow() ? f.now.left.get() : f.s.img.get();
   f.img.grey1 = rq.rgbd ? nullptr : f.s.img.get() + pixels(c);
@@ -303,6 +306,7 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat};
   f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
   f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
+  f.img.bin = c->binning; f.img.bin_grey = &f.s.bin_grey;
   if ((rc = grow_for(c, rq, f)) || (rc = upload_images(c, rq, f)) || (rc = estimate(c, rq, f))) return rc;
   static const ModTransform kUnused = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 1.0}};   // stands for the transform in HBM (never read)
   const ModFrameBatch in{1, 0, f.now.disparity, f.prev.disparity, f.s.flow, rq.odometry() ? &kUnused : rq.transform, &rq.dt};

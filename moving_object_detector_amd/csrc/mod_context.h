@@ -114,6 +114,9 @@ struct ModContext {
   ModImageLayout layout{};                  // of the host images (mod_set_image_layout) ...
   bool has_layout = false;                  // ... or, while false, mono8 packed at the camera's size
   bool side_by_side = false;                // mod_set_side_by_side: one message holds both eyes; read when a call / submit is made
+  // mod_set_image_binning: read when a call / submit is made ({1, 1, ..}: off).  The window every layout is checked against, the
+  // converters run at and a rectification map is built for is then the full one, (bx W) x (by H): full_window()
+  ModImageBinning binning{1, 1, MOD_BIN_MEAN, 0};
   int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
   ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
   // mod_set_cluster_members: read by the calls that write the lists when they enqueue the cluster stage (members_on false: off)
@@ -138,6 +141,9 @@ struct ModContext {
   // Bayer messages under a rectification are demosaiced whole (debayer, then rectify): the grey planes k_rectify then samples, one
   // per frame of mod_rectify_dev (the host paths have their own, beside their raw stages); allocated on first use, grow-only
   RawStage bayer_grey;
+  // with a binning set: the full-window grey planes the converters write and k_bin_mono reads, one per frame of
+  // mod_image_to_mono_dev / mod_rectify_dev (the host paths have their own two, beside their raw stages); on first use, grow-only
+  RawStage bin_grey;
   // RGB-D cameras (depth.hip): the depth messages' layout (mod_set_depth_layout; while has_depth_layout is false: 16UC1 packed at the
   // camera's size) and the opt-in registration to the image camera; both read when a call / submit is made
   ModDepthLayout depth_layout{};
@@ -160,7 +166,7 @@ struct ModContext {
     DevPtr<ModObject> objects;
   };
   // one-frame staging of the synchronous entry points (allocated on first use; ready: the last allocation has succeeded)
-  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; RawStage raw, bayer_grey; } staging;
+  struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; RawStage raw, bayer_grey, bin_grey; } staging;
   // host streaming (mod_submit_frame_host and the mod_submit_*_host image entries): a slot per ticket, a ring of MOD_PIPELINE_DEPTH + 1
   // planes (frame t's plane is frame t+1's "previous"), two copy streams and the events and fences that order them with the kernels
   struct Pipe {
@@ -183,6 +189,7 @@ struct ModContext {
       Fence stage_read;                              // ... the kernels that read them have been enqueued (context stream)
       RawStage raw;                                  // with a rectification set: the slot's two raw messages instead, behind the same fence
       RawStage bayer_grey;                           // ... and, for Bayer messages, their two demosaiced grey planes (k_rectify samples these)
+      RawStage bin_grey;                             // with a binning set: the frame's two full-window grey planes (k_bin_mono reads these), behind the same fence
       // mod_submit_depth_host: the slot's depth window (with a registration: whole message) as it arrives, and the kernels that read
       // it have been enqueued (context stream); the slot's z-buffer [maxN], written and read on the context's stream only
       RawStage depth;
@@ -291,13 +298,17 @@ inline const ModClusterMembers *cluster_members(const ModContext *c) { return c-
 int scene_flow_staged(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *out);
 
 // host_images.hip
+// The window the image paths take from a message: the camera's size, or with a binning b its (bx W) x (by H)
+struct Window { int w, h; size_t pixels() const { return (size_t)w * h; } };
+inline bool binned(const ModImageBinning &b) { return b.bx * b.by > 1; }
+inline Window full_window(const ModContext *c, const ModImageBinning &b) { return {b.bx * c->dc.W, b.by * c->dc.H}; }
 // the layout the host image entry points read (the set one, or mono8 packed W x H), checked against the camera
 int current_layout(ModContext *c, ModImageLayout *out);
 // where the pane of `eye` starts in a row of a side-by-side message
 inline size_t pane_offset(const ModImageLayout &l, int eye) { return eye == MOD_EYE_RIGHT ? (size_t)l.width * image_channels(l.encoding) : 0; }
 // side by side (mod_set_side_by_side): `right` of a call that takes one message for both eyes must be NULL or that message
 int check_one_message(ModContext *c, const uint8_t *left, const uint8_t *right);
-// with a rectification set (the caller has checked that, and eye): the map of `eye` for the window of `l` is in c->rect.map[eye].q when this returns MOD_OK (built, behind
+// with a rectification set (the caller has checked that, and eye): the map of `eye` for the window of `l` (the full one of the binning in force) is in c->rect.map[eye].q when this returns MOD_OK (built, behind
 // the context's stream, unless it is the cached one; refused while tickets are outstanding)
 int ensure_rectify_map(ModContext *c, int eye, const ModImageLayout &l);
 // room for `need` bytes in r; a buffer that has to grow is replaced once the context's streams have drained
@@ -308,22 +319,28 @@ size_t window_stage_bytes(const ModContext *c);   // what ImageIngest::stage mus
 // The one way of host images to grey, in two halves that a caller runs in order.  Where one call's / one frame's images go:
 struct ImageIngest {
   ModImageLayout lay;
+  ModImageBinning bin;              // the binning of this call / submit; while on, the converters write the full window into ...
+  ModContext::RawStage *bin_grey;   // ... two planes here (ensure_bin_stage), mono8 windows are copied there, and k_bin_mono makes grey0 / grey1
   bool rectify, panes;              // a rectification is set; img0 holds both eyes side by side (img1 is not read)
   int eye1;                         // rectifying: the map of the second image
   uint8_t *stage;                   // colour windows / Bayer regions as they arrive (unused for mono8 and when rectifying)
   ModContext::RawStage *raw, *bayer_grey;   // rectifying: the whole messages, and the demosaiced planes of Bayer ones (ensure_raw_stages)
-  uint8_t *grey0, *grey1;           // the results; mono8 windows are copied straight into them.  grey1 null: one image (RGB-D)
+  uint8_t *grey0, *grey1;           // the results; without a binning mono8 windows are copied straight into them.  grey1 null: one image (RGB-D)
   // the caller's choice: the two colour windows become grey in ONE k_to_mono launch of two frames, not two launches of one.  It needs
   // grey1 == grey0 + W H (the staged windows are a window's bytes apart anyway); the synchronous calls ask for it, the stream never does
   bool batch2;
   // the images pass through a stage and kernels make the grey images (false: mono8 windows, copied straight into grey0 / grey1)
-  bool staged() const { return rectify || lay.encoding != MOD_ENCODING_MONO8; }
+  bool staged() const { return rectify || lay.encoding != MOD_ENCODING_MONO8 || binned(bin); }
+  // ... and that stage is `stage` (false: raw messages when rectifying; mono8 windows on their way to k_bin_mono lie in bin_grey)
+  bool windows_staged() const { return !rectify && lay.encoding != MOD_ENCODING_MONO8; }
 };
 // rectifying: room for two raw messages of in.lay in *in.raw and, when they are Bayer mosaics, for their two grey planes in *in.bayer_grey
 int ensure_raw_stages(ModContext *c, const ImageIngest &in);
+// binning: room for the two full-window grey planes in *in.bin_grey (nothing to do while it is off)
+int ensure_bin_stage(ModContext *c, const ImageIngest &in);
 // the copies, on copy_stream: whole messages when rectifying, else Bayer regions / mono8 windows / colour windows
 int ingest_copy(ModContext *c, const ImageIngest &in, const uint8_t *img0, const uint8_t *img1, hipStream_t copy_stream);
-// the kernels, on the context's stream: k_rectify (behind k_bayer_to_mono), k_bayer_to_mono, k_to_mono; none unless in.staged()
+// the kernels, on the context's stream: k_rectify (behind k_bayer_to_mono), k_bayer_to_mono, k_to_mono, then k_bin_mono when binning; none unless in.staged()
 int ingest_to_grey(ModContext *c, const ImageIngest &in);
 // the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
 int current_depth_layout(ModContext *c, ModDepthLayout *out);

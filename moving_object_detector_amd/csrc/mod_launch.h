@@ -170,7 +170,11 @@ void launch_bayer_to_mono(int W, int H, int frames, const uint8_t *src, size_t f
 int bayer_phase(int encoding, int x, int y);
 inline bool is_bayer(int encoding) { return bayer_phase(encoding, 0, 0) >= 0; }
 
-// raw camera images to rectified grey (rectify.hip).  map: device int32 [H][W][2], where each pixel of the W x H window lies in the
+// grey planes reduced by an integer factor (binning.hip).  src: packed planes [frames][by H][bx W] -> dst [frames][H][W]; b: factors
+// and mode, checked by the caller (mod_set_image_binning)
+void launch_bin_mono(const ModImageBinning &b, int W, int H, int frames, const uint8_t *src, uint8_t *dst, hipStream_t s);
+
+// raw camera images to rectified grey (rectify.hip). map: device int32 [H][W][2], where each pixel of the W x H window lies in the
 // width x height message (1/32 pixel; launch_rectify_map fills it for the window at (x0, y0)) -> dst [frames][H][W].
 // Frames lie frame_bytes apart; `extent` bytes from a frame's first one may be loaded (step * height, or less for a pane of a
 // side-by-side message: src then points at the pane and width is the pane's)

@@ -83,6 +83,16 @@ class SceneFlowConstructor {
   // use submitStereo() or submitOdometry()), and the two submits treat them as missing images and return -1.  Switch it off before
   // handing two messages in again; frames already submitted keep the setting of their submit.
   void setSideBySide(bool on) { side_by_side_ = on; }
+  // image binning (mod_set_image_binning; image_proc/crop_decimate's step on the GPU): while set, submitOdometry() and submitDepth()
+  // take messages whose window at (x0, y0) is (bx W) x (by H) and reduce it to the camera's W x H; mode MOD_BIN_MEAN or
+  // MOD_BIN_NEAREST; bx = by = 1: off, the default.  The CameraInfo handed to setCameraInfo() is the BINNED one (include/mod_sf.h
+  // states the relation; sensor_msgs/CameraInfo's binning_x / binning_y describe the same thing).  estimateDisparity(),
+  // estimateOpticalFlow() and submitStereo() compare the message's size with the camera's and so refuse full-resolution messages:
+  // use the two submits above.  Throws where the library refuses the values; frames already submitted keep the setting of their submit.
+  void setImageBinning(int bx, int by, int mode = MOD_BIN_MEAN) {
+    const ModImageBinning b{bx, by, mode, 0};
+    check(mod_set_image_binning(ctx_, &b));
+  }
   bool estimateDisparity(const mod_host::Image *left_image, const mod_host::Image *right_image, const mod_host::CameraInfo &left_camera_info,
                          const mod_host::CameraInfo &right_camera_info, mod_host::DisparityImage *disparity, std::vector<float> *pixels) {
     if (!left_image || !right_image || !left_image->data || !right_image->data) return false;

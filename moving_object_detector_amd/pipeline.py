@@ -184,6 +184,19 @@ class Context:
         self._check(self.lib.mod_get_side_by_side(self.h, C.byref(on)))
         return bool(on.value)
 
+    def set_image_binning(self, bx: int = 1, by: int = 1, mode=capi.MOD_BIN_MEAN) -> None:
+        """Bin the camera images on the GPU at ingest (mod_set_image_binning, image_proc/crop_decimate's step): every image entry point
+        takes a (bx W) x (by H) window of its messages and reduces it to the context's W x H, `mode` capi.MOD_BIN_MEAN ("mean", the
+        rounded box mean) or capi.MOD_BIN_NEAREST ("nearest", the block's top-left pixel).  No arguments = off (the default).  The
+        camera given to set_camera is the binned one (capi.binned_camera).  Read when a call or a submit is made."""
+        b = capi.image_binning(bx, by, mode)
+        self._check(self.lib.mod_set_image_binning(self.h, C.byref(b)))
+
+    def get_image_binning(self) -> capi.ModImageBinning:
+        b = capi.ModImageBinning()
+        self._check(self.lib.mod_get_image_binning(self.h, C.byref(b)))
+        return b
+
     def set_depth_layout(self, layout: Optional[capi.ModDepthLayout]) -> None:
         """Layout of the depth messages of an RGB-D camera (mod_set_depth_layout, capi.depth_layout); None = 16UC1 packed at the camera
         size.  Read when a call or a submit is made."""
@@ -401,8 +414,10 @@ class Context:
 
     def rectification_map(self, eye: int = capi.MOD_EYE_LEFT, layout: Optional[capi.ModImageLayout] = None) -> np.ndarray:
         """The map k_rectify reads for `eye` and the window of `layout` (None = the context's), from the device
-        (mod_rectify_map_host): (H, W, 2) int32, (qx, qy) in 1/32 pixel of the raw message."""
-        out = np.empty((self.height, self.width, 2), dtype=np.int32)
+        (mod_rectify_map_host): (H, W, 2) int32, (qx, qy) in 1/32 pixel of the raw message; with a binning set the full window's map,
+        (by H, bx W, 2)."""
+        b = self.get_image_binning()
+        out = np.empty((b.by * self.height, b.bx * self.width, 2), dtype=np.int32)
         self._check(self.lib.mod_rectify_map_host(self.h, int(eye), C.byref(layout) if layout is not None else None, out.ctypes.data))
         return out
 
