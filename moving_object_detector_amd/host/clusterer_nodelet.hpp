@@ -46,11 +46,8 @@ class ClustererNodelet {
     check(mod_cluster_cloud_host(ctx_, input_pc_msg.data.data(), (int32_t)input_pc_msg.width, (int32_t)input_pc_msg.height,
                                  (int32_t)input_pc_msg.point_step, (int32_t)input_pc_msg.row_step,
                                  cluster_map ? cluster_map->data() : nullptr, objs.data(), (int32_t)objs.size(), &n_obj));
-    if (moving_objects) {              // publishMovingObjects (:324-343): header = input header, ids over accepted clusters
-      moving_objects->header = input_pc_msg.header;
-      moving_objects->moving_object_array.clear();
-      for (int i = 0; i < n_obj && i < (int)objs.size(); i++) moving_objects->moving_object_array.push_back(mod_host::to_message(objs[i]));
-    }
+    // publishMovingObjects (:324-343): header = input header, ids over accepted clusters
+    if (moving_objects) mod_host::fill_objects(*moving_objects, input_pc_msg.header, objs.data(), n_obj, objs.size());
   }
 
   void setMaxObjects(int n) { max_objects_ = n; }

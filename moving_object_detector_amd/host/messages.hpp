@@ -213,5 +213,32 @@ inline MovingObject to_message(const ModObject &o) {
   for (int i = 0; i < 4; i++) m.center.orientation[i] = o.orientation[i];
   return m;
 }
+// publishMovingObjects (clusterer_nodelet.cpp:324-343): the first n records the library reported, at most the `cap` the array holds
+inline void fill_objects(MovingObjectArray &out, const Header &header, const ModObject *objects, int n, size_t cap) {
+  out.header = header;
+  out.moving_object_array.clear();
+  for (int i = 0; i < n && i < (int)cap; i++) out.moving_object_array.push_back(to_message(objects[i]));
+}
+// publishPointcloud (scene_flow_constructor.cpp:351-362): the organized w x h cloud of 32-byte records around `data`
+inline void describe_cloud(PointCloud2 &cloud, const Header &header, int w, int h) {
+  cloud.header = header;
+  cloud.width = w; cloud.height = h;
+  cloud.point_step = 32; cloud.row_step = 32 * w;
+  cloud.is_dense = true;   // PCL's (width, height, value) constructor leaves is_dense = true
+}
+
+// geometry_msgs/Transform <-> the C ABI's ModTransform
+inline ModTransform to_mod(const Transform &x) {
+  ModTransform m{};
+  for (int i = 0; i < 3; i++) m.t[i] = x.translation[i];
+  for (int i = 0; i < 4; i++) m.q[i] = x.rotation[i];
+  return m;
+}
+inline Transform from_mod(const ModTransform &m) {
+  Transform x;
+  for (int i = 0; i < 3; i++) x.translation[i] = m.t[i];
+  for (int i = 0; i < 4; i++) x.rotation[i] = m.q[i];
+  return x;
+}
 
 }  // namespace mod_host

@@ -148,23 +148,39 @@ class SceneFlowConstructorNode {
     o.seq = h.seq; o.stamp = mod_host::Time(h.stamp.sec, h.stamp.nsec); o.frame_id = h.frame_id;
     return o;
   }
+  static mod_host::Transform transform_of(const geometry_msgs::Transform &m) {
+    mod_host::Transform t;
+    t.translation[0] = m.translation.x; t.translation[1] = m.translation.y; t.translation[2] = m.translation.z;
+    t.rotation[0] = m.rotation.x; t.rotation[1] = m.rotation.y; t.rotation[2] = m.rotation.z; t.rotation[3] = m.rotation.w;
+    return t;
+  }
+  static geometry_msgs::Transform message_of(const mod_host::Transform &t) {
+    geometry_msgs::Transform m;
+    m.translation.x = t.translation[0]; m.translation.y = t.translation[1]; m.translation.z = t.translation[2];
+    m.rotation.x = t.rotation[0]; m.rotation.y = t.rotation[1]; m.rotation.z = t.rotation[2]; m.rotation.w = t.rotation[3];
+    return m;
+  }
+  // the first-frame block (:368-375): camera model from the left CameraInfo, of the centred crop window when `crop` is set
+  // (image_crop.cpp:31-39); disparity fields as the estimator reports them
+  void setCamera(const sensor_msgs::CameraInfo &left_camera_info, const sensor_msgs::CameraInfo &right_camera_info, bool crop) {
+    mod_host::CameraInfo info;
+    info.width = left_camera_info.width; info.height = left_camera_info.height;
+    for (int i = 0; i < 12; i++) info.P[i] = left_camera_info.P[i];
+    if (crop) info = mod_host::crop_camera_info(info, crop_width_, crop_height_);
+    mod_host::DisparityImage d;
+    d.f = (float)left_camera_info.P[0];
+    d.T = (float)(-right_camera_info.P[3] / right_camera_info.P[0]);
+    d.min_disparity = 0.0f; d.max_disparity = max_disparity_;
+    impl_->setCameraInfo(info, d);
+    camera_set_ = true;
+  }
 
   // stereoCallback (:365-399)
   void stereoCallback(const sensor_msgs::ImageConstPtr &left_image, const sensor_msgs::ImageConstPtr &right_image,
                       const sensor_msgs::CameraInfoConstPtr &left_camera_info, const sensor_msgs::CameraInfoConstPtr &right_camera_info) {
     if (gpu_estimators_) { gpuCallback(left_image, right_image, left_camera_info, right_camera_info); return; }
     const ros::WallTime start_process = ros::WallTime::now();
-    if (!camera_set_) {               // first frame: camera model from the left CameraInfo (:368-375); disparity fields as the estimator reports them
-      mod_host::CameraInfo info;
-      info.width = left_camera_info->width; info.height = left_camera_info->height;
-      for (int i = 0; i < 12; i++) info.P[i] = left_camera_info->P[i];
-      mod_host::DisparityImage d;
-      d.f = (float)left_camera_info->P[0];
-      d.T = (float)(-right_camera_info->P[3] / right_camera_info->P[0]);
-      d.min_disparity = 0.0f; d.max_disparity = max_disparity_;
-      impl_->setCameraInfo(info, d);
-      camera_set_ = true;
-    }
+    if (!camera_set_) setCamera(*left_camera_info, *right_camera_info, false);   // first frame (:368-375); the crop is the GPU path's
     // the estimators of THIS frame (the reference runs them on three threads, :378-388); the GPU is meanwhile busy with the
     // previous frame's scene flow
     sensor_msgs::ImageConstPtr left_flow = previous_left_image_ ? estimateOpticalFlow(previous_left_image_, left_image) : sensor_msgs::ImageConstPtr();
@@ -180,11 +196,7 @@ class SceneFlowConstructorNode {
     if (left_flow) { f.header = header_of(left_flow->header); f.width = left_flow->width; f.height = left_flow->height;
                      f.data = reinterpret_cast<const float *>(left_flow->data.data()); }
     mod_host::Transform t;
-    if (transform_prev2now) {
-      t.translation[0] = transform_prev2now->translation.x; t.translation[1] = transform_prev2now->translation.y; t.translation[2] = transform_prev2now->translation.z;
-      t.rotation[0] = transform_prev2now->rotation.x; t.rotation[1] = transform_prev2now->rotation.y;
-      t.rotation[2] = transform_prev2now->rotation.z; t.rotation[3] = transform_prev2now->rotation.w;
-    }
+    if (transform_prev2now) t = transform_of(*transform_prev2now);
     if (left_flow && optflow_pub_.getNumSubscribers() > 0) optflow_pub_.publish(left_flow);                 // (:99-100)
     // ~depth and ~synthetic_optical_flow are debugging views the reference renders only for subscribers (:114,141); they need the
     // disparity on the host, which the streaming path avoids: when somebody listens, this frame's disparity is fetched as well
@@ -218,16 +230,7 @@ class SceneFlowConstructorNode {
     const ros::WallTime start_process = ros::WallTime::now();
     const bool crop = crop_width_ > 0 && crop_height_ > 0;
     if (!camera_set_) {               // first frame (:368-375); with the crop, the camera of the window (image_crop.cpp:31-39)
-      mod_host::CameraInfo info;
-      info.width = left_camera_info->width; info.height = left_camera_info->height;
-      for (int i = 0; i < 12; i++) info.P[i] = left_camera_info->P[i];
-      if (crop) info = mod_host::crop_camera_info(info, crop_width_, crop_height_);
-      mod_host::DisparityImage d;
-      d.f = (float)left_camera_info->P[0];
-      d.T = (float)(-right_camera_info->P[3] / right_camera_info->P[0]);
-      d.min_disparity = 0.0f; d.max_disparity = max_disparity_;
-      impl_->setCameraInfo(info, d);
-      camera_set_ = true;
+      setCamera(*left_camera_info, *right_camera_info, crop);
       camera_frame_id_ = left_image->header.frame_id;   // (:372)
     }
     publishPendingOdometry();
@@ -259,24 +262,16 @@ class SceneFlowConstructorNode {
       std::string error_msg;
       mod_host::Transform base_to_camera;            // identity unless TF knows better
       if (tf_buffer_.canTransform(base_link_frame_id_, camera_frame_id_, pending_header_.stamp, &error_msg)) {
-        const geometry_msgs::TransformStamped m = tf_buffer_.lookupTransform(base_link_frame_id_, camera_frame_id_, pending_header_.stamp);
-        base_to_camera.translation[0] = m.transform.translation.x; base_to_camera.translation[1] = m.transform.translation.y;
-        base_to_camera.translation[2] = m.transform.translation.z;
-        base_to_camera.rotation[0] = m.transform.rotation.x; base_to_camera.rotation[1] = m.transform.rotation.y;
-        base_to_camera.rotation[2] = m.transform.rotation.z; base_to_camera.rotation[3] = m.transform.rotation.w;
+        base_to_camera = transform_of(tf_buffer_.lookupTransform(base_link_frame_id_, camera_frame_id_, pending_header_.stamp).transform);
       } else {
         ROS_ERROR("The tf from '%s' to '%s' does not seem to be available, will assume it as identity! (%s)", base_link_frame_id_.c_str(),
                   camera_frame_id_.c_str(), error_msg.c_str());
       }
       impl_->setBaseToCamera(base_to_camera);
-      const mod_host::Transform odom_to_base = impl_->odomToBase().toTransform();
       geometry_msgs::TransformStamped msg;
       msg.header.stamp = pending_header_.stamp; msg.header.frame_id = odom_frame_id_;
       msg.child_frame_id = base_link_frame_id_;
-      msg.transform.translation.x = odom_to_base.translation[0]; msg.transform.translation.y = odom_to_base.translation[1];
-      msg.transform.translation.z = odom_to_base.translation[2];
-      msg.transform.rotation.x = odom_to_base.rotation[0]; msg.transform.rotation.y = odom_to_base.rotation[1];
-      msg.transform.rotation.z = odom_to_base.rotation[2]; msg.transform.rotation.w = odom_to_base.rotation[3];
+      msg.transform = message_of(impl_->odomToBase().toTransform());
       tf_broadcaster_.sendTransform(msg);
     }
     if (!pending_flow_.empty() && optflow_pub_.getNumSubscribers() > 0) {      // (:99-100)
@@ -353,9 +348,7 @@ class SceneFlowConstructorNode {
       if (mod_depth_image_host(ctx_, pixels.data(), reinterpret_cast<float *>(m.data.data())) == MOD_OK) depth_pub_.publish(m);
     }
     if (static_flow_pub_.getNumSubscribers() > 0 && t && !view_prev_disparity_.empty()) {
-      ModTransform tf{};
-      for (int i = 0; i < 3; i++) tf.t[i] = t->translation[i];
-      for (int i = 0; i < 4; i++) tf.q[i] = t->rotation[i];
+      const ModTransform tf = mod_host::to_mod(*t);
       sensor_msgs::Image m;
       m.header = header; m.width = l.width; m.height = l.height; m.encoding = "32FC2"; m.step = 8 * l.width; m.data.resize(8 * n);
       if (mod_static_flow_host(ctx_, view_prev_disparity_.data(), &tf, reinterpret_cast<float *>(m.data.data())) == MOD_OK) static_flow_pub_.publish(m);

@@ -132,11 +132,7 @@ class SceneFlowConstructor {
         if (drc > 0) depth_image->clear();   // a message without pixels: the reference publishes no depth image either
       }
     }
-    ModTransform tf{};
-    if (transform_prev2now) {
-      for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
-      for (int i = 0; i < 4; i++) tf.q[i] = transform_prev2now->rotation[i];
-    }
+    const ModTransform tf = transform_prev2now ? mod_host::to_mod(*transform_prev2now) : ModTransform{};
     // time_between_frames = stamp_now - stamp_previous (scene_flow_constructor.cpp:162-164)
     const double dt = (disparity_now && disparity_previous) ? mod_host::duration_sec(disparity_now->header.stamp, disparity_previous->header.stamp) : 0.0;
     const size_t n = (size_t)image_width_ * image_height_;
@@ -151,17 +147,9 @@ class SceneFlowConstructor {
                                           labels ? labels->data() : nullptr, objs.data(), (int32_t)objs.size(), &n_obj);
     if (rc > 0) return false;          // an input is missing: nothing is published (:104,110,122,127,133)
     check(rc);
-    if (pc_with_velocity) {            // publishPointcloud (:351-362): organized cloud, header of the flow image
-      pc_with_velocity->header = left_flow->header;
-      pc_with_velocity->width = image_width_; pc_with_velocity->height = image_height_;
-      pc_with_velocity->point_step = 32; pc_with_velocity->row_step = 32 * image_width_;
-      pc_with_velocity->is_dense = true;   // PCL's (width, height, value) constructor leaves is_dense = true
-    }
-    if (moving_objects) {
-      moving_objects->header = left_flow->header;
-      moving_objects->moving_object_array.clear();
-      for (int i = 0; i < n_obj && i < (int)objs.size(); i++) moving_objects->moving_object_array.push_back(mod_host::to_message(objs[i]));
-    }
+    // publishPointcloud (:351-362): organized cloud, header of the flow image
+    if (pc_with_velocity) mod_host::describe_cloud(*pc_with_velocity, left_flow->header, image_width_, image_height_);
+    if (moving_objects) mod_host::fill_objects(*moving_objects, left_flow->header, objs.data(), n_obj, objs.size());
     return true;
   }
 
@@ -192,28 +180,20 @@ class SceneFlowConstructor {
   int submit(const mod_host::DisparityImage *disparity_now, const mod_host::FlowImage *left_flow,
              const mod_host::Transform *transform_prev2now, mod_host::PointCloud2 *pc_with_velocity,
              mod_host::MovingObjectArray *moving_objects = nullptr) {
-    ModTransform tf{};
-    if (transform_prev2now) {
-      for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
-      for (int i = 0; i < 4; i++) tf.q[i] = transform_prev2now->rotation[i];
+    if (!disparity_now) {
+      check(mod_forget_previous(ctx_));   // estimateDisparity failed: disparity_now_.reset() (:272-276)
+      have_stamp_ = false; have_parked_ = false;
+      return -1;
     }
-    const double dt = (disparity_now && have_stamp_) ? mod_host::duration_sec(disparity_now->header.stamp, previous_stamp_) : 0.0;
     const size_t n = (size_t)image_width_ * image_height_;
-    int32_t ticket = -1;
-    int rc = MOD_SKIP_NO_DISPARITY_NOW;
-    if (disparity_now) {
-      if (pc_with_velocity && pc_with_velocity->data.size() != n * 32) pc_with_velocity->data.resize(n * 32);
-      Pending &p = pending_[next_slot_];
-      p.objects.resize(max_objects_);
+    if (pc_with_velocity && pc_with_velocity->data.size() != n * 32) pc_with_velocity->data.resize(n * 32);
+    const ModTransform tf = transform_prev2now ? mod_host::to_mod(*transform_prev2now) : ModTransform{};
+    return submitFrame(&disparity_now->header.stamp, left_flow ? &left_flow->header : nullptr, pc_with_velocity, moving_objects,
+                       [&](Pending &, double dt, void *cloud, ModObject *objects, int32_t max_objects, int32_t *ticket) {
       // previous disparity: resident in HBM from the last enqueued frame, or the host copy parked by a skipped frame
-      // moving_objects == nullptr: no cluster output is asked for and the library runs the scene-flow stage alone
-      rc = mod_submit_frame_host(ctx_, disparity_now->data, have_parked_ ? parked_.data() : nullptr,
-                                 left_flow ? left_flow->data : nullptr, transform_prev2now ? &tf : nullptr, dt,
-                                 pc_with_velocity ? pc_with_velocity->data.data() : nullptr, nullptr, moving_objects ? p.objects.data() : nullptr,
-                                 moving_objects ? (int32_t)p.objects.size() : 0, &ticket);
+      const int rc = mod_submit_frame_host(ctx_, disparity_now->data, have_parked_ ? parked_.data() : nullptr, left_flow ? left_flow->data : nullptr,
+                                           transform_prev2now ? &tf : nullptr, dt, cloud, nullptr, objects, max_objects, ticket);
       if (rc == MOD_OK) {
-        p.ticket = ticket; p.cloud = pc_with_velocity; p.objs = moving_objects; p.header = left_flow->header;
-        next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
         have_parked_ = false;
       } else if (rc > 0) {
         // nothing was enqueued, so this disparity never reached HBM — yet it IS the next frame's previous one
@@ -222,14 +202,8 @@ class SceneFlowConstructor {
         parked_.assign(disparity_now->data, disparity_now->data + n);
         have_parked_ = true;
       }
-      previous_stamp_ = disparity_now->header.stamp; have_stamp_ = true;
-    } else {
-      check(mod_forget_previous(ctx_));   // estimateDisparity failed: disparity_now_.reset() (:272-276)
-      have_stamp_ = false; have_parked_ = false;
-    }
-    if (rc > 0) return -1;
-    check(rc);
-    return ticket;
+      return rc;
+    });
   }
   // Pipelined stereoCallback() with the estimator on the GPU (BASELINE config 5): estimateDisparity() + construct() of one frame
   // in a single submission — images go in, the disparity plane is produced in HBM, serves as `now` here and as `previous` of the
@@ -244,31 +218,16 @@ class SceneFlowConstructor {
     const bool images = left_image && right_image && left_image->data && right_image->data && left_image->width == panes * image_width_ &&
                         left_image->height == image_height_ && right_image->width == panes * image_width_ &&
                         right_image->height == image_height_ && useLayout(*left_image, *right_image, 0, 0);
-    ModTransform tf{};
-    if (transform_prev2now) {
-      for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
-      for (int i = 0; i < 4; i++) tf.q[i] = transform_prev2now->rotation[i];
-    }
-    const double dt = (images && have_stamp_) ? mod_host::duration_sec(left_image->header.stamp, previous_stamp_) : 0.0;
     const size_t n = (size_t)image_width_ * image_height_;
     if (images && pc_with_velocity && pc_with_velocity->data.size() != n * 32) pc_with_velocity->data.resize(n * 32);
-    Pending &p = pending_[next_slot_];
-    p.objects.resize(max_objects_);
-    int32_t ticket = -1;
-    // pc_with_velocity == nullptr: the 32-byte cloud is neither packed nor copied to the host (nobody subscribes to ~scene_flow);
-    // moving_objects == nullptr: no cluster output is asked for and the library runs the scene-flow stage alone
-    const int rc = mod_submit_stereo_host(ctx_, images ? left_image->data : nullptr, images ? right_image->data : nullptr, &sgm_,
-                                          left_flow ? left_flow->data : nullptr, transform_prev2now ? &tf : nullptr, dt,
-                                          pc_with_velocity ? pc_with_velocity->data.data() : nullptr, nullptr, moving_objects ? p.objects.data() : nullptr,
-                                          moving_objects ? (int32_t)p.objects.size() : 0, nullptr, &ticket);
-    have_parked_ = false;                         // the previous disparity lives in HBM (or is gone with the images)
-    if (images) { previous_stamp_ = left_image->header.stamp; have_stamp_ = true; }
-    else have_stamp_ = false;
-    if (rc > 0) return -1;
-    check(rc);
-    p.ticket = ticket; p.cloud = pc_with_velocity; p.objs = moving_objects; p.header = left_flow->header;
-    next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
-    return ticket;
+    const ModTransform tf = transform_prev2now ? mod_host::to_mod(*transform_prev2now) : ModTransform{};
+    return submitFrame(images ? &left_image->header.stamp : nullptr, left_flow ? &left_flow->header : nullptr, pc_with_velocity, moving_objects,
+                       [&](Pending &, double dt, void *cloud, ModObject *objects, int32_t max_objects, int32_t *ticket) {
+      have_parked_ = false;                         // the previous disparity lives in HBM (or is gone with the images)
+      return mod_submit_stereo_host(ctx_, images ? left_image->data : nullptr, images ? right_image->data : nullptr, &sgm_,
+                                    left_flow ? left_flow->data : nullptr, transform_prev2now ? &tf : nullptr, dt, cloud, nullptr, objects, max_objects,
+                                    nullptr, ticket);
+    });
   }
   // Pipelined stereoCallback() with every estimator on the GPU: images in (any encoding the library takes, rows as the message
   // pads them, the camera-sized window at (x0, y0)), moving objects and the estimated camera motion out.  The layout is taken from
@@ -281,28 +240,14 @@ class SceneFlowConstructor {
                      mod_host::PointCloud2 *pc_with_velocity = nullptr) {
     if (side_by_side_ && !right_image) right_image = left_image;   // one message holds both eyes
     const bool images = left_image && right_image && left_image->data && right_image->data && useLayout(*left_image, *right_image, x0, y0);
-    const double dt = (images && have_stamp_) ? mod_host::duration_sec(left_image->header.stamp, previous_stamp_) : 0.0;
-    Pending &p = pending_[next_slot_];
-    p.objects.resize(max_objects_);
-    if (flow_out) flow_out->resize((size_t)image_width_ * image_height_ * 2);
-    if (disparity_out) disparity_out->resize((size_t)image_width_ * image_height_);
-    if (pc_with_velocity) pc_with_velocity->data.resize((size_t)image_width_ * image_height_ * 32);
-    int32_t ticket = -1;
-    ModFlowParams fp{4, 4, 5, 1, 1};
-    const int rc = mod_submit_odometry_host(ctx_, images ? left_image->data : nullptr, images ? right_image->data : nullptr, &sgm_, &fp,
-                                            &ego_, dt, pc_with_velocity ? pc_with_velocity->data.data() : nullptr, nullptr,
-                                            moving_objects ? p.objects.data() : nullptr,
-                                            moving_objects ? (int32_t)p.objects.size() : 0, disparity_out ? disparity_out->data() : nullptr,
-                                            flow_out ? flow_out->data() : nullptr,
-                                            &p.tf, &p.ego, &ticket);
-    have_parked_ = false;
-    if (images) { previous_stamp_ = left_image->header.stamp; have_stamp_ = true; }
-    else have_stamp_ = false;
-    if (rc > 0) return -1;
-    check(rc);
-    p.ticket = ticket; p.cloud = pc_with_velocity; p.objs = moving_objects; p.header = left_image->header;
-    next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
-    return ticket;
+    sizeOutputs(flow_out, disparity_out, pc_with_velocity);   // always, also for a frame that will be skipped
+    return submitFrame(images ? &left_image->header.stamp : nullptr, left_image ? &left_image->header : nullptr, pc_with_velocity, moving_objects,
+                       [&](Pending &p, double dt, void *cloud, ModObject *objects, int32_t max_objects, int32_t *ticket) {
+      have_parked_ = false;
+      return mod_submit_odometry_host(ctx_, images ? left_image->data : nullptr, images ? right_image->data : nullptr, &sgm_, &flow_, &ego_, dt, cloud,
+                                      nullptr, objects, max_objects, disparity_out ? disparity_out->data() : nullptr,
+                                      flow_out ? flow_out->data() : nullptr, &p.tf, &p.ego, ticket);
+    });
   }
   // RGB-D cameras (mod_submit_depth_host): the layout of the depth messages — `depth` is a sensor_msgs/Image with encoding "16UC1"
   // (millimetres) or "32FC1" (metres), little-endian; unit 0 = the REP 118 default — with the camera-sized window at (x0, y0), and the
@@ -328,31 +273,15 @@ class SceneFlowConstructor {
                   std::vector<float> *disparity_out = nullptr, mod_host::PointCloud2 *pc_with_velocity = nullptr) {
     // while setSideBySide() is on an image is two panes: an RGB-D frame is then a missing image, like two distinct images elsewhere
     const bool images = !side_by_side_ && image && depth && image->data && depth->data && useLayout(*image, *image, x0, y0);
-    ModTransform tf{};
-    if (transform_prev2now) {
-      for (int i = 0; i < 3; i++) tf.t[i] = transform_prev2now->translation[i];
-      for (int i = 0; i < 4; i++) tf.q[i] = transform_prev2now->rotation[i];
-    }
-    const double dt = (images && have_stamp_) ? mod_host::duration_sec(image->header.stamp, previous_stamp_) : 0.0;
-    Pending &p = pending_[next_slot_];
-    p.objects.resize(max_objects_);
-    if (flow_out) flow_out->resize((size_t)image_width_ * image_height_ * 2);
-    if (disparity_out) disparity_out->resize((size_t)image_width_ * image_height_);
-    if (pc_with_velocity) pc_with_velocity->data.resize((size_t)image_width_ * image_height_ * 32);
-    int32_t ticket = -1;
-    ModFlowParams fp{4, 4, 5, 1, 1};
-    const int rc = mod_submit_depth_host(ctx_, images ? image->data : nullptr, images ? depth->data : nullptr, &fp, &ego_, transform_prev2now ? &tf : nullptr,
-                                         dt, pc_with_velocity ? pc_with_velocity->data.data() : nullptr, nullptr, moving_objects ? p.objects.data() : nullptr,
-                                         moving_objects ? (int32_t)p.objects.size() : 0, disparity_out ? disparity_out->data() : nullptr,
-                                         flow_out ? flow_out->data() : nullptr, &p.tf, &p.ego, &ticket);
-    have_parked_ = false;
-    if (images) { previous_stamp_ = image->header.stamp; have_stamp_ = true; }
-    else have_stamp_ = false;
-    if (rc > 0) return -1;
-    check(rc);
-    p.ticket = ticket; p.cloud = pc_with_velocity; p.objs = moving_objects; p.header = image->header;
-    next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
-    return ticket;
+    sizeOutputs(flow_out, disparity_out, pc_with_velocity);   // always, like submitOdometry()
+    const ModTransform tf = transform_prev2now ? mod_host::to_mod(*transform_prev2now) : ModTransform{};
+    return submitFrame(images ? &image->header.stamp : nullptr, image ? &image->header : nullptr, pc_with_velocity, moving_objects,
+                       [&](Pending &p, double dt, void *cloud, ModObject *objects, int32_t max_objects, int32_t *ticket) {
+      have_parked_ = false;
+      return mod_submit_depth_host(ctx_, images ? image->data : nullptr, images ? depth->data : nullptr, &flow_, &ego_, transform_prev2now ? &tf : nullptr, dt,
+                                   cloud, nullptr, objects, max_objects, disparity_out ? disparity_out->data() : nullptr,
+                                   flow_out ? flow_out->data() : nullptr, &p.tf, &p.ego, ticket);
+    });
   }
   // collect() of an odometry ticket: fills the messages, integrates the pose (only when the estimate succeeded) and returns the
   // estimated motion prev -> now; false when visual odometry failed (nothing is published, the pose is unchanged, :251-255).
@@ -360,10 +289,7 @@ class SceneFlowConstructor {
     for (Pending &p : pending_) {
       if (p.ticket != ticket) continue;
       const int rc = finish(p, ticket);
-      if (motion) {
-        for (int i = 0; i < 3; i++) motion->translation[i] = p.tf.t[i];
-        for (int i = 0; i < 4; i++) motion->rotation[i] = p.tf.q[i];
-      }
+      if (motion) *motion = mod_host::from_mod(p.tf);
       return integrateEstimate(p.tf, rc == MOD_OK ? p.ego.status : MOD_EGO_DIVERGED);
     }
     throw std::runtime_error("collectOdometry(): unknown ticket");
@@ -375,10 +301,7 @@ class SceneFlowConstructor {
   // an estimate of the library: integrated only when it succeeded (the reference integrates inside `if (viso_success)`, :231-246)
   bool integrateEstimate(const ModTransform &tf, int ego_status) {
     if (ego_status != MOD_EGO_OK) return false;
-    mod_host::Transform m;
-    for (int i = 0; i < 3; i++) m.translation[i] = tf.t[i];
-    for (int i = 0; i < 4; i++) m.rotation[i] = tf.q[i];
-    integrate(m);
+    integrate(mod_host::from_mod(tf));
     return true;
   }
   void setBaseToCamera(const mod_host::Transform &base_to_camera) { base_to_camera_ = mod_host::Pose::fromTransform(base_to_camera); }
@@ -434,18 +357,40 @@ class SceneFlowConstructor {
     const int rc = mod_collect_frame_host(ctx_, ticket, &n_obj);
     p.ticket = -1;
     if (rc < 0) check(rc);
-    if (p.cloud) {
-      p.cloud->header = p.header;
-      p.cloud->width = image_width_; p.cloud->height = image_height_;
-      p.cloud->point_step = 32; p.cloud->row_step = 32 * image_width_;
-      p.cloud->is_dense = true;
-    }
-    if (p.objs) {
-      p.objs->header = p.header;
-      p.objs->moving_object_array.clear();
-      for (int i = 0; i < n_obj && i < (int)p.objects.size(); i++) p.objs->moving_object_array.push_back(mod_host::to_message(p.objects[i]));
-    }
+    if (p.cloud) mod_host::describe_cloud(*p.cloud, p.header, image_width_, image_height_);
+    if (p.objs) mod_host::fill_objects(*p.objs, p.header, p.objects.data(), n_obj, p.objects.size());
     return rc;
+  }
+
+  // One frame of a submit*(), the part the four entries share.  `stamp`: of the message that times the frame, null where the entry
+  // found its inputs unusable — dt is then 0 and the stamp is forgotten, so the next frame has no previous one either; dt is formed
+  // from the STORED stamp of the frame before.  `enqueue` makes the entry's one mod_submit_*_host call on the slot's buffers and returns
+  // its code: a skip returns -1, an error throws, and only an enqueued frame takes the slot — its ticket carries `header` (read only
+  // then) and the messages collect() fills.  have_parked_ is the entry's to set inside `enqueue`: submit() parks a host copy on a skip and
+  // keeps what is parked on an error, the submits whose previous disparity lives in HBM clear it whatever the code.  cloud == nullptr: the 32-byte cloud is neither packed nor copied to the host (nobody
+  // subscribes to ~scene_flow); objs == nullptr: no cluster output is asked for and the library runs the scene-flow stage alone.
+  template <class Enqueue>
+  int submitFrame(const mod_host::Time *stamp, const mod_host::Header *header, mod_host::PointCloud2 *cloud, mod_host::MovingObjectArray *objs,
+                  Enqueue enqueue) {
+    const double dt = (stamp && have_stamp_) ? mod_host::duration_sec(*stamp, previous_stamp_) : 0.0;
+    Pending &p = pending_[next_slot_];
+    p.objects.resize(max_objects_);
+    int32_t ticket = -1;
+    const int rc = enqueue(p, dt, cloud ? cloud->data.data() : nullptr, objs ? p.objects.data() : nullptr, objs ? (int32_t)p.objects.size() : 0, &ticket);
+    have_stamp_ = stamp != nullptr;
+    if (stamp) previous_stamp_ = *stamp;
+    if (rc > 0) return -1;
+    check(rc);
+    p.ticket = ticket; p.cloud = cloud; p.objs = objs; p.header = *header;
+    next_slot_ = (next_slot_ + 1) % MOD_PIPELINE_DEPTH;
+    return ticket;
+  }
+  // the host copies submitOdometry() and submitDepth() were asked for, at the camera's size
+  void sizeOutputs(std::vector<float> *flow_out, std::vector<float> *disparity_out, mod_host::PointCloud2 *pc_with_velocity) {
+    const size_t n = (size_t)image_width_ * image_height_;
+    if (flow_out) flow_out->resize(n * 2);
+    if (disparity_out) disparity_out->resize(n);
+    if (pc_with_velocity) pc_with_velocity->data.resize(n * 32);
   }
   Pending pending_[MOD_PIPELINE_DEPTH];
   int next_slot_ = 0;
@@ -465,6 +410,7 @@ class SceneFlowConstructor {
 
   ModContext *ctx_;
   ModSgmParams sgm_{128, 6, 96, 8, 1, 1};   // the published configuration of the estimator (oracle/sgm_ref.cpp)
+  ModFlowParams flow_{4, 4, 5, 1, 1};       // include/mod_sf.h defaults
   int image_width_ = 0, image_height_ = 0;
   int max_objects_ = 1024;
   bool have_previous_ = false;
