@@ -143,7 +143,8 @@ typedef struct ModSceneFlowPlanes {
 typedef struct ModClusterOut {
   int32_t   *labels;      /* optional [frames][H][W]: -1 = none, 0..K-1 in the reference's order (removeSmallClusters, :354-393).
                              The reference renders its cluster image only while somebody subscribes to it
-                             (publishClustersImage, :235-236,292-322): pass NULL and the 4 B/px plane is never written. */
+                             (publishClustersImage, :235-236,292-322): pass NULL and the 4 B/px plane is never written.
+                             mod_set_cluster_image draws that image from this plane on the device. */
   ModObject *objects;     /* [frames][max_objects] */
   int32_t   *n_objects;   /* [frames] accepted objects (publishMovingObjects, :324-343) */
   int32_t   *n_clusters;  /* [frames] K = clusters surviving the size filter (may be NULL) */
@@ -225,6 +226,47 @@ typedef struct ModClusterMembers {   /* 32 bytes; device pointers; the caller ow
 int  mod_set_cluster_members(ModContext *ctx, const ModClusterMembers *out);   /* NULL = off (the default) */
 /* *out: the setting in force (zeroed while off); *enabled: 0 / 1.  Either may be NULL. */
 int  mod_get_cluster_members(const ModContext *ctx, ModClusterMembers *out, int32_t *enabled);
+
+/* The cluster image and the markers' colours, opt-in: what publishClustersImage draws (~clusters_image, BGR8, one colour per cluster,
+ * black elsewhere; clusterer_nodelet.cpp:292-322) and the colour cluster2Marker gives marker k (:119-145, color_set.cpp).  Context
+ * state like mod_set_cluster_members.  NULL = off (the default): every call enqueues exactly what it did without this setting.
+ *   The colour of label k in a frame with K = n_clusters[f] clusters is entry (k * 255) / K (integer division) of a 256-entry table:
+ *     ColorSet::resize(K) per frame.  A label outside [0, K) — -1, anything else, every label when K <= 0 — is black (0, 0, 0) and
+ *     never indexes the table.
+ *   The built-in table (palette_bgr NULL) is this library's own hue wheel, NOT OpenCV's COLORMAP_HSV, whose 256 entries the reference
+ *     reads from cv::applyColorMap: for i in 0..255, t = 6 i, s = t >> 8 (0..5), f = t & 255, g = 255 - f, and (R, G, B) is
+ *     s = 0: (255, f, 0); 1: (g, 255, 0); 2: (0, 255, f); 3: (0, g, 255); 4: (f, 0, 255); 5: (255, 0, g); stored B, G, R.  Entry 0 is
+ *     (0, 0, 255), entry 255 is (5, 0, 255) as B, G, R.  A caller who has OpenCV passes COLORMAP_HSV's 768 bytes as palette_bgr and gets
+ *     the reference's bytes.  The table is copied at the call that takes it.
+ *   Which calls write `image` (device): every later mod_cluster_dev and mod_process_dev, chunked or not, for all their frames, after
+ *     the cluster stage, ordered on the context's stream.  They need out->labels and out->n_clusters: with either NULL while the
+ *     setting is on and image is not NULL they return MOD_ERR_INVALID_ARGUMENT and enqueue nothing.
+ *   Which calls write `host_image` (when not NULL): mod_process_frame_host and mod_cluster_cloud_host, frame 0, rendered from the
+ *     staging's own label plane whether or not the caller passed `labels`; the image request alone makes them run the cluster stage.
+ *     And, unlike the member lists, every pipelined submit (mod_submit_frame_host, _stereo_, _images_, _odometry_, _depth_host): the
+ *     submit reads host_image and the table as they are when it is made, the frame in flight keeps both, and the image is valid after
+ *     its ticket has been collected.  A caller rotates buffers by calling mod_set_cluster_image between submits, with tickets
+ *     outstanding too.  A frame that ends at a guard (MOD_SKIP_*) or fails leaves host_image untouched.
+ *   MOD_ERR_INVALID_ARGUMENT (the setting stays as it was): reserved != 0, image and host_image both NULL, image not 16-byte aligned.
+ * The launches are timed inside MOD_STAGE_FINAL. */
+typedef struct ModClusterImage {      /* 32 bytes */
+  uint8_t       *image;        /* device [frames][H][W][3] BGR8, packed (no row padding); for the *_dev calls; 16-byte aligned */
+  uint8_t       *host_image;   /* host  [H][W][3]; for the *_host calls (frame 0 / the ticket's frame) */
+  const uint8_t *palette_bgr;  /* host, 256 x 3 bytes B,G,R, copied at the call; NULL = the built-in table */
+  int64_t        reserved;     /* must be 0 */
+} ModClusterImage;
+int  mod_set_cluster_image(ModContext *ctx, const ModClusterImage *out);     /* NULL = off (the default) */
+/* *out: the setting in force (zeroed while off; palette_bgr: the context's copy of a caller's table, or NULL); *enabled: 0 / 1. */
+int  mod_get_cluster_image(const ModContext *ctx, ModClusterImage *out, int32_t *enabled);
+/* The renderer alone, on any device label plane [frames][H * W] and device n_clusters [frames] at the camera's size, into
+ * image [frames][H][W][3] (device, 16-byte aligned); ordered on the context's stream.  palette_bgr: host, 768 bytes, or NULL. */
+int  mod_cluster_image_dev(ModContext *ctx, int32_t frames, const int32_t *labels, const int32_t *n_clusters,
+                           const uint8_t *palette_bgr, uint8_t *image);
+/* Host only, no context, no GPU: the colour of label k among n_clusters (marker k's r, g, b are bgr[2], bgr[1], bgr[0] over 255.0,
+ * a = 1.0).  MOD_ERR_INVALID_ARGUMENT unless 0 <= k < n_clusters and bgr is not NULL. */
+int  mod_cluster_color(int32_t k, int32_t n_clusters, const uint8_t *palette_bgr, uint8_t bgr[3]);
+/* Host only: the built-in table, 256 x 3 bytes B, G, R. */
+int  mod_cluster_palette(uint8_t palette_bgr[768]);
 
 /* pcl::toROSMsg / pcl::fromROSMsg payload conversion (scene_flow_constructor.cpp:358-361, clusterer_nodelet.cpp:226). */
 int  mod_pack_cloud_dev(ModContext *ctx, int32_t frames, const ModSceneFlowPlanes *planes, void *cloud_aos);
@@ -824,7 +866,8 @@ int  mod_memcpy_d2h(ModContext *ctx, void *host_dst, const void *dev_src, uint64
                                      to 16 frames, as k_select behind it for larger ones (a stage of its own, "select",
                                      until ABI version 1)                                                        */
 #define MOD_STAGE_FINAL       4   /* k_final: labels plane + member compaction + cluster boxes; with
-                                     mod_set_cluster_members on, k_cluster_members: the ordered member lists     */
+                                     mod_set_cluster_members on, k_cluster_members: the ordered member lists; with
+                                     mod_set_cluster_image on, k_cluster_image: the BGR8 cluster image           */
 #define MOD_STAGE_MEDIAN      5   /* k_median + k_median_ties: median-velocity member; object ids               */
 #define MOD_STAGE_CLUSTER_GROUP 6 /* the whole cluster stage of a call, first launch to last (stages 1..5 and, in a chunked
                                      mod_process_dev, the overlap of its chunks: see ModConfig.batch_chunks).  While a timer

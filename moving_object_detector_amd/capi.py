@@ -82,6 +82,7 @@ EXPORTS = [
     "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
     "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
     "mod_set_cluster_members", "mod_get_cluster_members",
+    "mod_set_cluster_image", "mod_get_cluster_image", "mod_cluster_image_dev", "mod_cluster_color", "mod_cluster_palette",
 ]
 
 
@@ -271,7 +272,12 @@ class ModClusterMembers(C.Structure):
     _fields_ = [("offsets", C.c_void_p), ("indices", C.c_void_p), ("points", C.c_void_p), ("reserved", C.c_int64)]
 
 
+class ModClusterImage(C.Structure):
+    _fields_ = [("image", C.c_void_p), ("host_image", C.c_void_p), ("palette_bgr", C.c_void_p), ("reserved", C.c_int64)]
+
+
 MOD_OBJECT_BYTES = C.sizeof(ModObject)
+assert C.sizeof(ModClusterImage) == 32
 assert C.sizeof(ModClusterMembers) == 32
 assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
@@ -372,6 +378,11 @@ def load(require_torch_first: bool = True):
     L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
     L.mod_set_cluster_members.argtypes = [vp, C.POINTER(ModClusterMembers)]
     L.mod_get_cluster_members.argtypes = [vp, C.POINTER(ModClusterMembers), C.POINTER(i32)]
+    L.mod_set_cluster_image.argtypes = [vp, C.POINTER(ModClusterImage)]
+    L.mod_get_cluster_image.argtypes = [vp, C.POINTER(ModClusterImage), C.POINTER(i32)]
+    L.mod_cluster_image_dev.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.mod_cluster_color.argtypes = [i32, i32, vp, vp]
+    L.mod_cluster_palette.argtypes = [vp]
     L.mod_pack_cloud_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), vp]
     L.mod_unpack_cloud_dev.argtypes = [vp, i32, vp, C.POINTER(ModSceneFlowPlanes)]
     L.mod_process_frame_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModTransform), C.c_double, vp, vp, vp, i32,
@@ -396,6 +407,35 @@ def load(require_torch_first: bool = True):
             getattr(L, name).restype = C.c_int
     _lib = L
     return L
+
+
+def palette_bytes(palette):
+    """A caller's colour table as the 768 bytes B, G, R the library takes (a (256, 3) uint8 array, or anything of 768 bytes), or None."""
+    if palette is None:
+        return None
+    import numpy as np
+    b = np.ascontiguousarray(np.asarray(palette, dtype=np.uint8)).reshape(-1)
+    if b.size != 768:
+        raise ValueError("a colour table is 256 x 3 bytes B, G, R")
+    return (C.c_uint8 * 768).from_buffer_copy(b.tobytes())
+
+
+def cluster_color(k: int, K: int, palette=None):
+    """(b, g, r) of label k in a frame of K clusters (mod_cluster_color): entry (k * 255) // K of `palette`, or of the built-in table.
+    Needs no GPU.  Raises ValueError unless 0 <= k < K."""
+    out, pal = (C.c_uint8 * 3)(), palette_bytes(palette)
+    if load().mod_cluster_color(int(k), int(K), pal, out) != MOD_OK:
+        raise ValueError(f"cluster_color: need 0 <= k < K, got k={k}, K={K}")
+    return tuple(out)
+
+
+def cluster_palette():
+    """The built-in colour table (mod_cluster_palette) as a (256, 3) uint8 array B, G, R.  Needs no GPU."""
+    import numpy as np
+    out = (C.c_uint8 * 768)()
+    if load().mod_cluster_palette(out) != MOD_OK:
+        raise RuntimeError("mod_cluster_palette failed")
+    return np.frombuffer(bytes(out), dtype=np.uint8).reshape(256, 3).copy()
 
 
 def camera_struct(cam) -> ModCamera:

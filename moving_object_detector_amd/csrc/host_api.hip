@@ -53,6 +53,18 @@ static int download_sync(ModContext *c, void *dst, const void *src, size_t bytes
   return MOD_OK;
 }
 
+// The frame's cluster image (mod_set_cluster_image) from the buffers' own label plane and cluster count into b.image, on the context's stream
+static int render_frame_image(ModContext *c, ModContext::FrameBuffers &b) {
+  HIP_TRY(c, dalloc(b.image, 3 * c->maxN));
+  return render_cluster_image(c, 1, b.labels, b.nobj + 1, c->image_table, b.image);
+}
+// ... of a synchronous call: rendered and on its way to host_image; the call's last download waits for it
+static int image_sync(ModContext *c, uint8_t *host_image) {
+  if (int rc = render_frame_image(c, c->staging)) return rc;
+  HIP_TRY(c, hipMemcpyAsync(host_image, c->staging.image, 3 * pixels(c), hipMemcpyDeviceToHost, c->stream));
+  return MOD_OK;
+}
+
 static int fetch_cluster_results(ModContext *c, int32_t *labels, ModObject *objects, int32_t max_objects, int32_t *n_objects) {
   const ModContext::HostStaging &h = c->staging;
   int32_t n = 0;
@@ -124,10 +136,12 @@ static int finish_frame(ModContext *c, Pipe::Slot &s, Pipe::RingPlane &now, cons
   Pipe &p = c->pipe;
   const size_t N = pixels(c);
   const ModSceneFlowPlanes pl = planes_at(s.planes, N, o.cloud_aos ? s.aos.get() : nullptr);
-  const ModClusterOut out = cluster_out(s, o.labels);
-  const bool cluster = o.labels || o.objects;     // neither asked for: the scene-flow stage alone (see mod_process_frame_host)
+  uint8_t *const image = cluster_host_image(c);   // read now: the frame keeps the buffer (and, in its launch's arguments, the table) of its submit
+  const ModClusterOut out = cluster_out(s, o.labels || image);
+  const bool cluster = o.labels || o.objects || image;     // none asked for: the scene-flow stage alone (see mod_process_frame_host)
   int rc = cluster ? process_dev(c, &in, &pl, &out, nullptr) : scene_flow_staged(c, &in, &pl);   // (a ticketed frame never writes the member lists)
   if (rc) return rc;
+  if (image && (rc = render_frame_image(c, s))) return rc;
   HIP_TRY(c, hipEventRecord(s.ev_done, c->stream));
   // results: their own stream
   HIP_TRY(c, hipStreamWaitEvent(p.d2h, s.ev_done, 0));
@@ -135,6 +149,7 @@ static int finish_frame(ModContext *c, Pipe::Slot &s, Pipe::RingPlane &now, cons
   if (cluster) HIP_TRY(c, hipMemcpyAsync(s.h_n, s.nobj, sizeof(int32_t), hipMemcpyDeviceToHost, p.d2h));
   else *s.h_n = 0;
   if (o.labels) HIP_TRY(c, hipMemcpyAsync(o.labels, s.labels, sizeof(int32_t) * N, hipMemcpyDeviceToHost, p.d2h));
+  if (image) HIP_TRY(c, hipMemcpyAsync(image, s.image, 3 * N, hipMemcpyDeviceToHost, p.d2h));
   if (o.disparity) {
     HIP_TRY(c, hipMemcpyAsync(o.disparity, now.disparity, sizeof(float) * N, hipMemcpyDeviceToHost, p.d2h));
     HIP_TRY(c, now.copied_out.record(p.d2h));
@@ -377,12 +392,14 @@ int mod_process_frame_host(ModContext *c, const float *disparity_now, const floa
   HIP_TRY(c, plane_in(c, h.flow, flow, 2, c->stream));
   const ModFrameBatch in{1, 0, h.dnow, h.dprev, h.flow, transform, &dt};   // frames, reserved, now, previous, flow, transforms, dt
   const ModSceneFlowPlanes pl = planes_at(h.planes + 2 * N, N, cloud_aos ? h.aos.get() : nullptr);
-  const ModClusterOut out = cluster_out(h, labels);
-  // no cluster output asked for (neither labels nor objects nor their count): the scene-flow stage alone — a constructor whose
+  uint8_t *const image = cluster_host_image(c);
+  const ModClusterOut out = cluster_out(h, labels || image);
+  // no cluster output asked for (neither labels nor objects nor their count nor the cluster image): the scene-flow stage alone — a constructor whose
   // moving objects nobody takes does not cluster (the reference's constructor never does; its clusterer is a node of its own)
-  const bool cluster = labels || objects || n_objects;
-  rc = cluster ? mod_process_dev(c, &in, &pl, &out) : scene_flow_staged(c, &in, &pl);
+  const bool cluster = labels || objects || n_objects || image;
+  rc = cluster ? process_dev(c, &in, &pl, &out, cluster_members(c)) : scene_flow_staged(c, &in, &pl);
   if (rc) return rc;
+  if (image && (rc = image_sync(c, image))) return rc;
   if (cloud_aos) HIP_TRY(c, hipMemcpyAsync(cloud_aos, h.aos, 32 * N, hipMemcpyDeviceToHost, c->stream));
   return cluster ? fetch_cluster_results(c, labels, objects, max_objects, n_objects) : download_sync(c, nullptr, nullptr, 0);
 }
@@ -452,9 +469,11 @@ int mod_cluster_cloud_host(ModContext *c, const void *cloud, int32_t width, int3
   pl.x = h.planes; pl.y = h.planes + N;         // the caller's cloud unpacked for the clusterer: the x and y planes too
   launch_unpack(N, h.aos, pl.x, pl.y, pl.z, pl.vx, pl.vy, pl.vz, c->stream);
   HIP_TRY(c, hipGetLastError());
-  const ModClusterOut out = cluster_out(h, labels);
+  uint8_t *const image = cluster_host_image(c);
+  const ModClusterOut out = cluster_out(h, labels || image);
   if ((rc = begin_cluster_scratch(c)) || (rc = run_cluster(c, 1, &pl, c->b.cluster.mask, false, false, &out, cluster_members(c)))) return rc;
   c->scratch_clean = true;
+  if (image && (rc = image_sync(c, image))) return rc;
   return fetch_cluster_results(c, labels, objects, max_objects, n_objects);
 }
 

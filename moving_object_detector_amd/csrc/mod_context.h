@@ -122,6 +122,12 @@ struct ModContext {
   // mod_set_cluster_members: read by the calls that write the lists when they enqueue the cluster stage (members_on false: off)
   ModClusterMembers members{};
   bool members_on = false;
+  // mod_set_cluster_image: read by mod_cluster_dev / mod_process_dev (image) and by the *_host calls and the submits (host_image) when
+  // they enqueue their work; image_table: the table in force, a caller's copied at the set call (image_bytes: its bytes, for mod_get_cluster_image)
+  ModClusterImage image{};
+  bool image_on = false;
+  label_palette::Table image_table{};
+  uint8_t image_bytes[3 * label_palette::kEntries] = {};
   int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
   // mod_set_rectification: the calibrations and, per eye, the map in HBM with the window and the distortion model it was built for
   // (ensure_rectify_map builds it at the next use after the window, the calibration or the model changed, never under a frame in flight)
@@ -164,6 +170,7 @@ struct ModContext {
     DevPtr<void> aos;
     DevPtr<int32_t> labels, nobj;
     DevPtr<ModObject> objects;
+    DevPtr<uint8_t> image;                  // mod_set_cluster_image: the frame's BGR8 cluster image, 3 maxN bytes, allocated when first needed
   };
   // one-frame staging of the synchronous entry points (allocated on first use; ready: the last allocation has succeeded)
   struct HostStaging : FrameBuffers { DevPtr<float> dnow; bool ready = false; RawStage raw, bayer_grey, bin_grey; } staging;
@@ -293,6 +300,10 @@ int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const u
 // null for the pipelined submits — several tickets in flight would share one buffer
 int process_dev(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, const ModClusterOut *out, const ModClusterMembers *mem);
 inline const ModClusterMembers *cluster_members(const ModContext *c) { return c->members_on ? &c->members : nullptr; }
+// k_cluster_image over `frames` frames at the camera's size on the context's stream, timed inside MOD_STAGE_FINAL
+int render_cluster_image(ModContext *c, int frames, const int32_t *labels, const int32_t *n_clusters, const label_palette::Table &table, uint8_t *image);
+// where the *_host calls and the submits put the frame's image (mod_set_cluster_image), or null: no image is rendered
+inline uint8_t *cluster_host_image(const ModContext *c) { return c->image_on ? c->image.host_image : nullptr; }
 // the scene-flow stage of the host entry points: their SoA planes are internal staging that no caller sees (the cloud leaves as
 // 32-byte records straight from the kernel's registers), so the x and y planes are not written at all
 int scene_flow_staged(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *out);

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/mod_sf.h"
 #include "mod_device.h"
+#include "label_palette.h"
 
 struct SfArgs {
   const float *dnow, *dprev, *flow;   // [F][H][W], [F][H][W], [F][H][W][2]
@@ -81,6 +82,10 @@ void launch_median(const DevCam &c, const ClArgs &a, int frames, hipStream_t s);
 // indices [F][N], points [F][N][3] or null.  Between launch_final and launch_median: k_median_ties reuses the arrays it reads
 struct ClusterMemberOut { int32_t *offsets, *indices; float *points; };
 void launch_cluster_members(const DevCam &c, const ClArgs &a, const ClusterMemberOut &m, int frames, hipStream_t s);
+// The cluster image (label_image.hip): labels [frames][W H] and n_clusters [frames] -> image [frames][W H][3] B, G, R (4-byte aligned);
+// labels outside [0, n_clusters[f]) are black.  The table rides in the kernel's arguments
+void launch_cluster_image(int W, int H, int frames, const int32_t *labels, const int32_t *n_clusters, const label_palette::Table &table,
+                          uint8_t *image, hipStream_t s);
 int ccl_tile_rows();                 // tile height of k_ccl_tile
 int ccl_tiles(int mask_words, int H); // cluster tiles of a frame of H rows of mask_words words (a tile is one word wide)
 int ccl_request_capacity(int n);     // link requests one tile can emit at neighbor_distance n

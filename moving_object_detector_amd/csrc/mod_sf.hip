@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 
 namespace {
@@ -354,6 +355,22 @@ int run_cluster(ModContext *c, int frames, const ModSceneFlowPlanes *pl, const u
   return MOD_OK;
 }
 
+int render_cluster_image(ModContext *c, int frames, const int32_t *labels, const int32_t *n_clusters, const label_palette::Table &table, uint8_t *image) {
+  StageTimer t(c, MOD_STAGE_FINAL, c->stream);
+  launch_cluster_image(c->dc.W, c->dc.H, frames, labels, n_clusters, table, image, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+// mod_set_cluster_image's device image, or null: mod_cluster_dev / mod_process_dev draw none
+static uint8_t *dev_image(const ModContext *c) { return c->image_on ? c->image.image : nullptr; }
+// ... which needs the label plane and the cluster counts of the call
+static int check_image_io(ModContext *c, const ModClusterOut *out) {
+  if (dev_image(c) && out && (!out->labels || !out->n_clusters))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the cluster image is on (mod_set_cluster_image): cluster outputs labels and n_clusters are required");
+  return MOD_OK;
+}
+
 // construct() publishes ~depth as soon as disparity_now exists, before the guards that end a frame without scene flow
 // (scene_flow_constructor.cpp:110-123): on a skipped frame the depth plane is still produced when the caller asked for it.
 static int depth_on_skip(ModContext *c, int skip, const ModFrameBatch *in, const ModSceneFlowPlanes *out) {
@@ -487,14 +504,68 @@ int mod_cluster_dev(ModContext *c, int32_t frames, const ModSceneFlowPlanes *pl,
   int rc = check_ready(c, frames);
   if (rc) return rc;
   const bool have = pl && pl->dynamic_mask;
-  if ((rc = check_cluster_io(c, pl, false, out)) || (rc = begin_cluster_scratch(c))) return rc;
+  if ((rc = check_cluster_io(c, pl, false, out)) || (rc = check_image_io(c, out)) || (rc = begin_cluster_scratch(c))) return rc;
   if ((rc = run_cluster(c, frames, pl, have ? pl->dynamic_mask : c->b.cluster.mask.get(), have, false, out, cluster_members(c)))) return rc;
   c->scratch_clean = true;
-  return MOD_OK;
+  return dev_image(c) ? render_cluster_image(c, frames, out->labels, out->n_clusters, c->image_table, dev_image(c)) : MOD_OK;
 }
 
 int mod_process_dev(ModContext *c, const ModFrameBatch *in, const ModSceneFlowPlanes *pl, const ModClusterOut *out) {
-  return process_dev(c, in, pl, out, c ? cluster_members(c) : nullptr);
+  if (!c || !dev_image(c)) return process_dev(c, in, pl, out, c ? cluster_members(c) : nullptr);
+  // the image is drawn once, over all frames, behind the cluster stage (chunked: behind the join of its chunks)
+  int rc = check_batch(c, in);
+  if (!rc && (rc = check_image_io(c, out))) return rc;
+  if ((rc = process_dev(c, in, pl, out, cluster_members(c)))) return rc;
+  return render_cluster_image(c, in->frames, out->labels, out->n_clusters, c->image_table, dev_image(c));
+}
+
+int mod_set_cluster_image(ModContext *c, const ModClusterImage *m) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (m && m->reserved != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster image: reserved must be 0");
+  if (m && !m->image && !m->host_image) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster image: image or host_image is required");
+  if (m && ((uintptr_t)m->image & 15)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster image: image must be 16-byte aligned");
+  c->image_on = m != nullptr;
+  c->image = m ? *m : ModClusterImage{};
+  if (m && m->palette_bgr) {
+    memcpy(c->image_bytes, m->palette_bgr, sizeof(c->image_bytes));
+    c->image.palette_bgr = c->image_bytes;
+  } else {
+    label_palette::builtin_bytes(c->image_bytes);
+  }
+  label_palette::table_from_bytes(c->image_bytes, &c->image_table);
+  return MOD_OK;
+}
+int mod_get_cluster_image(const ModContext *c, ModClusterImage *m, int32_t *enabled) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (m) *m = c->image;
+  if (enabled) *enabled = c->image_on ? 1 : 0;
+  return MOD_OK;
+}
+
+int mod_cluster_image_dev(ModContext *c, int32_t frames, const int32_t *labels, const int32_t *n_clusters, const uint8_t *palette_bgr, uint8_t *image) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!labels || !n_clusters || !image) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster image: labels, n_clusters and image are required");
+  if ((uintptr_t)image & 15) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster image: image must be 16-byte aligned");
+  if ((uintptr_t)labels & 3) return fail(c, MOD_ERR_INVALID_ARGUMENT, "cluster image: labels must be 4-byte aligned");
+  label_palette::Table t;
+  if (palette_bgr) label_palette::table_from_bytes(palette_bgr, &t);
+  else { uint8_t b[3 * label_palette::kEntries]; label_palette::builtin_bytes(b); label_palette::table_from_bytes(b, &t); }
+  return render_cluster_image(c, frames, labels, n_clusters, t, image);
+}
+
+int mod_cluster_color(int32_t k, int32_t n_clusters, const uint8_t *palette_bgr, uint8_t bgr[3]) {
+  if (!bgr || k < 0 || k >= n_clusters) return MOD_ERR_INVALID_ARGUMENT;
+  const uint32_t i = label_palette::palette_index((uint32_t)k, (uint32_t)n_clusters);
+  const uint32_t v = palette_bgr ? (uint32_t)palette_bgr[3 * i] | ((uint32_t)palette_bgr[3 * i + 1] << 8) | ((uint32_t)palette_bgr[3 * i + 2] << 16)
+                                 : label_palette::builtin_bgr(i);
+  bgr[0] = (uint8_t)v; bgr[1] = (uint8_t)(v >> 8); bgr[2] = (uint8_t)(v >> 16);
+  return MOD_OK;
+}
+int mod_cluster_palette(uint8_t palette_bgr[768]) {
+  if (!palette_bgr) return MOD_ERR_INVALID_ARGUMENT;
+  label_palette::builtin_bytes(palette_bgr);
+  return MOD_OK;
 }
 
 int mod_set_cluster_members(ModContext *c, const ModClusterMembers *m) {

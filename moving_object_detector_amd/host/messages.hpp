@@ -2,6 +2,7 @@
 // and runs without ROS.  Field names follow the ROS definitions; a ROS build maps the real messages onto these views
 // (ros_adapter/) without copying pixels.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <memory>
@@ -71,6 +72,29 @@ struct Image {
   std::string encoding = "mono8";
   int step = 0;
 };
+
+// An image the mirror produces (~clusters_image): the pixels live in `pixels`, view.data points at them
+struct OwnedImage { Image view; std::vector<uint8_t> pixels; };
+
+// visualization_msgs/Marker(Array) (melodic): every field of the .msg, with the defaults roscpp gives a fresh message (all zero,
+// empty) — cluster2Marker (clusterer_nodelet.cpp:119-145) sets header, id, type, action, scale, color and points and leaves the rest
+struct ColorRGBA { float r = 0.f, g = 0.f, b = 0.f, a = 0.f; };
+struct Marker {
+  enum : int32_t { POINTS = 8, ADD = 0, DELETEALL = 3 };
+  Header header;
+  std::string ns;
+  int32_t id = 0, type = 0, action = 0;
+  struct { double position[3] = {0, 0, 0}; double orientation[4] = {0, 0, 0, 0}; /* x y z w */ } pose;
+  double scale[3] = {0, 0, 0};
+  ColorRGBA color;
+  struct { int32_t sec = 0, nsec = 0; } lifetime;
+  bool frame_locked = false;
+  std::vector<std::array<double, 3>> points;   // geometry_msgs/Point[]
+  std::vector<ColorRGBA> colors;
+  std::string text, mesh_resource;
+  bool mesh_use_embedded_materials = false;
+};
+struct MarkerArray { std::vector<Marker> markers; };
 
 // MOD_ENCODING_* of a sensor_msgs/Image encoding, -1 for one the library cannot take
 inline int image_encoding(const std::string &e) {

@@ -4,6 +4,8 @@
 //                                clusterer_nodelet.cpp:221-226), pcl::PointXYZVelocity records (pcl_point_xyz_velocity.h:8-34)
 //   moving_object_msgs/MovingObjectArray   out (clusterer_nodelet.cpp:324-343; moving_object_msgs/msg/*.msg)
 //   geometry_msgs/Transform      in   (scene_flow_constructor.cpp:249)
+//   sensor_msgs/Image            out  (~clusters_image, clusterer_nodelet.cpp:292-322)
+//   visualization_msgs/MarkerArray   out (~clusters, clusterer_nodelet.cpp:119-145,269-290)
 // so that recorded traffic (bag payloads, TCPROS bodies) can be fed to / produced by the host mirror byte for byte.
 // Format: little-endian scalars; string = uint32 length + bytes; T[] = uint32 count + elements; bool = uint8;
 // time = uint32 sec + uint32 nsec.  Field order = the .msg definitions of ROS melodic (std_msgs, sensor_msgs, stereo_msgs,
@@ -184,6 +186,97 @@ inline void deserialize(const uint8_t *p, size_t n, mod_host::MovingObjectArray 
     for (int i = 0; i < 3; i++) o.velocity[i] = r.get<double>();
     for (int i = 0; i < 3; i++) o.bounding_box[i] = r.get<double>();
   }
+}
+
+// ---- sensor_msgs/Image (~clusters_image: clusterer_nodelet.cpp:292-322) ----
+// header, height, width, encoding, is_bigendian, step, data[]: the image's `step * height` bytes (step 0: width * channels, packed)
+inline Bytes serialize(const mod_host::Image &m) {
+  const int known = mod_host::image_encoding(m.encoding), enc = known >= 0 ? known : mod_host::bayer_encoding(m.encoding);
+  if (enc < 0) throw std::runtime_error("ros_wire: image encoding '" + m.encoding + "' is not one this library knows");
+  const uint32_t step = (uint32_t)(m.step > 0 ? m.step : m.width * mod_host::image_channels(enc));
+  const size_t bytes = (size_t)step * (size_t)m.height;
+  Bytes b;
+  b.reserve(bytes + 64);
+  Writer w(b);
+  write(w, m.header);
+  w.put<uint32_t>((uint32_t)m.height); w.put<uint32_t>((uint32_t)m.width);
+  w.str(m.encoding);
+  w.put<uint8_t>(0);                                                // is_bigendian
+  w.put<uint32_t>(step);
+  w.put<uint32_t>((uint32_t)bytes); w.raw(m.data, bytes);
+  return b;
+}
+inline void deserialize(const uint8_t *p, size_t n, mod_host::OwnedImage &m) {
+  Reader r(p, n);
+  read(r, m.view.header);
+  m.view.height = (int)r.get<uint32_t>(); m.view.width = (int)r.get<uint32_t>();
+  m.view.encoding = r.str();
+  (void)r.get<uint8_t>();                                           // is_bigendian: 8-bit channels have no byte order
+  m.view.step = (int)r.get<uint32_t>();
+  const uint32_t len = r.get<uint32_t>();
+  if ((uint64_t)(uint32_t)m.view.step * (uint32_t)m.view.height != len) throw std::runtime_error("ros_wire: image geometry inconsistent");
+  const uint8_t *d = r.raw(len);
+  m.pixels.assign(d, d + len);
+  m.view.data = m.pixels.data();
+}
+
+// ---- visualization_msgs/MarkerArray (~clusters: clusterer_nodelet.cpp:119-145,269-290) ----
+// Marker: header, ns, id, type, action, pose (position 3 f64, orientation x y z w), scale (3 f64), color (r g b a f32),
+// lifetime (int32 sec, nsec), frame_locked, points[] (3 f64 each), colors[] (4 f32 each), text, mesh_resource,
+// mesh_use_embedded_materials
+inline void write(Writer &w, const mod_host::ColorRGBA &c) { w.put<float>(c.r); w.put<float>(c.g); w.put<float>(c.b); w.put<float>(c.a); }
+inline void read(Reader &r, mod_host::ColorRGBA &c) { c.r = r.get<float>(); c.g = r.get<float>(); c.b = r.get<float>(); c.a = r.get<float>(); }
+inline void write(Writer &w, const mod_host::Marker &m) {
+  write(w, m.header);
+  w.str(m.ns);
+  w.put<int32_t>(m.id); w.put<int32_t>(m.type); w.put<int32_t>(m.action);
+  for (int i = 0; i < 3; i++) w.put<double>(m.pose.position[i]);
+  for (int i = 0; i < 4; i++) w.put<double>(m.pose.orientation[i]);
+  for (int i = 0; i < 3; i++) w.put<double>(m.scale[i]);
+  write(w, m.color);
+  w.put<int32_t>(m.lifetime.sec); w.put<int32_t>(m.lifetime.nsec);
+  w.put<uint8_t>(m.frame_locked ? 1 : 0);
+  w.put<uint32_t>((uint32_t)m.points.size());
+  for (const std::array<double, 3> &q : m.points) for (int i = 0; i < 3; i++) w.put<double>(q[i]);
+  w.put<uint32_t>((uint32_t)m.colors.size());
+  for (const mod_host::ColorRGBA &c : m.colors) write(w, c);
+  w.str(m.text); w.str(m.mesh_resource);
+  w.put<uint8_t>(m.mesh_use_embedded_materials ? 1 : 0);
+}
+inline void read(Reader &r, mod_host::Marker &m) {
+  read(r, m.header);
+  m.ns = r.str();
+  m.id = r.get<int32_t>(); m.type = r.get<int32_t>(); m.action = r.get<int32_t>();
+  for (int i = 0; i < 3; i++) m.pose.position[i] = r.get<double>();
+  for (int i = 0; i < 4; i++) m.pose.orientation[i] = r.get<double>();
+  for (int i = 0; i < 3; i++) m.scale[i] = r.get<double>();
+  read(r, m.color);
+  m.lifetime.sec = r.get<int32_t>(); m.lifetime.nsec = r.get<int32_t>();
+  m.frame_locked = r.get<uint8_t>() != 0;
+  const uint32_t np = r.get<uint32_t>();
+  if ((uint64_t)np * 24 > r.left()) throw std::runtime_error("ros_wire: marker points longer than the message");
+  m.points.resize(np);
+  for (std::array<double, 3> &q : m.points) for (int i = 0; i < 3; i++) q[i] = r.get<double>();
+  const uint32_t nc = r.get<uint32_t>();
+  if ((uint64_t)nc * 16 > r.left()) throw std::runtime_error("ros_wire: marker colours longer than the message");
+  m.colors.resize(nc);
+  for (mod_host::ColorRGBA &c : m.colors) read(r, c);
+  m.text = r.str(); m.mesh_resource = r.str();
+  m.mesh_use_embedded_materials = r.get<uint8_t>() != 0;
+}
+inline Bytes serialize(const mod_host::MarkerArray &m) {
+  Bytes b;
+  Writer w(b);
+  w.put<uint32_t>((uint32_t)m.markers.size());
+  for (const mod_host::Marker &k : m.markers) write(w, k);
+  return b;
+}
+inline void deserialize(const uint8_t *p, size_t n, mod_host::MarkerArray &m) {
+  Reader r(p, n);
+  const uint32_t cnt = r.get<uint32_t>();
+  if ((uint64_t)cnt * 154 > r.left()) throw std::runtime_error("ros_wire: marker array longer than the message");   // an empty marker is 154 bytes
+  m.markers.assign(cnt, mod_host::Marker());
+  for (mod_host::Marker &k : m.markers) read(r, k);
 }
 
 }  // namespace ros_wire

@@ -59,6 +59,7 @@ class Context:
         self.mask_words = (width + 63) // 64
         self._ws = None
         self._members_ws = None
+        self._image_keep = None
 
     # ---- configuration ----------------------------------------------------------------------------------------
     def _check(self, rc: int) -> int:
@@ -138,6 +139,48 @@ class Context:
         m, on = capi.ModClusterMembers(), C.c_int32(-1)
         self._check(self.lib.mod_get_cluster_members(self.h, C.byref(m), C.byref(on)))
         return m, bool(on.value)
+
+    def set_cluster_image(self, ws: Optional[dict], host_image=None, palette=None) -> None:
+        """The BGR8 cluster image (mod_set_cluster_image), off by default.  ws (workspace(..., image=True)): every later cluster() /
+        process() draws all its frames into ws["image"].  host_image (a writable C-contiguous uint8 buffer of H * W * 3 bytes, e.g. a
+        numpy array): the synchronous host calls and every submit write their frame there; a ticketed frame keeps the buffer and the
+        table of its submit.  palette: a caller's (256, 3) B, G, R table, else the built-in one.  Both None: off.  The context keeps
+        `ws` and `host_image` alive while the setting is on."""
+        if ws is None and host_image is None:
+            self._check(self.lib.mod_set_cluster_image(self.h, None))
+            self._image_keep = None
+            return
+        if ws is not None and ws.get("image") is None:
+            raise ValueError("workspace(..., image=True) allocates the image tensor")
+        host = None
+        if host_image is not None:
+            view = memoryview(host_image)
+            if view.readonly or not view.c_contiguous or view.nbytes < 3 * self.height * self.width:
+                raise ValueError("host_image must be a writable C-contiguous buffer of H * W * 3 bytes")
+            host = C.addressof((C.c_uint8 * view.nbytes).from_buffer(host_image))
+        pal = capi.palette_bytes(palette)
+        m = capi.ModClusterImage(ws["image"].data_ptr() if ws is not None else None, host, C.addressof(pal) if pal is not None else None, 0)
+        self._check(self.lib.mod_set_cluster_image(self.h, C.byref(m)))
+        self._image_keep = (ws, host_image)
+
+    def get_cluster_image(self):
+        """(ModClusterImage in force, enabled)."""
+        m, on = capi.ModClusterImage(), C.c_int32(-1)
+        self._check(self.lib.mod_get_cluster_image(self.h, C.byref(m), C.byref(on)))
+        return m, bool(on.value)
+
+    def render_clusters(self, labels: torch.Tensor, n_clusters: torch.Tensor, palette=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The renderer alone (mod_cluster_image_dev): device int32 labels (F, H, W) or (F, H * W) and int32 n_clusters (F,) ->
+        (F, H, W, 3) uint8 B, G, R; labels outside [0, n_clusters[f]) are black.  Enqueued on the context's stream."""
+        F = int(n_clusters.shape[0])
+        if labels.dtype != torch.int32 or n_clusters.dtype != torch.int32 or labels.numel() != F * self.height * self.width:
+            raise ValueError("render_clusters takes int32 labels of F * H * W elements and int32 n_clusters of F")
+        labels, n_clusters = labels.contiguous(), n_clusters.contiguous()
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 3), dtype=torch.uint8, device=labels.device)
+        pal = capi.palette_bytes(palette)
+        self._check(self.lib.mod_cluster_image_dev(self.h, F, labels.data_ptr(), n_clusters.data_ptr(), pal, out.data_ptr()))
+        return out
 
     def set_flow_propagation(self, seeds: int = 1) -> None:
         """Neighbour-seed propagation of the on-GPU optical flow (mod_set_flow_propagation): 1 = off (the default), 5 = every finer
@@ -276,13 +319,14 @@ class Context:
 
     # ---- buffers ----------------------------------------------------------------------------------------------
     def workspace(self, frames: int, aos: bool = False, extras: bool = False, labels: bool = True, xy: bool = True, members: bool = False,
-                  points: bool = False) -> dict:
+                  points: bool = False, image: bool = False) -> dict:
         """Output buffers for `frames` frames, allocated once and reused.  labels=False: no cluster-label plane (the reference
         renders its cluster image only for subscribers, clusterer_nodelet.cpp:235-236).  xy=False: process() hands the library no x / y
         planes (nobody takes the cloud, scene_flow_constructor.cpp:141-142): the rows 0 and 1 of `planes` are then never written.
-        members=True: the tensors of the per-cluster member lists (set_cluster_members(ws) turns them on), points=True: their x, y, z too."""
+        members=True: the tensors of the per-cluster member lists (set_cluster_members(ws) turns them on), points=True: their x, y, z too.
+        image=True: the (F, H, W, 3) uint8 tensor of the cluster image (set_cluster_image(ws) turns it on; it needs labels=True)."""
         members = members or points
-        key = (frames, self.height, self.width, aos, extras, labels, xy, members, points)
+        key = (frames, self.height, self.width, aos, extras, labels, xy, members, points, image)
         if self._ws is not None and self._ws["key"] == key:
             return self._ws
         H, W, dev = self.height, self.width, self.device
@@ -301,6 +345,7 @@ class Context:
         ws["member_offsets"] = torch.zeros((frames, self.max_objects + 1), dtype=torch.int32, device=dev) if members else None
         ws["member_indices"] = torch.empty((frames, H * W), dtype=torch.int32, device=dev) if members else None
         ws["member_points"] = torch.empty((frames, H * W, 3), dtype=torch.float32, device=dev) if points else None
+        ws["image"] = torch.empty((frames, H, W, 3), dtype=torch.uint8, device=dev) if image else None
         self._ws = ws
         return ws
 
