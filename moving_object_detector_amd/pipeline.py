@@ -37,6 +37,20 @@ def staggered(sizes, dtype, device, stagger_bytes: int = PLANE_STAGGER_BYTES):
     return out
 
 
+class PinnedBuffer:
+    """Page-locked host memory of a context (Context.pinned_copy)."""
+
+    def __init__(self, ctx, ptr: int, nbytes: int):
+        self._ctx, self.ptr, self.nbytes, self.array = ctx, ptr, nbytes, None
+
+    def free(self) -> None:
+        if self.ptr:
+            self.array = None
+            self._ctx._check(self._ctx.lib.mod_host_free(self._ctx.h, self.ptr))
+            self._ctx._pinned.remove(self)
+            self.ptr = None
+
+
 class Context:
     """One context per GPU / stream (single caller), like one SceneFlowConstructor + one ClustererNodelet."""
 
@@ -60,12 +74,18 @@ class Context:
         self._ws = None
         self._members_ws = None
         self._image_keep = None
+        self._pinned = []
 
     # ---- configuration ----------------------------------------------------------------------------------------
     def _check(self, rc: int) -> int:
         if rc < 0:
             raise capi.ModError(rc, self.lib.mod_last_error(self.h).decode())
         return rc
+
+    def _done(self, rc: int, name: str) -> None:
+        """_check for a call that has no skip to report: any code but 0 raises."""
+        if self._check(rc) != 0:
+            raise capi.ModError(rc, f"{name} skipped")
 
     def set_camera(self, cam) -> None:
         s = cam if isinstance(cam, capi.ModCamera) else capi.camera_struct(cam)
@@ -279,20 +299,25 @@ class Context:
         fT / depth where the depth is positive and finite, min_disparity - 1 elsewhere; with a registration set the messages are
         registered to the image camera first (set_depth_splat: with their footprints).  Enqueued on the context's stream."""
         lay = layout if layout is not None else self.get_depth_layout()
-        if not dev.is_contiguous() or dev.device.type != "cuda":
-            raise ValueError("dev must be a contiguous device tensor")
-        frame, nbytes = lay.step * lay.height, dev.numel() * dev.element_size()
+        F, out = self._whole_messages(dev, lay, out, torch.float32, "dev", "messages")
+        self._done(self.lib.mod_depth_to_disparity_dev(self.h, F, dev.data_ptr(), C.byref(lay), out.data_ptr()), "mod_depth_to_disparity_dev")
+        return out
+
+    def _whole_messages(self, t: torch.Tensor, lay, out: Optional[torch.Tensor], out_dtype, name: str, unit: str):
+        """(F, out) for a contiguous device tensor `t` holding F whole messages of lay.step * lay.height bytes (uint8 where the output
+        is; any dtype for depth) and the (F, H, W) tensor the call writes, `out` or a new one."""
+        u8 = out_dtype == torch.uint8
+        if (u8 and t.dtype != torch.uint8) or not t.is_contiguous() or t.device.type != "cuda":
+            raise ValueError(f"{name} must be a contiguous {'uint8 ' if u8 else ''}device tensor")
+        frame, nbytes = lay.step * lay.height, t.numel() * t.element_size()
         if frame <= 0 or nbytes % frame:
-            raise ValueError("dev must hold whole messages of step * height bytes")
+            raise ValueError(f"{name} must hold whole {unit} of step * height bytes")
         F = nbytes // frame
         if out is None:
-            out = torch.empty((F, self.height, self.width), dtype=torch.float32, device=dev.device)
-        elif out.shape != (F, self.height, self.width) or out.dtype != torch.float32 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float32 tensor (F, H, W)")
-        rc = self._check(self.lib.mod_depth_to_disparity_dev(self.h, F, dev.data_ptr(), C.byref(lay), out.data_ptr()))
-        if rc != 0:
-            raise capi.ModError(rc, "mod_depth_to_disparity_dev skipped")
-        return out
+            out = torch.empty((F, self.height, self.width), dtype=out_dtype, device=t.device)
+        elif out.shape != (F, self.height, self.width) or out.dtype != out_dtype or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {str(out_dtype)[6:]} tensor (F, H, W)")
+        return F, out
 
     def speckle_filter(self, dev_planes: torch.Tensor, size: int, range: int) -> torch.Tensor:   # noqa: A002 (stereo_image_proc's name)
         """The speckle stage alone, in place (mod_disparity_speckle_dev), on device float32 planes (F, H, W) or (H, W) of the camera's
@@ -301,13 +326,25 @@ class Context:
         p = dev_planes[None] if dev_planes.dim() == 2 else dev_planes
         if p.dtype != torch.float32 or not p.is_contiguous() or p.device.type != "cuda" or p.shape[1:] != (self.height, self.width):
             raise ValueError("dev_planes must be a contiguous float32 device tensor (F, H, W) at the camera size")
-        rc = self._check(self.lib.mod_disparity_speckle_dev(self.h, p.shape[0], p.data_ptr(), int(size), int(range)))
-        if rc != 0:
-            raise capi.ModError(rc, "mod_disparity_speckle_dev skipped")
+        self._done(self.lib.mod_disparity_speckle_dev(self.h, p.shape[0], p.data_ptr(), int(size), int(range)), "mod_disparity_speckle_dev")
         return dev_planes
+
+    def pinned_copy(self, array) -> "PinnedBuffer":
+        """A copy of `array` in page-locked host memory (mod_host_malloc): .ptr, .nbytes, .array (a numpy view of the copy); the submit
+        methods of host_stream.HostStream take it where they take an array.  Freed by .free() or by close()."""
+        a = np.ascontiguousarray(array)
+        p = C.c_void_p()
+        self._check(self.lib.mod_host_malloc(self.h, a.nbytes, C.byref(p)))
+        buf = PinnedBuffer(self, p.value, a.nbytes)
+        buf.array = np.frombuffer((C.c_uint8 * a.nbytes).from_address(p.value), dtype=a.dtype).reshape(a.shape)
+        buf.array[...] = a
+        self._pinned.append(buf)
+        return buf
 
     def close(self) -> None:
         if getattr(self, "h", None):
+            for buf in list(self._pinned):
+                buf.free()
             self.lib.mod_destroy(self.h)
             self.h = None
 
@@ -409,9 +446,7 @@ class Context:
         elif out.shape != (F, self.height, self.width, 2) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32 tensor (F, H, W, 2)")
         prm = params if params is not None else capi.flow_params()
-        rc = self._check(self.lib.mod_flow_compute_dev(self.h, F, p4.data_ptr(), n4.data_ptr(), C.byref(prm), out.data_ptr()))
-        if rc != 0:
-            raise capi.ModError(rc, "mod_flow_compute_dev skipped")
+        self._done(self.lib.mod_flow_compute_dev(self.h, F, p4.data_ptr(), n4.data_ptr(), C.byref(prm), out.data_ptr()), "mod_flow_compute_dev")
         return out[0] if single and out.dim() == 4 else out
 
     def image_to_mono(self, src: torch.Tensor, layout: Optional[capi.ModImageLayout] = None,
@@ -421,19 +456,8 @@ class Context:
         window at (x0, y0) is converted with OpenCV's 8-bit BGR2GRAY formula (packed YUV 4:2:2: grey = Y).  Enqueued on the context's
         stream."""
         lay = layout if layout is not None else self.get_image_layout()
-        if src.dtype != torch.uint8 or not src.is_contiguous() or src.device.type != "cuda":
-            raise ValueError("src must be a contiguous uint8 device tensor")
-        frame = lay.step * lay.height
-        if frame <= 0 or src.numel() % frame:
-            raise ValueError("src must hold whole frames of step * height bytes")
-        F = src.numel() // frame
-        if out is None:
-            out = torch.empty((F, self.height, self.width), dtype=torch.uint8, device=src.device)
-        elif out.shape != (F, self.height, self.width) or out.dtype != torch.uint8 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 tensor (F, H, W)")
-        rc = self._check(self.lib.mod_image_to_mono_dev(self.h, F, src.data_ptr(), C.byref(lay), out.data_ptr()))
-        if rc != 0:
-            raise capi.ModError(rc, "mod_image_to_mono_dev skipped")
+        F, out = self._whole_messages(src, lay, out, torch.uint8, "src", "frames")
+        self._done(self.lib.mod_image_to_mono_dev(self.h, F, src.data_ptr(), C.byref(lay), out.data_ptr()), "mod_image_to_mono_dev")
         return out
 
     def rectify(self, src: torch.Tensor, layout: Optional[capi.ModImageLayout] = None, eye: int = capi.MOD_EYE_LEFT,
@@ -442,19 +466,8 @@ class Context:
         image_to_mono, `eye` selects the map (capi.MOD_EYE_LEFT / MOD_EYE_RIGHT) and, while side by side, the pane.  Enqueued on the
         context's stream."""
         lay = layout if layout is not None else self.get_image_layout()
-        if src.dtype != torch.uint8 or not src.is_contiguous() or src.device.type != "cuda":
-            raise ValueError("src must be a contiguous uint8 device tensor")
-        frame = lay.step * lay.height
-        if frame <= 0 or src.numel() % frame:
-            raise ValueError("src must hold whole frames of step * height bytes")
-        F = src.numel() // frame
-        if out is None:
-            out = torch.empty((F, self.height, self.width), dtype=torch.uint8, device=src.device)
-        elif out.shape != (F, self.height, self.width) or out.dtype != torch.uint8 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 tensor (F, H, W)")
-        rc = self._check(self.lib.mod_rectify_dev(self.h, F, src.data_ptr(), C.byref(lay), int(eye), out.data_ptr()))
-        if rc != 0:
-            raise capi.ModError(rc, "mod_rectify_dev skipped")
+        F, out = self._whole_messages(src, lay, out, torch.uint8, "src", "frames")
+        self._done(self.lib.mod_rectify_dev(self.h, F, src.data_ptr(), C.byref(lay), int(eye), out.data_ptr()), "mod_rectify_dev")
         return out
 
     def rectification_map(self, eye: int = capi.MOD_EYE_LEFT, layout: Optional[capi.ModImageLayout] = None) -> np.ndarray:
@@ -481,10 +494,8 @@ class Context:
         prm = params if params is not None else capi.ego_params()
         tf = torch.empty((F, 7), dtype=torch.float64, device=dn.device)
         res = torch.empty((F, C.sizeof(capi.ModEgoResult)), dtype=torch.uint8, device=dn.device)
-        rc = self._check(self.lib.mod_egomotion_dev(self.h, F, dp.data_ptr(), dn.data_ptr(), fl.data_ptr(), C.byref(prm), tf.data_ptr(),
-                                                    res.data_ptr()))
-        if rc != 0:
-            raise capi.ModError(rc, "mod_egomotion_dev skipped")
+        self._done(self.lib.mod_egomotion_dev(self.h, F, dp.data_ptr(), dn.data_ptr(), fl.data_ptr(), C.byref(prm), tf.data_ptr(),
+                                                    res.data_ptr()), "mod_egomotion_dev")
         self.synchronize()
         return tf.cpu().numpy(), np.frombuffer(res.cpu().numpy().tobytes(), dtype=EGO_RESULT_DTYPE).copy()
 

@@ -17,11 +17,14 @@ torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PKG = os.path.join(ROOT, "moving_object_detector_amd")
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "models"))
 import bayer_model as bm  # noqa: E402
+from util import assert_same_stream  # noqa: E402
 
 W, H, FR, CAP, DT = 64, 40, 4, 16, 1.0 / 15.0
 PATTERNS = ("rggb", "bggr", "gbrg", "grbg")
+KEYS = ("cloud", "labels", "disparity", "flow", "transform", "ego")      # (what a kind does not write keeps its sentinel)
 # name: message width, height, row padding, window origin (the last one: the camera is the whole message)
 CAMERAS = {"window": (80, 52, 5, 7, 5), "even origin": (80, 52, 0, 8, 6), "whole": (W, H, 3, 0, 0)}
 
@@ -92,66 +95,32 @@ def _params():
 
 def _run(ctx, kind, frames, feed=None):
     """The `kind` stream ("stereo", "images", "odometry") over frames = [(left, right or None, layout dict or None, side by side)],
-    up to MOD_PIPELINE_DEPTH in flight, the layout set in front of every submit.  feed: the flow and transform per frame a "stereo" /
-    "images" run is given (an odometry run's).  Returns every output of every frame."""
-    from moving_object_detector_amd import capi
+    up to MOD_PIPELINE_DEPTH in flight, the layout set in front of every submit.  feed: the odometry run whose flow and transform per
+    frame a "stereo" / "images" run is given.  Returns the finished HostStream: every output of every frame."""
+    from moving_object_detector_amd.host_stream import HostStream
     sp, fp, ep = _params()
-    n = len(frames)
-    out = {k: np.full((n,) + s, -7, t) for k, s, t in (("disp", (H, W), np.float32), ("flow", (H, W, 2), np.float32),
-                                                        ("lab", (H, W), np.int32), ("cloud", (H, W, 8), np.float32))}
-    objs = [(capi.ModObject * CAP)() for _ in range(n)]
-    tfs = [capi.ModTransform((0, 0, 0), (0, 0, 0, 1)) for _ in range(n)]
-    egos = [capi.ModEgoResult() for _ in range(n)]
-    rcs, counts, first = [None] * n, [0] * n, [None] * n
-    t, cnt = C.c_int32(-1), C.c_int32(-1)
-    pending = []
-    L = ctx.lib
-
-    def collect():
-        tk, g = pending.pop(0)
-        rcs[g] = L.mod_collect_frame_host(ctx.h, tk, C.byref(cnt))
-        counts[g] = cnt.value
-
-    assert L.mod_forget_previous(ctx.h) == 0
+    s = HostStream(ctx, len(frames), CAP, transform=((0, 0, 0), (0, 0, 0, 1)))
+    s.forget_previous()
     for f, (l, r, lay, sbs) in enumerate(frames):
-        if len(pending) == capi.MOD_PIPELINE_DEPTH:
-            collect()
+        s.make_room()
         _state(ctx, lay, sbs)
-        lp, rp = l.ctypes.data, (r.ctypes.data if r is not None else None)
-        tail = (out["cloud"][f].ctypes.data, out["lab"][f].ctypes.data, objs[f], CAP, out["disp"][f].ctypes.data)
         if kind == "odometry":
-            rc = L.mod_submit_odometry_host(ctx.h, lp, rp, C.byref(sp), C.byref(fp), C.byref(ep), DT, *tail, out["flow"][f].ctypes.data,
-                                            C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
+            s.submit_odometry(f, l, r, sp, fp, ep, DT)                 # (a negative code raises: a skip code of construct()'s guards only)
         elif kind == "images":
-            rc = L.mod_submit_images_host(ctx.h, lp, rp, C.byref(sp), C.byref(fp), C.byref(feed["tf"][f]), DT, *tail,
-                                          out["flow"][f].ctypes.data, C.byref(t))
+            s.submit_images(f, l, r, sp, fp, feed.transforms[f], DT)
         else:
-            rc = L.mod_submit_stereo_host(ctx.h, lp, rp, C.byref(sp), feed["flow"][f].ctypes.data, C.byref(feed["tf"][f]), DT, *tail, C.byref(t))
-        first[f] = rc
-        if rc == 0:
-            pending.append((t.value, f))
-        else:
-            assert rc > 0, (rc, L.mod_last_error(ctx.h))        # a skip code of construct()'s guards, never an error
-    while pending:
-        collect()
+            s.submit_stereo(f, l, r, sp, feed.flow[f], feed.transforms[f], DT)
+    s.finish()
     _state(ctx, None)
-    out.update(rc=rcs, n=counts, first=first, tfs=tfs, tf=[bytes(x) for x in tfs], ego=[bytes(x) for x in egos],
-               obj=[bytes(objs[f])[:C.sizeof(capi.ModObject) * min(counts[f], CAP)] for f in range(n)])
-    return out
+    return s
 
 
-def _same(a, b, kind):
-    assert a["first"] == b["first"] and a["rc"] == b["rc"] and a["n"] == b["n"]
-    assert any(rc == 0 for rc in a["first"]), "no frame took a ticket: the comparison would be weak"
-    for f in range(len(a["rc"])):
-        if a["first"][f] != 0:
-            continue
-        for k in ("disp", "lab", "cloud") + (("flow",) if kind != "stereo" else ()):
-            assert a[k][f].tobytes() == b[k][f].tobytes(), (k, f)
-        assert a["obj"][f] == b["obj"][f]
-        if kind == "odometry":
-            assert a["tf"][f] == b["tf"][f] and a["ego"][f] == b["ego"][f]
-        assert (a["disp"][f] >= 0).any(), "no disparity at all: the comparison would be weak"
+def _same(a, b):
+    assert any(rc == 0 for rc in a.first), "no frame took a ticket: the comparison would be weak"
+    assert_same_stream(a, b, KEYS)
+    for f in range(len(a.first)):
+        if a.first[f] == 0:
+            assert (a.disparity[f] >= 0).any(), "no disparity at all: the comparison would be weak"
 
 
 @pytest.mark.parametrize("pattern", PATTERNS)
@@ -184,8 +153,7 @@ def mono_runs(ctx):
             fr, lay = _messages(name, pattern, 41)
             grey = [(g[0], g[1], None, False) for _, g in fr]
             odo = _run(ctx, "odometry", grey)
-            feed = {"tf": odo["tfs"], "flow": odo["flow"]}
-            out[name, pattern] = (fr, lay, feed, {"odometry": odo, "images": _run(ctx, "images", grey, feed), "stereo": _run(ctx, "stereo", grey, feed)})
+            out[name, pattern] = (fr, lay, odo, {"odometry": odo, "images": _run(ctx, "images", grey, odo), "stereo": _run(ctx, "stereo", grey, odo)})
     return out
 
 
@@ -193,7 +161,7 @@ def mono_runs(ctx):
 def test_b_streams_match_mono8(ctx, mono_runs, kind):
     for (name, pattern), (fr, lay, feed, want) in mono_runs.items():
         got = _run(ctx, kind, [(m[0], m[1], lay, False) for m, _ in fr], feed)
-        _same(got, want[kind], kind)
+        _same(got, want[kind])
 
 
 @pytest.mark.parametrize("kind", ["images", "odometry"])
@@ -202,13 +170,13 @@ def test_c_frames_in_flight_keep_their_layout(ctx, mono_runs, kind):
     packed mono8, Bayer, mono8): each ticket keeps the layout of its own submit."""
     fr, lay, feed, want = mono_runs["window", "grbg"]
     frames = [(m[0], m[1], lay, False) if f % 2 == 0 else (g[0], g[1], None, False) for f, (m, g) in enumerate(fr)]
-    _same(_run(ctx, kind, frames, feed), want[kind], kind)
+    _same(_run(ctx, kind, frames, feed), want[kind])
     fr2, lay2, _, _ = mono_runs["even origin", "rggb"]     # two Bayer layouts in turn: the same scene seed, another origin and pattern
     other = mono_runs["even origin", "rggb"][3][kind]
     mixed = _run(ctx, kind, [(fr[0][0][0], fr[0][0][1], lay, False)] + [(m[0], m[1], lay2, False) for m, _ in fr2[1:]], feed)
     for f in range(2, FR):                                  # (frame 1's flow has frame 0 of the other layout in front of it)
-        assert mixed["disp"][f].tobytes() == other["disp"][f].tobytes()
-        assert mixed["flow"][f].tobytes() == other["flow"][f].tobytes()
+        assert mixed.disparity[f].tobytes() == other.disparity[f].tobytes()
+        assert mixed.flow[f].tobytes() == other.flow[f].tobytes()
 
 
 def _pane_messages(width, pattern, seed):
@@ -238,7 +206,7 @@ def test_d_side_by_side(ctx, width, pattern):
     sp, _, _ = _params()
     fr, blay = _pane_messages(width, pattern, 51)
     want = _run(ctx, "odometry", [(g[0], g[1], None, False) for _, g in fr])
-    _same(_run(ctx, "odometry", [(both, None, blay, True) for both, _ in fr]), want, "odometry")
+    _same(_run(ctx, "odometry", [(both, None, blay, True) for both, _ in fr]), want)
     got_d, want_d = (np.full((H, W), -7, np.float32) for _ in range(2))
     both, g = fr[1]
     try:
@@ -310,6 +278,7 @@ def test_g_the_smallest_estimator_camera(pattern):
     one, where the staged region's edges are the message's: mod_sgm_compute_host (the synchronous staging) and two
     mod_submit_stereo_host frames (the slot's stage) against the model's grey as mono8."""
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream
     from moving_object_detector_amd.pipeline import Context
     w, h = 9, 7
     c = Context(w, h, max_frames=1)
@@ -321,21 +290,20 @@ def test_g_the_smallest_estimator_camera(pattern):
     rng = np.random.default_rng(81)
     flow = np.zeros((h, w, 2), np.float32)
     tf = capi.ModTransform((0, 0, 0), (0, 0, 0, 1))
-    t, cnt = C.c_int32(-1), C.c_int32(-1)
 
     def run(imgs, lay):
         """[(left, right)] * 2 -> the synchronous disparity of pair 1 and the streamed disparity of pair 1"""
         _state(c, lay)
-        sync, streamed = np.full((h, w), -7, np.float32), np.full((h, w), -7, np.float32)
+        sync = np.full((h, w), -7, np.float32)
         assert c.lib.mod_sgm_compute_host(c.h, imgs[1][0].ctypes.data, imgs[1][1].ctypes.data, C.byref(sp), sync.ctypes.data) == 0
-        assert c.lib.mod_forget_previous(c.h) == 0
+        s = HostStream(c, 2, 0, outputs=("disparity",))
+        s.forget_previous()
         for k, (l, r) in enumerate(imgs):
-            rc = c.lib.mod_submit_stereo_host(c.h, l.ctypes.data, r.ctypes.data, C.byref(sp), flow.ctypes.data, C.byref(tf), DT, None, None, None, 0,
-                                              streamed.ctypes.data, C.byref(t))
-            assert rc == (capi.MOD_SKIP_NO_DISPARITY_PREV if k == 0 else 0), (rc, c.lib.mod_last_error(c.h))
-        assert c.lib.mod_collect_frame_host(c.h, t.value, C.byref(cnt)) == 0
+            s.submit_stereo(k, l, r, sp, flow, tf, DT)
+        s.finish()
+        assert s.first == [capi.MOD_SKIP_NO_DISPARITY_PREV, 0] and s.rc[1] == 0
         _state(c, None)
-        return sync.tobytes(), streamed.tobytes()
+        return sync.tobytes(), s.disparity[1].tobytes()
 
     try:
         for (mw, mh, pad, x0, y0) in [(w, h, 0, 0, 0), (w, h, 3, 0, 0), (12, 9, 1, 0, 0), (12, 9, 0, 3, 2), (12, 9, 2, 3, 0), (12, 9, 0, 1, 1)]:

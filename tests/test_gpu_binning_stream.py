@@ -13,12 +13,15 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "models"))
 import binning_model as bn  # noqa: E402
 import yuv422_model as ym  # noqa: E402
+from util import assert_same_stream  # noqa: E402
 
 W, H, BX, BY, FR, CAP, DT = 64, 32, 2, 2, 4, 16, 1.0 / 15.0
 MW, MH = BX * W, BY * H
+KEYS = ("cloud", "labels", "disparity", "flow", "transform", "ego")      # (what a kind does not write keeps its sentinel)
 
 
 @pytest.fixture(scope="module")
@@ -74,52 +77,24 @@ def _params():
 
 def _run(ctx, kind, imgs, state, feed=None, before_collect=None):
     """The `kind` stream ("stereo", "odometry") over imgs = [(left, right)], up to MOD_PIPELINE_DEPTH in flight; state(ctx) sets the
-    layout and the binning in front of every submit, before_collect(ctx) runs in front of every collect.  Returns every output."""
-    from moving_object_detector_amd import capi
+    layout and the binning in front of every submit, before_collect() runs in front of every collect; feed: the odometry run whose
+    flow and transforms a "stereo" run is given.  Returns the finished HostStream: every output."""
+    from moving_object_detector_amd.host_stream import HostStream
     sp, fp, ep = _params()
-    n = len(imgs)
-    out = {k: np.full((n,) + s, -7, t) for k, s, t in (("disp", (H, W), np.float32), ("flow", (H, W, 2), np.float32),
-                                                        ("lab", (H, W), np.int32), ("cloud", (H, W, 8), np.float32))}
-    objs = [(capi.ModObject * CAP)() for _ in range(n)]
-    tfs = [capi.ModTransform((0, 0, 0), (0, 0, 0, 1)) for _ in range(n)]
-    egos = [capi.ModEgoResult() for _ in range(n)]
-    rcs, counts, first = [None] * n, [0] * n, [None] * n
-    t, cnt = C.c_int32(-1), C.c_int32(-1)
-    pending = []
-    L = ctx.lib
-
-    def collect():
-        if before_collect:
-            before_collect(ctx)
-        tk, g = pending.pop(0)
-        rcs[g] = L.mod_collect_frame_host(ctx.h, tk, C.byref(cnt))
-        counts[g] = cnt.value
-
-    assert L.mod_forget_previous(ctx.h) == 0
+    s = HostStream(ctx, len(imgs), CAP, transform=((0, 0, 0), (0, 0, 0, 1)), before_collect=before_collect)
+    s.forget_previous()
     try:
         for f, (l, r) in enumerate(imgs):
-            if len(pending) == capi.MOD_PIPELINE_DEPTH:
-                collect()
+            s.make_room()
             state(ctx)
-            tail = (out["cloud"][f].ctypes.data, out["lab"][f].ctypes.data, objs[f], CAP, out["disp"][f].ctypes.data)
             if kind == "odometry":
-                rc = L.mod_submit_odometry_host(ctx.h, l.ctypes.data, r.ctypes.data, C.byref(sp), C.byref(fp), C.byref(ep), DT, *tail,
-                                                out["flow"][f].ctypes.data, C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
+                s.submit_odometry(f, l, r, sp, fp, ep, DT)             # (a negative code raises: a skip code of construct()'s guards only)
             else:
-                rc = L.mod_submit_stereo_host(ctx.h, l.ctypes.data, r.ctypes.data, C.byref(sp), feed["flow"][f].ctypes.data, C.byref(feed["tfs"][f]),
-                                              DT, *tail, C.byref(t))
-            first[f] = rc
-            if rc == 0:
-                pending.append((t.value, f))
-            else:
-                assert rc > 0, (rc, L.mod_last_error(ctx.h))        # a skip code of construct()'s guards, never an error
-        while pending:
-            collect()
+                s.submit_stereo(f, l, r, sp, feed.flow[f], feed.transforms[f], DT)
+        s.finish()
     finally:
         _off(ctx)
-    out.update(rc=rcs, n=counts, first=first, tfs=tfs, tf=[bytes(x) for x in tfs], ego=[bytes(x) for x in egos],
-               obj=[bytes(objs[f])[:C.sizeof(capi.ModObject) * min(counts[f], CAP)] for f in range(n)])
-    return out
+    return s
 
 
 def _off(ctx):
@@ -135,18 +110,12 @@ def _on(enc, mode):
     return state
 
 
-def _same(a, b, kind):
-    assert a["first"] == b["first"] and a["rc"] == b["rc"] and a["n"] == b["n"]
-    assert sum(rc == 0 for rc in a["first"]) >= 2, "fewer than two tickets: the comparison would be weak"
-    for f in range(len(a["rc"])):
-        if a["first"][f] != 0:
-            continue
-        for k in ("disp", "lab", "cloud") + (("flow",) if kind != "stereo" else ()):
-            assert a[k][f].tobytes() == b[k][f].tobytes(), (k, f)
-        assert a["obj"][f] == b["obj"][f]
-        if kind == "odometry":
-            assert a["tf"][f] == b["tf"][f] and a["ego"][f] == b["ego"][f]
-        assert (a["disp"][f] >= 0).mean() > 0.25, "hardly any disparity: the comparison would be weak"
+def _same(a, b):
+    assert sum(rc == 0 for rc in a.first) >= 2, "fewer than two tickets: the comparison would be weak"
+    assert_same_stream(a, b, KEYS)
+    for f in range(len(a.first)):
+        if a.first[f] == 0:
+            assert (a.disparity[f] >= 0).mean() > 0.25, "hardly any disparity: the comparison would be weak"
 
 
 @pytest.fixture(scope="module")
@@ -157,7 +126,7 @@ def wanted(ctx, frames):
         imgs = [tuple(fr["binned"][mode]) for fr in frames]
         odo = _run(ctx, "odometry", imgs, _off)
         out[mode] = {"odometry": odo, "stereo": _run(ctx, "stereo", imgs, _off, odo)}
-    assert out[bn.MEAN]["odometry"]["disp"].tobytes() != out[bn.NEAREST]["odometry"]["disp"].tobytes()
+    assert out[bn.MEAN]["odometry"].disparity.tobytes() != out[bn.NEAREST]["odometry"].disparity.tobytes()
     return out
 
 
@@ -165,19 +134,19 @@ def wanted(ctx, frames):
 @pytest.mark.parametrize("kind", ["stereo", "odometry"])
 def test_streams_match_the_binned_mono8(ctx, frames, wanted, kind, mode):
     imgs = [tuple(fr["mono8"]) for fr in frames]
-    _same(_run(ctx, kind, imgs, _on("mono8", mode), wanted[mode]["odometry"]), wanted[mode][kind], kind)
+    _same(_run(ctx, kind, imgs, _on("mono8", mode), wanted[mode]["odometry"]), wanted[mode][kind])
 
 
 def test_the_odometry_stream_on_bgr8(ctx, frames, wanted):
     imgs = [tuple(fr["bgr8"]) for fr in frames]
-    _same(_run(ctx, "odometry", imgs, _on("bgr8", bn.MEAN)), wanted[bn.MEAN]["odometry"], "odometry")
+    _same(_run(ctx, "odometry", imgs, _on("bgr8", bn.MEAN)), wanted[bn.MEAN]["odometry"])
 
 
 def test_a_ticket_keeps_the_binning_of_its_submit(ctx, frames, wanted):
     """every submit with binning on, the setting switched off in front of every collect (and on again by the next submit)"""
     imgs = [tuple(fr["mono8"]) for fr in frames]
-    got = _run(ctx, "odometry", imgs, _on("mono8", bn.MEAN), before_collect=lambda c: c.set_image_binning())
-    _same(got, wanted[bn.MEAN]["odometry"], "odometry")
+    got = _run(ctx, "odometry", imgs, _on("mono8", bn.MEAN), before_collect=ctx.set_image_binning)
+    _same(got, wanted[bn.MEAN]["odometry"])
 
 
 def test_binned_and_plain_submits_in_turn(ctx, frames, wanted):
@@ -190,7 +159,7 @@ def test_binned_and_plain_submits_in_turn(ctx, frames, wanted):
     def turn(c):
         (on if state["f"] % 2 == 0 else _off)(c)
         state["f"] += 1
-    _same(_run(ctx, "odometry", imgs, turn), wanted[bn.MEAN]["odometry"], "odometry")
+    _same(_run(ctx, "odometry", imgs, turn), wanted[bn.MEAN]["odometry"])
 
 
 def test_synchronous_host_calls(ctx, frames):

@@ -12,11 +12,14 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "models"))
 import ingest_model as im  # noqa: E402
+from util import assert_same_stream  # noqa: E402
 
 W, H, FR, CAP, DT = 1280, 720, 4, 64, 1.0 / 15.0
 CANVAS = (1344, 768)
+KEYS = ("labels", "disparity", "flow", "transform", "ego")
 
 
 @pytest.fixture(scope="module")
@@ -50,55 +53,25 @@ def _layout(lay):
 
 def _run(ctx, frames):
     """The odometry stream over `frames` = [(left payload, right payload, layout dict or None)], up to MOD_PIPELINE_DEPTH in flight, the
-    layout set in front of every submit.  Returns every output of every frame."""
+    layout set in front of every submit.  Returns the finished HostStream: every output of every frame."""
     from moving_object_detector_amd import capi
+    from moving_object_detector_amd.host_stream import HostStream
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
-    n = len(frames)
-    out = {k: np.full((n,) + s, -7, t) for k, s, t in (("disp", (H, W), np.float32), ("flow", (H, W, 2), np.float32),
-                                                        ("lab", (H, W), np.int32))}
-    objs = [(capi.ModObject * CAP)() for _ in range(n)]
-    tfs = [capi.ModTransform() for _ in range(n)]
-    egos = [capi.ModEgoResult() for _ in range(n)]
-    rcs, counts = [None] * n, [0] * n
-    t, cnt = C.c_int32(-1), C.c_int32(-1)
-    pending = []
-
-    def collect():
-        tk, g = pending.pop(0)
-        rcs[g] = ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(cnt))
-        counts[g] = cnt.value
-
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
+    s = HostStream(ctx, len(frames), CAP, outputs=KEYS[:3])
+    s.forget_previous()
     for f, (l, r, lay) in enumerate(frames):
-        if len(pending) == capi.MOD_PIPELINE_DEPTH:
-            collect()
+        s.make_room()
         ctx.set_image_layout(_layout(lay))
-        rc = ctx.lib.mod_submit_odometry_host(ctx.h, l.ctypes.data, r.ctypes.data, C.byref(sp), C.byref(fp), C.byref(ep), DT, None,
-                                              out["lab"][f].ctypes.data, objs[f], CAP, out["disp"][f].ctypes.data, out["flow"][f].ctypes.data,
-                                              C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
-        if f == 0:
-            assert rc == capi.MOD_SKIP_NO_FLOW, rc
-            continue
-        assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-        pending.append((t.value, f))
-    while pending:
-        collect()
+        s.submit_odometry(f, l, r, sp, fp, ep, DT)
+    s.finish()
     ctx.set_image_layout(None)
-    out["rc"] = rcs
-    out["n"] = counts
-    out["tf"] = [bytes(x) for x in tfs]
-    out["ego"] = [bytes(x) for x in egos]
-    out["obj"] = [bytes(objs[f])[:112 * counts[f]] for f in range(n)]
-    return out
+    assert s.first == [capi.MOD_SKIP_NO_FLOW] + [0] * (len(frames) - 1)
+    return s
 
 
 def _same(a, b):
-    for f in range(1, len(a["rc"])):
-        for k in ("disp", "flow", "lab"):
-            assert a[k][f].tobytes() == b[k][f].tobytes(), (k, f)
-        for k in ("rc", "n", "tf", "ego", "obj"):
-            assert a[k][f] == b[k][f], (k, f)
-    assert any(a["n"][1:]), "no object in the sequence: the comparison would be weak"
+    assert_same_stream(a, b, KEYS)
+    assert any(a.n[1:]), "no object in the sequence: the comparison would be weak"
 
 
 @pytest.fixture(scope="module")

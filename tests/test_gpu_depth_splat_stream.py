@@ -10,8 +10,9 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
+from moving_object_detector_amd import capi  # noqa: E402
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from test_gpu_depth_stream import DT, FR, H, W, _chain, _Stream  # noqa: E402,F401
+from test_gpu_depth_stream import FR, H, W, _chain, _check, _depth, _stream as _host_stream  # noqa: E402
 
 DW, DH, PAD = W // 2, H // 2, 6
 
@@ -73,11 +74,11 @@ def _separate(ctx, scene, modes, odometry):
 
 
 def _stream(ctx, scene, modes, odometry, flip_in_flight=False):
-    s = _Stream(ctx, FR)
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
+    s = _host_stream(ctx, FR)
+    s.forget_previous()
     for f in range(FR):
         ctx.set_depth_splat(modes[f])
-        s.depth(f, scene["left"][f], scene["depth"][f], None if odometry else (scene["tf"][f] or scene["tf"][1]))
+        _depth(s, f, scene["left"][f], scene["depth"][f], None if odometry else (scene["tf"][f] or scene["tf"][1]))
         if flip_in_flight:
             ctx.set_depth_splat(not modes[f])               # the ticket just submitted is outstanding: it keeps its own setting
     s.finish()
@@ -88,11 +89,11 @@ def _stream(ctx, scene, modes, odometry, flip_in_flight=False):
 def test_stream_with_the_mode_on_matches_the_separate_calls(ctx, scene, odometry):
     want = _separate(ctx, scene, [True] * FR, odometry)
     s = _stream(ctx, scene, [True] * FR, odometry)
-    assert s.first[0] == s.capi.MOD_SKIP_NO_FLOW
+    assert s.first[0] == capi.MOD_SKIP_NO_FLOW
     for f in range(1, FR):
-        s.check(f, want[f], odometry)
+        _check(s, f, want[f], odometry)
     if odometry:
-        assert all(s.egos[f].status == s.capi.MOD_EGO_OK for f in range(1, FR)), [s.egos[f].status for f in range(1, FR)]
+        assert all(s.ego[f].status == capi.MOD_EGO_OK for f in range(1, FR)), [s.ego[f].status for f in range(1, FR)]
 
 
 def test_a_ticket_in_flight_keeps_the_setting_of_its_submit(ctx, scene):
@@ -102,8 +103,8 @@ def test_a_ticket_in_flight_keeps_the_setting_of_its_submit(ctx, scene):
     s = _stream(ctx, scene, modes, False, flip_in_flight=True)
     assert len([f for f in range(FR) if s.first[f] == 0]) == FR - 1
     for f in range(1, FR):
-        s.check(f, want[f], False)
-    valid = [int((s.disp[f] > 0).sum()) for f in range(1, FR)]
+        _check(s, f, want[f], False)
+    valid = [int((s.disparity[f] > 0).sum()) for f in range(1, FR)]
     assert valid[0] < valid[1] and valid[3] < valid[2], valid   # frames 1 and 4 were submitted with the mode off, 2 and 3 with it on
 
 
@@ -112,8 +113,8 @@ def test_the_mode_fills_the_holes_of_the_stream(ctx, scene):
     on = _stream(ctx, scene, [True] * FR, False)
     off = _stream(ctx, scene, [False] * FR, False)
     for f in range(1, FR):
-        n_on, n_off = int((on.disp[f] > 0).sum()), int((off.disp[f] > 0).sum())
+        n_on, n_off = int((on.disparity[f] > 0).sum()), int((off.disparity[f] > 0).sum())
         assert n_on >= n_off and n_on > n_off, (f, n_on, n_off)
         assert n_off <= W * H * 3 // 10 and n_on >= W * H * 8 // 10, (f, n_on, n_off)      # a quarter of the targets against nearly all
-        both = off.disp[f] > 0
-        assert (on.disp[f][both] >= off.disp[f][both]).all()                                # the superset: a z no larger
+        both = off.disparity[f] > 0
+        assert (on.disparity[f][both] >= off.disparity[f][both]).all()                                # the superset: a z no larger

@@ -10,6 +10,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
+from moving_object_detector_amd import capi  # noqa: E402
 
 W, H, FR, CAP, DT = 128, 96, 5, 64, 1.0 / 15.0
 MW, MH, PAD, X0, Y0 = 140, 101, 6, 7, 3          # the depth message: the camera's window at (X0, Y0), rows padded by PAD bytes
@@ -93,65 +94,30 @@ def _chain(ctx, greys, depths, dlay, tfs, odometry):
     return out
 
 
-class _Stream:
-    """mod_submit_depth_host with up to MOD_PIPELINE_DEPTH tickets outstanding; every output of every frame"""
+def _stream(ctx, n):
+    """the driver of mod_submit_depth_host: labels, disparity and flow of n frames, the estimator's records prefilled with 9s"""
+    from moving_object_detector_amd.host_stream import HostStream
+    return HostStream(ctx, n, CAP, outputs=("labels", "disparity", "flow"), transform=((9, 9, 9), (9, 9, 9, 9)), ego=(-9, -9, -9, -9, -9.0))
 
-    def __init__(self, ctx, n):
-        from moving_object_detector_amd import capi
-        self.ctx, self.capi = ctx, capi
-        self.disp = np.full((n, H, W), -7, np.float32)
-        self.flow = np.full((n, H, W, 2), -7, np.float32)
-        self.lab = np.full((n, H, W), -7, np.int32)
-        self.objs = [(capi.ModObject * CAP)() for _ in range(n)]
-        self.tfs = [capi.ModTransform((9, 9, 9), (9, 9, 9, 9)) for _ in range(n)]
-        self.egos = [capi.ModEgoResult(-9, -9, -9, -9, -9.0) for _ in range(n)]
-        self.first, self.rc, self.n = [None] * n, [None] * n, [None] * n
-        self.pending = []
-        self.t, self.cnt = C.c_int32(-1), C.c_int32(-1)
 
-    def collect(self):
-        tk, g = self.pending.pop(0)
-        self.rc[g] = self.ctx.lib.mod_collect_frame_host(self.ctx.h, tk, C.byref(self.cnt))
-        self.n[g] = self.cnt.value
+def _depth(s, f, image, depth, transform):
+    fp, ep = _params()
+    s.submit_depth(f, image, depth, fp, ep, transform, DT)
 
-    def _tail(self, f):
-        return (None, self.lab[f].ctypes.data, self.objs[f], CAP, self.disp[f].ctypes.data, self.flow[f].ctypes.data,
-                C.byref(self.tfs[f]), C.byref(self.egos[f]), C.byref(self.t))
 
-    def _took(self, f, rc):
-        self.first[f] = rc
-        assert rc >= 0, (rc, self.ctx.lib.mod_last_error(self.ctx.h))
-        if rc == 0:
-            self.pending.append((self.t.value, f))
+def _stereo_odometry(s, f, left, right, sgm):
+    fp, ep = _params()
+    s.submit_odometry(f, left, right, sgm, fp, ep, DT)
 
-    def depth(self, f, image, depth, transform):
-        fp, ep = _params()
-        if len(self.pending) == self.capi.MOD_PIPELINE_DEPTH:
-            self.collect()
-        tf = self.capi.transforms_array([transform[0]], [transform[1]]) if transform is not None else None
-        self._took(f, self.ctx.lib.mod_submit_depth_host(self.ctx.h, image.ctypes.data if image is not None else None,
-                                                         depth.ctypes.data if depth is not None else None, C.byref(fp), C.byref(ep),
-                                                         C.byref(tf[0]) if tf is not None else None, DT, *self._tail(f)))
 
-    def stereo_odometry(self, f, left, right, sgm):
-        fp, ep = _params()
-        if len(self.pending) == self.capi.MOD_PIPELINE_DEPTH:
-            self.collect()
-        self._took(f, self.ctx.lib.mod_submit_odometry_host(self.ctx.h, left.ctypes.data, right.ctypes.data, C.byref(sgm), C.byref(fp), C.byref(ep), DT,
-                                                            *self._tail(f)))
-
-    def finish(self):
-        while self.pending:
-            self.collect()
-
-    def check(self, f, want, odometry):
-        assert self.first[f] == 0 and self.rc[f] == want["rc"] and self.n[f] == want["n"], (f, self.first[f], self.rc[f], self.n[f], want["rc"], want["n"])
-        assert self.disp[f].tobytes() == want["disp"].tobytes(), f
-        assert self.flow[f].tobytes() == want["flow"].tobytes(), f
-        assert self.lab[f].tobytes() == want["lab"].tobytes(), f
-        assert bytes(self.objs[f])[:112 * min(self.n[f], CAP)] == want["obj"][:112 * min(self.n[f], CAP)], f
-        if odometry:
-            assert bytes(self.tfs[f]) == want["tf"] and bytes(self.egos[f]) == want["ego"], f
+def _check(s, f, want, odometry):
+    assert s.first[f] == 0 and s.rc[f] == want["rc"] and s.n[f] == want["n"], (f, s.first[f], s.rc[f], s.n[f], want["rc"], want["n"])
+    assert s.disparity[f].tobytes() == want["disp"].tobytes(), f
+    assert s.flow[f].tobytes() == want["flow"].tobytes(), f
+    assert s.labels[f].tobytes() == want["lab"].tobytes(), f
+    assert s.objects_bytes(f) == want["obj"][:len(s.objects_bytes(f))], f
+    if odometry:
+        assert s.transform_bytes(f) == want["tf"] and s.ego_bytes(f) == want["ego"], f
 
 
 @pytest.fixture(scope="module")
@@ -163,10 +129,10 @@ def chains(ctx, scene):
 
 
 def _run(ctx, scene, odometry, images=None):
-    s = _Stream(ctx, FR)
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
+    s = _stream(ctx, FR)
+    s.forget_previous()
     for f in range(FR):
-        s.depth(f, (images or scene["left"])[f], scene["depth"][f], None if odometry else (scene["tf"][f] or scene["tf"][1]))
+        _depth(s, f, (images or scene["left"])[f], scene["depth"][f], None if odometry else (scene["tf"][f] or scene["tf"][1]))
     s.finish()
     return s
 
@@ -178,12 +144,12 @@ def test_stream_matches_the_separate_calls(ctx, scene, chains, odometry):
         s = _run(ctx, scene, odometry)
     finally:
         ctx.set_depth_layout(None)
-    assert s.first[0] == s.capi.MOD_SKIP_NO_FLOW                                   # no previous image yet
+    assert s.first[0] == capi.MOD_SKIP_NO_FLOW                                   # no previous image yet
     for f in range(1, FR):
-        s.check(f, chains[odometry][f], odometry)
-        assert (s.disp[f] > 0).sum() > W * H // 2
+        _check(s, f, chains[odometry][f], odometry)
+        assert (s.disparity[f] > 0).sum() > W * H // 2
     if odometry:
-        assert all(s.egos[f].status == s.capi.MOD_EGO_OK for f in range(1, FR)), [s.egos[f].status for f in range(1, FR)]
+        assert all(s.ego[f].status == capi.MOD_EGO_OK for f in range(1, FR)), [s.ego[f].status for f in range(1, FR)]
     else:
         assert sum(s.n[1:]) >= 1, "no object in the whole sequence: the comparison would be weak"
 
@@ -192,21 +158,21 @@ def test_guards(ctx, scene):
     """the packed default depth layout; what ends a frame without a ticket, and what the next frame then finds"""
     capi = pytest.importorskip("moving_object_detector_amd.capi")
     L, P, tf = scene["left"], scene["packed"], scene["tf"][1]
-    s = _Stream(ctx, 12)
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
-    s.depth(0, L[0], P[0], tf)
-    s.depth(1, L[1], P[1], tf)
+    s = _stream(ctx, 12)
+    s.forget_previous()
+    _depth(s, 0, L[0], P[0], tf)
+    _depth(s, 1, L[1], P[1], tf)
     assert s.first[:2] == [capi.MOD_SKIP_NO_FLOW, 0]
-    s.depth(2, L[2], None, tf)                                                       # NULL depth ...
-    s.depth(3, L[3], P[3], tf)                                                       # ... leaves neither a previous image nor a disparity
-    s.depth(4, L[4], P[4], tf)
+    _depth(s, 2, L[2], None, tf)                                                       # NULL depth ...
+    _depth(s, 3, L[3], P[3], tf)                                                       # ... leaves neither a previous image nor a disparity
+    _depth(s, 4, L[4], P[4], tf)
     assert s.first[2:5] == [capi.MOD_SKIP_NO_DISPARITY_NOW, capi.MOD_SKIP_NO_FLOW, 0]
-    s.depth(5, None, P[0], tf)                                                       # NULL image: the same
-    s.depth(6, L[0], P[0], tf)
+    _depth(s, 5, None, P[0], tf)                                                       # NULL image: the same
+    _depth(s, 6, L[0], P[0], tf)
     assert s.first[5:7] == [capi.MOD_SKIP_NO_DISPARITY_NOW, capi.MOD_SKIP_NO_FLOW]
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
-    s.depth(7, L[1], P[1], tf)
-    s.depth(8, L[2], P[2], tf)
+    s.forget_previous()
+    _depth(s, 7, L[1], P[1], tf)
+    _depth(s, 8, L[2], P[2], tf)
     assert s.first[7:9] == [capi.MOD_SKIP_NO_FLOW, 0]
     s.finish()
     # mod_submit_frame_host in between, a submit of another kind: the depth stream starts over, the disparity ring goes on
@@ -216,8 +182,8 @@ def test_guards(ctx, scene):
     t = C.c_int32(-1)
     assert ctx.lib.mod_submit_frame_host(ctx.h, d.ctypes.data, None, flow.ctypes.data, C.byref(tfs[0]), DT, None, None, None, 0, C.byref(t)) == 0
     assert ctx.lib.mod_collect_frame_host(ctx.h, t.value, None) == 0
-    s.depth(9, L[3], P[3], tf)
-    s.depth(10, L[4], P[4], tf)
+    _depth(s, 9, L[3], P[3], tf)
+    _depth(s, 10, L[4], P[4], tf)
     assert s.first[9:11] == [capi.MOD_SKIP_NO_FLOW, 0]
     s.finish()
     assert [s.rc[f] for f in (1, 4, 8, 10)] == [0, 0, 0, 0]
@@ -231,15 +197,15 @@ def test_the_packed_layout_and_a_colour_image_give_the_same(ctx, scene, chains):
     lay = colour[0][1]
     ctx.set_image_layout(capi.image_layout(lay["encoding"], lay["width"], lay["height"], lay["step"], lay["x0"], lay["y0"]))
     try:
-        s = _Stream(ctx, FR)
-        assert ctx.lib.mod_forget_previous(ctx.h) == 0
+        s = _stream(ctx, FR)
+        s.forget_previous()
         for f in range(FR):
-            s.depth(f, colour[f][0], scene["packed"][f], scene["tf"][f] or scene["tf"][1])
+            _depth(s, f, colour[f][0], scene["packed"][f], scene["tf"][f] or scene["tf"][1])
         s.finish()
     finally:
         ctx.set_image_layout(None)
     for f in range(1, FR):
-        s.check(f, chains[False][f], False)
+        _check(s, f, chains[False][f], False)
 
 
 def test_registered_stream(ctx, scene):
@@ -255,17 +221,17 @@ def test_registered_stream(ctx, scene):
     ctx.set_depth_layout(lay)
     try:
         want = _chain(ctx, scene["left"], msgs, lay, scene["tf"], True)
-        s = _Stream(ctx, FR)
-        assert ctx.lib.mod_forget_previous(ctx.h) == 0
+        s = _stream(ctx, FR)
+        s.forget_previous()
         for f in range(FR):
-            s.depth(f, scene["left"][f], msgs[f], None)
+            _depth(s, f, scene["left"][f], msgs[f], None)
         s.finish()
     finally:
         ctx.set_depth_layout(None)
         ctx.set_depth_registration(None)
     for f in range(1, FR):
-        s.check(f, want[f], True)
-        valid = s.disp[f] > 0
+        _check(s, f, want[f], True)
+        valid = s.disparity[f] > 0
         assert W * H // 4 < valid.sum() < W * H, "the registered disparity should be mostly valid, with holes"
 
 
@@ -276,22 +242,22 @@ def test_a_stereo_odometry_frame_in_between_is_a_submit_of_another_kind(ctx, sce
     sgm = capi.ModSgmParams(64, 6, 96, 8, 1, 1)
     ctx.set_depth_layout(_window_layout())
     try:
-        s = _Stream(ctx, FR)
-        assert ctx.lib.mod_forget_previous(ctx.h) == 0
+        s = _stream(ctx, FR)
+        s.forget_previous()
         for f in range(FR):
             if f == 2:
-                s.stereo_odometry(f, scene["left"][f], scene["right"][f], sgm)
+                _stereo_odometry(s, f, scene["left"][f], scene["right"][f], sgm)
             else:
-                s.depth(f, scene["left"][f], scene["depth"][f], None)
+                _depth(s, f, scene["left"][f], scene["depth"][f], None)
         s.finish()
     finally:
         ctx.set_depth_layout(None)
     assert s.first == [capi.MOD_SKIP_NO_FLOW, 0, capi.MOD_SKIP_NO_FLOW, capi.MOD_SKIP_NO_FLOW, 0]
-    s.check(1, chains[True][1], True)
-    s.check(4, chains[True][4], True)
+    _check(s, 1, chains[True][1], True)
+    _check(s, 4, chains[True][4], True)
     # ... and two stereo frames in a row still pair with each other
-    s2 = _Stream(ctx, 2)
-    s2.stereo_odometry(0, scene["left"][3], scene["right"][3], sgm)
-    s2.stereo_odometry(1, scene["left"][4], scene["right"][4], sgm)
+    s2 = _stream(ctx, 2)
+    _stereo_odometry(s2, 0, scene["left"][3], scene["right"][3], sgm)
+    _stereo_odometry(s2, 1, scene["left"][4], scene["right"][4], sgm)
     s2.finish()
     assert s2.first == [capi.MOD_SKIP_NO_FLOW, 0]

@@ -49,6 +49,7 @@ def _pair(rng, mw, mh, bpp, pad, sbs):
                          ids=["%dx%d-%s%s%s" % (*cm, n, "-rectified" if r else "", "-side_by_side" if s else "") for cm, n, r, s in CASES])
 def test_the_synchronous_and_the_stream_route_give_the_same_disparity(cam, name, rect, sbs):
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream
     from moving_object_detector_amd.pipeline import Context
     (W, H), (enc, bpp, dw, dh, pad, x0, y0) = cam, CONFIGS[name]
     mw, mh = W + dw, H + dh
@@ -67,19 +68,19 @@ def test_the_synchronous_and_the_stream_route_give_the_same_disparity(cam, name,
         pairs = [_pair(rng, mw, mh, bpp, pad, sbs) for _ in range(2)]
         ptr = lambda m: m.ctypes.data if m is not None else None
         sp = capi.ModSgmParams(8, 6, 96, 8, 1, 1)
-        sync, streamed = np.full((H, W), -7, np.float32), np.full((H, W), -7, np.float32)
+        sync = np.full((H, W), -7, np.float32)
         left, right = pairs[1]
         assert c.lib.mod_sgm_compute_host(c.h, ptr(left), ptr(right), C.byref(sp), sync.ctypes.data) == 0, c.lib.mod_last_error(c.h)
         flow = np.zeros((H, W, 2), np.float32)
         tf = capi.ModTransform((0, 0, 0), (0, 0, 0, 1))
-        t, cnt = C.c_int32(-1), C.c_int32(-1)
         # the stream needs a first frame (it has no previous disparity: it takes a plane and no ticket); the estimator carries nothing
         # from one frame to the next, so the second frame's plane is the second pair's alone, as the synchronous call's is
+        s = HostStream(c, 2, 0, outputs=("disparity",))
         for k, (l, r) in enumerate(pairs):
-            rc = c.lib.mod_submit_stereo_host(c.h, ptr(l), ptr(r), C.byref(sp), flow.ctypes.data, C.byref(tf), DT, None, None, None, 0,
-                                              streamed.ctypes.data, C.byref(t))
-            assert rc == (capi.MOD_SKIP_NO_DISPARITY_PREV if k == 0 else 0), (rc, c.lib.mod_last_error(c.h))
-        assert c.lib.mod_collect_frame_host(c.h, t.value, C.byref(cnt)) == 0, c.lib.mod_last_error(c.h)
+            s.submit_stereo(k, l, r, sp, flow, tf, DT)
+        s.finish()
+        assert s.first == [capi.MOD_SKIP_NO_DISPARITY_PREV, 0] and s.rc[1] == 0
+        streamed = s.disparity[1]
         assert not (sync == -7).any() and not (streamed == -7).any()
         if (W, H) != CAMERAS[0]:      # the plane saw the images (see the module's docstring)
             valid = sync[sync >= 0]

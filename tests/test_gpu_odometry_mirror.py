@@ -2,7 +2,6 @@
 built with g++ against libmod_sf.so) fed coloured bgra8 messages in a padded, larger canvas with the camera of crop_camera_info and
 the centred window: its objects, disparity and motion equal the library's odometry stream fed the grey of those windows (the
 comparison of test_gpu_colour_streams.py (b)), and its integrated pose equals the numpy composition of the collected motions."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -33,6 +32,7 @@ def _rot(q):
 
 def test_mirror_odometry_on_colour_messages(tmp_path):
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream
     from moving_object_detector_amd.pipeline import Context
     prm = synth.Params()
     assert (prm.dynamic_flow_diff, prm.cluster_size, prm.neighbor_distance, prm.depth_diff, prm.dynamic_speed) == (5, 2500, 4, 0.15, 0.3)
@@ -65,24 +65,12 @@ def test_mirror_odometry_on_colour_messages(tmp_path):
     ctx.set_camera(cam)
     ctx.set_params(prm)
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
-    disp = np.full((FR, H, W), -7, np.float32)
-    objs = [(capi.ModObject * CAP)() for _ in range(FR)]
-    tfs = [capi.ModTransform() for _ in range(FR)]
-    t, cnt = C.c_int32(-1), C.c_int32(-1)
-    pending, counts, rcs = [], {}, {}
+    s = HostStream(ctx, FR, CAP, outputs=("disparity",))
     for k in range(FR):
-        if len(pending) == 3:
-            tk, g = pending.pop(0)
-            rcs[g] = ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(cnt)); counts[g] = cnt.value
-        rc = ctx.lib.mod_submit_odometry_host(ctx.h, grey[k][0].ctypes.data, grey[k][1].ctypes.data, C.byref(sp), C.byref(fp), C.byref(ep), DT,
-                                              None, None, objs[k], CAP, disp[k].ctypes.data, None, C.byref(tfs[k]), None, C.byref(t))
-        if k == 0:
-            assert rc == capi.MOD_SKIP_NO_FLOW
-            continue
-        assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-        pending.append((t.value, k))
-    for tk, g in pending:
-        rcs[g] = ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(cnt)); counts[g] = cnt.value
+        s.submit_odometry(k, grey[k][0], grey[k][1], sp, fp, ep, DT)
+    s.finish()
+    assert s.first == [capi.MOD_SKIP_NO_FLOW] + [0] * (FR - 1)
+    disp, objs, tfs, counts, rcs = s.disparity, s.objects, s.transforms, s.n, s.rc
     ctx.close()
 
     buf = (tmp_path / "out.bin").read_bytes()

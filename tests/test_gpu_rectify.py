@@ -220,30 +220,17 @@ def _params():
 def _odometry(ctx, msgs, frames=3):
     """`frames` raw pairs through mod_submit_odometry_host, all in flight together; every output of every ticketed frame, as bytes."""
     from moving_object_detector_amd import capi
+    from moving_object_detector_amd.host_stream import HostStream
     sp, fp, ep = _params()
-    disp = np.full((frames, H_, W_), -7, np.float32)
-    flow = np.full((frames, H_, W_, 2), -7, np.float32)
-    lab = np.full((frames, H_, W_), -7, np.int32)
-    objs = [(capi.ModObject * CAP)() for _ in range(frames)]
-    tfs, egos = [capi.ModTransform() for _ in range(frames)], [capi.ModEgoResult() for _ in range(frames)]
-    t, n = C.c_int32(-1), C.c_int32(-1)
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
-    tickets, out = [], []
+    assert frames <= capi.MOD_PIPELINE_DEPTH + 1
+    s = HostStream(ctx, frames, CAP, outputs=("labels", "disparity", "flow"))
+    s.forget_previous()
     for f in range(frames):
-        rc = ctx.lib.mod_submit_odometry_host(ctx.h, msgs[f][0].ctypes.data, msgs[f][1].ctypes.data, C.byref(sp), C.byref(fp), C.byref(ep), DT,
-                                              None, lab[f].ctypes.data, objs[f], CAP, disp[f].ctypes.data, flow[f].ctypes.data,
-                                              C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
-        if f == 0:
-            assert rc == capi.MOD_SKIP_NO_FLOW, (rc, ctx.lib.mod_last_error(ctx.h))
-        else:
-            assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-            tickets.append(t.value)
-    for f, tk in enumerate(tickets, 1):
-        rc = ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(n))
-        assert rc >= 0, ctx.lib.mod_last_error(ctx.h)
-        out.append((rc, n.value, disp[f].tobytes(), flow[f].tobytes(), lab[f].tobytes(), bytes(tfs[f]), bytes(egos[f]),
-                    bytes(objs[f])[:112 * max(0, min(n.value, CAP))]))
-    return out
+        s.submit_odometry(f, msgs[f][0], msgs[f][1], sp, fp, ep, DT)
+    s.finish()
+    assert s.first == [capi.MOD_SKIP_NO_FLOW] + [0] * (frames - 1)
+    return [(s.rc[f], s.n[f], s.disparity[f].tobytes(), s.flow[f].tobytes(), s.labels[f].tobytes(), s.transform_bytes(f), s.ego_bytes(f),
+             s.objects_bytes(f)) for f in range(1, frames)]
 
 
 def test_identity_rectification_changes_nothing_on_the_host_paths(raw):

@@ -17,10 +17,12 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "models"))
 import yuv422_model as ym  # noqa: E402
 import yuv422_rectify_cases as yc  # noqa: E402
+from util import assert_same_stream  # noqa: E402
 
 W, H, FR, CAP, DT = 1280, 720, 4, 64, 1.0 / 15.0        # the sizes of tests/test_gpu_colour_streams.py
 CANVAS = (W + 14, H + 6)                                 # the window at the odd origin (7, 3) of each pane
 ENCODINGS = ("bgr8", "yuv422_yuy2")
+KEYS = ("labels", "disparity", "flow", "transform", "ego")
 
 
 def _calibration(mw, mh, eye):
@@ -94,55 +96,26 @@ def _frame(scene, enc, f, sbs):
 
 def _run(ctx, frames):
     """The odometry stream over `frames` = [(left, right or None, layout dict, side by side)], up to MOD_PIPELINE_DEPTH in flight,
-    the layout and the state set in front of every submit.  Returns every output of every frame."""
+    the layout and the state set in front of every submit.  Returns the finished HostStream: every output of every frame."""
     from moving_object_detector_amd import capi
+    from moving_object_detector_amd.host_stream import HostStream
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
-    n = len(frames)
-    out = {k: np.full((n,) + s, -7, t) for k, s, t in (("disp", (H, W), np.float32), ("flow", (H, W, 2), np.float32),
-                                                        ("lab", (H, W), np.int32))}
-    objs = [(capi.ModObject * CAP)() for _ in range(n)]
-    tfs = [capi.ModTransform() for _ in range(n)]
-    egos = [capi.ModEgoResult() for _ in range(n)]
-    rcs, counts = [None] * n, [0] * n
-    t, cnt = C.c_int32(-1), C.c_int32(-1)
-    pending = []
-
-    def collect():
-        tk, g = pending.pop(0)
-        rcs[g] = ctx.lib.mod_collect_frame_host(ctx.h, tk, C.byref(cnt))
-        counts[g] = cnt.value
-
-    assert ctx.lib.mod_forget_previous(ctx.h) == 0
+    s = HostStream(ctx, len(frames), CAP, outputs=KEYS[:3])
+    s.forget_previous()
     for f, (l, r, lay, sbs) in enumerate(frames):
-        if len(pending) == capi.MOD_PIPELINE_DEPTH:
-            collect()
+        s.make_room()
         _state(ctx, lay, sbs)
-        rc = ctx.lib.mod_submit_odometry_host(ctx.h, l.ctypes.data, r.ctypes.data if r is not None else None, C.byref(sp), C.byref(fp),
-                                              C.byref(ep), DT, None, out["lab"][f].ctypes.data, objs[f], CAP, out["disp"][f].ctypes.data,
-                                              out["flow"][f].ctypes.data, C.byref(tfs[f]), C.byref(egos[f]), C.byref(t))
-        if f == 0:
-            assert rc == capi.MOD_SKIP_NO_FLOW, (rc, ctx.lib.mod_last_error(ctx.h))
-            continue
-        assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-        pending.append((t.value, f))
-    while pending:
-        collect()
+        s.submit_odometry(f, l, r, sp, fp, ep, DT)
+    s.finish()
     _state(ctx, None, False)
-    out["rc"] = rcs
-    out["n"] = counts
-    out["tf"] = [bytes(x) for x in tfs]
-    out["ego"] = [bytes(x) for x in egos]
-    out["obj"] = [bytes(objs[f])[:112 * counts[f]] for f in range(n)]
-    return out
+    assert s.first == [capi.MOD_SKIP_NO_FLOW] + [0] * (len(frames) - 1)
+    return s
 
 
 def _same(a, b):
-    for f in range(1, len(a["rc"])):
-        for k in ("disp", "flow", "lab"):
-            assert a[k][f].tobytes() == b[k][f].tobytes(), (k, f)
-        for k in ("rc", "n", "tf", "ego", "obj"):
-            assert a[k][f] == b[k][f], (k, f)
-        assert (a["disp"][f] >= 0).any(), "no disparity at all: the comparison would be weak"
+    assert_same_stream(a, b, KEYS)
+    for f in range(1, len(a.rc)):
+        assert (a.disparity[f] >= 0).any(), "no disparity at all: the comparison would be weak"
 
 
 @pytest.fixture(scope="module")
@@ -155,8 +128,8 @@ def separate(scene, ctx):
             out[enc, rect] = _run(ctx, [_frame(scene, enc, f, False) for f in range(FR)])
     _rectification(ctx, scene, False)
     for enc in ENCODINGS:
-        assert any(out[enc, False]["n"][1:]), "no object in the sequence: the comparison would be weak"
-        assert out[enc, False]["disp"][1].tobytes() != out[enc, True]["disp"][1].tobytes()      # the rectification does something
+        assert any(out[enc, False].n[1:]), "no object in the sequence: the comparison would be weak"
+        assert out[enc, False].disparity[1].tobytes() != out[enc, True].disparity[1].tobytes()      # the rectification does something
     return out
 
 

@@ -159,3 +159,21 @@ def compare_objects_bits(gpu_objs, orc_objs):
         for k in ("center", "bounding_box", "velocity"):
             assert bits_equal64(g[k], np.asarray(o[k], np.float64)), (int(o["id"]), k, g[k].tolist(), np.asarray(o[k]).tolist(), o.get("ambiguous"))
         assert np.array_equal(g["orientation"], np.array([0.0, 0.0, 0.0, 1.0]))
+
+
+def assert_same_stream(a, b, keys, frames=None):
+    """Two finished host_stream.HostStream runs gave the same: first, rc and n of every frame in `frames` (None: all), and for the frames
+    that took a ticket, byte for byte, the outputs named in `keys` ("cloud", "labels", "disparity", "flow"; "transform" and "ego" for
+    the estimator's records) and the object records the library reported.  A failure names (key, frame)."""
+    for f in range(len(a.first)) if frames is None else frames:
+        for k in ("first", "rc", "n"):
+            assert getattr(a, k)[f] == getattr(b, k)[f], (k, f, getattr(a, k)[f], getattr(b, k)[f])
+        if a.first[f] != 0:
+            continue
+        for k in keys:
+            if k in ("transform", "ego"):
+                same = getattr(a, k + "_bytes")(f) == getattr(b, k + "_bytes")(f)
+            else:
+                same = getattr(a, k)[f].tobytes() == getattr(b, k)[f].tobytes()
+            assert same, (k, f)
+        assert a.objects_bytes(f) == b.objects_bytes(f), ("objects", f)

@@ -11,7 +11,6 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -80,6 +79,7 @@ def kernel(reps):
 def stream_fps(MW, MH, bx, by, reps):
     """the odometry stream on MW x MH mono8 messages, the camera MW / bx x MH / by"""
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     W, H = MW // bx, MH // by
     m = synth.make_ego_images(MW, MH, seed=1, frames=2)
@@ -90,41 +90,16 @@ def stream_fps(MW, MH, bx, by, reps):
     ctx.set_params(synth.Params())
     ctx.set_image_binning(bx, by, capi.MOD_BIN_MEAN)
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
-    imgs, pins = [], []
-    for k in ("left0", "right0", "left1", "right1"):
-        msg = np.ascontiguousarray(m[k])
-        p = C.c_void_p()
-        assert ctx.lib.mod_host_malloc(ctx.h, msg.nbytes, C.byref(p)) == 0
-        C.memmove(p.value, msg.ctypes.data, msg.nbytes)
-        pins.append(p)
-        imgs.append(p.value)
-    objs = [(capi.ModObject * 64)() for _ in range(3)]
-    t, n = C.c_int32(-1), C.c_int32(-1)
-    pending = []
+    imgs = [ctx.pinned_copy(m[k]) for k in ("left0", "right0", "left1", "right1")]
+    s = HostStream(ctx, 3, 64, outputs=())
 
     def step(i):
-        l, r = imgs[2 * (i % 2)], imgs[2 * (i % 2) + 1]
-        if len(pending) == 3:
-            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-        rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
-                                              None, None, None, None, C.byref(t))
-        assert rc in (0, capi.MOD_SKIP_NO_FLOW), (rc, ctx.lib.mod_last_error(ctx.h))
-        if rc == 0:
-            pending.append(t.value)
+        rc = s.submit_odometry(i % 3, imgs[2 * (i % 2)], imgs[2 * (i % 2) + 1], sp, fp, ep, 1.0 / 15.0)
+        assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
 
-    for i in range(10):
-        step(i)
-    frames = max(20, reps)
-    t0 = time.perf_counter()
-    for i in range(10, 10 + frames):
-        step(i)
-    while pending:
-        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-    dt = time.perf_counter() - t0
-    for p in pins:
-        ctx.lib.mod_host_free(ctx.h, p)
+    fps = stream_rate(s, step, max(20, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
     ctx.close()
-    return frames / dt
+    return fps
 
 
 def main():

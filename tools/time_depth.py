@@ -11,7 +11,6 @@ import functools
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -123,6 +122,7 @@ def ego_images():
 def stream_fps(reps, splat=None):
     """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on"""
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     m = ego_images()
     ctx = Context(W, H, max_frames=1)
@@ -139,42 +139,19 @@ def stream_fps(reps, splat=None):
     fp, ep = capi.flow_params(), capi.ego_params()
     pins = []
     for k in (0, 1):
-        bgr = np.ascontiguousarray(np.repeat(m[f"left{k}"][..., None], 3, axis=2))
+        bgr = np.repeat(m[f"left{k}"][..., None], 3, axis=2)
         mm = np.rint(1000.0 * fT / m[f"disparity{k}"].astype(np.float64)).astype(np.uint16)
-        if splat is not None:
-            mm = np.ascontiguousarray(mm[::2, ::2])
-        for a in (bgr, mm):
-            p = C.c_void_p()
-            assert ctx.lib.mod_host_malloc(ctx.h, a.nbytes, C.byref(p)) == 0
-            C.memmove(p.value, a.ctypes.data, a.nbytes)
-            pins.append(p)
-    objs = [(capi.ModObject * 64)() for _ in range(3)]
-    t, n = C.c_int32(-1), C.c_int32(-1)
-    pending = []
+        pins += [ctx.pinned_copy(bgr), ctx.pinned_copy(mm[::2, ::2] if splat is not None else mm)]
+    s = HostStream(ctx, 3, 64, outputs=())
 
     def step(i):
-        img, dep = (pins[0], pins[1]) if i % 2 == 0 else (pins[2], pins[3])
-        if len(pending) == 3:
-            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-        rc = ctx.lib.mod_submit_depth_host(ctx.h, img, dep, C.byref(fp), C.byref(ep), None, 1.0 / 15.0, None, None, objs[i % 3], 64, None, None,
-                                           None, None, C.byref(t))
+        rc = s.submit_depth(i % 3, pins[2 * (i % 2)], pins[2 * (i % 2) + 1], fp, ep, None, 1.0 / 15.0)
         assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
-        if rc == 0:
-            pending.append(t.value)
 
-    for i in range(10):
-        step(i)
-    frames = max(20, reps) if splat is None else max(300, reps)   # the alternating rounds want a window of a good half second
-    t0 = time.perf_counter()
-    for i in range(10, 10 + frames):
-        step(i)
-    while pending:
-        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-    dt = time.perf_counter() - t0
-    for p in pins:
-        ctx.lib.mod_host_free(ctx.h, p)
+    # the alternating rounds want a window of a good half second
+    fps = stream_rate(s, step, max(20, reps) if splat is None else max(300, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
     ctx.close()
-    return frames / dt
+    return fps
 
 
 def main():

@@ -6,7 +6,6 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -16,6 +15,7 @@ sys.path.insert(0, ROOT)
 
 def stream_fps(W, H, reps, odometry):
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     m = synth.make_ego_images(W, H, seed=1, frames=2)
     ctx = Context(W, H, max_frames=1)
@@ -25,43 +25,17 @@ def stream_fps(W, H, reps, odometry):
     ctx.set_params(synth.Params())
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
     tf = capi.transforms_array(m["t"][:1], m["q"][:1])
-    pins = []
-    for k in ("left0", "right0", "left1", "right1"):
-        p = C.c_void_p()
-        assert ctx.lib.mod_host_malloc(ctx.h, W * H, C.byref(p)) == 0
-        C.memmove(p.value, np.ascontiguousarray(m[k]).ctypes.data, W * H)
-        pins.append(p)
-    objs = [(capi.ModObject * 64)() for _ in range(3)]
-    t, n = C.c_int32(-1), C.c_int32(-1)
-    pending = []
+    pins = [ctx.pinned_copy(m[k]) for k in ("left0", "right0", "left1", "right1")]
+    s = HostStream(ctx, 3, 64, outputs=())
 
     def step(i):
-        l, r = (pins[0], pins[1]) if i % 2 == 0 else (pins[2], pins[3])
-        if len(pending) == 3:
-            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-        if odometry:
-            rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
-                                                  None, None, None, None, C.byref(t))
-        else:
-            rc = ctx.lib.mod_submit_images_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(tf[0]), 1.0 / 15.0, None, None, objs[i % 3], 64,
-                                                None, None, C.byref(t))
+        l, r = pins[2 * (i % 2)], pins[2 * (i % 2) + 1]
+        rc = s.submit_odometry(i % 3, l, r, sp, fp, ep, 1.0 / 15.0) if odometry else s.submit_images(i % 3, l, r, sp, fp, tf[0], 1.0 / 15.0)
         assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
-        if rc == 0:
-            pending.append(t.value)
 
-    for i in range(10):
-        step(i)
-    frames = max(20, reps)
-    t0 = time.perf_counter()
-    for i in range(10, 10 + frames):
-        step(i)
-    while pending:
-        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-    dt = time.perf_counter() - t0
-    for p in pins:
-        ctx.lib.mod_host_free(ctx.h, p)
+    fps = stream_rate(s, step, max(20, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
     ctx.close()
-    return frames / dt
+    return fps
 
 
 def main():

@@ -17,6 +17,7 @@ sys.path.insert(0, ROOT)
 def main():
     import torch
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     ap = argparse.ArgumentParser()
     ap.add_argument("reps", nargs="?", type=int, default=50)
@@ -60,40 +61,17 @@ def main():
             ctx.set_flow_propagation(seeds)
         sp = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
         tf = capi.transforms_array(np.zeros((1, 3)), np.array([[0.0, 0.0, 0.0, 1.0]]))
-        pins = []
-        for k in ("left0", "right0", "left1", "right1"):
-            p = C.c_void_p()
-            assert ctx.lib.mod_host_malloc(ctx.h, W * H, C.byref(p)) == 0
-            C.memmove(p.value, np.ascontiguousarray(m[k]).ctypes.data, W * H)
-            pins.append(p)
-        objs = [(capi.ModObject * 64)() for _ in range(3)]
-        t, n = C.c_int32(-1), C.c_int32(-1)
-        pending = []
+        pins = [ctx.pinned_copy(m[k]) for k in ("left0", "right0", "left1", "right1")]
+        s = HostStream(ctx, 3, 64, outputs=())
 
         def step(i):
-            l, r = (pins[0], pins[1]) if i % 2 == 0 else (pins[2], pins[3])
-            if len(pending) == 3:
-                assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) == 0
-            rc = ctx.lib.mod_submit_images_host(ctx.h, l, r, C.byref(sp), C.byref(prm), C.byref(tf[0]), 1.0 / 15.0, None, None, objs[i % 3], 64,
-                                                None, None, C.byref(t))
+            rc = s.submit_images(i % 3, pins[2 * (i % 2)], pins[2 * (i % 2) + 1], sp, prm, tf[0], 1.0 / 15.0)
             assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
-            if rc == 0:
-                pending.append(t.value)
 
-        for i in range(10):
-            step(i)
-        import time
         frames = max(20, reps)
-        t0 = time.perf_counter()
-        for i in range(10, 10 + frames):
-            step(i)
-        while pending:
-            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) == 0
-        dt = time.perf_counter() - t0
-        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "frames_per_s": round(frames / dt, 1),
-                          "ms_per_frame": round(1e3 * dt / frames, 3)}), flush=True)
-        for p in pins:
-            ctx.lib.mod_host_free(ctx.h, p)
+        fps = stream_rate(s, step, frames)
+        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "frames_per_s": round(fps, 1),
+                          "ms_per_frame": round(1e3 / fps, 3)}), flush=True)
         ctx.close()
 
 

@@ -9,7 +9,6 @@ import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
 
@@ -60,6 +59,7 @@ def kernel(reps, W=1920, H=1080, only=None):
 
 def stream_fps(W, H, reps, encoding, pinned, side_by_side=False):
     from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     m = synth.make_ego_images(W, H, seed=1, frames=2)
     ctx = Context(W, H, max_frames=1)
@@ -68,7 +68,6 @@ def stream_fps(W, H, reps, encoding, pinned, side_by_side=False):
     ctx.set_camera(cam)
     ctx.set_params(synth.Params())
     sp, fp, ep = capi.ModSgmParams(128, 6, 96, 8, 1, 1), capi.flow_params(), capi.ego_params()
-    imgs, pins, keep = [], [], []
     if encoding.startswith("bayer_"):
         msgs = [synth.to_bayer(m[k], encoding, seed=1) for k in ("left0", "right0", "left1", "right1")]
     else:
@@ -78,45 +77,19 @@ def stream_fps(W, H, reps, encoding, pinned, side_by_side=False):
     if side_by_side:                  # one message per frame: two messages in all, and no right pointer
         (a, lay), (b, _) = (synth.side_by_side(msgs[i], msgs[i + 1], lay) for i in (0, 2))
         msgs = [a, b]
-    for msg in msgs:
-        if pinned:
-            p = C.c_void_p()
-            assert ctx.lib.mod_host_malloc(ctx.h, msg.nbytes, C.byref(p)) == 0
-            C.memmove(p.value, msg.ctypes.data, msg.nbytes)
-            pins.append(p)
-            imgs.append(p.value)
-        else:
-            keep.append(msg)
-            imgs.append(msg.ctypes.data)
+    imgs = [ctx.pinned_copy(msg) for msg in msgs] if pinned else msgs
     ctx.set_image_layout(capi.image_layout(lay["encoding"], lay["width"], lay["height"], lay["step"]))
     ctx.set_side_by_side(side_by_side)
-    objs = [(capi.ModObject * 64)() for _ in range(3)]
-    t, n = C.c_int32(-1), C.c_int32(-1)
-    pending = []
+    s = HostStream(ctx, 3, 64, outputs=())
 
     def step(i):
         l, r = (imgs[i % 2], None) if side_by_side else (imgs[2 * (i % 2)], imgs[2 * (i % 2) + 1])
-        if len(pending) == 3:
-            assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-        rc = ctx.lib.mod_submit_odometry_host(ctx.h, l, r, C.byref(sp), C.byref(fp), C.byref(ep), 1.0 / 15.0, None, None, objs[i % 3], 64,
-                                              None, None, None, None, C.byref(t))
+        rc = s.submit_odometry(i % 3, l, r, sp, fp, ep, 1.0 / 15.0)
         assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
-        if rc == 0:
-            pending.append(t.value)
 
-    for i in range(10):
-        step(i)
-    frames = max(20, reps)
-    t0 = time.perf_counter()
-    for i in range(10, 10 + frames):
-        step(i)
-    while pending:
-        assert ctx.lib.mod_collect_frame_host(ctx.h, pending.pop(0), C.byref(n)) in (0, capi.MOD_SKIP_NO_TRANSFORM)
-    dt = time.perf_counter() - t0
-    for p in pins:
-        ctx.lib.mod_host_free(ctx.h, p)
+    fps = stream_rate(s, step, max(20, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
     ctx.close()
-    return frames / dt
+    return fps
 
 
 def main():
