@@ -268,6 +268,46 @@ int  mod_cluster_color(int32_t k, int32_t n_clusters, const uint8_t *palette_bgr
 /* Host only: the built-in table, 256 x 3 bytes B, G, R. */
 int  mod_cluster_palette(uint8_t palette_bgr[768]);
 
+/* Flow and disparity images: the constructor's per-pixel views (~optical_flow, ~synthetic_optical_flow, ~depth;
+ * scene_flow_constructor.cpp:45-48,100,118,145) colour-coded on the device, BGR8, 3 B/px out instead of the 8 or 4 B/px plane.
+ * Calls of their own: nothing is enqueued unless one of them is made, and they keep no state.  All planes are device memory at the
+ * camera's size, packed; every call is ordered on the context's stream and returns once its kernel is enqueued.
+ *   The colour rule.  F32 throughout; every operation is one correctly rounded IEEE operation (add, subtract, multiply, divide,
+ *     sqrtf, compare, truncation of a non-negative value): no atan2, no fused multiply-add.  For a vector (fx, fy) and max_px:
+ *     invalid: fx or fy NaN or +-inf -> (0, 0, 0).
+ *     magnitude: m = sqrtf(fx * fx + fy * fy), the two products and the sum rounded separately; m == 0 -> (255, 255, 255).
+ *     strength: s = min(255, (int)(255 * (m / max_px))): one division, then one multiplication.  The comparison is made in F32
+ *       ahead of the conversion — v = 255 * (m / max_px); s = v < 255 ? (int)v : 255 — so an m that overflowed to +inf gives 255.
+ *     direction: A = |fx| + |fy|, t = fy / A (in [-1, 1]), and the "diamond angle" q in [0, 4]:
+ *       fx >= 0 and fy >= 0: q = t;   fx < 0: q = 2 - t;   fx >= 0 and fy < 0: q = 4 + t   (a -0 component counts as >= 0);
+ *       idx = min(255, (int)(q * 64)), again compared ahead of the conversion; 64 q is exact.
+ *     palette: P = the built-in 256-entry hue wheel of mod_cluster_palette (no second table).
+ *     blend, per channel c, in integers: out_c = 255 - ((255 - P[idx][c]) * s + 127) / 255: white at rest, the full hue at max_px
+ *       and beyond.
+ *   The residual image applies the rule to (flow - static_flow), subtracted per component in F32: the field the dynamic test
+ *     thresholds (scene_flow_constructor.cpp:196-198).  NaN in either operand is black.
+ *   The disparity image: d NaN, +-inf, d < min_disparity, d > max_disparity or d == 0 -> (0, 0, 0) (getDisparity's and getPoint3D's
+ *     rejects); else idx = min(255, (int)(255 * ((d - min_disparity) / (max_disparity - min_disparity)))), compared ahead of the
+ *     conversion, and the pixel is P[idx].  The range is the camera's (ModCamera.min_disparity .. max_disparity).
+ *   Status, tested in this order: NULL ctx, frames outside 1 .. 65535, NULL output (or one not aligned: bgr 4 bytes, static_flow 8),
+ *     max_px not finite or <= 0 -> MOD_ERR_INVALID_ARGUMENT; no camera set -> MOD_ERR_NOT_CONFIGURED (mod_disparity_image_dev: also
+ *     max_disparity <= min_disparity); a NULL input plane -> the skip code of construct()'s guard for it (flow or static_flow:
+ *     MOD_SKIP_NO_FLOW; disparity_prev: MOD_SKIP_NO_DISPARITY_PREV; disparity: MOD_SKIP_NO_DISPARITY_NOW; transforms:
+ *     MOD_SKIP_NO_TRANSFORM); an input plane that is not 4-byte aligned (transforms: 8) -> MOD_ERR_INVALID_ARGUMENT.  Nothing is
+ *     enqueued unless the call returns MOD_OK.  frames is not held to ModConfig.max_frames: the calls use no scratch. */
+/* mod_static_flow_host on device planes: for every frame exactly that call's bytes (NaN where it writes NaN), from
+ * disparity_prev [frames][H][W] and transforms [frames] IN DEVICE MEMORY (e.g. mod_egomotion_dev's) into static_flow [frames][H][W][2]. */
+int  mod_static_flow_dev(ModContext *ctx, int32_t frames, const float *disparity_prev, const ModTransform *transforms, float *static_flow);
+/* flow [frames][H][W][2] -> bgr [frames][H][W][3] */
+int  mod_flow_image_dev(ModContext *ctx, int32_t frames, const float *flow, float max_px, uint8_t *bgr);
+/* (flow - static_flow) -> bgr, one launch */
+int  mod_flow_residual_image_dev(ModContext *ctx, int32_t frames, const float *flow, const float *static_flow, float max_px, uint8_t *bgr);
+/* disparity [frames][H][W] -> bgr [frames][H][W][3] */
+int  mod_disparity_image_dev(ModContext *ctx, int32_t frames, const float *disparity, uint8_t *bgr);
+/* Host only, no context, no GPU: the colour of one vector by the same arithmetic (the legend of a flow image).
+ * MOD_ERR_INVALID_ARGUMENT: bgr NULL, max_px not finite or <= 0. */
+int  mod_flow_color(float fx, float fy, float max_px, uint8_t bgr[3]);
+
 /* pcl::toROSMsg / pcl::fromROSMsg payload conversion (scene_flow_constructor.cpp:358-361, clusterer_nodelet.cpp:226). */
 int  mod_pack_cloud_dev(ModContext *ctx, int32_t frames, const ModSceneFlowPlanes *planes, void *cloud_aos);
 int  mod_unpack_cloud_dev(ModContext *ctx, int32_t frames, const void *cloud_aos, const ModSceneFlowPlanes *planes);

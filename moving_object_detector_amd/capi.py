@@ -83,6 +83,7 @@ EXPORTS = [
     "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
     "mod_set_cluster_members", "mod_get_cluster_members",
     "mod_set_cluster_image", "mod_get_cluster_image", "mod_cluster_image_dev", "mod_cluster_color", "mod_cluster_palette",
+    "mod_static_flow_dev", "mod_flow_image_dev", "mod_flow_residual_image_dev", "mod_disparity_image_dev", "mod_flow_color",
 ]
 
 
@@ -383,6 +384,11 @@ def load(require_torch_first: bool = True):
     L.mod_cluster_image_dev.argtypes = [vp, i32, vp, vp, vp, vp]
     L.mod_cluster_color.argtypes = [i32, i32, vp, vp]
     L.mod_cluster_palette.argtypes = [vp]
+    L.mod_static_flow_dev.argtypes = [vp, i32, vp, vp, vp]
+    L.mod_flow_image_dev.argtypes = [vp, i32, vp, C.c_float, vp]
+    L.mod_flow_residual_image_dev.argtypes = [vp, i32, vp, vp, C.c_float, vp]
+    L.mod_disparity_image_dev.argtypes = [vp, i32, vp, vp]
+    L.mod_flow_color.argtypes = [C.c_float, C.c_float, C.c_float, vp]
     L.mod_pack_cloud_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), vp]
     L.mod_unpack_cloud_dev.argtypes = [vp, i32, vp, C.POINTER(ModSceneFlowPlanes)]
     L.mod_process_frame_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModTransform), C.c_double, vp, vp, vp, i32,
@@ -436,6 +442,15 @@ def cluster_palette():
     if load().mod_cluster_palette(out) != MOD_OK:
         raise RuntimeError("mod_cluster_palette failed")
     return np.frombuffer(bytes(out), dtype=np.uint8).reshape(256, 3).copy()
+
+
+def flow_color(fx: float, fy: float, max_px: float):
+    """(b, g, r) of the flow vector (fx, fy) at full strength max_px (mod_flow_color): the legend of Context.flow_image, by the
+    renderer's own arithmetic.  Needs no GPU.  Raises ValueError unless max_px is finite and > 0."""
+    out = (C.c_uint8 * 3)()
+    if load().mod_flow_color(float(fx), float(fy), float(max_px), out) != MOD_OK:
+        raise ValueError(f"flow_color: max_px must be finite and > 0, got {max_px}")
+    return tuple(out)
 
 
 def camera_struct(cam) -> ModCamera:

@@ -86,6 +86,12 @@ void launch_cluster_members(const DevCam &c, const ClArgs &a, const ClusterMembe
 // labels outside [0, n_clusters[f]) are black.  The table rides in the kernel's arguments
 void launch_cluster_image(int W, int H, int frames, const int32_t *labels, const int32_t *n_clusters, const label_palette::Table &table,
                           uint8_t *image, hipStream_t s);
+// The flow and disparity images (flow_image.hip; flow_color.h has the rule): flow [frames][W H][2] (minus still, same shape, when
+// not null) or disparity [frames][W H] -> image [frames][W H][3] B, G, R (4-byte aligned); the planes 4-byte aligned
+void launch_flow_image(int W, int H, int frames, const float *flow, const float *still, float max_px, uint8_t *image, hipStream_t s);
+void launch_disparity_image(int W, int H, int frames, const float *disparity, float dmin, float dmax, uint8_t *image, hipStream_t s);
+// calculateStaticOpticalFlow alone: dprev [frames][H][W], transforms [frames] in device memory -> static_flow [frames][H][W][2] (8-byte aligned)
+void launch_static_flow(const DevCam &c, int frames, const float *dprev, const ModTransform *transforms, float *static_flow, hipStream_t s);
 int ccl_tile_rows();                 // tile height of k_ccl_tile
 int ccl_tiles(int mask_words, int H); // cluster tiles of a frame of H rows of mask_words words (a tile is one word wide)
 int ccl_request_capacity(int n);     // link requests one tile can emit at neighbor_distance n

@@ -3,6 +3,7 @@
 // the clusterer's ccl_*.hip / cluster_*.hip, the estimators in estimators.hip, image input in host_images.hip, the *_host calls in host_api.hip.
 #include "mod_context.h"
 #include "exact_div.h"
+#include "flow_color.h"
 #include "mod_sf_debug.h"
 
 #include <algorithm>
@@ -10,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <string>
 
 namespace {
 
@@ -565,6 +567,68 @@ int mod_cluster_color(int32_t k, int32_t n_clusters, const uint8_t *palette_bgr,
 int mod_cluster_palette(uint8_t palette_bgr[768]) {
   if (!palette_bgr) return MOD_ERR_INVALID_ARGUMENT;
   label_palette::builtin_bytes(palette_bgr);
+  return MOD_OK;
+}
+
+// ---- the constructor's views on device planes: static flow, flow / residual / disparity images (flow_image.hip) ----
+// What the four calls check in one order: context, frames (blockIdx.z carries them: 1 .. 65535), the output, then the camera
+static int check_view(ModContext *c, int32_t frames, const void *out, size_t out_align, const char *what) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (frames < 1 || frames > 65535) return fail(c, MOD_ERR_INVALID_ARGUMENT, std::string(what) + ": frames must be 1 .. 65535");
+  if (!out) return fail(c, MOD_ERR_INVALID_ARGUMENT, std::string(what) + ": null output");
+  if ((uintptr_t)out & (out_align - 1)) return fail(c, MOD_ERR_INVALID_ARGUMENT, std::string(what) + ": output must be " + std::to_string(out_align) + "-byte aligned");
+  return MOD_OK;
+}
+static int check_view_camera(ModContext *c, const char *what) {
+  return c->has_cam ? MOD_OK : fail(c, MOD_ERR_NOT_CONFIGURED, std::string(what) + ": the camera must be set first");
+}
+static bool usable_max_px(float max_px) { return std::isfinite(max_px) && max_px > 0.0f; }
+
+int mod_static_flow_dev(ModContext *c, int32_t frames, const float *disparity_prev, const ModTransform *transforms, float *static_flow) {
+  int rc = check_view(c, frames, static_flow, 8, "static flow");
+  if (rc || (rc = check_view_camera(c, "static flow"))) return rc;
+  if (!disparity_prev) return MOD_SKIP_NO_DISPARITY_PREV;
+  if (!transforms) return MOD_SKIP_NO_TRANSFORM;
+  if (((uintptr_t)disparity_prev & 3) || ((uintptr_t)transforms & 7))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "static flow: disparity_prev must be 4-byte and transforms 8-byte aligned");
+  launch_static_flow(c->dc, frames, disparity_prev, transforms, static_flow, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+static int flow_image(ModContext *c, int32_t frames, const float *flow, const float *still, bool residual, float max_px, uint8_t *bgr) {
+  int rc = check_view(c, frames, bgr, 4, "flow image");
+  if (rc) return rc;
+  if (!usable_max_px(max_px)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow image: max_px must be finite and > 0");
+  if ((rc = check_view_camera(c, "flow image"))) return rc;
+  if (!flow || (residual && !still)) return MOD_SKIP_NO_FLOW;
+  if (((uintptr_t)flow | (uintptr_t)still) & 3) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow image: the flow planes must be 4-byte aligned");
+  launch_flow_image(c->dc.W, c->dc.H, frames, flow, residual ? still : nullptr, max_px, bgr, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+int mod_flow_image_dev(ModContext *c, int32_t frames, const float *flow, float max_px, uint8_t *bgr) {
+  return flow_image(c, frames, flow, nullptr, false, max_px, bgr);
+}
+int mod_flow_residual_image_dev(ModContext *c, int32_t frames, const float *flow, const float *static_flow, float max_px, uint8_t *bgr) {
+  return flow_image(c, frames, flow, static_flow, true, max_px, bgr);
+}
+
+int mod_disparity_image_dev(ModContext *c, int32_t frames, const float *disparity, uint8_t *bgr) {
+  int rc = check_view(c, frames, bgr, 4, "disparity image");
+  if (rc || (rc = check_view_camera(c, "disparity image"))) return rc;
+  if (!(c->dc.dmax > c->dc.dmin)) return fail(c, MOD_ERR_NOT_CONFIGURED, "disparity image: the camera's max_disparity must exceed its min_disparity");
+  if (!disparity) return MOD_SKIP_NO_DISPARITY_NOW;
+  if ((uintptr_t)disparity & 3) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity image: the plane must be 4-byte aligned");
+  launch_disparity_image(c->dc.W, c->dc.H, frames, disparity, c->dc.dmin, c->dc.dmax, bgr, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_flow_color(float fx, float fy, float max_px, uint8_t bgr[3]) {
+  if (!bgr || !usable_max_px(max_px)) return MOD_ERR_INVALID_ARGUMENT;
+  const uint32_t v = flow_color::flow_bgr(fx, fy, max_px, flow_color::Builtin());
+  bgr[0] = (uint8_t)v; bgr[1] = (uint8_t)(v >> 8); bgr[2] = (uint8_t)(v >> 16);
   return MOD_OK;
 }
 

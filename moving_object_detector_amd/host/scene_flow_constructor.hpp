@@ -321,11 +321,45 @@ class SceneFlowConstructor {
     throw std::runtime_error("collect(): unknown ticket");
   }
 
+  // The constructor's per-pixel views as bgr8 messages, colour-coded on the device (mod_flow_image_dev and its siblings; the rule is
+  // in include/mod_sf.h): one frame from a DEVICE plane at the camera's size — ~optical_flow or ~synthetic_optical_flow (flow alone),
+  // the residual the dynamic test thresholds (flow and static_flow), ~depth's disparity (disparity alone).  3 B/px come back instead of
+  // the 8 or 4 B/px plane.  Fills *image like ClustererNodelet::publishClustersImage: frame_id and stamp of `header`, packed rows.
+  // false: an input was null (nothing rendered, *image untouched), as the reference publishes nothing for a missing input.
+  bool publishFlowImage(const mod_host::Header &header, const float *flow, const float *static_flow, float max_px, mod_host::OwnedImage *image) {
+    return publishView(header, image, [&](uint8_t *bgr) {
+      return static_flow ? mod_flow_residual_image_dev(ctx_, 1, flow, static_flow, max_px, bgr) : mod_flow_image_dev(ctx_, 1, flow, max_px, bgr);
+    });
+  }
+  bool publishDisparityImage(const mod_host::Header &header, const float *disparity, mod_host::OwnedImage *image) {
+    return publishView(header, image, [&](uint8_t *bgr) { return mod_disparity_image_dev(ctx_, 1, disparity, bgr); });
+  }
+
   void setMaxObjects(int n) { max_objects_ = n; }
   int imageWidth() const { return image_width_; }
   int imageHeight() const { return image_height_; }
 
  private:
+  // render(device bgr) into a device buffer of the camera's size, then the pixels and the message around them
+  template <class Render> bool publishView(const mod_host::Header &header, mod_host::OwnedImage *image, Render render) {
+    ModCamera cam{};
+    check(mod_get_camera(ctx_, &cam));
+    const size_t bytes = 3 * (size_t)cam.width * cam.height;
+    struct Dev { ModContext *c; void *p = nullptr; ~Dev() { if (p) (void)mod_free(c, p); } } dev{ctx_};
+    check(mod_malloc(ctx_, bytes, &dev.p));
+    const int rc = render(static_cast<uint8_t *>(dev.p));
+    check(rc);
+    if (rc != MOD_OK) return false;
+    image->pixels.resize(bytes);
+    check(mod_memcpy_d2h(ctx_, image->pixels.data(), dev.p, bytes));
+    mod_host::Image &v = image->view;
+    v.header = mod_host::Header();
+    v.header.frame_id = header.frame_id; v.header.stamp = header.stamp;
+    v.width = cam.width; v.height = cam.height;
+    v.encoding = "bgr8"; v.step = 3 * cam.width;
+    v.data = image->pixels.data();
+    return true;
+  }
 
   struct Pending {
     int ticket = -1;

@@ -202,6 +202,54 @@ class Context:
         self._check(self.lib.mod_cluster_image_dev(self.h, F, labels.data_ptr(), n_clusters.data_ptr(), pal, out.data_ptr()))
         return out
 
+    # ---- the constructor's views on device planes (mod_static_flow_dev, mod_flow_image_dev, ...) -----------------
+    def _plane(self, t: torch.Tensor, per_pixel: int, what: str) -> int:
+        """frames of a float32 device plane of per_pixel floats a pixel"""
+        n = self.height * self.width * per_pixel
+        if t.dtype != torch.float32 or t.numel() == 0 or t.numel() % n:
+            raise ValueError(f"{what} takes float32 planes of F * H * W * {per_pixel} elements")
+        return t.numel() // n
+
+    def static_flow(self, disp_prev: torch.Tensor, transforms: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """calculateStaticOpticalFlow on device planes (mod_static_flow_dev): float32 disp_prev (F, H, W) and float64 device
+        transforms (F, 7) (t[3] then q[4] x, y, z, w: ModTransform) -> (F, H, W, 2) float32, NaN where the reference leaves NaN."""
+        F = self._plane(disp_prev, 1, "static_flow")
+        if transforms.dtype != torch.float64 or transforms.numel() != 7 * F:
+            raise ValueError("static_flow takes float64 transforms of F * 7 elements")
+        disp_prev, transforms = disp_prev.contiguous(), transforms.contiguous()
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 2), dtype=torch.float32, device=disp_prev.device)
+        self._check(self.lib.mod_static_flow_dev(self.h, F, disp_prev.data_ptr(), transforms.data_ptr(), out.data_ptr()))
+        return out
+
+    def flow_image(self, flow: torch.Tensor, max_px: float, static: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The flow image (mod_flow_image_dev): float32 flow (F, H, W, 2) -> (F, H, W, 3) uint8 B, G, R; hue = direction, white at
+        rest, full at max_px (capi.flow_color is its legend), black where a component is NaN or inf.  static (same shape) given: the
+        image of flow - static (mod_flow_residual_image_dev).  Enqueued on the context's stream."""
+        F = self._plane(flow, 2, "flow_image")
+        if static is not None and (self._plane(static, 2, "flow_image") != F):
+            raise ValueError("flow_image: flow and static differ in size")
+        flow = flow.contiguous()
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 3), dtype=torch.uint8, device=flow.device)
+        if static is None:
+            self._check(self.lib.mod_flow_image_dev(self.h, F, flow.data_ptr(), float(max_px), out.data_ptr()))
+        else:
+            static = static.contiguous()
+            self._check(self.lib.mod_flow_residual_image_dev(self.h, F, flow.data_ptr(), static.data_ptr(), float(max_px), out.data_ptr()))
+        return out
+
+    def disparity_image(self, disp: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The disparity image (mod_disparity_image_dev): float32 disp (F, H, W) -> (F, H, W, 3) uint8 B, G, R over the camera's
+        min_disparity .. max_disparity, black where getDisparity / getPoint3D reject the pixel."""
+        F = self._plane(disp, 1, "disparity_image")
+        disp = disp.contiguous()
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 3), dtype=torch.uint8, device=disp.device)
+        self._check(self.lib.mod_disparity_image_dev(self.h, F, disp.data_ptr(), out.data_ptr()))
+        return out
+
     def set_flow_propagation(self, seeds: int = 1) -> None:
         """Neighbour-seed propagation of the on-GPU optical flow (mod_set_flow_propagation): 1 = off (the default), 5 = every finer
         level also tries the winners of the parent's four neighbours.  Takes effect for calls and submits made after it."""

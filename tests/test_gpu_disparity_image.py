@@ -1,0 +1,103 @@
+"""GPU: the disparity image (mod_disparity_image_dev, k_disparity_image) bit for bit against tests/models/flow_image_model.py, on the
+shapes of test_gpu_flow_image.py.  The planes hold NaN, +-inf, -1, +-0, min_disparity and max_disparity, the floats next to either on
+both sides, and the output of mod_sgm_compute_dev on a seeded pair with sub-pixel on (sixteenths, and the estimator's own invalid
+value), under a camera range that cuts through the estimator's."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "models"))
+import flow_image_model as M  # noqa: E402
+
+f32 = np.float32
+SHAPES = [(37, 5), (64, 3), (4, 1)]          # W x H
+F = 2
+DMIN, DMAX = 1.5, 6.25
+GUARD = 64
+
+
+@pytest.fixture(scope="module")
+def contexts():
+    from moving_object_detector_amd import synth
+    from moving_object_detector_amd.pipeline import Context
+    made = {}
+    for W, H in SHAPES:
+        ctx = Context(W, H, max_frames=F)
+        cam = synth.make_camera(W, H)
+        cam.min_disparity, cam.max_disparity = DMIN, DMAX
+        ctx.set_camera(cam); ctx.set_params(synth.Params())
+        made[(W, H)] = ctx
+    yield made
+    for ctx in made.values():
+        ctx.close()
+
+
+def _specials():
+    lo, hi = f32(DMIN), f32(DMAX)
+    up, down = f32(np.inf), f32(-np.inf)
+    return np.array([np.nan, -1.0, 0.0, -0.0, np.inf, -np.inf, lo, hi, np.nextafter(lo, down), np.nextafter(lo, up), np.nextafter(hi, down),
+                     np.nextafter(hi, up), 1e-40, -1e6, 1e6, 3.0, 3.0625, (DMIN + DMAX) / 2], f32)
+
+
+def _render(ctx, disp, misalign=0):
+    n = disp.size
+    store = torch.zeros(n + 4, dtype=torch.float32, device=ctx.device)
+    dev = store[misalign:misalign + n]
+    dev.copy_(torch.from_numpy(disp.reshape(-1)))
+    buf = torch.full((3 * n + 2 * GUARD,), 0xA5, dtype=torch.uint8, device=ctx.device)
+    out = buf[GUARD:GUARD + 3 * n]
+    assert ctx.disparity_image(dev, out=out).data_ptr() == out.data_ptr()
+    ctx.synchronize()
+    host = buf.cpu().numpy()
+    assert (host[:GUARD] == 0xA5).all() and (host[GUARD + 3 * n:] == 0xA5).all(), "bytes outside the image were written"
+    return host[GUARD:GUARD + 3 * n].reshape(disp.shape + (3,))
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+def test_disparity_image_matches_the_model(contexts, shape):
+    W, H = shape
+    rng = np.random.default_rng(W)
+    sp = _specials()
+    disp = (rng.random((F, H * W)) * 8.0).astype(f32)
+    for f in range(F):
+        n = min(len(sp), H * W)
+        disp[f, rng.permutation(H * W)[:n]] = np.roll(sp, -6 * f)[:n]
+    disp = disp.reshape(F, H, W)
+    want = M.disparity_image(disp, DMIN, DMAX)
+    for mis in (0, 1, 3):
+        got = _render(contexts[shape], disp, misalign=mis)
+        assert np.array_equal(got, want), (shape, mis, np.argwhere(got != want)[:4])
+    if shape != (4, 1):
+        lut = M.palette()
+        flat, img = disp.reshape(-1), want.reshape(-1, 3)
+        assert (img[flat == f32(DMIN)] == lut[0]).all() and (img[flat == f32(DMAX)] == lut[255]).all()
+        assert not img[np.isnan(flat) | (flat == 0) | (flat == -1) | (flat > f32(DMAX)) | (flat < f32(DMIN))].any()
+
+
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "%dx%d" % s)
+def test_the_estimators_plane(contexts, shape):
+    """mod_sgm_compute_dev's sub-pixel output, rendered where it lies (no copy in between)."""
+    from moving_object_detector_amd import capi, synth
+    W, H = shape
+    ctx = contexts[shape]
+    pairs = [synth.make_stereo_images(64, 16, seed=7 + f, D=8, n_boxes=2)[:2] for f in range(F)]      # the generator's smallest; cut to size
+    left = torch.from_numpy(np.ascontiguousarray(np.stack([p[0][:H, :W] for p in pairs]))).to(ctx.device)
+    right = torch.from_numpy(np.ascontiguousarray(np.stack([p[1][:H, :W] for p in pairs]))).to(ctx.device)
+    prm = capi.ModSgmParams(8, 6, 96, 8, 1, 1)
+    disp = torch.full((F, H, W), -7.0, dtype=torch.float32, device=ctx.device)
+    ctx.set_disparity_subpixel(True)
+    try:
+        rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, left.data_ptr(), right.data_ptr(), C.byref(prm), disp.data_ptr())
+    finally:
+        ctx.set_disparity_subpixel(False)
+    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
+    got = ctx.disparity_image(disp)
+    ctx.synchronize()
+    d = disp.cpu().numpy()
+    assert np.array_equal(got.cpu().numpy(), M.disparity_image(d, DMIN, DMAX))
+    assert got.shape == (F, H, W, 3) and got.dtype == torch.uint8
