@@ -60,33 +60,6 @@ CHANNELS = {MOD_ENCODING_MONO8: 1, MOD_ENCODING_BGR8: 3, MOD_ENCODING_RGB8: 3, M
 STAGE_NAMES = ("k_scene_flow", "k_ccl_bits+k_ccl_tile_list", "k_ccl_link", "k_ccl_merge", "k_final", "k_median+k_median_ties",
                "cluster group (first launch to last)")
 
-# every symbol include/mod_sf.h declares (tests check that the library exports all of them)
-EXPORTS = [
-    "mod_abi_version", "mod_create", "mod_destroy", "mod_last_error", "mod_set_camera", "mod_set_params",
-    "mod_get_camera", "mod_get_params", "mod_synchronize", "mod_scene_flow_dev", "mod_dynamic_mask_dev",
-    "mod_cluster_dev", "mod_process_dev", "mod_pack_cloud_dev", "mod_unpack_cloud_dev", "mod_process_frame_host",
-    "mod_cluster_cloud_host", "mod_submit_frame_host", "mod_submit_stereo_host", "mod_collect_frame_host", "mod_forget_previous", "mod_host_malloc", "mod_host_free",
-    "mod_malloc", "mod_free", "mod_memcpy_h2d", "mod_memcpy_d2h", "mod_set_profiling",
-    "mod_get_stage_time", "mod_reset_stage_times", "mod_depth_image_dev", "mod_depth_image_host", "mod_static_flow_host",
-    "mod_sgm_census_dev", "mod_sgm_path_dev", "mod_sgm_compute_dev", "mod_sgm_compute_host",
-    "mod_flow_compute_dev", "mod_flow_compute_host", "mod_submit_images_host",
-    "mod_egomotion_dev", "mod_egomotion_host", "mod_submit_odometry_host",
-    "mod_set_image_layout", "mod_get_image_layout", "mod_image_to_mono_dev",
-    "mod_set_disparity_subpixel", "mod_get_disparity_subpixel",
-    "mod_set_disparity_filters", "mod_get_disparity_filters", "mod_disparity_speckle_dev",
-    "mod_set_flow_propagation", "mod_get_flow_propagation",
-    "mod_set_rectification", "mod_get_rectification", "mod_rectify_dev", "mod_rectify_map_host",
-    "mod_set_distortion_model", "mod_get_distortion_model",
-    "mod_set_side_by_side", "mod_get_side_by_side",
-    "mod_set_image_binning", "mod_get_image_binning",
-    "mod_set_depth_layout", "mod_get_depth_layout", "mod_set_depth_registration", "mod_get_depth_registration",
-    "mod_depth_to_disparity_dev", "mod_submit_depth_host", "mod_set_depth_splat", "mod_get_depth_splat",
-    "mod_set_cluster_members", "mod_get_cluster_members",
-    "mod_set_cluster_image", "mod_get_cluster_image", "mod_cluster_image_dev", "mod_cluster_color", "mod_cluster_palette",
-    "mod_static_flow_dev", "mod_flow_image_dev", "mod_flow_residual_image_dev", "mod_disparity_image_dev", "mod_flow_color",
-]
-
-
 class ModConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_width", C.c_int32), ("max_height", C.c_int32), ("max_frames", C.c_int32),
                 ("max_objects", C.c_int32), ("batch_chunks", C.c_int32), ("stream", C.c_void_p)]
@@ -302,11 +275,134 @@ class ModError(RuntimeError):
         self.code = code
 
 
+_vp, _i32 = C.c_void_p, C.c_int32
+# Every symbol include/mod_sf.h declares, in the header's order of introduction, with its argtypes (None: not declared to ctypes).  The
+# restype is c_int except where _RESTYPES says otherwise.  tests/test_abi.py compares the names with the header.
+SIGNATURES = {
+    "mod_abi_version": None,
+    "mod_create": [C.POINTER(ModConfig), C.POINTER(_vp)],
+    "mod_destroy": [_vp],
+    "mod_last_error": [_vp],
+    "mod_set_camera": [_vp, C.POINTER(ModCamera)],
+    "mod_set_params": [_vp, C.POINTER(ModParams)],
+    "mod_get_camera": [_vp, C.POINTER(ModCamera)],
+    "mod_get_params": [_vp, C.POINTER(ModParams)],
+    "mod_synchronize": [_vp],
+    "mod_scene_flow_dev": [_vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes)],
+    "mod_dynamic_mask_dev": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "mod_cluster_dev": [_vp, _i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)],
+    "mod_process_dev": [_vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)],
+    "mod_pack_cloud_dev": [_vp, _i32, C.POINTER(ModSceneFlowPlanes), _vp],
+    "mod_unpack_cloud_dev": [_vp, _i32, _vp, C.POINTER(ModSceneFlowPlanes)],
+    "mod_process_frame_host": [_vp, _vp, _vp, _vp, C.POINTER(ModTransform), C.c_double, _vp, _vp, _vp, _i32, C.POINTER(_i32)],
+    "mod_cluster_cloud_host": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32)],
+    "mod_submit_frame_host": [_vp, _vp, _vp, _vp, C.POINTER(ModTransform), C.c_double, _vp, _vp, _vp, _i32, C.POINTER(_i32)],
+    "mod_submit_stereo_host": [_vp, _vp, _vp, C.POINTER(ModSgmParams), _vp, C.POINTER(ModTransform), C.c_double, _vp, _vp, _vp, _i32, _vp,
+                               C.POINTER(_i32)],
+    "mod_collect_frame_host": [_vp, _i32, C.POINTER(_i32)],
+    "mod_forget_previous": [_vp],
+    "mod_host_malloc": [_vp, C.c_uint64, C.POINTER(_vp)],
+    "mod_host_free": [_vp, _vp],
+    "mod_malloc": [_vp, C.c_uint64, C.POINTER(_vp)],
+    "mod_free": [_vp, _vp],
+    "mod_memcpy_h2d": [_vp, _vp, _vp, C.c_uint64],
+    "mod_memcpy_d2h": [_vp, _vp, _vp, C.c_uint64],
+    "mod_set_profiling": [_vp, _i32],
+    "mod_get_stage_time": [_vp, _i32, C.POINTER(C.c_double), C.POINTER(C.c_int64)],
+    "mod_reset_stage_times": [_vp],
+    "mod_depth_image_dev": [_vp, _i32, _vp, _vp],
+    "mod_depth_image_host": [_vp, _vp, _vp],
+    "mod_static_flow_host": [_vp, _vp, C.POINTER(ModTransform), _vp],
+    "mod_sgm_census_dev": [_vp, _i32, _vp, _vp],
+    "mod_sgm_path_dev": [_vp, _i32, _vp, _vp, C.POINTER(ModSgmParams), _i32, _vp, _vp],
+    "mod_sgm_compute_dev": [_vp, _i32, _vp, _vp, C.POINTER(ModSgmParams), _vp],
+    "mod_sgm_compute_host": [_vp, _vp, _vp, C.POINTER(ModSgmParams), _vp],
+    "mod_flow_compute_dev": [_vp, _i32, _vp, _vp, C.POINTER(ModFlowParams), _vp],
+    "mod_flow_compute_host": [_vp, _vp, _vp, C.POINTER(ModFlowParams), _vp],
+    "mod_submit_images_host": [_vp, _vp, _vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModTransform), C.c_double, _vp,
+                               _vp, _vp, _i32, _vp, _vp, C.POINTER(_i32)],
+    "mod_egomotion_dev": [_vp, _i32, _vp, _vp, _vp, C.POINTER(ModEgoParams), _vp, _vp],
+    "mod_egomotion_host": [_vp, _vp, _vp, _vp, C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.POINTER(ModEgoResult)],
+    "mod_submit_odometry_host": [_vp, _vp, _vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.c_double,
+                                 _vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(_i32)],
+    "mod_set_image_layout": [_vp, C.POINTER(ModImageLayout)],
+    "mod_get_image_layout": [_vp, C.POINTER(ModImageLayout)],
+    "mod_image_to_mono_dev": [_vp, _i32, _vp, C.POINTER(ModImageLayout), _vp],
+    "mod_set_disparity_subpixel": [_vp, _i32],
+    "mod_get_disparity_subpixel": [_vp, C.POINTER(_i32)],
+    "mod_set_disparity_filters": [_vp, C.POINTER(ModDisparityFilters)],
+    "mod_get_disparity_filters": [_vp, C.POINTER(ModDisparityFilters)],
+    "mod_disparity_speckle_dev": [_vp, _i32, _vp, _i32, _i32],
+    "mod_set_flow_propagation": [_vp, _i32],
+    "mod_get_flow_propagation": [_vp, C.POINTER(_i32)],
+    "mod_set_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)],
+    "mod_get_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(_i32)],
+    "mod_rectify_dev": [_vp, _i32, _vp, C.POINTER(ModImageLayout), _i32, _vp],
+    "mod_rectify_map_host": [_vp, _i32, C.POINTER(ModImageLayout), _vp],
+    "mod_set_distortion_model": [_vp, _i32],
+    "mod_get_distortion_model": [_vp, C.POINTER(_i32)],
+    "mod_set_side_by_side": [_vp, _i32],
+    "mod_get_side_by_side": [_vp, C.POINTER(_i32)],
+    "mod_set_image_binning": [_vp, C.POINTER(ModImageBinning)],
+    "mod_get_image_binning": [_vp, C.POINTER(ModImageBinning)],
+    "mod_set_depth_layout": [_vp, C.POINTER(ModDepthLayout)],
+    "mod_get_depth_layout": [_vp, C.POINTER(ModDepthLayout)],
+    "mod_set_depth_registration": [_vp, C.POINTER(ModDepthRegistration)],
+    "mod_get_depth_registration": [_vp, C.POINTER(ModDepthRegistration), C.POINTER(_i32)],
+    "mod_depth_to_disparity_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), _vp],
+    "mod_submit_depth_host": [_vp, _vp, _vp, C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.c_double, _vp,
+                              _vp, _vp, _i32, _vp, _vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(_i32)],
+    "mod_set_depth_splat": [_vp, _i32],
+    "mod_get_depth_splat": [_vp, C.POINTER(_i32)],
+    "mod_set_cluster_members": [_vp, C.POINTER(ModClusterMembers)],
+    "mod_get_cluster_members": [_vp, C.POINTER(ModClusterMembers), C.POINTER(_i32)],
+    "mod_set_cluster_image": [_vp, C.POINTER(ModClusterImage)],
+    "mod_get_cluster_image": [_vp, C.POINTER(ModClusterImage), C.POINTER(_i32)],
+    "mod_cluster_image_dev": [_vp, _i32, _vp, _vp, _vp, _vp],
+    "mod_cluster_color": [_i32, _i32, _vp, _vp],
+    "mod_cluster_palette": [_vp],
+    "mod_static_flow_dev": [_vp, _i32, _vp, _vp, _vp],
+    "mod_flow_image_dev": [_vp, _i32, _vp, C.c_float, _vp],
+    "mod_flow_residual_image_dev": [_vp, _i32, _vp, _vp, C.c_float, _vp],
+    "mod_disparity_image_dev": [_vp, _i32, _vp, _vp],
+    "mod_flow_color": [C.c_float, C.c_float, C.c_float, _vp],
+}
+_RESTYPES = {"mod_destroy": None, "mod_last_error": C.c_char_p}
+EXPORTS = list(SIGNATURES)
+# csrc/mod_sf_debug.h: only a build with the debug hooks compiled in exports these (the product does not)
+DEBUG_SIGNATURES = {
+    "mod_debug_read": [_vp, C.c_int, _vp, C.c_ulonglong],
+    "mod_debug_counters": [_vp, C.POINTER(C.c_uint64)],
+}
+
+
+def declare(L, missing_ok: bool = False):
+    """Give the functions of the loaded library `L` the argtypes and restypes of SIGNATURES, and those of DEBUG_SIGNATURES where `L`
+    exports them.  A name of SIGNATURES that `L` lacks raises AttributeError naming it, or is left out with missing_ok (an older build)."""
+    for table, optional in ((SIGNATURES, missing_ok), (DEBUG_SIGNATURES, True)):
+        for name, argtypes in table.items():
+            fn = getattr(L, name, None)
+            if fn is None:
+                if optional:
+                    continue
+                raise AttributeError(f"{getattr(L, '_name', L)} does not export {name}")
+            if argtypes is not None:
+                fn.argtypes = argtypes
+            fn.restype = _RESTYPES.get(name, C.c_int)
+    return L
+
+
+def bind(path: str, missing_ok: bool = False) -> C.CDLL:
+    """Load the build of the library at `path` and declare its functions (declare()).  Import torch first when device pointers of
+    torch's are to be handed to it (see the module docstring); load() does."""
+    return declare(C.CDLL(path), missing_ok)
+
+
 _lib = None
 
 
 def load(require_torch_first: bool = True):
-    """Load libmod_sf.so.  Raises (never falls back) when it is missing."""
+    """Load libmod_sf.so (once: the bound library is cached).  Raises (never falls back) when it is missing."""
     global _lib
     if _lib is not None:
         return _lib
@@ -316,103 +412,8 @@ def load(require_torch_first: bool = True):
                           f"There is no CPU fallback.")
     if require_torch_first:
         import torch  # noqa: F401  (see module docstring: one HIP runtime per process)
-    L = C.CDLL(LIB_PATH)
-    vp, i32, i64p, dp = C.c_void_p, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_double)
-    L.mod_abi_version.restype = C.c_int
-    L.mod_create.argtypes = [C.POINTER(ModConfig), C.POINTER(vp)]
-    L.mod_destroy.argtypes = [vp]
-    L.mod_destroy.restype = None
-    L.mod_last_error.argtypes = [vp]
-    L.mod_last_error.restype = C.c_char_p
-    L.mod_set_camera.argtypes = [vp, C.POINTER(ModCamera)]
-    L.mod_set_params.argtypes = [vp, C.POINTER(ModParams)]
-    L.mod_get_camera.argtypes = [vp, C.POINTER(ModCamera)]
-    L.mod_get_params.argtypes = [vp, C.POINTER(ModParams)]
-    L.mod_synchronize.argtypes = [vp]
-    L.mod_scene_flow_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes)]
-    L.mod_depth_image_dev.argtypes = [vp, i32, vp, vp]
-    L.mod_depth_image_host.argtypes = [vp, vp, vp]
-    L.mod_static_flow_host.argtypes = [vp, vp, C.POINTER(ModTransform), vp]
-    L.mod_sgm_census_dev.argtypes = [vp, i32, vp, vp]
-    L.mod_sgm_compute_dev.argtypes = [vp, i32, vp, vp, C.POINTER(ModSgmParams), vp]
-    L.mod_sgm_compute_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), vp]
-    L.mod_sgm_path_dev.argtypes = [vp, i32, vp, vp, C.POINTER(ModSgmParams), i32, vp, vp]
-    L.mod_flow_compute_dev.argtypes = [vp, i32, vp, vp, C.POINTER(ModFlowParams), vp]
-    L.mod_flow_compute_host.argtypes = [vp, vp, vp, C.POINTER(ModFlowParams), vp]
-    L.mod_submit_images_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModTransform), C.c_double,
-                                         vp, vp, vp, i32, vp, vp, C.POINTER(i32)]
-    L.mod_egomotion_dev.argtypes = [vp, i32, vp, vp, vp, C.POINTER(ModEgoParams), vp, vp]
-    L.mod_egomotion_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.POINTER(ModEgoResult)]
-    L.mod_submit_odometry_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.c_double,
-                                           vp, vp, vp, i32, vp, vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(i32)]
-    L.mod_set_image_layout.argtypes = [vp, C.POINTER(ModImageLayout)]
-    L.mod_get_image_layout.argtypes = [vp, C.POINTER(ModImageLayout)]
-    L.mod_image_to_mono_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), vp]
-    L.mod_set_disparity_subpixel.argtypes = [vp, i32]
-    L.mod_get_disparity_subpixel.argtypes = [vp, C.POINTER(i32)]
-    L.mod_set_disparity_filters.argtypes = [vp, C.POINTER(ModDisparityFilters)]
-    L.mod_get_disparity_filters.argtypes = [vp, C.POINTER(ModDisparityFilters)]
-    L.mod_disparity_speckle_dev.argtypes = [vp, i32, vp, i32, i32]
-    L.mod_set_flow_propagation.argtypes = [vp, i32]
-    L.mod_get_flow_propagation.argtypes = [vp, C.POINTER(i32)]
-    L.mod_set_rectification.argtypes = [vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)]
-    L.mod_get_rectification.argtypes = [vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(i32)]
-    L.mod_rectify_dev.argtypes = [vp, i32, vp, C.POINTER(ModImageLayout), i32, vp]
-    L.mod_rectify_map_host.argtypes = [vp, i32, C.POINTER(ModImageLayout), vp]
-    L.mod_set_distortion_model.argtypes = [vp, i32]
-    L.mod_get_distortion_model.argtypes = [vp, C.POINTER(i32)]
-    L.mod_set_side_by_side.argtypes = [vp, i32]
-    L.mod_get_side_by_side.argtypes = [vp, C.POINTER(i32)]
-    L.mod_set_image_binning.argtypes = [vp, C.POINTER(ModImageBinning)]
-    L.mod_get_image_binning.argtypes = [vp, C.POINTER(ModImageBinning)]
-    L.mod_set_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]
-    L.mod_get_depth_layout.argtypes = [vp, C.POINTER(ModDepthLayout)]
-    L.mod_set_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration)]
-    L.mod_get_depth_registration.argtypes = [vp, C.POINTER(ModDepthRegistration), C.POINTER(i32)]
-    L.mod_depth_to_disparity_dev.argtypes = [vp, i32, vp, C.POINTER(ModDepthLayout), vp]
-    L.mod_set_depth_splat.argtypes = [vp, i32]
-    L.mod_get_depth_splat.argtypes = [vp, C.POINTER(i32)]
-    L.mod_submit_depth_host.argtypes = [vp, vp, vp, C.POINTER(ModFlowParams), C.POINTER(ModEgoParams), C.POINTER(ModTransform), C.c_double,
-                                        vp, vp, vp, i32, vp, vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(i32)]
-    L.mod_dynamic_mask_dev.argtypes = [vp, i32, vp, vp, vp, vp]
-    L.mod_cluster_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
-    L.mod_process_dev.argtypes = [vp, C.POINTER(ModFrameBatch), C.POINTER(ModSceneFlowPlanes), C.POINTER(ModClusterOut)]
-    L.mod_set_cluster_members.argtypes = [vp, C.POINTER(ModClusterMembers)]
-    L.mod_get_cluster_members.argtypes = [vp, C.POINTER(ModClusterMembers), C.POINTER(i32)]
-    L.mod_set_cluster_image.argtypes = [vp, C.POINTER(ModClusterImage)]
-    L.mod_get_cluster_image.argtypes = [vp, C.POINTER(ModClusterImage), C.POINTER(i32)]
-    L.mod_cluster_image_dev.argtypes = [vp, i32, vp, vp, vp, vp]
-    L.mod_cluster_color.argtypes = [i32, i32, vp, vp]
-    L.mod_cluster_palette.argtypes = [vp]
-    L.mod_static_flow_dev.argtypes = [vp, i32, vp, vp, vp]
-    L.mod_flow_image_dev.argtypes = [vp, i32, vp, C.c_float, vp]
-    L.mod_flow_residual_image_dev.argtypes = [vp, i32, vp, vp, C.c_float, vp]
-    L.mod_disparity_image_dev.argtypes = [vp, i32, vp, vp]
-    L.mod_flow_color.argtypes = [C.c_float, C.c_float, C.c_float, vp]
-    L.mod_pack_cloud_dev.argtypes = [vp, i32, C.POINTER(ModSceneFlowPlanes), vp]
-    L.mod_unpack_cloud_dev.argtypes = [vp, i32, vp, C.POINTER(ModSceneFlowPlanes)]
-    L.mod_process_frame_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModTransform), C.c_double, vp, vp, vp, i32,
-                                         C.POINTER(i32)]
-    L.mod_cluster_cloud_host.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, C.POINTER(i32)]
-    L.mod_submit_frame_host.argtypes = [vp, vp, vp, vp, C.POINTER(ModTransform), C.c_double, vp, vp, vp, i32, C.POINTER(i32)]
-    L.mod_submit_stereo_host.argtypes = [vp, vp, vp, C.POINTER(ModSgmParams), vp, C.POINTER(ModTransform), C.c_double, vp, vp, vp, i32, vp,
-                                         C.POINTER(i32)]
-    L.mod_collect_frame_host.argtypes = [vp, i32, C.POINTER(i32)]
-    L.mod_forget_previous.argtypes = [vp]
-    L.mod_host_malloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-    L.mod_host_free.argtypes = [vp, vp]
-    L.mod_malloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
-    L.mod_free.argtypes = [vp, vp]
-    L.mod_memcpy_h2d.argtypes = [vp, vp, vp, C.c_uint64]
-    L.mod_memcpy_d2h.argtypes = [vp, vp, vp, C.c_uint64]
-    L.mod_set_profiling.argtypes = [vp, i32]
-    L.mod_get_stage_time.argtypes = [vp, i32, dp, i64p]
-    L.mod_reset_stage_times.argtypes = [vp]
-    for name in EXPORTS:
-        if name not in ("mod_destroy", "mod_last_error"):
-            getattr(L, name).restype = C.c_int
-    _lib = L
-    return L
+    _lib = bind(LIB_PATH)
+    return _lib
 
 
 def palette_bytes(palette):

@@ -1,6 +1,6 @@
 """One Python driver of the host frame stream (include/mod_sf.h: mod_submit_*_host, mod_collect_frame_host, mod_forget_previous) for
-tests and tools.  It adds nothing to the library: no threads, no torch, and the raw ``ctx.lib.mod_*`` route stays open to whoever wants
-to misuse the ABI on purpose."""
+tests and tools (host_calls.HostCalls has the synchronous calls).  It adds nothing to the library: no threads, no torch, and the raw
+``ctx.lib.mod_*`` route stays open to whoever wants to misuse the ABI on purpose."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,17 +9,9 @@ import time
 import numpy as np
 
 from . import capi
+from .host_calls import _ptr, _ref, _transform, objects_bytes
 
 _SHAPES = {"cloud": ((8,), np.float32), "labels": ((), np.int32), "disparity": ((), np.float32), "flow": ((2,), np.float32)}
-
-
-def _ptr(a):
-    """address of a numpy array or of a pinned buffer (Context.pinned_copy), None = NULL"""
-    return None if a is None else a.ptr if hasattr(a, "ptr") else a.ctypes.data
-
-
-def _ref(s):
-    return C.byref(s) if s is not None else None
 
 
 class HostStream:
@@ -77,24 +69,20 @@ class HostStream:
             raise capi.ModError(rc, self.ctx.lib.mod_last_error(self.ctx.h).decode())
         return rc
 
-    @staticmethod
-    def _transform(tf):
-        return tf if tf is None or isinstance(tf, capi.ModTransform) else capi.transforms_array([tf[0]], [tf[1]])[0]
-
     def submit_frame(self, f, disparity_now, disparity_prev, flow, transform, dt):
         tail, _, _, _ = self._out[f]
         return self._submit(f, self.ctx.lib.mod_submit_frame_host, _ptr(disparity_now), _ptr(disparity_prev), _ptr(flow),
-                            _ref(self._transform(transform)), dt, *tail)
+                            _ref(_transform(transform)), dt, *tail)
 
     def submit_stereo(self, f, left, right, sgm, flow, transform, dt):
         tail, disp, _, _ = self._out[f]
         return self._submit(f, self.ctx.lib.mod_submit_stereo_host, _ptr(left), _ptr(right), _ref(sgm), _ptr(flow),
-                            _ref(self._transform(transform)), dt, *tail, disp)
+                            _ref(_transform(transform)), dt, *tail, disp)
 
     def submit_images(self, f, left, right, sgm, flow_prm, transform, dt):
         tail, disp, flow, _ = self._out[f]
         return self._submit(f, self.ctx.lib.mod_submit_images_host, _ptr(left), _ptr(right), _ref(sgm), _ref(flow_prm),
-                            _ref(self._transform(transform)), dt, *tail, disp, flow)
+                            _ref(_transform(transform)), dt, *tail, disp, flow)
 
     def submit_odometry(self, f, left, right, sgm, flow_prm, ego_prm, dt):
         tail, disp, flow, est = self._out[f]
@@ -104,7 +92,7 @@ class HostStream:
     def submit_depth(self, f, image, depth, flow_prm, ego_prm, transform, dt):
         tail, disp, flow, est = self._out[f]
         return self._submit(f, self.ctx.lib.mod_submit_depth_host, _ptr(image), _ptr(depth), _ref(flow_prm), _ref(ego_prm),
-                            _ref(self._transform(transform)), dt, *tail, disp, flow, *est)
+                            _ref(_transform(transform)), dt, *tail, disp, flow, *est)
 
     def collect(self):
         """Collect the oldest ticket."""
@@ -130,7 +118,7 @@ class HostStream:
     # ---- results (of collected frames) ------------------------------------------------------------------------
     def objects_bytes(self, f):
         """the records the library reported for frame f: the one slicing rule"""
-        return bytes(self.objects[f])[:capi.MOD_OBJECT_BYTES * min(self.n[f], self.capacity)] if self.capacity else b""
+        return objects_bytes(self.objects[f], self.n[f], self.capacity)
 
     def transform_bytes(self, f):
         return bytes(self.transforms[f])

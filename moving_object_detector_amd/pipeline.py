@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import capi
+from .host_calls import HostCalls
 
 PLANES = ("x", "y", "z", "vx", "vy", "vz")
 
@@ -51,8 +52,9 @@ class PinnedBuffer:
             self.ptr = None
 
 
-class Context:
-    """One context per GPU / stream (single caller), like one SceneFlowConstructor + one ClustererNodelet."""
+class Context(HostCalls):
+    """One context per GPU / stream (single caller), like one SceneFlowConstructor + one ClustererNodelet.  The synchronous host
+    calls (disparity_host, process_frame_host, ...) are host_calls.HostCalls'."""
 
     def __init__(self, width: int, height: int, max_frames: int = 1, device: int = 0, max_objects: int = 0,
                  use_torch_stream: bool = True, batch_chunks: int = 0):
@@ -77,11 +79,6 @@ class Context:
         self._pinned = []
 
     # ---- configuration ----------------------------------------------------------------------------------------
-    def _check(self, rc: int) -> int:
-        if rc < 0:
-            raise capi.ModError(rc, self.lib.mod_last_error(self.h).decode())
-        return rc
-
     def _done(self, rc: int, name: str) -> None:
         """_check for a call that has no skip to report: any code but 0 raises."""
         if self._check(rc) != 0:
@@ -496,6 +493,24 @@ class Context:
         prm = params if params is not None else capi.flow_params()
         self._done(self.lib.mod_flow_compute_dev(self.h, F, p4.data_ptr(), n4.data_ptr(), C.byref(prm), out.data_ptr()), "mod_flow_compute_dev")
         return out[0] if single and out.dim() == 4 else out
+
+    def estimate_disparity(self, left: torch.Tensor, right: torch.Tensor, params: capi.ModSgmParams,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """On-GPU semi-global matching (mod_sgm_compute_dev): device uint8 tensors (F,H,W) or (H,W) of the camera size -> (F,H,W) /
+        (H,W) float32 disparity of the left image, min_disparity - 1 where rejected.  Enqueued on the context's stream."""
+        single = left.dim() == 2
+        l3, r3 = (left[None], right[None]) if single else (left, right)
+        if l3.shape != r3.shape or l3.dtype != torch.uint8 or r3.dtype != torch.uint8 or l3.shape[1:] != (self.height, self.width):
+            raise ValueError("left / right must be uint8 tensors of the same shape (F, H, W) at the camera size")
+        if not (l3.is_contiguous() and r3.is_contiguous()):
+            raise ValueError("left / right must be contiguous")
+        F = l3.shape[0]
+        if out is None:
+            out = torch.empty((F, self.height, self.width), dtype=torch.float32, device=left.device)
+        elif out.shape not in (l3.shape, l3.shape[1:])[:1 + (F == 1)] or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor (F, H, W) (one frame: or (H, W))")
+        self._done(self.lib.mod_sgm_compute_dev(self.h, F, l3.data_ptr(), r3.data_ptr(), C.byref(params), out.data_ptr()), "mod_sgm_compute_dev")
+        return out[0] if single and out.dim() == 3 else out
 
     def image_to_mono(self, src: torch.Tensor, layout: Optional[capi.ModImageLayout] = None,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -3,7 +3,6 @@ job_queue) through the clusterer of the library named by MOD_SF_LIB — the CHEC
 before using it (csrc/mod_device.h MOD_CHECK; 12 = a link-request slot past the tile's share of the buffer, 13 = a root or halo
 pixel outside the frame) — compares labels, cluster count and objects with the oracle, and prints the violation counters and the names
 of the cases that differ as JSON.  Started by tests/test_gpu_ccl_tile_wide.py, once, before the product build sees these cases."""
-import ctypes as C
 import json
 import os
 import sys
@@ -39,10 +38,7 @@ def main():
         for _ in range(2):                                   # twice: the second pass runs over scratch the first one left behind
             assert ctx.cluster(1, ws, mask_ready=False) == 0
             ctx.synchronize()
-        out = (C.c_uint64 * 96)()
-        ctx.lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        assert ctx.lib.mod_debug_counters(ctx.h, out) == 0
-        counters[:] += np.frombuffer(out, np.uint64)
+        counters[:] += ctx.debug_counters()
         rl, ro, rK = pyoracle.cluster(planes, prm, "tidy", max_objects=W * H // 2 + 16)
         try:
             assert int(ws["n_clusters"][0]) == rK

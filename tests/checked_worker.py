@@ -1,7 +1,6 @@
 """Helper PROGRAM (not a test): runs the hot path of the library named by MOD_SF_LIB — the CHECKED build, whose kernels verify
 every data-derived index before using it (csrc/mod_device.h MOD_CHECK) — over the shapes that matter for those indices, compares
 the results with the oracle, and prints the violation counters as JSON.  Started by tests/test_gpu_checked_build.py."""
-import ctypes as C
 import json
 import os
 import sys
@@ -35,10 +34,7 @@ def main():
         for _ in range(2):                                   # twice: the second pass runs over scratch the first one left behind
             assert ctx.process(b, ws) == 0
             ctx.synchronize()
-        out = (C.c_uint64 * 96)()
-        ctx.lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        assert ctx.lib.mod_debug_counters(ctx.h, out) == 0
-        counters[:] += np.frombuffer(out, np.uint64)
+        counters[:] += ctx.debug_counters()
         planes, labels, objs = ws["planes"].cpu().numpy(), ws["labels"].cpu().numpy(), ctx.objects_to_host(ws)
         for f in check_frames:
             ref = pyoracle.construct(cam, prm, batch["disparity_now"][f], batch["disparity_prev"][f], batch["flow"][f], batch["t"][f],
@@ -98,10 +94,7 @@ def main():
         for _ in range(2):
             assert ctx.cluster(1, ws, mask_ready=False) == 0
             ctx.synchronize()
-        out = (C.c_uint64 * 96)()
-        ctx.lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        assert ctx.lib.mod_debug_counters(ctx.h, out) == 0
-        counters[:] += np.frombuffer(out, np.uint64)
+        counters[:] += ctx.debug_counters()
         lab, ro, K = pyoracle.cluster(cloud, prm, "tidy", max_objects=64)
         assert K == 1 and ro[0]["ambiguous"]
         compare_objects(ctx.objects_to_host(ws)[0], ro, strict_velocity=True)

@@ -204,13 +204,13 @@ def test_sgm_compute_host_rectified(ctx, sbs):
                 msgs.append(m)
             planes = [bm.demosaic_messages(m, bm.Layout(*lay), 1)[0] for m in msgs]
         ctx.set_image_layout(capi.image_layout("mono8", MW, MH, MW, X0, Y0))
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, planes[0].ctypes.data, planes[1].ctypes.data, C.byref(sp), want.ctypes.data) == 0
+        assert ctx.disparity_host(planes[0], planes[1], sp, want)[0] == 0
         ctx.set_image_layout(capi.image_layout(*lay))
         if sbs:
             ctx.set_side_by_side(True)
-            assert ctx.lib.mod_sgm_compute_host(ctx.h, both.ctypes.data, None, C.byref(sp), got.ctypes.data) == 0
+            assert ctx.disparity_host(both, None, sp, got)[0] == 0
         else:
-            assert ctx.lib.mod_sgm_compute_host(ctx.h, msgs[0].ctypes.data, msgs[1].ctypes.data, C.byref(sp), got.ctypes.data) == 0
+            assert ctx.disparity_host(msgs[0], msgs[1], sp, got)[0] == 0
     finally:
         ctx.set_side_by_side(False)
         ctx.set_image_layout(None)

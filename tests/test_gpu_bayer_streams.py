@@ -4,7 +4,6 @@ k_bayer_to_mono runs on the staged region) give, bit for bit, what the same call
 64 x 40 camera inside 80 x 52 messages at an odd origin and on a camera that is the whole message; a layout change between submits
 while frames are in flight; side by side with an even and an odd pane width; the panes do not leak into each other; the C++ host
 mirror (tests/cpp/bayer_mirror_test.cpp)."""
-import ctypes as C
 import os
 import subprocess
 import sys
@@ -133,12 +132,12 @@ def test_a_single_frame_host_calls(ctx, name, pattern):
     got_f, want_f = (np.full((H, W, 2), -7, np.float32) for _ in range(2))
     try:
         _state(ctx, None)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, g1[0].ctypes.data, g1[1].ctypes.data, C.byref(sp), want_d.ctypes.data) == 0
-        assert ctx.lib.mod_flow_compute_host(ctx.h, g0[0].ctypes.data, g1[0].ctypes.data, C.byref(fp), want_f.ctypes.data) == 0
+        assert ctx.disparity_host(g1[0], g1[1], sp, want_d)[0] == 0
+        assert ctx.flow_host(g0[0], g1[0], fp, want_f)[0] == 0
         assert (want_d >= 0).any()
         _state(ctx, lay)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, m1[0].ctypes.data, m1[1].ctypes.data, C.byref(sp), got_d.ctypes.data) == 0
-        assert ctx.lib.mod_flow_compute_host(ctx.h, m0[0].ctypes.data, m1[0].ctypes.data, C.byref(fp), got_f.ctypes.data) == 0
+        assert ctx.disparity_host(m1[0], m1[1], sp, got_d)[0] == 0
+        assert ctx.flow_host(m0[0], m1[0], fp, got_f)[0] == 0
     finally:
         _state(ctx, None)
     assert got_d.tobytes() == want_d.tobytes() and got_f.tobytes() == want_f.tobytes()
@@ -211,9 +210,9 @@ def test_d_side_by_side(ctx, width, pattern):
     both, g = fr[1]
     try:
         _state(ctx, None)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, g[0].ctypes.data, g[1].ctypes.data, C.byref(sp), want_d.ctypes.data) == 0
+        assert ctx.disparity_host(g[0], g[1], sp, want_d)[0] == 0
         _state(ctx, blay, True)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, both.ctypes.data, None, C.byref(sp), got_d.ctypes.data) == 0
+        assert ctx.disparity_host(both, None, sp, got_d)[0] == 0
     finally:
         _state(ctx, None)
     assert got_d.tobytes() == want_d.tobytes() and (want_d >= 0).any()
@@ -295,7 +294,7 @@ def test_g_the_smallest_estimator_camera(pattern):
         """[(left, right)] * 2 -> the synchronous disparity of pair 1 and the streamed disparity of pair 1"""
         _state(c, lay)
         sync = np.full((h, w), -7, np.float32)
-        assert c.lib.mod_sgm_compute_host(c.h, imgs[1][0].ctypes.data, imgs[1][1].ctypes.data, C.byref(sp), sync.ctypes.data) == 0
+        assert c.disparity_host(imgs[1][0], imgs[1][1], sp, sync)[0] == 0
         s = HostStream(c, 2, 0, outputs=("disparity",))
         s.forget_previous()
         for k, (l, r) in enumerate(imgs):

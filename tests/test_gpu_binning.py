@@ -210,7 +210,9 @@ def test_capacity(ctx):
         img = np.zeros((40, 68), np.uint8)
         disp = np.zeros((10, 68), np.float32)
         sp = capi.ModSgmParams(16, 6, 96, 8, 1, 1)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, img.ctypes.data, img.ctypes.data, C.byref(sp), disp.ctypes.data) == capi.MOD_ERR_CAPACITY
+        with pytest.raises(capi.ModError) as e:
+            ctx.disparity_host(img, img, sp, disp)
+        assert e.value.code == capi.MOD_ERR_CAPACITY
     finally:
         ctx.set_image_binning()
 
@@ -243,7 +245,7 @@ def test_off_is_a_context_that_never_set_it():
             grey = c.image_to_mono(torch.from_numpy(msg).to(c.device), capi.image_layout(*lay))
             c.synchronize()
             disp = np.full((H, W), -7, np.float32)
-            assert c.lib.mod_sgm_compute_host(c.h, left.ctypes.data, right.ctypes.data, C.byref(sp), disp.ctypes.data) == 0
+            assert c.disparity_host(left, right, sp, disp)[0] == 0
             results.append((grey.cpu().numpy().tobytes(), disp.tobytes()))
         finally:
             c.close()

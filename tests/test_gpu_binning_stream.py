@@ -3,7 +3,6 @@ GPU) give, byte for byte, what the same context gives when fed the model's binne
 binning off: a 64 x 32 camera from 128 x 64 messages, SGM with 32 disparities, flow with two levels; mod_submit_stereo_host and
 mod_submit_odometry_host on mono8 messages, the odometry stream on bgr8 messages, the synchronous host calls, and a ticket whose
 binning is switched off before it is collected."""
-import ctypes as C
 import os
 import sys
 
@@ -173,11 +172,11 @@ def test_synchronous_host_calls(ctx, frames):
             got_f, want_f = (np.full((H, W, 2), -7, np.float32) for _ in range(2))
             try:
                 _off(ctx)
-                assert ctx.lib.mod_sgm_compute_host(ctx.h, b1[0].ctypes.data, b1[1].ctypes.data, C.byref(sp), want_d.ctypes.data) == 0
-                assert ctx.lib.mod_flow_compute_host(ctx.h, b0[0].ctypes.data, b1[0].ctypes.data, C.byref(fp), want_f.ctypes.data) == 0
+                assert ctx.disparity_host(b1[0], b1[1], sp, want_d)[0] == 0
+                assert ctx.flow_host(b0[0], b1[0], fp, want_f)[0] == 0
                 _on(enc, mode)(ctx)
-                assert ctx.lib.mod_sgm_compute_host(ctx.h, m1[0].ctypes.data, m1[1].ctypes.data, C.byref(sp), got_d.ctypes.data) == 0
-                assert ctx.lib.mod_flow_compute_host(ctx.h, m0[0].ctypes.data, m1[0].ctypes.data, C.byref(fp), got_f.ctypes.data) == 0
+                assert ctx.disparity_host(m1[0], m1[1], sp, got_d)[0] == 0
+                assert ctx.flow_host(m0[0], m1[0], fp, got_f)[0] == 0
             finally:
                 _off(ctx)
             assert got_d.tobytes() == want_d.tobytes() and got_f.tobytes() == want_f.tobytes(), (enc, mode)

@@ -202,10 +202,8 @@ def test_host_calls_with_and_without_labels(sequence):
     for want_labels in (True, False):
         host = np.full((H, W, 3), FILL, np.uint8)
         ctx.set_cluster_image(None, host_image=host)
-        objs, n = (capi.ModObject * CAP)(), C.c_int32(-1)
-        rc = ctx.lib.mod_process_frame_host(ctx.h, *args, None, labels.ctypes.data if want_labels else None, objs if want_labels else None, CAP,
-                                            C.byref(n) if want_labels else None)
-        assert rc == 0, ctx.lib.mod_last_error(ctx.h)
+        assert ctx.process_frame_host(*keep[:3], keep[3][0], args[4], labels=labels if want_labels else None, capacity=CAP * want_labels,
+                                      count=want_labels)[0] == 0
         images.append(host.copy())
     K = int(labels.max()) + 1
     assert K >= 1
@@ -220,9 +218,7 @@ def test_host_calls_with_and_without_labels(sequence):
     for want_labels in (True, False):
         host = np.full((H, W, 3), FILL, np.uint8)
         ctx.set_cluster_image(None, host_image=host)
-        objs, n = (capi.ModObject * CAP)(), C.c_int32(-1)
-        rc = ctx.lib.mod_cluster_cloud_host(ctx.h, rec.ctypes.data, W, H, 32, 32 * W, labels.ctypes.data if want_labels else None, objs, CAP, C.byref(n))
-        assert rc == 0, ctx.lib.mod_last_error(ctx.h)
+        assert ctx.cluster_cloud_host(rec, labels if want_labels else None, CAP)[0] == 0
         images.append(host.copy())
     assert int(labels.max()) + 1 == 384
     assert np.array_equal(images[0], M.render(labels[None], [384])[0]) and np.array_equal(images[1], images[0])

@@ -350,8 +350,7 @@ def test_submits_never_write_the_lists(fused_case):
     assert got[0] == got[1] and got[0][0] == len(refs[0][2])
     # the synchronous host call with the setting on fills frame 0
     _prefill(ws)
-    objs, n = (capi.ModObject * CAP)(), C.c_int32(-1)
-    assert ctx.lib.mod_process_frame_host(ctx.h, *args, None, None, objs, CAP, C.byref(n)) == 0
+    assert ctx.process_frame_host(sq["disparity"][1], sq["disparity"][0], flow0, tf[0], float(sq["dt"][0]), capacity=CAP)[0] == 0
     ctx.synchronize()
     _check_frame(ws, 0, refs[0][1], refs[0][3], refs[0][0], ctx.max_objects, count=False)
     ctx.close()
@@ -378,12 +377,10 @@ def test_validation_and_cluster_cloud_host(oracle):
     for j, k in zip((0, 1, 2, 4, 5, 6), PLANES):
         rec[..., j] = cl[k]
     _prefill(ws)
-    CAP = ctx.max_objects
-    objs, n = (capi.ModObject * CAP)(), C.c_int32(-1)
-    assert ctx.lib.mod_cluster_cloud_host(ctx.h, rec.ctypes.data, W, H, 32, 32 * W, None, objs, CAP, C.byref(n)) == 0, ctx.lib.mod_last_error(ctx.h)
+    rc, n, _ = ctx.cluster_cloud_host(rec, capacity=ctx.max_objects)
     ctx.synchronize()
     rl, ro, rK = oracle.cluster(cl, prm, "tidy", max_objects=W * H)
-    assert n.value == len(ro) == 1
+    assert rc == 0 and n == len(ro) == 1
     _check_frame(ws, 0, rl, rK, cl, ctx.max_objects, count=False)
     ctx.close()
 

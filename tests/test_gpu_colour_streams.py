@@ -2,7 +2,6 @@
 colour messages equals the mono8 stream fed their grey, bit for bit: B = G = R bgr8, coloured bgra8 in a padded larger message with a
 centred window, mono8 and colour submits alternating, layouts changed while frames are in flight, the single-frame SGM and flow host
 calls, and the NULL layout against a context that never set one."""
-import ctypes as C
 import os
 import sys
 
@@ -143,14 +142,11 @@ def test_d_single_frame_host_calls_under_a_colour_layout(scene, runs):
     ctx.set_image_layout(_layout(col[1][0][1]))
     disp = np.full((H, W), -7, np.float32)
     flow = np.full((H, W, 2), -7, np.float32)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, col[1][0][0].ctypes.data, col[1][1][0].ctypes.data, C.byref(sp), disp.ctypes.data) == 0
-    assert ctx.lib.mod_flow_compute_host(ctx.h, col[0][0][0].ctypes.data, col[1][0][0].ctypes.data, C.byref(fp), flow.ctypes.data) == 0
+    assert ctx.disparity_host(col[1][0][0], col[1][1][0], sp, disp)[0] == 0
+    assert ctx.flow_host(col[0][0][0], col[1][0][0], fp, flow)[0] == 0
     ctx.set_image_layout(None)
     gl, gr, gp = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (grey[1][0], grey[1][1], grey[0][0]))
-    d_disp = torch.empty((H, W), dtype=torch.float32, device=dev)
-    d_flow = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, gl.data_ptr(), gr.data_ptr(), C.byref(sp), d_disp.data_ptr()) == 0
-    assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, gp.data_ptr(), gl.data_ptr(), C.byref(fp), d_flow.data_ptr()) == 0
+    d_disp, d_flow = ctx.estimate_disparity(gl, gr, sp), ctx.estimate_flow(gp, gl, fp)
     ctx.synchronize()
     assert disp.tobytes() == d_disp.cpu().numpy().tobytes()
     assert flow.tobytes() == d_flow.cpu().numpy().tobytes()

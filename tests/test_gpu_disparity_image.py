@@ -2,7 +2,6 @@
 shapes of test_gpu_flow_image.py.  The planes hold NaN, +-inf, -1, +-0, min_disparity and max_disparity, the floats next to either on
 both sides, and the output of mod_sgm_compute_dev on a seeded pair with sub-pixel on (sixteenths, and the estimator's own invalid
 value), under a camera range that cuts through the estimator's."""
-import ctypes as C
 import os
 import sys
 
@@ -92,10 +91,9 @@ def test_the_estimators_plane(contexts, shape):
     disp = torch.full((F, H, W), -7.0, dtype=torch.float32, device=ctx.device)
     ctx.set_disparity_subpixel(True)
     try:
-        rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, left.data_ptr(), right.data_ptr(), C.byref(prm), disp.data_ptr())
+        ctx.estimate_disparity(left, right, prm, disp)
     finally:
         ctx.set_disparity_subpixel(False)
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
     got = ctx.disparity_image(disp)
     ctx.synchronize()
     d = disp.cpu().numpy()

@@ -89,10 +89,8 @@ def test_batch_equals_single_frames_repeats_and_the_host_form():
     for f in range(F):
         t1, r1 = ctx.estimate_egomotion(dp[f], dn[f], fl[f], p)
         assert t1.tobytes() == tf[f:f + 1].tobytes() and r1.tobytes() == res[f:f + 1].tobytes(), f
-        ht, hr = capi.ModTransform(), capi.ModEgoResult()
-        assert ctx.lib.mod_egomotion_host(ctx.h, frs[f].disparity_prev.ctypes.data, frs[f].disparity_now.ctypes.data, frs[f].flow.ctypes.data,
-                                          C.byref(p), C.byref(ht), C.byref(hr)) == 0
-        assert bytes(ht) == tf[f].tobytes() and bytes(hr) == res[f:f + 1].tobytes(), f
+        rc, ht, hr = ctx.egomotion_host(frs[f].disparity_prev, frs[f].disparity_now, frs[f].flow, p)
+        assert rc == 0 and bytes(ht) == tf[f].tobytes() and bytes(hr) == res[f:f + 1].tobytes(), f
     ctx.close()
 
 
@@ -264,11 +262,8 @@ def test_argument_and_capacity_codes():
     assert call(1, capi.ego_params(), c=None) == capi.MOD_SKIP_NO_FLOW
     assert call(1, capi.ego_params(), a=None) == capi.MOD_SKIP_NO_DISPARITY_PREV
     assert call(1, capi.ego_params(), b=None) == capi.MOD_SKIP_NO_DISPARITY_NOW
-    ht, hr = capi.ModTransform(), capi.ModEgoResult()
-    nan = np.full_like(frs[0].disparity_prev, np.nan)
-    assert ctx.lib.mod_egomotion_host(ctx.h, nan.ctypes.data, frs[0].disparity_now.ctypes.data, frs[0].flow.ctypes.data, C.byref(capi.ego_params()),
-                                      C.byref(ht), C.byref(hr)) == capi.MOD_SKIP_NO_TRANSFORM
-    assert hr.status == capi.MOD_EGO_FEW_POINTS and np.isnan(list(ht.t)).all()
+    rc, ht, hr = ctx.egomotion_host(np.full_like(frs[0].disparity_prev, np.nan), frs[0].disparity_now, frs[0].flow)
+    assert rc == capi.MOD_SKIP_NO_TRANSFORM and hr.status == capi.MOD_EGO_FEW_POINTS and np.isnan(list(ht.t)).all()
     l8 = np.zeros((H, W), np.uint8)
     tk = C.c_int32()
     sub = lambda sp, fp, ep: ctx.lib.mod_submit_odometry_host(ctx.h, l8.ctypes.data, l8.ctypes.data, sp, fp, ep, 0.1, None, None, None, 0, None, None,

@@ -160,10 +160,7 @@ def _host_ctx(raw):
 
 def _sgm_dev(ctx, raw, sp):
     l, r = (torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device) for a in raw["rect"])
-    disp = torch.empty((H_, W_), dtype=torch.float32, device=ctx.device)
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, l.data_ptr(), r.data_ptr(), C.byref(sp), disp.data_ptr()) == 0
-    ctx.synchronize()
-    return disp.cpu().numpy()
+    return ctx.estimate_disparity(l, r, sp).cpu().numpy()
 
 
 @pytest.mark.parametrize("side_by_side", [False, True])
@@ -183,10 +180,10 @@ def test_sgm_host_on_raw_fisheye_messages(raw, side_by_side):
         msg = np.ascontiguousarray(msg)
         ctx.set_image_layout(capi.image_layout("bgr8", RW, RH, layd["step"], raw["lay"][4], raw["lay"][5]))
         ctx.set_side_by_side(True)
-        rc = ctx.lib.mod_sgm_compute_host(ctx.h, msg.ctypes.data, None, C.byref(sp), d.ctypes.data)
+        rc, _ = ctx.disparity_host(msg, None, sp, d)
     else:
-        rc = ctx.lib.mod_sgm_compute_host(ctx.h, raw["msgs"][0].ctypes.data, raw["msgs"][1].ctypes.data, C.byref(sp), d.ctypes.data)
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
+        rc, _ = ctx.disparity_host(raw["msgs"][0], raw["msgs"][1], sp, d)
+    assert rc == 0
     assert d.tobytes() == want.tobytes()
     ctx.close()
 

@@ -38,10 +38,7 @@ def _gpu(ctx, prev, now, prm):
     dev = ctx.device
     tp, tn = torch.from_numpy(prev).to(dev), torch.from_numpy(now).to(dev)
     out = torch.full((F, H, W, 2), -7.0, dtype=torch.float32, device=dev)
-    rc = ctx.lib.mod_flow_compute_dev(ctx.h, F, tp.data_ptr(), tn.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-    ctx.synchronize()
-    return out.cpu().numpy()
+    return ctx.estimate_flow(tp, tn, prm, out).cpu().numpy()   # (.cpu() waits: the context runs on torch\'s stream)
 
 
 def _same(a, b):
@@ -87,7 +84,7 @@ def test_fixture_host_form_and_argument_checks():
         assert _same(dev, g["flow"][k]), k
         host = np.full((H, W, 2), -7.0, np.float32)
         pv, nw = np.ascontiguousarray(g["prev"][k]), np.ascontiguousarray(g["now"][k])
-        assert ctx.lib.mod_flow_compute_host(ctx.h, pv.ctypes.data, nw.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+        assert ctx.flow_host(pv, nw, prm, host)[0] == 0
         assert _same(host, dev), k
     # the pipeline wrapper, on device tensors
     tp, tn = torch.from_numpy(g["prev"][0]).to(ctx.device), torch.from_numpy(g["now"][0]).to(ctx.device)
@@ -101,14 +98,14 @@ def test_fixture_host_form_and_argument_checks():
     for bad in (capi.flow_params(window=4), capi.flow_params(window=9), capi.flow_params(levels=5), capi.flow_params(levels=0),
                 capi.flow_params(levels=7), capi.flow_params(radius=0), capi.flow_params(radius=9), capi.ModFlowParams(4, 4, 5, 2, 1)):
         assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, t3.data_ptr(), t3.data_ptr(), C.byref(bad), out.data_ptr()) == capi.MOD_ERR_INVALID_ARGUMENT
-        assert ctx.lib.mod_flow_compute_host(ctx.h, pv.ctypes.data, nw.ctypes.data, C.byref(bad), out.data_ptr()) == capi.MOD_ERR_INVALID_ARGUMENT
+        assert ctx.lib.mod_flow_compute_host(ctx.h, pv.ctypes.data, nw.ctypes.data, C.byref(bad), out.data_ptr()) == capi.MOD_ERR_INVALID_ARGUMENT   # a device pointer as the host output
     assert b"16 px" in ctx.lib.mod_last_error(ctx.h) or b"must" in ctx.lib.mod_last_error(ctx.h)
     ok = capi.flow_params()
     assert ctx.lib.mod_flow_compute_dev(ctx.h, 3, t3.data_ptr(), t3.data_ptr(), C.byref(ok), out.data_ptr()) == capi.MOD_ERR_CAPACITY
     assert ctx.lib.mod_flow_compute_dev(ctx.h, 0, t3.data_ptr(), t3.data_ptr(), C.byref(ok), out.data_ptr()) == capi.MOD_ERR_INVALID_ARGUMENT
     assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, None, t3.data_ptr(), C.byref(ok), out.data_ptr()) == capi.MOD_SKIP_NO_FLOW
     assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, t3.data_ptr(), None, C.byref(ok), out.data_ptr()) == capi.MOD_SKIP_NO_FLOW
-    assert ctx.lib.mod_flow_compute_host(ctx.h, None, nw.ctypes.data, C.byref(ok), out.data_ptr()) == capi.MOD_SKIP_NO_FLOW
+    assert ctx.lib.mod_flow_compute_host(ctx.h, None, nw.ctypes.data, C.byref(ok), out.data_ptr()) == capi.MOD_SKIP_NO_FLOW   # a device pointer as the host output
     assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, t3.data_ptr(), t3.data_ptr(), None, out.data_ptr()) == capi.MOD_ERR_INVALID_ARGUMENT
     assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, t3.data_ptr(), t3.data_ptr(), C.byref(ok), None) == capi.MOD_ERR_INVALID_ARGUMENT
     ctx.close()

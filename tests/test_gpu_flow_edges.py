@@ -135,5 +135,5 @@ def test_host_form_equals_the_device_form(name, contexts):
     host = np.full((c.H, c.W, 2), SENTINEL, np.uint32)
     pv, nw = np.ascontiguousarray(c.prev[0]), np.ascontiguousarray(c.now[0])
     prm = capi.flow_params(**c.params)
-    assert ctx.lib.mod_flow_compute_host(ctx.h, pv.ctypes.data, nw.ctypes.data, C.byref(prm), host.ctypes.data) == 0, ctx.lib.mod_last_error(ctx.h)
+    assert ctx.flow_host(pv, nw, prm, host)[0] == 0
     assert np.array_equal(host, dev), (name, int((host != dev).any(-1).sum()))

@@ -32,10 +32,7 @@ def _gpu(ctx, prev, now, prm):
     dev = ctx.device
     tp, tn = torch.from_numpy(prev).to(dev), torch.from_numpy(now).to(dev)
     out = torch.full((F, H, W, 2), -7.0, dtype=torch.float32, device=dev)
-    rc = ctx.lib.mod_flow_compute_dev(ctx.h, F, tp.data_ptr(), tn.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-    ctx.synchronize()
-    return out.cpu().numpy()
+    return ctx.estimate_flow(tp, tn, prm, out).cpu().numpy()   # (.cpu() waits: the context runs on torch\'s stream)
 
 
 def _diff(a, b):
@@ -86,7 +83,7 @@ def test_fixture_and_state():
         assert _diff(got, default[k]) > 0, k
         host = np.full((H, W, 2), -7.0, np.float32)               # the host form reads the same state
         pv, nw = np.ascontiguousarray(g["prev"][k]), np.ascontiguousarray(g["now"][k])
-        assert ctx.lib.mod_flow_compute_host(ctx.h, pv.ctypes.data, nw.ctypes.data, C.byref(prms[k]), host.ctypes.data) == 0
+        assert ctx.flow_host(pv, nw, prms[k], host)[0] == 0
         assert _diff(host, got) == 0, k
     ctx.set_flow_propagation(1)
     for k in range(len(prms)):

@@ -1,6 +1,5 @@
 """GPU: the HIP path through the C ABI against the committed golden fixtures — device entry points, the host-pointer
 entry points a ROS node would call, skip / error codes."""
-import ctypes as C
 import glob
 import os
 
@@ -52,59 +51,56 @@ def test_host_entry_points_match_golden(path):
     g = {k: np.ascontiguousarray(g[k]) for k in g.files}     # NpzFile hands out temporaries: keep the arrays alive
     ctx = _ctx(cam, prm)
     H, W = g["d_now"].shape
+    from moving_object_detector_amd.host_calls import objects_bytes
     cloud = np.zeros((H, W, 8), np.float32)
     labels = np.zeros((H, W), np.int32)
-    objs = np.zeros(64, OBJECT_DTYPE)
-    n = C.c_int32(-1)
-    tf = capi.transforms_array([g["t"]], [g["q"]])
-    rc = ctx.lib.mod_process_frame_host(ctx.h, g["d_now"].ctypes.data, g["d_prev"].ctypes.data, g["flow"].ctypes.data, tf,
-                                        float(np.asarray(g["dt"]).item()), cloud.ctypes.data, labels.ctypes.data, objs.ctypes.data, 64, C.byref(n))
+    tf = capi.transforms_array([g["t"]], [g["q"]])[0]
+    frame = (g["d_now"], g["d_prev"], g["flow"], tf, float(np.asarray(g["dt"]).item()))
+    rc, n, rec = ctx.process_frame_host(*frame, cloud, labels, 64)
     assert rc == 0
     for j, k in zip((0, 1, 2, 4, 5, 6), PLANES):
         assert bits_equal(cloud[..., j], g[k]), k
-    assert np.array_equal(labels, g["labels"]) and n.value == int(np.asarray(g["n_objects"]).item())
-    compare_objects(objs[: n.value], golden_objects(g), strict_velocity=False)
+    assert np.array_equal(labels, g["labels"]) and n == int(np.asarray(g["n_objects"]).item())
+    objs = objects_bytes(rec, n, 64)
+    compare_objects(np.frombuffer(objs, OBJECT_DTYPE), golden_objects(g), strict_velocity=False)
     # ~synthetic_optical_flow for a node with host buffers (calculateStaticOpticalFlow, scene_flow_constructor.cpp:65-89,141-145)
     sflow = np.full((H, W, 2), 7.0, np.float32)
-    assert ctx.lib.mod_static_flow_host(ctx.h, g["d_prev"].ctypes.data, tf, sflow.ctypes.data) == 0
+    assert ctx.static_flow_host(g["d_prev"], tf, sflow)[0] == 0
     assert bits_equal(sflow, g["static_flow"])
-    assert ctx.lib.mod_static_flow_host(ctx.h, None, tf, sflow.ctypes.data) == capi.MOD_SKIP_NO_DISPARITY_PREV
-    assert ctx.lib.mod_static_flow_host(ctx.h, g["d_prev"].ctypes.data, None, sflow.ctypes.data) == capi.MOD_SKIP_NO_TRANSFORM
+    assert ctx.static_flow_host(None, tf, sflow)[0] == capi.MOD_SKIP_NO_DISPARITY_PREV
+    assert ctx.static_flow_host(g["d_prev"], None, sflow)[0] == capi.MOD_SKIP_NO_TRANSFORM
     # clusterer alone on the PointCloud2 payload (ClustererNodelet::dataCB)
     labels2 = np.zeros((H, W), np.int32)
-    n2 = C.c_int32(-1)
-    rc = ctx.lib.mod_cluster_cloud_host(ctx.h, cloud.ctypes.data, W, H, 32, 32 * W, labels2.ctypes.data, objs.ctypes.data, 64, C.byref(n2))
-    assert rc == 0 and np.array_equal(labels2, g["labels"]) and n2.value == n.value
+    rc, n2, _ = ctx.cluster_cloud_host(cloud, labels2, 64)
+    assert rc == 0 and np.array_equal(labels2, g["labels"]) and n2 == n
     # without a labels plane (no subscriber of the cluster image, clusterer_nodelet.cpp:235-236): the same objects
-    objs3, n3 = np.zeros(64, OBJECT_DTYPE), C.c_int32(-1)
-    rc = ctx.lib.mod_process_frame_host(ctx.h, g["d_now"].ctypes.data, g["d_prev"].ctypes.data, g["flow"].ctypes.data, tf,
-                                        float(np.asarray(g["dt"]).item()), None, None, objs3.ctypes.data, 64, C.byref(n3))
-    assert rc == 0 and n3.value == n.value and objs3[: n3.value].tobytes() == objs[: n.value].tobytes()
-    rc = ctx.lib.mod_cluster_cloud_host(ctx.h, cloud.ctypes.data, W, H, 32, 32 * W, None, objs3.ctypes.data, 64, C.byref(n3))
-    assert rc == 0 and n3.value == n.value and objs3[: n3.value].tobytes() == objs[: n.value].tobytes()
+    rc, n3, rec3 = ctx.process_frame_host(*frame, capacity=64)
+    assert rc == 0 and n3 == n and objects_bytes(rec3, n3, 64) == objs
+    rc, n3, rec3 = ctx.cluster_cloud_host(cloud, capacity=64)
+    assert rc == 0 and n3 == n and objects_bytes(rec3, n3, 64) == objs
     # a caller that only counts the objects (n_objects alone) still gets the real count: the cluster stage runs
-    n5 = C.c_int32(-1)
-    rc = ctx.lib.mod_process_frame_host(ctx.h, g["d_now"].ctypes.data, g["d_prev"].ctypes.data, g["flow"].ctypes.data, tf,
-                                        float(np.asarray(g["dt"]).item()), None, None, None, 0, C.byref(n5))
-    assert rc == 0 and n5.value == n.value
+    assert ctx.process_frame_host(*frame) == (0, n, None)
     # ... and with no cluster output at all (not even the count) only the scene-flow stage runs: the cloud is the same
     cloud5 = np.zeros((H, W, 8), np.float32)
-    rc = ctx.lib.mod_process_frame_host(ctx.h, g["d_now"].ctypes.data, g["d_prev"].ctypes.data, g["flow"].ctypes.data, tf,
-                                        float(np.asarray(g["dt"]).item()), cloud5.ctypes.data, None, None, 0, None)
-    assert rc == 0 and cloud5.tobytes() == cloud.tobytes()
+    assert ctx.process_frame_host(*frame, cloud5, count=False) == (0, None, None) and cloud5.tobytes() == cloud.tobytes()
     # a clusterer-only context (the nodelet in its own process): no camera is ever set, the size comes with the cloud
     from moving_object_detector_amd.pipeline import Context
     solo = Context(W + 7, H + 3, max_frames=1, max_objects=(W + 7) * (H + 3) // prm.cluster_size + 1)
-    assert solo.lib.mod_cluster_cloud_host(solo.h, cloud.ctypes.data, W, H, 32, 32 * W, labels2.ctypes.data, objs3.ctypes.data, 64, C.byref(n3)) == capi.MOD_ERR_NOT_CONFIGURED
+    with pytest.raises(capi.ModError) as e:
+        solo.cluster_cloud_host(cloud, labels2, 64, width=W, height=H)
+    assert e.value.code == capi.MOD_ERR_NOT_CONFIGURED
     solo.set_params(prm)
     labels4 = np.full((H, W), -5, np.int32)
-    rc = solo.lib.mod_cluster_cloud_host(solo.h, cloud.ctypes.data, W, H, 32, 32 * W, labels4.ctypes.data, objs3.ctypes.data, 64, C.byref(n3))
-    assert rc == 0 and np.array_equal(labels4, g["labels"]) and n3.value == n.value and objs3[: n3.value].tobytes() == objs[: n.value].tobytes()
-    assert solo.lib.mod_cluster_cloud_host(solo.h, cloud.ctypes.data, W + 8, H, 32, 32 * W, None, objs3.ctypes.data, 64, C.byref(n3)) == capi.MOD_ERR_CAPACITY
+    rc, n3, rec3 = solo.cluster_cloud_host(cloud, labels4, 64, width=W, height=H)
+    assert rc == 0 and np.array_equal(labels4, g["labels"]) and n3 == n and objects_bytes(rec3, n3, 64) == objs
+    with pytest.raises(capi.ModError) as e:
+        solo.cluster_cloud_host(cloud, capacity=64, row_step=32 * W, width=W + 8, height=H)
+    assert e.value.code == capi.MOD_ERR_CAPACITY
     solo.close()
     # a cloud of the wrong size is an error, not a silent skip
-    rc = ctx.lib.mod_cluster_cloud_host(ctx.h, cloud.ctypes.data, W - 1, H, 32, 32 * W, labels2.ctypes.data, objs.ctypes.data, 64, C.byref(n2))
-    assert rc == capi.MOD_ERR_INVALID_ARGUMENT and b"cloud size" in ctx.lib.mod_last_error(ctx.h)
+    with pytest.raises(capi.ModError, match="cloud size") as e:
+        ctx.cluster_cloud_host(cloud, labels2, 64, row_step=32 * W, width=W - 1)
+    assert e.value.code == capi.MOD_ERR_INVALID_ARGUMENT
     ctx.close()
 
 
@@ -114,15 +110,14 @@ def test_missing_inputs_return_skip_codes():
     g, cam, prm = load_case(GOLD[0])
     g = {k: np.ascontiguousarray(g[k]) for k in g.files}
     ctx = _ctx(cam, prm)
-    n = C.c_int32(-1)
-    tf = capi.transforms_array([g["t"]], [g["q"]])
-    a = (g["d_now"].ctypes.data, g["d_prev"].ctypes.data, g["flow"].ctypes.data)
-    call = lambda dn, dp, fl, t: ctx.lib.mod_process_frame_host(ctx.h, dn, dp, fl, t, 0.1, None, None, None, 0, C.byref(n))
-    assert call(a[0], a[1], None, tf) == capi.MOD_SKIP_NO_FLOW and n.value == 0
-    assert call(a[0], None, a[2], tf) == capi.MOD_SKIP_NO_DISPARITY_PREV
-    assert call(a[0], a[1], a[2], None) == capi.MOD_SKIP_NO_TRANSFORM
-    assert call(None, a[1], a[2], tf) == capi.MOD_SKIP_NO_DISPARITY_NOW
-    assert call(a[0], a[1], a[2], tf) == 0
+    tf = capi.transforms_array([g["t"]], [g["q"]])[0]
+    a = (g["d_now"], g["d_prev"], g["flow"])
+    call = lambda dn, dp, fl, t: ctx.process_frame_host(dn, dp, fl, t, 0.1)[:2]   # noqa: E731
+    assert call(a[0], a[1], None, tf) == (capi.MOD_SKIP_NO_FLOW, 0)
+    assert call(a[0], None, a[2], tf)[0] == capi.MOD_SKIP_NO_DISPARITY_PREV
+    assert call(a[0], a[1], a[2], None)[0] == capi.MOD_SKIP_NO_TRANSFORM
+    assert call(None, a[1], a[2], tf)[0] == capi.MOD_SKIP_NO_DISPARITY_NOW
+    assert call(a[0], a[1], a[2], tf)[0] == 0
     ctx.close()
 
 
@@ -167,9 +162,9 @@ def test_depth_is_published_on_skipped_frames(path):
     ctx.synchronize()
     assert bits_equal(out[0].cpu().numpy(), g["depth"])
     host = np.full(g["d_now"].shape, -7.0, np.float32)
-    assert ctx.lib.mod_depth_image_host(ctx.h, g["d_now"].ctypes.data, host.ctypes.data) == 0
+    assert ctx.depth_image_host(g["d_now"], host)[0] == 0
     assert bits_equal(host, g["depth"])
-    assert ctx.lib.mod_depth_image_host(ctx.h, None, host.ctypes.data) == capi.MOD_SKIP_NO_DISPARITY_NOW
+    assert ctx.depth_image_host(None, host)[0] == capi.MOD_SKIP_NO_DISPARITY_NOW
     ctx.close()
 
 

@@ -9,7 +9,6 @@ case runs on a 48 x 32 camera too.  There the scene is two bands 4 and 7 pixels 
 whose new focal length is 0.8 of the old and whose principal points are 1.8 pixels apart, about 2 and 4): a plane that saw the
 images is valid over most of the camera and holds both bands' disparities and the values between them, so at least half of its
 pixels must be valid and at least three valid values distinct, rectified or not, before the planes are compared."""
-import ctypes as C
 import os
 import sys
 
@@ -66,11 +65,10 @@ def test_the_synchronous_and_the_stream_route_give_the_same_disparity(cam, name,
             c.set_rectification(*[capi.rectify_camera(*rm.distorted(mw, mh, eye)) for eye in (0, 1)])
         rng = np.random.default_rng(17)
         pairs = [_pair(rng, mw, mh, bpp, pad, sbs) for _ in range(2)]
-        ptr = lambda m: m.ctypes.data if m is not None else None
         sp = capi.ModSgmParams(8, 6, 96, 8, 1, 1)
         sync = np.full((H, W), -7, np.float32)
         left, right = pairs[1]
-        assert c.lib.mod_sgm_compute_host(c.h, ptr(left), ptr(right), C.byref(sp), sync.ctypes.data) == 0, c.lib.mod_last_error(c.h)
+        assert c.disparity_host(left, right, sp, sync)[0] == 0
         flow = np.zeros((H, W, 2), np.float32)
         tf = capi.ModTransform((0, 0, 0), (0, 0, 0, 1))
         # the stream needs a first frame (it has no previous disparity: it takes a plane and no ticket); the estimator carries nothing

@@ -39,11 +39,10 @@ def test_stream_matches_synchronous_path():
         n = C.c_int32(-1)
         if not stream:
             for f in range(F):
-                rc = ctx.lib.mod_process_frame_host(ctx.h, b["disparity_now"][f].ctypes.data, b["disparity_prev"][f].ctypes.data,
-                                                    b["flow"][f].ctypes.data, C.byref(tfs[f]), float(b["dt"][f]), clouds[f].ctypes.data,
-                                                    labels[f].ctypes.data, objs[f], CAP, C.byref(n))
+                rc, k, objs[f] = ctx.process_frame_host(b["disparity_now"][f], b["disparity_prev"][f], b["flow"][f], tfs[f], float(b["dt"][f]),
+                                                        clouds[f], labels[f], CAP)
                 assert rc == 0
-                counts.append(n.value)
+                counts.append(k)
         else:
             tickets = []
             t = C.c_int32(-1)
@@ -146,14 +145,13 @@ def test_stereo_stream_matches_estimate_then_process():
         objs = [(capi.ModObject * CAP)() for _ in range(F)]
         counts, n = [], C.c_int32(-1)
         for f in range(F):
-            assert ctx.lib.mod_sgm_compute_host(ctx.h, lefts[f].ctypes.data, rights[f].ctypes.data, C.byref(sp), disp[f].ctypes.data) == 0
+            assert ctx.disparity_host(lefts[f], rights[f], sp, disp[f])[0] == 0
             if f == 0:
                 counts.append(None)                                   # no previous disparity: construct() publishes nothing
                 continue
-            rc = ctx.lib.mod_process_frame_host(ctx.h, disp[f].ctypes.data, disp[f - 1].ctypes.data, flows[f].ctypes.data, C.byref(tf[f]), dt,
-                                                clouds[f].ctypes.data, labels[f].ctypes.data, objs[f], CAP, C.byref(n))
+            rc, k, objs[f] = ctx.process_frame_host(disp[f], disp[f - 1], flows[f], tf[f], dt, clouds[f], labels[f], CAP)
             assert rc == 0
-            counts.append(n.value)
+            counts.append(k)
         ctx.close()
         return disp, clouds, labels, objs, counts
 
@@ -237,9 +235,9 @@ def test_stereo_and_disparity_submissions_share_the_ring():
 
     ref = Context(W, H, max_frames=1)
     ref.set_camera(cam); ref.set_params(prm)
-    cloud0 = np.zeros((N, 8), np.float32); lab0 = np.full(N, -7, np.int32); objs0 = (capi.ModObject * CAP)()
-    rc = ref.lib.mod_process_frame_host(ref.h, disp.ctypes.data, disp.ctypes.data, flow.ctypes.data, C.byref(tf[0]), dt, cloud0.ctypes.data, lab0.ctypes.data, objs0, CAP, C.byref(n))
-    assert rc == 0 and n.value == n1 and n1 > 0
+    cloud0 = np.zeros((N, 8), np.float32); lab0 = np.full(N, -7, np.int32)
+    rc, n0, objs0 = ref.process_frame_host(disp, disp, flow, tf[0], dt, cloud0, lab0, CAP)
+    assert rc == 0 and n0 == n1 and n1 > 0
     ref.close()
     assert np.array_equal(lab1, lab0)
     assert np.array_equal(cloud1.view(np.uint32)[:, [0, 1, 2, 4, 5, 6]], cloud0.view(np.uint32)[:, [0, 1, 2, 4, 5, 6]])

@@ -45,13 +45,12 @@ def test_images_stream_matches_the_separate_estimators_and_the_oracle(oracle):
     for f in range(FR):
         d = torch.empty((1, H, W), dtype=torch.float32, device=dev)
         tl, tr = torch.from_numpy(lefts[f][None]).to(dev), torch.from_numpy(rights[f][None]).to(dev)
-        assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, tl.data_ptr(), tr.data_ptr(), C.byref(sp), d.data_ptr()) == 0
+        ctx.estimate_disparity(tl, tr, sp, d)
         ctx.synchronize()
         disp_ref.append(d[0].cpu().numpy())
         if f:
             tp = torch.from_numpy(lefts[f - 1][None]).to(dev)
-            fl = torch.empty((1, H, W, 2), dtype=torch.float32, device=dev)
-            assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, tp.data_ptr(), tl.data_ptr(), C.byref(fps[f]), fl.data_ptr()) == 0
+            fl = ctx.estimate_flow(tp, tl, fps[f])
             ctx.synchronize()
             flow_ref.append(fl[0].cpu().numpy())
     # the stream: three frames in flight

@@ -242,8 +242,7 @@ def test_identity_rectification_changes_nothing_on_the_host_paths(raw):
 
     def sgm():
         d = np.full((H_, W_), -7, np.float32)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, msgs[1][0].ctypes.data, msgs[1][1].ctypes.data, C.byref(sp), d.ctypes.data) == 0, \
-            ctx.lib.mod_last_error(ctx.h)
+        assert ctx.disparity_host(msgs[1][0], msgs[1][1], sp, d)[0] == 0
         return d.tobytes()
 
     plain = (sgm(), _odometry(ctx, msgs))
@@ -263,10 +262,7 @@ def _dev_estimates(ctx, raw, f):
     sp, fp, _ = _params()
     dev = ctx.device
     l, r, p = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (raw["rect"][f][0], raw["rect"][f][1], raw["rect"][f - 1][0]))
-    disp = torch.empty((H_, W_), dtype=torch.float32, device=dev)
-    flow = torch.empty((H_, W_, 2), dtype=torch.float32, device=dev)
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, l.data_ptr(), r.data_ptr(), C.byref(sp), disp.data_ptr()) == 0
-    assert ctx.lib.mod_flow_compute_dev(ctx.h, 1, p.data_ptr(), l.data_ptr(), C.byref(fp), flow.data_ptr()) == 0
+    disp, flow = ctx.estimate_disparity(l, r, sp), ctx.estimate_flow(p, l, fp)
     ctx.synchronize()
     return disp.cpu().numpy(), flow.cpu().numpy()
 
@@ -313,8 +309,8 @@ def test_streams_estimate_from_the_rectified_planes(raw):
     assert np.isfinite(want[1][1]).mean() > 0.2
     d = np.full((H_, W_), -7, np.float32)
     fl = np.full((H_, W_, 2), -7, np.float32)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, msgs[2][0].ctypes.data, msgs[2][1].ctypes.data, C.byref(sp), d.ctypes.data) == 0
-    assert ctx.lib.mod_flow_compute_host(ctx.h, msgs[1][0].ctypes.data, msgs[2][0].ctypes.data, C.byref(fp), fl.ctypes.data) == 0
+    assert ctx.disparity_host(msgs[2][0], msgs[2][1], sp, d)[0] == 0
+    assert ctx.flow_host(msgs[1][0], msgs[2][0], fp, fl)[0] == 0
     assert d.tobytes() == want[2][0].tobytes() and fl.tobytes() == want[2][1].tobytes()
     ctx.close()
 
@@ -359,7 +355,7 @@ def test_rectification_cannot_change_under_a_frame_in_flight(raw):
     rect = [rm.rectify(msgs[2][k], lay, rm.build_map(raw["cals"][1 - k], x0, y0, W_, H_))[0] for k in (0, 1)]
     l, r = (torch.from_numpy(a).to(ctx.device) for a in rect)
     want = torch.empty((H_, W_), dtype=torch.float32, device=ctx.device)
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, l.data_ptr(), r.data_ptr(), C.byref(sp), want.data_ptr()) == 0
+    ctx.estimate_disparity(l, r, sp, want)
     ctx.synchronize()
     assert disp[2].tobytes() == want.cpu().numpy().tobytes()
     assert disp[2].tobytes() != _dev_estimates(ctx, raw, 2)[0].tobytes()       # (the swap is visible)
@@ -401,11 +397,13 @@ def test_layout_and_argument_codes(raw):
         d = np.zeros((H_, W_), np.float32)
         t = C.c_int32(-1)
         tf = capi.transforms_array(np.zeros((1, 3)), np.array([[0.0, 0.0, 0.0, 1.0]]))
-        assert L.mod_sgm_compute_host(ctx.h, big.ctypes.data, big.ctypes.data, C.byref(sp), d.ctypes.data) == capi.MOD_ERR_INVALID_ARGUMENT
-        assert L.mod_flow_compute_host(ctx.h, big.ctypes.data, big.ctypes.data, C.byref(fp), d.ctypes.data) == capi.MOD_ERR_INVALID_ARGUMENT
+        with pytest.raises(capi.ModError) as e:
+            ctx.disparity_host(big, big, sp, d)
+        assert e.value.code == capi.MOD_ERR_INVALID_ARGUMENT
+        assert L.mod_flow_compute_host(ctx.h, big.ctypes.data, big.ctypes.data, C.byref(fp), d.ctypes.data) == capi.MOD_ERR_INVALID_ARGUMENT   # an output of half the size
         assert L.mod_submit_images_host(ctx.h, big.ctypes.data, big.ctypes.data, C.byref(sp), C.byref(fp), C.byref(tf[0]), DT, None, None, None, 0,
                                         None, None, C.byref(t)) == capi.MOD_ERR_INVALID_ARGUMENT
         assert t.value == -1
     ctx.set_rectification()                                                     # off: the odd-sized layout is served as ever
-    assert L.mod_sgm_compute_host(ctx.h, big.ctypes.data, big.ctypes.data, C.byref(sp), d.ctypes.data) == 0
+    assert ctx.disparity_host(big, big, sp, d)[0] == 0
     ctx.close()

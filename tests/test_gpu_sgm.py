@@ -98,10 +98,7 @@ def _compute(ctx, left, right, **kw):
                             int(kw.get("median", True)))
     out = torch.full((F, H, W), -7.0, dtype=torch.float32, device=dev)
     tl, tr = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)       # kept alive until the kernels have run
-    rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-    ctx.synchronize()
-    return out.cpu().numpy()
+    return ctx.estimate_disparity(tl, tr, prm, out).cpu().numpy()   # (.cpu() waits: the context runs on torch\'s stream)
 
 
 @pytest.mark.parametrize("W,H,D,F,seed", [(320, 240, 128, 2, 1), (131, 77, 64, 1, 2), (70, 9, 128, 1, 3), (9, 7, 8, 1, 5), (96, 40, 33, 11, 6),
@@ -126,9 +123,9 @@ def test_complete_estimator_matches_the_oracle(W, H, D, F, seed):
         gl, gr = np.ascontiguousarray(g["left"]), np.ascontiguousarray(g["right"])
         host = np.full((H, W), -7.0, np.float32)
         prm = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+        assert ctx.disparity_host(gl, gr, prm, host)[0] == 0
         assert np.array_equal(host, g["disparity"])
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, None, gr.ctypes.data, C.byref(prm), host.ctypes.data) == capi.MOD_SKIP_NO_DISPARITY_NOW
+        assert ctx.disparity_host(None, gr, prm, host)[0] == capi.MOD_SKIP_NO_DISPARITY_NOW
     ctx.close()
 
 
@@ -170,7 +167,7 @@ def test_config5_images_to_moving_objects(oracle):
     sp = capi.ModSgmParams(D, 6, 96, 8, 1, 1)
     imgs_l, imgs_r = torch.from_numpy(np.stack([l0, l1])).to(dev), torch.from_numpy(np.stack([r0, r1])).to(dev)
     disp = torch.empty((2, H, W), dtype=torch.float32, device=dev)                 # [0] = previous, [1] = now
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 2, imgs_l.data_ptr(), imgs_r.data_ptr(), C.byref(sp), disp.data_ptr()) == 0
+    ctx.estimate_disparity(imgs_l, imgs_r, sp, disp)
     ctx.synchronize()
     want = [pysgm.compute(l0, r0, D), pysgm.compute(l1, r1, D)]
     got = disp.cpu().numpy()

@@ -44,10 +44,7 @@ def _compute(ctx, left, right, D, P1, P2, paths=8, lr_check=True, median=True):
     prm = capi.ModSgmParams(D, P1, P2, paths, int(lr_check), int(median))
     out = torch.full((F, H, W), -7.0, dtype=torch.float32, device=ctx.device)
     tl, tr = torch.from_numpy(np.array(left)).to(ctx.device), torch.from_numpy(np.array(right)).to(ctx.device)      # (copies: the cases are read-only)
-    rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-    ctx.synchronize()
-    return out.cpu().numpy()
+    return ctx.estimate_disparity(tl, tr, prm, out).cpu().numpy()   # (.cpu() waits: the context runs on torch\'s stream)
 
 
 def _sums(left, right, D, P1, P2, paths):
@@ -174,8 +171,9 @@ def test_an_image_one_pixel_wide_is_refused_with_its_reason():
     prm = capi.ModSgmParams(8, 6, 96, 8, 1, 1)
     img = torch.zeros((1, H, W), dtype=torch.uint8, device=dev)
     out = torch.full((1, H, W), -7.0, dtype=torch.float32, device=dev)
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, img.data_ptr(), img.data_ptr(), C.byref(prm), out.data_ptr()) == capi.MOD_ERR_INVALID_ARGUMENT
-    assert b"at least 2 pixels wide" in ctx.lib.mod_last_error(ctx.h)
+    with pytest.raises(capi.ModError, match="at least 2 pixels wide") as e:
+        ctx.estimate_disparity(img, img, prm, out)
+    assert e.value.code == capi.MOD_ERR_INVALID_ARGUMENT
     cen = torch.zeros((1, H, W), dtype=torch.int32, device=dev)
     L = torch.full((1, H, W, 8), FILL, dtype=torch.uint8, device=dev)
     assert ctx.lib.mod_sgm_path_dev(ctx.h, 1, cen.data_ptr(), cen.data_ptr(), C.byref(prm), 0, L.data_ptr(), None) == capi.MOD_ERR_INVALID_ARGUMENT

@@ -43,10 +43,7 @@ def _compute(ctx, left, right, **kw):
     prm = _prm(kw)
     out = torch.full((F, H, W), -7.0, dtype=torch.float32, device=dev)
     tl, tr = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)       # kept alive until the kernels have run
-    rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-    ctx.synchronize()
-    return out.cpu().numpy()
+    return ctx.estimate_disparity(tl, tr, prm, out).cpu().numpy()   # (.cpu() waits: the context runs on torch\'s stream)
 
 
 def _sums(left, right, **kw):
@@ -152,20 +149,20 @@ def test_fixture_device_and_host_forms_and_off_is_off():
     assert np.array_equal(_compute(ctx, gl[None], gr[None], **kw)[0], g["disparity"])
     prm = _prm(kw)
     host = np.full((H, W), -7.0, np.float32)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+    assert ctx.disparity_host(gl, gr, prm, host)[0] == 0
     assert np.array_equal(host, g["disparity"])
     for kw2 in FLAGS[1:]:                                                                                  # the host form under the other flag combinations
         prm2 = _prm(dict(kw, **kw2))
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm2), host.ctypes.data) == 0
+        assert ctx.disparity_host(gl, gr, prm2, host)[0] == 0
         assert np.array_equal(host, _model(gl, gr, 4, filt, **dict(kw, **kw2))), kw2
     ctx.set_disparity_subpixel(0)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+    assert ctx.disparity_host(gl, gr, prm, host)[0] == 0
     assert np.array_equal(host, g["disparity_integer"])
     assert ctx.lib.mod_set_disparity_filters(ctx.h, None) == 0                                             # NULL turns everything off ...
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+    assert ctx.disparity_host(gl, gr, prm, host)[0] == 0
     assert np.array_equal(host, whole)                                                                     # ... and off is the oracle's plane
     assert np.array_equal(_compute(ctx, gl[None], gr[None], **kw)[0], whole)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, None, gr.ctypes.data, C.byref(prm), host.ctypes.data) == capi.MOD_SKIP_NO_DISPARITY_NOW
+    assert ctx.disparity_host(None, gr, prm, host)[0] == capi.MOD_SKIP_NO_DISPARITY_NOW
     ctx.close()
 
 
@@ -434,7 +431,7 @@ def test_images_to_moving_objects_with_the_filters_on(oracle):
     sp = capi.ModSgmParams(D, 6, 96, 8, 1, 1)
     tl, tr = torch.from_numpy(left[None]).to(dev), torch.from_numpy(right[None]).to(dev)
     disp = torch.empty((1, H, W), dtype=torch.float32, device=dev)
-    assert ctx.lib.mod_sgm_compute_dev(ctx.h, 1, tl.data_ptr(), tr.data_ptr(), C.byref(sp), disp.data_ptr()) == 0
+    ctx.estimate_disparity(tl, tr, sp, disp)
     want = _model(left, right, 4, filt)
     unfiltered = _model(left, right, 4, OFF)
     assert (want != unfiltered).sum() > 0

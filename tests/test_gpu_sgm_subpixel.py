@@ -41,10 +41,7 @@ def _compute(ctx, left, right, **kw):
     prm = _prm(kw)
     out = torch.full((F, H, W), -7.0, dtype=torch.float32, device=dev)
     tl, tr = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)       # kept alive until the kernels have run
-    rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
-    ctx.synchronize()
-    return out.cpu().numpy()
+    return ctx.estimate_disparity(tl, tr, prm, out).cpu().numpy()   # (.cpu() waits: the context runs on torch\'s stream)
 
 
 def _model(left, right, bits, **kw):
@@ -84,16 +81,16 @@ def test_fixture_device_and_host_forms():
     assert np.array_equal(_compute(ctx, gl[None], gr[None], **kw)[0], g["disparity"])
     prm = _prm(kw)
     host = np.full((H, W), -7.0, np.float32)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+    assert ctx.disparity_host(gl, gr, prm, host)[0] == 0
     assert np.array_equal(host, g["disparity"])
     for kw2 in FLAGS[1:]:                                                        # the host form under the other flag combinations
         prm2 = _prm(dict(kw, **kw2))
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm2), host.ctypes.data) == 0
+        assert ctx.disparity_host(gl, gr, prm2, host)[0] == 0
         assert np.array_equal(host, _model(gl, gr, 4, **dict(kw, **kw2))), kw2
     ctx.set_disparity_subpixel(False)
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, gl.ctypes.data, gr.ctypes.data, C.byref(prm), host.ctypes.data) == 0
+    assert ctx.disparity_host(gl, gr, prm, host)[0] == 0
     assert np.array_equal(host, g["disparity_integer"])
-    assert ctx.lib.mod_sgm_compute_host(ctx.h, None, gr.ctypes.data, C.byref(prm), host.ctypes.data) == capi.MOD_SKIP_NO_DISPARITY_NOW
+    assert ctx.disparity_host(None, gr, prm, host)[0] == capi.MOD_SKIP_NO_DISPARITY_NOW
     ctx.close()
 
 

@@ -166,16 +166,16 @@ def test_c_single_frame_host_calls(scene, ctx, enc, rect):
     try:
         want_d, want_f = np.full((H, W), -7, np.float32), np.full((H, W, 2), -7, np.float32)
         _state(ctx, e1["clay"], False)
-        assert ctx.lib.mod_sgm_compute_host(ctx.h, e1["cut"][0].ctypes.data, e1["cut"][1].ctypes.data, C.byref(sp), want_d.ctypes.data) == 0
-        assert ctx.lib.mod_flow_compute_host(ctx.h, e0["cut"][0].ctypes.data, e1["cut"][0].ctypes.data, C.byref(fp), want_f.ctypes.data) == 0
+        assert ctx.disparity_host(e1["cut"][0], e1["cut"][1], sp, want_d)[0] == 0
+        assert ctx.flow_host(e0["cut"][0], e1["cut"][0], fp, want_f)[0] == 0
         assert (want_d >= 0).any() and np.isfinite(want_f).any()
         _state(ctx, e1["blay"], True)
-        for right in (None, e1["both"].ctypes.data):
+        for right in (None, e1["both"]):
             got = np.full((H, W), -7, np.float32)
-            assert ctx.lib.mod_sgm_compute_host(ctx.h, e1["both"].ctypes.data, right, C.byref(sp), got.ctypes.data) == 0
+            assert ctx.disparity_host(e1["both"], right, sp, got)[0] == 0
             assert got.tobytes() == want_d.tobytes()
         got = np.full((H, W, 2), -7, np.float32)
-        assert ctx.lib.mod_flow_compute_host(ctx.h, e0["both"].ctypes.data, e1["both"].ctypes.data, C.byref(fp), got.ctypes.data) == 0
+        assert ctx.flow_host(e0["both"], e1["both"], fp, got)[0] == 0
         assert got.tobytes() == want_f.tobytes()
     finally:
         _state(ctx, None, False)
@@ -238,7 +238,7 @@ def test_e_argument_and_skip_codes(scene):
     flow = np.zeros((h, w, 2), np.float32)
     t = C.c_int32(-5)
     tf = capi.ModTransform((0, 0, 0), (0, 0, 0, 1))
-    sgm = lambda l, r: L.mod_sgm_compute_host(c.h, l, r, C.byref(sp), disp.ctypes.data)   # noqa: E731
+    sgm = lambda l, r: L.mod_sgm_compute_host(c.h, l, r, C.byref(sp), disp.ctypes.data)   # noqa: E731  (raw addresses: one points into the right pane)
     stereo = lambda l, r: L.mod_submit_stereo_host(c.h, l, r, C.byref(sp), flow.ctypes.data, C.byref(tf), DT, None, None, None, 0, None,   # noqa: E731
                                                    C.byref(t))
     images = lambda l, r: L.mod_submit_images_host(c.h, l, r, C.byref(sp), C.byref(fp), C.byref(tf), DT, None, None, None, 0, None, None,   # noqa: E731
@@ -275,8 +275,10 @@ def test_e_argument_and_skip_codes(scene):
     assert bare.lib.mod_set_side_by_side(bare.h, 1) == 0 and bare.get_side_by_side() is True
     bare.set_camera(cam)
     bare.set_params(synth.Params())
-    assert bare.lib.mod_sgm_compute_host(bare.h, m, None, C.byref(sp), disp.ctypes.data) == capi.MOD_ERR_INVALID_ARGUMENT   # at call time
+    with pytest.raises(capi.ModError) as e:                                                                                 # at call time
+        bare.disparity_host(msg, None, sp, disp)
+    assert e.value.code == capi.MOD_ERR_INVALID_ARGUMENT
     assert bare.lib.mod_set_image_layout(bare.h, C.byref(one)) == capi.MOD_ERR_INVALID_ARGUMENT
     bare.set_image_layout(two)
-    assert bare.lib.mod_sgm_compute_host(bare.h, m, None, C.byref(sp), disp.ctypes.data) == 0
+    assert bare.disparity_host(msg, None, sp, disp)[0] == 0
     bare.close()

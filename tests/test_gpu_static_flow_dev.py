@@ -47,7 +47,7 @@ def test_device_call_equals_three_host_calls():
     tfs = capi.transforms_array(t, q)
     want = np.full((F, H, W, 2), -7.0, f32)
     for f in range(F):
-        assert ctx.lib.mod_static_flow_host(ctx.h, d[f].ctypes.data, tfs[f], want[f].ctypes.data) == 0, ctx.lib.mod_last_error(ctx.h)
+        assert ctx.static_flow_host(d[f], tfs[f], want[f])[0] == 0
     tf_dev = torch.from_numpy(np.concatenate([t, q], axis=1)).to(ctx.device)
     assert tf_dev.shape == (F, 7) and tf_dev.dtype == torch.float64
     buf = torch.full((F * H * W * 2 + 32,), -7.0, dtype=torch.float32, device=ctx.device)

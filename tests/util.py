@@ -15,24 +15,17 @@ class EgoChecked:
 
     def __init__(self, W, H, F, cam):
         from moving_object_detector_amd import capi, synth
+        from moving_object_detector_amd.host_calls import HostCalls
         import moving_object_detector_amd.pipeline  # noqa: F401  (torch first: one HIP runtime)
-        L = C.CDLL(CHECKED_LIB)
-        vp = C.c_void_p
-        L.mod_create.argtypes = [C.POINTER(capi.ModConfig), C.POINTER(vp)]
-        L.mod_destroy.argtypes = [vp]
-        L.mod_destroy.restype = None
-        L.mod_set_camera.argtypes = [vp, C.POINTER(capi.ModCamera)]
-        L.mod_set_params.argtypes = [vp, C.POINTER(capi.ModParams)]
-        L.mod_egomotion_dev.argtypes = [vp, C.c_int32, vp, vp, vp, C.POINTER(capi.ModEgoParams), vp, vp]
-        L.mod_egomotion_host.argtypes = [vp, vp, vp, vp, C.POINTER(capi.ModEgoParams), C.POINTER(capi.ModTransform), C.POINTER(capi.ModEgoResult)]
-        L.mod_synchronize.argtypes = [vp]
-        L.mod_debug_read.argtypes = [vp, C.c_int, vp, C.c_ulonglong]
+        L = capi.bind(CHECKED_LIB)
         self.L, self.h = L, C.c_void_p()
         assert L.mod_create(C.byref(capi.ModConfig(0, W, H, F, 0, 0, None)), C.byref(self.h)) == 0
         assert L.mod_set_camera(self.h, C.byref(capi.camera_struct(cam))) == 0
         assert L.mod_set_params(self.h, C.byref(capi.params_struct(synth.Params()))) == 0
         self.W, self.H, self.F = W, H, F
         self.min_stride = None
+        self.calls = HostCalls()
+        self.calls.lib, self.calls.h, self.calls.width, self.calls.height = L, self.h, W, H
 
     def run(self, dp, dn, fl, prm):
         """One mod_egomotion_dev call on device tensors -> transforms (F, 7), results (EGO_RESULT_DTYPE), correspondence counts
@@ -51,16 +44,13 @@ class EgoChecked:
         corr = np.zeros((self.F, 9, cap), np.float64)
         cnt = np.zeros(F * prm.hypotheses, np.int32)          # [frames][hypotheses] of this call
         for which, a in ((5, n), (6, corr), (7, cnt)):
-            assert self.L.mod_debug_read(self.h, which, a.ctypes.data, a.nbytes) == 0
+            self.calls.debug_read(which, a)
         cnt = cnt.reshape(F, prm.hypotheses)
         return tf.cpu().numpy(), np.frombuffer(res.cpu().numpy().tobytes(), dtype=EGO_RESULT_DTYPE), n, corr, cnt
 
     def host(self, d_prev, d_now, flow, prm):
         """mod_egomotion_host of one frame of host arrays -> return code, ModTransform bytes, ModEgoResult bytes."""
-        from moving_object_detector_amd import capi
-        ht, hr = capi.ModTransform(), capi.ModEgoResult()
-        arrs = [np.ascontiguousarray(a, np.float32) for a in (d_prev, d_now, flow)]
-        rc = self.L.mod_egomotion_host(self.h, *[a.ctypes.data for a in arrs], C.byref(prm), C.byref(ht), C.byref(hr))
+        rc, ht, hr = self.calls.egomotion_host(*[np.ascontiguousarray(a, np.float32) for a in (d_prev, d_now, flow)], prm)
         return rc, bytes(ht), bytes(hr)
 
     def close(self):

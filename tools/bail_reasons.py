@@ -5,7 +5,7 @@ workload: 2755 / 44 + 3 "class not clear of the one before").  With kMaxClasses 
 slower where it matters (8 pairs: 60 -> 75 us, 64 pairs: 92 -> 110 us; 512 pairs: 0.372 -> 0.363 ms): one wave peeling eight classes
 takes longer than the four-wave union-find kernel takes for the tile.  Not adopted.
 MOD_SF_LIB=.../libmod_sf_bail.so MOD_DEBUG=0 python tools/bail_reasons.py"""
-import ctypes as C, os, sys
+import os, sys
 sys.path.insert(0, os.getcwd())
 import numpy as np, torch
 from moving_object_detector_amd import synth, capi
@@ -18,9 +18,7 @@ for name, kw in (("default stream", {}), ("nominal", dict(synth.NOMINAL))):
     ctx = Context(W, H, max_frames=F); ctx.set_camera(cam); ctx.set_params(synth.Params())
     ws = ctx.workspace(F)
     b = ctx.make_batch(d[1:].contiguous(), d[:-1].contiguous(), torch.from_numpy(sq["flow"]).to(dev), sq["t"], sq["q"], sq["dt"])
-    lib = ctx.lib; lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-    out = (C.c_uint64 * 96)()
-    ctx.process(b, ws); ctx.synchronize(); lib.mod_debug_counters(ctx.h, out)
-    ctx.process(b, ws); ctx.synchronize(); lib.mod_debug_counters(ctx.h, out)
+    ctx.process(b, ws); ctx.synchronize(); ctx.debug_counters()
+    ctx.process(b, ws); ctx.synchronize(); out = ctx.debug_counters()
     print(name, "active tiles", out[58], "bails: > 4 classes", out[52], "| class not clear of the one before, at pass 1 / 2 / 3:", out[54], out[55], out[56], "| > 32 pieces", out[57])
     ctx.close()

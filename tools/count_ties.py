@@ -1,6 +1,6 @@
 """How many clusters of the bench stream take the tie replay (k_median_ties)?  Needs a diagnostic build (mod_debug_read):
 MOD_SF_LIB=$PWD/moving_object_detector_amd/libmod_sf_checked.so python tools/count_ties.py [frames]"""
-import ctypes as C, os, sys
+import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from moving_object_detector_amd import synth, capi
@@ -15,11 +15,9 @@ ctx.set_camera(cam); ctx.set_params(synth.Params())
 ws = ctx.workspace(F)
 b = ctx.make_batch(d[1:][idx].contiguous(), d[:-1][idx].contiguous(), torch.from_numpy(sq["flow"]).to(dev)[idx].contiguous(), sq["t"][idx], sq["q"][idx], sq["dt"][idx])
 ctx.process(b, ws); ctx.synchronize()
-lib = ctx.lib
-lib.mod_debug_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
 MO = ctx.max_objects
 ci = np.zeros((F, MO, 8), np.int32)
-lib.mod_debug_read(ctx.h, 1, ci.ctypes.data, ci.nbytes)
+ctx.debug_read(1, ci)
 K = ws["n_clusters"].cpu().numpy()
 tot = tied = 0
 for f in range(F):

@@ -1,5 +1,5 @@
 """Phase cycle counters of k_ccl_tile (MOD_DEBUG=128). Diagnostic only."""
-import ctypes as C, os, sys
+import os, sys
 os.environ["MOD_DEBUG"] = os.environ.get("MOD_DEBUG", "128")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -14,13 +14,9 @@ ws = ctx.workspace(F)
 dev = ctx.device
 b = ctx.make_batch(torch.from_numpy(host["disparity_now"]).to(dev)[idx].contiguous(), torch.from_numpy(host["disparity_prev"]).to(dev)[idx].contiguous(),
                    torch.from_numpy(host["flow"]).to(dev)[idx].contiguous(), host["t"][idx], host["q"][idx], host["dt"][idx])
-lib = ctx.lib
-lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-out = (C.c_uint64 * 96)()
 for it in range(3):
     ctx.process(b, ws); ctx.synchronize()
-    lib.mod_debug_counters(ctx.h, out)
-    C.cast(out, C.POINTER(C.c_uint64))  # counters reset by the read
+    out = ctx.debug_counters()  # counters reset by the read
     if it < 2:
         pass
 names = ["A load+sync", "runs+sync", "B window tests", "B unions", "sync after B", "C publish", "halo publish", "sync", "D stats"]

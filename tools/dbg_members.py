@@ -1,4 +1,4 @@
-import ctypes as C, sys, os
+import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from moving_object_detector_amd import synth
@@ -11,11 +11,9 @@ ctx=Context(W,H,1); ctx.set_camera(cam); ctx.set_params(prm); ws=ctx.workspace(1
 dev=ctx.device
 b=ctx.make_batch(torch.from_numpy(batch["disparity_now"]).to(dev),torch.from_numpy(batch["disparity_prev"]).to(dev),torch.from_numpy(batch["flow"]).to(dev),batch["t"],batch["q"],batch["dt"])
 ctx.process(b,ws); ctx.synchronize()
-lib=ctx.lib
-lib.mod_debug_read.argtypes=[C.c_void_p,C.c_int,C.c_void_p,C.c_uint64]
 N=W*H
-mb=np.zeros(N,np.uint32); lib.mod_debug_read(ctx.h,0,mb.ctypes.data,mb.nbytes); mp=np.zeros(N,np.uint32); lib.mod_debug_read(ctx.h,4,mp.ctypes.data,mp.nbytes); mem=np.stack([mb,mp],1)
-cl=np.zeros((16,8),np.int32); lib.mod_debug_read(ctx.h,1,cl.ctypes.data,cl.nbytes)
+mb=ctx.debug_read(0,np.zeros(N,np.uint32)); mp=ctx.debug_read(4,np.zeros(N,np.uint32)); mem=np.stack([mb,mp],1)
+cl=ctx.debug_read(1,np.zeros((16,8),np.int32))
 labels=ws["labels"][0].cpu().numpy()
 vx,vy,vz=[ws["planes"][i,0].cpu().numpy() for i in (3,4,5)]
 K=int(ws["n_clusters"][0])

@@ -1,6 +1,6 @@
 """k_median / k_median_ties phase clocks (PHASE_COUNTERS build) on the bench stream + the cluster-size distribution.
 MOD_SF_LIB=.../libmod_sf_pc.so MOD_DEBUG=128 python tools/med_phases.py [frames]"""
-import ctypes as C, os, sys
+import os, sys
 os.environ.setdefault("MOD_DEBUG", "128")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -15,12 +15,9 @@ ctx = Context(W, H, max_frames=F)
 ctx.set_camera(cam); ctx.set_params(synth.Params())
 ws = ctx.workspace(F)
 b = ctx.make_batch(d[1:][idx].contiguous(), d[:-1][idx].contiguous(), torch.from_numpy(sq["flow"]).to(dev)[idx].contiguous(), sq["t"][idx], sq["q"][idx], sq["dt"][idx])
-lib = ctx.lib
-lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-out = (C.c_uint64 * 96)()
 for it in range(3):
     ctx.process(b, ws); ctx.synchronize()
-    lib.mod_debug_counters(ctx.h, out)
+    out = ctx.debug_counters()
 objs = ctx.objects_to_host(ws)
 sizes = np.concatenate([o["n_points"] for o in objs[:G]])
 print("clusters per frame %.2f; sizes: min %d median %d mean %d max %d; share > 8192: %.2f, > 16384: %.2f, > 32768: %.2f" % (

@@ -51,10 +51,7 @@ while time.time() < t_end:
     planes = ws["planes"].cpu().numpy(); labels = ws["labels"].cpu().numpy(); objs = ctx.objects_to_host(ws)
     sflow = ws["static_flow"].cpu().numpy(); nclu = ws["n_clusters"].cpu().numpy()
     if CHECKED:
-        import ctypes as C
-        cnt = (C.c_uint64 * 96)()
-        ctx.lib.mod_debug_counters.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
-        assert ctx.lib.mod_debug_counters(ctx.h, cnt) == 0
+        cnt = ctx.debug_counters()
         bad = {i - 64: int(cnt[i]) for i in range(64, 96) if cnt[i]}
         if bad:
             print("MISMATCH index check (code: count)", bad, dict(W=W, H=H, F=F, seed=seed, prm=prm)); sys.exit(1)

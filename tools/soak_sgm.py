@@ -5,7 +5,7 @@ Every fifth configuration runs independent noise images under penalties at their
 tied minima on most pixels, path costs up to 255); every third one turns the sub-pixel mode and / or the uniqueness test on and is
 compared with tests/models/sgm_filters_model.py on the restatement's path sums.
 usage (GPU box): python tools/soak_sgm.py [seconds] [seed]"""
-import ctypes as C, os, sys, time
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np
@@ -48,8 +48,7 @@ while time.time() < t_end:
     prm = capi.ModSgmParams(D, P1, P2, paths, int(lr), int(med))
     out = torch.full((F, H, W), -7.0, dtype=torch.float32, device=dev)
     tl, tr = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)
-    rc = ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
-    assert rc == 0, ctx.lib.mod_last_error(ctx.h)
+    ctx.estimate_disparity(tl, tr, prm, out)
     ctx.synchronize()
     got = out.cpu().numpy()
     ctx.close()

@@ -84,7 +84,7 @@ def main():
     for name in ("objects", "objects_labels", "objects_host_image"):
         ctx.set_cluster_image(None, host_image=host if name == "objects_host_image" else None)
         lp = labels.ctypes.data if name == "objects_labels" else None
-        call = lambda: ctx.lib.mod_cluster_cloud_host(ctx.h, rec.ctypes.data, W, H, 32, 32 * W, lp, objs, CAP, C.byref(n))
+        call = lambda: ctx.lib.mod_cluster_cloud_host(ctx.h, rec.ctypes.data, W, H, 32, 32 * W, lp, objs, CAP, C.byref(n))   # timed: one object array for every call
         for _ in range(a.warmup):
             assert call() == 0, ctx.lib.mod_last_error(ctx.h)
         t0 = time.perf_counter()

@@ -26,7 +26,7 @@ for use_pinned in ((True,) if ONLY else (False, True)):
         for i in range(0 if ONLY else NF):
             f = i % G
             rc = ctx.lib.mod_process_frame_host(ctx.h, dn[f].ctypes.data, dp[f].ctypes.data, fl[f].ctypes.data, C.byref(tfs[f]), 0.1,
-                                                s.cloud[0].ctypes.data if want_cloud else None, s.labels[0].ctypes.data, s.objects[0], CAP, C.byref(n))
+                                                s.cloud[0].ctypes.data if want_cloud else None, s.labels[0].ctypes.data, s.objects[0], CAP, C.byref(n))   # timed: the stream's own object array, no allocation per call
             assert rc == 0
         sync = NF / max(time.perf_counter() - t0, 1e-9)
         # pipelined

@@ -1,7 +1,7 @@
 """Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
 usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--reps N]
 (--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given)"""
-import argparse, ctypes as C, os, sys, time
+import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -32,11 +32,11 @@ out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
 for paths in (8, 4):
     prm = capi.ModSgmParams(D, 6, 96, paths, 1, 1)
     for _ in range(2):
-        assert ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr()) == 0
+        ctx.estimate_disparity(tl, tr, prm, out)
     ctx.synchronize()
     t0 = time.perf_counter()
     for _ in range(a.reps):
-        ctx.lib.mod_sgm_compute_dev(ctx.h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
+        ctx.estimate_disparity(tl, tr, prm, out)
     ctx.synchronize()
     ms = 1e3 * (time.perf_counter() - t0) / (a.reps * F)
     print(f"{W}x{H} D={D} paths={paths} frames={F} subpixel={'on' if a.subpixel else 'off'}{filters}: {ms:.3f} ms per frame ({1e3 / ms:.0f} frames/s); "

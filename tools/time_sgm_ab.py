@@ -3,8 +3,8 @@
 usage (GPU box): python tools/time_sgm_ab.py TAG [--lib PATH] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--sizes 1280x720,1920x1080] [--frames 16,64] [--seconds 1.5]
 
 The loop is tools/time_sgm.py's (mod_sgm_compute_dev, D = 128, 8 paths, two warm-up calls), timed in three windows of --seconds / 3
-each.  The library is bound here with plain ctypes — only the entry points the loop calls — so that an older build, which lacks newer
-entry points, can be timed against the current one: run the processes alternately (parent, this, parent, this ...) on one box and
+each.  The library is bound here with capi.bind(..., missing_ok=True) and driven without a Context, so that an older build, which
+lacks newer entry points, can be timed against the current one: run the processes alternately (parent, this, parent, this ...) on one box and
 compare the lines.  Line: {"tag", "subpixel", "uniqueness", "speckle", "<W>x<H>_F<frames>": [ms per frame of the three windows], "..._sum": sum of the output
 planes (equal sums: equal work)}.  profiles/sgm_subpixel_time.jsonl and profiles/sgm_filters_time.jsonl were written by it."""
 import argparse, ctypes as C, json, os, sys, time
@@ -25,19 +25,8 @@ ap.add_argument("--seconds", type=float, default=1.5)
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("no HIP device visible: nothing to time")
-vp, i32 = C.c_void_p, C.c_int32
-L = C.CDLL(a.lib)
-L.mod_create.argtypes = [C.POINTER(capi.ModConfig), C.POINTER(vp)]
-L.mod_destroy.argtypes, L.mod_destroy.restype = [vp], None
-L.mod_set_camera.argtypes = [vp, C.POINTER(capi.ModCamera)]
-L.mod_set_params.argtypes = [vp, C.POINTER(capi.ModParams)]
-L.mod_synchronize.argtypes = [vp]
-L.mod_sgm_compute_dev.argtypes = [vp, i32, vp, vp, C.POINTER(capi.ModSgmParams), vp]
-if a.subpixel:
-    L.mod_set_disparity_subpixel.argtypes = [vp, i32]
+L = capi.bind(a.lib, missing_ok=True)   # an older build lacks newer entry points
 filters = capi.ModDisparityFilters(a.uniqueness, a.speckle[0], a.speckle[1], 0)
-if a.uniqueness or a.speckle[0]:
-    L.mod_set_disparity_filters.argtypes = [vp, C.POINTER(capi.ModDisparityFilters)]
 dev = torch.device("cuda", 0)
 res = {"tag": a.tag, "subpixel": bool(a.subpixel), "uniqueness": a.uniqueness, "speckle": list(a.speckle)}
 for size in a.sizes.split(","):
@@ -45,7 +34,7 @@ for size in a.sizes.split(","):
     pairs = [synth.make_stereo_images(W, H, 7 + f, 128, n_boxes=5) for f in range(8)]     # eight distinct pairs, repeated
     Lh, Rh = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
     for F in (int(v) for v in a.frames.split(",")):
-        h = vp()
+        h = C.c_void_p()
         cfg = capi.ModConfig(0, W, H, F, 0, 0, torch.cuda.current_stream(dev).cuda_stream)
         assert L.mod_create(C.byref(cfg), C.byref(h)) == 0
         assert L.mod_set_camera(h, C.byref(capi.camera_struct(synth.make_camera(W, H)))) == 0
@@ -58,7 +47,7 @@ for size in a.sizes.split(","):
         tl, tr = torch.from_numpy(np.concatenate([Lh] * rep)[:F]).to(dev), torch.from_numpy(np.concatenate([Rh] * rep)[:F]).to(dev)
         out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
         prm = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
-        call = lambda: L.mod_sgm_compute_dev(h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())
+        call = lambda: L.mod_sgm_compute_dev(h, F, tl.data_ptr(), tr.data_ptr(), C.byref(prm), out.data_ptr())   # no Context: another build
         for _ in range(2):
             assert call() == 0
         assert L.mod_synchronize(h) == 0

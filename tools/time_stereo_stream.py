@@ -2,7 +2,7 @@
   two calls : mod_sgm_compute_host (disparity to the host) + mod_submit_frame_host (disparity back to the GPU) — round 2's only host-fed path
   one call  : mod_submit_stereo_host — the disparity plane stays in the pipe's ring in HBM
 Pinned host buffers, MOD_PIPELINE_DEPTH frames in flight, labels + objects back (no 32 B/px cloud).  usage (GPU box): python tools/time_stereo_stream.py"""
-import ctypes as C, json, os, sys, time
+import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from moving_object_detector_amd import capi, synth
@@ -36,7 +36,7 @@ for (W, H, NF) in ((1920, 1080, 24), (1280, 720, 40)):
             else:
                 s.make_room()
                 d = disp[i % (capi.MOD_PIPELINE_DEPTH + 1)]
-                assert ctx.lib.mod_sgm_compute_host(ctx.h, left[f].ptr, right[f].ptr, C.byref(sp), d.ptr) == 0
+                assert ctx.disparity_host(left[f], right[f], sp, d)[0] == 0
                 # frame 0 ends at a guard before anything is enqueued, so frame 1 brings its previous disparity along (what the host
                 # mirror's submit() does with its parked copy); from then on the previous plane is resident
                 rc = s.submit_frame(k, d, disp[(i - 1) % (capi.MOD_PIPELINE_DEPTH + 1)] if i == 1 else None, flow[f], tfs[f], dt)
