@@ -43,6 +43,8 @@ MOD_BIN_MEAN, MOD_BIN_NEAREST = 0, 1                     # mod_set_image_binning
 BIN_MODES = {"mean": MOD_BIN_MEAN, "nearest": MOD_BIN_NEAREST}
 MOD_DEPTH_16UC1, MOD_DEPTH_32FC1 = 0, 1                  # REP 118 depth images: uint16 millimetres / float32 metres
 MOD_DEPTH_SPLAT_MAX = 8                                  # targets per axis a footprint of mod_set_depth_splat may paint
+MOD_DEPTH_RAYS_CENTRES, MOD_DEPTH_RAYS_CORNERS = 0, 1    # mod_depth_rays_host: the ray table of the pixel centres / of the pixel corners
+MOD_DEPTH_UNDISTORT_ITERS = 20                           # fixed-point iterations behind every ray of mod_set_depth_distortion
 DEPTH_ENCODINGS = {"16UC1": MOD_DEPTH_16UC1, "32FC1": MOD_DEPTH_32FC1}
 DEPTH_BYTES = {MOD_DEPTH_16UC1: 2, MOD_DEPTH_32FC1: 4}   # bytes per sample
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
@@ -238,6 +240,19 @@ def depth_registration(fx: float, fy: float, cx: float, cy: float, R=(1, 0, 0, 0
     return ModDepthRegistration(float(fx), float(fy), float(cx), float(cy), (C.c_double * 9)(*r), (C.c_double * 3)(*tt))
 
 
+class ModDepthDistortion(C.Structure):
+    _fields_ = [("D", C.c_double * 8)]
+
+
+def depth_distortion(D) -> ModDepthDistortion:
+    """ModDepthDistortion from the D of the depth camera's sensor_msgs/CameraInfo: k1 k2 p1 p2 [k3 [k4 k5 k6]] (four, plumb_bob's five or
+    rational_polynomial's eight coefficients; shorter ones are padded with zeros)."""
+    d = [float(x) for x in D]
+    if len(d) not in (4, 5, 8):
+        raise ValueError("D must have 4, 5 or 8 coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+    return ModDepthDistortion((C.c_double * 8)(*(d + [0.0] * (8 - len(d)))))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -354,6 +369,9 @@ SIGNATURES = {
                               _vp, _vp, _i32, _vp, _vp, C.POINTER(ModTransform), C.POINTER(ModEgoResult), C.POINTER(_i32)],
     "mod_set_depth_splat": [_vp, _i32],
     "mod_get_depth_splat": [_vp, C.POINTER(_i32)],
+    "mod_set_depth_distortion": [_vp, C.POINTER(ModDepthDistortion)],
+    "mod_get_depth_distortion": [_vp, C.POINTER(ModDepthDistortion), C.POINTER(_i32)],
+    "mod_depth_rays_host": [_vp, C.POINTER(ModDepthLayout), _i32, _vp],
     "mod_set_cluster_members": [_vp, C.POINTER(ModClusterMembers)],
     "mod_get_cluster_members": [_vp, C.POINTER(ModClusterMembers), C.POINTER(_i32)],
     "mod_set_cluster_image": [_vp, C.POINTER(ModClusterImage)],

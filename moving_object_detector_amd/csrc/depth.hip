@@ -21,6 +21,11 @@
 // besides its point every sample paints its footprint, the target centres inside the bounding box of its four projected corners
 // (at most MOD_DEPTH_SPLAT_MAX per axis), with the same atomicMin and the same (float)Z.  One lane per sample; the off path's kernel
 // is untouched.
+//
+// k_depth_rays + k_depth_register_rays / k_depth_register_splat_rays (mod_set_depth_distortion, opt-in) are the registered path for a
+// depth camera with a lens: k_depth_rays tabulates the undistorted ray of every pixel centre and pixel corner once per calibration
+// (csrc/depth_rays.h holds the arithmetic), and the two kernels are the two above with X0 = x * Z0, Y0 = y * Z0 from those tables in
+// the pinhole's place.  The host chooses them where it chooses the splat kernel; the kernels above are untouched.
 #include "mod_launch.h"
 
 namespace {
@@ -186,6 +191,94 @@ __global__ __launch_bounds__(kBlock) void k_depth_register_splat(int width, cons
     for (int u = u0; u <= u1; u++) atomicMin(plane + (size_t)v * W + u, zf);
 }
 
+// ---- a depth camera with a lens (mod_set_depth_distortion): the ray tables and the kernels that read them --------------------------
+// One lane per lattice entry (i, j) of a table [rows][cols]: depth_rays::entry at (i + offset, j + offset), straight-line f64 (the
+// iteration is unrolled), one 16-byte store.  Launched once per lattice: offset 0 over width x height (pixel centres), offset -0.5
+// over (width + 1) x (height + 1) (pixel corners).  Runs once per calibration and message size, not per frame.
+__global__ __launch_bounds__(kBlock) void k_depth_rays(depth_rays::Lens lens, double offset, int cols, int rows, double2 *__restrict__ table) {
+  const int i = blockIdx.x * kBlock + threadIdx.x, j = blockIdx.y;
+  if (i >= cols || j >= rows) return;
+  double x, y;
+  depth_rays::entry(lens, (double)i + offset, (double)j + offset, x, y);
+  table[(size_t)j * cols + i] = make_double2(x, y);
+}
+
+// the header's chain with the table's ray in the pinhole's place: X0 = x * Z0, Y0 = y * Z0 (an invalid ray is NaN, and so is its Z)
+__device__ __forceinline__ void ray_to_image_frame(const DepthRegArgs &g, double2 r, double Z0, double &X, double &Y, double &Z) {
+  const double X0 = r.x * Z0, Y0 = r.y * Z0;
+  X = ((g.R[0] * X0 + g.R[1] * Y0) + g.R[2] * Z0) + g.t[0];
+  Y = ((g.R[3] * X0 + g.R[4] * Y0) + g.R[5] * Z0) + g.t[1];
+  Z = ((g.R[6] * X0 + g.R[7] * Y0) + g.R[8] * Z0) + g.t[2];
+}
+
+// k_depth_register with X0, Y0 from the centre table `rays` [height][width]: consecutive lanes are consecutive U of one row, so the
+// ray is one coalesced 16-byte load per lane.  Everything behind X0, Y0 is k_depth_register's, word for word.
+template <int Enc>
+__global__ __launch_bounds__(kBlock) void k_depth_register_rays(int width, const uint8_t *__restrict__ src, size_t frame_bytes, int step, float unit,
+                                                                DepthRegArgs g, const double2 *__restrict__ rays, int W, int H,
+                                                                uint32_t *__restrict__ zbuf) {
+  const int U = blockIdx.x * kBlock + threadIdx.x, V = blockIdx.y, f = blockIdx.z;
+  if (U >= width) return;
+  const float z = sample_z<Enc>(src + (size_t)f * frame_bytes + (size_t)V * step + (size_t)U * kBytes<Enc>, unit);
+  if (!(z > 0.0f && z < __builtin_inff())) return;
+  const double2 r = rays[(size_t)V * width + U];                            // one 16-byte load
+  double X, Y, Z;
+  ray_to_image_frame(g, r, (double)z, X, Y, Z);
+  if (!(Z > 0.0 && Z < __builtin_inf())) return;                            // (an invalid ray has a NaN Z: the sample is dropped here)
+  const double a = ((g.fx * X + g.Tx) / Z + g.cx) + 0.5, b = ((g.fy * Y + g.Ty) / Z + g.cy) + 0.5;
+  if (!(a >= 0.0 && a < (double)W && b >= 0.0 && b < (double)H)) return;   // as doubles, before any conversion (NaN fails)
+  const int ui = (int)floor(a), vi = (int)floor(b);                        // 0 <= ui < W, 0 <= vi < H by the test above
+  atomicMin(zbuf + ((size_t)f * H + vi) * W + ui, __float_as_uint((float)Z));
+}
+
+// k_depth_register_splat with the point's ray from `rays` and the four corner rays from `corners` [height + 1][width + 1]: entries
+// [V][U], [V + 1][U], [V][U + 1], [V + 1][U + 1] are the corners (-,-), (-,+), (+,-), (+,+) of (U, V).  A wave reads two row segments
+// of the corner table, and each entry serves the two lanes on either side of it through the cache.  A footprint with an invalid
+// corner ray is dropped (its Zc is NaN); its point stays.  Everything behind X0, Y0 is k_depth_register_splat's, word for word.
+template <int Enc>
+__global__ __launch_bounds__(kBlock) void k_depth_register_splat_rays(int width, const uint8_t *__restrict__ src, size_t frame_bytes, int step, float unit,
+                                                                      DepthRegArgs g, const double2 *__restrict__ rays,
+                                                                      const double2 *__restrict__ corners, int W, int H, uint32_t *__restrict__ zbuf) {
+  const int U = blockIdx.x * kBlock + threadIdx.x, V = blockIdx.y, f = blockIdx.z;
+  if (U >= width) return;
+  const float z = sample_z<Enc>(src + (size_t)f * frame_bytes + (size_t)V * step + (size_t)U * kBytes<Enc>, unit);
+  if (!(z > 0.0f && z < __builtin_inff())) return;
+  const double Z0 = (double)z;
+  const double2 r = rays[(size_t)V * width + U];                            // one 16-byte load
+  double X, Y, Z;
+  ray_to_image_frame(g, r, Z0, X, Y, Z);
+  if (!positive_finite(Z)) return;                                          // no zf (an invalid ray has a NaN Z): neither point nor footprint
+  const uint32_t zf = __float_as_uint((float)Z);
+  uint32_t *const plane = zbuf + (size_t)f * H * W;
+  // a. the point, as k_depth_register_rays
+  const double a = ((g.fx * X + g.Tx) / Z + g.cx) + 0.5, b = ((g.fy * Y + g.Ty) / Z + g.cy) + 0.5;
+  if (a >= 0.0 && a < (double)W && b >= 0.0 && b < (double)H) atomicMin(plane + (size_t)(int)floor(b) * W + (int)floor(a), zf);
+  // b. the footprint: corners (-,-), (-,+), (+,-), (+,+) of (U, V), all at Z0
+  const double2 *const c0 = corners + (size_t)V * (width + 1) + U, *const c1 = c0 + (width + 1);
+  const double2 cr[4] = {c0[0], c1[0], c0[1], c1[1]};
+  double p[4], q[4];
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    double Xc, Yc, Zc;
+    ray_to_image_frame(g, cr[k], Z0, Xc, Yc, Zc);
+    ok &= positive_finite(Zc);                                                    // (an invalid corner ray fails here)
+    p[k] = (g.fx * Xc + g.Tx) / Zc + g.cx;
+    q[k] = (g.fy * Yc + g.Ty) / Zc + g.cy;
+    ok &= is_finite(p[k]) & is_finite(q[k]);                                      // a non-finite corner makes a non-finite bound (NaN propagates)
+  }
+  if (!ok) return;
+  double ulo = ceil(fmin(fmin(p[0], p[1]), fmin(p[2], p[3]))), uhi = ceil(fmax(fmax(p[0], p[1]), fmax(p[2], p[3]))) - 1.0;
+  double vlo = ceil(fmin(fmin(q[0], q[1]), fmin(q[2], q[3]))), vhi = ceil(fmax(fmax(q[0], q[1]), fmax(q[2], q[3]))) - 1.0;
+  if ((uhi - ulo) + 1.0 > (double)kSplatMax || (vhi - vlo) + 1.0 > (double)kSplatMax) return;   // before clipping: the point alone
+  ulo = fmax(ulo, 0.0); uhi = fmin(uhi, (double)(W - 1));
+  vlo = fmax(vlo, 0.0); vhi = fmin(vhi, (double)(H - 1));
+  if (ulo > uhi || vlo > vhi) return;
+  const int u0 = (int)ulo, u1 = (int)uhi, v0 = (int)vlo, v1 = (int)vhi;       // 0 <= u0 <= u1 < W, 0 <= v0 <= v1 < H, at most kSplatMax apart
+  for (int v = v0; v <= v1; v++)
+    for (int u = u0; u <= u1; u++) atomicMin(plane + (size_t)v * W + u, zf);
+}
+
 // n words of z-buffer -> n disparities, four per lane (16-byte accesses when dst allows; zbuf is the context's own allocation)
 __global__ __launch_bounds__(kBlock) void k_zbuffer_to_disparity(size_t n, const uint32_t *__restrict__ zbuf, float fT, float invalid,
                                                                  float *__restrict__ dst) {
@@ -214,10 +307,18 @@ void launch_plain(int W, int H, int frames, const void *src, size_t frame_bytes,
 
 template <int Enc>
 void launch_register(int W, int H, int frames, const void *src, int width, int height, int step, float unit, const DepthRegArgs &g, bool splat,
-                     uint32_t *zbuf, hipStream_t s) {
+                     const DepthRayTables &rays, uint32_t *zbuf, hipStream_t s) {
   const dim3 grid((unsigned)((width + kBlock - 1) / kBlock), (unsigned)height, (unsigned)frames);
-  const auto kernel = splat ? k_depth_register_splat<Enc> : k_depth_register<Enc>;
-  hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, width, static_cast<const uint8_t *>(src), (size_t)step * height, step, unit, g, W, H, zbuf);
+  const uint8_t *const msg = static_cast<const uint8_t *>(src);
+  const size_t frame_bytes = (size_t)step * height;
+  if (rays.centres && splat) {
+    hipLaunchKernelGGL(k_depth_register_splat_rays<Enc>, grid, dim3(kBlock), 0, s, width, msg, frame_bytes, step, unit, g, rays.centres, rays.corners, W, H, zbuf);
+  } else if (rays.centres) {
+    hipLaunchKernelGGL(k_depth_register_rays<Enc>, grid, dim3(kBlock), 0, s, width, msg, frame_bytes, step, unit, g, rays.centres, W, H, zbuf);
+  } else {
+    const auto kernel = splat ? k_depth_register_splat<Enc> : k_depth_register<Enc>;
+    hipLaunchKernelGGL(kernel, grid, dim3(kBlock), 0, s, width, msg, frame_bytes, step, unit, g, W, H, zbuf);
+  }
 }
 
 }  // namespace
@@ -231,12 +332,19 @@ void launch_depth_to_disparity(int encoding, int W, int H, int frames, const voi
 }
 
 hipError_t launch_depth_register(int encoding, int W, int H, int frames, const void *src, int width, int height, int step, float unit,
-                                 const DepthRegArgs &g, bool splat, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s) {
+                                 const DepthRegArgs &g, bool splat, const DepthRayTables &rays, float fT, float invalid, uint32_t *zbuf,
+                                 float *dst, hipStream_t s) {
+  if (rays.centres && splat && !rays.corners) return hipErrorInvalidValue;   // (the caller builds both tables for the splat)
   const size_t n = (size_t)frames * W * H;
   const hipError_t e = hipMemsetAsync(zbuf, 0xff, 4 * n, s);
   if (e != hipSuccess) return e;
-  if (encoding == MOD_DEPTH_16UC1) launch_register<MOD_DEPTH_16UC1>(W, H, frames, src, width, height, step, unit, g, splat, zbuf, s);
-  else if (encoding == MOD_DEPTH_32FC1) launch_register<MOD_DEPTH_32FC1>(W, H, frames, src, width, height, step, unit, g, splat, zbuf, s);
+  if (encoding == MOD_DEPTH_16UC1) launch_register<MOD_DEPTH_16UC1>(W, H, frames, src, width, height, step, unit, g, splat, rays, zbuf, s);
+  else if (encoding == MOD_DEPTH_32FC1) launch_register<MOD_DEPTH_32FC1>(W, H, frames, src, width, height, step, unit, g, splat, rays, zbuf, s);
   hipLaunchKernelGGL(k_zbuffer_to_disparity, dim3((unsigned)((n + 4 * kBlock - 1) / (4 * kBlock))), dim3(kBlock), 0, s, n, zbuf, fT, invalid, dst);
   return hipSuccess;
+}
+
+hipError_t launch_depth_rays(const depth_rays::Lens &lens, double offset, int cols, int rows, double2 *table, hipStream_t s) {
+  hipLaunchKernelGGL(k_depth_rays, dim3((unsigned)((cols + kBlock - 1) / kBlock), (unsigned)rows), dim3(kBlock), 0, s, lens, offset, cols, rows, table);
+  return hipGetLastError();
 }

@@ -193,18 +193,20 @@ struct StereoFrame {
   ImageIngest img;                   // layout, rectification and side by side as they are at this submit; the slot's stages; grow_for: the grey images
   ModDepthLayout dlay;               // RGB-D: the depth message's layout at this submit, and then the staged copy's
   bool splat;                        // ... and mod_set_depth_splat's setting at this submit
+  DepthRayTables rays;               // ... and mod_set_depth_distortion's tables (null: off)
 };
 
 // what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
-static int rgbd_checks(ModContext *c, ModDepthLayout *dlay) {
+static int rgbd_checks(ModContext *c, ModDepthLayout *dlay, DepthRayTables *rays) {
   if (c->side_by_side) return fail(c, MOD_ERR_INVALID_ARGUMENT, "mod_submit_depth_host takes one image: side by side must be off");
   if (c->rect.on && !c->has_depth_reg)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "a depth image aligned to the raw image cannot be aligned to the rectified one: set a depth registration");
-  return current_depth_layout(c, dlay);
+  if (int rc = current_depth_layout(c, dlay)) return rc;
+  return depth_ray_tables(c, *dlay, c->depth_splat, rays);
 }
 
-static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay, ModDepthLayout *dlay) {
-  if (int rc = rq.rgbd ? rgbd_checks(c, dlay) : MOD_OK) return rc;
+static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay, ModDepthLayout *dlay, DepthRayTables *rays) {
+  if (int rc = rq.rgbd ? rgbd_checks(c, dlay, rays) : MOD_OK) return rc;
   // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276); side by side, left holds both eyes
   if (!rq.left || (rq.rgbd ? !rq.depth : !rq.right && !c->side_by_side)) {
     c->pipe.have_prev = false;      // ... which becomes the next frame's (missing) previous disparity (:397-398)
@@ -283,7 +285,7 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   HIP_TRY(c, f.now.copied_out.wait_once(c->stream));
   if (rq.rgbd) {                    // the depth conversion (depth.hip) in the estimator's place
-    if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.splat, f.s.zbuf, f.now.disparity)) return rc;
+    if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.splat, f.rays, f.s.zbuf, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.depth_read.record(c->stream));
   } else {
     if (int rc = mod_sgm_compute_dev(c, 1, f.img.grey0, f.img.grey1, rq.sgm, f.now.disparity)) return rc;
@@ -316,9 +318,10 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   Pipe::Frame at;
   ModImageLayout lay;
   ModDepthLayout dlay{};
-  int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay); });
+  DepthRayTables rays{nullptr, nullptr};
+  int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay, &rays); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat};
+  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat, rays};
   f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
   f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
   f.img.bin = c->binning; f.img.bin_grey = &f.s.bin_grey;

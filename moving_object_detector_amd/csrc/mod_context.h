@@ -158,6 +158,20 @@ struct ModContext {
   bool has_depth_reg = false;
   bool depth_splat = false;                 // mod_set_depth_splat: the registered path paints footprints (k_depth_register_splat)
   DevPtr<uint32_t> depth_zbuf;              // mod_depth_to_disparity_dev's z-buffer, [max_frames][maxN], allocated on first registered call
+  // mod_set_depth_distortion: the depth camera's lens and, per lattice (MOD_DEPTH_RAYS_*), the ray table in HBM with the lens and the
+  // message size it was built for (ensure_depth_rays builds it at the next use after one of them changed, never over a table that a
+  // frame in flight may read)
+  struct DepthLens {
+    bool on = false;
+    ModDepthDistortion dist{};
+    struct Table {
+      DevPtr<double2> rays;                   // [rows][cols], allocated on first use for the message at hand, grow-only
+      size_t entries = 0;                     // ... its capacity
+      bool valid = false;
+      depth_rays::Lens lens{};
+      int32_t width = 0, height = 0;
+    } table[2];
+  } depth_lens;
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -357,7 +371,13 @@ int ingest_to_grey(ModContext *c, const ImageIngest &in);
 int current_depth_layout(ModContext *c, ModDepthLayout *out);
 // `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,
 // or with a registration in force the scatter through zbuf [frames][W H]
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, uint32_t *zbuf, float *disparity);
+// (rays: depth_ray_tables' at the same call / submit)
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, const DepthRayTables &rays,
+                           uint32_t *zbuf, float *disparity);
+// the ray tables a call / submit of layout `l` reads (mod_set_depth_distortion; both null while it is off): the centre table and, with
+// `splat`, the corner table, built behind the context's stream unless they are the cached ones.  Refused without a registration, and
+// when a table in use would have to be rebuilt while tickets are outstanding
+int depth_ray_tables(ModContext *c, const ModDepthLayout &l, bool splat, DepthRayTables *out);
 
 // estimators.hip
 int check_sgm_params(ModContext *c, const ModSgmParams *p);

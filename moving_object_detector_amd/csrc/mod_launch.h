@@ -3,6 +3,7 @@
 #include "../../include/mod_sf.h"
 #include "mod_device.h"
 #include "label_palette.h"
+#include "depth_rays.h"
 
 struct SfArgs {
   const float *dnow, *dprev, *flow;   // [F][H][W], [F][H][W], [F][H][W][2]
@@ -206,5 +207,15 @@ struct DepthRegArgs { double fxd, fyd, cxd, cyd, R[9], t[3], fx, fy, cx, cy, Tx,
 // the registered path: every sample of the whole width x height messages (frames step * height bytes apart) through g into the
 // z-buffer zbuf [frames][H][W] (cleared here), the nearest sample of every target -> dst as above, targets nothing hit -> `invalid`;
 // splat: every sample paints its footprint too (k_depth_register_splat, mod_set_depth_splat)
+// rays.centres non-null (mod_set_depth_distortion): X0, Y0 come from the depth camera's ray tables instead of the pinhole
+// (k_depth_register_rays, k_depth_register_splat_rays; the splat reads rays.corners too)
+struct DepthRayTables {
+  const double2 *centres;   // [height][width]: the ray of message pixel (U, V); null: no distortion
+  const double2 *corners;   // [height + 1][width + 1]: entry [j][i] is the ray of (i - 0.5, j - 0.5); read by the splat only
+};
 hipError_t launch_depth_register(int encoding, int W, int H, int frames, const void *src, int width, int height, int step, float unit,
-                                 const DepthRegArgs &g, bool splat, float fT, float invalid, uint32_t *zbuf, float *dst, hipStream_t s);
+                                 const DepthRegArgs &g, bool splat, const DepthRayTables &rays, float fT, float invalid, uint32_t *zbuf,
+                                 float *dst, hipStream_t s);
+// k_depth_rays on s: table [rows][cols], entry [j][i] = the ray of lattice point (i + offset, j + offset) of the depth message
+// (offset 0: pixel centres, cols x rows the message's size; offset -0.5: pixel corners, one more per axis)
+hipError_t launch_depth_rays(const depth_rays::Lens &lens, double offset, int cols, int rows, double2 *table, hipStream_t s);

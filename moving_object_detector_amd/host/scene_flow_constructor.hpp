@@ -260,6 +260,10 @@ class SceneFlowConstructor {
     return mod_set_depth_layout(ctx_, &lay) == MOD_OK;
   }
   void setDepthRegistration(const ModDepthRegistration *registration) { check(mod_set_depth_registration(ctx_, registration)); }
+  // a depth camera whose stream is not rectified (an Azure Kinect's depth/image_raw): the D of its CameraInfo, plumb_bob or
+  // rational_polynomial, k1 k2 p1 p2 k3 k4 k5 k6; null = off (the default).  Needs setDepthRegistration(); refused while a distortion is
+  // set and tickets are outstanding, so set it before the first submitDepth()
+  void setDepthDistortion(const ModDepthDistortion *distortion) { check(mod_set_depth_distortion(ctx_, distortion)); }
   // a depth camera of fewer pixels than the image camera (a registration is set): every depth sample fills the image pixels inside its
   // projected footprint instead of one, depth_image_proc/register's fill_upsampling_holes; off by default, read at each submitDepth()
   void setDepthSplat(bool on) { check(mod_set_depth_splat(ctx_, on ? 1 : 0)); }

@@ -338,6 +338,29 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_depth_splat(self.h, C.byref(on)))
         return bool(on.value)
 
+    def set_depth_distortion(self, d: Optional[capi.ModDepthDistortion] = None) -> None:
+        """Lens model of the depth camera (mod_set_depth_distortion, capi.depth_distortion): the registered path back-projects every
+        sample along its undistorted ray, from a table built on the GPU, instead of a pinhole's; None = off (the default).  Needs a
+        registration (aligned cameras: identity pose and the depth intrinsics).  Refused while a distortion is set and tickets are
+        outstanding."""
+        self._check(self.lib.mod_set_depth_distortion(self.h, C.byref(d) if d is not None else None))
+
+    def get_depth_distortion(self):
+        """The ModDepthDistortion in force, or None while it is off."""
+        d, on = capi.ModDepthDistortion(), C.c_int32(-1)
+        self._check(self.lib.mod_get_depth_distortion(self.h, C.byref(d), C.byref(on)))
+        return d if on.value else None
+
+    def depth_rays(self, layout: Optional[capi.ModDepthLayout] = None, lattice: int = capi.MOD_DEPTH_RAYS_CENTRES) -> np.ndarray:
+        """The ray table the registration kernels read (mod_depth_rays_host): (h, w, 2) float64 for the pixel centres of the layout's
+        message (None = the context's), (h + 1, w + 1, 2) for capi.MOD_DEPTH_RAYS_CORNERS, entry [j][i] the ray of (i - 0.5, j - 0.5);
+        NaN where the lens has no inverse.  Synchronises the context's stream."""
+        lay = layout if layout is not None else self.get_depth_layout()
+        k = 1 if int(lattice) == capi.MOD_DEPTH_RAYS_CORNERS else 0
+        out = np.empty((lay.height + k, lay.width + k, 2), np.float64)
+        self._check(self.lib.mod_depth_rays_host(self.h, C.byref(layout) if layout is not None else None, int(lattice), out.ctypes.data))
+        return out
+
     def depth_to_disparity(self, dev: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Disparity planes (F, H, W) float32 at the camera size from device depth messages (mod_depth_to_disparity_dev): `dev` holds F
         messages of layout.step * layout.height bytes each, back to back (any dtype and shape, contiguous); layout None = the context's.

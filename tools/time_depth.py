@@ -5,7 +5,11 @@ image, odometry kind, three frames in flight) in frames/s.  Prints one JSON line
 --splat: the registered path and the depth stream on a depth message of HALF the camera's width and height (the case
 mod_set_depth_splat exists for) with the mode off and on, the two alternating in one process for ROUNDS rounds: every round's figure,
 the median and the spread (largest - smallest) of each.
-Run on the GPU: python tools/time_depth.py [reps] [--splat]"""
+--distorted: a Kinect-like depth camera with a lens (mod_set_depth_distortion: 640 x 576, fx = fy = 504, cx = 320, cy = 330, D = 5.4,
+3.5, -5e-5, 1e-4, 0.18, 5.7, 5.2, 0.95) under the 1280 x 720 camera, with the splat off and on: k_depth_rays per rebuild (a one-frame
+call whose D alternates, so that every call rebuilds its tables, less the same call with the tables cached), the registered path per
+frame with and without the distortion, alternating in one process, and the depth stream in frames/s with and without it.
+Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted]"""
 import ctypes as C
 import functools
 import json
@@ -113,14 +117,74 @@ def kernels_splat(reps):
     ctx.close()
 
 
+KW, KH = 640, 576
+KINECT_D = (5.4, 3.5, -5e-5, 1e-4, 0.18, 5.7, 5.2, 0.95)
+
+
+def kinect_registration(capi):
+    """the Kinect-like depth camera beside the image camera, turned by half a degree"""
+    a = np.radians(0.5)
+    return capi.depth_registration(504.0, 504.0, 320.0, 330.0, [np.cos(a), 0, np.sin(a), 0, 1, 0, -np.sin(a), 0, np.cos(a)], (0.02, 0.0, 0.0))
+
+
+def kernels_distorted(reps):
+    """memset + the registration kernel + k_zbuffer_to_disparity on F 640 x 576 16UC1 messages: pinhole (k_depth_register[_splat])
+    against the ray tables (k_depth_register[_splat]_rays); and what a rebuild of the tables costs"""
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F)
+    cam = synth.make_camera(W, H)
+    ctx.set_camera(cam)
+    ctx.set_depth_registration(kinect_registration(capi))
+    out = torch.empty((F, H, W), dtype=torch.float32, device=ctx.device)
+    rng = np.random.default_rng(0)
+    mm = torch.from_numpy(rng.integers(0, 8000, size=(F, KH, KW)).astype(np.uint16).view(np.int16)).to(ctx.device)
+    lay = capi.depth_layout("16UC1", KW, KH)
+    lens = [capi.depth_distortion(KINECT_D), capi.depth_distortion(tuple(v * 1.01 for v in KINECT_D))]
+    configs = [(d, on) for on in (0, 1) for d in (0, 1)]
+    ms = {c: [] for c in configs}
+    for _ in range(ROUNDS):
+        for d, on in configs:
+            ctx.set_depth_splat(on)
+            ctx.set_depth_distortion(lens[0] if d else None)
+            ms[d, on].append(timed(torch, lambda: ctx.lib.mod_depth_to_disparity_dev(ctx.h, F, mm.data_ptr(), C.byref(lay), out.data_ptr()), reps))
+    for d, on in configs:
+        ctx.set_depth_splat(on)
+        ctx.set_depth_distortion(lens[0] if d else None)
+        assert ctx.lib.mod_depth_to_disparity_dev(ctx.h, 1, mm.data_ptr(), C.byref(lay), out.data_ptr()) == 0
+        ctx.synchronize()
+        print(json.dumps({"what": "registered path, 640 x 576 depth message", "distorted": d, "splat": on, "encoding": "16UC1", "W": W, "H": H,
+                          "frames": F, "ms_per_call": spread(ms[d, on]), "ms_per_frame_median": round(float(np.median(ms[d, on])) / F, 5),
+                          "valid_share_of_frame_0": round(float((out[0] >= 0).float().mean().item()), 4)}), flush=True)
+    # a rebuild: one frame per call; D alternates (every call builds its tables) against D fixed (the tables are cached)
+    turn = [0]
+
+    def one_frame(alternate):
+        if alternate:
+            turn[0] ^= 1
+            ctx.set_depth_distortion(lens[turn[0]])
+        return ctx.lib.mod_depth_to_disparity_dev(ctx.h, 1, mm.data_ptr(), C.byref(lay), out.data_ptr())
+    for on in (0, 1):
+        ctx.set_depth_splat(on)
+        ctx.set_depth_distortion(lens[0])
+        us = {a: [1000.0 * timed(torch, lambda: one_frame(a), reps) for _ in range(ROUNDS)] for a in (False, True)}
+        entries = KW * KH + (on * (KW + 1) * (KH + 1))
+        print(json.dumps({"what": "k_depth_rays, one rebuild", "tables": "centres + corners" if on else "centres", "width": KW, "height": KH,
+                          "table_bytes": 16 * entries, "us_one_frame_call_cached": spread(us[False]), "us_one_frame_call_rebuilding": spread(us[True]),
+                          "us_per_rebuild_median": round(float(np.median(us[True]) - np.median(us[False])), 2)}), flush=True)
+    ctx.close()
+
+
 @functools.lru_cache(maxsize=None)
 def ego_images():
     from moving_object_detector_amd import synth
     return synth.make_ego_images(W, H, seed=1, frames=2)
 
 
-def stream_fps(reps, splat=None):
-    """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on"""
+def stream_fps(reps, splat=None, kinect=None):
+    """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on;
+    kinect 0 / 1: the message is the Kinect-like camera's 640 x 576 instead, without / with its distortion"""
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
@@ -135,13 +199,18 @@ def stream_fps(reps, splat=None):
         ctx.set_depth_registration(half_size_registration(capi, cam))
         ctx.set_depth_layout(capi.depth_layout("16UC1", W // 2, H // 2))
         ctx.set_depth_splat(splat)
+    if kinect is not None:
+        ctx.set_depth_registration(kinect_registration(capi))
+        ctx.set_depth_layout(capi.depth_layout("16UC1", KW, KH))
+        ctx.set_depth_distortion(capi.depth_distortion(KINECT_D) if kinect else None)
     fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
     fp, ep = capi.flow_params(), capi.ego_params()
     pins = []
     for k in (0, 1):
         bgr = np.repeat(m[f"left{k}"][..., None], 3, axis=2)
         mm = np.rint(1000.0 * fT / m[f"disparity{k}"].astype(np.float64)).astype(np.uint16)
-        pins += [ctx.pinned_copy(bgr), ctx.pinned_copy(mm[::2, ::2] if splat is not None else mm)]
+        small = np.ascontiguousarray(mm[:KH, :KW]) if kinect is not None else mm[::2, ::2] if splat is not None else mm
+        pins += [ctx.pinned_copy(bgr), ctx.pinned_copy(small)]
     s = HostStream(ctx, 3, 64, outputs=())
 
     def step(i):
@@ -155,8 +224,19 @@ def stream_fps(reps, splat=None):
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--splat"]
+    args = [a for a in sys.argv[1:] if a not in ("--splat", "--distorted")]
     reps = int(args[0]) if args else 50
+    if "--distorted" in sys.argv[1:]:
+        kernels_distorted(reps)
+        configs = [(d, on) for on in (0, 1) for d in (0, 1)]
+        fps = {c: [] for c in configs}
+        for _ in range(ROUNDS):
+            for d, on in configs:
+                fps[d, on].append(stream_fps(reps, on, d))
+        for d, on in configs:
+            print(json.dumps({"what": "mod_submit_depth_host, 640 x 576 registered depth message", "distorted": d, "splat": on, "image": "bgr8",
+                              "depth": "16UC1", "kind": "odometry", "W": W, "H": H, "frames_per_s": spread(fps[d, on])}), flush=True)
+        return
     if "--splat" in sys.argv[1:]:
         kernels_splat(reps)
         fps = {0: [], 1: []}
