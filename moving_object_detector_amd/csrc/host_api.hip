@@ -1,6 +1,6 @@
 // host_api.hip — the C ABI's host-pointer entry points: the single-frame *_host calls, which stage one frame through device buffers
 // of the context, and the submit / collect stream with its pipe of slots, copy streams and ring of planes.  Host-side only; how a
-// host image becomes grey on the device is host_images.hip's (ImageIngest).
+// host image becomes grey on the device is host_images.hip's (ImageIngest), how a depth message becomes disparity host_depth.hip's.
 #include "mod_context.h"
 
 #include <algorithm>

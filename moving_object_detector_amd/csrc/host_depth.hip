@@ -1,0 +1,230 @@
+// host_depth.hip — the C ABI's depth input, host side (no kernel): depth layouts, the registration, the splat and the distortion
+// settings, the ray-table cache, and the one way of device depth messages to disparity planes (run_depth_to_disparity) with the
+// entry points around them.  The kernels live in depth.hip.
+#include "mod_context.h"
+
+#include <cmath>
+#include <cstring>
+
+static const char kLensNeedsRegistration[] = "a depth distortion needs a depth registration (aligned cameras: R = I, t = 0 and the depth intrinsics)";
+
+// registered: a registration is in force (the whole message is scattered: no window, any message size)
+static int check_depth_layout(ModContext *c, const ModDepthLayout &l, bool registered) {
+  const int B = depth_bytes(l.encoding);
+  if (!B) return fail(c, MOD_ERR_INVALID_ARGUMENT, "unknown depth encoding");
+  if (l.width < 1 || l.height < 1 || l.width > MOD_MAX_WIDTH || l.height > MOD_MAX_WIDTH)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: width and height must be in 1..MOD_MAX_WIDTH");
+  if ((int64_t)l.step < (int64_t)l.width * B || l.step % B) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: step must be a multiple of the sample size and >= width * sample size");
+  if ((int64_t)l.step * l.height > INT32_MAX) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: step * height must be below 2^31");
+  if (!std::isfinite(l.unit) || l.unit < 0.0f) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: unit must be 0 (the REP 118 default) or finite and positive");
+  if (registered) {
+    if (l.x0 || l.y0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: x0 and y0 must be 0 while a depth registration is set (the whole message is registered)");
+  } else if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height) {
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the depth image");
+  }
+  return MOD_OK;
+}
+
+static ModDepthLayout default_depth_layout(const ModContext *c) { return ModDepthLayout{MOD_DEPTH_16UC1, c->dc.W, c->dc.H, 2 * c->dc.W, 0, 0, 0.0f}; }
+
+int current_depth_layout(ModContext *c, ModDepthLayout *out) {
+  *out = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  return check_depth_layout(c, *out, c->has_depth_reg);   // the camera or the registration may have changed since the layout was set
+}
+
+// the layout a call works on: the given one, checked as `registered` says, or the context's
+static int resolve_depth_layout(ModContext *c, const ModDepthLayout *given, bool registered, ModDepthLayout *l) {
+  if (!given) return current_depth_layout(c, l);
+  *l = *given;
+  return check_depth_layout(c, *l, registered);
+}
+
+static depth_rays::Lens depth_lens_of(const ModContext *c) {
+  depth_rays::Lens lens{};
+  for (int i = 0; i < 8; i++) lens.D[i] = c->depth_lens.dist.D[i];
+  lens.fx = c->depth_reg.fx; lens.fy = c->depth_reg.fy; lens.cx = c->depth_reg.cx; lens.cy = c->depth_reg.cy;
+  return lens;
+}
+
+// (callers have checked that a distortion and a registration are set and that lattice is one of the two)
+static int ensure_depth_rays(ModContext *c, const ModDepthLayout &l, int lattice) {
+  ModContext::DepthLens::Table &t = c->depth_lens.table[lattice];
+  const depth_rays::Lens lens = depth_lens_of(c);
+  if (t.valid && t.width == l.width && t.height == l.height && !memcmp(&t.lens, &lens, sizeof lens)) return MOD_OK;
+  if (t.valid && c->pipe.in_flight > 0)   // (a table never built has no reader)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth ray table must be rebuilt while frames are in flight: collect every ticket first");
+  const int cols = l.width + lattice, rows = l.height + lattice;   // corners: one more per axis
+  const size_t need = (size_t)cols * rows;
+  t.valid = false;
+  if (t.entries < need) {          // the old table's readers are on the context's stream
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    t.rays.reset(); t.entries = 0;
+    HIP_TRY(c, dalloc(t.rays, need));
+    t.entries = need;
+  }
+  // No wait: every reader of the old table (the registration kernels, mod_depth_rays_host's copy) and k_depth_rays are enqueued on
+  // the context's stream, in program order.
+  HIP_TRY(c, launch_depth_rays(lens, lattice == MOD_DEPTH_RAYS_CORNERS ? -0.5 : 0.0, cols, rows, t.rays, c->stream));
+  t.lens = lens; t.width = l.width; t.height = l.height;
+  t.valid = true;
+  return MOD_OK;
+}
+
+int depth_ray_tables(ModContext *c, const ModDepthLayout &l, bool splat, DepthRayTables *out) {
+  *out = DepthRayTables{nullptr, nullptr};
+  if (!c->depth_lens.on) return MOD_OK;
+  if (!c->has_depth_reg) return fail(c, MOD_ERR_INVALID_ARGUMENT, kLensNeedsRegistration);
+  if (int rc = ensure_depth_rays(c, l, MOD_DEPTH_RAYS_CENTRES)) return rc;
+  if (int rc = splat ? ensure_depth_rays(c, l, MOD_DEPTH_RAYS_CORNERS) : MOD_OK) return rc;
+  out->centres = c->depth_lens.table[MOD_DEPTH_RAYS_CENTRES].rays;
+  out->corners = splat ? c->depth_lens.table[MOD_DEPTH_RAYS_CORNERS].rays.get() : nullptr;
+  return MOD_OK;
+}
+
+// a distortion is set, tickets are outstanding and a table in use was built for other intrinsics (r) / another message size (l)
+static bool rebuilds_depth_rays(const ModContext *c, const ModDepthRegistration *r, const ModDepthLayout *l) {
+  if (!c->depth_lens.on || c->pipe.in_flight <= 0) return false;
+  for (const ModContext::DepthLens::Table &t : c->depth_lens.table) {
+    if (!t.valid) continue;
+    if (r && (t.lens.fx != r->fx || t.lens.fy != r->fy || t.lens.cx != r->cx || t.lens.cy != r->cy)) return true;
+    if (l && (t.width != l->width || t.height != l->height)) return true;
+  }
+  return false;
+}
+
+int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, const DepthRayTables &rays,
+                           uint32_t *zbuf, float *disparity) {
+  const float unit = l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f;
+  const float invalid = c->dc.dmin - 1.0f;
+  if (c->has_depth_reg) {
+    const ModDepthRegistration &r = c->depth_reg;
+    DepthRegArgs g{};
+    g.fxd = r.fx; g.fyd = r.fy; g.cxd = r.cx; g.cyd = r.cy;
+    for (int i = 0; i < 9; i++) g.R[i] = r.R[i];
+    for (int i = 0; i < 3; i++) g.t[i] = r.t[i];
+    g.fx = c->cam.fx; g.fy = c->cam.fy; g.cx = c->cam.cx; g.cy = c->cam.cy; g.Tx = c->cam.Tx; g.Ty = c->cam.Ty;
+    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, unit, g, splat, rays, c->dc.fT, invalid,
+                                     zbuf, disparity, c->stream));
+  } else {
+    launch_depth_to_disparity(l.encoding, c->dc.W, c->dc.H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, unit, c->dc.fT, invalid,
+                              disparity, c->stream);
+  }
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+extern "C" {
+
+int mod_set_depth_layout(ModContext *c, const ModDepthLayout *l) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (int rc = need_camera(c)) return rc;
+  const ModDepthLayout nl = l ? *l : default_depth_layout(c);
+  if (int rc = check_depth_layout(c, nl, c->has_depth_reg)) return rc;
+  if (rebuilds_depth_rays(c, nullptr, &nl))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "a depth layout of another message size would rebuild the depth ray tables while frames are in flight: collect every ticket first");
+  if (l) c->depth_layout = *l;
+  c->has_depth_layout = l != nullptr;
+  return MOD_OK;
+}
+
+int mod_get_depth_layout(const ModContext *c, ModDepthLayout *l) {
+  if (!c || !l) return MOD_ERR_INVALID_ARGUMENT;
+  if (!c->has_cam) return MOD_ERR_NOT_CONFIGURED;
+  *l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  return MOD_OK;
+}
+
+int mod_set_depth_registration(ModContext *c, const ModDepthRegistration *r) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (r) {
+    for (const double v : {r->fx, r->fy, r->cx, r->cy}) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite intrinsics");
+    for (const double v : r->R) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite entry in R");
+    for (const double v : r->t) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: non-finite entry in t");
+    if (r->fx <= 0.0 || r->fy <= 0.0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: the focal lengths must be positive");
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        const double d = r->R[3 * i] * r->R[3 * j] + r->R[3 * i + 1] * r->R[3 * j + 1] + r->R[3 * i + 2] * r->R[3 * j + 2];
+        if (std::fabs(d - (i == j ? 1.0 : 0.0)) > 1e-6)
+          return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: R is not a rotation (R R^T differs from I by more than 1e-6)");
+      }
+    if (rebuilds_depth_rays(c, r, nullptr))
+      return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: other intrinsics would rebuild the depth ray tables while frames are in flight: collect every ticket first");
+    c->depth_reg = *r;
+  }
+  c->has_depth_reg = r != nullptr;
+  return MOD_OK;
+}
+
+int mod_get_depth_registration(const ModContext *c, ModDepthRegistration *r, int32_t *enabled) {
+  if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
+  *enabled = c->has_depth_reg;
+  if (c->has_depth_reg && r) *r = c->depth_reg;
+  return MOD_OK;
+}
+
+int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth, const ModDepthLayout *layout, float *disparity) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (int rc = need_camera(c)) return rc;
+  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
+  ModDepthLayout l;
+  if (int rc = resolve_depth_layout(c, layout, c->has_depth_reg, &l)) return rc;
+  if (!depth) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity planes");
+  if ((uintptr_t)depth % depth_bytes(l.encoding) || (uintptr_t)disparity % 4)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth must be aligned to its sample size and disparity to 4 bytes");
+  DepthRayTables rays;
+  if (int rc = depth_ray_tables(c, l, c->depth_splat, &rays)) return rc;
+  if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
+  return run_depth_to_disparity(c, frames, depth, l, c->depth_splat, rays, c->depth_zbuf, disparity);
+}
+
+int mod_set_depth_splat(ModContext *c, int32_t on) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (on != 0 && on != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth splat: on must be 0 or 1");
+  c->depth_splat = on != 0;
+  return MOD_OK;
+}
+
+int mod_get_depth_splat(const ModContext *c, int32_t *on) {
+  if (!c || !on) return MOD_ERR_INVALID_ARGUMENT;
+  *on = c->depth_splat;
+  return MOD_OK;
+}
+
+int mod_set_depth_distortion(ModContext *c, const ModDepthDistortion *d) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (d)
+    for (const double v : d->D) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth distortion: non-finite coefficient");
+  if (c->depth_lens.on && c->pipe.in_flight > 0)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth distortion cannot change while frames are in flight: collect every ticket first");
+  if (d) c->depth_lens.dist = *d;
+  c->depth_lens.on = d != nullptr;   // part of each table's key: rebuilt at the next use, behind the context's stream
+  return MOD_OK;
+}
+
+int mod_get_depth_distortion(const ModContext *c, ModDepthDistortion *d, int32_t *enabled) {
+  if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
+  *enabled = c->depth_lens.on;
+  if (c->depth_lens.on && d) *d = c->depth_lens.dist;
+  return MOD_OK;
+}
+
+int mod_depth_rays_host(ModContext *c, const ModDepthLayout *layout, int32_t lattice, double *rays) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (int rc = need_camera(c)) return rc;
+  if (lattice != MOD_DEPTH_RAYS_CENTRES && lattice != MOD_DEPTH_RAYS_CORNERS)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "lattice must be MOD_DEPTH_RAYS_CENTRES or MOD_DEPTH_RAYS_CORNERS");
+  if (!rays) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null rays");
+  if (!c->depth_lens.on) return fail(c, MOD_ERR_NOT_CONFIGURED, "no depth distortion is set");
+  if (!c->has_depth_reg) return fail(c, MOD_ERR_INVALID_ARGUMENT, kLensNeedsRegistration);
+  ModDepthLayout l;
+  if (int rc = resolve_depth_layout(c, layout, true, &l)) return rc;
+  if (int rc = ensure_depth_rays(c, l, lattice)) return rc;
+  const size_t entries = (size_t)(l.width + lattice) * (l.height + lattice);
+  HIP_TRY(c, hipMemcpyAsync(rays, c->depth_lens.table[lattice].rays, sizeof(double2) * entries, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  return MOD_OK;
+}
+
+}  // extern "C"

@@ -1,6 +1,7 @@
 // mod_context.h — the context behind the C ABI and what its host-side files share (internal to libmod_sf.so, not installed):
-// mod_sf.hip (lifecycle, the batched scene-flow / cluster path), estimators.hip (SGM, flow, ego-motion), host_images.hip (image and
-// depth layouts, rectification, the host images' way to grey), host_api.hip (*_host calls).
+// mod_sf.hip (lifecycle, the batched scene-flow / cluster path), estimators.hip (SGM, flow, ego-motion), host_images.hip (image
+// layouts, rectification, the host images' way to grey), host_depth.hip (depth layouts, registration, ray tables, depth to
+// disparity), host_api.hip (*_host calls).
 #pragma once
 #include "../../include/mod_sf.h"
 #include "frame_const.h"
@@ -295,6 +296,10 @@ inline int check_ready(ModContext *c, int frames) {
   return MOD_OK;
 }
 
+inline int need_camera(ModContext *c) {
+  return c->has_cam ? MOD_OK : fail(c, MOD_ERR_NOT_CONFIGURED, "the camera must be set first (the window is the camera's size)");
+}
+
 // construct()'s guards, in its order: nothing is published when an input is missing (scene_flow_constructor.cpp:104,110,122,127,133)
 inline int construct_skip(bool flow, bool prev, bool transform, bool now) {
   if (!flow) return MOD_SKIP_NO_FLOW;
@@ -367,6 +372,8 @@ int ensure_bin_stage(ModContext *c, const ImageIngest &in);
 int ingest_copy(ModContext *c, const ImageIngest &in, const uint8_t *img0, const uint8_t *img1, hipStream_t copy_stream);
 // the kernels, on the context's stream: k_rectify (behind k_bayer_to_mono), k_bayer_to_mono, k_to_mono, then k_bin_mono when binning; none unless in.staged()
 int ingest_to_grey(ModContext *c, const ImageIngest &in);
+
+// host_depth.hip
 // the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
 int current_depth_layout(ModContext *c, ModDepthLayout *out);
 // `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,

@@ -4,11 +4,12 @@ include/mod_sf.h, "A depth camera with a lens"), bit for bit.  TEST INFRASTRUCTU
 Two ray tables, the pixel centres [h][w][2] and the pixel corners [h + 1][w + 1][2] (entry [j][i] = the ray of (i - 0.5, j - 0.5)),
 np.float64 in the header's operation order, one operation at a time; an invalid ray is np.nan in both components (the bit pattern
 0x7ff8000000000000, as the kernel writes it).  The registered path with a distortion set differs from depth_model.register /
-depth_splat_model.register_splat in one place, X0 = x * Z0 and Y0 = y * Z0 with (x, y) from the tables; the z-buffer is theirs."""
+depth_splat_model.register_splat in one place, X0 = x * Z0 and Y0 = y * Z0 with (x, y) from the tables: the scatter is theirs,
+depth_model.zbuffer, given the tables."""
 import numpy as np
 
-from depth_model import EMPTY, samples, valid
-from depth_splat_model import SPLAT_MAX
+import depth_model
+from depth_model import count, zbuffer_to_disparity
 
 ITERS = 20
 TOL = 1.0 / 64
@@ -63,75 +64,20 @@ def rays(D, reg, width, height, lattice=CENTRES, iters=ITERS, residual=False):
     return (table, res) if residual else table
 
 
+
+
 def zbuffer(buf, lay, reg, D, cam, W, H, frames=1, splat=False):
     """(z-buffer uint32 [frames * H * W], counts) of the registered path with distortion D.  counts, over all frames: `invalid_ray`
     valid samples dropped for their ray, `invalid_corner` footprints dropped for a corner ray while their point stayed, `kept` samples
     whose point landed, `painted` footprints painted, `empty` targets nothing reached."""
-    assert lay.x0 == 0 and lay.y0 == 0
-    z = samples(buf, lay, frames)
-    ok = valid(z)
-    fr, V, U = np.nonzero(ok)
-    Z0 = z[ok].astype(f64)
-    R, t = [f64(v) for v in reg.R], [f64(v) for v in reg.t]
-    fx, fy, cx, cy, Tx, Ty = (f64(getattr(cam, k)) for k in ("fx", "fy", "cx", "cy", "Tx", "Ty"))
-    centres = rays(D, reg, lay.width, lay.height, CENTRES)
-
-    def chain(ray):
-        X0, Y0 = ray[:, 0] * Z0, ray[:, 1] * Z0
-        X = ((R[0] * X0 + R[1] * Y0) + R[2] * Z0) + t[0]
-        Y = ((R[3] * X0 + R[4] * Y0) + R[5] * Z0) + t[1]
-        Z = ((R[6] * X0 + R[7] * Y0) + R[8] * Z0) + t[2]
-        return X, Y, Z
-
-    zbuf = np.full(frames * H * W, EMPTY, np.uint32)
-    with np.errstate(all="ignore"):
-        ray = centres[V, U]
-        has_ray = ~np.isnan(ray[:, 0])
-        X, Y, Z = chain(ray)
-        front = has_ray & (Z > 0.0) & np.isfinite(Z)
-        a = ((fx * X + Tx) / Z + cx) + 0.5
-        b = ((fy * Y + Ty) / Z + cy) + 0.5
-        inside = front & (a >= 0.0) & (a < f64(W)) & (b >= 0.0) & (b < f64(H))
-        bits = np.ascontiguousarray(Z.astype(np.float32)).view(np.uint32)
-        ui, vi = np.floor(a[inside]).astype(np.int64), np.floor(b[inside]).astype(np.int64)
-        np.minimum.at(zbuf, (fr[inside] * H + vi) * W + ui, bits[inside])
-        counts = {"invalid_ray": int(np.count_nonzero(~has_ray)), "kept": int(np.count_nonzero(inside)), "invalid_corner": 0, "painted": 0}
-        if splat:
-            corners = rays(D, reg, lay.width, lay.height, CORNERS)
-            p, q, good, all_rays = [], [], np.ones(len(Z0), bool), np.ones(len(Z0), bool)
-            for du in (0, 1):                       # corners (-,-), (-,+), (+,-), (+,+): entries [V][U], [V + 1][U], [V][U + 1], [V + 1][U + 1]
-                for dv in (0, 1):
-                    cr = corners[V + dv, U + du]
-                    all_rays &= ~np.isnan(cr[:, 0])
-                    Xc, Yc, Zc = chain(cr)
-                    good &= (Zc > 0.0) & np.isfinite(Zc)
-                    p.append((fx * Xc + Tx) / Zc + cx)
-                    q.append((fy * Yc + Ty) / Zc + cy)
-            ulo = np.ceil(np.minimum(np.minimum(p[0], p[1]), np.minimum(p[2], p[3])))
-            uhi = np.ceil(np.maximum(np.maximum(p[0], p[1]), np.maximum(p[2], p[3]))) - 1.0
-            vlo = np.ceil(np.minimum(np.minimum(q[0], q[1]), np.minimum(q[2], q[3])))
-            vhi = np.ceil(np.maximum(np.maximum(q[0], q[1]), np.maximum(q[2], q[3]))) - 1.0
-            keep = front & all_rays & good & np.isfinite(ulo) & np.isfinite(uhi) & np.isfinite(vlo) & np.isfinite(vhi)
-            keep &= ~(((uhi - ulo) + 1.0 > f64(SPLAT_MAX)) | ((vhi - vlo) + 1.0 > f64(SPLAT_MAX)))
-            ulo, uhi = np.maximum(ulo, 0.0), np.minimum(uhi, f64(W - 1))
-            vlo, vhi = np.maximum(vlo, 0.0), np.minimum(vhi, f64(H - 1))
-            keep &= ~((ulo > uhi) | (vlo > vhi))
-            counts["invalid_corner"] = int(np.count_nonzero(front & ~all_rays))
-            counts["painted"] = int(np.count_nonzero(keep))
-            u0, u1, v0, v1 = (k[keep].astype(np.int64) for k in (ulo, uhi, vlo, vhi))
-            base, zf = fr[keep] * H, bits[keep]
-            for dv in range(SPLAT_MAX):
-                for du in range(SPLAT_MAX):
-                    m = (u0 + du <= u1) & (v0 + dv <= v1)
-                    np.minimum.at(zbuf, ((base[m] + v0[m] + dv) * W + u0[m] + du), zf[m])
-    counts["empty"] = int(np.count_nonzero(zbuf == EMPTY))
+    tables = rays(D, reg, lay.width, lay.height, CENTRES), rays(D, reg, lay.width, lay.height, CORNERS) if splat else None
+    zbuf, s = depth_model.zbuffer(buf, lay, reg, cam, W, H, frames, splat, tables)
+    counts = {"invalid_ray": count(~s["has_ray"]), "kept": count(s["inside"]), "invalid_corner": count(s["front"], ~s["corner_rays"]) if splat else 0,
+              "painted": count(s["painted"]) if splat else 0, "empty": count(zbuf == depth_model.EMPTY)}
     return zbuf, counts
 
 
 def register(buf, lay, reg, D, cam, W, H, fT, min_disparity, frames=1, splat=False):
     """the registered path with distortion D (and, with splat, the footprints): ([frames][H][W] float32, counts of zbuffer())"""
     zbuf, counts = zbuffer(buf, lay, reg, D, cam, W, H, frames, splat)
-    fT, bad = np.float32(fT), np.float32(min_disparity) - np.float32(1.0)
-    with np.errstate(all="ignore"):
-        d = np.where(zbuf != EMPTY, fT / zbuf.view(np.float32), bad).astype(np.float32)
-    return d.reshape(frames, H, W), counts
+    return zbuffer_to_disparity(zbuf, W, H, fT, min_disparity, frames), counts
