@@ -132,7 +132,10 @@ typedef struct ModSceneFlowPlanes {
                                           moving objects alone passes x = y = NULL, the scene-flow kernel then writes 16 instead of 24
                                           bytes per pixel and the cluster stage recomputes its members' x, y from z (bit-identical) */
   uint64_t *dynamic_mask;  /* optional [frames][H][mod_mask_words(W)]: bit b of word k of a row = pixel 64k+b is dynamic
-                              (calculateDynamicMap, clusterer_nodelet.cpp:40-54) */
+                              (calculateDynamicMap, clusterer_nodelet.cpp:40-54).  The bits of a row's last word at columns >= W
+                              must be 0 in a caller's mask (mod_cluster_dev reads the words whole and takes every set bit for a
+                              pixel of that row: a set bit there addresses memory beyond the row, beyond the planes in the last
+                              one); the library's own masks (mod_scene_flow_dev, mod_process_dev, mod_dynamic_mask_dev) have them 0 */
   void     *cloud_aos;     /* optional [frames][H][W] 32-byte pcl::PointXYZVelocity records
                               (scene_flow_constructor/pcl_point_xyz_velocity.h:8-34: x@0 y@4 z@8 vx@16 vy@20 vz@24) */
   float    *depth;         /* optional ~depth image (disparity_image_processor.cpp:105-120) */

@@ -25,6 +25,11 @@ def _mask_bits(words, W):
     return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=-1, bitorder="little")[..., :W].astype(bool)
 
 
+def _mask_tail(words, W):
+    """the bits at columns W .. 64 mask_words - 1 of every row (no columns when W % 64 == 0)"""
+    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=-1, bitorder="little")[..., W:].astype(bool)
+
+
 def _context(case, frames):
     from moving_object_detector_amd.pipeline import Context
     cam, prm, b = sc.make_case(case.name)
@@ -57,6 +62,9 @@ def _check_velocity_planes(case, planes, mask, keys):
         want = numpy_ref.dynamic_mask(prm, ref["vx"], ref["vy"], ref["vz"])
         got = _mask_bits(mask[f], case.W)
         assert np.array_equal(got, want), (where, "mask", int((got != want).sum()), np.argwhere(got != want)[:4].tolist())
+        # the cluster kernels read mask words whole: the bits of a row's last word at columns >= W are 0
+        tail = _mask_tail(mask[f], case.W)
+        assert not tail.any(), (where, "mask bits at columns >= W", np.argwhere(tail)[:4].tolist())
 
 
 @pytest.mark.parametrize("name", [c.name for c in sc.CASES])
