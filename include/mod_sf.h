@@ -321,7 +321,8 @@ int  mod_unpack_cloud_dev(ModContext *ctx, int32_t frames, const void *cloud_aos
  * parameters and every choice the publication leaves open: oracle/sgm_ref.cpp (semi-global matching: centre-symmetric 9 x 7
  * census, Hamming cost, 8 paths with P1 / P2, winner-take-all, 3 x 3 median, left-right check).  Images are 8-bit, rectified,
  * [frames][H][W] of the configured camera size; the result is the `image` of a stereo_msgs/DisparityImage (32FC1, invalid
- * pixels -1 = min_disparity - 1) whose other fields are f, T of the camera, min_disparity 0, max_disparity disparities - 1 —
+ * pixels -1 = min_disparity - 1) whose other fields are f, T of the camera, min_disparity 0, max_disparity disparities - 1
+ * (with a disparity offset d0, mod_set_disparity_offset below: d0 and d0 + disparities - 1, invalid pixels still -1) —
  * exactly what mod_set_camera takes as disp_f, disp_T, min_disparity, max_disparity
  * (disparity_image_proc/src/disparity_image_processor.cpp:25-27,41-42). */
 #define MOD_SGM_MAX_DISPARITIES 128
@@ -371,6 +372,26 @@ typedef struct ModDisparityFilters {   /* 16 bytes; all zero = off */
 /* NULL = all off.  Out-of-range values and a non-zero `reserved`: MOD_ERR_INVALID_ARGUMENT, and the settings stay as they were. */
 int  mod_set_disparity_filters(ModContext *ctx, const ModDisparityFilters *filters);
 int  mod_get_disparity_filters(const ModContext *ctx, ModDisparityFilters *filters);
+/* Minimum-disparity offset, opt-in (minDisparity of StereoBM / StereoSGBM, min_disparity of stereo_image_proc): context state like
+ * the sub-pixel mode, read when a call or a submit enqueues its estimator (the same five entry points) and by mod_sgm_path_dev; a
+ * frame in flight completes with the offset of its own submit.  0 (the default): the window [0, disparities), the kernels and the
+ * bytes of an estimator without the setting.  d0 in 0..128: index d in [0, disparities) of every volume and map stands for the
+ * disparity d0 + d, the window is [d0, d0 + disparities).  Integer arithmetic as everywhere in the estimator
+ * (tests/models/sgm_offset_model.py restates it bit for bit):
+ *   matching cost   C(x, d) = popcount(cl(x) ^ cr(x - d0 - d)) if x - d0 - d >= 0, else the border cost 31.
+ *   paths           unchanged over d: penalties, the first minimum dl(x) of the summed costs S(x, .), the fraction q, the uniqueness
+ *                   test and the 3 x 3 median with its markers 255 / 65535.
+ *   right map       dr(xr) = the first minimum over d of S(xr + d0 + d, d), taken over the d with xr + d0 + d < W; 0 if there is none.
+ *   left-right      xs = x - d0 - dl(x).  With lr_check on, the pixel is valid iff xs >= 0 and |dr(xs) - dl(x)| <= 1 (the sub-pixel
+ *                   mode checks (v + 8) >> 4 in dl's place); with lr_check off this rule rejects nothing, as without an offset.
+ *   output          d0 + dl(x), or d0 + v / 16 in the sub-pixel mode: exact in float (at most 255.5).  An invalid pixel is -1 WHATEVER
+ *                   d0 is — not min_disparity - 1: a caller whose camera keeps min_disparity 0 never sees a rejected pixel pass as a
+ *                   disparity.  The estimator's speckle stage keeps its rule (>= 0 takes part, removed pixels become -1).
+ *   DisparityImage  min_disparity = d0, max_disparity = d0 + disparities - 1.  The camera (mod_set_camera) is the caller's to set.
+ * An image no wider than d0 is legal: every cost is 31.  Values outside 0..128: MOD_ERR_INVALID_ARGUMENT, and the offset stays as it
+ * was.  MOD_SGM_MAX_DISPARITIES stays the width of the window, not its end. */
+int  mod_set_disparity_offset(ModContext *ctx, int32_t min_disparity);
+int  mod_get_disparity_offset(const ModContext *ctx, int32_t *min_disparity);
 /* The speckle stage alone, in place, on any 32FC1 disparity planes [frames][H][W] of the camera's size (a caller's own matcher):
  * a pixel takes part iff it is finite and >= the camera's min_disparity; removed pixels become min_disparity - 1.  speckle_size 0:
  * nothing to do.  Ordered on the context's stream; scratch (8 bytes per pixel of max_frames frames) is allocated on first use.
@@ -379,7 +400,8 @@ int  mod_disparity_speckle_dev(ModContext *ctx, int32_t frames, float *disparity
 /* stages, for tests and tracing: centre-symmetric census (31 bits per pixel, 0 where the window leaves the image) ... */
 int  mod_sgm_census_dev(ModContext *ctx, int32_t frames, const uint8_t *image, uint32_t *census);
 /* ... and one aggregation path L_r [frames][H][W][disparities] uint8 over the Hamming cost of the census words; direction 0..7 =
- * (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,-1) (-1,+1) (+1,-1).  matching_cost (optional) receives C itself. */
+ * (+1,0) (-1,0) (0,+1) (0,-1) (+1,+1) (-1,-1) (-1,+1) (+1,-1).  matching_cost (optional) receives C itself.  Both are those of
+ * the disparity offset in force (mod_set_disparity_offset). */
 int  mod_sgm_path_dev(ModContext *ctx, int32_t frames, const uint32_t *census_left, const uint32_t *census_right,
                       const ModSgmParams *params, int32_t direction, uint8_t *path_cost, uint8_t *matching_cost);
 

@@ -347,6 +347,8 @@ SIGNATURES = {
     "mod_get_disparity_subpixel": [_vp, C.POINTER(_i32)],
     "mod_set_disparity_filters": [_vp, C.POINTER(ModDisparityFilters)],
     "mod_get_disparity_filters": [_vp, C.POINTER(ModDisparityFilters)],
+    "mod_set_disparity_offset": [_vp, _i32],
+    "mod_get_disparity_offset": [_vp, C.POINTER(_i32)],
     "mod_disparity_speckle_dev": [_vp, _i32, _vp, _i32, _i32],
     "mod_set_flow_propagation": [_vp, _i32],
     "mod_get_flow_propagation": [_vp, C.POINTER(_i32)],

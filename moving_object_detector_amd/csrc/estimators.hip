@@ -80,7 +80,7 @@ static SgmSet sgm_set(const Buffers::Sgm &b, int k, int group, int frames, size_
 }
 
 // census of the group on the context's stream, then its aggregation paths on the side streams
-static int sgm_start(ModContext *c, const ModSgmParams *p, const uint8_t *left, const uint8_t *right, SgmSet &s) {
+static int sgm_start(ModContext *c, const ModSgmParams *p, int off, const uint8_t *left, const uint8_t *right, SgmSet &s) {
   const int W = c->dc.W, H = c->dc.H, D = p->disparities;
   const size_t N = (size_t)W * H;
   const Stream *side = c->b.sgm.side;
@@ -89,26 +89,27 @@ static int sgm_start(ModContext *c, const ModSgmParams *p, const uint8_t *left, 
   HIP_TRY(c, hipEventRecord(s.fork, c->stream));
   // the published configuration: all paths in ONE grid on one side stream (sgm.hip k_sgm_paths_all)
   HIP_TRY(c, hipStreamWaitEvent(side[0], s.fork, 0));
-  if ((s.all_in_one = launch_sgm_paths_all(W, H, s.g, D, p->p1, p->p2, p->paths, s.path_stride, s.cl, s.cr, s.S, side[0]))) {
+  if ((s.all_in_one = launch_sgm_paths_all(W, H, s.g, D, off, p->p1, p->p2, p->paths, s.path_stride, s.cl, s.cr, s.S, side[0]))) {
     HIP_TRY(c, hipEventRecord(s.join[0], side[0]));
     return MOD_OK;
   }
   for (int i = 0; i < p->paths; i++) {   // 4 paths: directions 0 .. 3
     HIP_TRY(c, hipStreamWaitEvent(side[i], s.fork, 0));   // a failed wait would let a path read census planes in flight
-    launch_sgm_path(W, H, s.g, D, p->p1, p->p2, i, s.cl, s.cr, s.S + i * s.path_stride, nullptr, side[i]);
+    launch_sgm_path(W, H, s.g, D, off, p->p1, p->p2, i, s.cl, s.cr, s.S + i * s.path_stride, nullptr, side[i]);
     HIP_TRY(c, hipEventRecord(s.join[i], side[i]));
   }
   return MOD_OK;
 }
 
 // winner-take-all .. left-right check of the group (and the speckle filter) on the context's stream, behind its paths
-static int sgm_finish(ModContext *c, const ModSgmParams *p, const ModDisparityFilters &filters, const SgmSet &s, const SgmMaps &maps, float *disparity) {
+static int sgm_finish(ModContext *c, const ModSgmParams *p, int off, const ModDisparityFilters &filters, const SgmSet &s, const SgmMaps &maps, float *disparity) {
   const int W = c->dc.W, H = c->dc.H;
   float *out = disparity + s.f0 * ((size_t)W * H);
   // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
   for (int i = 0; i < (s.all_in_one ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, s.join[i], 0));
-  launch_sgm_finish(W, H, s.g, p->disparities, p->paths, s.path_stride, p->median, p->lr_check, filters.uniqueness_ratio, s.S, maps, out, c->stream);
-  // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever)
+  launch_sgm_finish(W, H, s.g, p->disparities, off, p->paths, s.path_stride, p->median, p->lr_check, filters.uniqueness_ratio, s.S, maps, out, c->stream);
+  // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever);
+  // invalid pixels are -1 whatever the disparity offset is, so ">= 0 takes part" holds with one
   if (filters.speckle_size > 0)
     launch_speckle(W, H, s.g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, out, c->b.spk.parent, c->b.spk.size, c->b.dbg, c->stream);
   return MOD_OK;
@@ -255,7 +256,9 @@ int mod_sgm_path_dev(ModContext *c, int32_t frames, const uint32_t *census_left,
   if (!census_left || !census_right || !path_cost) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null plane");
   if ((rc = check_sgm_params(c, p))) return rc;
   if (direction < 0 || direction > 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "direction must be 0..7");
-  // (stage entry point, tests and tracing) D == 128: the right plane behind the lead those kernels need (mod_launch.h), in a copy
+  // (stage entry point, tests and tracing) D == 128: the right plane behind the lead those kernels need (mod_launch.h), in a copy;
+  // the lead is zeroed, not "border": the kernels replace what they read there by the border cost
+  const int off = c->sgm_offset;
   const size_t words = (size_t)frames * c->dc.W * c->dc.H;
   DevPtr<uint32_t> padded;
   hipError_t e = hipSuccess;
@@ -265,7 +268,7 @@ int mod_sgm_path_dev(ModContext *c, int32_t frames, const uint32_t *census_left,
     if (e == hipSuccess) e = hipMemcpyAsync(padded + kSgmCensusLead, census_right, words * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream);
   }
   if (e == hipSuccess) {
-    launch_sgm_path(c->dc.W, c->dc.H, frames, p->disparities, p->p1, p->p2, direction, census_left, padded ? padded + kSgmCensusLead : census_right,
+    launch_sgm_path(c->dc.W, c->dc.H, frames, p->disparities, off, p->p1, p->p2, direction, census_left, padded ? padded + kSgmCensusLead : census_right,
                     path_cost, matching_cost, c->stream);
     e = hipGetLastError();
   }
@@ -283,6 +286,7 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   int group = 1;
   const bool subpixel = c->sgm_fraction_bits != 0;       // the setting of THIS call: every kernel below is enqueued before it returns
   const ModDisparityFilters filters = c->sgm_filters;   // ... and so are the filters
+  const int off = c->sgm_offset;                         // ... and the disparity offset
   if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
   if (filters.speckle_size > 0 && (rc = ensure_speckle_scratch(c, group))) return rc;
   const size_t N = (size_t)c->dc.W * c->dc.H;
@@ -294,11 +298,11 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   const int ngroups = (frames + group - 1) / group;
   const SgmMaps maps = sgm_carve_maps(b.maps, N, group, subpixel);
   SgmSet set[2];
-  const auto start = [&](int k) { return sgm_start(c, p, left, right, set[k & 1] = sgm_set(b, k, group, frames, N, p->disparities)); };
+  const auto start = [&](int k) { return sgm_start(c, p, off, left, right, set[k & 1] = sgm_set(b, k, group, frames, N, p->disparities)); };
   if ((rc = start(0))) return rc;
   for (int k = 0; k < ngroups; k++) {
     if (k + 1 < ngroups && (rc = start(k + 1))) return rc;
-    if ((rc = sgm_finish(c, p, filters, set[k & 1], maps, disparity))) return rc;
+    if ((rc = sgm_finish(c, p, off, filters, set[k & 1], maps, disparity))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
@@ -315,6 +319,19 @@ int mod_set_disparity_subpixel(ModContext *c, int32_t fraction_bits) {
 int mod_get_disparity_subpixel(const ModContext *c, int32_t *fraction_bits) {
   if (!c || !fraction_bits) return MOD_ERR_INVALID_ARGUMENT;
   *fraction_bits = c->sgm_fraction_bits;
+  return MOD_OK;
+}
+
+int mod_set_disparity_offset(ModContext *c, int32_t min_disparity) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (min_disparity < 0 || min_disparity > kSgmMaxOffset) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity offset must be in 0..128");
+  c->sgm_offset = min_disparity;
+  return MOD_OK;
+}
+
+int mod_get_disparity_offset(const ModContext *c, int32_t *min_disparity) {
+  if (!c || !min_disparity) return MOD_ERR_INVALID_ARGUMENT;
+  *min_disparity = c->sgm_offset;
   return MOD_OK;
 }
 

@@ -100,14 +100,15 @@ int ccl_request_capacity(int n);     // link requests one tile can emit at neigh
 // on-GPU disparity (sgm.hip)
 constexpr int kSgmPaths = 8;          // aggregation paths at most: the side streams, the join events and the volumes of a set count them
 // words that must be readable in front of a right census plane `cr` when D == 128: the four-lines-per-wave kernels (the only ones for
-// that count) read their census windows unconditionally, up to kSgmCensusLead - 1 words to the left of a row; those words belong to
-// disparities that do not exist and are never used
-constexpr int kSgmCensusLead = 128;
+// that count) read their census windows unconditionally, up to off + 127 <= kSgmCensusLead - 1 words to the left of a row (off: the
+// disparity offset, at most kSgmMaxOffset); those words belong to disparities that do not exist and are never used
+constexpr int kSgmMaxOffset = 128;    // mod_set_disparity_offset's largest value
+constexpr int kSgmCensusLead = kSgmMaxOffset + 128;
 void launch_sgm_census(int W, int H, int frames, const uint8_t *img, uint32_t *out, hipStream_t s);
-// direction: the reference's numbering (sgm.hip kSgmDir)
-void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
+// direction: the reference's numbering (sgm.hip kSgmDir); off: the disparity offset (index d stands for the disparity off + d)
+void launch_sgm_path(int W, int H, int frames, int D, int off, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
                      uint8_t *L, uint8_t *cost, hipStream_t s);
-bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int paths, size_t path_stride, const uint32_t *cl, const uint32_t *cr,
+bool launch_sgm_paths_all(int W, int H, int frames, int D, int off, int P1, int P2, int paths, size_t path_stride, const uint32_t *cl, const uint32_t *cr,
                           uint8_t *L, hipStream_t s);
 
 // The winner-take-all maps of a group and their 3 x 3 medians, [group][N] each, inside one allocation.  The left maps hold d in 8 bits
@@ -125,7 +126,7 @@ inline SgmMaps sgm_carve_maps(uint8_t *base, size_t N, int group, bool subpixel)
   return {base, base + 2 * n, base + n, base + 3 * n, 1};
 }
 // winner-take-all, median, left-right check.  uniqueness: 0 = off, else the ratio in percent (mod_set_disparity_filters)
-void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
+void launch_sgm_finish(int W, int H, int frames, int D, int off, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
                        const SgmMaps &m, float *disparity, hipStream_t s);
 
 // speckle filter (disparity_filter.hip), in place on `disparity` [frames][H][W]: regions (4-connected, neighbours within speckle_range,

@@ -7,6 +7,11 @@
 // every choice the publication leaves open are stated in oracle/sgm_ref.cpp, which these kernels match bit for bit.
 // Kernels: census transform, the eight aggregation paths (matching cost computed on the fly, never stored unless asked),
 // winner-take-all over the summed paths (left and right disparity), 3 x 3 median, left-right check.
+// Disparity offset `off` (mod_set_disparity_offset, 0 .. 128): index d of every volume and map stands for the disparity off + d.  The
+// recurrences over d are untouched; the right census word of (x, d) is word x - off - d (the D == 128 kernels shift the right plane's
+// base by `off` words, the one-line kernels the column), the border is x < off + d, the right map's column is x - off - d, and the
+// left-right kernel adds `off` to what it stores.  off == 0 enqueues the same kernels and gives the same bytes as the estimator
+// without the setting.
 #include "mod_launch.h"
 #include <cstdlib>
 #include <string>
@@ -127,10 +132,12 @@ __device__ __forceinline__ void sgm_emit(const SgmOut &o, const SgmLane &ln, siz
 // (x - d0).  They are read as ONE pair at max(x - d1, 0) — never left of the row (a saturating subtraction) — so near the left
 // border (x < d1) the pair is (word 0, word 1) and the masked branch below picks word 0 for d0 == x.  Needs W >= 2.
 struct SgmPair { uint32_t a, b; };
-// matching costs of the lane's two disparities at column x (31 where the disparity leaves the right image); dlast = D - 1
+// matching costs of the lane's two disparities at column x (31 where the disparity leaves the right image); dlast = D - 1.
+// With a disparity offset the caller passes x - off (the pair was read at max(x - off, 0)): a negative x takes the branch and
+// gets 31 twice
 __device__ __forceinline__ uint32_t sgm_cost_pk(uint32_t wl, SgmPair r, int x, int d0, int dlast) {
   uint32_t c = (uint32_t)__popc(wl ^ r.b) + ((uint32_t)__popc(wl ^ r.a) << 16);
-  if (x <= dlast) {                                                   // wave-uniform: only the first D columns (x == D - 1: an odd D's last
+  if (x <= dlast) {                                                   // wave-uniform: only the first off + D columns (x == D - 1: an odd D's last
                                                                       // lane owns d0 = x alone, its pair was read at word 0 as well)
     asm volatile("" ::: "memory");                                    // keep this a branch: the other columns skip it
     const uint32_t c0 = x > d0 ? (c & 0xffffu) : x == d0 ? (c >> 16) : 31u;
@@ -141,7 +148,7 @@ __device__ __forceinline__ uint32_t sgm_cost_pk(uint32_t wl, SgmPair r, int x, i
 }
 
 template <bool RTL>
-__global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, int P2, const uint32_t *__restrict__ cl,
+__global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int off, int P1, int P2, const uint32_t *__restrict__ cl,
                                                    const uint32_t *__restrict__ cr, SgmOut out) {
   extern __shared__ uint32_t srow[];                 // [W + 1] right census row, [W] left census row
   const int lane = threadIdx.x, y = blockIdx.x, f = blockIdx.y;
@@ -162,7 +169,7 @@ __global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, 
   uint32_t lp = kSgmNone | (kSgmNone << 16);
   // the census words of a step are read one step ahead, unconditionally: their LDS latency hides behind the recurrence of the
   // step before
-  auto pair = [&](int xx) { const uint32_t i = __builtin_elementwise_sub_sat((uint32_t)xx, (uint32_t)d1); SgmPair r; r.a = sr[i]; r.b = sr[i + 1]; return r; };
+  auto pair = [&](int xx) { const uint32_t i = __builtin_elementwise_sub_sat((uint32_t)max(xx - off, 0), (uint32_t)d1); SgmPair r; r.a = sr[i]; r.b = sr[i + 1]; return r; };
   SgmShift sh = sgm_shift_init();
   int x = RTL ? W - 1 : 0;
   uint32_t wl = sl[x];
@@ -171,7 +178,7 @@ __global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, 
     const int xn = min(max(RTL ? x - 1 : x + 1, 0), W - 1);
     const uint32_t wln = sl[xn];
     const SgmPair rn = pair(xn);
-    const uint32_t c = sgm_cost_pk(wl, r, x, d0, dlast);
+    const uint32_t c = sgm_cost_pk(wl, r, x - off, d0, dlast);
     uint32_t l = step > 0 ? sgm_step(lp, c, p1pk, (uint32_t)P2, sh) : c;
     l = (l & ln.keep) | ln.none;
     sgm_emit(out, ln, ((size_t)y * W + x) * D, lane, l, c, even_d, sel);
@@ -187,7 +194,7 @@ __global__ __launch_bounds__(64) void k_sgm_path_h(int W, int H, int D, int P1, 
 // memory round trip per step would dominate it.
 constexpr int kSgmPF = 4;
 template <int RX, int RY>
-__global__ __launch_bounds__(64) void k_sgm_path_line(int W, int H, int D, int P1, int P2, const uint32_t *__restrict__ cl,
+__global__ __launch_bounds__(64) void k_sgm_path_line(int W, int H, int D, int off, int P1, int P2, const uint32_t *__restrict__ cl,
                                                       const uint32_t *__restrict__ cr, SgmOut out) {
   const int lane = threadIdx.x, line = blockIdx.x, f = blockIdx.y;
   int x, y;
@@ -211,7 +218,7 @@ __global__ __launch_bounds__(64) void k_sgm_path_line(int W, int H, int D, int P
     const int k = min(i, len - 1), xx = x + RX * k, yy = y + RY * k;
     const size_t rowp = (size_t)yy * W;
     wl = cl[rowp + xx];
-    const SGM_GLOBAL uint32_t *q = (const SGM_GLOBAL uint32_t *)(sgm_uniform(cr + rowp) + 4u * __builtin_elementwise_sub_sat((uint32_t)xx, (uint32_t)d1));
+    const SGM_GLOBAL uint32_t *q = (const SGM_GLOBAL uint32_t *)(sgm_uniform(cr + rowp) + 4u * __builtin_elementwise_sub_sat((uint32_t)max(xx - off, 0), (uint32_t)d1));
     r.a = q[0]; r.b = q[1];
   };
   uint32_t wl[kSgmPF];
@@ -226,7 +233,7 @@ __global__ __launch_bounds__(64) void k_sgm_path_line(int W, int H, int D, int P
       const int i = i0 + u;
       if (i >= len) break;                           // wave-uniform
       const int xx = x + RX * i, yy = y + RY * i;
-      const uint32_t c = sgm_cost_pk(wl[u], r[u], xx, d0, dlast);
+      const uint32_t c = sgm_cost_pk(wl[u], r[u], xx - off, d0, dlast);
       fetch(i + kSgmPF, wl[u], r[u]);                // slot u is free again: the words of pixel i + kPF
       uint32_t l = i > 0 ? sgm_step(lp, c, p1pk, (uint32_t)P2, sh) : c;
       l = (l & ln.keep) | ln.none;
@@ -254,7 +261,7 @@ typedef uint32_t sgm_u2 __attribute__((ext_vector_type(2)));
 // slot leaves the younger slot's loads outstanding (a conditional store makes it wait for everything).  COST: also emit the
 // matching cost (stage entry point only).
 template <int RX, int RY, bool UNIFORM, bool COST>
-__device__ __forceinline__ void sgm_path_q_body(int W, int H, int P1, int P2, const uint32_t *__restrict__ cl, const uint32_t *__restrict__ cr,
+__device__ __forceinline__ void sgm_path_q_body(int W, int H, int off, int P1, int P2, const uint32_t *__restrict__ cl, const uint32_t *__restrict__ cr,
                                                 SgmOut out, int blk, int f) {
   constexpr int D = 128, kPF = kSgmPrefetch;
   const int lane = threadIdx.x, q = lane >> 4, t = lane & 15;
@@ -274,13 +281,15 @@ __device__ __forceinline__ void sgm_path_q_body(int W, int H, int P1, int P2, co
   const int maxlen = max(max(__builtin_amdgcn_readlane(len, 0), __builtin_amdgcn_readlane(len, 16)),
                          max(__builtin_amdgcn_readlane(len, 32), __builtin_amdgcn_readlane(len, 48)));
   const size_t plane = (size_t)f * H * W, vol = plane * D;
-  SGM_GLOBAL uint8_t *cl_b = sgm_uniform(cl + plane), *cr_b = sgm_uniform(cr + plane);
+  // the right plane's base `off` words early: word x - d of it is the plane's word x - off - d, and every load below stays as it is
+  SGM_GLOBAL uint8_t *cl_b = sgm_uniform(cl + plane), *cr_b = sgm_uniform((cr + plane) - off);
   SGM_GLOBAL uint8_t *outL = sgm_uniform(out.L + vol), *outC = COST ? sgm_uniform(out.C + vol) : nullptr;
   const uint32_t p1pk = (uint32_t)P1 | ((uint32_t)P1 << 16), p2pk = (uint32_t)P2 | ((uint32_t)P2 << 16);
   const int dbase = 8 * t;
   // census words of the line's k-th pixel (clamped to the line): the left word, and the eight right words x - dbase - 7 .. x - dbase
-  // (word j of the window belongs to disparity dbase + 7 - j).  Where a window would start left of the row (x < 127 somewhere in the
-  // wave) every word is fetched on its own at max(x - d, 0): such disparities do not exist and get the border cost below.
+  // of the shifted plane (word j of the window belongs to disparity index dbase + 7 - j).  Where a window starts left of the row
+  // (x < off + 127 somewhere in the wave) the words in front of the row belong to disparities that do not exist: they get the border
+  // cost below, whatever was read.
   struct Slot { uint32_t wl; uint32_t r[8]; };
   auto fetch = [&](int k, Slot &sl) {
     const int kk = max(min(k, len - 1), 0), xx = x + RX * kk, yy = y + RY * kk;
@@ -288,8 +297,8 @@ __device__ __forceinline__ void sgm_path_q_body(int W, int H, int P1, int P2, co
     sl.wl = *(const SGM_GLOBAL uint32_t *)(cl_b + (rowo + (uint32_t)xx * 4u));
     // ALWAYS the same three loads (the compiler can then count them: the wait before a slot's use leaves the younger slot's loads
     // in flight).  Near the left border the window starts left of the row — in the row above, or (first row of the plane) up to
-    // 127 words before the plane: the caller guarantees those bytes are readable; the words read there belong to disparities
-    // that do not exist and are replaced by the border cost.
+    // off + 127 <= kSgmCensusLead - 1 words before the plane: the caller guarantees those bytes are readable; the words read there
+    // belong to disparities that do not exist and are replaced by the border cost.
     const SGM_GLOBAL sgm_u4 *w = (const SGM_GLOBAL sgm_u4 *)(cr_b + (int32_t)(rowo + (uint32_t)(xx - dbase - 7) * 4u));
     const sgm_u4 a = w[0], b = w[1];
     sl.r[0] = a.x; sl.r[1] = a.y; sl.r[2] = a.z; sl.r[3] = a.w; sl.r[4] = b.x; sl.r[5] = b.y; sl.r[6] = b.z; sl.r[7] = b.w;
@@ -310,8 +319,8 @@ __device__ __forceinline__ void sgm_path_q_body(int W, int H, int P1, int P2, co
 #pragma unroll
       for (int j = 0; j < 4; j++)
         c[j] = (uint32_t)__popc(slot[u].wl ^ slot[u].r[7 - 2 * j]) + ((uint32_t)__popc(slot[u].wl ^ slot[u].r[6 - 2 * j]) << 16);
-      if (!__all(xx >= D - 1)) {                        // wave-uniform: only near the left border
-        const int nvalid = xx - dbase + 1;              // disparities dbase .. dbase + nvalid - 1 exist (d <= x)
+      if (!__all(xx >= off + D - 1)) {                  // wave-uniform: only near the left border, the first off + D - 1 columns
+        const int nvalid = xx - off - dbase + 1;        // indices dbase .. dbase + nvalid - 1 exist (off + d <= x)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const uint32_t lo = 2 * j < nvalid ? (c[j] & 0xffffu) : 31u, hi = 2 * j + 1 < nvalid ? (c[j] >> 16) : 31u;
@@ -361,9 +370,9 @@ __device__ __forceinline__ void sgm_path_q_body(int W, int H, int P1, int P2, co
 }
 
 template <int RX, int RY, bool UNIFORM, bool COST>
-__global__ __launch_bounds__(64) void k_sgm_path_q(int W, int H, int P1, int P2, const uint32_t *__restrict__ cl,
+__global__ __launch_bounds__(64) void k_sgm_path_q(int W, int H, int off, int P1, int P2, const uint32_t *__restrict__ cl,
                                                    const uint32_t *__restrict__ cr, SgmOut out) {
-  sgm_path_q_body<RX, RY, UNIFORM, COST>(W, H, P1, P2, cl, cr, out, (int)blockIdx.x, (int)blockIdx.y);
+  sgm_path_q_body<RX, RY, UNIFORM, COST>(W, H, off, P1, P2, cl, cr, out, (int)blockIdx.x, (int)blockIdx.y);
 }
 
 // All aggregation paths of a group of frames in ONE launch: blockIdx.x runs over the four-line blocks of direction 0, then 1, ...
@@ -372,29 +381,29 @@ __global__ __launch_bounds__(64) void k_sgm_path_q(int W, int H, int P1, int P2,
 // trace of round 3) and the short ones queued behind the long ones; inside one grid the dispatcher fills every free wave slot
 // with whatever block is next.  Path i writes its volume at out.L + i * path_stride.
 template <bool UH, bool UV>
-__global__ __launch_bounds__(64) void k_sgm_paths_all(int W, int H, int P1, int P2, int paths, size_t path_stride, const uint32_t *__restrict__ cl,
+__global__ __launch_bounds__(64) void k_sgm_paths_all(int W, int H, int off, int P1, int P2, int paths, size_t path_stride, const uint32_t *__restrict__ cl,
                                                       const uint32_t *__restrict__ cr, uint8_t *__restrict__ L) {
   const int nh = (H + 3) / 4, nv = (W + 3) / 4, nd = (W + H - 1 + 3) / 4;
   int blk = (int)blockIdx.x;
   const int f = (int)blockIdx.y;
   SgmOut o{L, nullptr};
   // numbering of oracle/sgm_ref.cpp: 0 (+1,0) 1 (-1,0) 2 (0,+1) 3 (0,-1) 4 (+1,+1) 5 (-1,-1) 6 (-1,+1) 7 (+1,-1)
-  if (blk < nh) { sgm_path_q_body<1, 0, UH, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nh) { sgm_path_q_body<1, 0, UH, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   blk -= nh; o.L += path_stride;
-  if (blk < nh) { sgm_path_q_body<-1, 0, UH, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nh) { sgm_path_q_body<-1, 0, UH, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   blk -= nh; o.L += path_stride;
-  if (blk < nv) { sgm_path_q_body<0, 1, UV, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nv) { sgm_path_q_body<0, 1, UV, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   blk -= nv; o.L += path_stride;
-  if (blk < nv) { sgm_path_q_body<0, -1, UV, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nv) { sgm_path_q_body<0, -1, UV, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   if (paths <= 4) return;
   blk -= nv; o.L += path_stride;
-  if (blk < nd) { sgm_path_q_body<1, 1, false, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nd) { sgm_path_q_body<1, 1, false, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   blk -= nd; o.L += path_stride;
-  if (blk < nd) { sgm_path_q_body<-1, -1, false, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nd) { sgm_path_q_body<-1, -1, false, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   blk -= nd; o.L += path_stride;
-  if (blk < nd) { sgm_path_q_body<-1, 1, false, false>(W, H, P1, P2, cl, cr, o, blk, f); return; }
+  if (blk < nd) { sgm_path_q_body<-1, 1, false, false>(W, H, off, P1, P2, cl, cr, o, blk, f); return; }
   blk -= nd; o.L += path_stride;
-  sgm_path_q_body<1, -1, false, false>(W, H, P1, P2, cl, cr, o, blk, f);
+  sgm_path_q_body<1, -1, false, false>(W, H, off, P1, P2, cl, cr, o, blk, f);
 }
 
 // Winner-take-all over the sum of the path volumes, one workgroup (4 waves) per image row.  A wave takes every fourth pixel:
@@ -402,7 +411,8 @@ __global__ __launch_bounds__(64) void k_sgm_paths_all(int W, int H, int P1, int 
 //   left  disparity of x : first minimum of S(x, .)              -> DPP minimum over keys (S << 8 | d): the smallest d wins ties
 //   right disparity of x': first minimum of S(x' + d, d), x' + d < W -> the pixel x contributes its S(x, d) to x' = x - d with an LDS
 //                          atomicMin on the same keys (one row of keys in LDS): the cost volume is read ONCE, coalesced, instead of
-//                          gathering a diagonal per pixel
+//                          gathering a diagonal per pixel.  With a disparity offset the column is x' = x - off - d, and a column no pixel
+//                          contributes to (x' + off >= W) gets 0
 //
 // SUB (the sub-pixel mode, mod_set_disparity_subpixel): the left map holds v = 16 d + q, q the vertex of the parabola through
 // S(x, d - 1), S(x, d), S(x, d + 1) in sixteenths (sgm_fraction).  The keys, the reduction and the right map are those of the
@@ -435,7 +445,7 @@ __device__ __forceinline__ bool sgm_ambiguous(uint32_t best, uint32_t second, in
 }
 
 template <bool SUB, class TL, bool UNIQ>
-__global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
+__global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int off, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
                                                  TL *__restrict__ dl, uint8_t *__restrict__ dr, int u) {
   extern __shared__ uint32_t rkey[];                 // [W]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, y = blockIdx.x, f = blockIdx.y;
@@ -467,11 +477,11 @@ __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths,
       if ((uint32_t)lane == (d >> 1))                // the lane that owns the winner
         dl[(size_t)y * W + x] = (TL)(rejected ? kSgmRejected<TL> : (d & 1u) ? sgm_fraction(s0, kl >> 8, above, d, D) : sgm_fraction(below, kl >> 8, s1, d, D));
     }
-    if (d0 < D && x - d0 >= 0) atomicMin(&rkey[x - d0], k0);
-    if (d1 < D && x - d1 >= 0) atomicMin(&rkey[x - d1], k1);
+    if (d0 < D && x - off - d0 >= 0) atomicMin(&rkey[x - off - d0], k0);
+    if (d1 < D && x - off - d1 >= 0) atomicMin(&rkey[x - off - d1], k1);
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < W; i += 256) dr[(size_t)y * W + i] = (uint8_t)(rkey[i] & 255u);
+  for (int i = threadIdx.x; i < W; i += 256) dr[(size_t)y * W + i] = (uint8_t)(rkey[i] == 0xffffffffu ? 0u : rkey[i] & 255u);
 }
 
 // The same for disparity counts that are multiples of 16 (the default 128 is): lane = (pixel of the wave's group of 8, 16 consecutive
@@ -483,7 +493,7 @@ __global__ __launch_bounds__(256) void k_sgm_wta(int W, int H, int D, int paths,
 // UNIQ: as above.  The second minimum runs over the lane's 16 keys again with those next to the winner masked, then through the same
 // three DPP steps; every lane of the pixel holds it, so whichever lane stores the pixel does the one compare.
 template <bool SUB, class TL, bool UNIQ>
-__global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
+__global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int off, int paths, size_t path_stride, const uint8_t *__restrict__ Lv,
                                                    TL *__restrict__ dl, uint8_t *__restrict__ dr, int u) {
   extern __shared__ uint32_t rkey[];                 // [W]
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, y = blockIdx.x, f = blockIdx.y;
@@ -518,7 +528,7 @@ __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int path
       const uint32_t k0 = ((e[j] & 0xffffu) << 8) | d, k1 = ((o[j] & 0xffffu) << 8) | (d + 1), k2 = ((e[j] >> 16) << 8) | (d + 2), k3 = ((o[j] >> 16) << 8) | (d + 3);
       if (live) {
         best = min(best, min(min(k0, k1), min(k2, k3)));
-        const int xr = x - (int)d;
+        const int xr = x - off - (int)d;
         if (xr >= 0) atomicMin(&rkey[xr], k0);
         if (xr >= 1) atomicMin(&rkey[xr - 1], k1);
         if (xr >= 2) atomicMin(&rkey[xr - 2], k2);
@@ -564,7 +574,7 @@ __global__ __launch_bounds__(256) void k_sgm_wta16(int W, int H, int D, int path
     }
   }
   __syncthreads();
-  for (int i = threadIdx.x; i < W; i += 256) dr[(size_t)y * W + i] = (uint8_t)(rkey[i] & 255u);
+  for (int i = threadIdx.x; i < W; i += 256) dr[(size_t)y * W + i] = (uint8_t)(rkey[i] == 0xffffffffu ? 0u : rkey[i] & 255u);
 }
 
 // 3 x 3 median of a uint8 map, or of the sub-pixel mode's uint16 left map (border pixels keep their value): exact 9-element
@@ -585,9 +595,10 @@ __global__ __launch_bounds__(256) void k_sgm_median3(int W, int H, const T *__re
 
 // left-right consistency check -> DisparityImage pixels (float, -1 = invalid).  A uint8 left map stores d itself; the sub-pixel mode's
 // uint16 map stores v = 16 d + q: the check runs on the nearest integer, the pixel leaves as v / 16 (exact).  UNIQ: the marker of a
-// pixel the uniqueness test (or the median of a rejected patch) left is -1 whatever the check says
+// pixel the uniqueness test (or the median of a rejected patch) left is -1 whatever the check says.  off: the disparity offset — the
+// maps hold indices, the matching right column is x - off - d, the pixel leaves as off + its value (exact: at most 255.5)
 template <class TL, bool UNIQ>
-__global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, const TL *__restrict__ dl, const uint8_t *__restrict__ dr,
+__global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int off, int lr_check, const TL *__restrict__ dl, const uint8_t *__restrict__ dr,
                                                 float *__restrict__ disp) {
   const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
   if (x >= W || y >= H) return;
@@ -596,9 +607,10 @@ __global__ __launch_bounds__(256) void k_sgm_lr(int W, int H, int lr_check, cons
   const size_t p = (size_t)y * W + x;
   const int v = dl[p], d = sizeof(TL) == 1 ? v : (v + 8) >> 4;
   bool ok = true;
-  if (lr_check) ok = x - d >= 0 && abs((int)dr[p - min(d, x)] - d) <= 1;
+  const int xs = x - off - d;
+  if (lr_check) ok = xs >= 0 && abs((int)dr[(size_t)y * W + max(xs, 0)] - d) <= 1;
   if (UNIQ && v == (int)kSgmRejected<TL>) ok = false;
-  disp[p] = ok ? (sizeof(TL) == 1 ? (float)d : (float)v * 0.0625f) : -1.0f;
+  disp[p] = ok ? (sizeof(TL) == 1 ? (float)(off + d) : (float)v * 0.0625f + (float)off) : -1.0f;
 }
 
 }  // namespace
@@ -625,7 +637,7 @@ static void with_flags(F &&f, bool flag, B... rest) {
   else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
-void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
+void launch_sgm_path(int W, int H, int frames, int D, int off, int P1, int P2, int direction, const uint32_t *cl, const uint32_t *cr,
                      uint8_t *L, uint8_t *cost, hipStream_t s) {
   SgmOut o{L, cost};
   with_direction(direction, [&](auto dir) {
@@ -635,30 +647,30 @@ void launch_sgm_path(int W, int H, int frames, int D, int P1, int P2, int direct
     // serve every other disparity count
     if (D == 128)
       with_flags([&](auto uniform, auto costs) {
-        hipLaunchKernelGGL((k_sgm_path_q<RX, RY, uniform.value, costs.value>), dim3((lines + 3) / 4, frames), dim3(64), 0, s, W, H, P1, P2, cl, cr, o);
+        hipLaunchKernelGGL((k_sgm_path_q<RX, RY, uniform.value, costs.value>), dim3((lines + 3) / 4, frames), dim3(64), 0, s, W, H, off, P1, P2, cl, cr, o);
       }, (RX == 0 || RY == 0) && (lines & 3) == 0, cost != nullptr);
     else if constexpr (RY == 0)
-      hipLaunchKernelGGL(k_sgm_path_h<(RX < 0)>, dim3(lines, frames), dim3(64), ((size_t)2 * W + 1) * sizeof(uint32_t), s, W, H, D, P1, P2, cl, cr, o);
+      hipLaunchKernelGGL(k_sgm_path_h<(RX < 0)>, dim3(lines, frames), dim3(64), ((size_t)2 * W + 1) * sizeof(uint32_t), s, W, H, D, off, P1, P2, cl, cr, o);
     else
-      hipLaunchKernelGGL((k_sgm_path_line<RX, RY>), dim3(lines, frames), dim3(64), 0, s, W, H, D, P1, P2, cl, cr, o);
+      hipLaunchKernelGGL((k_sgm_path_line<RX, RY>), dim3(lines, frames), dim3(64), 0, s, W, H, D, off, P1, P2, cl, cr, o);
   });
 }
 
 // every path of the published configuration (D == 128) in one grid; returns false when the combination is not covered (other D,
 // other path counts): the caller then launches the paths one by one
-bool launch_sgm_paths_all(int W, int H, int frames, int D, int P1, int P2, int paths, size_t path_stride, const uint32_t *cl, const uint32_t *cr,
+bool launch_sgm_paths_all(int W, int H, int frames, int D, int off, int P1, int P2, int paths, size_t path_stride, const uint32_t *cl, const uint32_t *cr,
                           uint8_t *L, hipStream_t s) {
   if (D != 128 || (paths != 8 && paths != 4)) return false;
   const int nh = (H + 3) / 4, nv = (W + 3) / 4, nd = (W + H - 1 + 3) / 4;
   const dim3 g(2 * nh + 2 * nv + (paths == 8 ? 4 * nd : 0), frames), b(64);
   with_flags([&](auto uh, auto uv) {
-    hipLaunchKernelGGL((k_sgm_paths_all<uh.value, uv.value>), g, b, 0, s, W, H, P1, P2, paths, path_stride, cl, cr, L);
+    hipLaunchKernelGGL((k_sgm_paths_all<uh.value, uv.value>), g, b, 0, s, W, H, off, P1, P2, paths, path_stride, cl, cr, L);
   }, (H & 3) == 0, (W & 3) == 0);
   return true;
 }
 
 // uniqueness: 0 = off (the instantiations without the test), else the ratio u in percent
-void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
+void launch_sgm_finish(int W, int H, int frames, int D, int off, int paths, size_t path_stride, int median, int lr_check, int uniqueness, const uint8_t *Lv,
                        const SgmMaps &m, float *disparity, hipStream_t s) {
   const dim3 g((W + 63) / 64, (H + 3) / 4, frames), b(64, 4), gw(H, frames), bw(256);
   const size_t lds = (size_t)W * sizeof(uint32_t);
@@ -666,12 +678,12 @@ void launch_sgm_finish(int W, int H, int frames, int D, int paths, size_t path_s
   with_flags([&](auto sub, auto uniq, auto by16) {     // sub-pixel mode: 16-bit left maps, the right maps as ever
     using TL = std::conditional_t<sub.value, uint16_t, uint8_t>;
     TL *dl = static_cast<TL *>(m.left), *dlm = static_cast<TL *>(m.left_median);
-    if constexpr (by16.value) hipLaunchKernelGGL((k_sgm_wta16<sub.value, TL, uniq.value>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, dl, m.right, u);
-    else hipLaunchKernelGGL((k_sgm_wta<sub.value, TL, uniq.value>), gw, bw, lds, s, W, H, D, paths, path_stride, Lv, dl, m.right, u);
+    if constexpr (by16.value) hipLaunchKernelGGL((k_sgm_wta16<sub.value, TL, uniq.value>), gw, bw, lds, s, W, H, D, off, paths, path_stride, Lv, dl, m.right, u);
+    else hipLaunchKernelGGL((k_sgm_wta<sub.value, TL, uniq.value>), gw, bw, lds, s, W, H, D, off, paths, path_stride, Lv, dl, m.right, u);
     if (median) {
       hipLaunchKernelGGL(k_sgm_median3<TL>, g, b, 0, s, W, H, dl, dlm);
       hipLaunchKernelGGL(k_sgm_median3<uint8_t>, g, b, 0, s, W, H, m.right, m.right_median);
     }
-    hipLaunchKernelGGL((k_sgm_lr<TL, uniq.value>), g, b, 0, s, W, H, lr_check, median ? dlm : dl, median ? m.right_median : m.right, disparity);
+    hipLaunchKernelGGL((k_sgm_lr<TL, uniq.value>), g, b, 0, s, W, H, off, lr_check, median ? dlm : dl, median ? m.right_median : m.right, disparity);
   }, m.left_bytes == 2, u != 0, D % 16 == 0);
 }

@@ -65,6 +65,11 @@ class SceneFlowConstructor {
   // sub-pixel disparity (mod_set_disparity_subpixel: sixteenths of a pixel); off unless asked for.  Frames already submitted keep
   // the setting of their submit.
   void setDisparitySubpixel(bool on) { check(mod_set_disparity_subpixel(ctx_, on ? MOD_SGM_FRACTION_BITS : 0)); }
+  // minimum disparity of the estimator (mod_set_disparity_offset; stereo_image_proc's min_disparity): the search window becomes
+  // [d0, d0 + disparities), 0 <= d0 <= 128; 0 = off, the default.  estimateDisparity() fills the DisparityImage's min_disparity /
+  // max_disparity accordingly; invalid pixels stay -1.  Throws where the library refuses the value; frames already submitted keep
+  // the offset of their submit.
+  void setDisparityOffset(int d0) { check(mod_set_disparity_offset(ctx_, d0)); disparity_offset_ = d0; }
   // rejection filters of the disparity (mod_set_disparity_filters; stereo_image_proc's names): uniqueness ratio in percent, regions of at
   // most speckle_size pixels whose neighbours differ by at most speckle_range disparities are invalidated; all 0 = off, the default.
   // Frames already submitted keep the settings of their submit.
@@ -111,8 +116,8 @@ class SceneFlowConstructor {
     disparity->data = pixels->data();
     disparity->f = (float)left_camera_info.P[0];
     disparity->T = (float)(-right_camera_info.P[3] / right_camera_info.P[0]);
-    disparity->min_disparity = 0.0f;
-    disparity->max_disparity = (float)(sgm_.disparities - 1);
+    disparity->min_disparity = (float)disparity_offset_;
+    disparity->max_disparity = (float)(disparity_offset_ + sgm_.disparities - 1);
     return true;
   }
 
@@ -448,6 +453,7 @@ class SceneFlowConstructor {
 
   ModContext *ctx_;
   ModSgmParams sgm_{128, 6, 96, 8, 1, 1};   // the published configuration of the estimator (oracle/sgm_ref.cpp)
+  int disparity_offset_ = 0;                // setDisparityOffset(): what the context holds
   ModFlowParams flow_{4, 4, 5, 1, 1};       // include/mod_sf.h defaults
   int image_width_ = 0, image_height_ = 0;
   int max_objects_ = 1024;

@@ -136,6 +136,17 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_disparity_filters(self.h, C.byref(f)))
         return {"uniqueness_ratio": f.uniqueness_ratio, "speckle_size": f.speckle_size, "speckle_range": f.speckle_range}
 
+    def set_disparity_offset(self, d0: int = 0) -> None:
+        """Minimum disparity of the on-GPU disparity estimator (mod_set_disparity_offset): the search window is [d0, d0 + disparities),
+        0 <= d0 <= 128; 0 (the default) = the window starts at 0.  Invalid pixels stay -1.  Read when a call or a submit enqueues its
+        estimator."""
+        self._check(self.lib.mod_set_disparity_offset(self.h, int(d0)))
+
+    def get_disparity_offset(self) -> int:
+        d0 = C.c_int32(-1)
+        self._check(self.lib.mod_get_disparity_offset(self.h, C.byref(d0)))
+        return d0.value
+
     def set_cluster_members(self, ws: Optional[dict]) -> None:
         """Per-cluster member lists (mod_set_cluster_members), off by default: every later cluster() / process() and the synchronous
         host calls write offsets, indices (and points) into the tensors of `ws` (workspace(..., members=True)); None turns them off.

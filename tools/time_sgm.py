@@ -1,6 +1,7 @@
 """Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
-usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--reps N]
-(--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given)"""
+usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--offset N] [--reps N]
+(--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given; --offset:
+mod_set_disparity_offset, the images' disparities then start at N)"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -14,18 +15,24 @@ ap.add_argument("D", type=int, nargs="?", default=128)
 ap.add_argument("--subpixel", action="store_true")
 ap.add_argument("--uniqueness", type=int, default=0, metavar="U", help="uniqueness ratio in percent (0 = off)")
 ap.add_argument("--speckle", type=int, nargs=2, default=(0, 0), metavar=("SIZE", "RANGE"), help="speckle filter (size 0 = off)")
+ap.add_argument("--offset", type=int, default=0, metavar="N", help="minimum disparity: the window is [N, N + D) (0 = off)")
 ap.add_argument("--reps", type=int, default=3)
 a = ap.parse_args()
 W, H, D = a.W, a.H, a.D
 F = int(os.environ.get("SGM_F", "16"))
 pairs = [synth.make_stereo_images(W, H, 7 + f, D, n_boxes=5) for f in range(F)]
+if a.offset:      # the same scenes N px nearer: right(x) = right0(x + N), the columns without a source repeat the last one
+    pairs = [(l, np.ascontiguousarray(r[:, np.minimum(np.arange(W) + a.offset, W - 1)])) for l, r, _ in pairs]
 ctx = Context(W, H, max_frames=F)
 ctx.set_camera(synth.make_camera(W, H)); ctx.set_params(synth.Params())
 if a.subpixel:
     ctx.set_disparity_subpixel(True)
+if a.offset:
+    ctx.set_disparity_offset(a.offset)
 if a.uniqueness or a.speckle[0]:
     ctx.set_disparity_filters(a.uniqueness, a.speckle[0], a.speckle[1])
 filters = f" uniqueness={a.uniqueness} speckle={a.speckle[0]}/{a.speckle[1]}" if a.uniqueness or a.speckle[0] else ""
+filters += f" offset={a.offset}" if a.offset else ""
 dev = ctx.device
 tl = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev); tr = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
 out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
