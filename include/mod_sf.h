@@ -452,6 +452,55 @@ int  mod_flow_compute_host(ModContext *ctx, const uint8_t *prev, const uint8_t *
 int  mod_set_flow_propagation(ModContext *ctx, int32_t seeds);
 int  mod_get_flow_propagation(const ModContext *ctx, int32_t *seeds);
 
+/* ---- texture threshold of the on-GPU estimators ---------------------------------------------------------------------------- */
+/* Opt-in rejection of pixels without image texture, for both estimators above (textureThreshold of StereoBM / stereo_image_proc's
+ * texture_threshold in idea): where the image is flat every census word is the same, every candidate costs the same, and the
+ * winner is decided by tie rules and the smoothness term.  The rule, integers throughout (tests/models/texture_model.py restates it
+ * bit for bit) — for a grey plane I (uint8, W x H), a window w, a cap c and a threshold t:
+ *   g(x, y) = min(|I(min(x + 1, W - 1), y) - I(max(x - 1, 0), y)|, c)      the horizontal central difference, columns CLAMPED
+ *   T(x, y) = sum of g(x + i, y + j) over |i|, |j| <= (w - 1) / 2          window positions outside the image add 0
+ *   rejected(x, y)  iff  T(x, y) < t
+ * T <= 15 * 15 * 255 = 57375 fits a uint16.  Only the horizontal gradient counts: the vertical one says nothing about a horizontal
+ * search.  Positions outside the image add 0, so the border band is rejected more readily; the census words there are 0 in both
+ * images anyway.  The formula is this library's own: it is StereoBM's idea (a sum of capped horizontal gradient magnitudes over the
+ * matching window), and bit parity with OpenCV's Sobel-prefiltered textureThreshold is NOT claimed.
+ *
+ * mod_set_texture_filter: context state like mod_set_disparity_filters, read when a call or a submit enqueues its estimator; a
+ * frame in flight completes with the setting of its own submit, and the setting may change while tickets are outstanding.  NULL or
+ * threshold 0: off (the default) — every entry point enqueues the kernels it always did and writes the same bytes.  With threshold 0
+ * the other fields are still checked.  Out-of-range values, an even window or `apply` outside 1..3: MOD_ERR_INVALID_ARGUMENT, and
+ * the setting stays as it was.
+ *   apply & MOD_TEXTURE_DISPARITY  every entry point that runs the disparity estimator (mod_sgm_compute_dev / _host,
+ *       mod_submit_stereo_host, mod_submit_images_host, mod_submit_odometry_host): behind the left-right check and BEFORE the speckle
+ *       stage (StereoBM's order: a rejected pixel splits regions for the speckle filter), every pixel whose T of the LEFT image is below
+ *       t becomes -1, the estimator's "invalid" whatever the disparity offset is.  The disparity mod_submit_depth_host converts from a
+ *       depth image is not filtered: a depth sensor does not fail on flat surfaces.
+ *   apply & MOD_TEXTURE_FLOW       every entry point that runs the flow estimator (mod_flow_compute_dev / _host, mod_submit_images_host,
+ *       mod_submit_odometry_host, mod_submit_depth_host): behind the finishing step, every pixel whose T of the NOW image (the flow is
+ *       indexed at the now pixel) is below t becomes (NaN, NaN), both words 0x7fc00000 like every other invalid flow pixel. */
+#define MOD_TEXTURE_DISPARITY 1
+#define MOD_TEXTURE_FLOW      2
+typedef struct ModTextureFilter {   /* 16 bytes; NULL or threshold 0: off (the default) */
+  int32_t threshold;                /* 0..57375 */
+  int32_t window;                   /* odd, 3..15 */
+  int32_t cap;                      /* 1..255 */
+  int32_t apply;                    /* MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW, at least one */
+} ModTextureFilter;
+int  mod_set_texture_filter(ModContext *ctx, const ModTextureFilter *filter);
+/* as set; never set, or set with NULL: {0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW} */
+int  mod_get_texture_filter(const ModContext *ctx, ModTextureFilter *filter);
+/* T itself, [frames][H][W] uint16, of grey planes [frames][H][W] of the camera's size: what one looks at to choose a threshold.
+ * filter NULL: the context's; only window and cap are used and checked.  Ordered on the context's stream; keeps no state, needs no
+ * scratch. */
+int  mod_texture_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const ModTextureFilter *filter, uint16_t *texture);
+/* The rule alone, in place, on a caller's own planes (another matcher's output), like mod_disparity_speckle_dev: where T of `grey`
+ * is below the threshold, `disparity` [frames][H][W] becomes the camera's min_disparity - 1 and `flow` [frames][H][W][2] (NaN, NaN).
+ * Either plane may be NULL (the planes given decide, not `apply`, which is checked all the same); both NULL, or a NULL `grey`:
+ * MOD_SKIP_NO_DISPARITY_NOW.  filter NULL: the context's.  threshold 0: nothing is enqueued.  No other pixel of either plane is read
+ * or written. */
+int  mod_texture_reject_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const ModTextureFilter *filter, float *disparity,
+                            float *flow);
+
 /* ---- on-GPU stereo ego-motion ---------------------------------------------------------------------------------------------- */
 /* The reference obtains transform_prev2now_ from libviso2 (VisualOdometryStereo::process + getMotion(),
  * scene_flow_constructor.cpp:214-256), sparse features matched in four images on the CPU.  This estimator is NOT libviso2 and

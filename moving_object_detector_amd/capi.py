@@ -34,6 +34,8 @@ MOD_EGO_OK, MOD_EGO_FEW_POINTS, MOD_EGO_FEW_INLIERS, MOD_EGO_DIVERGED = 0, 1, 2,
 MOD_EGO_MAX_HYPOTHESES = 4096
 MOD_SGM_FRACTION_BITS = 4
 MOD_FLOW_SEEDS = 5
+MOD_TEXTURE_DISPARITY, MOD_TEXTURE_FLOW = 1, 2           # ModTextureFilter.apply: the estimators the texture threshold rejects in
+MOD_TEXTURE_MAX = 15 * 15 * 255                          # the largest texture sum (window 15, cap 255): it fits a uint16
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
 MOD_DISTORTION_RATIONAL, MOD_DISTORTION_EQUIDISTANT = 0, 1   # how ModRectifyCamera.D is read (mod_set_distortion_model)
 DISTORTION_MODELS = {"plumb_bob": MOD_DISTORTION_RATIONAL, "rational_polynomial": MOD_DISTORTION_RATIONAL,
@@ -105,6 +107,16 @@ class ModSgmParams(C.Structure):
 
 class ModDisparityFilters(C.Structure):
     _fields_ = [("uniqueness_ratio", C.c_int32), ("speckle_size", C.c_int32), ("speckle_range", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ModTextureFilter(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("window", C.c_int32), ("cap", C.c_int32), ("apply", C.c_int32)]
+
+
+def texture_filter(threshold: int = 0, window: int = 9, cap: int = 31, apply: int = MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW) -> ModTextureFilter:
+    """ModTextureFilter with the defaults of include/mod_sf.h (threshold 0 = off): T = the window x window sum of the horizontal central
+    differences capped at `cap`; pixels with T < threshold are rejected in the estimators named by `apply`."""
+    return ModTextureFilter(int(threshold), int(window), int(cap), int(apply))
 
 
 class ModFlowParams(C.Structure):
@@ -272,6 +284,7 @@ assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 assert C.sizeof(ModImageBinning) == 16
+assert C.sizeof(ModTextureFilter) == 16
 
 
 def distortion_model(model) -> int:
@@ -352,6 +365,10 @@ SIGNATURES = {
     "mod_disparity_speckle_dev": [_vp, _i32, _vp, _i32, _i32],
     "mod_set_flow_propagation": [_vp, _i32],
     "mod_get_flow_propagation": [_vp, C.POINTER(_i32)],
+    "mod_set_texture_filter": [_vp, C.POINTER(ModTextureFilter)],
+    "mod_get_texture_filter": [_vp, C.POINTER(ModTextureFilter)],
+    "mod_texture_dev": [_vp, _i32, _vp, C.POINTER(ModTextureFilter), _vp],
+    "mod_texture_reject_dev": [_vp, _i32, _vp, C.POINTER(ModTextureFilter), _vp, _vp],
     "mod_set_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)],
     "mod_get_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(_i32)],
     "mod_rectify_dev": [_vp, _i32, _vp, C.POINTER(ModImageLayout), _i32, _vp],

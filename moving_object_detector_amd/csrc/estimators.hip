@@ -1,5 +1,6 @@
 // estimators.hip — the C ABI's on-GPU estimators (SGM disparity, census optical flow, stereo ego-motion): their *_dev entry points
-// and scratch.  Host-side only; the kernels live in sgm.hip, flow.hip and egomotion.hip.
+// and scratch, and the texture threshold both image estimators share.  Host-side only; the kernels live in sgm.hip, flow.hip,
+// egomotion.hip, disparity_filter.hip and texture.hip.
 #include "mod_context.h"
 
 #include <algorithm>
@@ -101,13 +102,37 @@ static int sgm_start(ModContext *c, const ModSgmParams *p, int off, const uint8_
   return MOD_OK;
 }
 
-// winner-take-all .. left-right check of the group (and the speckle filter) on the context's stream, behind its paths
-static int sgm_finish(ModContext *c, const ModSgmParams *p, int off, const ModDisparityFilters &filters, const SgmSet &s, const SgmMaps &maps, float *disparity) {
+// ---- texture filter (texture.hip) ---------------------------------------------------------------------------------------------
+constexpr int kTextureMax = 225 * 255;   // 57375: a 15 x 15 window of differences capped at 255
+
+// window and cap: what the kernel needs; threshold and apply: what the rule and the estimators need
+static int check_texture_kernel(ModContext *c, const ModTextureFilter &f) {
+  if (f.window < 3 || f.window > 15 || f.window % 2 == 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "texture window must be odd and in 3..15");
+  if (f.cap < 1 || f.cap > 255) return fail(c, MOD_ERR_INVALID_ARGUMENT, "texture cap must be in 1..255");
+  return MOD_OK;
+}
+
+static int check_texture_filter(ModContext *c, const ModTextureFilter &f) {
+  if (f.threshold < 0 || f.threshold > kTextureMax) return fail(c, MOD_ERR_INVALID_ARGUMENT, "texture threshold must be in 0..57375");
+  if (int rc = check_texture_kernel(c, f)) return rc;
+  if (f.apply < 1 || f.apply > (MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "texture apply must be MOD_TEXTURE_DISPARITY, MOD_TEXTURE_FLOW or both");
+  return MOD_OK;
+}
+
+static bool texture_applies(const ModTextureFilter &f, int to) { return f.threshold > 0 && (f.apply & to) != 0; }
+
+// winner-take-all .. left-right check of the group (and the texture and speckle filters) on the context's stream, behind its paths
+static int sgm_finish(ModContext *c, const ModSgmParams *p, int off, const ModDisparityFilters &filters, const ModTextureFilter &tex, const uint8_t *left,
+                      const SgmSet &s, const SgmMaps &maps, float *disparity) {
   const int W = c->dc.W, H = c->dc.H;
   float *out = disparity + s.f0 * ((size_t)W * H);
   // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
   for (int i = 0; i < (s.all_in_one ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, s.join[i], 0));
   launch_sgm_finish(W, H, s.g, p->disparities, off, p->paths, s.path_stride, p->median, p->lr_check, filters.uniqueness_ratio, s.S, maps, out, c->stream);
+  // the texture rule on the group's left planes, BEFORE the speckle stage (StereoBM's order: a rejected pixel splits regions)
+  if (texture_applies(tex, MOD_TEXTURE_DISPARITY))
+    launch_texture(W, H, s.g, tex.window, tex.cap, tex.threshold, left + s.f0 * ((size_t)W * H), nullptr, out, -1.0f, nullptr, c->stream);
   // the last stage, behind the group's left-right kernel on the context's stream (the paths of the next group run beside it as ever);
   // invalid pixels are -1 whatever the disparity offset is, so ">= 0 takes part" holds with one
   if (filters.speckle_size > 0)
@@ -287,6 +312,7 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   const bool subpixel = c->sgm_fraction_bits != 0;       // the setting of THIS call: every kernel below is enqueued before it returns
   const ModDisparityFilters filters = c->sgm_filters;   // ... and so are the filters
   const int off = c->sgm_offset;                         // ... and the disparity offset
+  const ModTextureFilter tex = c->texture;               // ... and the texture filter
   if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
   if (filters.speckle_size > 0 && (rc = ensure_speckle_scratch(c, group))) return rc;
   const size_t N = (size_t)c->dc.W * c->dc.H;
@@ -302,7 +328,7 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   if ((rc = start(0))) return rc;
   for (int k = 0; k < ngroups; k++) {
     if (k + 1 < ngroups && (rc = start(k + 1))) return rc;
-    if ((rc = sgm_finish(c, p, off, filters, set[k & 1], maps, disparity))) return rc;
+    if ((rc = sgm_finish(c, p, off, filters, tex, left, set[k & 1], maps, disparity))) return rc;
   }
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
@@ -376,6 +402,43 @@ int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, i
   return MOD_OK;
 }
 
+int mod_set_texture_filter(ModContext *c, const ModTextureFilter *f) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!f) { c->texture = ModContext{}.texture; return MOD_OK; }
+  if (int rc = check_texture_filter(c, *f)) return rc;
+  c->texture = *f;
+  return MOD_OK;
+}
+
+int mod_get_texture_filter(const ModContext *c, ModTextureFilter *f) {
+  if (!c || !f) return MOD_ERR_INVALID_ARGUMENT;
+  *f = c->texture;
+  return MOD_OK;
+}
+
+int mod_texture_dev(ModContext *c, int32_t frames, const uint8_t *grey, const ModTextureFilter *f, uint16_t *texture) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!grey || !texture) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey / texture plane");
+  const ModTextureFilter t = f ? *f : c->texture;
+  if ((rc = check_texture_kernel(c, t))) return rc;
+  launch_texture(c->dc.W, c->dc.H, frames, t.window, t.cap, 0, grey, texture, nullptr, 0.0f, nullptr, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_texture_reject_dev(ModContext *c, int32_t frames, const uint8_t *grey, const ModTextureFilter *f, float *disparity, float *flow) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!grey || (!disparity && !flow)) return MOD_SKIP_NO_DISPARITY_NOW;
+  const ModTextureFilter t = f ? *f : c->texture;
+  if ((rc = check_texture_filter(c, t))) return rc;
+  if (t.threshold == 0) return MOD_OK;
+  launch_texture(c->dc.W, c->dc.H, frames, t.window, t.cap, t.threshold, grey, nullptr, disparity, c->cam.min_disparity - 1.0f, flow, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
 int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, const uint8_t *now, const ModFlowParams *p, float *flow) {
   int rc = check_ready(c, frames);
   if (rc) return rc;
@@ -387,6 +450,7 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   const Buffers::Flow &b = c->b.flow;
   const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
   const int seeds = c->flow_seeds;                       // the setting of THIS call: every kernel below is enqueued before it returns
+  const ModTextureFilter tex = c->texture;               // ... and the texture filter
   const int *const W = lv.W, *const H = lv.H; uint8_t *const img = b.img; uint32_t *const cen = b.census;   // level l >= 1 at img + lv.img[l], level l of the census planes at cen + lv.cen[l]: [2][F][H[l]][W[l]]
   const size_t N = (size_t)W[0] * H[0];
   for (int l = 1; l < L; l++) {
@@ -405,6 +469,8 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
                       coarsest ? nullptr : b.winners + ((l + 1) & 1) * set, b.winners + (l & 1) * set, l == 0 ? sub : nullptr, c->stream);
   }
   launch_flow_finish(W[0], H[0], F, b.winners, dirs == 2 ? b.winners + (size_t)F * N : nullptr, sub, p->fb_check, flow, c->stream);
+  // the texture rule on the NOW image: the flow is indexed at the now pixel
+  if (texture_applies(tex, MOD_TEXTURE_FLOW)) launch_texture(W[0], H[0], F, tex.window, tex.cap, tex.threshold, now, nullptr, nullptr, 0.0f, flow, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -134,6 +134,13 @@ void launch_sgm_finish(int W, int H, int frames, int D, int off, int paths, size
 void launch_speckle(int W, int H, int frames, float lo, float invalid, int speckle_size, int speckle_range, float *disparity,
                     int32_t *parent, int32_t *size, unsigned long long *dbg, hipStream_t s);
 
+// texture measure (texture.hip) of grey planes [frames][H][W]: T = the window x window sum of the horizontal central differences capped
+// at `cap` (window odd in 3..15, cap in 1..255; checked by the caller).  ONE launch: `texture` non-null: T itself into [frames][H][W]
+// uint16; else every pixel with T < threshold becomes `invalid` in `disparity` [frames][H][W] and (NaN, NaN) in `flow` [frames][H][W][2]
+// (either may be null), and nothing else of the two planes is read or written
+void launch_texture(int W, int H, int frames, int window, int cap, int threshold, const uint8_t *grey, uint16_t *texture, float *disparity,
+                    float invalid, float *flow, hipStream_t s);
+
 // on-GPU optical flow (flow.hip).  Pyramid level of both images: src0 / src1 [frames][Hs][Ws] -> dst [2][frames][H][W].
 void launch_flow_pyramid(int Ws, int Hs, int W, int H, int frames, const uint8_t *src0, const uint8_t *src1, uint8_t *dst, hipStream_t s);
 // one level, `dirs` directions (1: forward, 2: + backward); coarse == nullptr: the coarsest level.  census [2][frames][H][W] (prev, now),

@@ -70,6 +70,14 @@ class SceneFlowConstructor {
   // max_disparity accordingly; invalid pixels stay -1.  Throws where the library refuses the value; frames already submitted keep
   // the offset of their submit.
   void setDisparityOffset(int d0) { check(mod_set_disparity_offset(ctx_, d0)); disparity_offset_ = d0; }
+  // texture threshold of the disparity and flow estimators (mod_set_texture_filter; stereo_image_proc's texture_threshold in idea):
+  // pixels whose window x window sum of capped horizontal differences is below `threshold` become invalid in the estimators named by
+  // `apply` (MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW); threshold 0 = off, the default.  Throws where the library refuses a value;
+  // frames already submitted keep the setting of their submit.
+  void setTextureFilter(int threshold, int window = 9, int cap = 31, int apply = MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW) {
+    const ModTextureFilter f{threshold, window, cap, apply};
+    check(mod_set_texture_filter(ctx_, &f));
+  }
   // rejection filters of the disparity (mod_set_disparity_filters; stereo_image_proc's names): uniqueness ratio in percent, regions of at
   // most speckle_size pixels whose neighbours differ by at most speckle_range disparities are invalidated; all 0 = off, the default.
   // Frames already submitted keep the settings of their submit.

@@ -147,6 +147,23 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_disparity_offset(self.h, C.byref(d0)))
         return d0.value
 
+    def set_texture_filter(self, threshold=None, window: int = 9, cap: int = 31,
+                           apply: int = capi.MOD_TEXTURE_DISPARITY | capi.MOD_TEXTURE_FLOW) -> None:   # noqa: A002 (the header's name)
+        """Texture threshold of the on-GPU disparity and flow estimators (mod_set_texture_filter), off by default: pixels whose texture
+        sum T (Context.texture) is below `threshold` become -1 in the disparity / (NaN, NaN) in the flow of the estimators named by
+        `apply`.  No argument or None turns it off; a capi.ModTextureFilter is taken as it is.  Read when a call or a submit enqueues
+        its estimator."""
+        if threshold is None:
+            self._check(self.lib.mod_set_texture_filter(self.h, None))
+            return
+        f = threshold if isinstance(threshold, capi.ModTextureFilter) else capi.texture_filter(threshold, window, cap, apply)
+        self._check(self.lib.mod_set_texture_filter(self.h, C.byref(f)))
+
+    def get_texture_filter(self) -> capi.ModTextureFilter:
+        f = capi.ModTextureFilter(-1, -1, -1, -1)
+        self._check(self.lib.mod_get_texture_filter(self.h, C.byref(f)))
+        return f
+
     def set_cluster_members(self, ws: Optional[dict]) -> None:
         """Per-cluster member lists (mod_set_cluster_members), off by default: every later cluster() / process() and the synchronous
         host calls write offsets, indices (and points) into the tensors of `ws` (workspace(..., members=True)); None turns them off.
@@ -407,6 +424,47 @@ class Context(HostCalls):
             raise ValueError("dev_planes must be a contiguous float32 device tensor (F, H, W) at the camera size")
         self._done(self.lib.mod_disparity_speckle_dev(self.h, p.shape[0], p.data_ptr(), int(size), int(range)), "mod_disparity_speckle_dev")
         return dev_planes
+
+    def _grey_planes(self, grey: torch.Tensor) -> torch.Tensor:
+        g = grey[None] if grey.dim() == 2 else grey
+        if g.dtype != torch.uint8 or not g.is_contiguous() or g.device.type != "cuda" or g.shape[1:] != (self.height, self.width):
+            raise ValueError("grey must be a contiguous uint8 device tensor (F, H, W) at the camera size")
+        return g
+
+    def texture(self, grey: torch.Tensor, filter: Optional[capi.ModTextureFilter] = None,   # noqa: A002 (the header's name)
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The texture sum T of device grey planes (F, H, W) or (H, W) (mod_texture_dev) as uint16 of the same shape: what one looks at to
+        choose a threshold.  filter None = the context's (only window and cap are used).  Enqueued on the context's stream."""
+        g = self._grey_planes(grey)
+        if out is None:
+            out = torch.empty(g.shape, dtype=torch.uint16, device=g.device)
+        elif out.shape not in (g.shape, grey.shape) or out.dtype != torch.uint16 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint16 tensor of grey's shape")
+        self._done(self.lib.mod_texture_dev(self.h, g.shape[0], g.data_ptr(), C.byref(filter) if filter is not None else None, out.data_ptr()),
+                   "mod_texture_dev")
+        return out[0] if grey.dim() == 2 and out.dim() == 3 else out
+
+    def texture_reject(self, grey: Optional[torch.Tensor], disparity: Optional[torch.Tensor] = None, flow: Optional[torch.Tensor] = None,
+                       filter: Optional[capi.ModTextureFilter] = None) -> int:   # noqa: A002
+        """The texture rule alone, in place (mod_texture_reject_dev), on a caller's own device planes: where T of `grey` is below the
+        threshold, `disparity` (F, H, W) float32 becomes the camera's min_disparity - 1 and `flow` (F, H, W, 2) float32 (NaN, NaN); either
+        may be None.  filter None = the context's.  Returns the library's code: 0, or the skip code when there is no grey or no plane."""
+        F = None
+        if grey is not None:
+            grey = self._grey_planes(grey)
+            F = grey.shape[0]
+        for name, t, tail in (("disparity", disparity, ()), ("flow", flow, (2,))):
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device.type != "cuda" or t.shape[-len(tail) - 2:] != (self.height, self.width) + tail:
+                raise ValueError(f"{name} must be a contiguous float32 device tensor (F, H, W{', 2' if tail else ''}) at the camera size")
+            n = t.numel() // (self.height * self.width * (2 if tail else 1))
+            if F is not None and n != F:
+                raise ValueError(f"{name} must hold as many frames as grey")
+            F = n if F is None else F
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        return self._check(self.lib.mod_texture_reject_dev(self.h, F or 1, ptr(grey), C.byref(filter) if filter is not None else None,
+                                                           ptr(disparity), ptr(flow)))
 
     def pinned_copy(self, array) -> "PinnedBuffer":
         """A copy of `array` in page-locked host memory (mod_host_malloc): .ptr, .nbytes, .array (a numpy view of the copy); the submit

@@ -1,7 +1,9 @@
 """HIP-event timing of the on-GPU optical flow: mod_flow_compute_dev (default parameters, forward-backward check on) at 1280 x 720 and
 1920 x 1080 for 1 and 8 frames, and the images stream (mod_submit_images_host: SGM disparity + flow + scene flow + clustering per
 frame, three frames in flight) in frames/s.  Prints one JSON line per measurement.  Run on the GPU:
-    python tools/time_flow.py [REPS] [--seeds N]        (--seeds 5: mod_set_flow_propagation(5); 1, the default, never calls it)"""
+    python tools/time_flow.py [REPS] [--seeds N] [--texture T]
+(--seeds 5: mod_set_flow_propagation(5); 1, the default, never calls it.  --texture T: mod_set_texture_filter(T) with the default window
+and cap, for the flow and, in the stream, the disparity; 0, the default, never calls it)"""
 import argparse
 import json
 import os
@@ -21,8 +23,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("reps", nargs="?", type=int, default=50)
     ap.add_argument("--seeds", type=int, default=1, metavar="N", help="mod_set_flow_propagation: 1 (off) or 5")
+    ap.add_argument("--texture", type=int, default=0, metavar="T", help="mod_set_texture_filter: the threshold (0 = off)")
     args = ap.parse_args()
-    reps, seeds = args.reps, args.seeds
+    reps, seeds, texture = args.reps, args.seeds, args.texture
     prm = capi.flow_params()
     for W, H in ((1280, 720), (1920, 1080)):
         m = synth.make_moving_images(W, H, seed=1, n_boxes=4)
@@ -32,6 +35,8 @@ def main():
             ctx.set_params(synth.Params())
             if seeds != 1:
                 ctx.set_flow_propagation(seeds)
+            if texture:
+                ctx.set_texture_filter(texture)
             dev = ctx.device
             tp = torch.from_numpy(np.stack([m["left0"]] * F)).to(dev)
             tn = torch.from_numpy(np.stack([m["left1"]] * F)).to(dev)
@@ -47,7 +52,7 @@ def main():
             b.record()
             b.synchronize()
             ms = a.elapsed_time(b) / reps
-            print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "seeds": seeds, "ms_per_call": round(ms, 4),
+            print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "seeds": seeds, "texture": texture, "ms_per_call": round(ms, 4),
                               "ms_per_frame": round(ms / F, 4)}), flush=True)
             ctx.close()
         # the images stream
@@ -58,6 +63,8 @@ def main():
         ctx.set_params(synth.Params())
         if seeds != 1:
             ctx.set_flow_propagation(seeds)
+        if texture:
+            ctx.set_texture_filter(texture)
         sp = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
         tf = capi.transforms_array(np.zeros((1, 3)), np.array([[0.0, 0.0, 0.0, 1.0]]))
         pins = [ctx.pinned_copy(m[k]) for k in ("left0", "right0", "left1", "right1")]
@@ -69,7 +76,7 @@ def main():
 
         frames = max(20, reps)
         fps = stream_rate(s, step, frames)
-        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "frames_per_s": round(fps, 1),
+        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "texture": texture, "frames_per_s": round(fps, 1),
                           "ms_per_frame": round(1e3 / fps, 3)}), flush=True)
         ctx.close()
 

@@ -1,7 +1,9 @@
 """Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
-usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--offset N] [--reps N]
+usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--offset N] [--texture T [--texture-window w]]
+[--reps N]
 (--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given; --offset:
-mod_set_disparity_offset, the images' disparities then start at N)"""
+mod_set_disparity_offset, the images' disparities then start at N; --texture: mod_set_texture_filter(T, w, 31, MOD_TEXTURE_DISPARITY),
+off unless given)"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -16,6 +18,8 @@ ap.add_argument("--subpixel", action="store_true")
 ap.add_argument("--uniqueness", type=int, default=0, metavar="U", help="uniqueness ratio in percent (0 = off)")
 ap.add_argument("--speckle", type=int, nargs=2, default=(0, 0), metavar=("SIZE", "RANGE"), help="speckle filter (size 0 = off)")
 ap.add_argument("--offset", type=int, default=0, metavar="N", help="minimum disparity: the window is [N, N + D) (0 = off)")
+ap.add_argument("--texture", type=int, default=0, metavar="T", help="texture threshold (0 = off)")
+ap.add_argument("--texture-window", type=int, default=9, metavar="w", help="window of the texture sum (odd, 3..15)")
 ap.add_argument("--reps", type=int, default=3)
 a = ap.parse_args()
 W, H, D = a.W, a.H, a.D
@@ -33,6 +37,9 @@ if a.uniqueness or a.speckle[0]:
     ctx.set_disparity_filters(a.uniqueness, a.speckle[0], a.speckle[1])
 filters = f" uniqueness={a.uniqueness} speckle={a.speckle[0]}/{a.speckle[1]}" if a.uniqueness or a.speckle[0] else ""
 filters += f" offset={a.offset}" if a.offset else ""
+if a.texture:
+    ctx.set_texture_filter(a.texture, a.texture_window, 31, capi.MOD_TEXTURE_DISPARITY)
+    filters += f" texture={a.texture}/{a.texture_window}"
 dev = ctx.device
 tl = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev); tr = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
 out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
