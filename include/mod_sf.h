@@ -501,6 +501,53 @@ int  mod_texture_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const
 int  mod_texture_reject_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const ModTextureFilter *filter, float *disparity,
                             float *flow);
 
+/* ---- min-eigenvalue (aperture) threshold of the on-GPU optical flow -------------------------------------------------------- */
+/* Opt-in rejection of flow pixels whose displacement the image does not determine in BOTH axes.  The texture rule above sums
+ * horizontal gradients, which is right for a horizontal search and not for a 2-D one: a pixel on a vertical edge passes it although
+ * its motion along the edge is undetermined (the aperture problem), and a pixel on a horizontal edge fails it although its vertical
+ * motion is determined.  This rule asks what a 2-D tracker asks (Shi-Tomasi's measure; minEigThreshold of calcOpticalFlowPyrLK in
+ * idea): whether the gradient structure tensor over the window has two large eigenvalues.  Integers throughout
+ * (tests/models/corner_model.py restates it bit for bit) — for a grey plane I (uint8, W x H), an odd window
+ * w, a cap c and a threshold t:
+ *   gx(x, y) = clamp(I(min(x + 1, W - 1), y) - I(max(x - 1, 0), y), -c, c)     signed; columns CLAMPED as in the texture rule
+ *   gy(x, y) = clamp(I(x, min(y + 1, H - 1)) - I(x, max(y - 1, 0)), -c, c)     rows CLAMPED
+ *   A = sum gx^2,  B = sum gx gy,  C = sum gy^2    over |i|, |j| <= (w - 1) / 2; window positions outside the image add 0
+ *   S = A + C,  D = (A - C)^2 + 4 B^2,  r = the smallest integer with r^2 >= D
+ *   E(x, y) = (S - r) >> 1                 the floor of the tensor's smaller eigenvalue; S >= r always (the tensor is PSD)
+ *   rejected(x, y)  iff  E(x, y) < t       equivalently, with no square root: not (S - 2 t >= 0 and (S - 2 t)^2 >= D)
+ * A, C and |B| are at most 225 * 255^2 = 14630625 = MOD_CORNER_MAX (int32), so is E (stored as uint32); D is below 1.1e15 (int64, and
+ * below 2^53).  E = 0 on a flat image and on stripes or a step edge of either direction.  The formula is this library's own: bit
+ * parity with OpenCV's cornerMinEigenVal is NOT claimed.
+ *
+ * mod_set_flow_corner_filter: context state like mod_set_texture_filter, read when a call or a submit enqueues the flow estimator; a
+ * frame in flight completes with the setting of its own submit, and the setting may change while tickets are outstanding.  NULL or
+ * threshold 0: off (the default) — every entry point enqueues the kernels it always did and writes the same bytes.  With threshold 0
+ * the other fields are still checked.  Out-of-range values, an even window or reserved != 0: MOD_ERR_INVALID_ARGUMENT, the setting
+ * stays as it was, and mod_last_error names the corner filter.  Every entry point that runs the flow estimator (mod_flow_compute_dev /
+ * _host, mod_submit_images_host, mod_submit_odometry_host, mod_submit_depth_host): behind the finishing step, and behind the texture
+ * rule when that is on, every pixel whose E of the NOW image is below t becomes (NaN, NaN), both words 0x7fc00000.  The rule stores
+ * only where it rejects and never reads the flow, so its order against the texture rule changes no byte.  The ego-motion estimator
+ * below skips non-finite flow and is unchanged: with the filter on, its correspondences are the pixels whose flow the image
+ * determines in both axes. */
+#define MOD_CORNER_MAX 14630625
+typedef struct ModCornerFilter {   /* 16 bytes; NULL or threshold 0: off (the default) */
+  int32_t threshold;               /* 0..MOD_CORNER_MAX */
+  int32_t window;                  /* odd, 3..15; default 9 */
+  int32_t cap;                     /* 1..255; default 31 */
+  int32_t reserved;                /* must be 0 */
+} ModCornerFilter;
+int  mod_set_flow_corner_filter(ModContext *ctx, const ModCornerFilter *filter);
+/* as set; never set, or set with NULL: {0, 9, 31, 0} */
+int  mod_get_flow_corner_filter(const ModContext *ctx, ModCornerFilter *filter);
+/* E itself, [frames][H][W] uint32, of grey planes [frames][H][W] of the camera's size: what one looks at to choose a threshold.
+ * filter NULL: the context's; only window and cap are used and checked.  A NULL grey or strength plane: MOD_ERR_INVALID_ARGUMENT.
+ * Ordered on the context's stream; keeps no state, needs no scratch. */
+int  mod_flow_corner_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const ModCornerFilter *filter, uint32_t *strength);
+/* The rule alone, in place, on a caller's own flow [frames][H][W][2] (another matcher's output): where E of `grey` is below the
+ * threshold the pixel becomes (NaN, NaN).  A NULL `grey` or `flow`: MOD_SKIP_NO_FLOW.  filter NULL: the context's.  threshold 0:
+ * nothing is enqueued.  No other pixel is read or written. */
+int  mod_flow_corner_reject_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const ModCornerFilter *filter, float *flow);
+
 /* ---- on-GPU stereo ego-motion ---------------------------------------------------------------------------------------------- */
 /* The reference obtains transform_prev2now_ from libviso2 (VisualOdometryStereo::process + getMotion(),
  * scene_flow_constructor.cpp:214-256), sparse features matched in four images on the CPU.  This estimator is NOT libviso2 and

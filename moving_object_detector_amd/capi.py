@@ -36,6 +36,7 @@ MOD_SGM_FRACTION_BITS = 4
 MOD_FLOW_SEEDS = 5
 MOD_TEXTURE_DISPARITY, MOD_TEXTURE_FLOW = 1, 2           # ModTextureFilter.apply: the estimators the texture threshold rejects in
 MOD_TEXTURE_MAX = 15 * 15 * 255                          # the largest texture sum (window 15, cap 255): it fits a uint16
+MOD_CORNER_MAX = 15 * 15 * 255 * 255                     # 14630625: the largest min-eigenvalue (ModCornerFilter.threshold's upper end)
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
 MOD_DISTORTION_RATIONAL, MOD_DISTORTION_EQUIDISTANT = 0, 1   # how ModRectifyCamera.D is read (mod_set_distortion_model)
 DISTORTION_MODELS = {"plumb_bob": MOD_DISTORTION_RATIONAL, "rational_polynomial": MOD_DISTORTION_RATIONAL,
@@ -117,6 +118,16 @@ def texture_filter(threshold: int = 0, window: int = 9, cap: int = 31, apply: in
     """ModTextureFilter with the defaults of include/mod_sf.h (threshold 0 = off): T = the window x window sum of the horizontal central
     differences capped at `cap`; pixels with T < threshold are rejected in the estimators named by `apply`."""
     return ModTextureFilter(int(threshold), int(window), int(cap), int(apply))
+
+
+class ModCornerFilter(C.Structure):
+    _fields_ = [("threshold", C.c_int32), ("window", C.c_int32), ("cap", C.c_int32), ("reserved", C.c_int32)]
+
+
+def corner_filter(threshold: int = 0, window: int = 9, cap: int = 31) -> ModCornerFilter:
+    """ModCornerFilter with the defaults of include/mod_sf.h (threshold 0 = off): E = the floor of the smaller eigenvalue of the window x
+    window gradient structure tensor, gradients capped at +-`cap`; flow pixels with E < threshold are rejected."""
+    return ModCornerFilter(int(threshold), int(window), int(cap), 0)
 
 
 class ModFlowParams(C.Structure):
@@ -285,6 +296,7 @@ assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
+assert C.sizeof(ModCornerFilter) == 16
 
 
 def distortion_model(model) -> int:
@@ -369,6 +381,10 @@ SIGNATURES = {
     "mod_get_texture_filter": [_vp, C.POINTER(ModTextureFilter)],
     "mod_texture_dev": [_vp, _i32, _vp, C.POINTER(ModTextureFilter), _vp],
     "mod_texture_reject_dev": [_vp, _i32, _vp, C.POINTER(ModTextureFilter), _vp, _vp],
+    "mod_set_flow_corner_filter": [_vp, C.POINTER(ModCornerFilter)],
+    "mod_get_flow_corner_filter": [_vp, C.POINTER(ModCornerFilter)],
+    "mod_flow_corner_dev": [_vp, _i32, _vp, C.POINTER(ModCornerFilter), _vp],
+    "mod_flow_corner_reject_dev": [_vp, _i32, _vp, C.POINTER(ModCornerFilter), _vp],
     "mod_set_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)],
     "mod_get_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(_i32)],
     "mod_rectify_dev": [_vp, _i32, _vp, C.POINTER(ModImageLayout), _i32, _vp],

@@ -1,6 +1,6 @@
 // estimators.hip — the C ABI's on-GPU estimators (SGM disparity, census optical flow, stereo ego-motion): their *_dev entry points
-// and scratch, and the texture threshold both image estimators share.  Host-side only; the kernels live in sgm.hip, flow.hip,
-// egomotion.hip, disparity_filter.hip and texture.hip.
+// and scratch, the texture threshold both image estimators share and the flow's min-eigenvalue threshold.  Host-side only; the kernels
+// live in sgm.hip, flow.hip, egomotion.hip, disparity_filter.hip, texture.hip and corner.hip.
 #include "mod_context.h"
 
 #include <algorithm>
@@ -121,6 +121,21 @@ static int check_texture_filter(ModContext *c, const ModTextureFilter &f) {
 }
 
 static bool texture_applies(const ModTextureFilter &f, int to) { return f.threshold > 0 && (f.apply & to) != 0; }
+
+// ---- min-eigenvalue filter of the flow (corner.hip) -----------------------------------------------------------------------------
+// window and cap: what the kernel needs; threshold and reserved: what the rule and the setter need
+static int check_corner_kernel(ModContext *c, const ModCornerFilter &f) {
+  if (f.window < 3 || f.window > 15 || f.window % 2 == 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "corner window must be odd and in 3..15");
+  if (f.cap < 1 || f.cap > 255) return fail(c, MOD_ERR_INVALID_ARGUMENT, "corner cap must be in 1..255");
+  return MOD_OK;
+}
+
+static int check_corner_filter(ModContext *c, const ModCornerFilter &f) {
+  if (f.threshold < 0 || f.threshold > MOD_CORNER_MAX) return fail(c, MOD_ERR_INVALID_ARGUMENT, "corner threshold must be in 0..14630625");
+  if (int rc = check_corner_kernel(c, f)) return rc;
+  if (f.reserved != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "corner reserved must be 0");
+  return MOD_OK;
+}
 
 // winner-take-all .. left-right check of the group (and the texture and speckle filters) on the context's stream, behind its paths
 static int sgm_finish(ModContext *c, const ModSgmParams *p, int off, const ModDisparityFilters &filters, const ModTextureFilter &tex, const uint8_t *left,
@@ -439,6 +454,43 @@ int mod_texture_reject_dev(ModContext *c, int32_t frames, const uint8_t *grey, c
   return MOD_OK;
 }
 
+int mod_set_flow_corner_filter(ModContext *c, const ModCornerFilter *f) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!f) { c->corner = ModContext{}.corner; return MOD_OK; }
+  if (int rc = check_corner_filter(c, *f)) return rc;
+  c->corner = *f;
+  return MOD_OK;
+}
+
+int mod_get_flow_corner_filter(const ModContext *c, ModCornerFilter *f) {
+  if (!c || !f) return MOD_ERR_INVALID_ARGUMENT;
+  *f = c->corner;
+  return MOD_OK;
+}
+
+int mod_flow_corner_dev(ModContext *c, int32_t frames, const uint8_t *grey, const ModCornerFilter *f, uint32_t *strength) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!grey || !strength) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null grey / corner strength plane");
+  const ModCornerFilter t = f ? *f : c->corner;
+  if ((rc = check_corner_kernel(c, t))) return rc;
+  launch_corner(c->dc.W, c->dc.H, frames, t.window, t.cap, 0, grey, strength, nullptr, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_flow_corner_reject_dev(ModContext *c, int32_t frames, const uint8_t *grey, const ModCornerFilter *f, float *flow) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!grey || !flow) return MOD_SKIP_NO_FLOW;
+  const ModCornerFilter t = f ? *f : c->corner;
+  if ((rc = check_corner_filter(c, t))) return rc;
+  if (t.threshold == 0) return MOD_OK;
+  launch_corner(c->dc.W, c->dc.H, frames, t.window, t.cap, t.threshold, grey, nullptr, flow, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
 int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, const uint8_t *now, const ModFlowParams *p, float *flow) {
   int rc = check_ready(c, frames);
   if (rc) return rc;
@@ -451,6 +503,7 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
   const int seeds = c->flow_seeds;                       // the setting of THIS call: every kernel below is enqueued before it returns
   const ModTextureFilter tex = c->texture;               // ... and the texture filter
+  const ModCornerFilter cor = c->corner;                 // ... and the min-eigenvalue filter
   const int *const W = lv.W, *const H = lv.H; uint8_t *const img = b.img; uint32_t *const cen = b.census;   // level l >= 1 at img + lv.img[l], level l of the census planes at cen + lv.cen[l]: [2][F][H[l]][W[l]]
   const size_t N = (size_t)W[0] * H[0];
   for (int l = 1; l < L; l++) {
@@ -471,6 +524,9 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   launch_flow_finish(W[0], H[0], F, b.winners, dirs == 2 ? b.winners + (size_t)F * N : nullptr, sub, p->fb_check, flow, c->stream);
   // the texture rule on the NOW image: the flow is indexed at the now pixel
   if (texture_applies(tex, MOD_TEXTURE_FLOW)) launch_texture(W[0], H[0], F, tex.window, tex.cap, tex.threshold, now, nullptr, nullptr, 0.0f, flow, c->stream);
+  // the min-eigenvalue rule, on the NOW image as well; it stores only where it rejects and reads no flow, so its order against the
+  // texture launch changes no byte
+  if (cor.threshold > 0) launch_corner(W[0], H[0], F, cor.window, cor.cap, cor.threshold, now, nullptr, flow, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -123,6 +123,8 @@ struct ModContext {
   int32_t sgm_offset = 0;                   // mod_set_disparity_offset: read at the same moment, and by mod_sgm_path_dev (0: the window starts at 0)
   // mod_set_texture_filter: read when a call / submit enqueues its disparity or flow estimator (threshold 0: off, nothing is enqueued)
   ModTextureFilter texture{0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW};
+  // mod_set_flow_corner_filter: read when a call / submit enqueues its flow estimator (threshold 0: off, nothing is enqueued)
+  ModCornerFilter corner{0, 9, 31, 0};
   // mod_set_cluster_members: read by the calls that write the lists when they enqueue the cluster stage (members_on false: off)
   ModClusterMembers members{};
   bool members_on = false;

@@ -141,6 +141,13 @@ void launch_speckle(int W, int H, int frames, float lo, float invalid, int speck
 void launch_texture(int W, int H, int frames, int window, int cap, int threshold, const uint8_t *grey, uint16_t *texture, float *disparity,
                     float invalid, float *flow, hipStream_t s);
 
+// min-eigenvalue measure (corner.hip) of grey planes [frames][H][W]: E = the floor of the smaller eigenvalue of the window x window sum
+// of the gradient structure tensor, gradients capped at +-`cap` (window odd in 3..15, cap in 1..255; checked by the caller).  ONE
+// launch: `strength` non-null: E itself into [frames][H][W] uint32; else every pixel with E < threshold becomes (NaN, NaN) in `flow`
+// [frames][H][W][2], and nothing else of it is read or written
+void launch_corner(int W, int H, int frames, int window, int cap, int threshold, const uint8_t *grey, uint32_t *strength, float *flow,
+                   hipStream_t s);
+
 // on-GPU optical flow (flow.hip).  Pyramid level of both images: src0 / src1 [frames][Hs][Ws] -> dst [2][frames][H][W].
 void launch_flow_pyramid(int Ws, int Hs, int W, int H, int frames, const uint8_t *src0, const uint8_t *src1, uint8_t *dst, hipStream_t s);
 // one level, `dirs` directions (1: forward, 2: + backward); coarse == nullptr: the coarsest level.  census [2][frames][H][W] (prev, now),

@@ -78,6 +78,14 @@ class SceneFlowConstructor {
     const ModTextureFilter f{threshold, window, cap, apply};
     check(mod_set_texture_filter(ctx_, &f));
   }
+  // min-eigenvalue (aperture) threshold of the flow estimator (mod_set_flow_corner_filter; calcOpticalFlowPyrLK's minEigThreshold in
+  // idea): flow pixels whose window x window gradient structure tensor of the now image has a smaller eigenvalue below `threshold`
+  // become (NaN, NaN); threshold 0 = off, the default.  Throws where the library refuses a value; frames already submitted keep the
+  // setting of their submit.
+  void setFlowCornerFilter(int threshold, int window = 9, int cap = 31) {
+    const ModCornerFilter f{threshold, window, cap, 0};
+    check(mod_set_flow_corner_filter(ctx_, &f));
+  }
   // rejection filters of the disparity (mod_set_disparity_filters; stereo_image_proc's names): uniqueness ratio in percent, regions of at
   // most speckle_size pixels whose neighbours differ by at most speckle_range disparities are invalidated; all 0 = off, the default.
   // Frames already submitted keep the settings of their submit.

@@ -164,6 +164,21 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_texture_filter(self.h, C.byref(f)))
         return f
 
+    def set_flow_corner_filter(self, threshold=None, window: int = 9, cap: int = 31) -> None:
+        """Min-eigenvalue (aperture) threshold of the on-GPU flow estimator (mod_set_flow_corner_filter), off by default: pixels whose
+        strength E (Context.flow_corner) of the now image is below `threshold` become (NaN, NaN) in the flow.  No argument or None turns
+        it off; a capi.ModCornerFilter is taken as it is.  Read when a call or a submit enqueues the flow estimator."""
+        if threshold is None:
+            self._check(self.lib.mod_set_flow_corner_filter(self.h, None))
+            return
+        f = threshold if isinstance(threshold, capi.ModCornerFilter) else capi.corner_filter(threshold, window, cap)
+        self._check(self.lib.mod_set_flow_corner_filter(self.h, C.byref(f)))
+
+    def get_flow_corner_filter(self) -> capi.ModCornerFilter:
+        f = capi.ModCornerFilter(-1, -1, -1, -1)
+        self._check(self.lib.mod_get_flow_corner_filter(self.h, C.byref(f)))
+        return f
+
     def set_cluster_members(self, ws: Optional[dict]) -> None:
         """Per-cluster member lists (mod_set_cluster_members), off by default: every later cluster() / process() and the synchronous
         host calls write offsets, indices (and points) into the tensors of `ws` (workspace(..., members=True)); None turns them off.
@@ -465,6 +480,40 @@ class Context(HostCalls):
         ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         return self._check(self.lib.mod_texture_reject_dev(self.h, F or 1, ptr(grey), C.byref(filter) if filter is not None else None,
                                                            ptr(disparity), ptr(flow)))
+
+    def flow_corner(self, grey: torch.Tensor, filter: Optional[capi.ModCornerFilter] = None,   # noqa: A002 (the header's name)
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The min-eigenvalue strength E of device grey planes (F, H, W) or (H, W) (mod_flow_corner_dev) as int32 of the same shape (E <=
+        capi.MOD_CORNER_MAX, so the uint32 the library writes reads the same as int32; `out` may be int32 or uint32): what one looks at
+        to choose a threshold.  filter None = the context's (only window and cap are used).  Enqueued on the context's stream."""
+        g = self._grey_planes(grey)
+        if out is None:
+            out = torch.empty(g.shape, dtype=torch.int32, device=g.device)
+        elif out.shape not in (g.shape, grey.shape) or out.dtype not in (torch.int32, torch.uint32) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous int32 or uint32 tensor of grey's shape")
+        self._done(self.lib.mod_flow_corner_dev(self.h, g.shape[0], g.data_ptr(), C.byref(filter) if filter is not None else None,
+                                                out.data_ptr()), "mod_flow_corner_dev")
+        return out[0] if grey.dim() == 2 and out.dim() == 3 else out
+
+    def flow_corner_reject(self, grey: Optional[torch.Tensor], flow: Optional[torch.Tensor],
+                           filter: Optional[capi.ModCornerFilter] = None) -> int:   # noqa: A002
+        """The min-eigenvalue rule alone, in place (mod_flow_corner_reject_dev), on a caller's own device flow (F, H, W, 2) float32: where
+        E of `grey` is below the threshold the pixel becomes (NaN, NaN).  filter None = the context's.  Returns the library's code: 0,
+        or the skip code when there is no grey or no flow."""
+        F = None
+        if grey is not None:
+            grey = self._grey_planes(grey)
+            F = grey.shape[0]
+        if flow is not None:
+            if flow.dtype != torch.float32 or not flow.is_contiguous() or flow.device.type != "cuda" or flow.shape[-3:] != (self.height, self.width, 2):
+                raise ValueError("flow must be a contiguous float32 device tensor (F, H, W, 2) at the camera size")
+            n = flow.numel() // (self.height * self.width * 2)
+            if F is not None and n != F:
+                raise ValueError("flow must hold as many frames as grey")
+            F = n
+        ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
+        return self._check(self.lib.mod_flow_corner_reject_dev(self.h, F or 1, ptr(grey), C.byref(filter) if filter is not None else None,
+                                                               ptr(flow)))
 
     def pinned_copy(self, array) -> "PinnedBuffer":
         """A copy of `array` in page-locked host memory (mod_host_malloc): .ptr, .nbytes, .array (a numpy view of the copy); the submit

@@ -1,9 +1,12 @@
 """HIP-event timing of the on-GPU optical flow: mod_flow_compute_dev (default parameters, forward-backward check on) at 1280 x 720 and
 1920 x 1080 for 1 and 8 frames, and the images stream (mod_submit_images_host: SGM disparity + flow + scene flow + clustering per
 frame, three frames in flight) in frames/s.  Prints one JSON line per measurement.  Run on the GPU:
-    python tools/time_flow.py [REPS] [--seeds N] [--texture T]
+    python tools/time_flow.py [REPS] [--seeds N] [--texture T] [--corner T [--corner-window W]]
 (--seeds 5: mod_set_flow_propagation(5); 1, the default, never calls it.  --texture T: mod_set_texture_filter(T) with the default window
-and cap, for the flow and, in the stream, the disparity; 0, the default, never calls it)"""
+and cap, for the flow and, in the stream, the disparity; 0, the default, never calls it.  --corner T: mod_set_flow_corner_filter(T,
+W, 31) for the flow call and the stream; 0, the default, never calls it.  With --corner the tool also times, per size, the rule's
+kernel alone (mod_flow_corner_reject_dev: k_corner's reject form) beside k_texture's flow-reject form (mod_texture_reject_dev at
+threshold 400, the same window and cap) on the same 8 frames)"""
 import argparse
 import json
 import os
@@ -24,8 +27,24 @@ def main():
     ap.add_argument("reps", nargs="?", type=int, default=50)
     ap.add_argument("--seeds", type=int, default=1, metavar="N", help="mod_set_flow_propagation: 1 (off) or 5")
     ap.add_argument("--texture", type=int, default=0, metavar="T", help="mod_set_texture_filter: the threshold (0 = off)")
+    ap.add_argument("--corner", type=int, default=0, metavar="T", help="mod_set_flow_corner_filter: the threshold (0 = off)")
+    ap.add_argument("--corner-window", type=int, default=9, metavar="W", help="the window of --corner (odd, 3..15)")
     args = ap.parse_args()
-    reps, seeds, texture = args.reps, args.seeds, args.texture
+    reps, seeds, texture, corner, cwin = args.reps, args.seeds, args.texture, args.corner, args.corner_window
+
+    def timed(call):
+        """ms per call over `reps` calls between two HIP events, after five warm-up calls"""
+        for _ in range(5):
+            call()
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            call()
+        b.record()
+        b.synchronize()
+        return a.elapsed_time(b) / reps
+
     prm = capi.flow_params()
     for W, H in ((1280, 720), (1920, 1080)):
         m = synth.make_moving_images(W, H, seed=1, n_boxes=4)
@@ -37,23 +56,23 @@ def main():
                 ctx.set_flow_propagation(seeds)
             if texture:
                 ctx.set_texture_filter(texture)
+            if corner:
+                ctx.set_flow_corner_filter(corner, cwin)
             dev = ctx.device
             tp = torch.from_numpy(np.stack([m["left0"]] * F)).to(dev)
             tn = torch.from_numpy(np.stack([m["left1"]] * F)).to(dev)
             out = torch.empty((F, H, W, 2), dtype=torch.float32, device=dev)
-            call = lambda: ctx.estimate_flow(tp, tn, prm, out)
-            for _ in range(5):
-                call()
-            torch.cuda.synchronize()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            for _ in range(reps):
-                call()
-            b.record()
-            b.synchronize()
-            ms = a.elapsed_time(b) / reps
-            print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "seeds": seeds, "texture": texture, "ms_per_call": round(ms, 4),
-                              "ms_per_frame": round(ms / F, 4)}), flush=True)
+            ms = timed(lambda: ctx.estimate_flow(tp, tn, prm, out))
+            print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "seeds": seeds, "texture": texture, "corner": corner,
+                              "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4)}), flush=True)
+            if corner and F == 8:
+                # the two rejection kernels alone, in place on the flow just computed, on the same now frames in this process
+                cf, xf = capi.corner_filter(corner, cwin), capi.texture_filter(400, cwin, 31, capi.MOD_TEXTURE_FLOW)
+                for what, call in (("k_corner reject", lambda: ctx.flow_corner_reject(tn, out, cf)),
+                                   ("k_texture flow reject", lambda: ctx.texture_reject(tn, flow=out, filter=xf))):
+                    ms = timed(call)
+                    print(json.dumps({"what": what, "W": W, "H": H, "frames": F, "window": cwin, "ms_per_call": round(ms, 4),
+                                      "ms_per_frame": round(ms / F, 4)}), flush=True)
             ctx.close()
         # the images stream
         ctx = Context(W, H, max_frames=1)
@@ -65,6 +84,8 @@ def main():
             ctx.set_flow_propagation(seeds)
         if texture:
             ctx.set_texture_filter(texture)
+        if corner:
+            ctx.set_flow_corner_filter(corner, cwin)
         sp = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
         tf = capi.transforms_array(np.zeros((1, 3)), np.array([[0.0, 0.0, 0.0, 1.0]]))
         pins = [ctx.pinned_copy(m[k]) for k in ("left0", "right0", "left1", "right1")]
@@ -76,7 +97,8 @@ def main():
 
         frames = max(20, reps)
         fps = stream_rate(s, step, frames)
-        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "texture": texture, "frames_per_s": round(fps, 1),
+        print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "texture": texture, "corner": corner,
+                          "frames_per_s": round(fps, 1),
                           "ms_per_frame": round(1e3 / fps, 3)}), flush=True)
         ctx.close()
 
