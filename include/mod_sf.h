@@ -548,6 +548,47 @@ int  mod_flow_corner_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, c
  * nothing is enqueued.  No other pixel is read or written. */
 int  mod_flow_corner_reject_dev(ModContext *ctx, int32_t frames, const uint8_t *grey, const ModCornerFilter *filter, float *flow);
 
+/* ---- NaN-aware median filter of the on-GPU optical flow --------------------------------------------------------------------- */
+/* Opt-in post-filter of the finished flow.  The forward-backward check and the two rules above remove vectors the image cannot
+ * determine; none removes a vector the image did determine, wrongly — the isolated outlier a block matcher leaves inside a smooth
+ * field, which the dynamic test downstream turns into a "moving" pixel.  The cure is the small median every classical flow pipeline
+ * carries behind its matcher (cv::medianBlur on the two channels in idea; bit parity with it is NOT claimed: this one knows invalid
+ * pixels and clips its window).  The rule (tests/models/flow_median_model.py restates it bit for bit):
+ *   A flow pixel is VALID when both of its components are finite; any NaN or +-inf makes it invalid (the rule mod_flow_image_dev
+ *   draws black by).  For a pixel p of frame f let S be the valid pixels of the window x window square centred on p, CLIPPED to the
+ *   image — no replication, no wrap, no other frame — and n = |S|.
+ *     p invalid:                  the output pixel is the input pixel, bit for bit, both words, payloads included: no hole is filled
+ *     p valid and n < min_valid:  the output is (NaN, NaN), both words 0x7fc00000, as the texture and corner rules write it
+ *     otherwise:                  out.x is the LOWER MEDIAN of the x components of S and out.y the lower median of the y components,
+ *                                 taken independently: the element of index (n - 1) / 2 (integer division) in ascending order
+ *   "Ascending" is the order of the integer key k(b) = b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000) of the float's 32 bits b, compared
+ *   as uint32: for finite floats the numeric order with -0.0 before +0.0.  It does not depend on denormal flushing and makes the
+ *   selected BIT PATTERN unique: every output word of a filtered pixel is one of the input words of S.
+ * window: 0 (off, the default), 3 or 5.  min_valid: 0 .. window^2; 0 and 1 mean "no isolation test" (a valid p counts itself).
+ *
+ * mod_set_flow_median: context state like mod_set_flow_corner_filter, read when a call or a submit enqueues the flow estimator; a
+ * frame in flight completes with the setting of its own submit.  NULL or window 0: off — every entry point enqueues the kernels it
+ * always did, allocates nothing and writes the same bytes.  A window other than 0 / 3 / 5, min_valid outside 0 .. window^2 or a
+ * non-zero reserved word: MOD_ERR_INVALID_ARGUMENT, the setting stays as it was, and mod_last_error names the flow median.  Every
+ * entry point that runs the flow estimator (mod_flow_compute_dev / _host, mod_submit_images_host, mod_submit_odometry_host,
+ * mod_submit_depth_host) filters LAST, behind the finishing step, the texture rule and the min-eigenvalue rule, so that a rejected
+ * vector never votes: those write a scratch plane of max_frames x max_width x max_height x 8 bytes (allocated at the first call with
+ * the filter on, never when off), and the filter writes the caller's plane.  The ego-motion and the scene flow of the odometry and
+ * depth streams consume the filtered flow. */
+typedef struct ModFlowMedian {     /* 16 bytes; NULL or window 0: off (the default) */
+  int32_t window;                  /* 0, 3 or 5 */
+  int32_t min_valid;               /* 0 .. window * window */
+  int32_t reserved[2];             /* must be 0 */
+} ModFlowMedian;
+int  mod_set_flow_median(ModContext *ctx, const ModFlowMedian *filter);
+/* as set; never set, or set with NULL: {0, 0, {0, 0}} */
+int  mod_get_flow_median(const ModContext *ctx, ModFlowMedian *filter);
+/* The filter alone, on a caller's own flow [frames][H][W][2] (another matcher's output) into flow_out of the same size.  filter NULL:
+ * the context's.  A stencil cannot run in place: flow_in and flow_out must not overlap.  A NULL plane, overlapping planes, an invalid
+ * filter or window 0 (nothing to do): MOD_ERR_INVALID_ARGUMENT.  Every pixel of flow_out is stored; flow_in is only read.  Ordered on
+ * the context's stream; keeps no state, needs no scratch. */
+int  mod_flow_median_dev(ModContext *ctx, int32_t frames, const float *flow_in, const ModFlowMedian *filter, float *flow_out);
+
 /* ---- on-GPU stereo ego-motion ---------------------------------------------------------------------------------------------- */
 /* The reference obtains transform_prev2now_ from libviso2 (VisualOdometryStereo::process + getMotion(),
  * scene_flow_constructor.cpp:214-256), sparse features matched in four images on the CPU.  This estimator is NOT libviso2 and

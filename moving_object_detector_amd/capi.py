@@ -130,6 +130,16 @@ def corner_filter(threshold: int = 0, window: int = 9, cap: int = 31) -> ModCorn
     return ModCornerFilter(int(threshold), int(window), int(cap), 0)
 
 
+class ModFlowMedian(C.Structure):
+    _fields_ = [("window", C.c_int32), ("min_valid", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+def flow_median(window: int = 5, min_valid: int = 0) -> ModFlowMedian:
+    """ModFlowMedian of include/mod_sf.h (window 0 = off, 3 or 5): every valid flow pixel becomes the per-component lower median of the
+    valid pixels of its window x window square, or (NaN, NaN) where fewer than `min_valid` of them are valid; invalid pixels stay."""
+    return ModFlowMedian(int(window), int(min_valid), (0, 0))
+
+
 class ModFlowParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("radius", C.c_int32), ("window", C.c_int32), ("subpixel", C.c_int32), ("fb_check", C.c_int32)]
 
@@ -297,6 +307,7 @@ assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
+assert C.sizeof(ModFlowMedian) == 16
 
 
 def distortion_model(model) -> int:
@@ -385,6 +396,9 @@ SIGNATURES = {
     "mod_get_flow_corner_filter": [_vp, C.POINTER(ModCornerFilter)],
     "mod_flow_corner_dev": [_vp, _i32, _vp, C.POINTER(ModCornerFilter), _vp],
     "mod_flow_corner_reject_dev": [_vp, _i32, _vp, C.POINTER(ModCornerFilter), _vp],
+    "mod_set_flow_median": [_vp, C.POINTER(ModFlowMedian)],
+    "mod_get_flow_median": [_vp, C.POINTER(ModFlowMedian)],
+    "mod_flow_median_dev": [_vp, _i32, _vp, C.POINTER(ModFlowMedian), _vp],
     "mod_set_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)],
     "mod_get_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(_i32)],
     "mod_rectify_dev": [_vp, _i32, _vp, C.POINTER(ModImageLayout), _i32, _vp],

@@ -1,6 +1,6 @@
 // estimators.hip — the C ABI's on-GPU estimators (SGM disparity, census optical flow, stereo ego-motion): their *_dev entry points
-// and scratch, the texture threshold both image estimators share and the flow's min-eigenvalue threshold.  Host-side only; the kernels
-// live in sgm.hip, flow.hip, egomotion.hip, disparity_filter.hip, texture.hip and corner.hip.
+// and scratch, the texture threshold both image estimators share, the flow's min-eigenvalue threshold and its median filter.  Host-side
+// only; the kernels live in sgm.hip, flow.hip, egomotion.hip, disparity_filter.hip, texture.hip, corner.hip and flow_median.hip.
 #include "mod_context.h"
 
 #include <algorithm>
@@ -134,6 +134,14 @@ static int check_corner_filter(ModContext *c, const ModCornerFilter &f) {
   if (f.threshold < 0 || f.threshold > MOD_CORNER_MAX) return fail(c, MOD_ERR_INVALID_ARGUMENT, "corner threshold must be in 0..14630625");
   if (int rc = check_corner_kernel(c, f)) return rc;
   if (f.reserved != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "corner reserved must be 0");
+  return MOD_OK;
+}
+
+// ---- median filter of the flow (flow_median.hip) ---------------------------------------------------------------------------------
+static int check_flow_median(ModContext *c, const ModFlowMedian &f) {
+  if (f.window != 0 && f.window != 3 && f.window != 5) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow median window must be 0, 3 or 5");
+  if (f.min_valid < 0 || f.min_valid > f.window * f.window) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow median min_valid must be in 0..window^2");
+  if (f.reserved[0] != 0 || f.reserved[1] != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow median reserved must be 0");
   return MOD_OK;
 }
 
@@ -491,6 +499,34 @@ int mod_flow_corner_reject_dev(ModContext *c, int32_t frames, const uint8_t *gre
   return MOD_OK;
 }
 
+int mod_set_flow_median(ModContext *c, const ModFlowMedian *f) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (!f) { c->median = ModFlowMedian{}; return MOD_OK; }
+  if (int rc = check_flow_median(c, *f)) return rc;
+  c->median = *f;
+  return MOD_OK;
+}
+
+int mod_get_flow_median(const ModContext *c, ModFlowMedian *f) {
+  if (!c || !f) return MOD_ERR_INVALID_ARGUMENT;
+  *f = c->median;
+  return MOD_OK;
+}
+
+int mod_flow_median_dev(ModContext *c, int32_t frames, const float *flow_in, const ModFlowMedian *f, float *flow_out) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!flow_in || !flow_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow median plane");
+  const ModFlowMedian m = f ? *f : c->median;
+  if ((rc = check_flow_median(c, m))) return rc;
+  if (m.window == 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow median window 0: nothing to do");
+  const uintptr_t a = (uintptr_t)flow_in, b = (uintptr_t)flow_out, bytes = (uintptr_t)frames * c->dc.W * c->dc.H * 8;
+  if (a < b + bytes && b < a + bytes) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow median planes overlap: a stencil cannot run in place");
+  launch_flow_median(c->dc.W, c->dc.H, frames, m.window, m.min_valid, flow_in, flow_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
 int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, const uint8_t *now, const ModFlowParams *p, float *flow) {
   int rc = check_ready(c, frames);
   if (rc) return rc;
@@ -499,7 +535,12 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   if ((rc = check_flow_params(c, p, frames))) return rc;
   const FlowPlan lv = flow_plan(c);
   if ((rc = ensure_flow_scratch(c, lv))) return rc;
+  const ModFlowMedian med = c->median;                   // the setting of THIS call, like the three below
+  if (med.window) HIP_TRY(c, dalloc(c->b.flow.unfiltered, (size_t)c->cfg.max_frames * c->maxN));
   const Buffers::Flow &b = c->b.flow;
+  // with the median filter on, the finishing step and the two rules write the scratch plane and the filter, last, the caller's
+  float *const caller = flow;
+  if (med.window) flow = reinterpret_cast<float *>(b.unfiltered.get());
   const int L = p->levels, F = frames, dirs = p->fb_check >= 0 ? 2 : 1;
   const int seeds = c->flow_seeds;                       // the setting of THIS call: every kernel below is enqueued before it returns
   const ModTextureFilter tex = c->texture;               // ... and the texture filter
@@ -527,6 +568,8 @@ int mod_flow_compute_dev(ModContext *c, int32_t frames, const uint8_t *prev, con
   // the min-eigenvalue rule, on the NOW image as well; it stores only where it rejects and reads no flow, so its order against the
   // texture launch changes no byte
   if (cor.threshold > 0) launch_corner(W[0], H[0], F, cor.window, cor.cap, cor.threshold, now, nullptr, flow, c->stream);
+  // the median filter, last: a vector the rules above rejected never votes
+  if (med.window) launch_flow_median(W[0], H[0], F, med.window, med.min_valid, flow, caller, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

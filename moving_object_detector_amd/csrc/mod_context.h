@@ -97,6 +97,7 @@ struct Buffers {
     DevPtr<uint32_t> census;                // census planes of levels 0 .. kFlowMaxLevels - 1 of both images
     DevPtr<short2> winners;                 // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
     DevPtr<short4> sub;                     // [maxF][maxN] sub-pixel terms of level 0
+    DevPtr<float2> unfiltered;              // [maxF][maxN] the flow in front of the median filter; allocated at the first call with mod_set_flow_median on
   } flow;
   struct Ego {                              // on-GPU ego-motion (allocated on first use; the correspondence buffers grow to the smallest stride seen: ensure_ego_scratch)
     DevPtr<double> corr, hyp;               // [maxF][9][cap], [maxF][MOD_EGO_MAX_HYPOTHESES][12]
@@ -125,6 +126,8 @@ struct ModContext {
   ModTextureFilter texture{0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW};
   // mod_set_flow_corner_filter: read when a call / submit enqueues its flow estimator (threshold 0: off, nothing is enqueued)
   ModCornerFilter corner{0, 9, 31, 0};
+  // mod_set_flow_median: read at the same moment (window 0: off, nothing is allocated or enqueued)
+  ModFlowMedian median{};
   // mod_set_cluster_members: read by the calls that write the lists when they enqueue the cluster stage (members_on false: off)
   ModClusterMembers members{};
   bool members_on = false;

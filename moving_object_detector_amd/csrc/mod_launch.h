@@ -148,6 +148,11 @@ void launch_texture(int W, int H, int frames, int window, int cap, int threshold
 void launch_corner(int W, int H, int frames, int window, int cap, int threshold, const uint8_t *grey, uint32_t *strength, float *flow,
                    hipStream_t s);
 
+// NaN-aware median of a finished flow (flow_median.hip): `in` [frames][H][W][2] -> `out` of the same size, a different plane (a
+// stencil cannot run in place; checked by the caller, as window 3 or 5 and min_valid 0 .. window^2 are).  ONE launch; every pixel of
+// `out` is stored, `in` is only read
+void launch_flow_median(int W, int H, int frames, int window, int min_valid, const float *in, float *out, hipStream_t s);
+
 // on-GPU optical flow (flow.hip).  Pyramid level of both images: src0 / src1 [frames][Hs][Ws] -> dst [2][frames][H][W].
 void launch_flow_pyramid(int Ws, int Hs, int W, int H, int frames, const uint8_t *src0, const uint8_t *src1, uint8_t *dst, hipStream_t s);
 // one level, `dirs` directions (1: forward, 2: + backward); coarse == nullptr: the coarsest level.  census [2][frames][H][W] (prev, now),

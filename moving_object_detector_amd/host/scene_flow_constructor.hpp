@@ -86,6 +86,14 @@ class SceneFlowConstructor {
     const ModCornerFilter f{threshold, window, cap, 0};
     check(mod_set_flow_corner_filter(ctx_, &f));
   }
+  // NaN-aware median filter of the flow estimator (mod_set_flow_median; cv::medianBlur on the two channels in idea): behind every other
+  // step each valid flow pixel becomes the per-component lower median of the valid pixels of its window x window square (window 3 or
+  // 5), or (NaN, NaN) where fewer than min_valid of them are valid; invalid pixels stay.  window 0 = off, the default.  Throws where the
+  // library refuses a value; frames already submitted keep the setting of their submit.
+  void setFlowMedian(int window, int min_valid = 0) {
+    const ModFlowMedian f{window, min_valid, {0, 0}};
+    check(mod_set_flow_median(ctx_, &f));
+  }
   // rejection filters of the disparity (mod_set_disparity_filters; stereo_image_proc's names): uniqueness ratio in percent, regions of at
   // most speckle_size pixels whose neighbours differ by at most speckle_range disparities are invalidated; all 0 = off, the default.
   // Frames already submitted keep the settings of their submit.

@@ -179,6 +179,22 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_flow_corner_filter(self.h, C.byref(f)))
         return f
 
+    def set_flow_median(self, window=None, min_valid: int = 0) -> None:
+        """NaN-aware median filter of the on-GPU flow estimator (mod_set_flow_median), off by default: behind every other step, each valid
+        flow pixel becomes the per-component lower median of the valid pixels of its window x window square (window 3 or 5), or (NaN,
+        NaN) where fewer than `min_valid` of them are valid; invalid pixels stay.  No argument or None turns it off; a
+        capi.ModFlowMedian is taken as it is.  Read when a call or a submit enqueues the flow estimator."""
+        if window is None:
+            self._check(self.lib.mod_set_flow_median(self.h, None))
+            return
+        f = window if isinstance(window, capi.ModFlowMedian) else capi.flow_median(window, min_valid)
+        self._check(self.lib.mod_set_flow_median(self.h, C.byref(f)))
+
+    def get_flow_median(self) -> capi.ModFlowMedian:
+        f = capi.ModFlowMedian(-1, -1, (-1, -1))
+        self._check(self.lib.mod_get_flow_median(self.h, C.byref(f)))
+        return f
+
     def set_cluster_members(self, ws: Optional[dict]) -> None:
         """Per-cluster member lists (mod_set_cluster_members), off by default: every later cluster() / process() and the synchronous
         host calls write offsets, indices (and points) into the tensors of `ws` (workspace(..., members=True)); None turns them off.
@@ -514,6 +530,22 @@ class Context(HostCalls):
         ptr = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         return self._check(self.lib.mod_flow_corner_reject_dev(self.h, F or 1, ptr(grey), C.byref(filter) if filter is not None else None,
                                                                ptr(flow)))
+
+    def flow_median(self, flow: torch.Tensor, filter: Optional[capi.ModFlowMedian] = None,   # noqa: A002 (the header's name)
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The NaN-aware median filter alone (mod_flow_median_dev) on a device flow (F, H, W, 2) or (H, W, 2) float32 at the camera size,
+        into `out` (another tensor of the same size; a new one when None) — returned as (F, H, W, 2).  filter None = the context's;
+        window 0 is refused.  Enqueued on the context's stream."""
+        if flow.dtype != torch.float32 or not flow.is_contiguous() or flow.device.type != "cuda" or flow.shape[-3:] != (self.height, self.width, 2):
+            raise ValueError("flow must be a contiguous float32 device tensor (F, H, W, 2) at the camera size")
+        F = flow.numel() // (self.height * self.width * 2)
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 2), dtype=torch.float32, device=flow.device)
+        elif out.numel() != flow.numel() or out.shape[-3:] != flow.shape[-3:] or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of flow's size")
+        self._done(self.lib.mod_flow_median_dev(self.h, F, flow.data_ptr(), C.byref(filter) if filter is not None else None, out.data_ptr()),
+                   "mod_flow_median_dev")
+        return out.view(F, self.height, self.width, 2)
 
     def pinned_copy(self, array) -> "PinnedBuffer":
         """A copy of `array` in page-locked host memory (mod_host_malloc): .ptr, .nbytes, .array (a numpy view of the copy); the submit

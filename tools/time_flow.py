@@ -1,12 +1,15 @@
 """HIP-event timing of the on-GPU optical flow: mod_flow_compute_dev (default parameters, forward-backward check on) at 1280 x 720 and
 1920 x 1080 for 1 and 8 frames, and the images stream (mod_submit_images_host: SGM disparity + flow + scene flow + clustering per
 frame, three frames in flight) in frames/s.  Prints one JSON line per measurement.  Run on the GPU:
-    python tools/time_flow.py [REPS] [--seeds N] [--texture T] [--corner T [--corner-window W]]
+    python tools/time_flow.py [REPS] [--seeds N] [--texture T] [--corner T [--corner-window W]] [--median {3,5} [--median-min-valid N]]
 (--seeds 5: mod_set_flow_propagation(5); 1, the default, never calls it.  --texture T: mod_set_texture_filter(T) with the default window
 and cap, for the flow and, in the stream, the disparity; 0, the default, never calls it.  --corner T: mod_set_flow_corner_filter(T,
 W, 31) for the flow call and the stream; 0, the default, never calls it.  With --corner the tool also times, per size, the rule's
 kernel alone (mod_flow_corner_reject_dev: k_corner's reject form) beside k_texture's flow-reject form (mod_texture_reject_dev at
-threshold 400, the same window and cap) on the same 8 frames)"""
+threshold 400, the same window and cap) on the same 8 frames.  --median W: mod_set_flow_median(W, N) for the flow call and the
+stream; 0, the default, never calls it.  With --median the tool also times, per size, the filter's kernel alone (mod_flow_median_dev:
+k_flow_median<W>) on the 8 flow frames just computed, with the bytes per second of the 16 bytes per pixel it must move, beside
+k_corner's reject form (threshold 200, window 9, cap 31) on the same frames)"""
 import argparse
 import json
 import os
@@ -29,8 +32,11 @@ def main():
     ap.add_argument("--texture", type=int, default=0, metavar="T", help="mod_set_texture_filter: the threshold (0 = off)")
     ap.add_argument("--corner", type=int, default=0, metavar="T", help="mod_set_flow_corner_filter: the threshold (0 = off)")
     ap.add_argument("--corner-window", type=int, default=9, metavar="W", help="the window of --corner (odd, 3..15)")
+    ap.add_argument("--median", type=int, default=0, choices=(0, 3, 5), metavar="W", help="mod_set_flow_median: the window, 3 or 5 (0 = off)")
+    ap.add_argument("--median-min-valid", type=int, default=0, metavar="N", help="min_valid of --median (0..W*W)")
     args = ap.parse_args()
     reps, seeds, texture, corner, cwin = args.reps, args.seeds, args.texture, args.corner, args.corner_window
+    median, mvalid = args.median, args.median_min_valid
 
     def timed(call):
         """ms per call over `reps` calls between two HIP events, after five warm-up calls"""
@@ -58,13 +64,15 @@ def main():
                 ctx.set_texture_filter(texture)
             if corner:
                 ctx.set_flow_corner_filter(corner, cwin)
+            if median:
+                ctx.set_flow_median(median, mvalid)
             dev = ctx.device
             tp = torch.from_numpy(np.stack([m["left0"]] * F)).to(dev)
             tn = torch.from_numpy(np.stack([m["left1"]] * F)).to(dev)
             out = torch.empty((F, H, W, 2), dtype=torch.float32, device=dev)
             ms = timed(lambda: ctx.estimate_flow(tp, tn, prm, out))
             print(json.dumps({"what": "mod_flow_compute_dev", "W": W, "H": H, "frames": F, "seeds": seeds, "texture": texture, "corner": corner,
-                              "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4)}), flush=True)
+                              "median": median, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4)}), flush=True)
             if corner and F == 8:
                 # the two rejection kernels alone, in place on the flow just computed, on the same now frames in this process
                 cf, xf = capi.corner_filter(corner, cwin), capi.texture_filter(400, cwin, 31, capi.MOD_TEXTURE_FLOW)
@@ -73,6 +81,18 @@ def main():
                     ms = timed(call)
                     print(json.dumps({"what": what, "W": W, "H": H, "frames": F, "window": cwin, "ms_per_call": round(ms, 4),
                                       "ms_per_frame": round(ms / F, 4)}), flush=True)
+            if median and F == 8:
+                # the filter's kernel alone, from the flow just computed into a plane of its own, beside k_corner's reject form (in
+                # place on that plane) in this process
+                mf, cf, filtered = capi.flow_median(median, mvalid), capi.corner_filter(200, 9, 31), torch.empty_like(out)
+                for what, call, nbytes in (("k_flow_median", lambda: ctx.flow_median(out, mf, filtered), 16 * F * H * W),
+                                           ("k_corner reject", lambda: ctx.flow_corner_reject(tn, filtered, cf), None)):
+                    ms = timed(call)
+                    line = {"what": what, "W": W, "H": H, "frames": F, "window": median if nbytes else 9, "ms_per_call": round(ms, 4),
+                            "ms_per_frame": round(ms / F, 4)}
+                    if nbytes:
+                        line["min_valid"], line["gbytes_per_s"] = mvalid, round(nbytes / ms / 1e6, 1)
+                    print(json.dumps(line), flush=True)
             ctx.close()
         # the images stream
         ctx = Context(W, H, max_frames=1)
@@ -86,6 +106,8 @@ def main():
             ctx.set_texture_filter(texture)
         if corner:
             ctx.set_flow_corner_filter(corner, cwin)
+        if median:
+            ctx.set_flow_median(median, mvalid)
         sp = capi.ModSgmParams(128, 6, 96, 8, 1, 1)
         tf = capi.transforms_array(np.zeros((1, 3)), np.array([[0.0, 0.0, 0.0, 1.0]]))
         pins = [ctx.pinned_copy(m[k]) for k in ("left0", "right0", "left1", "right1")]
@@ -98,7 +120,7 @@ def main():
         frames = max(20, reps)
         fps = stream_rate(s, step, frames)
         print(json.dumps({"what": "mod_submit_images_host", "W": W, "H": H, "frames": frames, "seeds": seeds, "texture": texture, "corner": corner,
-                          "frames_per_s": round(fps, 1),
+                          "median": median, "frames_per_s": round(fps, 1),
                           "ms_per_frame": round(1e3 / fps, 3)}), flush=True)
         ctx.close()
 
