@@ -991,6 +991,55 @@ int  mod_get_depth_distortion(const ModContext *ctx, ModDepthDistortion *d, int3
 #define MOD_DEPTH_RAYS_CORNERS 1   /* [h+1][w+1][2] doubles: entry [j][i] is the ray of (i - 0.5, j - 0.5) */
 int  mod_depth_rays_host(ModContext *ctx, const ModDepthLayout *layout, int32_t lattice, double *rays);
 #define MOD_DEPTH_UNDISTORT_ITERS 20
+/* The depth filter (mod_set_depth_filter, opt-in, off by default; while it is off nothing is allocated and every call enqueues exactly
+ * what it enqueues without this section).  Depth cameras report flying (mixed, shadow) pixels at depth discontinuities, samples
+ * somewhere between foreground and background, and readings outside the range the sensor can be trusted in.  Both are removed on the
+ * depth camera's own lattice, in front of everything else: the filter maps a depth MESSAGE to a depth message of the same encoding,
+ * width, height and step, and the plain path, the registration, the splat and the distortion run unchanged on the result.  What
+ * PCL's ShadowPoints, laser_filters' ScanShadowsFilter and the vendors' post-processing blocks are for; parity with none is claimed.
+ * All F32, one operation at a time, -ffp-contract=off, for message pixel (U, V):
+ *   z(U, V) by the rule above (16UC1: (float)r * unit; 32FC1: value * unit; unit == 0: the encoding's default);
+ *   valid0 iff z > 0.0f and z is finite
+ *   The range rule.  in_range iff valid0 and (z_min == 0 or z >= z_min) and (z_max == 0 or z <= z_max): both bounds inclusive
+ *   The support rule (window = 3 or 5, R = window / 2), for a pixel p with in_range(p):
+ *     t = tol_abs + tol_rel * z_p                                                   (one multiply, then one add)
+ *     n = the number of pixels q != p with |Uq - Up| <= R, |Vq - Vp| <= R, q inside the message, in_range(q) and fabsf(z_q - z_p) <= t
+ *     p is kept iff n >= min_support
+ *   Support is counted on the INPUT, after the range rule only: a neighbour the support rule itself removes still supports, so the
+ *   filter is one pass and does not cascade.  Pixels outside the message never support.
+ *   Output: a kept sample is the input word, bit for bit.  A sample with valid0 that a rule removed becomes the encoding's "no reading"
+ *   word: 0 for 16UC1, the bit pattern 0x7fc00000 for 32FC1.  A sample without valid0 (0, -0.0, negatives, NaNs of any payload, +-inf)
+ *   is copied bit for bit: the filter only ever invalidates valid samples.  Bytes of a row beyond `width` samples are not defined.
+ * The neighbourhood is the message's, not the window's: on the plain path with x0, y0 > 0, samples outside the W x H window but inside
+ * the message support (mod_submit_depth_host sends the window's apron of R message pixels, clamped to the message, across PCIe with
+ * it).  tests/models/depth_filter_model.py restates the rule word for word.
+ *   mod_set_depth_filter        NULL, or z_min = z_max = 0 and window = 0: off (the default).  Context state like mod_set_depth_splat:
+ *                               read when mod_depth_to_disparity_dev is called and at the submit of mod_submit_depth_host; a ticket in
+ *                               flight keeps the filter of its own submit; may change while tickets are outstanding.
+ *                               MOD_ERR_INVALID_ARGUMENT, the state stays as it was: a non-finite or negative z_min, z_max, tol_abs or
+ *                               tol_rel; z_max != 0 and z_max < z_min; a window not in {0, 3, 5}; with window != 0 a min_support
+ *                               outside 1 .. window * window - 1; a non-zero reserved.  With window == 0, min_support, tol_abs and
+ *                               tol_rel are ignored, but tol_abs and tol_rel are still checked for finiteness and sign.
+ *   mod_get_depth_filter        the filter in force; all zeros when it was never set or set to NULL
+ *   mod_depth_filter_dev        the stage alone: `frames` device messages stacked at step * height bytes -> depth_out, same layout, on
+ *                               the context's stream.  Not in place: depth_out != depth_in, and overlap is the caller's error.  layout
+ *                               NULL = the context's (that needs a camera); its x0, y0 are ignored, the whole message is filtered, and
+ *                               any message size passes.  filter NULL = the context's; a filter that is off copies the samples.
+ *                               depth_in NULL: MOD_SKIP_NO_DISPARITY_NOW.  Both pointers aligned to the sample size;
+ *                               frames <= ModConfig.max_frames.
+ * The filtered messages are context scratch, allocated on first use with the filter on and freed in mod_destroy.
+ * Not done: a temporal filter; an edge-preserving spatial smoother; hole filling; windows above 5; node parameters. */
+typedef struct ModDepthFilter {   /* 32 bytes; NULL, or z_min = z_max = 0 and window = 0: off (the default) */
+  float   z_min, z_max;           /* range rule, in the units of z above (metres); 0 = that bound is off */
+  int32_t window;                 /* support rule: 0 = off, else 3 or 5 */
+  int32_t min_support;            /* 1 .. window * window - 1 */
+  float   tol_abs, tol_rel;       /* >= 0, finite */
+  int32_t reserved[2];            /* must be 0 */
+} ModDepthFilter;
+int  mod_set_depth_filter(ModContext *ctx, const ModDepthFilter *filter);
+int  mod_get_depth_filter(const ModContext *ctx, ModDepthFilter *filter);
+int  mod_depth_filter_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
+                          const ModDepthFilter *filter, void *depth_out);
 
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()

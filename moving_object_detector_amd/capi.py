@@ -286,6 +286,20 @@ def depth_distortion(D) -> ModDepthDistortion:
     return ModDepthDistortion((C.c_double * 8)(*(d + [0.0] * (8 - len(d)))))
 
 
+class ModDepthFilter(C.Structure):
+    _fields_ = [("z_min", C.c_float), ("z_max", C.c_float), ("window", C.c_int32), ("min_support", C.c_int32), ("tol_abs", C.c_float),
+                ("tol_rel", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def depth_filter(z_min: float = 0.0, z_max: float = 0.0, window: int = 0, min_support: int = 3, tol_abs: float = 0.0,
+                 tol_rel: float = 0.02) -> ModDepthFilter:
+    """ModDepthFilter of mod_set_depth_filter: the range rule keeps z_min <= z <= z_max (metres; 0 = that bound is off); the support
+    rule (window 3 or 5, 0 = off) keeps a sample that at least min_support of its window's other samples agree with to within
+    tol_abs + tol_rel * z, which removes flying pixels at depth discontinuities.  The defaults are a convenience, NOT tuned on camera
+    data: choose min_support and the tolerances for the sensor at hand.  All defaults together are the filter switched off."""
+    return ModDepthFilter(float(z_min), float(z_max), int(window), int(min_support), float(tol_abs), float(tol_rel), (C.c_int32 * 2)(0, 0))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -304,6 +318,7 @@ assert C.sizeof(ModClusterMembers) == 32
 assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
+assert C.sizeof(ModDepthFilter) == 32
 assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
@@ -421,6 +436,9 @@ SIGNATURES = {
     "mod_set_depth_distortion": [_vp, C.POINTER(ModDepthDistortion)],
     "mod_get_depth_distortion": [_vp, C.POINTER(ModDepthDistortion), C.POINTER(_i32)],
     "mod_depth_rays_host": [_vp, C.POINTER(ModDepthLayout), _i32, _vp],
+    "mod_set_depth_filter": [_vp, C.POINTER(ModDepthFilter)],
+    "mod_get_depth_filter": [_vp, C.POINTER(ModDepthFilter)],
+    "mod_depth_filter_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthFilter), _vp],
     "mod_set_cluster_members": [_vp, C.POINTER(ModClusterMembers)],
     "mod_get_cluster_members": [_vp, C.POINTER(ModClusterMembers), C.POINTER(_i32)],
     "mod_set_cluster_image": [_vp, C.POINTER(ModClusterImage)],

@@ -194,6 +194,7 @@ struct StereoFrame {
   ModDepthLayout dlay;               // RGB-D: the depth message's layout at this submit, and then the staged copy's
   bool splat;                        // ... and mod_set_depth_splat's setting at this submit
   DepthRayTables rays;               // ... and mod_set_depth_distortion's tables (null: off)
+  ModDepthFilter flt;                // ... and mod_set_depth_filter's filter (all zeros: off)
 };
 
 // what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
@@ -223,16 +224,19 @@ static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout 
   return rq.rgbd ? MOD_OK : ensure_rectify_map(c, MOD_EYE_RIGHT, *lay);
 }
 
-// RGB-D: bytes of the depth message that cross PCIe (the window, packed; with a registration the whole message)
-static size_t depth_stage_bytes(const ModContext *c, const ModDepthLayout &l) {
-  return c->has_depth_reg ? (size_t)l.step * l.height : pixels(c) * depth_bytes(l.encoding);
+// RGB-D: bytes of the depth message that cross PCIe (the window, packed; with a registration the whole message; with the filter's
+// support rule on, the window's apron of window / 2 message pixels with it: at most that many either side)
+static size_t depth_stage_bytes(const ModContext *c, const ModDepthLayout &l, const ModDepthFilter &flt) {
+  if (c->has_depth_reg) return (size_t)l.step * l.height;
+  const size_t apron = 2 * (size_t)(flt.window / 2);
+  return (c->dc.W + apron) * (c->dc.H + apron) * depth_bytes(l.encoding);
 }
 
 static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   if (!rq.rgbd) HIP_TRY(c, dalloc(f.s.img, 2 * c->maxN));
   if (rq.estimates_flow()) HIP_TRY(c, dalloc(f.now.left, c->maxN));
   if (rq.rgbd) {
-    if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage_bytes(c, f.dlay))) return rc;
+    if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage_bytes(c, f.dlay, f.flt))) return rc;
     if (c->has_depth_reg) HIP_TRY(c, dalloc(f.s.zbuf, c->maxN));
   }
   if (f.img.rectify) {
@@ -246,7 +250,9 @@ static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
 }
 
 // RGB-D: the depth window (with a registration: the whole message) to the slot's stage on the copy stream, rows packed like
-// copy_window's; f.dlay becomes the layout of the staged copy
+// copy_window's; f.dlay becomes the layout of the staged copy.  With the filter's support rule on, the window's apron of R = window / 2
+// message pixels, clamped to the message, crosses with it (the Bayer region's precedent): the staged copy is then a message of its own
+// with the window at (x0, y0) <= (R, R), and every sample of the window sees the neighbours the whole message would show it
 static int upload_depth(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   Pipe &p = c->pipe;
   ModDepthLayout &l = f.dlay;
@@ -256,8 +262,11 @@ static int upload_depth(ModContext *c, const StereoRequest &rq, StereoFrame &f) 
     return MOD_OK;
   }
   const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H;
-  HIP_TRY(c, copy_window(rq.depth, l.step, l.x0, l.y0, B, W, H, f.s.depth.buf, p.h2d));
-  l.width = W; l.height = H; l.step = W * B; l.x0 = l.y0 = 0;
+  const int R = f.flt.window / 2;
+  const int ax = l.x0 < R ? l.x0 : R, ay = l.y0 < R ? l.y0 : R;                              // the apron in front of the window ...
+  const int bx = l.width - (l.x0 + W) < R ? l.width - (l.x0 + W) : R, by = l.height - (l.y0 + H) < R ? l.height - (l.y0 + H) : R;   // ... and behind
+  HIP_TRY(c, copy_window(rq.depth, l.step, l.x0 - ax, l.y0 - ay, B, W + ax + bx, H + ay + by, f.s.depth.buf, p.h2d));
+  l.width = W + ax + bx; l.height = H + ay + by; l.step = l.width * B; l.x0 = ax; l.y0 = ay;
   return MOD_OK;
 }
 
@@ -285,7 +294,9 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   HIP_TRY(c, f.now.copied_out.wait_once(c->stream));
   if (rq.rgbd) {                    // the depth conversion (depth.hip) in the estimator's place
-    if (int rc = run_depth_to_disparity(c, 1, f.s.depth.buf, f.dlay, f.splat, f.rays, f.s.zbuf, f.now.disparity)) return rc;
+    const void *msg = f.s.depth.buf;  // with a filter: the context's filtered copy (one for every slot: its writer and its reader are on the context's stream, in program order)
+    if (int rc = filter_depth_messages(c, 1, msg, f.dlay, f.flt, &msg)) return rc;
+    if (int rc = run_depth_to_disparity(c, 1, msg, f.dlay, f.splat, f.rays, f.s.zbuf, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.depth_read.record(c->stream));
   } else {
     if (int rc = mod_sgm_compute_dev(c, 1, f.img.grey0, f.img.grey1, rq.sgm, f.now.disparity)) return rc;
@@ -321,7 +332,7 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   DepthRayTables rays{nullptr, nullptr};
   int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay, &rays); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat, rays};
+  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat, rays, c->depth_filter};
   f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
   f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
   f.img.bin = c->binning; f.img.bin_grey = &f.s.bin_grey;

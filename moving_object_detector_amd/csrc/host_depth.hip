@@ -113,7 +113,68 @@ int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const M
   return MOD_OK;
 }
 
+static bool depth_filter_on(const ModDepthFilter &f) { return f.z_min != 0.0f || f.z_max != 0.0f || f.window != 0; }
+static float depth_unit(const ModDepthLayout &l) { return l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f; }
+
+// null: valid, else what is wrong with it
+static const char *check_depth_filter(const ModDepthFilter &f) {
+  for (const float v : {f.z_min, f.z_max, f.tol_abs, f.tol_rel})
+    if (!std::isfinite(v) || v < 0.0f) return "depth filter: z_min, z_max, tol_abs and tol_rel must be finite and >= 0";
+  if (f.z_max != 0.0f && f.z_max < f.z_min) return "depth filter: z_max must be 0 (unbounded) or >= z_min";
+  if (f.window != 0 && f.window != 3 && f.window != 5) return "depth filter: window must be 0 (off), 3 or 5";
+  if (f.window != 0 && (f.min_support < 1 || f.min_support > f.window * f.window - 1)) return "depth filter: min_support must be in 1 .. window * window - 1";
+  if (f.reserved[0] || f.reserved[1]) return "depth filter: reserved must be 0";
+  return nullptr;
+}
+
+int filter_depth_messages(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, const ModDepthFilter &flt, const void **out) {
+  *out = depth;
+  if (!depth_filter_on(flt)) return MOD_OK;
+  if (int rc = ensure_stage_bytes(c, c->depth_filtered, (size_t)frames * l.step * l.height)) return rc;
+  launch_depth_filter(l.encoding, l.width, l.height, frames, depth, l.step, depth_unit(l), flt, c->depth_filtered.buf, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  *out = c->depth_filtered.buf;
+  return MOD_OK;
+}
+
 extern "C" {
+
+int mod_set_depth_filter(ModContext *c, const ModDepthFilter *f) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (const char *why = f ? check_depth_filter(*f) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  c->depth_filter = f ? *f : ModDepthFilter{};
+  return MOD_OK;
+}
+
+int mod_get_depth_filter(const ModContext *c, ModDepthFilter *f) {
+  if (!c || !f) return MOD_ERR_INVALID_ARGUMENT;
+  *f = c->depth_filter;
+  return MOD_OK;
+}
+
+int mod_depth_filter_dev(ModContext *c, int32_t frames, const void *depth_in, const ModDepthLayout *layout, const ModDepthFilter *filter, void *depth_out) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
+  ModDepthLayout l;
+  if (layout) {
+    l = *layout;
+  } else {
+    if (int rc = need_camera(c)) return rc;
+    l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  }
+  l.x0 = l.y0 = 0;                  // the whole message is filtered, whatever window a path reads of it
+  if (int rc = check_depth_layout(c, l, true)) return rc;
+  if (const char *why = filter ? check_depth_filter(*filter) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  if (!depth_in) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!depth_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null depth_out");
+  if (depth_out == depth_in) return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth filter does not work in place");
+  if ((uintptr_t)depth_in % depth_bytes(l.encoding) || (uintptr_t)depth_out % depth_bytes(l.encoding))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth_in and depth_out must be aligned to the sample size");
+  launch_depth_filter(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), filter ? *filter : c->depth_filter, depth_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
 
 int mod_set_depth_layout(ModContext *c, const ModDepthLayout *l) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
@@ -176,6 +237,7 @@ int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth,
   DepthRayTables rays;
   if (int rc = depth_ray_tables(c, l, c->depth_splat, &rays)) return rc;
   if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
+  if (int rc = filter_depth_messages(c, frames, depth, l, c->depth_filter, &depth)) return rc;   // the whole messages: samples outside the window support
   return run_depth_to_disparity(c, frames, depth, l, c->depth_splat, rays, c->depth_zbuf, disparity);
 }
 

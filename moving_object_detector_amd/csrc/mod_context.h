@@ -167,6 +167,11 @@ struct ModContext {
   bool has_depth_reg = false;
   bool depth_splat = false;                 // mod_set_depth_splat: the registered path paints footprints (k_depth_register_splat)
   DevPtr<uint32_t> depth_zbuf;              // mod_depth_to_disparity_dev's z-buffer, [max_frames][maxN], allocated on first registered call
+  // mod_set_depth_filter (all zeros: off) and the filtered messages that run_depth_to_disparity reads in the messages' place: allocated
+  // on first use with the filter on, grow-only.  One for the synchronous call and every slot of the stream: k_depth_filter and the
+  // kernels that read its output are enqueued on the context's stream, back to back
+  ModDepthFilter depth_filter{};
+  RawStage depth_filtered;
   // mod_set_depth_distortion: the depth camera's lens and, per lattice (MOD_DEPTH_RAYS_*), the ray table in HBM with the lens and the
   // message size it was built for (ensure_depth_rays builds it at the next use after one of them changed, never over a table that a
   // frame in flight may read)
@@ -389,6 +394,9 @@ int current_depth_layout(ModContext *c, ModDepthLayout *out);
 // (rays: depth_ray_tables' at the same call / submit)
 int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, const DepthRayTables &rays,
                            uint32_t *zbuf, float *disparity);
+// with `flt` on: `frames` device messages of `l` through k_depth_filter into the context's scratch on the context's stream, and *out is the
+// scratch; with it off: nothing is allocated or enqueued and *out is `depth`
+int filter_depth_messages(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, const ModDepthFilter &flt, const void **out);
 // the ray tables a call / submit of layout `l` reads (mod_set_depth_distortion; both null while it is off): the centre table and, with
 // `splat`, the corner table, built behind the context's stream unless they are the cached ones.  Refused without a registration, and
 // when a table in use would have to be rebuilt while tickets are outstanding

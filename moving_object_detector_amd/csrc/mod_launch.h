@@ -222,6 +222,10 @@ const char *check_rectify_camera(const ModRectifyCamera &cam);   // null: valid,
 int depth_bytes(int encoding);      // bytes per sample; 0: unknown encoding
 void launch_depth_to_disparity(int encoding, int W, int H, int frames, const void *src, size_t frame_bytes, int step, int x0, int y0, float unit,
                                float fT, float invalid, float *dst, hipStream_t s);
+// the range and flying-pixel filter (depth_filter.hip, mod_set_depth_filter): `frames` whole width x height messages of row pitch
+// `step`, step * height bytes apart, src -> dst of the same layout (not in place); flt is valid; window 0 and both bounds 0: a copy
+void launch_depth_filter(int encoding, int width, int height, int frames, const void *src, int step, float unit, const ModDepthFilter &flt,
+                         void *dst, hipStream_t s);
 // the depth camera (of the whole message) and its pose, then the image camera whose W x H window the samples land in
 struct DepthRegArgs { double fxd, fyd, cxd, cyd, R[9], t[3], fx, fy, cx, cy, Tx, Ty; };
 // the registered path: every sample of the whole width x height messages (frames step * height bytes apart) through g into the

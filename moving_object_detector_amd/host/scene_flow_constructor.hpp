@@ -296,6 +296,9 @@ class SceneFlowConstructor {
   // a depth camera of fewer pixels than the image camera (a registration is set): every depth sample fills the image pixels inside its
   // projected footprint instead of one, depth_image_proc/register's fill_upsampling_holes; off by default, read at each submitDepth()
   void setDepthSplat(bool on) { check(mod_set_depth_splat(ctx_, on ? 1 : 0)); }
+  // the range and flying-pixel filter of the depth messages, on the depth camera's own lattice ahead of the conversion and the
+  // registration (include/mod_sf.h: ModDepthFilter); null = off (the default), read at each submitDepth()
+  void setDepthFilter(const ModDepthFilter *filter) { check(mod_set_depth_filter(ctx_, filter)); }
   // submitOdometry() for an RGB-D camera: one image (any encoding the library takes, the window at (x0, y0)) and one depth image of the
   // layout setDepthLayout() set, in the disparity estimator's place the conversion fT / depth on the GPU.  transform_prev2now null: the
   // camera motion is estimated on the GPU (collectOdometry() joins the ticket and integrates it); else the caller's (collect()).

@@ -430,6 +430,38 @@ class Context(HostCalls):
         self._done(self.lib.mod_depth_to_disparity_dev(self.h, F, dev.data_ptr(), C.byref(lay), out.data_ptr()), "mod_depth_to_disparity_dev")
         return out
 
+    def set_depth_filter(self, filter: Optional[capi.ModDepthFilter] = None) -> None:   # noqa: A002 (the ABI's name)
+        """Range and flying-pixel filter of the depth messages, on the depth camera's own lattice ahead of everything else
+        (mod_set_depth_filter, capi.depth_filter); None = off (the default).  Read when a call or a submit is made; a ticket in
+        flight keeps the filter of its submit."""
+        self._check(self.lib.mod_set_depth_filter(self.h, C.byref(filter) if filter is not None else None))
+
+    def get_depth_filter(self) -> capi.ModDepthFilter:
+        """The ModDepthFilter in force; all zeros while it is off."""
+        f = capi.ModDepthFilter()
+        self._check(self.lib.mod_get_depth_filter(self.h, C.byref(f)))
+        return f
+
+    def depth_filter(self, dev_depth: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, filter: Optional[capi.ModDepthFilter] = None,  # noqa: A002
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The filter stage alone (mod_depth_filter_dev): `dev_depth` holds F whole messages of layout.step * layout.height bytes each,
+        back to back (any dtype and shape, contiguous); the result has its dtype and shape, samples a rule removed set to "no reading"
+        (0 for 16UC1, NaN for 32FC1), everything else bit for bit; bytes of a row beyond `width` samples are not defined.  layout None =
+        the context's, filter None = the context's (off: a copy).  Not in place.  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_depth_layout()
+        if not dev_depth.is_contiguous() or dev_depth.device.type != "cuda":
+            raise ValueError("dev_depth must be a contiguous device tensor")
+        frame, nbytes = lay.step * lay.height, dev_depth.numel() * dev_depth.element_size()
+        if frame <= 0 or nbytes % frame:
+            raise ValueError("dev_depth must hold whole messages of step * height bytes")
+        if out is None:
+            out = torch.empty_like(dev_depth)
+        elif out.shape != dev_depth.shape or out.dtype != dev_depth.dtype or not out.is_contiguous() or out.device != dev_depth.device:
+            raise ValueError("out must be a contiguous device tensor of dev_depth's shape and dtype")
+        self._done(self.lib.mod_depth_filter_dev(self.h, nbytes // frame, dev_depth.data_ptr(), C.byref(lay),
+                                                 C.byref(filter) if filter is not None else None, out.data_ptr()), "mod_depth_filter_dev")
+        return out
+
     def _whole_messages(self, t: torch.Tensor, lay, out: Optional[torch.Tensor], out_dtype, name: str, unit: str):
         """(F, out) for a contiguous device tensor `t` holding F whole messages of lay.step * lay.height bytes (uint8 where the output
         is; any dtype for depth) and the (F, H, W) tensor the call writes, `out` or a new one."""

@@ -9,7 +9,12 @@ the median and the spread (largest - smallest) of each.
 3.5, -5e-5, 1e-4, 0.18, 5.7, 5.2, 0.95) under the 1280 x 720 camera, with the splat off and on: k_depth_rays per rebuild (a one-frame
 call whose D alternates, so that every call rebuilds its tables, less the same call with the tables cached), the registered path per
 frame with and without the distortion, alternating in one process, and the depth stream in frames/s with and without it.
-Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted]"""
+--filter [--filter-window 3|5] [--filter-size WxH]: mod_set_depth_filter (k_depth_filter, csrc/depth_filter.hip) on 64 16UC1 messages of
+1280 x 720 (or 640x576, the Kinect-like case) per call: the kernel alone (mod_depth_filter_dev) in ms and TB/s of its algorithmic 4 B a
+sample, with the share of 8 TB/s, k_depth_to_disparity beside it in the same run, the two alternating for ROUNDS rounds; then the depth
+stream in frames/s with the filter off and on, alternating likewise (at 640x576: the registered Kinect-like message under the 1280 x 720
+camera).  The scene is a wall with boxes in front of it and flying pixels at their sides.
+Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter]"""
 import ctypes as C
 import functools
 import json
@@ -176,13 +181,51 @@ def kernels_distorted(reps):
     ctx.close()
 
 
+def filter_of(capi, window):
+    return capi.depth_filter(z_min=0.3, z_max=7.5, window=window, min_support=3 if window == 3 else 7, tol_abs=0.005, tol_rel=0.02)
+
+
+def kernels_filter(reps, window, fw, fh):
+    """k_depth_filter alone and k_depth_to_disparity on the same F 16UC1 messages of fw x fh"""
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(fw, fh, max_frames=F)
+    ctx.set_camera(synth.make_camera(fw, fh))
+    rng = np.random.default_rng(0)
+    mm = np.full((F, fh, fw), 4000, np.uint16) + rng.integers(-15, 16, size=(F, fh, fw)).astype(np.uint16)
+    for k in range(12):                                            # boxes at 2 m with a column of flying pixels either side
+        y, x = int(rng.integers(0, fh - 80)), int(rng.integers(2, fw - 122))
+        mm[:, y:y + 80, x:x + 120] = 2000
+        mm[:, y:y + 80, x - 1] = 2700
+        mm[:, y:y + 80, x + 120] = 3300
+    mm[rng.random((F, fh, fw)) < 0.02] = 0
+    src = torch.from_numpy(mm.view(np.int16)).to(ctx.device)
+    dst = torch.empty_like(src)
+    out = torch.empty((F, fh, fw), dtype=torch.float32, device=ctx.device)
+    lay, flt = capi.depth_layout("16UC1", fw, fh), filter_of(capi, window)
+    ms = {"filter": [], "convert": []}
+    for _ in range(ROUNDS):
+        ms["filter"].append(timed(torch, lambda: ctx.lib.mod_depth_filter_dev(ctx.h, F, src.data_ptr(), C.byref(lay), C.byref(flt), dst.data_ptr()), reps))
+        ms["convert"].append(timed(torch, lambda: ctx.lib.mod_depth_to_disparity_dev(ctx.h, F, src.data_ptr(), C.byref(lay), out.data_ptr()), reps))
+    ctx.synchronize()
+    removed = float(((dst[0] == 0) & (src[0] != 0)).float().mean().item())
+    for what, key, bytes_ in (("k_depth_filter", "filter", 4), ("k_depth_to_disparity", "convert", 6)):
+        med = float(np.median(ms[key]))
+        tb = F * fw * fh * bytes_ / med / 1e9
+        print(json.dumps({"what": what, "encoding": "16UC1", "window": window if key == "filter" else None, "W": fw, "H": fh, "frames": F,
+                          "bytes_per_sample": bytes_, "ms_per_call": spread(ms[key]), "TB_per_s": round(tb, 3), "share_of_8_TB_per_s": round(tb / 8.0, 3),
+                          "removed_share_of_frame_0": round(removed, 4) if key == "filter" else None}), flush=True)
+    ctx.close()
+
+
 @functools.lru_cache(maxsize=None)
 def ego_images():
     from moving_object_detector_amd import synth
     return synth.make_ego_images(W, H, seed=1, frames=2)
 
 
-def stream_fps(reps, splat=None, kinect=None):
+def stream_fps(reps, splat=None, kinect=None, filter_window=None):
     """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on;
     kinect 0 / 1: the message is the Kinect-like camera's 640 x 576 instead, without / with its distortion"""
     from moving_object_detector_amd import capi, synth
@@ -203,6 +246,8 @@ def stream_fps(reps, splat=None, kinect=None):
         ctx.set_depth_registration(kinect_registration(capi))
         ctx.set_depth_layout(capi.depth_layout("16UC1", KW, KH))
         ctx.set_depth_distortion(capi.depth_distortion(KINECT_D) if kinect else None)
+    if filter_window:
+        ctx.set_depth_filter(filter_of(capi, filter_window))
     fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
     fp, ep = capi.flow_params(), capi.ego_params()
     pins = []
@@ -218,14 +263,37 @@ def stream_fps(reps, splat=None, kinect=None):
         assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
 
     # the alternating rounds want a window of a good half second
-    fps = stream_rate(s, step, max(20, reps) if splat is None else max(300, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
+    fps = stream_rate(s, step, max(20, reps) if splat is None and filter_window is None else max(300, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
     ctx.close()
     return fps
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a not in ("--splat", "--distorted")]
+    argv = sys.argv[1:]
+    window, size = 3, (W, H)
+    for flag in ("--filter-window", "--filter-size"):
+        if flag in argv:
+            i = argv.index(flag)
+            value = argv[i + 1]
+            del argv[i:i + 2]
+            if flag == "--filter-window":
+                window = int(value)
+            else:
+                size = tuple(int(v) for v in value.lower().split("x"))
+    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter")]
     reps = int(args[0]) if args else 50
+    if "--filter" in argv:
+        assert window in (3, 5) and size in ((W, H), (KW, KH)), "--filter-window 3 or 5; --filter-size 1280x720 or 640x576"
+        kernels_filter(reps, window, *size)
+        kinect = 0 if size == (KW, KH) else None
+        fps = {0: [], window: []}
+        for _ in range(ROUNDS):
+            for w in (0, window):
+                fps[w].append(stream_fps(reps, None, kinect, w))
+        for w in (0, window):
+            print(json.dumps({"what": "mod_submit_depth_host" + (", 640 x 576 registered depth message" if kinect is not None else ""), "filter_window": w,
+                              "image": "bgr8", "depth": "16UC1", "kind": "odometry", "W": W, "H": H, "frames_per_s": spread(fps[w])}), flush=True)
+        return
     if "--distorted" in sys.argv[1:]:
         kernels_distorted(reps)
         configs = [(d, on) for on in (0, 1) for d in (0, 1)]
