@@ -1,7 +1,6 @@
-// mod_context.h — the context behind the C ABI and what its host-side files share (internal to libmod_sf.so, not installed):
-// mod_sf.hip (lifecycle, the batched scene-flow / cluster path), estimators.hip (SGM, flow, ego-motion), host_images.hip (image
-// layouts, rectification, the host images' way to grey), host_depth.hip (depth layouts, registration, ray tables, depth to
-// disparity), host_api.hip (*_host calls).
+// mod_context.h — the context behind the C ABI and what its host-side files share (internal to libmod_sf.so, not installed): mod_sf.hip (lifecycle, the batched scene-flow /
+// cluster path), host_sgm.hip, host_flow.hip, host_ego.hip (the estimators), host_filters.hip (their stand-alone filters), host_images.hip (image layouts, rectification, the
+// host images' way to grey), host_depth.hip (depth layouts, registration, ray tables, depth to disparity), host_api.hip (*_host calls).
 #pragma once
 #include "../../include/mod_sf.h"
 #include "frame_const.h"
@@ -87,7 +86,7 @@ struct Buffers {
     // the aggregation paths are independent of each other: they run side by side on these streams (forked from / joined to the
     // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
     Stream side[kSgmPaths];
-    Event fork[2], join[2][kSgmPaths];      // per set (estimators.hip SgmSet)
+    Event fork[2], join[2][kSgmPaths];      // per set (host_sgm.hip SgmSet)
   } sgm;
   // speckle filter (disparity_filter.hip): union-find parents and region sizes of its own, [frames][maxN] each — a group of the
   // estimator or max_frames of mod_disparity_speckle_dev; allocated on first use with the filter on, grow-only (ensure_speckle_scratch)
@@ -107,6 +106,14 @@ struct Buffers {
   } ego;
 };
 
+// The options of the two image estimators, one member per mod_set_* / mod_get_* pair and named like it (host_options.h); these initialisers are the defaults.
+// Read when a call or submit enqueues its estimator; every kernel of the call is enqueued from the snapshot.  A zero threshold / window / speckle_size: that stage is off
+struct EstimatorOptions {
+  int32_t disparity_subpixel = 0, disparity_offset = 0; ModDisparityFilters disparity_filters{};   // disparity: fraction bits; where the window starts (mod_sgm_path_dev reads it too)
+  ModTextureFilter texture_filter{0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW};             // both, as `apply` says
+  int32_t flow_propagation = 1; ModCornerFilter flow_corner_filter{0, 9, 31, 0}; ModFlowMedian flow_median{};   // flow: seeds of a search (1: the parent's winner alone)
+};
+
 // Every resource is a member handle: mod_destroy synchronizes the streams below, and `delete` releases the rest.
 struct ModContext {
   ModConfig cfg{};
@@ -119,15 +126,7 @@ struct ModContext {
   // mod_set_image_binning: read when a call / submit is made ({1, 1, ..}: off).  The window every layout is checked against, the
   // converters run at and a rectification map is built for is then the full one, (bx W) x (by H): full_window()
   ModImageBinning binning{1, 1, MOD_BIN_MEAN, 0};
-  int32_t sgm_fraction_bits = 0;            // mod_set_disparity_subpixel: read by mod_sgm_compute_dev when a call / submit enqueues its kernels
-  ModDisparityFilters sgm_filters{};        // mod_set_disparity_filters: read at the same moment (all zero: off)
-  int32_t sgm_offset = 0;                   // mod_set_disparity_offset: read at the same moment, and by mod_sgm_path_dev (0: the window starts at 0)
-  // mod_set_texture_filter: read when a call / submit enqueues its disparity or flow estimator (threshold 0: off, nothing is enqueued)
-  ModTextureFilter texture{0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW};
-  // mod_set_flow_corner_filter: read when a call / submit enqueues its flow estimator (threshold 0: off, nothing is enqueued)
-  ModCornerFilter corner{0, 9, 31, 0};
-  // mod_set_flow_median: read at the same moment (window 0: off, nothing is allocated or enqueued)
-  ModFlowMedian median{};
+  EstimatorOptions opt;
   // mod_set_cluster_members: read by the calls that write the lists when they enqueue the cluster stage (members_on false: off)
   ModClusterMembers members{};
   bool members_on = false;
@@ -137,7 +136,6 @@ struct ModContext {
   bool image_on = false;
   label_palette::Table image_table{};
   uint8_t image_bytes[3 * label_palette::kEntries] = {};
-  int32_t flow_seeds = 1;                   // mod_set_flow_propagation: read by mod_flow_compute_dev when a call / submit enqueues its kernels
   // mod_set_rectification: the calibrations and, per eye, the map in HBM with the window and the distortion model it was built for
   // (ensure_rectify_map builds it at the next use after the window, the calibration or the model changed, never under a frame in flight)
   struct Rectify {
@@ -402,12 +400,14 @@ int filter_depth_messages(ModContext *c, int frames, const void *depth, const Mo
 // when a table in use would have to be rebuilt while tickets are outstanding
 int depth_ray_tables(ModContext *c, const ModDepthLayout &l, bool splat, DepthRayTables *out);
 
-// estimators.hip
+// host_sgm.hip
 int check_sgm_params(ModContext *c, const ModSgmParams *p);
+// host_flow.hip
 int check_flow_params(ModContext *c, const ModFlowParams *p, int frames);
+// host_filters.hip
+inline bool texture_applies(const ModTextureFilter &f, int to) { return f.threshold > 0 && (f.apply & to) != 0; }   // to: MOD_TEXTURE_DISPARITY / _FLOW
+int ensure_speckle_scratch(ModContext *c, int frames);   // the speckle filter's planes for `frames` frames (grow-only)
+// host_ego.hip
 int check_ego_params(ModContext *c, const ModEgoParams *p);
-int check_disparity_filters(ModContext *c, const ModDisparityFilters *f);
-// the ego-motion estimator over `frames` frames; tf == null: into b.ego.tf, res == null: into b.ego.res; fc != null: also the frames'
-// scene-flow constants (with dt) into fc
-int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p,
-                  ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt);
+// the ego-motion estimator over `frames` frames; tf == null: into b.ego.tf, res == null: into b.ego.res; fc != null: also the frames' scene-flow constants (with dt) into fc
+int run_egomotion(ModContext *c, int frames, const float *dprev, const float *dnow, const float *flow, const ModEgoParams *p, ModTransform *tf, ModEgoResult *res, FrameConst *fc, double dt);

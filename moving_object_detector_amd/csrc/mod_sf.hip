@@ -1,6 +1,6 @@
 // mod_sf.hip — C ABI (include/mod_sf.h) over the gfx950 kernels: context lifecycle, camera and parameters, the batched scene-flow /
 // cluster / process path, parameter folding, stage timers, memory helpers.  Host-side only; the kernels live in sceneflow.hip and
-// the clusterer's ccl_*.hip / cluster_*.hip, the estimators in estimators.hip, image input in host_images.hip, depth input in host_depth.hip, the *_host calls in host_api.hip.
+// the clusterer's ccl_*.hip / cluster_*.hip, the estimators in host_sgm.hip / host_flow.hip / host_ego.hip and their stand-alone filters in host_filters.hip, image input in host_images.hip, depth input in host_depth.hip, the *_host calls in host_api.hip.
 #include "mod_context.h"
 #include "exact_div.h"
 #include "flow_color.h"

@@ -1,5 +1,5 @@
 """The batches, edge shapes and option rows tests/test_estimator_chain_cases.py (CPU: what every case reaches, from the models alone)
-and tests/test_gpu_estimator_chains.py (GPU: the filter chains of csrc/estimators.hip against tests/models/estimator_chain_model.py,
+and tests/test_gpu_estimator_chains.py (GPU: the filter chains of csrc/host_sgm.hip and host_flow.hip against tests/models/estimator_chain_model.py,
 bit for bit) share.  A plain module, not a conftest: no fixtures, numpy only, every input generated deterministically.
 
 Disparity.  An option row is a chain_model.SgmSettings: paths, lr_check, median, fraction bits, uniqueness, offset, texture, speckle.

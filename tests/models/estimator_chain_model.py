@@ -1,4 +1,4 @@
-"""The two estimator chains as csrc/estimators.hip enqueues them (sgm_finish; mod_flow_compute_dev), composed of the models of their
+"""The two estimator chains as csrc/host_sgm.hip and host_flow.hip enqueue them (sgm_finish; flow_finish), composed of the models of their
 stages and of nothing else.  TEST INFRASTRUCTURE ONLY.
 
   disparity   winner-take-all, uniqueness, sub-pixel, 3 x 3 median, left-right check   sgm_filters_model.compute (with an offset:

@@ -1,6 +1,6 @@
 """GPU: a context whose capacity (ModConfig) is larger than its camera.  The cluster scratch is allocated, cleared and grown for the
 capacity, while the frames of a call lie the camera's strides apart inside it (mod_sf.hip: cluster_alloc, cluster_carve); the flow
-estimator's level regions are sized for the capacity and walked with the camera's sizes (estimators.hip: FlowPlan).  Every other test
+estimator's level regions are sized for the capacity and walked with the camera's sizes (host_flow.hip: FlowPlan).  Every other test
 sizes its context exactly to its camera and batch, where the two kinds of stride cannot differ.  Every comparison here is bit for bit,
 against a fresh context sized exactly to the call and run in one chunk, and at chunk borders against the oracle."""
 import functools

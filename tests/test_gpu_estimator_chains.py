@@ -1,5 +1,5 @@
-"""GPU: the filter chains behind the two image estimators, as csrc/estimators.hip strings their stages together (sgm_finish: winner-take-
-all .. left-right check, texture rule, speckle filter, per GROUP of frames and under a disparity offset; mod_flow_compute_dev: finish,
+"""GPU: the filter chains behind the two image estimators, as csrc/host_sgm.hip and host_flow.hip string their stages together (sgm_finish: winner-take-
+all .. left-right check, texture rule, speckle filter, per GROUP of frames and under a disparity offset; flow_finish: finish,
 texture rule, min-eigenvalue rule, median through the scratch plane), through the C ABI, bit for bit (uint32 views) against
 tests/models/estimator_chain_model.py on the cases of tests/estimator_chain_cases.py.  What the cases reach — the option lists are
 pairwise complete, no frame of a batch can pass with another group's image, every stage changes something — is asserted on the CPU, from
