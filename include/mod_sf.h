@@ -1028,7 +1028,7 @@ int  mod_depth_rays_host(ModContext *ctx, const ModDepthLayout *layout, int32_t 
  *                               depth_in NULL: MOD_SKIP_NO_DISPARITY_NOW.  Both pointers aligned to the sample size;
  *                               frames <= ModConfig.max_frames.
  * The filtered messages are context scratch, allocated on first use with the filter on and freed in mod_destroy.
- * Not done: a temporal filter; an edge-preserving spatial smoother; hole filling; windows above 5; node parameters. */
+ * Not done: an edge-preserving spatial smoother; hole filling; windows above 5; node parameters.  (The temporal filter: below.) */
 typedef struct ModDepthFilter {   /* 32 bytes; NULL, or z_min = z_max = 0 and window = 0: off (the default) */
   float   z_min, z_max;           /* range rule, in the units of z above (metres); 0 = that bound is off */
   int32_t window;                 /* support rule: 0 = off, else 3 or 5 */
@@ -1040,6 +1040,65 @@ int  mod_set_depth_filter(ModContext *ctx, const ModDepthFilter *filter);
 int  mod_get_depth_filter(const ModContext *ctx, ModDepthFilter *filter);
 int  mod_depth_filter_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
                           const ModDepthFilter *filter, void *depth_out);
+/* The temporal depth filter with hold (mod_set_depth_temporal, opt-in, off by default; while it is off nothing is allocated and every
+ * call enqueues exactly what it enqueues without this section).  The scene-flow stage differences two consecutive disparity planes, so
+ * a depth camera's frame-to-frame noise goes straight into vz = dz / dt, and a pixel that drops out for a frame punches a hole into
+ * both the `now` and the next `previous` plane.  This stage smooths each pixel over time where the scene stands still, restarts where it
+ * changed, and can repeat a pixel's last average for a few frames.  It maps depth messages to depth messages of the same encoding,
+ * width, height and step, behind the depth filter above (samples that filter removed never enter the state) and in front of the
+ * registration, the distortion, the splat and the conversion.  In idea it is librealsense's temporal filter with persistence and the
+ * Azure Kinect's post-processing; the rule is this library's own and parity with no SDK is claimed.
+ * State, one per context, on the lattice of the messages the stage is handed, packed height x width whatever `step` is:
+ *   s    F32, in raw units (the units of x below)
+ *   age  u8: the consecutive frames without a reading since the last valid one; 255 = empty.  An empty pixel stores s = 0.0f.
+ * The rule.  All F32, one operation at a time, -ffp-contract=off.  For a message pixel with input word w:
+ *   x = (float)w for 16UC1, x = value for 32FC1;  z = x * unit (unit == 0: the encoding's default);  valid0(z) iff z > 0.0f and z is finite
+ *   enc(s): 16UC1: (uint16)min(max(rintf(s), 1.0f), 65535.0f), ties to even;  32FC1: the bits of s
+ * Frames of one call are consecutive in time, frame 0 oldest; calls and submits follow in program order.  Per pixel and frame:
+ *   valid0 and empty state:       s = x, age = 0.  The output is w, bit for bit.
+ *   valid0 and non-empty state:   zs = s * unit;  t = delta_abs + delta_rel * zs             (one multiply, then one add)
+ *                                 if fabsf(z - zs) <= t:  s = s + alpha * (x - s)            (subtract, multiply, add)
+ *                                 otherwise:              s = x                              (the scene changed: restart)
+ *                                 in both cases age = 0 and the output is enc(s); when s == x that is the input word.
+ *   not valid0, state non-empty and age < hold:   age += 1.  The output is enc(s), a held value.
+ *   not valid0 otherwise:         the state becomes empty (age = 255, s = 0.0f).  The output is w, bit for bit: NaN payloads, -0.0,
+ *                                 negatives and +-inf pass through, as in the depth filter.
+ * Consequences: alpha == 1 with hold == 0 is the identity, bit for bit.  Only hold > 0 ever fills a hole.  Bytes of a row beyond `width`
+ * samples are not defined.  tests/models/depth_temporal_model.py restates the rule word for word.
+ * The context's state empties (the next launch neither reads nor trusts the planes: no memset races the stream) on every successful
+ * mod_set_depth_temporal, on mod_reset_depth_temporal, on mod_forget_previous, when a depth submit is skipped for a NULL image or
+ * depth, and when the geometry the stage sees changes: encoding, width, height, unit and, for the stream's staged window copy, the
+ * staged region's origin in the camera's message (it moves with x0 / y0 and with the depth filter's apron).  The synchronous call and
+ * the stream share the one state, in program order on the context's stream.
+ *   mod_set_depth_temporal      NULL or alpha == 0: off (the default).  Read when mod_depth_to_disparity_dev is called and at the submit
+ *                               of mod_submit_depth_host; a ticket in flight keeps the parameters of its own submit; may change while
+ *                               tickets are outstanding.  MOD_ERR_INVALID_ARGUMENT, parameters and state stay as they were: alpha
+ *                               outside [0, 1] or NaN; a non-finite or negative delta_abs or delta_rel; hold outside 0 .. 254; a
+ *                               non-zero reserved.
+ *   mod_get_depth_temporal      the parameters in force; all zeros while it is off
+ *   mod_reset_depth_temporal    empties the context's state, nothing else
+ *   mod_depth_temporal_dev      the stage alone: `frames` consecutive device messages stacked at step * height bytes -> depth_out, same
+ *                               layout, on the context's stream.  state_s (float[height * width]) and state_age (uint8[height * width])
+ *                               are caller-owned device planes, updated in place (to start empty, fill state_age with 255); both NULL =
+ *                               the context's state; one NULL is an error.  depth_out == depth_in is allowed: the rule is pointwise.
+ *                               layout NULL = the context's (that needs a camera); its x0, y0 are ignored and any message size passes.
+ *                               filter NULL = the context's; a filter that is off copies the samples and touches no state.
+ *                               depth_in NULL: MOD_SKIP_NO_DISPARITY_NOW.  The messages aligned to the sample size, state_s to 4 bytes;
+ *                               frames <= ModConfig.max_frames.
+ * The state planes are allocated on first use with the filter on and freed in mod_destroy.  The library never writes a caller's input:
+ * it works in place on its own copies (the filtered scratch, the slot's staged copy) or writes the filtered scratch.
+ * Not done: motion-compensated state (the state is per pixel of the depth camera: under camera motion the gate restarts it); fusion
+ * with k_depth_filter in one kernel; node parameters. */
+typedef struct ModDepthTemporal {   /* 32 bytes; NULL or alpha == 0: off (the default) */
+  float alpha, delta_abs, delta_rel;   /* the average's weight of the new sample, in (0, 1]; the gate, in the units of z (metres), >= 0 */
+  int32_t hold;                        /* 0 .. 254: the frames a pixel without a reading repeats its average */
+  int32_t reserved[4];                 /* must be 0 */
+} ModDepthTemporal;
+int  mod_set_depth_temporal(ModContext *ctx, const ModDepthTemporal *filter);
+int  mod_get_depth_temporal(const ModContext *ctx, ModDepthTemporal *filter);
+int  mod_reset_depth_temporal(ModContext *ctx);
+int  mod_depth_temporal_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
+                            const ModDepthTemporal *filter, float *state_s, uint8_t *state_age, void *depth_out);
 
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()

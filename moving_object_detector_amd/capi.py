@@ -300,6 +300,19 @@ def depth_filter(z_min: float = 0.0, z_max: float = 0.0, window: int = 0, min_su
     return ModDepthFilter(float(z_min), float(z_max), int(window), int(min_support), float(tol_abs), float(tol_rel), (C.c_int32 * 2)(0, 0))
 
 
+class ModDepthTemporal(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("delta_abs", C.c_float), ("delta_rel", C.c_float), ("hold", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+
+def depth_temporal(alpha: float = 0.4, delta_abs: float = 0.02, delta_rel: float = 0.0, hold: int = 0) -> ModDepthTemporal:
+    """ModDepthTemporal of mod_set_depth_temporal: per pixel an exponential moving average over the frames, s += alpha * (x - s), while
+    the new depth stays within delta_abs + delta_rel * z (metres) of the average, a restart at the new sample where it does not; a
+    pixel without a reading repeats its average for at most `hold` frames (0: never, 254 at most).  alpha = 0 is the filter switched
+    off; alpha = 1 with hold = 0 is the identity.  The defaults are a convenience, NOT tuned on camera data: choose alpha and the gate
+    for the sensor's noise and the scene's motion."""
+    return ModDepthTemporal(float(alpha), float(delta_abs), float(delta_rel), int(hold), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -319,6 +332,7 @@ assert MOD_OBJECT_BYTES == 112
 assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 assert C.sizeof(ModDepthFilter) == 32
+assert C.sizeof(ModDepthTemporal) == 32
 assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
@@ -439,6 +453,10 @@ SIGNATURES = {
     "mod_set_depth_filter": [_vp, C.POINTER(ModDepthFilter)],
     "mod_get_depth_filter": [_vp, C.POINTER(ModDepthFilter)],
     "mod_depth_filter_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthFilter), _vp],
+    "mod_set_depth_temporal": [_vp, C.POINTER(ModDepthTemporal)],
+    "mod_get_depth_temporal": [_vp, C.POINTER(ModDepthTemporal)],
+    "mod_reset_depth_temporal": [_vp],
+    "mod_depth_temporal_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthTemporal), _vp, _vp, _vp],
     "mod_set_cluster_members": [_vp, C.POINTER(ModClusterMembers)],
     "mod_get_cluster_members": [_vp, C.POINTER(ModClusterMembers), C.POINTER(_i32)],
     "mod_set_cluster_image": [_vp, C.POINTER(ModClusterImage)],

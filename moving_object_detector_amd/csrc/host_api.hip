@@ -195,6 +195,8 @@ struct StereoFrame {
   bool splat;                        // ... and mod_set_depth_splat's setting at this submit
   DepthRayTables rays;               // ... and mod_set_depth_distortion's tables (null: off)
   ModDepthFilter flt;                // ... and mod_set_depth_filter's filter (all zeros: off)
+  ModDepthTemporal tmp;              // ... and mod_set_depth_temporal's (all zeros: off)
+  int dox, doy;                      // ... and the origin of the staged copy in the camera's depth message (upload_depth)
 };
 
 // what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
@@ -212,6 +214,7 @@ static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout 
   if (!rq.left || (rq.rgbd ? !rq.depth : !rq.right && !c->side_by_side)) {
     c->pipe.have_prev = false;      // ... which becomes the next frame's (missing) previous disparity (:397-398)
     c->pipe.have_prev_img = false;  // ... and the next frame has no previous image to estimate the flow from
+    if (rq.rgbd) c->depth_tstate.fresh = true;   // ... and the temporal depth filter starts over with it
     return MOD_SKIP_NO_DISPARITY_NOW;
   }
   if (int rc = rq.rgbd ? MOD_OK : check_sgm_params(c, rq.sgm)) return rc;
@@ -266,6 +269,7 @@ static int upload_depth(ModContext *c, const StereoRequest &rq, StereoFrame &f) 
   const int ax = l.x0 < R ? l.x0 : R, ay = l.y0 < R ? l.y0 : R;                              // the apron in front of the window ...
   const int bx = l.width - (l.x0 + W) < R ? l.width - (l.x0 + W) : R, by = l.height - (l.y0 + H) < R ? l.height - (l.y0 + H) : R;   // ... and behind
   HIP_TRY(c, copy_window(rq.depth, l.step, l.x0 - ax, l.y0 - ay, B, W + ax + bx, H + ay + by, f.s.depth.buf, p.h2d));
+  f.dox = l.x0 - ax; f.doy = l.y0 - ay;
   l.width = W + ax + bx; l.height = H + ay + by; l.step = l.width * B; l.x0 = ax; l.y0 = ay;
   return MOD_OK;
 }
@@ -296,6 +300,7 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   if (rq.rgbd) {                    // the depth conversion (depth.hip) in the estimator's place
     const void *msg = f.s.depth.buf;  // with a filter: the context's filtered copy (one for every slot: its writer and its reader are on the context's stream, in program order)
     if (int rc = filter_depth_messages(c, 1, msg, f.dlay, f.flt, &msg)) return rc;
+    if (int rc = temporal_depth_messages(c, 1, msg, true, f.dlay, f.dox, f.doy, f.tmp, &msg)) return rc;   // in place: the slot's stage or the filtered scratch
     if (int rc = run_depth_to_disparity(c, 1, msg, f.dlay, f.splat, f.rays, f.s.zbuf, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.depth_read.record(c->stream));
   } else {
@@ -332,7 +337,7 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   DepthRayTables rays{nullptr, nullptr};
   int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay, &rays); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat, rays, c->depth_filter};
+  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat, rays, c->depth_filter, c->depth_temporal, 0, 0};
   f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
   f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
   f.img.bin = c->binning; f.img.bin_grey = &f.s.bin_grey;
@@ -587,6 +592,7 @@ int mod_forget_previous(ModContext *c) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   c->pipe.have_prev = false;
   c->pipe.have_prev_img = false;
+  c->depth_tstate.fresh = true;     // the temporal depth filter's state goes with the previous disparity
   return MOD_OK;
 }
 

@@ -137,7 +137,110 @@ int filter_depth_messages(ModContext *c, int frames, const void *depth, const Mo
   return MOD_OK;
 }
 
+static bool depth_temporal_on(const ModDepthTemporal &t) { return t.alpha != 0.0f; }
+
+// null: valid, else what is wrong with it
+static const char *check_depth_temporal(const ModDepthTemporal &t) {
+  if (!(t.alpha >= 0.0f && t.alpha <= 1.0f)) return "depth temporal filter: alpha must be 0 (off) or in (0, 1]";
+  for (const float v : {t.delta_abs, t.delta_rel})
+    if (!std::isfinite(v) || v < 0.0f) return "depth temporal filter: delta_abs and delta_rel must be finite and >= 0";
+  if (t.hold < 0 || t.hold > 254) return "depth temporal filter: hold must be in 0 .. 254";
+  for (const int32_t v : t.reserved) if (v) return "depth temporal filter: reserved must be 0";
+  return nullptr;
+}
+
+// the context's state planes for messages of `l` whose origin in the camera's message is (ox, oy): grown where they are too small,
+// and marked fresh where the geometry differs from the last launch's
+static int context_temporal_state(ModContext *c, const ModDepthLayout &l, int ox, int oy) {
+  ModContext::DepthTemporalState &st = c->depth_tstate;
+  const float unit = depth_unit(l);
+  if (st.encoding != l.encoding || st.width != l.width || st.height != l.height || st.unit != unit || st.ox != ox || st.oy != oy) st.fresh = true;
+  st.encoding = l.encoding; st.width = l.width; st.height = l.height; st.unit = unit; st.ox = ox; st.oy = oy;
+  const size_t n = (size_t)l.width * l.height;
+  if (st.s.bytes < 4 * n || st.age.bytes < n) st.fresh = true;    // new planes hold nothing
+  if (int rc = ensure_stage_bytes(c, st.s, 4 * n)) return rc;
+  return ensure_stage_bytes(c, st.age, n);
+}
+
+int temporal_depth_messages(ModContext *c, int frames, const void *depth, bool writable, const ModDepthLayout &l, int ox, int oy,
+                            const ModDepthTemporal &t, const void **out) {
+  *out = depth;
+  if (!depth_temporal_on(t)) return MOD_OK;
+  void *dst = const_cast<void *>(depth);   // (written only when the caller says it is the library's own copy)
+  if (!writable) {
+    if (int rc = ensure_stage_bytes(c, c->depth_filtered, (size_t)frames * l.step * l.height)) return rc;
+    dst = c->depth_filtered.buf;
+  }
+  if (int rc = context_temporal_state(c, l, ox, oy)) return rc;
+  ModContext::DepthTemporalState &st = c->depth_tstate;
+  launch_depth_temporal(l.encoding, l.width, l.height, frames, depth, l.step, depth_unit(l), t, st.fresh, reinterpret_cast<float *>(st.s.buf.get()),
+                        st.age.buf, dst, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  st.fresh = false;
+  *out = dst;
+  return MOD_OK;
+}
+
 extern "C" {
+
+int mod_set_depth_temporal(ModContext *c, const ModDepthTemporal *t) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (const char *why = t ? check_depth_temporal(*t) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  c->depth_temporal = t && depth_temporal_on(*t) ? *t : ModDepthTemporal{};
+  c->depth_tstate.fresh = true;     // every successful call empties the state, in stream order: the next launch does not read it
+  return MOD_OK;
+}
+
+int mod_get_depth_temporal(const ModContext *c, ModDepthTemporal *t) {
+  if (!c || !t) return MOD_ERR_INVALID_ARGUMENT;
+  *t = c->depth_temporal;
+  return MOD_OK;
+}
+
+int mod_reset_depth_temporal(ModContext *c) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  c->depth_tstate.fresh = true;
+  return MOD_OK;
+}
+
+int mod_depth_temporal_dev(ModContext *c, int32_t frames, const void *depth_in, const ModDepthLayout *layout, const ModDepthTemporal *filter,
+                           float *state_s, uint8_t *state_age, void *depth_out) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
+  ModDepthLayout l;
+  if (layout) {
+    l = *layout;
+  } else {
+    if (int rc = need_camera(c)) return rc;
+    l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  }
+  l.x0 = l.y0 = 0;                  // the whole message is filtered, whatever window a path reads of it
+  if (int rc = check_depth_layout(c, l, true)) return rc;
+  if (const char *why = filter ? check_depth_temporal(*filter) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  if (!state_s != !state_age) return fail(c, MOD_ERR_INVALID_ARGUMENT, "state_s and state_age must both be given or both be NULL (the context's state)");
+  if (!depth_in) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!depth_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null depth_out");
+  if ((uintptr_t)depth_in % depth_bytes(l.encoding) || (uintptr_t)depth_out % depth_bytes(l.encoding) || (uintptr_t)state_s % 4)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth_in and depth_out must be aligned to the sample size and state_s to 4 bytes");
+  const ModDepthTemporal t = filter ? *filter : c->depth_temporal;
+  if (!depth_temporal_on(t)) {      // off: a copy; no state is touched
+    if (depth_out != depth_in) HIP_TRY(c, hipMemcpyAsync(depth_out, depth_in, (size_t)frames * l.step * l.height, hipMemcpyDeviceToDevice, c->stream));
+    return MOD_OK;
+  }
+  const bool own = !state_s;
+  bool fresh = false;
+  if (own) {
+    if (int rc = context_temporal_state(c, l, 0, 0)) return rc;
+    state_s = reinterpret_cast<float *>(c->depth_tstate.s.buf.get());
+    state_age = c->depth_tstate.age.buf;
+    fresh = c->depth_tstate.fresh;
+  }
+  launch_depth_temporal(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), t, fresh, state_s, state_age, depth_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  if (own) c->depth_tstate.fresh = false;
+  return MOD_OK;
+}
 
 int mod_set_depth_filter(ModContext *c, const ModDepthFilter *f) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
@@ -237,7 +340,9 @@ int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth,
   DepthRayTables rays;
   if (int rc = depth_ray_tables(c, l, c->depth_splat, &rays)) return rc;
   if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
+  const void *const given = depth;
   if (int rc = filter_depth_messages(c, frames, depth, l, c->depth_filter, &depth)) return rc;   // the whole messages: samples outside the window support
+  if (int rc = temporal_depth_messages(c, frames, depth, depth != given, l, 0, 0, c->depth_temporal, &depth)) return rc;   // never into the caller's input
   return run_depth_to_disparity(c, frames, depth, l, c->depth_splat, rays, c->depth_zbuf, disparity);
 }
 

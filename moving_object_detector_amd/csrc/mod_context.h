@@ -170,6 +170,17 @@ struct ModContext {
   // kernels that read its output are enqueued on the context's stream, back to back
   ModDepthFilter depth_filter{};
   RawStage depth_filtered;
+  // mod_set_depth_temporal (all zeros: off) and its per-pixel state, one per context: packed [height][width] planes on the lattice of the
+  // messages the stage was last handed (s: F32; age: u8, 255 = empty), allocated on first use with the filter on, grow-only.  `fresh`
+  // empties it: the next launch neither reads nor trusts the planes (no memset that would race the stream).  The key is the geometry of
+  // that lattice: encoding, size, unit and the origin of the staged region in the camera's message
+  ModDepthTemporal depth_temporal{};
+  struct DepthTemporalState {
+    RawStage s, age;
+    bool fresh = true;
+    int32_t encoding = 0, width = 0, height = 0, ox = 0, oy = 0;
+    float unit = 0.0f;
+  } depth_tstate;
   // mod_set_depth_distortion: the depth camera's lens and, per lattice (MOD_DEPTH_RAYS_*), the ray table in HBM with the lens and the
   // message size it was built for (ensure_depth_rays builds it at the next use after one of them changed, never over a table that a
   // frame in flight may read)
@@ -395,6 +406,12 @@ int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const M
 // with `flt` on: `frames` device messages of `l` through k_depth_filter into the context's scratch on the context's stream, and *out is the
 // scratch; with it off: nothing is allocated or enqueued and *out is `depth`
 int filter_depth_messages(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, const ModDepthFilter &flt, const void **out);
+// with `t` on: `frames` consecutive device messages of `l` through k_depth_temporal on the context's stream, against the context's state
+// (emptied first when the geometry of `l` and the origin (ox, oy) of the messages in the camera's message differ from the last
+// launch's); in place when `writable` (*out stays `depth`), else into the context's filtered scratch (*out is the scratch).  With it
+// off: nothing is allocated or enqueued and *out is `depth`
+int temporal_depth_messages(ModContext *c, int frames, const void *depth, bool writable, const ModDepthLayout &l, int ox, int oy,
+                            const ModDepthTemporal &t, const void **out);
 // the ray tables a call / submit of layout `l` reads (mod_set_depth_distortion; both null while it is off): the centre table and, with
 // `splat`, the corner table, built behind the context's stream unless they are the cached ones.  Refused without a registration, and
 // when a table in use would have to be rebuilt while tickets are outstanding

@@ -226,6 +226,11 @@ void launch_depth_to_disparity(int encoding, int W, int H, int frames, const voi
 // `step`, step * height bytes apart, src -> dst of the same layout (not in place); flt is valid; window 0 and both bounds 0: a copy
 void launch_depth_filter(int encoding, int width, int height, int frames, const void *src, int step, float unit, const ModDepthFilter &flt,
                          void *dst, hipStream_t s);
+// the temporal filter with hold (depth_temporal.hip, mod_set_depth_temporal): `frames` consecutive whole width x height messages of row
+// pitch `step`, step * height bytes apart, src -> dst of the same layout (dst == src is allowed); state_s / state_age are packed
+// height x width planes, updated in place; fresh: they are not read and every pixel starts empty; t is valid and on (alpha != 0)
+void launch_depth_temporal(int encoding, int width, int height, int frames, const void *src, int step, float unit, const ModDepthTemporal &t,
+                           bool fresh, float *state_s, uint8_t *state_age, void *dst, hipStream_t s);
 // the depth camera (of the whole message) and its pose, then the image camera whose W x H window the samples land in
 struct DepthRegArgs { double fxd, fyd, cxd, cyd, R[9], t[3], fx, fy, cx, cy, Tx, Ty; };
 // the registered path: every sample of the whole width x height messages (frames step * height bytes apart) through g into the

@@ -299,6 +299,9 @@ class SceneFlowConstructor {
   // the range and flying-pixel filter of the depth messages, on the depth camera's own lattice ahead of the conversion and the
   // registration (include/mod_sf.h: ModDepthFilter); null = off (the default), read at each submitDepth()
   void setDepthFilter(const ModDepthFilter *filter) { check(mod_set_depth_filter(ctx_, filter)); }
+  // the temporal filter with hold of the depth messages, behind the depth filter (include/mod_sf.h: ModDepthTemporal); null = off (the
+  // default), read at each submitDepth(); every call empties the filter's per-pixel state
+  void setDepthTemporal(const ModDepthTemporal *filter) { check(mod_set_depth_temporal(ctx_, filter)); }
   // submitOdometry() for an RGB-D camera: one image (any encoding the library takes, the window at (x0, y0)) and one depth image of the
   // layout setDepthLayout() set, in the disparity estimator's place the conversion fT / depth on the GPU.  transform_prev2now null: the
   // camera motion is estimated on the GPU (collectOdometry() joins the ticket and integrates it); else the caller's (collect()).

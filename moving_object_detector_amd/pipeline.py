@@ -462,6 +462,51 @@ class Context(HostCalls):
                                                  C.byref(filter) if filter is not None else None, out.data_ptr()), "mod_depth_filter_dev")
         return out
 
+    def set_depth_temporal(self, filter: Optional[capi.ModDepthTemporal] = None) -> None:   # noqa: A002 (the ABI's name)
+        """Temporal filter with hold of the depth messages, behind the depth filter and ahead of everything else
+        (mod_set_depth_temporal, capi.depth_temporal); None or alpha = 0: off (the default).  Every call empties the context's state.
+        Read when a call or a submit is made; a ticket in flight keeps the parameters of its submit."""
+        self._check(self.lib.mod_set_depth_temporal(self.h, C.byref(filter) if filter is not None else None))
+
+    def get_depth_temporal(self) -> capi.ModDepthTemporal:
+        """The ModDepthTemporal in force; all zeros while it is off."""
+        f = capi.ModDepthTemporal()
+        self._check(self.lib.mod_get_depth_temporal(self.h, C.byref(f)))
+        return f
+
+    def reset_depth_temporal(self) -> None:
+        """Empties the temporal filter's state in the context (mod_reset_depth_temporal): the next frame starts every pixel anew."""
+        self._check(self.lib.mod_reset_depth_temporal(self.h))
+
+    def depth_temporal(self, dev_depth: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, filter: Optional[capi.ModDepthTemporal] = None,  # noqa: A002
+                       state: Optional[tuple] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The temporal stage alone (mod_depth_temporal_dev): `dev_depth` holds F consecutive whole messages of layout.step *
+        layout.height bytes each, oldest first (any dtype and shape, contiguous); the result has its dtype and shape; bytes of a row
+        beyond `width` samples are not defined.  state = (s, age): contiguous device tensors of height * width float32 and uint8,
+        updated in place (age filled with 255: empty); None = the context's state.  layout None = the context's, filter None = the
+        context's (off: a copy).  out may be dev_depth itself.  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_depth_layout()
+        if not dev_depth.is_contiguous() or dev_depth.device.type != "cuda":
+            raise ValueError("dev_depth must be a contiguous device tensor")
+        frame, nbytes = lay.step * lay.height, dev_depth.numel() * dev_depth.element_size()
+        if frame <= 0 or nbytes % frame:
+            raise ValueError("dev_depth must hold whole messages of step * height bytes")
+        if out is None:
+            out = torch.empty_like(dev_depth)
+        elif out.shape != dev_depth.shape or out.dtype != dev_depth.dtype or not out.is_contiguous() or out.device != dev_depth.device:
+            raise ValueError("out must be a contiguous device tensor of dev_depth's shape and dtype")
+        ps = pa = None
+        if state is not None:
+            s, age = state
+            n = lay.width * lay.height
+            for t, dt in ((s, torch.float32), (age, torch.uint8)):
+                if t.dtype != dt or t.numel() != n or not t.is_contiguous() or t.device != dev_depth.device:
+                    raise ValueError("state must be (float32, uint8) contiguous device tensors of height * width elements")
+            ps, pa = s.data_ptr(), age.data_ptr()
+        self._done(self.lib.mod_depth_temporal_dev(self.h, nbytes // frame, dev_depth.data_ptr(), C.byref(lay),
+                                                   C.byref(filter) if filter is not None else None, ps, pa, out.data_ptr()), "mod_depth_temporal_dev")
+        return out
+
     def _whole_messages(self, t: torch.Tensor, lay, out: Optional[torch.Tensor], out_dtype, name: str, unit: str):
         """(F, out) for a contiguous device tensor `t` holding F whole messages of lay.step * lay.height bytes (uint8 where the output
         is; any dtype for depth) and the (F, H, W) tensor the call writes, `out` or a new one."""

@@ -14,7 +14,12 @@ frame with and without the distortion, alternating in one process, and the depth
 sample, with the share of 8 TB/s, k_depth_to_disparity beside it in the same run, the two alternating for ROUNDS rounds; then the depth
 stream in frames/s with the filter off and on, alternating likewise (at 640x576: the registered Kinect-like message under the 1280 x 720
 camera).  The scene is a wall with boxes in front of it and flying pixels at their sides.
-Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter]"""
+--temporal [--temporal-hold N]: mod_set_depth_temporal (k_depth_temporal, csrc/depth_temporal.hip) on 16UC1 messages of 1280 x 720, one
+frame a call (what the stream does: 14 algorithmic bytes a sample, the state read and written every frame) and 64 frames a call (the
+state once: 4 + 10 / 64 bytes), in ms and TB/s, beside k_depth_filter with window 0 and no bounds (the copy kernel, 4 bytes a sample) at
+the same two call sizes in the same run, alternating for ROUNDS rounds; then the depth stream in frames/s with the filter off and on,
+alternating likewise.  The scene is a static wall with millimetre noise, 2 % dropouts and a few pixels that jump.
+Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter | --temporal]"""
 import ctypes as C
 import functools
 import json
@@ -27,6 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 W, H, F = 1280, 720, 64
 ROUNDS = 5
+TEMPORAL_ROUNDS = False            # --temporal: the runs with the filter off take the long window of the alternating rounds too
 
 
 def timed(torch, call, reps):
@@ -219,19 +225,63 @@ def kernels_filter(reps, window, fw, fh):
     ctx.close()
 
 
+def temporal_of(capi, hold):
+    return capi.depth_temporal(alpha=0.4, delta_abs=0.02, delta_rel=0.0, hold=hold)
+
+
+def kernels_temporal(reps, hold):
+    """k_depth_temporal and the copy kernel (k_depth_filter, window 0) on the same 16UC1 messages, 1 and F frames a call"""
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F)
+    ctx.set_camera(synth.make_camera(W, H))
+    rng = np.random.default_rng(0)
+    mm = np.full((F, H, W), 4000, np.uint16) + rng.integers(-4, 5, size=(F, H, W)).astype(np.uint16)
+    mm[rng.random((F, H, W)) < 0.01] = 2500                       # jumps: the gate restarts
+    mm[rng.random((F, H, W)) < 0.02] = 0
+    src = torch.from_numpy(mm.view(np.int16)).to(ctx.device)
+    dst = torch.empty_like(src)
+    s = torch.zeros(H * W, dtype=torch.float32, device=ctx.device)
+    age = torch.full((H * W,), 255, dtype=torch.uint8, device=ctx.device)
+    lay, tmp, off = capi.depth_layout("16UC1", W, H), temporal_of(capi, hold), capi.depth_filter()
+    calls = {("k_depth_temporal", n): (lambda n=n: ctx.lib.mod_depth_temporal_dev(ctx.h, n, src.data_ptr(), C.byref(lay), C.byref(tmp), s.data_ptr(),
+                                                                                   age.data_ptr(), dst.data_ptr())) for n in (1, F)}
+    calls.update({("k_depth_filter, window 0 (copy)", n): (lambda n=n: ctx.lib.mod_depth_filter_dev(ctx.h, n, src.data_ptr(), C.byref(lay), C.byref(off),
+                                                                                                     dst.data_ptr())) for n in (1, F)})
+    ms = {k: [] for k in calls}
+    for _ in range(ROUNDS):
+        for k, call in calls.items():
+            ms[k].append(timed(torch, call, reps * (8 if k[1] == 1 else 1)))
+    ctx.synchronize()
+    rate = {}
+    for (what, n), v in ms.items():
+        bytes_ = 4 + 10 / n if what == "k_depth_temporal" else 4
+        med = float(np.median(v))
+        rate[what, n] = tb = n * W * H * bytes_ / med / 1e9
+        print(json.dumps({"what": what, "encoding": "16UC1", "hold": hold if what == "k_depth_temporal" else None, "W": W, "H": H, "frames_per_call": n,
+                          "bytes_per_sample": round(bytes_, 3), "ms_per_call": spread(v), "TB_per_s": round(tb, 3),
+                          "share_of_8_TB_per_s": round(tb / 8.0, 3)}), flush=True)
+    for n in (1, F):
+        print(json.dumps({"what": "k_depth_temporal's rate over the copy kernel's", "frames_per_call": n,
+                          "ratio": round(rate["k_depth_temporal", n] / rate["k_depth_filter, window 0 (copy)", n], 3)}), flush=True)
+    ctx.close()
+
+
 @functools.lru_cache(maxsize=None)
 def ego_images():
     from moving_object_detector_amd import synth
     return synth.make_ego_images(W, H, seed=1, frames=2)
 
 
-def stream_fps(reps, splat=None, kinect=None, filter_window=None):
+def stream_fps(reps, splat=None, kinect=None, filter_window=None, temporal_hold=None):
     """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on;
     kinect 0 / 1: the message is the Kinect-like camera's 640 x 576 instead, without / with its distortion"""
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     m = ego_images()
+    temporal = temporal_hold is not None or TEMPORAL_ROUNDS
     ctx = Context(W, H, max_frames=1)
     cam = synth.make_camera(W, H)
     cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
@@ -248,6 +298,8 @@ def stream_fps(reps, splat=None, kinect=None, filter_window=None):
         ctx.set_depth_distortion(capi.depth_distortion(KINECT_D) if kinect else None)
     if filter_window:
         ctx.set_depth_filter(filter_of(capi, filter_window))
+    if temporal_hold is not None:
+        ctx.set_depth_temporal(temporal_of(capi, temporal_hold))
     fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
     fp, ep = capi.flow_params(), capi.ego_params()
     pins = []
@@ -263,25 +315,40 @@ def stream_fps(reps, splat=None, kinect=None, filter_window=None):
         assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
 
     # the alternating rounds want a window of a good half second
-    fps = stream_rate(s, step, max(20, reps) if splat is None and filter_window is None else max(300, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
+    fps = stream_rate(s, step, max(20, reps) if splat is None and filter_window is None and not temporal else max(300, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
     ctx.close()
     return fps
 
 
 def main():
     argv = sys.argv[1:]
-    window, size = 3, (W, H)
-    for flag in ("--filter-window", "--filter-size"):
+    global TEMPORAL_ROUNDS
+    window, size, hold = 3, (W, H), 2
+    for flag in ("--filter-window", "--filter-size", "--temporal-hold"):
         if flag in argv:
             i = argv.index(flag)
             value = argv[i + 1]
             del argv[i:i + 2]
             if flag == "--filter-window":
                 window = int(value)
+            elif flag == "--temporal-hold":
+                hold = int(value)
             else:
                 size = tuple(int(v) for v in value.lower().split("x"))
-    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter")]
+    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter", "--temporal")]
     reps = int(args[0]) if args else 50
+    if "--temporal" in argv:
+        assert 0 <= hold <= 254, "--temporal-hold 0 .. 254"
+        TEMPORAL_ROUNDS = True
+        kernels_temporal(reps, hold)
+        fps = {False: [], True: []}
+        for _ in range(ROUNDS):
+            for on in (False, True):
+                fps[on].append(stream_fps(reps, temporal_hold=hold if on else None))
+        for on in (False, True):
+            print(json.dumps({"what": "mod_submit_depth_host", "temporal": on, "hold": hold if on else None, "image": "bgr8", "depth": "16UC1",
+                              "kind": "odometry", "W": W, "H": H, "frames_per_s": spread(fps[on])}), flush=True)
+        return
     if "--filter" in argv:
         assert window in (3, 5) and size in ((W, H), (KW, KH)), "--filter-window 3 or 5; --filter-size 1280x720 or 640x576"
         kernels_filter(reps, window, *size)
