@@ -1,6 +1,6 @@
 // host_api.hip — the C ABI's host-pointer entry points: the single-frame *_host calls, which stage one frame through device buffers
 // of the context, and the submit / collect stream with its pipe of slots, copy streams and ring of planes.  Host-side only; how a
-// host image becomes grey on the device is host_images.hip's (ImageIngest), how a depth message becomes disparity host_depth.hip's.
+// host image becomes grey on the device is host_images.hip's (ImageIngest), how a depth message becomes disparity host_depth.hip's (DepthPlan).
 #include "mod_context.h"
 
 #include <algorithm>
@@ -191,30 +191,26 @@ struct StereoFrame {
   Pipe::Slot &s;
   Pipe::RingPlane &now, &prev;
   ImageIngest img;                   // layout, rectification and side by side as they are at this submit; the slot's stages; grow_for: the grey images
-  ModDepthLayout dlay;               // RGB-D: the depth message's layout at this submit, and then the staged copy's
-  bool splat;                        // ... and mod_set_depth_splat's setting at this submit
-  DepthRayTables rays;               // ... and mod_set_depth_distortion's tables (null: off)
-  ModDepthFilter flt;                // ... and mod_set_depth_filter's filter (all zeros: off)
-  ModDepthTemporal tmp;              // ... and mod_set_depth_temporal's (all zeros: off)
-  int dox, doy;                      // ... and the origin of the staged copy in the camera's depth message (upload_depth)
+  DepthPlan depth;                   // RGB-D: the depth settings as they are at this submit; upload_depth: of the staged copy
 };
 
 // what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
-static int rgbd_checks(ModContext *c, ModDepthLayout *dlay, DepthRayTables *rays) {
+static int rgbd_checks(ModContext *c, DepthPlan *plan) {
   if (c->side_by_side) return fail(c, MOD_ERR_INVALID_ARGUMENT, "mod_submit_depth_host takes one image: side by side must be off");
-  if (c->rect.on && !c->has_depth_reg)
+  if (c->rect.on && !c->depth.has_registration)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "a depth image aligned to the raw image cannot be aligned to the rectified one: set a depth registration");
-  if (int rc = current_depth_layout(c, dlay)) return rc;
-  return depth_ray_tables(c, *dlay, c->depth_splat, rays);
+  ModDepthLayout l;
+  if (int rc = current_depth_layout(c, &l)) return rc;
+  return depth_plan(c, l, true, plan);   // the chain reads the slot's stage
 }
 
-static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay, ModDepthLayout *dlay, DepthRayTables *rays) {
-  if (int rc = rq.rgbd ? rgbd_checks(c, dlay, rays) : MOD_OK) return rc;
+static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout *lay, DepthPlan *plan) {
+  if (int rc = rq.rgbd ? rgbd_checks(c, plan) : MOD_OK) return rc;
   // estimateDisparity() has nothing to work on: disparity_now_.reset() (scene_flow_constructor.cpp:272-276); side by side, left holds both eyes
   if (!rq.left || (rq.rgbd ? !rq.depth : !rq.right && !c->side_by_side)) {
     c->pipe.have_prev = false;      // ... which becomes the next frame's (missing) previous disparity (:397-398)
     c->pipe.have_prev_img = false;  // ... and the next frame has no previous image to estimate the flow from
-    if (rq.rgbd) c->depth_tstate.fresh = true;   // ... and the temporal depth filter starts over with it
+    if (rq.rgbd) forget_depth_history(c);   // ... and the temporal depth filter starts over with it
     return MOD_SKIP_NO_DISPARITY_NOW;
   }
   if (int rc = rq.rgbd ? MOD_OK : check_sgm_params(c, rq.sgm)) return rc;
@@ -227,20 +223,12 @@ static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout 
   return rq.rgbd ? MOD_OK : ensure_rectify_map(c, MOD_EYE_RIGHT, *lay);
 }
 
-// RGB-D: bytes of the depth message that cross PCIe (the window, packed; with a registration the whole message; with the filter's
-// support rule on, the window's apron of window / 2 message pixels with it: at most that many either side)
-static size_t depth_stage_bytes(const ModContext *c, const ModDepthLayout &l, const ModDepthFilter &flt) {
-  if (c->has_depth_reg) return (size_t)l.step * l.height;
-  const size_t apron = 2 * (size_t)(flt.window / 2);
-  return (c->dc.W + apron) * (c->dc.H + apron) * depth_bytes(l.encoding);
-}
-
 static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   if (!rq.rgbd) HIP_TRY(c, dalloc(f.s.img, 2 * c->maxN));
   if (rq.estimates_flow()) HIP_TRY(c, dalloc(f.now.left, c->maxN));
   if (rq.rgbd) {
-    if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage_bytes(c, f.dlay, f.flt))) return rc;
-    if (c->has_depth_reg) HIP_TRY(c, dalloc(f.s.zbuf, c->maxN));
+    if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage(c, f.depth).bytes())) return rc;
+    if (f.depth.registered) HIP_TRY(c, dalloc(f.s.zbuf, c->maxN));
   }
   if (f.img.rectify) {
     if (int rc = ensure_raw_stages(c, f.img)) return rc;
@@ -252,25 +240,12 @@ static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   return MOD_OK;
 }
 
-// RGB-D: the depth window (with a registration: the whole message) to the slot's stage on the copy stream, rows packed like
-// copy_window's; f.dlay becomes the layout of the staged copy.  With the filter's support rule on, the window's apron of R = window / 2
-// message pixels, clamped to the message, crosses with it (the Bayer region's precedent): the staged copy is then a message of its own
-// with the window at (x0, y0) <= (R, R), and every sample of the window sees the neighbours the whole message would show it
+// RGB-D: what depth_stage says of the depth message to the slot's stage on the copy stream; f.depth becomes the plan of the staged copy
 static int upload_depth(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
-  Pipe &p = c->pipe;
-  ModDepthLayout &l = f.dlay;
-  HIP_TRY(c, f.s.depth_read.wait(p.h2d));
-  if (c->has_depth_reg) {
-    HIP_TRY(c, hipMemcpyAsync(f.s.depth.buf, rq.depth, (size_t)l.step * l.height, hipMemcpyHostToDevice, p.h2d));
-    return MOD_OK;
-  }
-  const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H;
-  const int R = f.flt.window / 2;
-  const int ax = l.x0 < R ? l.x0 : R, ay = l.y0 < R ? l.y0 : R;                              // the apron in front of the window ...
-  const int bx = l.width - (l.x0 + W) < R ? l.width - (l.x0 + W) : R, by = l.height - (l.y0 + H) < R ? l.height - (l.y0 + H) : R;   // ... and behind
-  HIP_TRY(c, copy_window(rq.depth, l.step, l.x0 - ax, l.y0 - ay, B, W + ax + bx, H + ay + by, f.s.depth.buf, p.h2d));
-  f.dox = l.x0 - ax; f.doy = l.y0 - ay;
-  l.width = W + ax + bx; l.height = H + ay + by; l.step = l.width * B; l.x0 = ax; l.y0 = ay;
+  const DepthStage st = depth_stage(c, f.depth);
+  HIP_TRY(c, f.s.depth_read.wait(c->pipe.h2d));
+  HIP_TRY(c, copy_window(rq.depth, f.depth.lay.step, st.x, st.y, st.bpp, st.w, st.h, f.s.depth.buf, c->pipe.h2d));
+  f.depth.lay = st.lay; f.depth.ox = st.x; f.depth.oy = st.y;
   return MOD_OK;
 }
 
@@ -298,10 +273,7 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   // Kernels of older frames that read the plane being replaced are ahead of the estimator on the same stream.
   HIP_TRY(c, f.now.copied_out.wait_once(c->stream));
   if (rq.rgbd) {                    // the depth conversion (depth.hip) in the estimator's place
-    const void *msg = f.s.depth.buf;  // with a filter: the context's filtered copy (one for every slot: its writer and its reader are on the context's stream, in program order)
-    if (int rc = filter_depth_messages(c, 1, msg, f.dlay, f.flt, &msg)) return rc;
-    if (int rc = temporal_depth_messages(c, 1, msg, true, f.dlay, f.dox, f.doy, f.tmp, &msg)) return rc;   // in place: the slot's stage or the filtered scratch
-    if (int rc = run_depth_to_disparity(c, 1, msg, f.dlay, f.splat, f.rays, f.s.zbuf, f.now.disparity)) return rc;
+    if (int rc = run_depth_chain(c, 1, f.s.depth.buf, f.depth, f.s.zbuf, f.now.disparity)) return rc;
     HIP_TRY(c, f.s.depth_read.record(c->stream));
   } else {
     if (int rc = mod_sgm_compute_dev(c, 1, f.img.grey0, f.img.grey1, rq.sgm, f.now.disparity)) return rc;
@@ -333,11 +305,10 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
 static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq) {
   Pipe::Frame at;
   ModImageLayout lay;
-  ModDepthLayout dlay{};
-  DepthRayTables rays{nullptr, nullptr};
-  int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &dlay, &rays); });
+  DepthPlan plan{};
+  int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &plan); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, dlay, c->depth_splat, rays, c->depth_filter, c->depth_temporal, 0, 0};
+  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, plan};
   f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
   f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
   f.img.bin = c->binning; f.img.bin_grey = &f.s.bin_grey;
@@ -592,7 +563,7 @@ int mod_forget_previous(ModContext *c) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   c->pipe.have_prev = false;
   c->pipe.have_prev_img = false;
-  c->depth_tstate.fresh = true;     // the temporal depth filter's state goes with the previous disparity
+  forget_depth_history(c);          // the temporal depth filter's state goes with the previous disparity
   return MOD_OK;
 }
 

@@ -1,8 +1,10 @@
-// host_depth.hip — the C ABI's depth input, host side (no kernel): depth layouts, the registration, the splat and the distortion
-// settings, the ray-table cache, and the one way of device depth messages to disparity planes (run_depth_to_disparity) with the
-// entry points around them.  The kernels live in depth.hip.
+// host_depth.hip — the C ABI's depth input, host side (no kernel): the settings (DepthOptions) and their set / get calls, the ray-table
+// cache, the snapshot a call or submit takes of them (depth_plan), the one chain from device depth messages to disparity planes
+// (run_depth_chain), what the stream stages of a host message (depth_stage), and the entry points around them.  The kernels live in
+// depth.hip, depth_filter.hip, depth_temporal.hip.
 #include "mod_context.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -26,10 +28,12 @@ static int check_depth_layout(ModContext *c, const ModDepthLayout &l, bool regis
 }
 
 static ModDepthLayout default_depth_layout(const ModContext *c) { return ModDepthLayout{MOD_DEPTH_16UC1, c->dc.W, c->dc.H, 2 * c->dc.W, 0, 0, 0.0f}; }
+static ModDepthLayout layout_in_force(const ModContext *c) { return c->depth.has_layout ? c->depth.layout : default_depth_layout(c); }
+static float depth_unit(const ModDepthLayout &l) { return l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f; }
 
 int current_depth_layout(ModContext *c, ModDepthLayout *out) {
-  *out = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
-  return check_depth_layout(c, *out, c->has_depth_reg);   // the camera or the registration may have changed since the layout was set
+  *out = layout_in_force(c);
+  return check_depth_layout(c, *out, c->depth.has_registration);   // the camera or the registration may have changed since the layout was set
 }
 
 // the layout a call works on: the given one, checked as `registered` says, or the context's
@@ -41,14 +45,15 @@ static int resolve_depth_layout(ModContext *c, const ModDepthLayout *given, bool
 
 static depth_rays::Lens depth_lens_of(const ModContext *c) {
   depth_rays::Lens lens{};
-  for (int i = 0; i < 8; i++) lens.D[i] = c->depth_lens.dist.D[i];
-  lens.fx = c->depth_reg.fx; lens.fy = c->depth_reg.fy; lens.cx = c->depth_reg.cx; lens.cy = c->depth_reg.cy;
+  const ModDepthRegistration &r = c->depth.registration;
+  for (int i = 0; i < 8; i++) lens.D[i] = c->depth.distortion.D[i];
+  lens.fx = r.fx; lens.fy = r.fy; lens.cx = r.cx; lens.cy = r.cy;
   return lens;
 }
 
 // (callers have checked that a distortion and a registration are set and that lattice is one of the two)
 static int ensure_depth_rays(ModContext *c, const ModDepthLayout &l, int lattice) {
-  ModContext::DepthLens::Table &t = c->depth_lens.table[lattice];
+  ModContext::DepthRayTable &t = c->depth_rays[lattice];
   const depth_rays::Lens lens = depth_lens_of(c);
   if (t.valid && t.width == l.width && t.height == l.height && !memcmp(&t.lens, &lens, sizeof lens)) return MOD_OK;
   if (t.valid && c->pipe.in_flight > 0)   // (a table never built has no reader)
@@ -70,21 +75,30 @@ static int ensure_depth_rays(ModContext *c, const ModDepthLayout &l, int lattice
   return MOD_OK;
 }
 
-int depth_ray_tables(ModContext *c, const ModDepthLayout &l, bool splat, DepthRayTables *out) {
-  *out = DepthRayTables{nullptr, nullptr};
-  if (!c->depth_lens.on) return MOD_OK;
-  if (!c->has_depth_reg) return fail(c, MOD_ERR_INVALID_ARGUMENT, kLensNeedsRegistration);
+int depth_plan(ModContext *c, const ModDepthLayout &l, bool own_input, DepthPlan *p) {
+  const DepthOptions &o = c->depth;
+  *p = DepthPlan{l, depth_unit(l), o.has_registration, DepthRegArgs{}, o.splat, DepthRayTables{nullptr, nullptr}, o.filter, o.temporal, 0, 0, own_input};
+  if (p->registered) {
+    const ModDepthRegistration &r = o.registration;
+    DepthRegArgs &g = p->reg;
+    g.fxd = r.fx; g.fyd = r.fy; g.cxd = r.cx; g.cyd = r.cy;
+    for (int i = 0; i < 9; i++) g.R[i] = r.R[i];
+    for (int i = 0; i < 3; i++) g.t[i] = r.t[i];
+    g.fx = c->cam.fx; g.fy = c->cam.fy; g.cx = c->cam.cx; g.cy = c->cam.cy; g.Tx = c->cam.Tx; g.Ty = c->cam.Ty;
+  }
+  if (!o.has_distortion) return MOD_OK;
+  if (!p->registered) return fail(c, MOD_ERR_INVALID_ARGUMENT, kLensNeedsRegistration);
   if (int rc = ensure_depth_rays(c, l, MOD_DEPTH_RAYS_CENTRES)) return rc;
-  if (int rc = splat ? ensure_depth_rays(c, l, MOD_DEPTH_RAYS_CORNERS) : MOD_OK) return rc;
-  out->centres = c->depth_lens.table[MOD_DEPTH_RAYS_CENTRES].rays;
-  out->corners = splat ? c->depth_lens.table[MOD_DEPTH_RAYS_CORNERS].rays.get() : nullptr;
+  if (int rc = p->splat ? ensure_depth_rays(c, l, MOD_DEPTH_RAYS_CORNERS) : MOD_OK) return rc;
+  p->rays.centres = c->depth_rays[MOD_DEPTH_RAYS_CENTRES].rays;
+  p->rays.corners = p->splat ? c->depth_rays[MOD_DEPTH_RAYS_CORNERS].rays.get() : nullptr;
   return MOD_OK;
 }
 
 // a distortion is set, tickets are outstanding and a table in use was built for other intrinsics (r) / another message size (l)
 static bool rebuilds_depth_rays(const ModContext *c, const ModDepthRegistration *r, const ModDepthLayout *l) {
-  if (!c->depth_lens.on || c->pipe.in_flight <= 0) return false;
-  for (const ModContext::DepthLens::Table &t : c->depth_lens.table) {
+  if (!c->depth.has_distortion || c->pipe.in_flight <= 0) return false;
+  for (const ModContext::DepthRayTable &t : c->depth_rays) {
     if (!t.valid) continue;
     if (r && (t.lens.fx != r->fx || t.lens.fy != r->fy || t.lens.cx != r->cx || t.lens.cy != r->cy)) return true;
     if (l && (t.width != l->width || t.height != l->height)) return true;
@@ -92,29 +106,8 @@ static bool rebuilds_depth_rays(const ModContext *c, const ModDepthRegistration 
   return false;
 }
 
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, const DepthRayTables &rays,
-                           uint32_t *zbuf, float *disparity) {
-  const float unit = l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f;
-  const float invalid = c->dc.dmin - 1.0f;
-  if (c->has_depth_reg) {
-    const ModDepthRegistration &r = c->depth_reg;
-    DepthRegArgs g{};
-    g.fxd = r.fx; g.fyd = r.fy; g.cxd = r.cx; g.cyd = r.cy;
-    for (int i = 0; i < 9; i++) g.R[i] = r.R[i];
-    for (int i = 0; i < 3; i++) g.t[i] = r.t[i];
-    g.fx = c->cam.fx; g.fy = c->cam.fy; g.cx = c->cam.cx; g.cy = c->cam.cy; g.Tx = c->cam.Tx; g.Ty = c->cam.Ty;
-    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, unit, g, splat, rays, c->dc.fT, invalid,
-                                     zbuf, disparity, c->stream));
-  } else {
-    launch_depth_to_disparity(l.encoding, c->dc.W, c->dc.H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, unit, c->dc.fT, invalid,
-                              disparity, c->stream);
-  }
-  HIP_TRY(c, hipGetLastError());
-  return MOD_OK;
-}
-
 static bool depth_filter_on(const ModDepthFilter &f) { return f.z_min != 0.0f || f.z_max != 0.0f || f.window != 0; }
-static float depth_unit(const ModDepthLayout &l) { return l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f; }
+static bool depth_temporal_on(const ModDepthTemporal &t) { return t.alpha != 0.0f; }
 
 // null: valid, else what is wrong with it
 static const char *check_depth_filter(const ModDepthFilter &f) {
@@ -127,18 +120,6 @@ static const char *check_depth_filter(const ModDepthFilter &f) {
   return nullptr;
 }
 
-int filter_depth_messages(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, const ModDepthFilter &flt, const void **out) {
-  *out = depth;
-  if (!depth_filter_on(flt)) return MOD_OK;
-  if (int rc = ensure_stage_bytes(c, c->depth_filtered, (size_t)frames * l.step * l.height)) return rc;
-  launch_depth_filter(l.encoding, l.width, l.height, frames, depth, l.step, depth_unit(l), flt, c->depth_filtered.buf, c->stream);
-  HIP_TRY(c, hipGetLastError());
-  *out = c->depth_filtered.buf;
-  return MOD_OK;
-}
-
-static bool depth_temporal_on(const ModDepthTemporal &t) { return t.alpha != 0.0f; }
-
 // null: valid, else what is wrong with it
 static const char *check_depth_temporal(const ModDepthTemporal &t) {
   if (!(t.alpha >= 0.0f && t.alpha <= 1.0f)) return "depth temporal filter: alpha must be 0 (off) or in (0, 1]";
@@ -150,35 +131,71 @@ static const char *check_depth_temporal(const ModDepthTemporal &t) {
 }
 
 // the context's state planes for messages of `l` whose origin in the camera's message is (ox, oy): grown where they are too small,
-// and marked fresh where the geometry differs from the last launch's
+// and emptied where the geometry differs from the last launch's
 static int context_temporal_state(ModContext *c, const ModDepthLayout &l, int ox, int oy) {
   ModContext::DepthTemporalState &st = c->depth_tstate;
   const float unit = depth_unit(l);
-  if (st.encoding != l.encoding || st.width != l.width || st.height != l.height || st.unit != unit || st.ox != ox || st.oy != oy) st.fresh = true;
-  st.encoding = l.encoding; st.width = l.width; st.height = l.height; st.unit = unit; st.ox = ox; st.oy = oy;
   const size_t n = (size_t)l.width * l.height;
-  if (st.s.bytes < 4 * n || st.age.bytes < n) st.fresh = true;    // new planes hold nothing
+  if (st.encoding != l.encoding || st.width != l.width || st.height != l.height || st.unit != unit || st.ox != ox || st.oy != oy ||
+      st.s.bytes < 4 * n || st.age.bytes < n)   // (new planes hold nothing)
+    forget_depth_history(c);
+  st.encoding = l.encoding; st.width = l.width; st.height = l.height; st.unit = unit; st.ox = ox; st.oy = oy;
   if (int rc = ensure_stage_bytes(c, st.s, 4 * n)) return rc;
   return ensure_stage_bytes(c, st.age, n);
 }
 
-int temporal_depth_messages(ModContext *c, int frames, const void *depth, bool writable, const ModDepthLayout &l, int ox, int oy,
-                            const ModDepthTemporal &t, const void **out) {
-  *out = depth;
-  if (!depth_temporal_on(t)) return MOD_OK;
-  void *dst = const_cast<void *>(depth);   // (written only when the caller says it is the library's own copy)
-  if (!writable) {
-    if (int rc = ensure_stage_bytes(c, c->depth_filtered, (size_t)frames * l.step * l.height)) return rc;
-    dst = c->depth_filtered.buf;
+int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPlan &p, uint32_t *zbuf, float *disparity) {
+  const ModDepthLayout &l = p.lay;
+  const size_t bytes = (size_t)frames * l.step * l.height;
+  bool own = p.own_input;             // `depth` is the library's: the slot's stage, or from the first stage that runs on the scratch
+  if (depth_filter_on(p.filter)) {    // the whole messages: samples outside the window support
+    if (int rc = ensure_stage_bytes(c, c->depth_filtered, bytes)) return rc;
+    launch_depth_filter(l.encoding, l.width, l.height, frames, depth, l.step, p.unit, p.filter, c->depth_filtered.buf, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    depth = c->depth_filtered.buf; own = true;
   }
-  if (int rc = context_temporal_state(c, l, ox, oy)) return rc;
-  ModContext::DepthTemporalState &st = c->depth_tstate;
-  launch_depth_temporal(l.encoding, l.width, l.height, frames, depth, l.step, depth_unit(l), t, st.fresh, reinterpret_cast<float *>(st.s.buf.get()),
-                        st.age.buf, dst, c->stream);
+  if (depth_temporal_on(p.temporal)) {
+    if (int rc = own ? MOD_OK : ensure_stage_bytes(c, c->depth_filtered, bytes)) return rc;
+    void *dst = own ? const_cast<void *>(depth) : c->depth_filtered.buf.get();   // in place, but never into a caller's input
+    if (int rc = context_temporal_state(c, l, p.ox, p.oy)) return rc;
+    ModContext::DepthTemporalState &st = c->depth_tstate;
+    launch_depth_temporal(l.encoding, l.width, l.height, frames, depth, l.step, p.unit, p.temporal, st.fresh, reinterpret_cast<float *>(st.s.buf.get()),
+                          st.age.buf, dst, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    st.fresh = false;
+    depth = dst;
+  }
+  const float invalid = c->dc.dmin - 1.0f;
+  if (p.registered)
+    HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, p.unit, p.reg, p.splat, p.rays, c->dc.fT, invalid,
+                                     zbuf, disparity, c->stream));
+  else
+    launch_depth_to_disparity(l.encoding, c->dc.W, c->dc.H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, p.unit, c->dc.fT, invalid,
+                              disparity, c->stream);
   HIP_TRY(c, hipGetLastError());
-  st.fresh = false;
-  *out = dst;
   return MOD_OK;
+}
+
+DepthStage depth_stage(const ModContext *c, const DepthPlan &p) {
+  const ModDepthLayout &l = p.lay;
+  if (p.registered) return DepthStage{0, 0, 1, l.step, l.height, l};
+  const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H, R = p.filter.window / 2;
+  const int ax = std::min(l.x0, R), ay = std::min(l.y0, R);                                     // the apron in front of the window ...
+  const int bx = std::min(l.width - (l.x0 + W), R), by = std::min(l.height - (l.y0 + H), R);    // ... and behind it
+  const int w = W + ax + bx, h = H + ay + by;
+  return DepthStage{l.x0 - ax, l.y0 - ay, B, w, h, ModDepthLayout{l.encoding, w, h, w * B, ax, ay, l.unit}};
+}
+
+// The beginning of the two stand-alone stage calls: *l is the layout they work on, `layout` or the one in force, with the window dropped
+// (the whole messages are filtered, whatever window a path reads of them)
+static int stage_call_layout(ModContext *c, int32_t frames, const ModDepthLayout *layout, ModDepthLayout *l) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
+  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
+  if (int rc = layout ? MOD_OK : need_camera(c)) return rc;
+  *l = layout ? *layout : layout_in_force(c);
+  l->x0 = l->y0 = 0;
+  return check_depth_layout(c, *l, true);
 }
 
 extern "C" {
@@ -186,44 +203,34 @@ extern "C" {
 int mod_set_depth_temporal(ModContext *c, const ModDepthTemporal *t) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   if (const char *why = t ? check_depth_temporal(*t) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
-  c->depth_temporal = t && depth_temporal_on(*t) ? *t : ModDepthTemporal{};
-  c->depth_tstate.fresh = true;     // every successful call empties the state, in stream order: the next launch does not read it
+  c->depth.temporal = t && depth_temporal_on(*t) ? *t : ModDepthTemporal{};
+  forget_depth_history(c);          // every successful call does
   return MOD_OK;
 }
 
 int mod_get_depth_temporal(const ModContext *c, ModDepthTemporal *t) {
   if (!c || !t) return MOD_ERR_INVALID_ARGUMENT;
-  *t = c->depth_temporal;
+  *t = c->depth.temporal;
   return MOD_OK;
 }
 
 int mod_reset_depth_temporal(ModContext *c) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  c->depth_tstate.fresh = true;
+  forget_depth_history(c);
   return MOD_OK;
 }
 
 int mod_depth_temporal_dev(ModContext *c, int32_t frames, const void *depth_in, const ModDepthLayout *layout, const ModDepthTemporal *filter,
                            float *state_s, uint8_t *state_age, void *depth_out) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
-  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
   ModDepthLayout l;
-  if (layout) {
-    l = *layout;
-  } else {
-    if (int rc = need_camera(c)) return rc;
-    l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
-  }
-  l.x0 = l.y0 = 0;                  // the whole message is filtered, whatever window a path reads of it
-  if (int rc = check_depth_layout(c, l, true)) return rc;
+  if (int rc = stage_call_layout(c, frames, layout, &l)) return rc;
   if (const char *why = filter ? check_depth_temporal(*filter) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
   if (!state_s != !state_age) return fail(c, MOD_ERR_INVALID_ARGUMENT, "state_s and state_age must both be given or both be NULL (the context's state)");
   if (!depth_in) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!depth_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null depth_out");
   if ((uintptr_t)depth_in % depth_bytes(l.encoding) || (uintptr_t)depth_out % depth_bytes(l.encoding) || (uintptr_t)state_s % 4)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth_in and depth_out must be aligned to the sample size and state_s to 4 bytes");
-  const ModDepthTemporal t = filter ? *filter : c->depth_temporal;
+  const ModDepthTemporal t = filter ? *filter : c->depth.temporal;
   if (!depth_temporal_on(t)) {      // off: a copy; no state is touched
     if (depth_out != depth_in) HIP_TRY(c, hipMemcpyAsync(depth_out, depth_in, (size_t)frames * l.step * l.height, hipMemcpyDeviceToDevice, c->stream));
     return MOD_OK;
@@ -245,36 +252,26 @@ int mod_depth_temporal_dev(ModContext *c, int32_t frames, const void *depth_in, 
 int mod_set_depth_filter(ModContext *c, const ModDepthFilter *f) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   if (const char *why = f ? check_depth_filter(*f) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
-  c->depth_filter = f ? *f : ModDepthFilter{};
+  c->depth.filter = f ? *f : ModDepthFilter{};
   return MOD_OK;
 }
 
 int mod_get_depth_filter(const ModContext *c, ModDepthFilter *f) {
   if (!c || !f) return MOD_ERR_INVALID_ARGUMENT;
-  *f = c->depth_filter;
+  *f = c->depth.filter;
   return MOD_OK;
 }
 
 int mod_depth_filter_dev(ModContext *c, int32_t frames, const void *depth_in, const ModDepthLayout *layout, const ModDepthFilter *filter, void *depth_out) {
-  if (!c) return MOD_ERR_INVALID_ARGUMENT;
-  if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
-  if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
   ModDepthLayout l;
-  if (layout) {
-    l = *layout;
-  } else {
-    if (int rc = need_camera(c)) return rc;
-    l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
-  }
-  l.x0 = l.y0 = 0;                  // the whole message is filtered, whatever window a path reads of it
-  if (int rc = check_depth_layout(c, l, true)) return rc;
+  if (int rc = stage_call_layout(c, frames, layout, &l)) return rc;
   if (const char *why = filter ? check_depth_filter(*filter) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
   if (!depth_in) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!depth_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null depth_out");
   if (depth_out == depth_in) return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth filter does not work in place");
   if ((uintptr_t)depth_in % depth_bytes(l.encoding) || (uintptr_t)depth_out % depth_bytes(l.encoding))
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth_in and depth_out must be aligned to the sample size");
-  launch_depth_filter(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), filter ? *filter : c->depth_filter, depth_out, c->stream);
+  launch_depth_filter(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), filter ? *filter : c->depth.filter, depth_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
@@ -283,18 +280,18 @@ int mod_set_depth_layout(ModContext *c, const ModDepthLayout *l) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   if (int rc = need_camera(c)) return rc;
   const ModDepthLayout nl = l ? *l : default_depth_layout(c);
-  if (int rc = check_depth_layout(c, nl, c->has_depth_reg)) return rc;
+  if (int rc = check_depth_layout(c, nl, c->depth.has_registration)) return rc;
   if (rebuilds_depth_rays(c, nullptr, &nl))
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "a depth layout of another message size would rebuild the depth ray tables while frames are in flight: collect every ticket first");
-  if (l) c->depth_layout = *l;
-  c->has_depth_layout = l != nullptr;
+  if (l) c->depth.layout = *l;
+  c->depth.has_layout = l != nullptr;
   return MOD_OK;
 }
 
 int mod_get_depth_layout(const ModContext *c, ModDepthLayout *l) {
   if (!c || !l) return MOD_ERR_INVALID_ARGUMENT;
   if (!c->has_cam) return MOD_ERR_NOT_CONFIGURED;
-  *l = c->has_depth_layout ? c->depth_layout : default_depth_layout(c);
+  *l = layout_in_force(c);
   return MOD_OK;
 }
 
@@ -313,16 +310,16 @@ int mod_set_depth_registration(ModContext *c, const ModDepthRegistration *r) {
       }
     if (rebuilds_depth_rays(c, r, nullptr))
       return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth registration: other intrinsics would rebuild the depth ray tables while frames are in flight: collect every ticket first");
-    c->depth_reg = *r;
+    c->depth.registration = *r;
   }
-  c->has_depth_reg = r != nullptr;
+  c->depth.has_registration = r != nullptr;
   return MOD_OK;
 }
 
 int mod_get_depth_registration(const ModContext *c, ModDepthRegistration *r, int32_t *enabled) {
   if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
-  *enabled = c->has_depth_reg;
-  if (c->has_depth_reg && r) *r = c->depth_reg;
+  *enabled = c->depth.has_registration;
+  if (c->depth.has_registration && r) *r = c->depth.registration;
   return MOD_OK;
 }
 
@@ -332,30 +329,27 @@ int mod_depth_to_disparity_dev(ModContext *c, int32_t frames, const void *depth,
   if (frames < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "frames must be >= 1");
   if (frames > c->cfg.max_frames) return fail(c, MOD_ERR_CAPACITY, "frames exceeds ModConfig.max_frames");
   ModDepthLayout l;
-  if (int rc = resolve_depth_layout(c, layout, c->has_depth_reg, &l)) return rc;
+  if (int rc = resolve_depth_layout(c, layout, c->depth.has_registration, &l)) return rc;
   if (!depth) return MOD_SKIP_NO_DISPARITY_NOW;
   if (!disparity) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null disparity planes");
   if ((uintptr_t)depth % depth_bytes(l.encoding) || (uintptr_t)disparity % 4)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth must be aligned to its sample size and disparity to 4 bytes");
-  DepthRayTables rays;
-  if (int rc = depth_ray_tables(c, l, c->depth_splat, &rays)) return rc;
-  if (c->has_depth_reg) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
-  const void *const given = depth;
-  if (int rc = filter_depth_messages(c, frames, depth, l, c->depth_filter, &depth)) return rc;   // the whole messages: samples outside the window support
-  if (int rc = temporal_depth_messages(c, frames, depth, depth != given, l, 0, 0, c->depth_temporal, &depth)) return rc;   // never into the caller's input
-  return run_depth_to_disparity(c, frames, depth, l, c->depth_splat, rays, c->depth_zbuf, disparity);
+  DepthPlan p;
+  if (int rc = depth_plan(c, l, false, &p)) return rc;   // the messages are the caller's
+  if (p.registered) HIP_TRY(c, dalloc(c->depth_zbuf, (size_t)c->cfg.max_frames * c->maxN));
+  return run_depth_chain(c, frames, depth, p, c->depth_zbuf, disparity);
 }
 
 int mod_set_depth_splat(ModContext *c, int32_t on) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   if (on != 0 && on != 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth splat: on must be 0 or 1");
-  c->depth_splat = on != 0;
+  c->depth.splat = on != 0;
   return MOD_OK;
 }
 
 int mod_get_depth_splat(const ModContext *c, int32_t *on) {
   if (!c || !on) return MOD_ERR_INVALID_ARGUMENT;
-  *on = c->depth_splat;
+  *on = c->depth.splat;
   return MOD_OK;
 }
 
@@ -363,17 +357,17 @@ int mod_set_depth_distortion(ModContext *c, const ModDepthDistortion *d) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
   if (d)
     for (const double v : d->D) if (!std::isfinite(v)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth distortion: non-finite coefficient");
-  if (c->depth_lens.on && c->pipe.in_flight > 0)
+  if (c->depth.has_distortion && c->pipe.in_flight > 0)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth distortion cannot change while frames are in flight: collect every ticket first");
-  if (d) c->depth_lens.dist = *d;
-  c->depth_lens.on = d != nullptr;   // part of each table's key: rebuilt at the next use, behind the context's stream
+  if (d) c->depth.distortion = *d;
+  c->depth.has_distortion = d != nullptr;   // part of each table's key: rebuilt at the next use, behind the context's stream
   return MOD_OK;
 }
 
 int mod_get_depth_distortion(const ModContext *c, ModDepthDistortion *d, int32_t *enabled) {
   if (!c || !enabled) return MOD_ERR_INVALID_ARGUMENT;
-  *enabled = c->depth_lens.on;
-  if (c->depth_lens.on && d) *d = c->depth_lens.dist;
+  *enabled = c->depth.has_distortion;
+  if (c->depth.has_distortion && d) *d = c->depth.distortion;
   return MOD_OK;
 }
 
@@ -383,13 +377,13 @@ int mod_depth_rays_host(ModContext *c, const ModDepthLayout *layout, int32_t lat
   if (lattice != MOD_DEPTH_RAYS_CENTRES && lattice != MOD_DEPTH_RAYS_CORNERS)
     return fail(c, MOD_ERR_INVALID_ARGUMENT, "lattice must be MOD_DEPTH_RAYS_CENTRES or MOD_DEPTH_RAYS_CORNERS");
   if (!rays) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null rays");
-  if (!c->depth_lens.on) return fail(c, MOD_ERR_NOT_CONFIGURED, "no depth distortion is set");
-  if (!c->has_depth_reg) return fail(c, MOD_ERR_INVALID_ARGUMENT, kLensNeedsRegistration);
+  if (!c->depth.has_distortion) return fail(c, MOD_ERR_NOT_CONFIGURED, "no depth distortion is set");
+  if (!c->depth.has_registration) return fail(c, MOD_ERR_INVALID_ARGUMENT, kLensNeedsRegistration);
   ModDepthLayout l;
   if (int rc = resolve_depth_layout(c, layout, true, &l)) return rc;
   if (int rc = ensure_depth_rays(c, l, lattice)) return rc;
   const size_t entries = (size_t)(l.width + lattice) * (l.height + lattice);
-  HIP_TRY(c, hipMemcpyAsync(rays, c->depth_lens.table[lattice].rays, sizeof(double2) * entries, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipMemcpyAsync(rays, c->depth_rays[lattice].rays, sizeof(double2) * entries, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   return MOD_OK;
 }

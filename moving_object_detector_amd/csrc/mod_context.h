@@ -1,6 +1,6 @@
 // mod_context.h — the context behind the C ABI and what its host-side files share (internal to libmod_sf.so, not installed): mod_sf.hip (lifecycle, the batched scene-flow /
 // cluster path), host_sgm.hip, host_flow.hip, host_ego.hip (the estimators), host_filters.hip (their stand-alone filters), host_images.hip (image layouts, rectification, the
-// host images' way to grey), host_depth.hip (depth layouts, registration, ray tables, depth to disparity), host_api.hip (*_host calls).
+// host images' way to grey), host_depth.hip (DepthOptions, ray tables, DepthPlan and the chain from depth messages to disparity), host_api.hip (*_host calls).
 #pragma once
 #include "../../include/mod_sf.h"
 #include "frame_const.h"
@@ -114,6 +114,30 @@ struct EstimatorOptions {
   int32_t flow_propagation = 1; ModCornerFilter flow_corner_filter{0, 9, 31, 0}; ModFlowMedian flow_median{};   // flow: seeds of a search (1: the parent's winner alone)
 };
 
+// The settings of the depth input (RGB-D cameras), one member per mod_set_depth_* / mod_get_depth_* pair and named like it (host_depth.hip); these initialisers
+// are the defaults.  Read when a call or submit is made: depth_plan() takes the snapshot, and everything the call or the ticket enqueues runs from that DepthPlan
+struct DepthOptions {
+  ModDepthLayout layout{}; bool has_layout = false;                       // while false: 16UC1 packed at the camera's size (layout_in_force)
+  ModDepthRegistration registration{}; bool has_registration = false;     // opt-in: the whole message is scattered into the image camera (no window)
+  bool splat = false;                                                     // ... and paints footprints (k_depth_register_splat)
+  ModDepthDistortion distortion{}; bool has_distortion = false;           // the depth camera's lens: the registered path reads ray tables (DepthRayTable)
+  ModDepthFilter filter{};                                                // all zeros: off
+  ModDepthTemporal temporal{};                                            // all zeros: off
+};
+
+// What one call or one ticket does with its depth messages: DepthOptions as they were when it was made, resolved (host_depth.hip depth_plan)
+struct DepthPlan {
+  ModDepthLayout lay;               // checked; of the messages the chain is handed (the stream: of the staged copy, once stage_depth has run)
+  float unit;                       // metres per raw unit, resolved (lay.unit 0: the encoding's REP 118 default)
+  bool registered; DepthRegArgs reg;   // a registration is in force; then its arguments with the image camera's, else unused
+  bool splat;
+  DepthRayTables rays;              // both null: no distortion
+  ModDepthFilter filter;
+  ModDepthTemporal temporal;
+  int ox, oy;                       // where the messages the chain is handed begin in the camera's message (the temporal state's key)
+  bool own_input;                   // the chain's input buffer is the library's own: a stage may write it in place (false: a caller's, never written)
+};
+
 // Every resource is a member handle: mod_destroy synchronizes the streams below, and `delete` releases the rest.
 struct ModContext {
   ModConfig cfg{};
@@ -157,44 +181,28 @@ struct ModContext {
   // with a binning set: the full-window grey planes the converters write and k_bin_mono reads, one per frame of
   // mod_image_to_mono_dev / mod_rectify_dev (the host paths have their own two, beside their raw stages); on first use, grow-only
   RawStage bin_grey;
-  // RGB-D cameras (depth.hip): the depth messages' layout (mod_set_depth_layout; while has_depth_layout is false: 16UC1 packed at the
-  // camera's size) and the opt-in registration to the image camera; both read when a call / submit is made
-  ModDepthLayout depth_layout{};
-  bool has_depth_layout = false;
-  ModDepthRegistration depth_reg{};
-  bool has_depth_reg = false;
-  bool depth_splat = false;                 // mod_set_depth_splat: the registered path paints footprints (k_depth_register_splat)
-  DevPtr<uint32_t> depth_zbuf;              // mod_depth_to_disparity_dev's z-buffer, [max_frames][maxN], allocated on first registered call
-  // mod_set_depth_filter (all zeros: off) and the filtered messages that run_depth_to_disparity reads in the messages' place: allocated
-  // on first use with the filter on, grow-only.  One for the synchronous call and every slot of the stream: k_depth_filter and the
-  // kernels that read its output are enqueued on the context's stream, back to back
-  ModDepthFilter depth_filter{};
-  RawStage depth_filtered;
-  // mod_set_depth_temporal (all zeros: off) and its per-pixel state, one per context: packed [height][width] planes on the lattice of the
-  // messages the stage was last handed (s: F32; age: u8, 255 = empty), allocated on first use with the filter on, grow-only.  `fresh`
-  // empties it: the next launch neither reads nor trusts the planes (no memset that would race the stream).  The key is the geometry of
-  // that lattice: encoding, size, unit and the origin of the staged region in the camera's message
-  ModDepthTemporal depth_temporal{};
+  // RGB-D cameras (depth.hip): the mod_set_depth_* settings, then their resources.  Each is allocated on first use, grow-only, and written and
+  // read on the context's stream alone, in program order: so one of each serves the synchronous calls and every slot of the stream
+  DepthOptions depth;
+  DevPtr<uint32_t> depth_zbuf;              // the registered path's z-buffer, [max_frames][maxN], of mod_depth_to_disparity_dev (a slot has its own: Slot::zbuf)
+  RawStage depth_filtered;                  // the messages a filter of the chain wrote where it could not work in place (run_depth_chain)
+  // the temporal filter's per-pixel state: packed [height][width] planes on the lattice of the messages the stage was last handed (s: F32; age: u8,
+  // 255 = empty).  Its key is the geometry of that lattice: encoding, size, unit and the origin in the camera's message.  fresh: forget_depth_history
   struct DepthTemporalState {
     RawStage s, age;
     bool fresh = true;
     int32_t encoding = 0, width = 0, height = 0, ox = 0, oy = 0;
     float unit = 0.0f;
   } depth_tstate;
-  // mod_set_depth_distortion: the depth camera's lens and, per lattice (MOD_DEPTH_RAYS_*), the ray table in HBM with the lens and the
-  // message size it was built for (ensure_depth_rays builds it at the next use after one of them changed, never over a table that a
-  // frame in flight may read)
-  struct DepthLens {
-    bool on = false;
-    ModDepthDistortion dist{};
-    struct Table {
-      DevPtr<double2> rays;                   // [rows][cols], allocated on first use for the message at hand, grow-only
-      size_t entries = 0;                     // ... its capacity
-      bool valid = false;
-      depth_rays::Lens lens{};
-      int32_t width = 0, height = 0;
-    } table[2];
-  } depth_lens;
+  // mod_set_depth_distortion: per lattice (MOD_DEPTH_RAYS_*) the ray table in HBM with the lens and the message size it was built for
+  // (ensure_depth_rays builds it at the next use after one of them changed, never over a table that a frame in flight may read)
+  struct DepthRayTable {
+    DevPtr<double2> rays;                     // [rows][cols], allocated on first use for the message at hand, grow-only
+    size_t entries = 0;                       // ... its capacity
+    bool valid = false;
+    depth_rays::Lens lens{};
+    int32_t width = 0, height = 0;
+  } depth_rays[2];
   Stream own_stream;                        // the stream the context created when ModConfig.stream was null (a caller's is never destroyed)
   hipStream_t stream = nullptr;             // own_stream or the caller's
   DevCam dc{};
@@ -396,26 +404,26 @@ int ingest_copy(ModContext *c, const ImageIngest &in, const uint8_t *img0, const
 int ingest_to_grey(ModContext *c, const ImageIngest &in);
 
 // host_depth.hip
+// The temporal depth filter's history is gone (a set or reset call, mod_forget_previous, a skipped depth submit, new planes, another lattice).
+// A flag and not a memset, which would have to be ordered with the enqueued work: the next launch is told neither to read nor to trust the planes
+inline void forget_depth_history(ModContext *c) { c->depth_tstate.fresh = true; }
 // the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
 int current_depth_layout(ModContext *c, ModDepthLayout *out);
-// `frames` device depth messages of `l` (checked by the caller) to disparity planes on the context's stream: k_depth_to_disparity,
-// or with a registration in force the scatter through zbuf [frames][W H]
-// (rays: depth_ray_tables' at the same call / submit)
-int run_depth_to_disparity(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, bool splat, const DepthRayTables &rays,
-                           uint32_t *zbuf, float *disparity);
-// with `flt` on: `frames` device messages of `l` through k_depth_filter into the context's scratch on the context's stream, and *out is the
-// scratch; with it off: nothing is allocated or enqueued and *out is `depth`
-int filter_depth_messages(ModContext *c, int frames, const void *depth, const ModDepthLayout &l, const ModDepthFilter &flt, const void **out);
-// with `t` on: `frames` consecutive device messages of `l` through k_depth_temporal on the context's stream, against the context's state
-// (emptied first when the geometry of `l` and the origin (ox, oy) of the messages in the camera's message differ from the last
-// launch's); in place when `writable` (*out stays `depth`), else into the context's filtered scratch (*out is the scratch).  With it
-// off: nothing is allocated or enqueued and *out is `depth`
-int temporal_depth_messages(ModContext *c, int frames, const void *depth, bool writable, const ModDepthLayout &l, int ox, int oy,
-                            const ModDepthTemporal &t, const void **out);
-// the ray tables a call / submit of layout `l` reads (mod_set_depth_distortion; both null while it is off): the centre table and, with
-// `splat`, the corner table, built behind the context's stream unless they are the cached ones.  Refused without a registration, and
-// when a table in use would have to be rebuilt while tickets are outstanding
-int depth_ray_tables(ModContext *c, const ModDepthLayout &l, bool splat, DepthRayTables *out);
+// The snapshot of a call / submit whose messages have the checked layout `l`, made once its arguments are checked: the ray tables are built behind
+// the context's stream unless they are the cached ones (refused without a registration, and when a table in use would have to be rebuilt while
+// tickets are outstanding; p->rays stays null while no distortion is set)
+int depth_plan(ModContext *c, const ModDepthLayout &l, bool own_input, DepthPlan *p);
+// The one chain of device depth messages to disparity planes, on the context's stream: `frames` messages of p.lay through k_depth_filter, then
+// k_depth_temporal (against the context's state, emptied first where the lattice differs from the last launch's), then k_depth_to_disparity or,
+// registered, the scatter through zbuf [frames][W H].  A stage that is off allocates and enqueues nothing.  The temporal stage works in place
+// on the library's own buffers (p.own_input, the filtered scratch) and writes the scratch where its input is a caller's
+int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPlan &p, uint32_t *zbuf, float *disparity);
+// What of a host depth message crosses PCIe for a submit: copy_window's rectangle at (x, y) of w x h pixels of bpp bytes, and the layout of the
+// staged copy, a message of its own that begins at (x, y) of the camera's.  Unregistered: the camera's window with, while the filter's support
+// rule is on, its apron of window / 2 message pixels clamped to the message (every sample of the window sees the neighbours the whole message
+// would show it), rows packed.  Registered: the whole message as it is, rows of `step` bytes
+struct DepthStage { int x, y, bpp, w, h; ModDepthLayout lay; size_t bytes() const { return (size_t)w * bpp * h; } };
+DepthStage depth_stage(const ModContext *c, const DepthPlan &p);
 
 // host_sgm.hip
 int check_sgm_params(ModContext *c, const ModSgmParams *p);
