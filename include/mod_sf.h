@@ -1028,7 +1028,7 @@ int  mod_depth_rays_host(ModContext *ctx, const ModDepthLayout *layout, int32_t 
  *                               depth_in NULL: MOD_SKIP_NO_DISPARITY_NOW.  Both pointers aligned to the sample size;
  *                               frames <= ModConfig.max_frames.
  * The filtered messages are context scratch, allocated on first use with the filter on and freed in mod_destroy.
- * Not done: an edge-preserving spatial smoother; hole filling; windows above 5; node parameters.  (The temporal filter: below.) */
+ * Not done: windows above 5; node parameters.  (The temporal filter and the spatial smoother with hole fill: below.) */
 typedef struct ModDepthFilter {   /* 32 bytes; NULL, or z_min = z_max = 0 and window = 0: off (the default) */
   float   z_min, z_max;           /* range rule, in the units of z above (metres); 0 = that bound is off */
   int32_t window;                 /* support rule: 0 = off, else 3 or 5 */
@@ -1068,7 +1068,7 @@ int  mod_depth_filter_dev(ModContext *ctx, int32_t frames, const void *depth_in,
  * The context's state empties (the next launch neither reads nor trusts the planes: no memset races the stream) on every successful
  * mod_set_depth_temporal, on mod_reset_depth_temporal, on mod_forget_previous, when a depth submit is skipped for a NULL image or
  * depth, and when the geometry the stage sees changes: encoding, width, height, unit and, for the stream's staged window copy, the
- * staged region's origin in the camera's message (it moves with x0 / y0 and with the depth filter's apron).  The synchronous call and
+ * staged region's origin in the camera's message (it moves with x0 / y0 and with the two spatial stages' aprons).  The synchronous call and
  * the stream share the one state, in program order on the context's stream.
  *   mod_set_depth_temporal      NULL or alpha == 0: off (the default).  Read when mod_depth_to_disparity_dev is called and at the submit
  *                               of mod_submit_depth_host; a ticket in flight keeps the parameters of its own submit; may change while
@@ -1099,6 +1099,73 @@ int  mod_get_depth_temporal(const ModContext *ctx, ModDepthTemporal *filter);
 int  mod_reset_depth_temporal(ModContext *ctx);
 int  mod_depth_temporal_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
                             const ModDepthTemporal *filter, float *state_s, uint8_t *state_age, void *depth_out);
+/* The spatial depth smoother and hole fill (mod_set_depth_spatial, opt-in, off by default; while it is off nothing is allocated and every
+ * call enqueues exactly what it enqueues without this section).  The scene-flow stage differences two disparity planes, so per-pixel
+ * depth noise becomes false vz; the temporal filter above removes it only where the camera stands still.  And the depth filter only
+ * ever invalidates: every flying pixel it removes, and every occlusion shadow a structured-light head reports beside a foreground
+ * edge, is a hole that takes the pixel out of the cloud.  This stage smooths each valid sample over the neighbours on its own surface
+ * and puts a sample into a hole from the surface BEHIND it.  It maps a depth MESSAGE to a depth message of the same encoding, width,
+ * height and step, behind the depth filter (flying pixels are gone before any mean is formed, and the holes they leave are refilled
+ * from the background) and in front of the temporal filter (whose state then averages smoothed samples, and whose hold is left for
+ * dropouts in time), the registration, the distortion, the splat and the conversion.
+ * The rule.  All F32, one operation at a time, -ffp-contract=off.  For a message pixel with input word w:
+ *   x = (float)w for 16UC1, x = value for 32FC1;  z = x * unit (unit == 0: the encoding's default);  valid0 iff z > 0.0f and z is finite
+ *   enc(m): 16UC1: (uint16)min(max(rintf(m), 1.0f), 65535.0f), ties to even;  32FC1: the bits of m        (the temporal filter's enc)
+ *   R = window / 2.  The neighbourhood of p: the pixels q with |Uq - Up| <= R and |Vq - Vp| <= R that lie inside the message, p
+ *   included.  Pixels outside the message never take part.
+ * Both rules below read the INPUT only, so the stage is one pass and cannot cascade: a filled hole never supports a neighbour, and a
+ * smoothed value never enters another mean.
+ *   Smoothing (smooth != 0, p has valid0): a gated box mean, Lee's sigma filter, a bilateral filter with box weights.
+ *     t = tol_abs + tol_rel * z_p                                                   (one multiply, then one add)
+ *     members: every q of the neighbourhood, p included, with valid0(q) and fabsf(z_q - z_p) <= t
+ *     sum = 0.0f;  sum = sum + x_q member by member in row-major order: V ascending, then U ascending
+ *     m = sum / (float)n;  the output is enc(m)
+ *     A pixel whose only member is itself comes out bit for bit.  For 16UC1 the sum is exact (49 * 65535 < 2^24): the order is then
+ *     immaterial and the output lies between the smallest and the largest member word.
+ *   Hole fill (fill_min > 0, p lacks valid0): let V be the neighbours q with valid0.
+ *     V empty: the output is w, bit for bit.
+ *     a = the largest z_q over V;  t = tol_abs + tol_rel * a                        (one multiply, then one add)
+ *     members: the q in V with a - z_q <= t                                         (one subtract)
+ *     n >= fill_min: the output is enc(m) of the members, summed as above.  Otherwise the output is w, bit for bit.
+ *     The anchor is the farthest surface on purpose: a hole beside a depth edge is the foreground's occlusion shadow on the background,
+ *     or a flying pixel the depth filter removed, and filling it from the foreground would grow objects and invent moving pixels.  In
+ *     idea this is librealsense's farthest_from_around; parity with no SDK is claimed.
+ *   Every other sample is copied bit for bit: valid samples while smooth == 0, samples without valid0 while fill_min == 0 (NaN
+ *   payloads, -0.0, negatives and +-inf).  Bytes of a row beyond `width` samples are not defined.
+ * The neighbourhood is the message's, not the window's: on the plain path mod_submit_depth_host sends the window's apron of
+ * R_filter + R_spatial message pixels (each 0 while its stage is off), clamped to the message per side, across PCIe, so a spatial
+ * neighbour outside the window has itself been filtered with its full neighbourhood.  tests/models/depth_spatial_model.py restates
+ * the rule word for word.
+ *   mod_set_depth_spatial       NULL or window == 0: off (the default).  Context state like mod_set_depth_filter: read when
+ *                               mod_depth_to_disparity_dev is called and at the submit of mod_submit_depth_host; a ticket in flight
+ *                               keeps the setting of its own submit; may change while tickets are outstanding.
+ *                               MOD_ERR_INVALID_ARGUMENT, the state stays as it was: a window not in {0, 3, 5, 7}; smooth not 0 or 1;
+ *                               fill_min outside 0 .. window * window - 1; a window with neither smooth nor fill_min; a non-finite or
+ *                               negative tol_abs or tol_rel; a non-zero reserved.  With window == 0 everything else is still checked
+ *                               (smooth, fill_min == 0, the tolerances, reserved) and then ignored.
+ *   mod_get_depth_spatial       the setting in force; all zeros while it is off
+ *   mod_depth_spatial_dev       the stage alone: `frames` device messages stacked at step * height bytes -> depth_out, same layout, on
+ *                               the context's stream.  Not in place: depth_out != depth_in, and overlap is the caller's error.  layout
+ *                               NULL = the context's (that needs a camera); its x0, y0 are ignored, the whole message is processed, and
+ *                               any message size passes.  spatial NULL = the context's; a stage that is off copies the samples.
+ *                               depth_in NULL: MOD_SKIP_NO_DISPARITY_NOW.  Both pointers aligned to the sample size;
+ *                               frames <= ModConfig.max_frames.
+ * The stage reads neighbours, so it never works in place: behind the depth filter it reads the filtered scratch and writes a second
+ * scratch, without it it reads the input and writes the filtered scratch; the second scratch is allocated on first use with both
+ * stages on and freed in mod_destroy.  The library never writes a caller's input.
+ * Not done: an iterated or cascaded fill; windows above 7; Gaussian weights; an image-guided gate; fusion with k_depth_filter; node
+ * parameters. */
+typedef struct ModDepthSpatial {   /* 32 bytes; NULL or window == 0: off (the default) */
+  int32_t window;                  /* 0 = off, else 3, 5 or 7 */
+  int32_t smooth;                  /* 0 or 1 */
+  int32_t fill_min;                /* 0 = no hole fill, else 1 .. window * window - 1 */
+  float   tol_abs, tol_rel;        /* the gate, in the units of z (metres); finite, >= 0 */
+  int32_t reserved[3];             /* must be 0 */
+} ModDepthSpatial;
+int  mod_set_depth_spatial(ModContext *ctx, const ModDepthSpatial *spatial);
+int  mod_get_depth_spatial(const ModContext *ctx, ModDepthSpatial *spatial);
+int  mod_depth_spatial_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
+                           const ModDepthSpatial *spatial, void *depth_out);
 
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()

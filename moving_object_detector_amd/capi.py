@@ -313,6 +313,20 @@ def depth_temporal(alpha: float = 0.4, delta_abs: float = 0.02, delta_rel: float
     return ModDepthTemporal(float(alpha), float(delta_abs), float(delta_rel), int(hold), (C.c_int32 * 4)(0, 0, 0, 0))
 
 
+class ModDepthSpatial(C.Structure):
+    _fields_ = [("window", C.c_int32), ("smooth", C.c_int32), ("fill_min", C.c_int32), ("tol_abs", C.c_float), ("tol_rel", C.c_float),
+                ("reserved", C.c_int32 * 3)]
+
+
+def depth_spatial(window: int = 5, smooth: bool = True, fill_min: int = 0, tol_abs: float = 0.0, tol_rel: float = 0.02) -> ModDepthSpatial:
+    """ModDepthSpatial of mod_set_depth_spatial: with `smooth` a valid sample becomes the mean of the valid samples of its window (3, 5
+    or 7; 0 = off) within tol_abs + tol_rel * z (metres) of it, so depth edges are not blurred; with fill_min > 0 a sample without a
+    reading becomes the mean of its window's valid samples within that gate of the FARTHEST of them, where at least fill_min lie there
+    (the background fills a hole, never the foreground).  One pass over the input: nothing cascades.  The defaults are a convenience,
+    NOT tuned on camera data: choose the window, fill_min and the gate for the sensor's noise and its shadows."""
+    return ModDepthSpatial(int(window), int(bool(smooth)), int(fill_min), float(tol_abs), float(tol_rel), (C.c_int32 * 3)(0, 0, 0))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -333,6 +347,7 @@ assert C.sizeof(ModRectifyCamera) == 312
 assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 assert C.sizeof(ModDepthFilter) == 32
 assert C.sizeof(ModDepthTemporal) == 32
+assert C.sizeof(ModDepthSpatial) == 32
 assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
@@ -453,6 +468,9 @@ SIGNATURES = {
     "mod_set_depth_filter": [_vp, C.POINTER(ModDepthFilter)],
     "mod_get_depth_filter": [_vp, C.POINTER(ModDepthFilter)],
     "mod_depth_filter_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthFilter), _vp],
+    "mod_set_depth_spatial": [_vp, C.POINTER(ModDepthSpatial)],
+    "mod_get_depth_spatial": [_vp, C.POINTER(ModDepthSpatial)],
+    "mod_depth_spatial_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthSpatial), _vp],
     "mod_set_depth_temporal": [_vp, C.POINTER(ModDepthTemporal)],
     "mod_get_depth_temporal": [_vp, C.POINTER(ModDepthTemporal)],
     "mod_reset_depth_temporal": [_vp],

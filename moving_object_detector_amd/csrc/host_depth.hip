@@ -1,7 +1,7 @@
 // host_depth.hip — the C ABI's depth input, host side (no kernel): the settings (DepthOptions) and their set / get calls, the ray-table
 // cache, the snapshot a call or submit takes of them (depth_plan), the one chain from device depth messages to disparity planes
 // (run_depth_chain), what the stream stages of a host message (depth_stage), and the entry points around them.  The kernels live in
-// depth.hip, depth_filter.hip, depth_temporal.hip.
+// depth.hip, depth_filter.hip, depth_spatial.hip, depth_temporal.hip.
 #include "mod_context.h"
 
 #include <algorithm>
@@ -77,7 +77,7 @@ static int ensure_depth_rays(ModContext *c, const ModDepthLayout &l, int lattice
 
 int depth_plan(ModContext *c, const ModDepthLayout &l, bool own_input, DepthPlan *p) {
   const DepthOptions &o = c->depth;
-  *p = DepthPlan{l, depth_unit(l), o.has_registration, DepthRegArgs{}, o.splat, DepthRayTables{nullptr, nullptr}, o.filter, o.temporal, 0, 0, own_input};
+  *p = DepthPlan{l, depth_unit(l), o.has_registration, DepthRegArgs{}, o.splat, DepthRayTables{nullptr, nullptr}, o.filter, o.spatial, o.temporal, 0, 0, own_input};
   if (p->registered) {
     const ModDepthRegistration &r = o.registration;
     DepthRegArgs &g = p->reg;
@@ -108,6 +108,7 @@ static bool rebuilds_depth_rays(const ModContext *c, const ModDepthRegistration 
 
 static bool depth_filter_on(const ModDepthFilter &f) { return f.z_min != 0.0f || f.z_max != 0.0f || f.window != 0; }
 static bool depth_temporal_on(const ModDepthTemporal &t) { return t.alpha != 0.0f; }
+static bool depth_spatial_on(const ModDepthSpatial &s) { return s.window != 0; }
 
 // null: valid, else what is wrong with it
 static const char *check_depth_filter(const ModDepthFilter &f) {
@@ -117,6 +118,18 @@ static const char *check_depth_filter(const ModDepthFilter &f) {
   if (f.window != 0 && f.window != 3 && f.window != 5) return "depth filter: window must be 0 (off), 3 or 5";
   if (f.window != 0 && (f.min_support < 1 || f.min_support > f.window * f.window - 1)) return "depth filter: min_support must be in 1 .. window * window - 1";
   if (f.reserved[0] || f.reserved[1]) return "depth filter: reserved must be 0";
+  return nullptr;
+}
+
+// null: valid, else what is wrong with it
+static const char *check_depth_spatial(const ModDepthSpatial &s) {
+  if (s.window != 0 && s.window != 3 && s.window != 5 && s.window != 7) return "depth spatial: window must be 0 (off), 3, 5 or 7";
+  if (s.smooth != 0 && s.smooth != 1) return "depth spatial: smooth must be 0 or 1";
+  if (s.fill_min < 0 || s.fill_min > std::max(s.window * s.window - 1, 0)) return "depth spatial: fill_min must be in 0 .. window * window - 1";
+  if (s.window != 0 && !s.smooth && !s.fill_min) return "depth spatial: a window needs smooth or fill_min";
+  for (const float v : {s.tol_abs, s.tol_rel})
+    if (!std::isfinite(v) || v < 0.0f) return "depth spatial: tol_abs and tol_rel must be finite and >= 0";
+  for (const int32_t v : s.reserved) if (v) return "depth spatial: reserved must be 0";
   return nullptr;
 }
 
@@ -154,6 +167,13 @@ int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPla
     HIP_TRY(c, hipGetLastError());
     depth = c->depth_filtered.buf; own = true;
   }
+  if (depth_spatial_on(p.spatial)) {  // the whole messages too, and never in place: it reads neighbours
+    ModContext::RawStage &to = depth == c->depth_filtered.buf.get() ? c->depth_smoothed : c->depth_filtered;
+    if (int rc = ensure_stage_bytes(c, to, bytes)) return rc;
+    launch_depth_spatial(l.encoding, l.width, l.height, frames, depth, l.step, p.unit, p.spatial, to.buf, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    depth = to.buf; own = true;
+  }
   if (depth_temporal_on(p.temporal)) {
     if (int rc = own ? MOD_OK : ensure_stage_bytes(c, c->depth_filtered, bytes)) return rc;
     void *dst = own ? const_cast<void *>(depth) : c->depth_filtered.buf.get();   // in place, but never into a caller's input
@@ -179,14 +199,14 @@ int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPla
 DepthStage depth_stage(const ModContext *c, const DepthPlan &p) {
   const ModDepthLayout &l = p.lay;
   if (p.registered) return DepthStage{0, 0, 1, l.step, l.height, l};
-  const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H, R = p.filter.window / 2;
+  const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H, R = p.filter.window / 2 + p.spatial.window / 2;
   const int ax = std::min(l.x0, R), ay = std::min(l.y0, R);                                     // the apron in front of the window ...
   const int bx = std::min(l.width - (l.x0 + W), R), by = std::min(l.height - (l.y0 + H), R);    // ... and behind it
   const int w = W + ax + bx, h = H + ay + by;
   return DepthStage{l.x0 - ax, l.y0 - ay, B, w, h, ModDepthLayout{l.encoding, w, h, w * B, ax, ay, l.unit}};
 }
 
-// The beginning of the two stand-alone stage calls: *l is the layout they work on, `layout` or the one in force, with the window dropped
+// The beginning of the three stand-alone stage calls: *l is the layout they work on, `layout` or the one in force, with the window dropped
 // (the whole messages are filtered, whatever window a path reads of them)
 static int stage_call_layout(ModContext *c, int32_t frames, const ModDepthLayout *layout, ModDepthLayout *l) {
   if (!c) return MOD_ERR_INVALID_ARGUMENT;
@@ -246,6 +266,38 @@ int mod_depth_temporal_dev(ModContext *c, int32_t frames, const void *depth_in, 
   launch_depth_temporal(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), t, fresh, state_s, state_age, depth_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   if (own) c->depth_tstate.fresh = false;
+  return MOD_OK;
+}
+
+int mod_set_depth_spatial(ModContext *c, const ModDepthSpatial *s) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (const char *why = s ? check_depth_spatial(*s) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  c->depth.spatial = s && depth_spatial_on(*s) ? *s : ModDepthSpatial{};
+  return MOD_OK;
+}
+
+int mod_get_depth_spatial(const ModContext *c, ModDepthSpatial *s) {
+  if (!c || !s) return MOD_ERR_INVALID_ARGUMENT;
+  *s = c->depth.spatial;
+  return MOD_OK;
+}
+
+int mod_depth_spatial_dev(ModContext *c, int32_t frames, const void *depth_in, const ModDepthLayout *layout, const ModDepthSpatial *spatial, void *depth_out) {
+  ModDepthLayout l;
+  if (int rc = stage_call_layout(c, frames, layout, &l)) return rc;
+  if (const char *why = spatial ? check_depth_spatial(*spatial) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  if (!depth_in) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!depth_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null depth_out");
+  if (depth_out == depth_in) return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth spatial stage does not work in place");
+  if ((uintptr_t)depth_in % depth_bytes(l.encoding) || (uintptr_t)depth_out % depth_bytes(l.encoding))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth_in and depth_out must be aligned to the sample size");
+  const ModDepthSpatial s = spatial ? *spatial : c->depth.spatial;
+  if (!depth_spatial_on(s)) {       // off: a copy
+    HIP_TRY(c, hipMemcpyAsync(depth_out, depth_in, (size_t)frames * l.step * l.height, hipMemcpyDeviceToDevice, c->stream));
+    return MOD_OK;
+  }
+  launch_depth_spatial(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), s, depth_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }
 

@@ -122,6 +122,7 @@ struct DepthOptions {
   bool splat = false;                                                     // ... and paints footprints (k_depth_register_splat)
   ModDepthDistortion distortion{}; bool has_distortion = false;           // the depth camera's lens: the registered path reads ray tables (DepthRayTable)
   ModDepthFilter filter{};                                                // all zeros: off
+  ModDepthSpatial spatial{};                                              // all zeros: off
   ModDepthTemporal temporal{};                                            // all zeros: off
 };
 
@@ -133,6 +134,7 @@ struct DepthPlan {
   bool splat;
   DepthRayTables rays;              // both null: no distortion
   ModDepthFilter filter;
+  ModDepthSpatial spatial;
   ModDepthTemporal temporal;
   int ox, oy;                       // where the messages the chain is handed begin in the camera's message (the temporal state's key)
   bool own_input;                   // the chain's input buffer is the library's own: a stage may write it in place (false: a caller's, never written)
@@ -186,6 +188,7 @@ struct ModContext {
   DepthOptions depth;
   DevPtr<uint32_t> depth_zbuf;              // the registered path's z-buffer, [max_frames][maxN], of mod_depth_to_disparity_dev (a slot has its own: Slot::zbuf)
   RawStage depth_filtered;                  // the messages a filter of the chain wrote where it could not work in place (run_depth_chain)
+  RawStage depth_smoothed;                  // ... and the spatial stage's where its input is depth_filtered (it never works in place)
   // the temporal filter's per-pixel state: packed [height][width] planes on the lattice of the messages the stage was last handed (s: F32; age: u8,
   // 255 = empty).  Its key is the geometry of that lattice: encoding, size, unit and the origin in the camera's message.  fresh: forget_depth_history
   struct DepthTemporalState {
@@ -414,14 +417,15 @@ int current_depth_layout(ModContext *c, ModDepthLayout *out);
 // tickets are outstanding; p->rays stays null while no distortion is set)
 int depth_plan(ModContext *c, const ModDepthLayout &l, bool own_input, DepthPlan *p);
 // The one chain of device depth messages to disparity planes, on the context's stream: `frames` messages of p.lay through k_depth_filter, then
-// k_depth_temporal (against the context's state, emptied first where the lattice differs from the last launch's), then k_depth_to_disparity or,
-// registered, the scatter through zbuf [frames][W H].  A stage that is off allocates and enqueues nothing.  The temporal stage works in place
-// on the library's own buffers (p.own_input, the filtered scratch) and writes the scratch where its input is a caller's
+// k_depth_spatial, then k_depth_temporal (against the context's state, emptied first where the lattice differs from the last launch's), then
+// k_depth_to_disparity or, registered, the scatter through zbuf [frames][W H].  A stage that is off allocates and enqueues nothing.  The spatial
+// stage never works in place (it writes the filtered scratch, or a second one where that is its input); the temporal stage works in place
+// on the library's own buffers (p.own_input, the scratches) and writes the filtered scratch where its input is a caller's
 int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPlan &p, uint32_t *zbuf, float *disparity);
 // What of a host depth message crosses PCIe for a submit: copy_window's rectangle at (x, y) of w x h pixels of bpp bytes, and the layout of the
-// staged copy, a message of its own that begins at (x, y) of the camera's.  Unregistered: the camera's window with, while the filter's support
-// rule is on, its apron of window / 2 message pixels clamped to the message (every sample of the window sees the neighbours the whole message
-// would show it), rows packed.  Registered: the whole message as it is, rows of `step` bytes
+// staged copy, a message of its own that begins at (x, y) of the camera's.  Unregistered: the camera's window with its apron of R_filter + R_spatial
+// message pixels (window / 2 of the filter's support rule and of the spatial stage, each 0 while it is off) clamped to the message per side: every
+// sample of the window sees the neighbours the whole message would show it, and those neighbours theirs; rows packed.  Registered: the whole message as it is, rows of `step` bytes
 struct DepthStage { int x, y, bpp, w, h; ModDepthLayout lay; size_t bytes() const { return (size_t)w * bpp * h; } };
 DepthStage depth_stage(const ModContext *c, const DepthPlan &p);
 

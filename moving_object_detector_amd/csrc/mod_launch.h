@@ -226,6 +226,10 @@ void launch_depth_to_disparity(int encoding, int W, int H, int frames, const voi
 // `step`, step * height bytes apart, src -> dst of the same layout (not in place); flt is valid; window 0 and both bounds 0: a copy
 void launch_depth_filter(int encoding, int width, int height, int frames, const void *src, int step, float unit, const ModDepthFilter &flt,
                          void *dst, hipStream_t s);
+// the edge-preserving smoother and hole fill (depth_spatial.hip, mod_set_depth_spatial): `frames` whole width x height messages of row
+// pitch `step`, step * height bytes apart, src -> dst of the same layout (not in place); sp is valid and on (window 3, 5 or 7)
+void launch_depth_spatial(int encoding, int width, int height, int frames, const void *src, int step, float unit, const ModDepthSpatial &sp,
+                          void *dst, hipStream_t s);
 // the temporal filter with hold (depth_temporal.hip, mod_set_depth_temporal): `frames` consecutive whole width x height messages of row
 // pitch `step`, step * height bytes apart, src -> dst of the same layout (dst == src is allowed); state_s / state_age are packed
 // height x width planes, updated in place; fresh: they are not read and every pixel starts empty; t is valid and on (alpha != 0)

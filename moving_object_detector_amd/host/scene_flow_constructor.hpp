@@ -299,6 +299,9 @@ class SceneFlowConstructor {
   // the range and flying-pixel filter of the depth messages, on the depth camera's own lattice ahead of the conversion and the
   // registration (include/mod_sf.h: ModDepthFilter); null = off (the default), read at each submitDepth()
   void setDepthFilter(const ModDepthFilter *filter) { check(mod_set_depth_filter(ctx_, filter)); }
+  // the edge-preserving smoother and hole fill of the depth messages, behind the depth filter and in front of the temporal filter
+  // (include/mod_sf.h: ModDepthSpatial); null = off (the default), read at each submitDepth()
+  void setDepthSpatial(const ModDepthSpatial *spatial) { check(mod_set_depth_spatial(ctx_, spatial)); }
   // the temporal filter with hold of the depth messages, behind the depth filter (include/mod_sf.h: ModDepthTemporal); null = off (the
   // default), read at each submitDepth(); every call empties the filter's per-pixel state
   void setDepthTemporal(const ModDepthTemporal *filter) { check(mod_set_depth_temporal(ctx_, filter)); }

@@ -462,6 +462,38 @@ class Context(HostCalls):
                                                  C.byref(filter) if filter is not None else None, out.data_ptr()), "mod_depth_filter_dev")
         return out
 
+    def set_depth_spatial(self, spatial: Optional[capi.ModDepthSpatial] = None) -> None:
+        """Edge-preserving smoother and hole fill of the depth messages, behind the depth filter and in front of the temporal filter
+        (mod_set_depth_spatial, capi.depth_spatial); None or window = 0: off (the default).  Read when a call or a submit is made; a
+        ticket in flight keeps the setting of its submit."""
+        self._check(self.lib.mod_set_depth_spatial(self.h, C.byref(spatial) if spatial is not None else None))
+
+    def get_depth_spatial(self) -> capi.ModDepthSpatial:
+        """The ModDepthSpatial in force; all zeros while it is off."""
+        s = capi.ModDepthSpatial()
+        self._check(self.lib.mod_get_depth_spatial(self.h, C.byref(s)))
+        return s
+
+    def depth_spatial(self, dev_depth: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, spatial: Optional[capi.ModDepthSpatial] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The spatial stage alone (mod_depth_spatial_dev): `dev_depth` holds F whole messages of layout.step * layout.height bytes each,
+        back to back (any dtype and shape, contiguous); the result has its dtype and shape: smoothed samples, filled holes, everything
+        else bit for bit; bytes of a row beyond `width` samples are not defined.  layout None = the context's, spatial None = the
+        context's (off: a copy).  Not in place.  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_depth_layout()
+        if not dev_depth.is_contiguous() or dev_depth.device.type != "cuda":
+            raise ValueError("dev_depth must be a contiguous device tensor")
+        frame, nbytes = lay.step * lay.height, dev_depth.numel() * dev_depth.element_size()
+        if frame <= 0 or nbytes % frame:
+            raise ValueError("dev_depth must hold whole messages of step * height bytes")
+        if out is None:
+            out = torch.empty_like(dev_depth)
+        elif out.shape != dev_depth.shape or out.dtype != dev_depth.dtype or not out.is_contiguous() or out.device != dev_depth.device:
+            raise ValueError("out must be a contiguous device tensor of dev_depth's shape and dtype")
+        self._done(self.lib.mod_depth_spatial_dev(self.h, nbytes // frame, dev_depth.data_ptr(), C.byref(lay),
+                                                  C.byref(spatial) if spatial is not None else None, out.data_ptr()), "mod_depth_spatial_dev")
+        return out
+
     def set_depth_temporal(self, filter: Optional[capi.ModDepthTemporal] = None) -> None:   # noqa: A002 (the ABI's name)
         """Temporal filter with hold of the depth messages, behind the depth filter and ahead of everything else
         (mod_set_depth_temporal, capi.depth_temporal); None or alpha = 0: off (the default).  Every call empties the context's state.

@@ -19,7 +19,12 @@ frame a call (what the stream does: 14 algorithmic bytes a sample, the state rea
 state once: 4 + 10 / 64 bytes), in ms and TB/s, beside k_depth_filter with window 0 and no bounds (the copy kernel, 4 bytes a sample) at
 the same two call sizes in the same run, alternating for ROUNDS rounds; then the depth stream in frames/s with the filter off and on,
 alternating likewise.  The scene is a static wall with millimetre noise, 2 % dropouts and a few pixels that jump.
-Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter | --temporal]"""
+--spatial [--spatial-window 3|5|7] [--spatial-fill N] [--filter-size WxH]: mod_set_depth_spatial (k_depth_spatial, csrc/depth_spatial.hip)
+on 64 16UC1 messages of 1280 x 720 (or 640x576) per call: the kernel alone (mod_depth_spatial_dev, smoothing on, the hole fill with
+fill_min N, 0 = off) in ms and TB/s of its algorithmic 4 B a sample, beside k_depth_filter at window 5 and at window 0 (the copy
+kernel) on the same messages in the same run, the three alternating for ROUNDS rounds; then the depth stream in frames/s with the stage
+off and on, alternating likewise.  The scene is --filter's.
+Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter | --temporal | --spatial]"""
 import ctypes as C
 import functools
 import json
@@ -198,15 +203,7 @@ def kernels_filter(reps, window, fw, fh):
     from moving_object_detector_amd.pipeline import Context
     ctx = Context(fw, fh, max_frames=F)
     ctx.set_camera(synth.make_camera(fw, fh))
-    rng = np.random.default_rng(0)
-    mm = np.full((F, fh, fw), 4000, np.uint16) + rng.integers(-15, 16, size=(F, fh, fw)).astype(np.uint16)
-    for k in range(12):                                            # boxes at 2 m with a column of flying pixels either side
-        y, x = int(rng.integers(0, fh - 80)), int(rng.integers(2, fw - 122))
-        mm[:, y:y + 80, x:x + 120] = 2000
-        mm[:, y:y + 80, x - 1] = 2700
-        mm[:, y:y + 80, x + 120] = 3300
-    mm[rng.random((F, fh, fw)) < 0.02] = 0
-    src = torch.from_numpy(mm.view(np.int16)).to(ctx.device)
+    src = torch.from_numpy(filter_scene(np.random.default_rng(0), fw, fh).view(np.int16)).to(ctx.device)
     dst = torch.empty_like(src)
     out = torch.empty((F, fh, fw), dtype=torch.float32, device=ctx.device)
     lay, flt = capi.depth_layout("16UC1", fw, fh), filter_of(capi, window)
@@ -222,6 +219,53 @@ def kernels_filter(reps, window, fw, fh):
         print(json.dumps({"what": what, "encoding": "16UC1", "window": window if key == "filter" else None, "W": fw, "H": fh, "frames": F,
                           "bytes_per_sample": bytes_, "ms_per_call": spread(ms[key]), "TB_per_s": round(tb, 3), "share_of_8_TB_per_s": round(tb / 8.0, 3),
                           "removed_share_of_frame_0": round(removed, 4) if key == "filter" else None}), flush=True)
+    ctx.close()
+
+
+def spatial_of(capi, window, fill):
+    return capi.depth_spatial(window=window, smooth=True, fill_min=fill, tol_abs=0.005, tol_rel=0.02)
+
+
+def filter_scene(rng, fw, fh):
+    """F 16UC1 messages: a wall at 4 m, boxes at 2 m with a column of flying pixels either side, 2 % without a reading"""
+    mm = np.full((F, fh, fw), 4000, np.uint16) + rng.integers(-15, 16, size=(F, fh, fw)).astype(np.uint16)
+    for k in range(12):
+        y, x = int(rng.integers(0, fh - 80)), int(rng.integers(2, fw - 122))
+        mm[:, y:y + 80, x:x + 120] = 2000
+        mm[:, y:y + 80, x - 1] = 2700
+        mm[:, y:y + 80, x + 120] = 3300
+    mm[rng.random((F, fh, fw)) < 0.02] = 0
+    return mm
+
+
+def kernels_spatial(reps, window, fill, fw, fh):
+    """k_depth_spatial, k_depth_filter at window 5 and the copy kernel (k_depth_filter, window 0) on the same F 16UC1 messages of fw x fh"""
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(fw, fh, max_frames=F)
+    ctx.set_camera(synth.make_camera(fw, fh))
+    src = torch.from_numpy(filter_scene(np.random.default_rng(0), fw, fh).view(np.int16)).to(ctx.device)
+    dst = torch.empty_like(src)
+    lay, spa, flt, off = capi.depth_layout("16UC1", fw, fh), spatial_of(capi, window, fill), filter_of(capi, 5), capi.depth_filter()
+    calls = {"k_depth_spatial": lambda: ctx.lib.mod_depth_spatial_dev(ctx.h, F, src.data_ptr(), C.byref(lay), C.byref(spa), dst.data_ptr()),
+             "k_depth_filter, window 5": lambda: ctx.lib.mod_depth_filter_dev(ctx.h, F, src.data_ptr(), C.byref(lay), C.byref(flt), dst.data_ptr()),
+             "k_depth_filter, window 0 (copy)": lambda: ctx.lib.mod_depth_filter_dev(ctx.h, F, src.data_ptr(), C.byref(lay), C.byref(off), dst.data_ptr())}
+    ms = {k: [] for k in calls}
+    for _ in range(ROUNDS):
+        for k, call in calls.items():
+            ms[k].append(timed(torch, call, reps))
+    assert calls["k_depth_spatial"]() == 0
+    ctx.synchronize()
+    filled = float(((dst[0] != 0) & (src[0] == 0)).float().mean().item())
+    changed = float((dst[0] != src[0]).float().mean().item())
+    for what, v in ms.items():
+        tb = F * fw * fh * 4 / float(np.median(v)) / 1e9
+        own = what == "k_depth_spatial"
+        print(json.dumps({"what": what, "encoding": "16UC1", "window": window if own else None, "fill_min": fill if own else None, "W": fw, "H": fh,
+                          "frames": F, "bytes_per_sample": 4, "ms_per_call": spread(v), "TB_per_s": round(tb, 3), "share_of_8_TB_per_s": round(tb / 8.0, 3),
+                          "changed_share_of_frame_0": round(changed, 4) if own else None, "filled_share_of_frame_0": round(filled, 4) if own else None}),
+              flush=True)
     ctx.close()
 
 
@@ -274,14 +318,14 @@ def ego_images():
     return synth.make_ego_images(W, H, seed=1, frames=2)
 
 
-def stream_fps(reps, splat=None, kinect=None, filter_window=None, temporal_hold=None):
+def stream_fps(reps, splat=None, kinect=None, filter_window=None, temporal_hold=None, spatial=None):
     """splat None: the depth message is the camera's size and aligned; 0 / 1: half-size, registered, with the mode off / on;
     kinect 0 / 1: the message is the Kinect-like camera's 640 x 576 instead, without / with its distortion"""
     from moving_object_detector_amd import capi, synth
     from moving_object_detector_amd.host_stream import HostStream, stream_rate
     from moving_object_detector_amd.pipeline import Context
     m = ego_images()
-    temporal = temporal_hold is not None or TEMPORAL_ROUNDS
+    temporal = temporal_hold is not None or TEMPORAL_ROUNDS or spatial is not None     # spatial: (window, fill_min), or () for the rounds with it off
     ctx = Context(W, H, max_frames=1)
     cam = synth.make_camera(W, H)
     cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
@@ -300,6 +344,8 @@ def stream_fps(reps, splat=None, kinect=None, filter_window=None, temporal_hold=
         ctx.set_depth_filter(filter_of(capi, filter_window))
     if temporal_hold is not None:
         ctx.set_depth_temporal(temporal_of(capi, temporal_hold))
+    if spatial:
+        ctx.set_depth_spatial(spatial_of(capi, *spatial))
     fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
     fp, ep = capi.flow_params(), capi.ego_params()
     pins = []
@@ -323,8 +369,8 @@ def stream_fps(reps, splat=None, kinect=None, filter_window=None, temporal_hold=
 def main():
     argv = sys.argv[1:]
     global TEMPORAL_ROUNDS
-    window, size, hold = 3, (W, H), 2
-    for flag in ("--filter-window", "--filter-size", "--temporal-hold"):
+    window, size, hold, swindow, fill = 3, (W, H), 2, 5, 0
+    for flag in ("--filter-window", "--filter-size", "--temporal-hold", "--spatial-window", "--spatial-fill"):
         if flag in argv:
             i = argv.index(flag)
             value = argv[i + 1]
@@ -333,10 +379,27 @@ def main():
                 window = int(value)
             elif flag == "--temporal-hold":
                 hold = int(value)
+            elif flag == "--spatial-window":
+                swindow = int(value)
+            elif flag == "--spatial-fill":
+                fill = int(value)
             else:
                 size = tuple(int(v) for v in value.lower().split("x"))
-    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter", "--temporal")]
+    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter", "--temporal", "--spatial")]
     reps = int(args[0]) if args else 50
+    if "--spatial" in argv:
+        assert swindow in (3, 5, 7) and 0 <= fill < swindow * swindow and size in ((W, H), (KW, KH)), "--spatial-window 3, 5 or 7; --spatial-fill 0 .. window^2 - 1"
+        kernels_spatial(reps, swindow, fill, *size)
+        kinect = 0 if size == (KW, KH) else None
+        fps = {False: [], True: []}
+        for _ in range(ROUNDS):
+            for on in (False, True):
+                fps[on].append(stream_fps(reps, None, kinect, spatial=(swindow, fill) if on else ()))
+        for on in (False, True):
+            print(json.dumps({"what": "mod_submit_depth_host" + (", 640 x 576 registered depth message" if kinect is not None else ""), "spatial": on,
+                              "window": swindow if on else None, "fill_min": fill if on else None, "image": "bgr8", "depth": "16UC1", "kind": "odometry",
+                              "W": W, "H": H, "frames_per_s": spread(fps[on])}), flush=True)
+        return
     if "--temporal" in argv:
         assert 0 <= hold <= 254, "--temporal-hold 0 .. 254"
         TEMPORAL_ROUNDS = True
