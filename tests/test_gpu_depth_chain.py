@@ -1,5 +1,7 @@
 """GPU: the chain from depth messages to disparity planes (filter, then temporal filter, then registration or conversion) is one chain,
-whoever runs it.  Every comparison is between two runs of the same kernels and is exact.
+whoever runs it.  Every comparison is between two runs of the same kernels and is exact, and every call here carries ONE frame (the
+contexts have max_frames = 1): batches of frames a call, and the comparison of the chain with the composed numpy models, are
+tests/test_gpu_depth_chain_batches.py's.
 
 (a) Composition: mod_depth_filter_dev, then mod_depth_temporal_dev on caller-owned state, then mod_depth_to_disparity_dev with no filter
 set on the context give, frame after frame, what mod_depth_to_disparity_dev gives with the filters set on the context, and what

@@ -1,6 +1,8 @@
 """GPU: the spatial stage (mod_set_depth_spatial) inside the chain from depth messages to disparity planes: depth filter, then the
 spatial stage, then the temporal filter, then registration or conversion, whoever runs it.  Every comparison is between two runs of the
-same kernels and is exact.  The rig is tests/test_gpu_depth_chain.py's, copied: a 40 x 24 camera, a 48 x 30 message, four frames.
+same kernels and is exact.  The rig is tests/test_gpu_depth_chain.py's, copied: a 40 x 24 camera, a 48 x 30 message, four frames, ONE
+frame a call (the contexts have max_frames = 1).  Batches of frames a call, and the comparison of the chain with the composed numpy
+models, are tests/test_gpu_depth_chain_batches.py's.
 
 (a) Composition: mod_depth_filter_dev, then mod_depth_spatial_dev, then mod_depth_temporal_dev on caller-owned state, then
 mod_depth_to_disparity_dev with no setting on the context give, frame after frame, what mod_depth_to_disparity_dev gives with the three
