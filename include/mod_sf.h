@@ -749,8 +749,9 @@ int  mod_get_side_by_side(const ModContext *ctx, int32_t *on);
  *     full-resolution P, fx_b = fx / bx, fy_b = fy / by, Tx_b = Tx / bx, Ty_b = Ty / by, disp_f_b = disp_f / bx;
  *     MOD_BIN_NEAREST: cx_b = (cx - x0) / bx, cy_b = (cy - y0) / by; MOD_BIN_MEAN: cx_b = (cx - x0 - (bx - 1) / 2) / bx,
  *     cy_b = (cy - y0 - (by - 1) / 2) / by (the block's centre).
- *   - Depth images are NOT binned: mod_submit_depth_host bins the image, and the depth message must match the binned camera (or go
- *     through mod_set_depth_registration, whose scatter lands in whatever size the image camera has).
+ *   - Depth images are not binned by THIS setting: mod_submit_depth_host bins the image, and the depth message must match the binned
+ *     camera, be reduced by mod_set_depth_decimation (below, a reduction of its own that knows about validity), or go through
+ *     mod_set_depth_registration, whose scatter lands in whatever size the image camera has.
  *   - Capacity: bx W <= ModConfig.max_width and by H <= ModConfig.max_height, else MOD_ERR_CAPACITY; checked when the binning is
  *     set if a camera is known, and again at call time (the camera may have changed).
  *   mod_set_image_binning  NULL, or bx = by = 1 with either mode: off.  A factor outside 1..4, an unknown mode or a non-zero
@@ -1166,6 +1167,75 @@ int  mod_set_depth_spatial(ModContext *ctx, const ModDepthSpatial *spatial);
 int  mod_get_depth_spatial(const ModContext *ctx, ModDepthSpatial *spatial);
 int  mod_depth_spatial_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
                            const ModDepthSpatial *spatial, void *depth_out);
+/* The depth decimation (mod_set_depth_decimation, opt-in, off by default; while it is off nothing is allocated and every call and submit
+ * enqueues exactly what it enqueues without this section).  mod_set_image_binning reduces the IMAGE of an RGB-D camera; this stage
+ * reduces its DEPTH, so that a depth image aligned to the colour image at the colour camera's resolution (RealSense align_depth, Azure
+ * Kinect depth_to_rgb, depth_registered/image_rect) meets the binned camera without a host loop.  Depth cannot take k_bin_mono's box
+ * mean: a mean over a block that holds foreground, background and "no reading" words invents a surface between them, the flying pixel
+ * the depth filter removes.  This reduction knows validity and picks, or averages, samples of one surface only; in idea it is
+ * librealsense's decimation block and depth_image_proc-style pipelines, and parity with none is claimed.  It maps depth messages to
+ * PACKED depth messages of the same encoding by integer factors dx, dy in 1..4 on the depth camera's lattice, and is the last
+ * message-to-message stage: k_depth_filter -> k_depth_spatial -> k_depth_temporal -> k_depth_decimate -> k_depth_to_disparity.  The
+ * filters stay at full resolution, so flying pixels are removed before a block can select one; the temporal state keeps its
+ * full-resolution lattice and its keys; the conversion reads the decimated W x H message at origin (0, 0).
+ * The rule.  All F32, one operation at a time, -ffp-contract=off.  x, z = x * unit, valid0 (z > 0 and finite) and enc(m) are those of
+ * the spatial stage above.
+ *   Output sample (X, Y) reads the block of message pixels (x0 + dx X + i, y0 + dy Y + j), i < dx, j < dy.  "Row-major order" is j
+ *   ascending, then i ascending.  V is the set of the block's samples with valid0.  The "no reading" word is 0 for 16UC1 and
+ *   0x7fc00000 for 32FC1.
+ *   MOD_DEPTH_DECIMATE_MEDIAN (0, the default).  If |V| < max(min_valid, 1): no reading.  Otherwise sort V ascending by
+ *     (z, row-major index).  The output is the INPUT WORD of element (|V| - 1) / 2, the lower median.  Every valid output word is one
+ *     of the block's input words.
+ *   MOD_DEPTH_DECIMATE_MIN (1).  Same min_valid test.  The output is the input word of the first element of that order, the nearest
+ *     surface.  This is the z-buffer's rule, what the registered path does when several samples land on one pixel.
+ *   MOD_DEPTH_DECIMATE_MEAN (2).  Same min_valid test.  a = the z of the lower median.  t = tol_abs + tol_rel * a, one multiply and
+ *     then one add.  Members are the q in V with fabsf(z_q - a) <= t.  The median itself is always a member.
+ *     sum = 0.0f; sum = sum + x_q, member by member in row-major order.  m = sum / (float)n.  The output is enc(m).
+ *     For 16UC1 the sum is exact, because 16 * 65535 < 2^24.
+ *   MOD_DEPTH_DECIMATE_NEAREST (3).  The output is the block's top-left input word, bit for bit, whatever it is.  This is
+ *     crop_decimate's default.  min_valid and the tolerances are ignored.
+ *   dx = dy = 1, or a NULL struct, means the stage is off.  The stage alone then copies the window's words bit for bit.
+ * tests/models/depth_decimate_model.py restates the rule word for word.
+ * In the chain (the plain path): the window taken from the depth message becomes (dx W) x (dy H) at the layout's (x0, y0), and that
+ * window must fit; mod_submit_depth_host sends that window, plus the filters' apron of R message pixels clamped as before, across PCIe.
+ * The default layout while decimation is on is 16UC1 packed at (dx W) x (dy H).  With a registration in force and decimation on,
+ * mod_depth_to_disparity_dev and mod_submit_depth_host return MOD_ERR_INVALID_ARGUMENT: the scatter already lands a larger message in
+ * the camera's size with a z-buffer minimum, and decimating ahead of it would need the registration's intrinsics and the ray tables
+ * rescaled.
+ * The camera is the caller's, as with binning (the section on binning has the formulas): MEDIAN, MIN and MEAN describe the block, so
+ * the binned camera is MOD_BIN_MEAN's (the block's centre); NEAREST goes with MOD_BIN_NEAREST.  The library does not tie the two
+ * settings together, and nothing forces dx == bx.
+ *   mod_set_depth_decimation    NULL or dx = dy = 1: off (the default).  Context state like mod_set_depth_filter: read when
+ *                               mod_depth_to_disparity_dev is called and at the submit of mod_submit_depth_host; a ticket in flight
+ *                               keeps the setting of its own submit; may change while tickets are outstanding.
+ *                               MOD_ERR_INVALID_ARGUMENT, the state stays as it was: a factor outside 1..4; an unknown mode; min_valid
+ *                               outside 0 .. dx * dy; a non-finite or negative tol_abs or tol_rel; a non-zero reserved.
+ *   mod_get_depth_decimation    the setting in force; dx = dy = 1 and zeros while it is off
+ *   mod_depth_decimate_dev      the stage alone: `frames` device messages stacked at step * height bytes -> depth_out on the context's
+ *                               stream.  It honours the layout's x0, y0 (the blocks start there) and any message size passes.  The
+ *                               output is `frames` packed messages of the same encoding: out_w = (width - x0) / dx and
+ *                               out_h = (height - y0) / dy (integer division), step out_w * B, frames stacked at out_w * B * out_h
+ *                               bytes.  MOD_ERR_INVALID_ARGUMENT: out_w or out_h below 1; a NULL depth_out; pointers not aligned to
+ *                               the sample size; depth_out == depth_in (overlap is the caller's error).  frames <=
+ *                               ModConfig.max_frames.  depth_in NULL: MOD_SKIP_NO_DISPARITY_NOW.  decimation NULL = the context's;
+ *                               layout NULL = the context's (that needs a camera).
+ * The decimated messages are context scratch, [frames] W x H samples, allocated on first use with the stage on and freed in mod_destroy.
+ * Not done: decimation under a registration or a distortion; factors above 4; fusion into k_depth_to_disparity; node parameters. */
+#define MOD_DEPTH_DECIMATE_MEDIAN  0   /* the lower median of the block's valid samples */
+#define MOD_DEPTH_DECIMATE_MIN     1   /* the nearest of them (the z-buffer's rule) */
+#define MOD_DEPTH_DECIMATE_MEAN    2   /* the mean of those within the gate of the median */
+#define MOD_DEPTH_DECIMATE_NEAREST 3   /* the block's top-left word (crop_decimate's default) */
+typedef struct ModDepthDecimation {   /* 32 bytes; NULL or dx = dy = 1: off (the default) */
+  int32_t dx, dy;            /* 1..4 each */
+  int32_t mode;              /* MOD_DEPTH_DECIMATE_* */
+  int32_t min_valid;         /* 0 (= 1) .. dx * dy */
+  float   tol_abs, tol_rel;  /* MEAN's gate, metres; finite, >= 0 */
+  int32_t reserved[2];       /* must be 0 */
+} ModDepthDecimation;
+int  mod_set_depth_decimation(ModContext *ctx, const ModDepthDecimation *decimation);
+int  mod_get_depth_decimation(const ModContext *ctx, ModDepthDecimation *decimation);
+int  mod_depth_decimate_dev(ModContext *ctx, int32_t frames, const void *depth_in, const ModDepthLayout *layout,
+                            const ModDepthDecimation *decimation, void *depth_out);
 
 /* ---- host-pointer convenience (what a ROS node with host-side messages calls) ----------------------------- */
 /* One frame, host buffers in/out; any output pointer may be NULL.  Returns a skip code exactly where construct()

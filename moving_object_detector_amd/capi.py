@@ -48,6 +48,10 @@ MOD_DEPTH_16UC1, MOD_DEPTH_32FC1 = 0, 1                  # REP 118 depth images:
 MOD_DEPTH_SPLAT_MAX = 8                                  # targets per axis a footprint of mod_set_depth_splat may paint
 MOD_DEPTH_RAYS_CENTRES, MOD_DEPTH_RAYS_CORNERS = 0, 1    # mod_depth_rays_host: the ray table of the pixel centres / of the pixel corners
 MOD_DEPTH_UNDISTORT_ITERS = 20                           # fixed-point iterations behind every ray of mod_set_depth_distortion
+# mod_set_depth_decimation: the block's lower median / nearest / gated mean around the median / top-left word
+MOD_DEPTH_DECIMATE_MEDIAN, MOD_DEPTH_DECIMATE_MIN, MOD_DEPTH_DECIMATE_MEAN, MOD_DEPTH_DECIMATE_NEAREST = 0, 1, 2, 3
+DEPTH_DECIMATE_MODES = {"median": MOD_DEPTH_DECIMATE_MEDIAN, "min": MOD_DEPTH_DECIMATE_MIN, "mean": MOD_DEPTH_DECIMATE_MEAN,
+                        "nearest": MOD_DEPTH_DECIMATE_NEAREST}
 DEPTH_ENCODINGS = {"16UC1": MOD_DEPTH_16UC1, "32FC1": MOD_DEPTH_32FC1}
 DEPTH_BYTES = {MOD_DEPTH_16UC1: 2, MOD_DEPTH_32FC1: 4}   # bytes per sample
 MOD_ENCODING_MONO8, MOD_ENCODING_BGR8, MOD_ENCODING_RGB8, MOD_ENCODING_BGRA8, MOD_ENCODING_RGBA8 = 0, 1, 2, 3, 4
@@ -327,6 +331,21 @@ def depth_spatial(window: int = 5, smooth: bool = True, fill_min: int = 0, tol_a
     return ModDepthSpatial(int(window), int(bool(smooth)), int(fill_min), float(tol_abs), float(tol_rel), (C.c_int32 * 3)(0, 0, 0))
 
 
+class ModDepthDecimation(C.Structure):
+    _fields_ = [("dx", C.c_int32), ("dy", C.c_int32), ("mode", C.c_int32), ("min_valid", C.c_int32), ("tol_abs", C.c_float), ("tol_rel", C.c_float),
+                ("reserved", C.c_int32 * 2)]
+
+
+def depth_decimation(dx: int = 2, dy: int = 2, mode="median", min_valid: int = 1, tol_abs: float = 0.0, tol_rel: float = 0.02) -> ModDepthDecimation:
+    """ModDepthDecimation of mod_set_depth_decimation: every dx x dy block of the depth message (factors 1..4; dx = dy = 1 is off) becomes
+    one sample, `mode` a MOD_DEPTH_DECIMATE_* value or "median" (the lower median of the block's valid samples, an input word), "min"
+    (the nearest of them), "mean" (the mean of those within tol_abs + tol_rel * z, metres, of the median) or "nearest" (the block's
+    top-left word, whatever it is); a block with fewer than max(min_valid, 1) valid samples has no reading.  The camera is the
+    caller's: the first three go with MOD_BIN_MEAN's binned camera, "nearest" with MOD_BIN_NEAREST's (binned_camera)."""
+    return ModDepthDecimation(int(dx), int(dy), int(DEPTH_DECIMATE_MODES.get(mode, mode)), int(min_valid), float(tol_abs), float(tol_rel),
+                              (C.c_int32 * 2)(0, 0))
+
+
 class ModClusterOut(C.Structure):
     _fields_ = [("labels", C.c_void_p), ("objects", C.c_void_p), ("n_objects", C.c_void_p), ("n_clusters", C.c_void_p)]
 
@@ -348,6 +367,7 @@ assert C.sizeof(ModDepthLayout) == 28 and C.sizeof(ModDepthRegistration) == 128
 assert C.sizeof(ModDepthFilter) == 32
 assert C.sizeof(ModDepthTemporal) == 32
 assert C.sizeof(ModDepthSpatial) == 32
+assert C.sizeof(ModDepthDecimation) == 32
 assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
@@ -471,6 +491,9 @@ SIGNATURES = {
     "mod_set_depth_spatial": [_vp, C.POINTER(ModDepthSpatial)],
     "mod_get_depth_spatial": [_vp, C.POINTER(ModDepthSpatial)],
     "mod_depth_spatial_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthSpatial), _vp],
+    "mod_set_depth_decimation": [_vp, C.POINTER(ModDepthDecimation)],
+    "mod_get_depth_decimation": [_vp, C.POINTER(ModDepthDecimation)],
+    "mod_depth_decimate_dev": [_vp, _i32, _vp, C.POINTER(ModDepthLayout), C.POINTER(ModDepthDecimation), _vp],
     "mod_set_depth_temporal": [_vp, C.POINTER(ModDepthTemporal)],
     "mod_get_depth_temporal": [_vp, C.POINTER(ModDepthTemporal)],
     "mod_reset_depth_temporal": [_vp],

@@ -1,7 +1,7 @@
 // host_depth.hip — the C ABI's depth input, host side (no kernel): the settings (DepthOptions) and their set / get calls, the ray-table
 // cache, the snapshot a call or submit takes of them (depth_plan), the one chain from device depth messages to disparity planes
 // (run_depth_chain), what the stream stages of a host message (depth_stage), and the entry points around them.  The kernels live in
-// depth.hip, depth_filter.hip, depth_spatial.hip, depth_temporal.hip.
+// depth.hip, depth_filter.hip, depth_spatial.hip, depth_temporal.hip, depth_decimate.hip.
 #include "mod_context.h"
 
 #include <algorithm>
@@ -21,13 +21,19 @@ static int check_depth_layout(ModContext *c, const ModDepthLayout &l, bool regis
   if (!std::isfinite(l.unit) || l.unit < 0.0f) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: unit must be 0 (the REP 118 default) or finite and positive");
   if (registered) {
     if (l.x0 || l.y0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth image: x0 and y0 must be 0 while a depth registration is set (the whole message is registered)");
-  } else if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + c->dc.W > l.width || (int64_t)l.y0 + c->dc.H > l.height) {
-    return fail(c, MOD_ERR_INVALID_ARGUMENT, "the camera-sized window does not fit inside the depth image");
+  } else {
+    const ModDepthDecimation &d = c->depth.decimation;   // the window taken from the message: (dx W) x (dy H)
+    if (l.x0 < 0 || l.y0 < 0 || (int64_t)l.x0 + (int64_t)d.dx * c->dc.W > l.width || (int64_t)l.y0 + (int64_t)d.dy * c->dc.H > l.height)
+      return fail(c, MOD_ERR_INVALID_ARGUMENT, d.dx * d.dy > 1 ? "the window of (dx W) x (dy H) samples that the depth decimation reads does not fit inside the depth image"
+                                                               : "the camera-sized window does not fit inside the depth image");
   }
   return MOD_OK;
 }
 
-static ModDepthLayout default_depth_layout(const ModContext *c) { return ModDepthLayout{MOD_DEPTH_16UC1, c->dc.W, c->dc.H, 2 * c->dc.W, 0, 0, 0.0f}; }
+static ModDepthLayout default_depth_layout(const ModContext *c) {
+  const int w = c->depth.decimation.dx * c->dc.W, h = c->depth.decimation.dy * c->dc.H;
+  return ModDepthLayout{MOD_DEPTH_16UC1, w, h, 2 * w, 0, 0, 0.0f};
+}
 static ModDepthLayout layout_in_force(const ModContext *c) { return c->depth.has_layout ? c->depth.layout : default_depth_layout(c); }
 static float depth_unit(const ModDepthLayout &l) { return l.unit != 0.0f ? l.unit : l.encoding == MOD_DEPTH_16UC1 ? 0.001f : 1.0f; }
 
@@ -75,9 +81,13 @@ static int ensure_depth_rays(ModContext *c, const ModDepthLayout &l, int lattice
   return MOD_OK;
 }
 
+static bool depth_decimation_on(const ModDepthDecimation &d) { return d.dx * d.dy > 1; }
+
 int depth_plan(ModContext *c, const ModDepthLayout &l, bool own_input, DepthPlan *p) {
   const DepthOptions &o = c->depth;
-  *p = DepthPlan{l, depth_unit(l), o.has_registration, DepthRegArgs{}, o.splat, DepthRayTables{nullptr, nullptr}, o.filter, o.spatial, o.temporal, 0, 0, own_input};
+  *p = DepthPlan{l, depth_unit(l), o.has_registration, DepthRegArgs{}, o.splat, DepthRayTables{nullptr, nullptr}, o.filter, o.spatial, o.temporal, o.decimation, 0, 0, own_input};
+  if (p->registered && depth_decimation_on(o.decimation))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth decimation does not run under a depth registration (the scatter already lands the message in the camera's size): turn one of them off");
   if (p->registered) {
     const ModDepthRegistration &r = o.registration;
     DepthRegArgs &g = p->reg;
@@ -143,6 +153,17 @@ static const char *check_depth_temporal(const ModDepthTemporal &t) {
   return nullptr;
 }
 
+// null: valid, else what is wrong with it
+static const char *check_depth_decimation(const ModDepthDecimation &d) {
+  if (d.dx < 1 || d.dx > 4 || d.dy < 1 || d.dy > 4) return "depth decimation: dx and dy must be in 1..4";
+  if (d.mode < MOD_DEPTH_DECIMATE_MEDIAN || d.mode > MOD_DEPTH_DECIMATE_NEAREST) return "depth decimation: mode must be one of MOD_DEPTH_DECIMATE_*";
+  if (d.min_valid < 0 || d.min_valid > d.dx * d.dy) return "depth decimation: min_valid must be in 0 .. dx * dy";
+  for (const float v : {d.tol_abs, d.tol_rel})
+    if (!std::isfinite(v) || v < 0.0f) return "depth decimation: tol_abs and tol_rel must be finite and >= 0";
+  for (const int32_t v : d.reserved) if (v) return "depth decimation: reserved must be 0";
+  return nullptr;
+}
+
 // the context's state planes for messages of `l` whose origin in the camera's message is (ox, oy): grown where they are too small,
 // and emptied where the geometry differs from the last launch's
 static int context_temporal_state(ModContext *c, const ModDepthLayout &l, int ox, int oy) {
@@ -186,6 +207,15 @@ int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPla
     depth = dst;
   }
   const float invalid = c->dc.dmin - 1.0f;
+  if (depth_decimation_on(p.decimation)) {   // (never registered: depth_plan) the window's blocks -> packed W x H messages, read at origin 0
+    const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H;
+    if (int rc = ensure_stage_bytes(c, c->depth_decimated, (size_t)frames * W * H * B)) return rc;
+    launch_depth_decimate(l.encoding, W, H, frames, depth, (size_t)l.step * l.height, l.step, l.x0, l.y0, p.unit, p.decimation, c->depth_decimated.buf, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    launch_depth_to_disparity(l.encoding, W, H, frames, c->depth_decimated.buf, (size_t)W * B * H, W * B, 0, 0, p.unit, c->dc.fT, invalid, disparity, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    return MOD_OK;
+  }
   if (p.registered)
     HIP_TRY(c, launch_depth_register(l.encoding, c->dc.W, c->dc.H, frames, depth, l.width, l.height, l.step, p.unit, p.reg, p.splat, p.rays, c->dc.fT, invalid,
                                      zbuf, disparity, c->stream));
@@ -199,7 +229,7 @@ int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPla
 DepthStage depth_stage(const ModContext *c, const DepthPlan &p) {
   const ModDepthLayout &l = p.lay;
   if (p.registered) return DepthStage{0, 0, 1, l.step, l.height, l};
-  const int B = depth_bytes(l.encoding), W = c->dc.W, H = c->dc.H, R = p.filter.window / 2 + p.spatial.window / 2;
+  const int B = depth_bytes(l.encoding), W = p.decimation.dx * c->dc.W, H = p.decimation.dy * c->dc.H, R = p.filter.window / 2 + p.spatial.window / 2;
   const int ax = std::min(l.x0, R), ay = std::min(l.y0, R);                                     // the apron in front of the window ...
   const int bx = std::min(l.width - (l.x0 + W), R), by = std::min(l.height - (l.y0 + H), R);    // ... and behind it
   const int w = W + ax + bx, h = H + ay + by;
@@ -297,6 +327,40 @@ int mod_depth_spatial_dev(ModContext *c, int32_t frames, const void *depth_in, c
     return MOD_OK;
   }
   launch_depth_spatial(l.encoding, l.width, l.height, frames, depth_in, l.step, depth_unit(l), s, depth_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_set_depth_decimation(ModContext *c, const ModDepthDecimation *d) {
+  if (!c) return MOD_ERR_INVALID_ARGUMENT;
+  if (const char *why = d ? check_depth_decimation(*d) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  c->depth.decimation = d && depth_decimation_on(*d) ? *d : DepthOptions{}.decimation;
+  return MOD_OK;
+}
+
+int mod_get_depth_decimation(const ModContext *c, ModDepthDecimation *d) {
+  if (!c || !d) return MOD_ERR_INVALID_ARGUMENT;
+  *d = c->depth.decimation;
+  return MOD_OK;
+}
+
+int mod_depth_decimate_dev(ModContext *c, int32_t frames, const void *depth_in, const ModDepthLayout *layout, const ModDepthDecimation *decimation,
+                           void *depth_out) {
+  ModDepthLayout l;
+  if (int rc = stage_call_layout(c, frames, layout, &l)) return rc;   // (drops the window's origin: the message itself is checked) ...
+  l.x0 = layout ? layout->x0 : layout_in_force(c).x0;                  // ... but this stage honours it: the blocks start there
+  l.y0 = layout ? layout->y0 : layout_in_force(c).y0;
+  if (const char *why = decimation ? check_depth_decimation(*decimation) : nullptr) return fail(c, MOD_ERR_INVALID_ARGUMENT, why);
+  const ModDepthDecimation d = decimation ? *decimation : c->depth.decimation;
+  if (l.x0 < 0 || l.y0 < 0 || l.x0 >= l.width || l.y0 >= l.height) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth decimation: x0, y0 must lie inside the depth image");
+  const int out_w = (l.width - l.x0) / d.dx, out_h = (l.height - l.y0) / d.dy;
+  if (out_w < 1 || out_h < 1) return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth decimation: the message holds no whole block behind (x0, y0)");
+  if (!depth_in) return MOD_SKIP_NO_DISPARITY_NOW;
+  if (!depth_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null depth_out");
+  if (depth_out == depth_in) return fail(c, MOD_ERR_INVALID_ARGUMENT, "the depth decimation does not work in place");
+  if ((uintptr_t)depth_in % depth_bytes(l.encoding) || (uintptr_t)depth_out % depth_bytes(l.encoding))
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "depth_in and depth_out must be aligned to the sample size");
+  launch_depth_decimate(l.encoding, out_w, out_h, frames, depth_in, (size_t)l.step * l.height, l.step, l.x0, l.y0, depth_unit(l), d, depth_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -124,6 +124,7 @@ struct DepthOptions {
   ModDepthFilter filter{};                                                // all zeros: off
   ModDepthSpatial spatial{};                                              // all zeros: off
   ModDepthTemporal temporal{};                                            // all zeros: off
+  ModDepthDecimation decimation{1, 1, MOD_DEPTH_DECIMATE_MEDIAN, 0, 0.0f, 0.0f, {0, 0}};   // dx = dy = 1: off
 };
 
 // What one call or one ticket does with its depth messages: DepthOptions as they were when it was made, resolved (host_depth.hip depth_plan)
@@ -136,6 +137,7 @@ struct DepthPlan {
   ModDepthFilter filter;
   ModDepthSpatial spatial;
   ModDepthTemporal temporal;
+  ModDepthDecimation decimation;    // dx = dy = 1: off; else lay's window is (dx W) x (dy H) and the conversion reads the decimated scratch
   int ox, oy;                       // where the messages the chain is handed begin in the camera's message (the temporal state's key)
   bool own_input;                   // the chain's input buffer is the library's own: a stage may write it in place (false: a caller's, never written)
 };
@@ -189,6 +191,7 @@ struct ModContext {
   DevPtr<uint32_t> depth_zbuf;              // the registered path's z-buffer, [max_frames][maxN], of mod_depth_to_disparity_dev (a slot has its own: Slot::zbuf)
   RawStage depth_filtered;                  // the messages a filter of the chain wrote where it could not work in place (run_depth_chain)
   RawStage depth_smoothed;                  // ... and the spatial stage's where its input is depth_filtered (it never works in place)
+  RawStage depth_decimated;                 // the decimation's packed [frames] W x H messages, which the conversion then reads (run_depth_chain)
   // the temporal filter's per-pixel state: packed [height][width] planes on the lattice of the messages the stage was last handed (s: F32; age: u8,
   // 255 = empty).  Its key is the geometry of that lattice: encoding, size, unit and the origin in the camera's message.  fresh: forget_depth_history
   struct DepthTemporalState {
@@ -410,7 +413,7 @@ int ingest_to_grey(ModContext *c, const ImageIngest &in);
 // The temporal depth filter's history is gone (a set or reset call, mod_forget_previous, a skipped depth submit, new planes, another lattice).
 // A flag and not a memset, which would have to be ordered with the enqueued work: the next launch is told neither to read nor to trust the planes
 inline void forget_depth_history(ModContext *c) { c->depth_tstate.fresh = true; }
-// the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H), checked against the camera and the registration
+// the depth layout the RGB-D entry points read (the set one, or 16UC1 packed W x H; with a decimation (dx W) x (dy H)), checked against the camera and the registration
 int current_depth_layout(ModContext *c, ModDepthLayout *out);
 // The snapshot of a call / submit whose messages have the checked layout `l`, made once its arguments are checked: the ray tables are built behind
 // the context's stream unless they are the cached ones (refused without a registration, and when a table in use would have to be rebuilt while
@@ -418,13 +421,14 @@ int current_depth_layout(ModContext *c, ModDepthLayout *out);
 int depth_plan(ModContext *c, const ModDepthLayout &l, bool own_input, DepthPlan *p);
 // The one chain of device depth messages to disparity planes, on the context's stream: `frames` messages of p.lay through k_depth_filter, then
 // k_depth_spatial, then k_depth_temporal (against the context's state, emptied first where the lattice differs from the last launch's), then
+// k_depth_decimate (the window's blocks into a packed scratch of the camera's size, which the conversion reads at origin 0), then
 // k_depth_to_disparity or, registered, the scatter through zbuf [frames][W H].  A stage that is off allocates and enqueues nothing.  The spatial
 // stage never works in place (it writes the filtered scratch, or a second one where that is its input); the temporal stage works in place
 // on the library's own buffers (p.own_input, the scratches) and writes the filtered scratch where its input is a caller's
 int run_depth_chain(ModContext *c, int frames, const void *depth, const DepthPlan &p, uint32_t *zbuf, float *disparity);
 // What of a host depth message crosses PCIe for a submit: copy_window's rectangle at (x, y) of w x h pixels of bpp bytes, and the layout of the
 // staged copy, a message of its own that begins at (x, y) of the camera's.  Unregistered: the camera's window with its apron of R_filter + R_spatial
-// message pixels (window / 2 of the filter's support rule and of the spatial stage, each 0 while it is off) clamped to the message per side: every
+// message pixels (window / 2 of the filter's support rule and of the spatial stage, each 0 while it is off; with a decimation the window is (dx W) x (dy H)) clamped to the message per side: every
 // sample of the window sees the neighbours the whole message would show it, and those neighbours theirs; rows packed.  Registered: the whole message as it is, rows of `step` bytes
 struct DepthStage { int x, y, bpp, w, h; ModDepthLayout lay; size_t bytes() const { return (size_t)w * bpp * h; } };
 DepthStage depth_stage(const ModContext *c, const DepthPlan &p);

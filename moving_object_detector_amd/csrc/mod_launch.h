@@ -235,6 +235,11 @@ void launch_depth_spatial(int encoding, int width, int height, int frames, const
 // height x width planes, updated in place; fresh: they are not read and every pixel starts empty; t is valid and on (alpha != 0)
 void launch_depth_temporal(int encoding, int width, int height, int frames, const void *src, int step, float unit, const ModDepthTemporal &t,
                            bool fresh, float *state_s, uint8_t *state_age, void *dst, hipStream_t s);
+// the decimation (depth_decimate.hip, mod_set_depth_decimation): the d.dx x d.dy blocks that start at (x0, y0) of `frames` messages of row
+// pitch `step`, frame_bytes apart -> dst, PACKED messages of out_w x out_h samples (x0 + d.dx out_w <= width, y0 + d.dy out_h <= height:
+// checked by the caller, as d is); not in place; d.dx = d.dy = 1: a copy of the window
+void launch_depth_decimate(int encoding, int out_w, int out_h, int frames, const void *src, size_t frame_bytes, int step, int x0, int y0, float unit,
+                           const ModDepthDecimation &d, void *dst, hipStream_t s);
 // the depth camera (of the whole message) and its pose, then the image camera whose W x H window the samples land in
 struct DepthRegArgs { double fxd, fyd, cxd, cyd, R[9], t[3], fx, fy, cx, cy, Tx, Ty; };
 // the registered path: every sample of the whole width x height messages (frames step * height bytes apart) through g into the

@@ -302,6 +302,10 @@ class SceneFlowConstructor {
   // the edge-preserving smoother and hole fill of the depth messages, behind the depth filter and in front of the temporal filter
   // (include/mod_sf.h: ModDepthSpatial); null = off (the default), read at each submitDepth()
   void setDepthSpatial(const ModDepthSpatial *spatial) { check(mod_set_depth_spatial(ctx_, spatial)); }
+  // the decimation of the depth messages by integer factors, behind the filters and in front of the conversion: a depth image aligned to
+  // the full-resolution colour image meets the camera that setImageBinning's image has (include/mod_sf.h: ModDepthDecimation; the depth
+  // layout's window is then (dx W) x (dy H)); null or dx = dy = 1: off (the default), read at each submitDepth(); not with a registration
+  void setDepthDecimation(const ModDepthDecimation *decimation) { check(mod_set_depth_decimation(ctx_, decimation)); }
   // the temporal filter with hold of the depth messages, behind the depth filter (include/mod_sf.h: ModDepthTemporal); null = off (the
   // default), read at each submitDepth(); every call empties the filter's per-pixel state
   void setDepthTemporal(const ModDepthTemporal *filter) { check(mod_set_depth_temporal(ctx_, filter)); }

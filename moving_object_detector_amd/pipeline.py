@@ -494,6 +494,44 @@ class Context(HostCalls):
                                                   C.byref(spatial) if spatial is not None else None, out.data_ptr()), "mod_depth_spatial_dev")
         return out
 
+    def set_depth_decimation(self, d: Optional[capi.ModDepthDecimation] = None) -> None:
+        """Decimation of the depth messages by integer factors, the last stage in front of the conversion (mod_set_depth_decimation,
+        capi.depth_decimation); None or dx = dy = 1: off (the default).  The window taken from a depth message is then (dx W) x (dy H).
+        Read when a call or a submit is made; a ticket in flight keeps the setting of its submit.  Not with a registration."""
+        self._check(self.lib.mod_set_depth_decimation(self.h, C.byref(d) if d is not None else None))
+
+    def get_depth_decimation(self) -> capi.ModDepthDecimation:
+        """The ModDepthDecimation in force; dx = dy = 1 while it is off."""
+        d = capi.ModDepthDecimation()
+        self._check(self.lib.mod_get_depth_decimation(self.h, C.byref(d)))
+        return d
+
+    def depth_decimate(self, dev_depth: torch.Tensor, layout: Optional[capi.ModDepthLayout] = None, decimation: Optional[capi.ModDepthDecimation] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The decimation stage alone (mod_depth_decimate_dev): `dev_depth` holds F whole messages of layout.step * layout.height bytes
+        each, back to back (any dtype and shape, contiguous).  The blocks start at the layout's (x0, y0); the result is (F, out_h, out_w)
+        packed samples, uint16 for 16UC1 and the words as uint32 for 32FC1 (`.view(torch.float32)` reads them), with
+        out_w = (width - x0) // dx and out_h = (height - y0) // dy.  layout None = the context's, decimation None = the context's (off: a
+        copy of the window).  Not in place.  Enqueued on the context's stream."""
+        lay = layout if layout is not None else self.get_depth_layout()
+        d = decimation if decimation is not None else self.get_depth_decimation()
+        if not dev_depth.is_contiguous() or dev_depth.device.type != "cuda":
+            raise ValueError("dev_depth must be a contiguous device tensor")
+        frame, nbytes = lay.step * lay.height, dev_depth.numel() * dev_depth.element_size()
+        if frame <= 0 or nbytes % frame:
+            raise ValueError("dev_depth must hold whole messages of step * height bytes")
+        F = nbytes // frame
+        shape = (F, (lay.height - lay.y0) // max(d.dy, 1), (lay.width - lay.x0) // max(d.dx, 1))
+        dtype = torch.uint16 if lay.encoding == capi.MOD_DEPTH_16UC1 else torch.uint32
+        if out is None:
+            out = torch.empty([max(n, 0) for n in shape], dtype=dtype, device=dev_depth.device)
+        elif out.numel() * out.element_size() != shape[0] * shape[1] * shape[2] * capi.DEPTH_BYTES.get(lay.encoding, 0) or not out.is_contiguous() \
+                or out.device != dev_depth.device:
+            raise ValueError("out must be a contiguous device tensor of F * out_h * out_w samples")
+        self._done(self.lib.mod_depth_decimate_dev(self.h, F, dev_depth.data_ptr(), C.byref(lay),
+                                                   C.byref(decimation) if decimation is not None else None, out.data_ptr()), "mod_depth_decimate_dev")
+        return out
+
     def set_depth_temporal(self, filter: Optional[capi.ModDepthTemporal] = None) -> None:   # noqa: A002 (the ABI's name)
         """Temporal filter with hold of the depth messages, behind the depth filter and ahead of everything else
         (mod_set_depth_temporal, capi.depth_temporal); None or alpha = 0: off (the default).  Every call empties the context's state.

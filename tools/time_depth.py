@@ -24,7 +24,13 @@ on 64 16UC1 messages of 1280 x 720 (or 640x576) per call: the kernel alone (mod_
 fill_min N, 0 = off) in ms and TB/s of its algorithmic 4 B a sample, beside k_depth_filter at window 5 and at window 0 (the copy
 kernel) on the same messages in the same run, the three alternating for ROUNDS rounds; then the depth stream in frames/s with the stage
 off and on, alternating likewise.  The scene is --filter's.
-Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter | --temporal | --spatial]"""
+--decimate [--decimate-factor 2] [--decimate-mode median]: mod_set_depth_decimation (k_depth_decimate, csrc/depth_decimate.hip) on 64
+16UC1 messages of 1280 x 720 per call: the kernel alone (mod_depth_decimate_dev, factor x factor blocks) in ms and TB/s of its
+algorithmic (factor^2 + 1) * 2 bytes an output sample, beside the copy kernel (k_depth_filter, window 0, 4 bytes a sample) on the same
+messages in the same run, alternating for ROUNDS rounds; then the depth stream in frames/s for a 1280 x 720 aligned depth and bgr8
+image with factor x factor binning and decimation under a camera of 1280 / factor x 720 / factor, and the same stream for a native
+camera of that size (messages that size, both settings off), alternating likewise.  The scene is --filter's.
+Run on the GPU: python tools/time_depth.py [reps] [--splat | --distorted | --filter | --temporal | --spatial | --decimate]"""
 import ctypes as C
 import functools
 import json
@@ -269,6 +275,75 @@ def kernels_spatial(reps, window, fill, fw, fh):
     ctx.close()
 
 
+def kernels_decimate(reps, factor, mode):
+    """k_depth_decimate and the copy kernel (k_depth_filter, window 0) on the same F 16UC1 messages of W x H"""
+    import torch
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.pipeline import Context
+    ctx = Context(W, H, max_frames=F)
+    ctx.set_camera(synth.make_camera(W, H))
+    src = torch.from_numpy(filter_scene(np.random.default_rng(0), W, H).view(np.int16)).to(ctx.device)
+    dst = torch.empty_like(src)
+    lay, dec, off = capi.depth_layout("16UC1", W, H), capi.depth_decimation(factor, factor, mode), capi.depth_filter()
+    calls = {"k_depth_decimate": lambda: ctx.lib.mod_depth_decimate_dev(ctx.h, F, src.data_ptr(), C.byref(lay), C.byref(dec), dst.data_ptr()),
+             "k_depth_filter, window 0 (copy)": lambda: ctx.lib.mod_depth_filter_dev(ctx.h, F, src.data_ptr(), C.byref(lay), C.byref(off), dst.data_ptr())}
+    ms = {k: [] for k in calls}
+    for _ in range(ROUNDS):
+        for k, call in calls.items():
+            ms[k].append(timed(torch, call, reps))
+    ctx.synchronize()
+    ow, oh = W // factor, H // factor
+    for what, v in ms.items():
+        own = what == "k_depth_decimate"
+        nbytes = F * ow * oh * (factor * factor + 1) * 2 if own else F * W * H * 4
+        tb = nbytes / float(np.median(v)) / 1e9
+        print(json.dumps({"what": what, "encoding": "16UC1", "factor": factor if own else None, "mode": mode if own else None, "W": W, "H": H,
+                          "out_W": ow if own else None, "out_H": oh if own else None, "frames": F,
+                          "bytes_per_output_sample" if own else "bytes_per_sample": (factor * factor + 1) * 2 if own else 4,
+                          "ms_per_call": spread(v), "TB_per_s": round(tb, 3), "share_of_8_TB_per_s": round(tb / 8.0, 3)}), flush=True)
+    ctx.close()
+
+
+def stream_fps_decimate(reps, factor, mode, native):
+    """the depth stream under a camera of W / factor x H / factor: full-size bgr8 and aligned 16UC1 messages with factor x factor binning
+    and decimation, or (native) messages of the camera's size with both off"""
+    from moving_object_detector_amd import capi, synth
+    from moving_object_detector_amd.host_stream import HostStream, stream_rate
+    from moving_object_detector_amd.pipeline import Context
+    m = ego_images()
+    cw, ch = W // factor, H // factor
+    ctx = Context(W, H, max_frames=1)
+    cam = synth.make_camera(cw, ch)
+    cam.min_disparity, cam.max_disparity = np.float32(0.0), np.float32(127.0)
+    ctx.set_camera(cam)
+    ctx.set_params(synth.Params())
+    if native:
+        ctx.set_image_layout(capi.image_layout("bgr8", cw, ch))
+    else:
+        ctx.set_image_binning(factor, factor, capi.MOD_BIN_NEAREST if mode == "nearest" else capi.MOD_BIN_MEAN)
+        ctx.set_image_layout(capi.image_layout("bgr8", factor * cw, factor * ch))
+        ctx.set_depth_decimation(capi.depth_decimation(factor, factor, mode))
+        ctx.set_depth_layout(capi.depth_layout("16UC1", factor * cw, factor * ch))
+    fT = float(np.float32(cam.disp_f) * np.float32(cam.disp_T))
+    fp, ep = capi.flow_params(), capi.ego_params()
+    pins = []
+    for k in (0, 1):
+        bgr = np.repeat(m[f"left{k}"][..., None], 3, axis=2)[:factor * ch, :factor * cw]
+        mm = np.rint(1000.0 * fT / m[f"disparity{k}"].astype(np.float64)).astype(np.uint16)[:factor * ch, :factor * cw]
+        if native:
+            bgr, mm = bgr[::factor, ::factor], mm[::factor, ::factor]
+        pins += [ctx.pinned_copy(np.ascontiguousarray(bgr)), ctx.pinned_copy(np.ascontiguousarray(mm))]
+    s = HostStream(ctx, 3, 64, outputs=())
+
+    def step(i):
+        rc = s.submit_depth(i % 3, pins[2 * (i % 2)], pins[2 * (i % 2) + 1], fp, ep, None, 1.0 / 15.0)
+        assert rc in (0, capi.MOD_SKIP_NO_FLOW), rc
+
+    fps = stream_rate(s, step, max(300, reps), ok=(0, capi.MOD_SKIP_NO_TRANSFORM))
+    ctx.close()
+    return fps
+
+
 def temporal_of(capi, hold):
     return capi.depth_temporal(alpha=0.4, delta_abs=0.02, delta_rel=0.0, hold=hold)
 
@@ -369,8 +444,8 @@ def stream_fps(reps, splat=None, kinect=None, filter_window=None, temporal_hold=
 def main():
     argv = sys.argv[1:]
     global TEMPORAL_ROUNDS
-    window, size, hold, swindow, fill = 3, (W, H), 2, 5, 0
-    for flag in ("--filter-window", "--filter-size", "--temporal-hold", "--spatial-window", "--spatial-fill"):
+    window, size, hold, swindow, fill, factor, mode = 3, (W, H), 2, 5, 0, 2, "median"
+    for flag in ("--filter-window", "--filter-size", "--temporal-hold", "--spatial-window", "--spatial-fill", "--decimate-factor", "--decimate-mode"):
         if flag in argv:
             i = argv.index(flag)
             value = argv[i + 1]
@@ -383,10 +458,26 @@ def main():
                 swindow = int(value)
             elif flag == "--spatial-fill":
                 fill = int(value)
+            elif flag == "--decimate-factor":
+                factor = int(value)
+            elif flag == "--decimate-mode":
+                mode = value
             else:
                 size = tuple(int(v) for v in value.lower().split("x"))
-    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter", "--temporal", "--spatial")]
+    args = [a for a in argv if a not in ("--splat", "--distorted", "--filter", "--temporal", "--spatial", "--decimate")]
     reps = int(args[0]) if args else 50
+    if "--decimate" in argv:
+        assert factor in (2, 3, 4) and mode in ("median", "min", "mean", "nearest"), "--decimate-factor 2, 3 or 4; --decimate-mode median, min, mean or nearest"
+        kernels_decimate(reps, factor, mode)
+        fps = {False: [], True: []}
+        for _ in range(ROUNDS):
+            for native in (False, True):
+                fps[native].append(stream_fps_decimate(reps, factor, mode, native))
+        for native in (False, True):
+            print(json.dumps({"what": "mod_submit_depth_host", "camera": [W // factor, H // factor], "messages": [W // factor, H // factor] if native else
+                              [W // factor * factor, H // factor * factor], "binning": None if native else factor, "decimation": None if native else factor,
+                              "mode": None if native else mode, "image": "bgr8", "depth": "16UC1", "kind": "odometry", "frames_per_s": spread(fps[native])}), flush=True)
+        return
     if "--spatial" in argv:
         assert swindow in (3, 5, 7) and 0 <= fill < swindow * swindow and size in ((W, H), (KW, KH)), "--spatial-window 3, 5 or 7; --spatial-fill 0 .. window^2 - 1"
         kernels_spatial(reps, swindow, fill, *size)
