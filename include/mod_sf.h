@@ -589,6 +589,60 @@ int  mod_get_flow_median(const ModContext *ctx, ModFlowMedian *filter);
  * the context's stream; keeps no state, needs no scratch. */
 int  mod_flow_median_dev(ModContext *ctx, int32_t frames, const float *flow_in, const ModFlowMedian *filter, float *flow_out);
 
+/* ---- disparity-gated hole fill of the on-GPU optical flow ------------------------------------------------------------------- */
+/* Opt-in last stage of the flow in the submits that hold the same frame's disparity.  The forward-backward check, the texture rule,
+ * the min-eigenvalue rule and the median above only ever remove vectors; the scene flow gives a pixel without a vector no velocity
+ * and the clusterer counts it as static.  The rejections fall on the border of a moving object (occluded or revealed background)
+ * and on its flat interior, the pixels the windowed clusterer needs.  A blind fill would carry motion across the object's edge, so a
+ * hole is filled only from valid neighbours ON THE SAME SURFACE: those whose disparity lies within a gate of the hole's own.  The
+ * rule (tests/models/flow_fill_model.py restates it bit for bit), for a flow [F][H][W][2] float32 and the
+ * disparity planes of the same frames [F][H][W] float32:
+ *   A flow pixel is VALID when both of its components are finite (mod_flow_median_dev's definition).  A disparity word d is VALID
+ *   when it is finite and d > 0: the rejected pixels' -1, 0, NaN and +-inf are invalid; the camera's range is not consulted.
+ *   The gate of a pixel p with disparity d_p is g = tol_abs + tol_rel * d_p, computed as two float32 operations, a multiply and then
+ *   an add, each rounded (never one fma).  A neighbour q PASSES when the float32 result of fabsf(d_q - d_p) is <= g.
+ *   S is the set of pixels q != p of the window x window square centred on p, CLIPPED to the image — no replication, no wrap, no
+ *   other frame — that have a valid flow, a valid disparity and pass the gate; n = |S|.
+ *     p valid:                                        the output pixel is the input pixel, both words, bit for bit: the fill never
+ *                                                     changes a measured vector
+ *     p invalid with an invalid disparity, or n < min_valid:  the same: NaN payloads and +-inf stay exactly as they came
+ *     any other invalid p:                            FILLED: out.x is the LOWER MEDIAN of the x components of S and out.y the lower
+ *                                                     median of the y components, each taken on its own: the element of index
+ *                                                     (n - 1) / 2 (integer division) in ascending order of the key
+ *                                                     k(b) = b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000) of the float's bits, the
+ *                                                     median filter's order.  Every filled word is one of the input words of S.
+ *   ONE PASS: the fill reads the input plane and writes another; a filled pixel never feeds another fill, nothing cascades.
+ * window: 0 (off, the default), 3, 5 or 7.  min_valid: 1 .. window^2 - 1 (not looked at while window is 0).  tol_abs, tol_rel:
+ * finite, >= 0, in disparity pixels / per disparity pixel.
+ *
+ * mod_set_flow_fill: context state like mod_set_flow_median, read when a submit is made; a frame in flight completes with the setting
+ * of its own submit.  NULL or window 0: off — every entry point enqueues the kernels it always did, allocates nothing and writes the
+ * same bytes.  A window other than 0 / 3 / 5 / 7, min_valid out of range, a negative or non-finite tolerance or a non-zero reserved
+ * word: MOD_ERR_INVALID_ARGUMENT, the setting stays as it was, and mod_last_error names the flow fill.  While on, the fill runs in the
+ * three submits that hold the flow and the same frame's disparity in HBM: mod_submit_images_host, mod_submit_odometry_host and
+ * mod_submit_depth_host.  It is the LAST flow stage, behind the median, and reads the disparity of the NOW frame, the pixel the flow is
+ * addressed at.  In the odometry and depth streams it runs behind the ego-motion estimate, which sees measured vectors only (a filled
+ * vector is a copy of a measured one and would vote twice), and in front of the scene flow, which sees the filled flow.  The flow
+ * plane a submit hands back (flow_out) is the FILLED one.  The measured flow goes to a plane of max_width x max_height x 8 bytes,
+ * allocated at the first submit with the fill on and never when off.  mod_flow_compute_dev / _host have no disparity and are NOT
+ * affected, and neither is mod_submit_stereo_host, whose flow is the caller's. */
+typedef struct ModFlowFill {       /* 24 bytes; NULL or window 0: off (the default) */
+  int32_t window;                  /* 0, 3, 5 or 7 */
+  int32_t min_valid;               /* 1 .. window * window - 1 */
+  float   tol_abs, tol_rel;        /* finite, >= 0; disparity pixels */
+  int32_t reserved[2];             /* must be 0 */
+} ModFlowFill;
+int  mod_set_flow_fill(ModContext *ctx, const ModFlowFill *fill);
+/* as set; never set, or set with NULL: all zero */
+int  mod_get_flow_fill(const ModContext *ctx, ModFlowFill *fill);
+/* The fill alone, on a caller's own flow [frames][H][W][2] and the disparity planes [frames][H][W] of the same frames, into flow_out
+ * of the flow's size.  fill NULL: the context's.  A stencil cannot run in place: flow_in and flow_out must not overlap.  A NULL
+ * plane, overlapping planes, an invalid fill or window 0 (nothing to do): MOD_ERR_INVALID_ARGUMENT; before a camera is set:
+ * MOD_ERR_NOT_CONFIGURED.  Every pixel of flow_out is stored; flow_in and disparity are only read.  Ordered on the context's stream;
+ * keeps no state, needs no scratch. */
+int  mod_flow_fill_dev(ModContext *ctx, int32_t frames, const float *flow_in, const float *disparity, const ModFlowFill *fill,
+                       float *flow_out);
+
 /* ---- on-GPU stereo ego-motion ---------------------------------------------------------------------------------------------- */
 /* The reference obtains transform_prev2now_ from libviso2 (VisualOdometryStereo::process + getMotion(),
  * scene_flow_constructor.cpp:214-256), sparse features matched in four images on the CPU.  This estimator is NOT libviso2 and

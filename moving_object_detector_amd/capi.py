@@ -144,6 +144,17 @@ def flow_median(window: int = 5, min_valid: int = 0) -> ModFlowMedian:
     return ModFlowMedian(int(window), int(min_valid), (0, 0))
 
 
+class ModFlowFill(C.Structure):
+    _fields_ = [("window", C.c_int32), ("min_valid", C.c_int32), ("tol_abs", C.c_float), ("tol_rel", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+def flow_fill(window: int = 5, min_valid: int = 3, tol_abs: float = 1.0, tol_rel: float = 0.0) -> ModFlowFill:
+    """ModFlowFill of include/mod_sf.h (window 0 = off, 3, 5 or 7): an invalid flow pixel with a valid disparity d becomes the
+    per-component lower median of the valid flow pixels of its window x window square whose disparity lies within tol_abs + tol_rel * d
+    of d, where at least `min_valid` of them do; every other pixel stays.  These defaults are placeholders, not tuned on any scene."""
+    return ModFlowFill(int(window), int(min_valid), float(tol_abs), float(tol_rel), (0, 0))
+
+
 class ModFlowParams(C.Structure):
     _fields_ = [("levels", C.c_int32), ("radius", C.c_int32), ("window", C.c_int32), ("subpixel", C.c_int32), ("fb_check", C.c_int32)]
 
@@ -372,6 +383,7 @@ assert C.sizeof(ModImageBinning) == 16
 assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
 assert C.sizeof(ModFlowMedian) == 16
+assert C.sizeof(ModFlowFill) == 24
 
 
 def distortion_model(model) -> int:
@@ -463,6 +475,9 @@ SIGNATURES = {
     "mod_set_flow_median": [_vp, C.POINTER(ModFlowMedian)],
     "mod_get_flow_median": [_vp, C.POINTER(ModFlowMedian)],
     "mod_flow_median_dev": [_vp, _i32, _vp, C.POINTER(ModFlowMedian), _vp],
+    "mod_set_flow_fill": [_vp, C.POINTER(ModFlowFill)],
+    "mod_get_flow_fill": [_vp, C.POINTER(ModFlowFill)],
+    "mod_flow_fill_dev": [_vp, _i32, _vp, _vp, C.POINTER(ModFlowFill), _vp],
     "mod_set_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera)],
     "mod_get_rectification": [_vp, C.POINTER(ModRectifyCamera), C.POINTER(ModRectifyCamera), C.POINTER(_i32)],
     "mod_rectify_dev": [_vp, _i32, _vp, C.POINTER(ModImageLayout), _i32, _vp],

@@ -192,6 +192,8 @@ struct StereoFrame {
   Pipe::RingPlane &now, &prev;
   ImageIngest img;                   // layout, rectification and side by side as they are at this submit; the slot's stages; grow_for: the grey images
   DepthPlan depth;                   // RGB-D: the depth settings as they are at this submit; upload_depth: of the staged copy
+  ModFlowFill fill;                  // the flow's hole fill as it is at this submit; window 0 (and every submit that estimates no flow): off
+  bool fills() const { return fill.window != 0; }
 };
 
 // what an RGB-D submit cannot do, whatever its arguments: the state stays as it was
@@ -226,6 +228,7 @@ static int stereo_checks(ModContext *c, const StereoRequest &rq, ModImageLayout 
 static int grow_for(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   if (!rq.rgbd) HIP_TRY(c, dalloc(f.s.img, 2 * c->maxN));
   if (rq.estimates_flow()) HIP_TRY(c, dalloc(f.now.left, c->maxN));
+  if (f.fills()) HIP_TRY(c, dalloc(c->b.flow.unfilled, c->maxN));
   if (rq.rgbd) {
     if (int rc = ensure_stage_bytes(c, f.s.depth, depth_stage(c, f.depth).bytes())) return rc;
     if (f.depth.registered) HIP_TRY(c, dalloc(f.s.zbuf, c->maxN));
@@ -288,18 +291,27 @@ static int estimate(ModContext *c, const StereoRequest &rq, StereoFrame &f) {
   p.prev_img_rgbd = rq.rgbd;
   // disparity_now exists by now
   if (int rc = construct_skip(has_flow, had_prev, rq.transform || rq.odometry(), true)) return rc;
+  // with the hole fill on, the measured flow goes to the context's plane in front of the fill (all flow work is on the context's stream, so one
+  // plane serves every frame in flight) and the fill, below, writes the frame's flow buffer: everything behind it reads that one as ever
+  float *const measured = f.fills() ? reinterpret_cast<float *>(c->b.flow.unfilled.get()) : f.s.flow.get();
   if (rq.estimates_flow()) {        // estimateOpticalFlow (:279-290) on the GPU, straight into the frame's flow buffer
-    if (int rc = mod_flow_compute_dev(c, 1, f.prev.left, f.now.left, rq.flow_prm, f.s.flow)) return rc;
+    if (int rc = mod_flow_compute_dev(c, 1, f.prev.left, f.now.left, rq.flow_prm, measured)) return rc;
     HIP_TRY(c, f.prev.left_read.record(c->stream));
     HIP_TRY(c, f.now.left_read.record(c->stream));
   }
-  if (!rq.odometry()) return MOD_OK;
-  // the odometry stream: libviso2's process + getMotion (:214-256) on the GPU; its last kernel writes the frame's constants into b.fc,
-  // which the scene-flow launch reads (fc_resident)
-  HIP_TRY(c, dalloc(p.ego, MOD_PIPELINE_DEPTH));
-  f.s.ego = p.ego.get() + (&f.s - p.slot);
-  if (!f.s.h_ego) HIP_TRY(c, hipHostMalloc((void **)f.s.h_ego.put(), sizeof(Pipe::EgoSlot), hipHostMallocDefault));
-  return run_egomotion(c, 1, f.prev.disparity, f.now.disparity, f.s.flow, rq.ego_prm, &f.s.ego->tf, &f.s.ego->res, c->b.fc, rq.dt);
+  if (rq.odometry()) {
+    // the odometry stream: libviso2's process + getMotion (:214-256) on the GPU; its last kernel writes the frame's constants into b.fc,
+    // which the scene-flow launch reads (fc_resident).  It sees measured vectors only: a filled one is a copy of a measured one and would vote twice
+    HIP_TRY(c, dalloc(p.ego, MOD_PIPELINE_DEPTH));
+    f.s.ego = p.ego.get() + (&f.s - p.slot);
+    if (!f.s.h_ego) HIP_TRY(c, hipHostMalloc((void **)f.s.h_ego.put(), sizeof(Pipe::EgoSlot), hipHostMallocDefault));
+    if (int rc = run_egomotion(c, 1, f.prev.disparity, f.now.disparity, measured, rq.ego_prm, &f.s.ego->tf, &f.s.ego->res, c->b.fc, rq.dt)) return rc;
+  }
+  if (!f.fills()) return MOD_OK;
+  // the hole fill, the last flow stage, gated by disparity_now: the flow is addressed at the NOW pixel (sceneflow.hip reads flow[i] beside dnow[i] to find the previous point)
+  launch_flow_fill(c->dc.W, c->dc.H, 1, f.fill.window, f.fill.min_valid, f.fill.tol_abs, f.fill.tol_rel, measured, f.now.disparity, f.s.flow, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
 }
 
 static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq) {
@@ -308,7 +320,7 @@ static int submit_stereo(ModContext *c, int32_t *ticket, const StereoRequest &rq
   DepthPlan plan{};
   int rc = open_frame(c, ticket, &at, [&] { return stereo_checks(c, rq, &lay, &plan); });
   if (rc) return rc;
-  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, plan};
+  StereoFrame f{*at.s, *at.now, *at.prev, ImageIngest{}, plan, rq.estimates_flow() ? c->opt.flow_fill : ModFlowFill{}};
   f.img.lay = lay; f.img.rectify = c->rect.on; f.img.panes = c->side_by_side; f.img.eye1 = MOD_EYE_RIGHT; f.img.batch2 = false;
   f.img.raw = &f.s.raw; f.img.bayer_grey = &f.s.bayer_grey;
   f.img.bin = c->binning; f.img.bin_grey = &f.s.bin_grey;

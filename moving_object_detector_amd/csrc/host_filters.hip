@@ -1,9 +1,11 @@
 // host_filters.hip — the rules of the two image estimators that also exist as calls of their own, host side (no kernel): per filter its
 // check, its setting's set / get pair (the defaults are EstimatorOptions') and its stand-alone entry points — the disparity's rejection
-// filters with the speckle scratch, the texture threshold both estimators share, the flow's min-eigenvalue threshold and its median.
+// filters with the speckle scratch, the texture threshold both estimators share, the flow's min-eigenvalue threshold, its median and its hole fill.
 // host_sgm.hip and host_flow.hip enqueue the same launches inside their chains.  The kernels live in disparity_filter.hip (uniqueness:
-// sgm.hip), texture.hip, corner.hip and flow_median.hip.
+// sgm.hip), texture.hip, corner.hip, flow_median.hip and flow_fill.hip.
 #include "host_options.h"
+
+#include <cfloat>
 
 // ---- rejection filters of the disparity (sgm.hip: uniqueness; disparity_filter.hip: speckle) -------------------------------
 static int check_disparity_filters(ModContext *c, const ModDisparityFilters &f) {
@@ -62,9 +64,20 @@ static int check_flow_median(ModContext *c, const ModFlowMedian &f) {
   return MOD_OK;
 }
 
+// ---- disparity-gated hole fill of the flow (flow_fill.hip) -------------------------------------------------------------------------
+static int check_flow_fill(ModContext *c, const ModFlowFill &f) {
+  if (f.window != 0 && f.window != 3 && f.window != 5 && f.window != 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow fill window must be 0, 3, 5 or 7");
+  if (f.window != 0 && (f.min_valid < 1 || f.min_valid > f.window * f.window - 1)) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow fill min_valid must be in 1..window^2 - 1");
+  // (window 0, off: min_valid has no range to lie in and is not looked at)
+  if (!(f.tol_abs >= 0.0f && f.tol_abs <= FLT_MAX) || !(f.tol_rel >= 0.0f && f.tol_rel <= FLT_MAX))   // a NaN fails both comparisons
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow fill tolerances must be finite and >= 0");
+  if (f.reserved[0] != 0 || f.reserved[1] != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow fill reserved must be 0");
+  return MOD_OK;
+}
+
 extern "C" {
 
-// ---- the four settings ------------------------------------------------------------------------------------------------------
+// ---- the five settings ------------------------------------------------------------------------------------------------------
 int mod_set_disparity_filters(ModContext *c, const ModDisparityFilters *f) { return set_option(c, &EstimatorOptions::disparity_filters, f, check_disparity_filters); }
 int mod_get_disparity_filters(const ModContext *c, ModDisparityFilters *f) { return get_option(c, &EstimatorOptions::disparity_filters, f); }
 int mod_set_texture_filter(ModContext *c, const ModTextureFilter *f) { return set_option(c, &EstimatorOptions::texture_filter, f, check_texture_filter); }
@@ -73,6 +86,8 @@ int mod_set_flow_corner_filter(ModContext *c, const ModCornerFilter *f) { return
 int mod_get_flow_corner_filter(const ModContext *c, ModCornerFilter *f) { return get_option(c, &EstimatorOptions::flow_corner_filter, f); }
 int mod_set_flow_median(ModContext *c, const ModFlowMedian *f) { return set_option(c, &EstimatorOptions::flow_median, f, check_flow_median); }
 int mod_get_flow_median(const ModContext *c, ModFlowMedian *f) { return get_option(c, &EstimatorOptions::flow_median, f); }
+int mod_set_flow_fill(ModContext *c, const ModFlowFill *f) { return set_option(c, &EstimatorOptions::flow_fill, f, check_flow_fill); }
+int mod_get_flow_fill(const ModContext *c, ModFlowFill *f) { return get_option(c, &EstimatorOptions::flow_fill, f); }
 
 // ---- the stand-alone calls (f == null: the setting in force) -------------------------------------------------------------------
 int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, int32_t speckle_size, int32_t speckle_range) {
@@ -144,6 +159,20 @@ int mod_flow_median_dev(ModContext *c, int32_t frames, const float *flow_in, con
   const uintptr_t a = (uintptr_t)flow_in, b = (uintptr_t)flow_out, bytes = (uintptr_t)frames * c->dc.W * c->dc.H * 8;
   if (a < b + bytes && b < a + bytes) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow median planes overlap: a stencil cannot run in place");
   launch_flow_median(c->dc.W, c->dc.H, frames, m.window, m.min_valid, flow_in, flow_out, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_flow_fill_dev(ModContext *c, int32_t frames, const float *flow_in, const float *disparity, const ModFlowFill *f, float *flow_out) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!flow_in || !disparity || !flow_out) return fail(c, MOD_ERR_INVALID_ARGUMENT, "null flow fill plane");
+  const ModFlowFill m = f ? *f : c->opt.flow_fill;
+  if ((rc = check_flow_fill(c, m))) return rc;
+  if (m.window == 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow fill window 0: nothing to do");
+  const uintptr_t a = (uintptr_t)flow_in, b = (uintptr_t)flow_out, bytes = (uintptr_t)frames * c->dc.W * c->dc.H * 8;
+  if (a < b + bytes && b < a + bytes) return fail(c, MOD_ERR_INVALID_ARGUMENT, "flow fill planes overlap: a stencil cannot run in place");
+  launch_flow_fill(c->dc.W, c->dc.H, frames, m.window, m.min_valid, m.tol_abs, m.tol_rel, flow_in, disparity, flow_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -97,6 +97,7 @@ struct Buffers {
     DevPtr<short2> winners;                 // [2 levels, ping-pong][2 directions][maxF][maxN] integer winners
     DevPtr<short4> sub;                     // [maxF][maxN] sub-pixel terms of level 0
     DevPtr<float2> unfiltered;              // [maxF][maxN] the flow in front of the median filter; allocated at the first call with mod_set_flow_median on
+    DevPtr<float2> unfilled;                // [maxN] a submit's flow in front of the hole fill (the slot's buffer takes the filled one); allocated at the first submit with mod_set_flow_fill on
   } flow;
   struct Ego {                              // on-GPU ego-motion (allocated on first use; the correspondence buffers grow to the smallest stride seen: ensure_ego_scratch)
     DevPtr<double> corr, hyp;               // [maxF][9][cap], [maxF][MOD_EGO_MAX_HYPOTHESES][12]
@@ -111,7 +112,7 @@ struct Buffers {
 struct EstimatorOptions {
   int32_t disparity_subpixel = 0, disparity_offset = 0; ModDisparityFilters disparity_filters{};   // disparity: fraction bits; where the window starts (mod_sgm_path_dev reads it too)
   ModTextureFilter texture_filter{0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW};             // both, as `apply` says
-  int32_t flow_propagation = 1; ModCornerFilter flow_corner_filter{0, 9, 31, 0}; ModFlowMedian flow_median{};   // flow: seeds of a search (1: the parent's winner alone)
+  int32_t flow_propagation = 1; ModCornerFilter flow_corner_filter{0, 9, 31, 0}; ModFlowMedian flow_median{}; ModFlowFill flow_fill{};   // flow: seeds of a search (1: the parent's winner alone); the fill runs in the submits only (host_api.hip)
 };
 
 // The settings of the depth input (RGB-D cameras), one member per mod_set_depth_* / mod_get_depth_* pair and named like it (host_depth.hip); these initialisers

@@ -153,6 +153,12 @@ void launch_corner(int W, int H, int frames, int window, int cap, int threshold,
 // `out` is stored, `in` is only read
 void launch_flow_median(int W, int H, int frames, int window, int min_valid, const float *in, float *out, hipStream_t s);
 
+// disparity-gated hole fill of a finished flow (flow_fill.hip): `in` [frames][H][W][2] and the disparity planes of the same frames
+// [frames][H][W] -> `out` of the flow's size, a different plane (checked by the caller, as window 3, 5 or 7, min_valid 1 .. window^2 - 1
+// and the two tolerances are).  ONE launch; every pixel of `out` is stored, `in` and `disparity` are only read
+void launch_flow_fill(int W, int H, int frames, int window, int min_valid, float tol_abs, float tol_rel, const float *in, const float *disparity,
+                      float *out, hipStream_t s);
+
 // on-GPU optical flow (flow.hip).  Pyramid level of both images: src0 / src1 [frames][Hs][Ws] -> dst [2][frames][H][W].
 void launch_flow_pyramid(int Ws, int Hs, int W, int H, int frames, const uint8_t *src0, const uint8_t *src1, uint8_t *dst, hipStream_t s);
 // one level, `dirs` directions (1: forward, 2: + backward); coarse == nullptr: the coarsest level.  census [2][frames][H][W] (prev, now),

@@ -94,6 +94,15 @@ class SceneFlowConstructor {
     const ModFlowMedian f{window, min_valid, {0, 0}};
     check(mod_set_flow_median(ctx_, &f));
   }
+  // disparity-gated hole fill of the flow (mod_set_flow_fill): the last flow stage of the submits that estimate the flow, behind the
+  // median and the ego-motion estimate, in front of the scene flow.  An invalid flow pixel with a valid disparity d becomes the
+  // per-component lower median of the valid flow pixels of its window x window square (window 3, 5 or 7) whose disparity lies within
+  // tol_abs + tol_rel * d of d, where at least min_valid of them do; every other pixel stays.  window 0 = off, the default.  Throws
+  // where the library refuses a value; frames already submitted keep the setting of their submit.  No node parameter sets it.
+  void setFlowFill(int window, int min_valid, float tol_abs, float tol_rel) {
+    const ModFlowFill f{window, min_valid, tol_abs, tol_rel, {0, 0}};
+    check(mod_set_flow_fill(ctx_, &f));
+  }
   // rejection filters of the disparity (mod_set_disparity_filters; stereo_image_proc's names): uniqueness ratio in percent, regions of at
   // most speckle_size pixels whose neighbours differ by at most speckle_range disparities are invalidated; all 0 = off, the default.
   // Frames already submitted keep the settings of their submit.

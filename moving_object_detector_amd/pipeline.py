@@ -195,6 +195,23 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_flow_median(self.h, C.byref(f)))
         return f
 
+    def set_flow_fill(self, window=None, min_valid: int = 3, tol_abs: float = 1.0, tol_rel: float = 0.0) -> None:
+        """Disparity-gated hole fill of the flow in the submits that estimate it (mod_set_flow_fill), off by default: the last flow stage,
+        behind the median and the ego-motion estimate and in front of the scene flow; an invalid flow pixel with a valid disparity d
+        becomes the per-component lower median of the valid flow pixels of its window x window square (window 3, 5 or 7) whose disparity
+        lies within tol_abs + tol_rel * d of d, where at least `min_valid` do.  No argument or None turns it off; a capi.ModFlowFill is
+        taken as it is.  Read when a submit is made.  The defaults are not tuned."""
+        if window is None:
+            self._check(self.lib.mod_set_flow_fill(self.h, None))
+            return
+        f = window if isinstance(window, capi.ModFlowFill) else capi.flow_fill(window, min_valid, tol_abs, tol_rel)
+        self._check(self.lib.mod_set_flow_fill(self.h, C.byref(f)))
+
+    def get_flow_fill(self) -> capi.ModFlowFill:
+        f = capi.ModFlowFill(-1, -1, -1.0, -1.0, (-1, -1))
+        self._check(self.lib.mod_get_flow_fill(self.h, C.byref(f)))
+        return f
+
     def set_cluster_members(self, ws: Optional[dict]) -> None:
         """Per-cluster member lists (mod_set_cluster_members), off by default: every later cluster() / process() and the synchronous
         host calls write offsets, indices (and points) into the tensors of `ws` (workspace(..., members=True)); None turns them off.
@@ -692,6 +709,25 @@ class Context(HostCalls):
             raise ValueError("out must be a contiguous float32 tensor of flow's size")
         self._done(self.lib.mod_flow_median_dev(self.h, F, flow.data_ptr(), C.byref(filter) if filter is not None else None, out.data_ptr()),
                    "mod_flow_median_dev")
+        return out.view(F, self.height, self.width, 2)
+
+    def flow_fill(self, flow: torch.Tensor, disparity: torch.Tensor, fill: Optional[capi.ModFlowFill] = None,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The disparity-gated hole fill alone (mod_flow_fill_dev) on a device flow (F, H, W, 2) or (H, W, 2) float32 and the disparity
+        planes (F, H, W) or (H, W) float32 of the same frames, at the camera size, into `out` (another tensor of the flow's size; a new
+        one when None) — returned as (F, H, W, 2).  fill None = the context's; window 0 is refused.  Enqueued on the context's stream."""
+        if flow.dtype != torch.float32 or not flow.is_contiguous() or flow.device.type != "cuda" or flow.shape[-3:] != (self.height, self.width, 2):
+            raise ValueError("flow must be a contiguous float32 device tensor (F, H, W, 2) at the camera size")
+        F = flow.numel() // (self.height * self.width * 2)
+        if (disparity.dtype != torch.float32 or not disparity.is_contiguous() or disparity.device != flow.device
+                or disparity.shape[-2:] != (self.height, self.width) or disparity.numel() != F * self.height * self.width):
+            raise ValueError("disparity must be a contiguous float32 tensor (F, H, W) on the flow's device, with the flow's frames")
+        if out is None:
+            out = torch.empty((F, self.height, self.width, 2), dtype=torch.float32, device=flow.device)
+        elif out.numel() != flow.numel() or out.shape[-3:] != flow.shape[-3:] or out.dtype != torch.float32 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 tensor of flow's size")
+        self._done(self.lib.mod_flow_fill_dev(self.h, F, flow.data_ptr(), disparity.data_ptr(), C.byref(fill) if fill is not None else None,
+                                              out.data_ptr()), "mod_flow_fill_dev")
         return out.view(F, self.height, self.width, 2)
 
     def pinned_copy(self, array) -> "PinnedBuffer":
