@@ -397,6 +397,52 @@ int  mod_get_disparity_offset(const ModContext *ctx, int32_t *min_disparity);
  * nothing to do.  Ordered on the context's stream; scratch (8 bytes per pixel of max_frames frames) is allocated on first use.
  * NULL plane -> MOD_SKIP_NO_DISPARITY_NOW. */
 int  mod_disparity_speckle_dev(ModContext *ctx, int32_t frames, float *disparity, int32_t speckle_size, int32_t speckle_range);
+/* Occlusion hole fill, opt-in (the "discontinuity preserving interpolation" of Hirschmueller's SGM refinement, without its
+ * classification): context state like the rejection filters, read when a call or a submit enqueues its estimator (the same five entry
+ * points); a frame in flight completes with the setting of its own submit.  The left-right check, the uniqueness, texture and speckle
+ * rules only ever remove disparities; the check removes by design the strip left of every foreground object that the right camera
+ * cannot see, and a pixel at -1 has no 3-D point, no velocity and no part in a cluster.  The fill is the LAST stage of the estimator,
+ * behind the speckle stage.  The rule (tests/models/disparity_fill_model.py restates it bit for bit), for
+ * planes [F][H][W] float32:
+ *   VALIDITY     a word d is valid iff it is finite and d >= lo.  Inside the estimator lo = 0.0f, the speckle stage's rule: -1 is
+ *                invalid whatever the disparity offset is, and -0.0 is valid.  In mod_disparity_fill_dev lo is the camera's
+ *                min_disparity, as in mod_disparity_speckle_dev.
+ *   SEARCH       an invalid pixel p = (x, y) walks each of the first `directions` of mod_sgm_path_dev's list, (+1,0) (-1,0) (0,+1)
+ *                (0,-1) (+1,+1) (-1,-1) (-1,+1) (+1,-1): direction k visits p + s * (dx_k, dy_k) for s = 1 .. reach and stops at the
+ *                first valid word v_k, or where the next step would leave the image of its own frame: a walk never wraps into the next
+ *                row, the next frame or the plane before it.  n is the number of directions that found a word.
+ *   CONDITION    p valid, or n < min_found: out = in, bit for bit — NaN payloads, +-inf and -1 pass through unchanged.
+ *   VALUE        otherwise out is the element of rank r of the n found words in ascending order of the integer key
+ *                k(b) = b ^ ((b >> 31) ? 0xFFFFFFFF : 0x80000000) of their bits (the flow median's order: -0.0 sorts before +0.0):
+ *                MIN r = 0 (the background, the farthest surface in sight: an occlusion is never filled from the object that hides it),
+ *                SECOND r = min(1, n - 1) (the paper's choice for an occlusion), MEDIAN r = (n - 1) >> 1 (its choice for a mismatch).
+ *                No float arithmetic: every output word is one of the input plane's words, so a filled pixel lies inside the
+ *                DisparityImage's [min_disparity, max_disparity].
+ *   SINGLE PASS  the fill reads one plane and writes another; a filled pixel feeds no other fill.
+ * reach 0 or NULL: off (the default) — the estimator allocates nothing, enqueues exactly the kernels it did and writes the same bytes.
+ * While on, the stages in front of the fill work on a scratch plane of a group of frames (4 bytes per pixel of the group, allocated at
+ * the first call with the fill on, grow-only) and the fill writes the caller's plane.  Consequences: the ego-motion estimator and the
+ * gate of mod_set_flow_fill both see the FILLED disparity; the sub-pixel mode and the disparity offset need nothing special, the fill
+ * copies float words.  reach outside 0..256, directions other than 2, 4 or 8, a mode other than the three, min_found outside
+ * 1..directions (none of the three looked at while reach is 0): MOD_ERR_INVALID_ARGUMENT, the setting stays as it was, and
+ * mod_last_error names the disparity fill. */
+#define MOD_DISPARITY_FILL_MIN    0
+#define MOD_DISPARITY_FILL_SECOND 1
+#define MOD_DISPARITY_FILL_MEDIAN 2
+typedef struct ModDisparityFill {   /* 16 bytes; NULL or reach 0: off (the default) */
+  int32_t reach;             /* 0..256: the steps a direction may walk; 0 = off */
+  int32_t directions;        /* 2, 4 or 8: the first so many of the list above */
+  int32_t mode;              /* MOD_DISPARITY_FILL_MIN (0), _SECOND (1) or _MEDIAN (2) */
+  int32_t min_found;         /* 1..directions: with fewer found words the hole stays */
+} ModDisparityFill;
+int  mod_set_disparity_fill(ModContext *ctx, const ModDisparityFill *fill);
+/* as set; never set, or set with NULL: all zero */
+int  mod_get_disparity_fill(const ModContext *ctx, ModDisparityFill *fill);
+/* The fill alone, on any 32FC1 disparity planes [frames][H][W] of the camera's size (a caller's own matcher) into disparity_out of the
+ * same size, with lo = the camera's min_disparity.  fill NULL: the context's.  Not in place: overlapping planes, an invalid fill or
+ * reach 0 (nothing to do): MOD_ERR_INVALID_ARGUMENT; a NULL plane -> MOD_SKIP_NO_DISPARITY_NOW.  Every pixel of disparity_out is
+ * stored, disparity_in is only read.  Ordered on the context's stream; keeps no state, needs no scratch. */
+int  mod_disparity_fill_dev(ModContext *ctx, int32_t frames, const float *disparity_in, const ModDisparityFill *fill, float *disparity_out);
 /* stages, for tests and tracing: centre-symmetric census (31 bits per pixel, 0 where the window leaves the image) ... */
 int  mod_sgm_census_dev(ModContext *ctx, int32_t frames, const uint8_t *image, uint32_t *census);
 /* ... and one aggregation path L_r [frames][H][W][disparities] uint8 over the Hamming cost of the census words; direction 0..7 =

@@ -35,6 +35,7 @@ MOD_EGO_MAX_HYPOTHESES = 4096
 MOD_SGM_FRACTION_BITS = 4
 MOD_FLOW_SEEDS = 5
 MOD_TEXTURE_DISPARITY, MOD_TEXTURE_FLOW = 1, 2           # ModTextureFilter.apply: the estimators the texture threshold rejects in
+MOD_DISPARITY_FILL_MIN, MOD_DISPARITY_FILL_SECOND, MOD_DISPARITY_FILL_MEDIAN = 0, 1, 2   # ModDisparityFill.mode: the rank taken of the found words
 MOD_TEXTURE_MAX = 15 * 15 * 255                          # the largest texture sum (window 15, cap 255): it fits a uint16
 MOD_CORNER_MAX = 15 * 15 * 255 * 255                     # 14630625: the largest min-eigenvalue (ModCornerFilter.threshold's upper end)
 MOD_EYE_LEFT, MOD_EYE_RIGHT = 0, 1
@@ -112,6 +113,35 @@ class ModSgmParams(C.Structure):
 
 class ModDisparityFilters(C.Structure):
     _fields_ = [("uniqueness_ratio", C.c_int32), ("speckle_size", C.c_int32), ("speckle_range", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ModDisparityFill(C.Structure):
+    _fields_ = [("reach", C.c_int32), ("directions", C.c_int32), ("mode", C.c_int32), ("min_found", C.c_int32)]
+
+
+_DISPARITY_FILL_MODES = {"min": MOD_DISPARITY_FILL_MIN, "second": MOD_DISPARITY_FILL_SECOND, "median": MOD_DISPARITY_FILL_MEDIAN}
+
+
+def disparity_fill(reach: int, directions: int = 8, mode="min", min_found: int = 1) -> ModDisparityFill:
+    """ModDisparityFill of include/mod_sf.h (reach 0 = off): an invalid disparity walks the first `directions` (2, 4 or 8) of the path
+    directions for up to `reach` (0..256) steps each to the first valid word, and where at least `min_found` (1..directions) of them find
+    one it becomes the lowest ("min", the background), the second lowest ("second") or the lower median ("median") of the found words;
+    every other pixel stays.  `mode` is one of the three names or MOD_DISPARITY_FILL_*.  Raises ValueError where the library would
+    refuse the value.  These defaults are placeholders, not tuned on any scene."""
+    if isinstance(mode, str):
+        if mode not in _DISPARITY_FILL_MODES:
+            raise ValueError(f"disparity fill mode must be one of {sorted(_DISPARITY_FILL_MODES)}, not {mode!r}")
+        mode = _DISPARITY_FILL_MODES[mode]
+    reach, directions, mode, min_found = int(reach), int(directions), int(mode), int(min_found)
+    if not 0 <= reach <= 256:
+        raise ValueError("disparity fill reach must be in 0..256")
+    if directions not in (2, 4, 8):
+        raise ValueError("disparity fill directions must be 2, 4 or 8")
+    if mode not in _DISPARITY_FILL_MODES.values():
+        raise ValueError("disparity fill mode must be MOD_DISPARITY_FILL_MIN, _SECOND or _MEDIAN")
+    if not 1 <= min_found <= directions:
+        raise ValueError("disparity fill min_found must be in 1..directions")
+    return ModDisparityFill(reach, directions, mode, min_found)
 
 
 class ModTextureFilter(C.Structure):
@@ -384,6 +414,7 @@ assert C.sizeof(ModTextureFilter) == 16
 assert C.sizeof(ModCornerFilter) == 16
 assert C.sizeof(ModFlowMedian) == 16
 assert C.sizeof(ModFlowFill) == 24
+assert C.sizeof(ModDisparityFill) == 16
 
 
 def distortion_model(model) -> int:
@@ -462,6 +493,9 @@ SIGNATURES = {
     "mod_set_disparity_offset": [_vp, _i32],
     "mod_get_disparity_offset": [_vp, C.POINTER(_i32)],
     "mod_disparity_speckle_dev": [_vp, _i32, _vp, _i32, _i32],
+    "mod_set_disparity_fill": [_vp, C.POINTER(ModDisparityFill)],
+    "mod_get_disparity_fill": [_vp, C.POINTER(ModDisparityFill)],
+    "mod_disparity_fill_dev": [_vp, _i32, _vp, C.POINTER(ModDisparityFill), _vp],
     "mod_set_flow_propagation": [_vp, _i32],
     "mod_get_flow_propagation": [_vp, C.POINTER(_i32)],
     "mod_set_texture_filter": [_vp, C.POINTER(ModTextureFilter)],

@@ -1,8 +1,8 @@
 // host_filters.hip — the rules of the two image estimators that also exist as calls of their own, host side (no kernel): per filter its
 // check, its setting's set / get pair (the defaults are EstimatorOptions') and its stand-alone entry points — the disparity's rejection
-// filters with the speckle scratch, the texture threshold both estimators share, the flow's min-eigenvalue threshold, its median and its hole fill.
-// host_sgm.hip and host_flow.hip enqueue the same launches inside their chains.  The kernels live in disparity_filter.hip (uniqueness:
-// sgm.hip), texture.hip, corner.hip, flow_median.hip and flow_fill.hip.
+// filters with the speckle scratch and its occlusion hole fill, the texture threshold both estimators share, the flow's min-eigenvalue threshold,
+// its median and its hole fill.  host_sgm.hip and host_flow.hip enqueue the same launches inside their chains.  The kernels live in
+// disparity_filter.hip (uniqueness: sgm.hip), disparity_fill.hip, texture.hip, corner.hip, flow_median.hip and flow_fill.hip.
 #include "host_options.h"
 
 #include <cfloat>
@@ -26,6 +26,29 @@ int ensure_speckle_scratch(ModContext *c, int frames) {
   HIP_TRY(c, dalloc(size, (size_t)frames * c->maxN));
   b.parent = std::move(parent); b.size = std::move(size);   // (swaps: the old planes are released with the locals)
   b.frames = frames;
+  return MOD_OK;
+}
+
+// ---- occlusion hole fill of the disparity (disparity_fill.hip) -------------------------------------------------------------------------
+static int check_disparity_fill(ModContext *c, const ModDisparityFill &f) {
+  if (f.reach < 0 || f.reach > 256) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fill reach must be in 0..256");
+  if (f.reach == 0) return MOD_OK;          // off: the other fields have no range to lie in and are not looked at
+  if (f.directions != 2 && f.directions != 4 && f.directions != 8) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fill directions must be 2, 4 or 8");
+  if (f.mode != MOD_DISPARITY_FILL_MIN && f.mode != MOD_DISPARITY_FILL_SECOND && f.mode != MOD_DISPARITY_FILL_MEDIAN)
+    return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fill mode must be MOD_DISPARITY_FILL_MIN, _SECOND or _MEDIAN");
+  if (f.min_found < 1 || f.min_found > f.directions) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fill min_found must be in 1..directions");
+  return MOD_OK;
+}
+
+// the estimator's plane in front of the fill, for a group of `frames` frames (grow-only; host_sgm.hip)
+int ensure_disparity_fill_scratch(ModContext *c, int frames) {
+  Buffers::Sgm &b = c->b.sgm;
+  if (b.unfilled_frames >= frames) return MOD_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevPtr<float> plane;
+  HIP_TRY(c, dalloc(plane, (size_t)frames * c->maxN));
+  b.unfilled = std::move(plane);            // (swaps: the old plane is released with the local)
+  b.unfilled_frames = frames;
   return MOD_OK;
 }
 
@@ -77,9 +100,11 @@ static int check_flow_fill(ModContext *c, const ModFlowFill &f) {
 
 extern "C" {
 
-// ---- the five settings ------------------------------------------------------------------------------------------------------
+// ---- the six settings -------------------------------------------------------------------------------------------------------
 int mod_set_disparity_filters(ModContext *c, const ModDisparityFilters *f) { return set_option(c, &EstimatorOptions::disparity_filters, f, check_disparity_filters); }
 int mod_get_disparity_filters(const ModContext *c, ModDisparityFilters *f) { return get_option(c, &EstimatorOptions::disparity_filters, f); }
+int mod_set_disparity_fill(ModContext *c, const ModDisparityFill *f) { return set_option(c, &EstimatorOptions::disparity_fill, f, check_disparity_fill); }
+int mod_get_disparity_fill(const ModContext *c, ModDisparityFill *f) { return get_option(c, &EstimatorOptions::disparity_fill, f); }
 int mod_set_texture_filter(ModContext *c, const ModTextureFilter *f) { return set_option(c, &EstimatorOptions::texture_filter, f, check_texture_filter); }
 int mod_get_texture_filter(const ModContext *c, ModTextureFilter *f) { return get_option(c, &EstimatorOptions::texture_filter, f); }
 int mod_set_flow_corner_filter(ModContext *c, const ModCornerFilter *f) { return set_option(c, &EstimatorOptions::flow_corner_filter, f, check_corner_filter); }
@@ -99,6 +124,20 @@ int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, i
   if ((rc = ensure_speckle_scratch(c, c->cfg.max_frames))) return rc;
   launch_speckle(c->dc.W, c->dc.H, frames, c->cam.min_disparity, c->cam.min_disparity - 1.0f, speckle_size, speckle_range, disparity,
                  c->b.spk.parent, c->b.spk.size, c->b.dbg, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_disparity_fill_dev(ModContext *c, int32_t frames, const float *disparity_in, const ModDisparityFill *f, float *disparity_out) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!disparity_in || !disparity_out) return MOD_SKIP_NO_DISPARITY_NOW;
+  const ModDisparityFill m = f ? *f : c->opt.disparity_fill;
+  if ((rc = check_disparity_fill(c, m))) return rc;
+  if (m.reach == 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fill reach 0: nothing to do");
+  const uintptr_t a = (uintptr_t)disparity_in, b = (uintptr_t)disparity_out, bytes = (uintptr_t)frames * c->dc.W * c->dc.H * 4;
+  if (a < b + bytes && b < a + bytes) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity fill planes overlap: the fill cannot run in place");
+  launch_disparity_fill(c->dc.W, c->dc.H, frames, c->cam.min_disparity, m.reach, m.directions, m.mode, m.min_found, disparity_in, disparity_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -134,6 +134,12 @@ void launch_sgm_finish(int W, int H, int frames, int D, int off, int paths, size
 void launch_speckle(int W, int H, int frames, float lo, float invalid, int speckle_size, int speckle_range, float *disparity,
                     int32_t *parent, int32_t *size, unsigned long long *dbg, hipStream_t s);
 
+// occlusion hole fill of a finished disparity (disparity_fill.hip): `in` [frames][H][W] -> `out` of the same size, a different plane
+// (checked by the caller, as reach 1..256, directions 2 / 4 / 8, the mode and min_found 1..directions are); a word is valid when it is
+// finite and >= lo.  ONE launch; every pixel of `out` is stored, `in` is only read
+void launch_disparity_fill(int W, int H, int frames, float lo, int reach, int directions, int mode, int min_found, const float *in, float *out,
+                           hipStream_t s);
+
 // texture measure (texture.hip) of grey planes [frames][H][W]: T = the window x window sum of the horizontal central differences capped
 // at `cap` (window odd in 3..15, cap in 1..255; checked by the caller).  ONE launch: `texture` non-null: T itself into [frames][H][W]
 // uint16; else every pixel with T < threshold becomes `invalid` in `disparity` [frames][H][W] and (NaN, NaN) in `flow` [frames][H][W][2]

@@ -110,6 +110,15 @@ class SceneFlowConstructor {
     const ModDisparityFilters f{uniqueness_ratio, speckle_size, speckle_range, 0};
     check(mod_set_disparity_filters(ctx_, &f));
   }
+  // occlusion hole fill of the disparity (mod_set_disparity_fill): the estimator's last stage, behind the speckle stage.  An invalid
+  // disparity walks the first `directions` (2, 4 or 8) path directions for up to `reach` (1..256) steps each to the first valid word and
+  // becomes the lowest (MOD_DISPARITY_FILL_MIN), second lowest (_SECOND) or lower median (_MEDIAN) of the found words where at least
+  // min_found directions found one; every other pixel stays.  reach 0 = off, the default.  Throws where the library refuses a value;
+  // frames already submitted keep the setting of their submit.  No node parameter sets it.
+  void setDisparityFill(int reach, int directions, int mode, int min_found) {
+    const ModDisparityFill f{reach, directions, mode, min_found};
+    check(mod_set_disparity_fill(ctx_, &f));
+  }
   // neighbour-seed propagation of the optical flow (mod_set_flow_propagation): 1 = off, the default; 5 = every finer level also tries the
   // winners of the parent's four neighbours.  Frames already submitted keep the setting of their submit.
   void setFlowPropagation(int seeds) { check(mod_set_flow_propagation(ctx_, seeds)); }

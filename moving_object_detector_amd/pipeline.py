@@ -136,6 +136,24 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_disparity_filters(self.h, C.byref(f)))
         return {"uniqueness_ratio": f.uniqueness_ratio, "speckle_size": f.speckle_size, "speckle_range": f.speckle_range}
 
+    def set_disparity_fill(self, reach=None, directions: int = 8, mode="min", min_found: int = 1) -> None:
+        """Occlusion hole fill of the on-GPU disparity estimator (mod_set_disparity_fill), off by default: the estimator's last stage,
+        behind the speckle stage; an invalid disparity walks the first `directions` (2, 4 or 8) path directions for up to `reach`
+        (1..256) steps each to the first valid word and becomes the lowest ("min"), second lowest ("second") or lower median ("median")
+        of the found words where at least `min_found` directions found one.  No argument, None or 0 turns it off; a
+        capi.ModDisparityFill is taken as it is.  Read when a call or a submit enqueues its estimator; the ego-motion estimator and the
+        flow fill's gate see the filled disparity.  The defaults are not tuned."""
+        if reach is None:
+            self._check(self.lib.mod_set_disparity_fill(self.h, None))
+            return
+        f = reach if isinstance(reach, capi.ModDisparityFill) else capi.disparity_fill(reach, directions, mode, min_found)
+        self._check(self.lib.mod_set_disparity_fill(self.h, C.byref(f)))
+
+    def get_disparity_fill(self) -> capi.ModDisparityFill:
+        f = capi.ModDisparityFill(-1, -1, -1, -1)
+        self._check(self.lib.mod_get_disparity_fill(self.h, C.byref(f)))
+        return f
+
     def set_disparity_offset(self, d0: int = 0) -> None:
         """Minimum disparity of the on-GPU disparity estimator (mod_set_disparity_offset): the search window is [d0, d0 + disparities),
         0 <= d0 <= 128; 0 (the default) = the window starts at 0.  Invalid pixels stay -1.  Read when a call or a submit enqueues its
@@ -619,6 +637,21 @@ class Context(HostCalls):
             raise ValueError("dev_planes must be a contiguous float32 device tensor (F, H, W) at the camera size")
         self._done(self.lib.mod_disparity_speckle_dev(self.h, p.shape[0], p.data_ptr(), int(size), int(range)), "mod_disparity_speckle_dev")
         return dev_planes
+
+    def disparity_fill(self, planes: torch.Tensor, fill: Optional[capi.ModDisparityFill] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The occlusion hole fill alone (mod_disparity_fill_dev) on device float32 planes (F, H, W) or (H, W) of the camera's size, into
+        `out` (another tensor of the planes' size; a new one when None) — returned as (F, H, W).  A word is valid when finite and >= the
+        camera's min_disparity.  fill None = the context's; reach 0 is refused.  Enqueued on the context's stream."""
+        p = planes[None] if planes.dim() == 2 else planes
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device.type != "cuda" or p.shape[1:] != (self.height, self.width):
+            raise ValueError("planes must be a contiguous float32 device tensor (F, H, W) at the camera size")
+        if out is None:
+            out = torch.empty_like(p)
+        elif out.numel() != p.numel() or out.shape[-2:] != p.shape[-2:] or out.dtype != torch.float32 or not out.is_contiguous() or out.device != p.device:
+            raise ValueError("out must be a contiguous float32 tensor of the planes' size on their device")
+        self._done(self.lib.mod_disparity_fill_dev(self.h, p.shape[0], p.data_ptr(), C.byref(fill) if fill is not None else None, out.data_ptr()),
+                   "mod_disparity_fill_dev")
+        return out.view(p.shape)
 
     def _grey_planes(self, grey: torch.Tensor) -> torch.Tensor:
         g = grey[None] if grey.dim() == 2 else grey

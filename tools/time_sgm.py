@@ -1,10 +1,15 @@
 """Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
 usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--offset N] [--texture T [--texture-window w]]
-[--reps N]
+[--reps N] [--fill REACH [--fill-directions N] [--fill-mode M]]
 (--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given; --offset:
 mod_set_disparity_offset, the images' disparities then start at N; --texture: mod_set_texture_filter(T, w, 31, MOD_TEXTURE_DISPARITY),
-off unless given)"""
-import argparse, os, sys, time
+off unless given; --fill REACH: mod_set_disparity_fill(REACH, N, M, 1), off unless given.  With --fill the tool also prints JSON lines:
+the fill's kernel alone (mod_disparity_fill_dev: k_disparity_fill) between HIP events on the estimator's own output of the 8-path run, with the
+share of holes and of filled pixels and the bytes per second of the 8 bytes per pixel it must move, beside the speckle stage alone
+(mod_disparity_speckle_dev, size 100, range 1, on a copy restored before every call outside the timed span) and a plain copy of the same
+planes in the same process; the kernel again on that output with every other pixel made a hole; and, per foreground box of the synthetic
+scenes and for the background, the share of its true pixels that carry a disparity with the fill off and on)"""
+import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -21,6 +26,9 @@ ap.add_argument("--offset", type=int, default=0, metavar="N", help="minimum disp
 ap.add_argument("--texture", type=int, default=0, metavar="T", help="texture threshold (0 = off)")
 ap.add_argument("--texture-window", type=int, default=9, metavar="w", help="window of the texture sum (odd, 3..15)")
 ap.add_argument("--reps", type=int, default=3)
+ap.add_argument("--fill", type=int, default=0, metavar="REACH", help="mod_set_disparity_fill: the reach, 1..256 (0 = off)")
+ap.add_argument("--fill-directions", type=int, default=8, choices=(2, 4, 8), metavar="N", help="directions of --fill")
+ap.add_argument("--fill-mode", default="min", choices=("min", "second", "median"), metavar="M", help="mode of --fill")
 a = ap.parse_args()
 W, H, D = a.W, a.H, a.D
 F = int(os.environ.get("SGM_F", "16"))
@@ -40,6 +48,9 @@ filters += f" offset={a.offset}" if a.offset else ""
 if a.texture:
     ctx.set_texture_filter(a.texture, a.texture_window, 31, capi.MOD_TEXTURE_DISPARITY)
     filters += f" texture={a.texture}/{a.texture_window}"
+if a.fill:
+    ctx.set_disparity_fill(a.fill, a.fill_directions, a.fill_mode, 1)
+    filters += f" fill={a.fill}/{a.fill_directions}/{a.fill_mode}"
 dev = ctx.device
 tl = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev); tr = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
 out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
@@ -55,3 +66,42 @@ for paths in (8, 4):
     ms = 1e3 * (time.perf_counter() - t0) / (a.reps * F)
     print(f"{W}x{H} D={D} paths={paths} frames={F} subpixel={'on' if a.subpixel else 'off'}{filters}: {ms:.3f} ms per frame ({1e3 / ms:.0f} frames/s); "
           f"valid {float((out >= 0).float().mean()):.2f}")
+    if a.fill and paths == 8:
+        def timed(call, before=None, reps=20):
+            """ms per call between two HIP events, one pair per call (so that `before` stays outside), after three warm-up calls"""
+            total = 0.0
+            for i in range(3 + reps):
+                if before:
+                    before()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(); call(); e1.record(); e1.synchronize()
+                total += e0.elapsed_time(e1) if i >= 3 else 0.0
+            return total / reps
+
+        ff = ctx.get_disparity_fill()
+        ctx.set_disparity_fill()
+        plain = ctx.estimate_disparity(tl, tr, prm).clone()          # the estimator's output in front of the fill
+        ctx.set_disparity_fill(ff)
+        half = plain.clone(); half.view(F, -1)[:, ::2] = -1.0
+        filled, work = torch.empty_like(plain), torch.empty_like(plain)
+        base = {"W": W, "H": H, "D": D, "frames": F, "reach": ff.reach, "directions": ff.directions, "mode": a.fill_mode}
+        for what, src in (("k_disparity_fill", plain), ("k_disparity_fill half holes", half)):
+            ms = timed(lambda: ctx.disparity_fill(src, ff, filled))
+            holes = src < 0
+            print(json.dumps({"what": what, **base, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4),
+                              "gbytes_per_s": round(8 * F * H * W / ms / 1e6, 1), "holes": round(float(holes.float().mean()), 4),
+                              "filled": round(float((holes & (filled >= 0)).float().mean()), 4)}), flush=True)
+        ms = timed(lambda: ctx.speckle_filter(work, 100, 1), before=lambda: work.copy_(plain))
+        print(json.dumps({"what": "k_speckle", **base, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4)}), flush=True)
+        ms = timed(lambda: work.copy_(plain))
+        print(json.dumps({"what": "copy", **base, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4),
+                          "gbytes_per_s": round(8 * F * H * W / ms / 1e6, 1)}), flush=True)
+        # the scene figure: per true surface of the synthetic pairs, the share of its pixels that carry a disparity, fill off / on
+        truth = np.stack([p[2] for p in pairs])
+        off, on = plain.cpu().numpy() >= 0, out.cpu().numpy() >= 0
+        back = np.array([np.min(t) for t in truth])[:, None, None]
+        surfaces = {"background": truth == back}
+        surfaces.update({f"box d={int(d)}": (truth == d) & (truth != back) for d in np.unique(truth) if (truth != back)[truth == d].any()})
+        for name, m in surfaces.items():
+            print(json.dumps({"what": "valid share", **base, "surface": name, "pixels": int(m.sum()), "off": round(float(off[m].mean()), 4),
+                              "on": round(float(on[m].mean()), 4)}), flush=True)
