@@ -397,6 +397,52 @@ int  mod_get_disparity_offset(const ModContext *ctx, int32_t *min_disparity);
  * nothing to do.  Ordered on the context's stream; scratch (8 bytes per pixel of max_frames frames) is allocated on first use.
  * NULL plane -> MOD_SKIP_NO_DISPARITY_NOW. */
 int  mod_disparity_speckle_dev(ModContext *ctx, int32_t frames, float *disparity, int32_t speckle_size, int32_t speckle_range);
+/* Edge-preserving smoother, opt-in: context state like the rejection filters, read when a call or a submit enqueues its estimator (the
+ * same five entry points); a frame in flight completes with the setting of its own submit.  Every other stage behind the winner removes
+ * disparities or copies measured words into holes; this one reduces the noise of the disparities that stay, which is what the scene flow
+ * differentiates.  It works in the disparity domain, where matching noise is roughly uniform, so one gate in px serves near and far.  It
+ * is the estimator's stage behind the speckle stage and in front of the hole fill (a fill then copies smoothed words).  The rule
+ * (tests/models/disparity_smooth_model.py restates it bit for bit), for planes [F][H][W] float32, every step one
+ * IEEE float32 operation:
+ *   VALIDITY     a word w is valid iff it is finite and w >= lo.  Inside the estimator lo = 0.0f, what the hole fill uses at the same
+ *                place: -1 is invalid whatever the disparity offset is, and -0.0 is valid.  In mod_disparity_smooth_dev lo is the camera's
+ *                min_disparity, as in mod_disparity_fill_dev.
+ *   INVALID      an invalid pixel: out = in, bit for bit — NaN payloads, +-inf and -1 pass through unchanged.  The smoother never fills a
+ *                hole and never makes one.
+ *   MEMBERS      for a valid pixel with word d: the valid words q of its window x window square (window 3, 5 or 7; the square is clipped
+ *                to the image of the pixel's own frame, it never reaches into the next row's far end, the next frame or the plane before
+ *                it) whose gate fabsf(q - d) <= tol holds, the subtraction rounded to float32.  The pixel is always its own member.
+ *                n is the number of members.
+ *   CONDITION    n < min_members (1..window^2): out = in, bit for bit.
+ *   VALUE        otherwise sum = 0.0f; the members are added one at a time in row-major order of the window, top row first, left to
+ *                right, each step sum = sum + q; out = fmaxf(sum / (float)n, lo).  The order is part of the rule (it is what makes
+ *                arbitrary planes reproducible); the clamp keeps a valid pixel valid where rounding takes the mean below lo.  (A mean of
+ *                -0.0 words is +0.0.  Words so large that the sum of a window's members overflows float32 give +inf: no disparity is.)
+ *   SINGLE PASS  the smoother reads one plane and writes another; a smoothed pixel feeds no other pixel.
+ * A gated mean also turns whole-number disparities on a slanted surface into fractions, with the sub-pixel mode off too.
+ * NULL (or an all-zero struct, what the getter returns while off): off (the default) — the estimator allocates nothing, enqueues exactly
+ * the kernels it did and writes the same bytes.  While on, the stages in front of the smoother work on a scratch plane of a group of
+ * frames (4 bytes per pixel of the group, allocated at the first call with the smoother on, grow-only); the smoother writes the hole
+ * fill's scratch plane where the fill is on and the caller's plane where it is off: no stage reads the plane it writes.  Consequences: the
+ * ego-motion estimator and the gate of mod_set_flow_fill both see the SMOOTHED disparity; smoothed words are not multiples of 1/16.
+ * A window other than 3, 5 or 7, a tol that is negative, NaN or infinite, min_members outside 1..window^2, a non-zero reserved:
+ * MOD_ERR_INVALID_ARGUMENT, the setting stays as it was, and mod_last_error names the disparity smooth.  The defaults of the bindings
+ * (window 5, tol 1, min_members 1) are not tuned on camera data. */
+typedef struct ModDisparitySmooth {   /* 16 bytes; NULL: off (the default) */
+  int32_t window;            /* 3, 5 or 7: the side of the square */
+  int32_t min_members;       /* 1..window^2: with fewer members the pixel stays */
+  float   tol;               /* >= 0, finite: the gate in px of disparity */
+  int32_t reserved;          /* 0 */
+} ModDisparitySmooth;
+int  mod_set_disparity_smooth(ModContext *ctx, const ModDisparitySmooth *smooth);
+/* as set; never set, or set with NULL: all zero */
+int  mod_get_disparity_smooth(const ModContext *ctx, ModDisparitySmooth *smooth);
+/* The smoother alone, on any 32FC1 disparity planes [frames][H][W] of the camera's size (a caller's own matcher) into disparity_out of
+ * the same size, with lo = the camera's min_disparity.  smooth NULL: the context's.  Not in place: disparity_in == disparity_out or any
+ * overlap of the planes, an invalid setting or none (nothing to do): MOD_ERR_INVALID_ARGUMENT; a NULL plane ->
+ * MOD_SKIP_NO_DISPARITY_NOW.  Every pixel of disparity_out is stored, disparity_in is only read.  Ordered on the context's stream; keeps
+ * no state, needs no scratch. */
+int  mod_disparity_smooth_dev(ModContext *ctx, int32_t frames, const float *disparity_in, const ModDisparitySmooth *smooth, float *disparity_out);
 /* Occlusion hole fill, opt-in (the "discontinuity preserving interpolation" of Hirschmueller's SGM refinement, without its
  * classification): context state like the rejection filters, read when a call or a submit enqueues its estimator (the same five entry
  * points); a frame in flight completes with the setting of its own submit.  The left-right check, the uniqueness, texture and speckle

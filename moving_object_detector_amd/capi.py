@@ -144,6 +144,25 @@ def disparity_fill(reach: int, directions: int = 8, mode="min", min_found: int =
     return ModDisparityFill(reach, directions, mode, min_found)
 
 
+class ModDisparitySmooth(C.Structure):
+    _fields_ = [("window", C.c_int32), ("min_members", C.c_int32), ("tol", C.c_float), ("reserved", C.c_int32)]
+
+
+def disparity_smooth(window: int = 5, tol: float = 1.0, min_members: int = 1) -> ModDisparitySmooth:
+    """ModDisparitySmooth of include/mod_sf.h: a valid disparity d becomes the mean, summed in row-major order, of the valid disparities
+    of its `window` x `window` square (3, 5 or 7) that lie within `tol` px (finite, >= 0) of d, where at least `min_members`
+    (1..window^2) do, itself included; every other pixel stays.  Raises ValueError where the library would refuse the value.  These
+    defaults are placeholders, not tuned on camera data."""
+    window, min_members, tol = int(window), int(min_members), float(tol)
+    if window not in (3, 5, 7):
+        raise ValueError("disparity smooth window must be 3, 5 or 7")
+    if not 0.0 <= tol <= 3.4028234663852886e38:          # NaN fails both comparisons; the upper end is FLT_MAX
+        raise ValueError("disparity smooth tol must be finite and >= 0")
+    if not 1 <= min_members <= window * window:
+        raise ValueError("disparity smooth min_members must be in 1..window^2")
+    return ModDisparitySmooth(window, min_members, tol, 0)
+
+
 class ModTextureFilter(C.Structure):
     _fields_ = [("threshold", C.c_int32), ("window", C.c_int32), ("cap", C.c_int32), ("apply", C.c_int32)]
 
@@ -415,6 +434,7 @@ assert C.sizeof(ModCornerFilter) == 16
 assert C.sizeof(ModFlowMedian) == 16
 assert C.sizeof(ModFlowFill) == 24
 assert C.sizeof(ModDisparityFill) == 16
+assert C.sizeof(ModDisparitySmooth) == 16
 
 
 def distortion_model(model) -> int:
@@ -493,6 +513,9 @@ SIGNATURES = {
     "mod_set_disparity_offset": [_vp, _i32],
     "mod_get_disparity_offset": [_vp, C.POINTER(_i32)],
     "mod_disparity_speckle_dev": [_vp, _i32, _vp, _i32, _i32],
+    "mod_set_disparity_smooth": [_vp, C.POINTER(ModDisparitySmooth)],
+    "mod_get_disparity_smooth": [_vp, C.POINTER(ModDisparitySmooth)],
+    "mod_disparity_smooth_dev": [_vp, _i32, _vp, C.POINTER(ModDisparitySmooth), _vp],
     "mod_set_disparity_fill": [_vp, C.POINTER(ModDisparityFill)],
     "mod_get_disparity_fill": [_vp, C.POINTER(ModDisparityFill)],
     "mod_disparity_fill_dev": [_vp, _i32, _vp, C.POINTER(ModDisparityFill), _vp],

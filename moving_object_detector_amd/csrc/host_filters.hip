@@ -1,8 +1,8 @@
 // host_filters.hip — the rules of the two image estimators that also exist as calls of their own, host side (no kernel): per filter its
 // check, its setting's set / get pair (the defaults are EstimatorOptions') and its stand-alone entry points — the disparity's rejection
-// filters with the speckle scratch and its occlusion hole fill, the texture threshold both estimators share, the flow's min-eigenvalue threshold,
+// filters with the speckle scratch, its smoother and its occlusion hole fill, the texture threshold both estimators share, the flow's min-eigenvalue threshold,
 // its median and its hole fill.  host_sgm.hip and host_flow.hip enqueue the same launches inside their chains.  The kernels live in
-// disparity_filter.hip (uniqueness: sgm.hip), disparity_fill.hip, texture.hip, corner.hip, flow_median.hip and flow_fill.hip.
+// disparity_filter.hip (uniqueness: sgm.hip), disparity_smooth.hip, disparity_fill.hip, texture.hip, corner.hip, flow_median.hip and flow_fill.hip.
 #include "host_options.h"
 
 #include <cfloat>
@@ -26,6 +26,28 @@ int ensure_speckle_scratch(ModContext *c, int frames) {
   HIP_TRY(c, dalloc(size, (size_t)frames * c->maxN));
   b.parent = std::move(parent); b.size = std::move(size);   // (swaps: the old planes are released with the locals)
   b.frames = frames;
+  return MOD_OK;
+}
+
+// ---- edge-preserving smoother of the disparity (disparity_smooth.hip) -----------------------------------------------------------------
+static int check_disparity_smooth(ModContext *c, const ModDisparitySmooth &f) {
+  if (f.window == 0 && f.min_members == 0 && f.tol == 0.0f && f.reserved == 0) return MOD_OK;   // all zero: off, what the getter returns for it
+  if (f.window != 3 && f.window != 5 && f.window != 7) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth window must be 3, 5 or 7");
+  if (!(f.tol >= 0.0f) || f.tol > FLT_MAX) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth tol must be finite and >= 0");
+  if (f.min_members < 1 || f.min_members > f.window * f.window) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth min_members must be in 1..window^2");
+  if (f.reserved != 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth reserved field must be 0");
+  return MOD_OK;
+}
+
+// the estimator's plane in front of the smoother, for a group of `frames` frames (grow-only; host_sgm.hip)
+int ensure_disparity_smooth_scratch(ModContext *c, int frames) {
+  Buffers::Sgm &b = c->b.sgm;
+  if (b.unsmoothed_frames >= frames) return MOD_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevPtr<float> plane;
+  HIP_TRY(c, dalloc(plane, (size_t)frames * c->maxN));
+  b.unsmoothed = std::move(plane);          // (swaps: the old plane is released with the local)
+  b.unsmoothed_frames = frames;
   return MOD_OK;
 }
 
@@ -100,9 +122,11 @@ static int check_flow_fill(ModContext *c, const ModFlowFill &f) {
 
 extern "C" {
 
-// ---- the six settings -------------------------------------------------------------------------------------------------------
+// ---- the seven settings -----------------------------------------------------------------------------------------------------
 int mod_set_disparity_filters(ModContext *c, const ModDisparityFilters *f) { return set_option(c, &EstimatorOptions::disparity_filters, f, check_disparity_filters); }
 int mod_get_disparity_filters(const ModContext *c, ModDisparityFilters *f) { return get_option(c, &EstimatorOptions::disparity_filters, f); }
+int mod_set_disparity_smooth(ModContext *c, const ModDisparitySmooth *f) { return set_option(c, &EstimatorOptions::disparity_smooth, f, check_disparity_smooth); }
+int mod_get_disparity_smooth(const ModContext *c, ModDisparitySmooth *f) { return get_option(c, &EstimatorOptions::disparity_smooth, f); }
 int mod_set_disparity_fill(ModContext *c, const ModDisparityFill *f) { return set_option(c, &EstimatorOptions::disparity_fill, f, check_disparity_fill); }
 int mod_get_disparity_fill(const ModContext *c, ModDisparityFill *f) { return get_option(c, &EstimatorOptions::disparity_fill, f); }
 int mod_set_texture_filter(ModContext *c, const ModTextureFilter *f) { return set_option(c, &EstimatorOptions::texture_filter, f, check_texture_filter); }
@@ -124,6 +148,21 @@ int mod_disparity_speckle_dev(ModContext *c, int32_t frames, float *disparity, i
   if ((rc = ensure_speckle_scratch(c, c->cfg.max_frames))) return rc;
   launch_speckle(c->dc.W, c->dc.H, frames, c->cam.min_disparity, c->cam.min_disparity - 1.0f, speckle_size, speckle_range, disparity,
                  c->b.spk.parent, c->b.spk.size, c->b.dbg, c->stream);
+  HIP_TRY(c, hipGetLastError());
+  return MOD_OK;
+}
+
+int mod_disparity_smooth_dev(ModContext *c, int32_t frames, const float *disparity_in, const ModDisparitySmooth *f, float *disparity_out) {
+  int rc = check_ready(c, frames);
+  if (rc) return rc;
+  if (!disparity_in || !disparity_out) return MOD_SKIP_NO_DISPARITY_NOW;
+  const ModDisparitySmooth m = f ? *f : c->opt.disparity_smooth;
+  if ((rc = check_disparity_smooth(c, m))) return rc;
+  if (m.window == 0) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth window must be 3, 5 or 7 (0: nothing to do)");
+  const uintptr_t a = (uintptr_t)disparity_in, b = (uintptr_t)disparity_out, bytes = (uintptr_t)frames * c->dc.W * c->dc.H * 4;
+  if (a < b + bytes && b < a + bytes) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth planes overlap: the smoother cannot run in place");
+  if ((a | b) & 3) return fail(c, MOD_ERR_INVALID_ARGUMENT, "disparity smooth planes must be 4-byte aligned");
+  launch_disparity_smooth(c->dc.W, c->dc.H, frames, c->cam.min_disparity, m.window, m.tol, m.min_members, disparity_in, disparity_out, c->stream);
   HIP_TRY(c, hipGetLastError());
   return MOD_OK;
 }

@@ -1,6 +1,7 @@
 // host_sgm.hip — the C ABI's on-GPU disparity estimator, host side (no kernel): its parameter check, the scratch of a group of frames,
 // what a set holds (SgmSet) with the two halves of a group (sgm_start, sgm_finish), the entry points around them and the sub-pixel and
-// offset settings.  The kernels live in sgm.hip; the texture and speckle stages and the hole fill of sgm_finish are host_filters.hip's.
+// offset settings.  The kernels live in sgm.hip; the texture and speckle stages, the smoother and the hole fill of sgm_finish are
+// host_filters.hip's.
 #include "host_options.h"
 
 #include <algorithm>
@@ -105,11 +106,14 @@ static int sgm_finish(ModContext *c, const ModSgmParams *p, const EstimatorOptio
   const int W = c->dc.W, H = c->dc.H;
   const ModDisparityFilters &filters = opt.disparity_filters;
   const ModTextureFilter &tex = opt.texture_filter;
+  const ModDisparitySmooth &smooth = opt.disparity_smooth;
   const ModDisparityFill &fill = opt.disparity_fill;
   // with the hole fill on, the stages below work on the group's scratch plane (all of them are on the context's stream, so one plane serves
-  // every group) and the fill, the last stage, writes the caller's
+  // every group) and the fill, the last stage, writes the caller's; with the smoother on they work on its scratch plane and the smoother
+  // writes the fill's, or the caller's where the fill is off: neither stage reads the plane it writes
   float *const filled = disparity + s.f0 * ((size_t)W * H);
-  float *const out = fill.reach ? c->b.sgm.unfilled.get() : filled;
+  float *const smoothed = fill.reach ? c->b.sgm.unfilled.get() : filled;
+  float *const out = smooth.window ? c->b.sgm.unsmoothed.get() : smoothed;
   // a failed wait would let the winner-take-all read volumes the path kernels are still writing: surface it
   for (int i = 0; i < (s.all_in_one ? 1 : p->paths); i++) HIP_TRY(c, hipStreamWaitEvent(c->stream, s.join[i], 0));
   launch_sgm_finish(W, H, s.g, p->disparities, opt.disparity_offset, p->paths, s.path_stride, p->median, p->lr_check, filters.uniqueness_ratio, s.S, maps, out, c->stream);
@@ -120,8 +124,9 @@ static int sgm_finish(ModContext *c, const ModSgmParams *p, const EstimatorOptio
   // invalid pixels are -1 whatever the disparity offset is, so ">= 0 takes part" holds with one
   if (filters.speckle_size > 0)
     launch_speckle(W, H, s.g, 0.0f, -1.0f, filters.speckle_size, filters.speckle_range, out, c->b.spk.parent, c->b.spk.size, c->b.dbg, c->stream);
-  // invalid is "not finite or < 0" here too: the speckle stage's rule, whatever the offset is
-  if (fill.reach) launch_disparity_fill(W, H, s.g, 0.0f, fill.reach, fill.directions, fill.mode, fill.min_found, out, filled, c->stream);
+  // invalid is "not finite or < 0" in both stages below too: the speckle stage's rule, whatever the offset is
+  if (smooth.window) launch_disparity_smooth(W, H, s.g, 0.0f, smooth.window, smooth.tol, smooth.min_members, out, smoothed, c->stream);
+  if (fill.reach) launch_disparity_fill(W, H, s.g, 0.0f, fill.reach, fill.directions, fill.mode, fill.min_found, smoothed, filled, c->stream);
   return MOD_OK;
 }
 
@@ -188,6 +193,7 @@ int mod_sgm_compute_dev(ModContext *c, int32_t frames, const uint8_t *left, cons
   int group = 1;
   if ((rc = ensure_sgm_scratch(c, p->disparities, frames, subpixel, &group))) return rc;
   if (opt.disparity_filters.speckle_size > 0 && (rc = ensure_speckle_scratch(c, group))) return rc;
+  if (opt.disparity_smooth.window && (rc = ensure_disparity_smooth_scratch(c, group))) return rc;
   if (opt.disparity_fill.reach && (rc = ensure_disparity_fill_scratch(c, group))) return rc;
   const size_t N = (size_t)c->dc.W * c->dc.H;
   const Buffers::Sgm &b = c->b.sgm;

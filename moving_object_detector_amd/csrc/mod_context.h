@@ -87,6 +87,7 @@ struct Buffers {
     // context's stream with events), so that the waves of one path fill the SIMD slots another leaves idle
     Stream side[kSgmPaths];
     Event fork[2], join[2][kSgmPaths];      // per set (host_sgm.hip SgmSet)
+    DevPtr<float> unsmoothed; int unsmoothed_frames = 0;   // [group][maxN] a group's disparity in front of the smoother (its output goes to `unfilled` with the hole fill on, else to the caller's plane); allocated at the first call with mod_set_disparity_smooth on, grow-only
     DevPtr<float> unfilled; int unfilled_frames = 0;   // [group][maxN] a group's disparity in front of the hole fill (the caller's plane takes the filled one); allocated at the first call with mod_set_disparity_fill on, grow-only
   } sgm;
   // speckle filter (disparity_filter.hip): union-find parents and region sizes of its own, [frames][maxN] each — a group of the
@@ -112,6 +113,7 @@ struct Buffers {
 // Read when a call or submit enqueues its estimator; every kernel of the call is enqueued from the snapshot.  A zero threshold / window / speckle_size: that stage is off
 struct EstimatorOptions {
   int32_t disparity_subpixel = 0, disparity_offset = 0; ModDisparityFilters disparity_filters{};   // disparity: fraction bits; where the window starts (mod_sgm_path_dev reads it too)
+  ModDisparitySmooth disparity_smooth{};                                                           // window 0: off; sgm_finish's stage behind the speckle stage, in front of the fill
   ModDisparityFill disparity_fill{};                                                               // reach 0: off; the last stage of sgm_finish (host_sgm.hip)
   ModTextureFilter texture_filter{0, 9, 31, MOD_TEXTURE_DISPARITY | MOD_TEXTURE_FLOW};             // both, as `apply` says
   int32_t flow_propagation = 1; ModCornerFilter flow_corner_filter{0, 9, 31, 0}; ModFlowMedian flow_median{}; ModFlowFill flow_fill{};   // flow: seeds of a search (1: the parent's winner alone); the fill runs in the submits only (host_api.hip)
@@ -444,6 +446,7 @@ int check_flow_params(ModContext *c, const ModFlowParams *p, int frames);
 inline bool texture_applies(const ModTextureFilter &f, int to) { return f.threshold > 0 && (f.apply & to) != 0; }   // to: MOD_TEXTURE_DISPARITY / _FLOW
 int ensure_speckle_scratch(ModContext *c, int frames);   // the speckle filter's planes for `frames` frames (grow-only)
 int ensure_disparity_fill_scratch(ModContext *c, int frames);   // the disparity plane in front of the hole fill for `frames` frames (grow-only)
+int ensure_disparity_smooth_scratch(ModContext *c, int frames);   // the disparity plane in front of the smoother for `frames` frames (grow-only)
 // host_ego.hip
 int check_ego_params(ModContext *c, const ModEgoParams *p);
 // the ego-motion estimator over `frames` frames; tf == null: into b.ego.tf, res == null: into b.ego.res; fc != null: also the frames' scene-flow constants (with dt) into fc

@@ -134,6 +134,11 @@ void launch_sgm_finish(int W, int H, int frames, int D, int off, int paths, size
 void launch_speckle(int W, int H, int frames, float lo, float invalid, int speckle_size, int speckle_range, float *disparity,
                     int32_t *parent, int32_t *size, unsigned long long *dbg, hipStream_t s);
 
+// edge-preserving smoother of a finished disparity (disparity_smooth.hip): `in` [frames][H][W] -> `out` of the same size, a different plane
+// (checked by the caller, as window 3 / 5 / 7, a finite tol >= 0 and min_members 1..window^2 are); a word is valid when it is finite and
+// >= lo.  ONE launch; every pixel of `out` is stored, `in` is only read
+void launch_disparity_smooth(int W, int H, int frames, float lo, int window, float tol, int min_members, const float *in, float *out, hipStream_t s);
+
 // occlusion hole fill of a finished disparity (disparity_fill.hip): `in` [frames][H][W] -> `out` of the same size, a different plane
 // (checked by the caller, as reach 1..256, directions 2 / 4 / 8, the mode and min_found 1..directions are); a word is valid when it is
 // finite and >= lo.  ONE launch; every pixel of `out` is stored, `in` is only read

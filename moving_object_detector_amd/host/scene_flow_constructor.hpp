@@ -110,6 +110,15 @@ class SceneFlowConstructor {
     const ModDisparityFilters f{uniqueness_ratio, speckle_size, speckle_range, 0};
     check(mod_set_disparity_filters(ctx_, &f));
   }
+  // edge-preserving smoother of the disparity (mod_set_disparity_smooth): the estimator's stage behind the speckle stage and in front of
+  // the hole fill.  A valid disparity d becomes the mean of the valid disparities of its window x window square (3, 5 or 7) within tol
+  // px of d, where at least min_members (1..window^2) lie there; every other pixel stays.  window 0 = off, the default.  Throws where the
+  // library refuses a value; frames already submitted keep the setting of their submit.  No node parameter sets it.
+  void setDisparitySmooth(int window, float tol, int min_members) {
+    const ModDisparitySmooth f{window, min_members, tol, 0};
+    if (window == 0) check(mod_set_disparity_smooth(ctx_, nullptr));
+    else check(mod_set_disparity_smooth(ctx_, &f));
+  }
   // occlusion hole fill of the disparity (mod_set_disparity_fill): the estimator's last stage, behind the speckle stage.  An invalid
   // disparity walks the first `directions` (2, 4 or 8) path directions for up to `reach` (1..256) steps each to the first valid word and
   // becomes the lowest (MOD_DISPARITY_FILL_MIN), second lowest (_SECOND) or lower median (_MEDIAN) of the found words where at least

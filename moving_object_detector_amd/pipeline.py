@@ -154,6 +154,23 @@ class Context(HostCalls):
         self._check(self.lib.mod_get_disparity_fill(self.h, C.byref(f)))
         return f
 
+    def set_disparity_smooth(self, window=None, tol: float = 1.0, min_members: int = 1) -> None:
+        """Edge-preserving smoother of the on-GPU disparity estimator (mod_set_disparity_smooth), off by default: the estimator's stage
+        behind the speckle stage and in front of the hole fill; a valid disparity d becomes the mean of the valid disparities of its
+        `window` x `window` square (3, 5 or 7) within `tol` px of d, where at least `min_members` lie there; every other pixel stays.
+        No argument or None turns it off; a capi.ModDisparitySmooth is taken as it is.  Read when a call or a submit enqueues its
+        estimator; the ego-motion estimator and the flow fill's gate see the smoothed disparity.  The defaults are not tuned."""
+        if window is None:
+            self._check(self.lib.mod_set_disparity_smooth(self.h, None))
+            return
+        f = window if isinstance(window, capi.ModDisparitySmooth) else capi.disparity_smooth(window, tol, min_members)
+        self._check(self.lib.mod_set_disparity_smooth(self.h, C.byref(f)))
+
+    def get_disparity_smooth(self) -> capi.ModDisparitySmooth:
+        f = capi.ModDisparitySmooth(-1, -1, -1.0, -1)
+        self._check(self.lib.mod_get_disparity_smooth(self.h, C.byref(f)))
+        return f
+
     def set_disparity_offset(self, d0: int = 0) -> None:
         """Minimum disparity of the on-GPU disparity estimator (mod_set_disparity_offset): the search window is [d0, d0 + disparities),
         0 <= d0 <= 128; 0 (the default) = the window starts at 0.  Invalid pixels stay -1.  Read when a call or a submit enqueues its
@@ -651,6 +668,22 @@ class Context(HostCalls):
             raise ValueError("out must be a contiguous float32 tensor of the planes' size on their device")
         self._done(self.lib.mod_disparity_fill_dev(self.h, p.shape[0], p.data_ptr(), C.byref(fill) if fill is not None else None, out.data_ptr()),
                    "mod_disparity_fill_dev")
+        return out.view(p.shape)
+
+    def disparity_smooth(self, planes: torch.Tensor, smooth: Optional[capi.ModDisparitySmooth] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The edge-preserving smoother alone (mod_disparity_smooth_dev) on device float32 planes (F, H, W) or (H, W) of the camera's
+        size, into `out` (another tensor of the planes' size; a new one when None) — returned as (F, H, W).  A word is valid when finite
+        and >= the camera's min_disparity.  smooth None = the context's; with none set the call is refused.  Enqueued on the context's
+        stream."""
+        p = planes[None] if planes.dim() == 2 else planes
+        if p.dtype != torch.float32 or not p.is_contiguous() or p.device.type != "cuda" or p.shape[1:] != (self.height, self.width):
+            raise ValueError("planes must be a contiguous float32 device tensor (F, H, W) at the camera size")
+        if out is None:
+            out = torch.empty_like(p)
+        elif out.numel() != p.numel() or out.shape[-2:] != p.shape[-2:] or out.dtype != torch.float32 or not out.is_contiguous() or out.device != p.device:
+            raise ValueError("out must be a contiguous float32 tensor of the planes' size on their device")
+        self._done(self.lib.mod_disparity_smooth_dev(self.h, p.shape[0], p.data_ptr(), C.byref(smooth) if smooth is not None else None, out.data_ptr()),
+                   "mod_disparity_smooth_dev")
         return out.view(p.shape)
 
     def _grey_planes(self, grey: torch.Tensor) -> torch.Tensor:

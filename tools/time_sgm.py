@@ -1,6 +1,6 @@
 """Time of the on-GPU disparity estimator (mod_sgm_compute_dev) per frame.
 usage (GPU box): python tools/time_sgm.py [W H [D]] [--subpixel] [--uniqueness U] [--speckle SIZE RANGE] [--offset N] [--texture T [--texture-window w]]
-[--reps N] [--fill REACH [--fill-directions N] [--fill-mode M]]
+[--reps N] [--fill REACH [--fill-directions N] [--fill-mode M]] [--smooth W [--smooth-tol T] [--smooth-min-members N]]
 (--subpixel: mod_set_disparity_subpixel(4); --uniqueness / --speckle: mod_set_disparity_filters, off unless given; --offset:
 mod_set_disparity_offset, the images' disparities then start at N; --texture: mod_set_texture_filter(T, w, 31, MOD_TEXTURE_DISPARITY),
 off unless given; --fill REACH: mod_set_disparity_fill(REACH, N, M, 1), off unless given.  With --fill the tool also prints JSON lines:
@@ -8,7 +8,12 @@ the fill's kernel alone (mod_disparity_fill_dev: k_disparity_fill) between HIP e
 share of holes and of filled pixels and the bytes per second of the 8 bytes per pixel it must move, beside the speckle stage alone
 (mod_disparity_speckle_dev, size 100, range 1, on a copy restored before every call outside the timed span) and a plain copy of the same
 planes in the same process; the kernel again on that output with every other pixel made a hole; and, per foreground box of the synthetic
-scenes and for the background, the share of its true pixels that carry a disparity with the fill off and on)"""
+scenes and for the background, the share of its true pixels that carry a disparity with the fill off and on.  --smooth W:
+mod_set_disparity_smooth(W, T, N), off unless given.  With --smooth the tool also prints JSON lines: the smoother's kernel alone
+(mod_disparity_smooth_dev: k_disparity_smooth) at windows 3, 5 and 7 with T and N between HIP events on the estimator's own output of the
+8-path run with the smoother off, with the share of valid words and of words it changes and the bytes per second of the 8 bytes per pixel
+it must move, beside k_disparity_fill (reach 64, 8 directions) on the same planes with their holes closed, the speckle stage alone and a
+plain copy of the same planes in the same process)"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -29,6 +34,9 @@ ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--fill", type=int, default=0, metavar="REACH", help="mod_set_disparity_fill: the reach, 1..256 (0 = off)")
 ap.add_argument("--fill-directions", type=int, default=8, choices=(2, 4, 8), metavar="N", help="directions of --fill")
 ap.add_argument("--fill-mode", default="min", choices=("min", "second", "median"), metavar="M", help="mode of --fill")
+ap.add_argument("--smooth", type=int, default=0, choices=(0, 3, 5, 7), metavar="W", help="mod_set_disparity_smooth: the window (0 = off)")
+ap.add_argument("--smooth-tol", type=float, default=1.0, metavar="T", help="gate of --smooth in px of disparity")
+ap.add_argument("--smooth-min-members", type=int, default=1, metavar="N", help="min_members of --smooth")
 a = ap.parse_args()
 W, H, D = a.W, a.H, a.D
 F = int(os.environ.get("SGM_F", "16"))
@@ -51,7 +59,24 @@ if a.texture:
 if a.fill:
     ctx.set_disparity_fill(a.fill, a.fill_directions, a.fill_mode, 1)
     filters += f" fill={a.fill}/{a.fill_directions}/{a.fill_mode}"
+if a.smooth:
+    ctx.set_disparity_smooth(a.smooth, a.smooth_tol, a.smooth_min_members)
+    filters += f" smooth={a.smooth}/{a.smooth_tol:g}/{a.smooth_min_members}"
 dev = ctx.device
+
+
+def timed(call, before=None, reps=20):
+    """ms per call between two HIP events, one pair per call (so that `before` stays outside), after three warm-up calls"""
+    total = 0.0
+    for i in range(3 + reps):
+        if before:
+            before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); call(); e1.record(); e1.synchronize()
+        total += e0.elapsed_time(e1) if i >= 3 else 0.0
+    return total / reps
+
+
 tl = torch.from_numpy(np.stack([p[0] for p in pairs])).to(dev); tr = torch.from_numpy(np.stack([p[1] for p in pairs])).to(dev)
 out = torch.empty((F, H, W), dtype=torch.float32, device=dev)
 for paths in (8, 4):
@@ -67,17 +92,6 @@ for paths in (8, 4):
     print(f"{W}x{H} D={D} paths={paths} frames={F} subpixel={'on' if a.subpixel else 'off'}{filters}: {ms:.3f} ms per frame ({1e3 / ms:.0f} frames/s); "
           f"valid {float((out >= 0).float().mean()):.2f}")
     if a.fill and paths == 8:
-        def timed(call, before=None, reps=20):
-            """ms per call between two HIP events, one pair per call (so that `before` stays outside), after three warm-up calls"""
-            total = 0.0
-            for i in range(3 + reps):
-                if before:
-                    before()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(); call(); e1.record(); e1.synchronize()
-                total += e0.elapsed_time(e1) if i >= 3 else 0.0
-            return total / reps
-
         ff = ctx.get_disparity_fill()
         ctx.set_disparity_fill()
         plain = ctx.estimate_disparity(tl, tr, prm).clone()          # the estimator's output in front of the fill
@@ -105,3 +119,27 @@ for paths in (8, 4):
         for name, m in surfaces.items():
             print(json.dumps({"what": "valid share", **base, "surface": name, "pixels": int(m.sum()), "off": round(float(off[m].mean()), 4),
                               "on": round(float(on[m].mean()), 4)}), flush=True)
+    if a.smooth and paths == 8:
+        ss, ff = ctx.get_disparity_smooth(), ctx.get_disparity_fill()
+        ctx.set_disparity_smooth(); ctx.set_disparity_fill()
+        plain = ctx.estimate_disparity(tl, tr, prm).clone()          # the estimator's output in front of the smoother
+        ctx.set_disparity_smooth(ss); ctx.set_disparity_fill(ff)
+        whole = torch.where(plain >= 0, plain, torch.full_like(plain, float(D // 2)))      # no hole: what the fill only copies
+        done, work = torch.empty_like(plain), torch.empty_like(plain)
+        base = {"W": W, "H": H, "D": D, "frames": F, "subpixel": bool(a.subpixel), "tol": a.smooth_tol, "min_members": a.smooth_min_members}
+        for w in (3, 5, 7):
+            sp = capi.disparity_smooth(w, a.smooth_tol, min(a.smooth_min_members, w * w))
+            for what, src in ((f"k_disparity_smooth<{w}>", plain), (f"k_disparity_smooth<{w}> no holes", whole)):
+                ms = timed(lambda: ctx.disparity_smooth(src, sp, done))
+                print(json.dumps({"what": what, **base, "window": w, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4),
+                                  "gbytes_per_s": round(8 * F * H * W / ms / 1e6, 1), "valid": round(float((src >= 0).float().mean()), 4),
+                                  "changed": round(float((done.view(torch.int32) != src.view(torch.int32)).float().mean()), 4)}), flush=True)
+        f64 = capi.disparity_fill(64, 8, "min", 1)
+        ms = timed(lambda: ctx.disparity_fill(whole, f64, done))
+        print(json.dumps({"what": "k_disparity_fill no holes", **base, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4),
+                          "gbytes_per_s": round(8 * F * H * W / ms / 1e6, 1)}), flush=True)
+        ms = timed(lambda: ctx.speckle_filter(work, 100, 1), before=lambda: work.copy_(plain))
+        print(json.dumps({"what": "k_speckle", **base, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4)}), flush=True)
+        ms = timed(lambda: work.copy_(plain))
+        print(json.dumps({"what": "copy", **base, "ms_per_call": round(ms, 4), "ms_per_frame": round(ms / F, 4),
+                          "gbytes_per_s": round(8 * F * H * W / ms / 1e6, 1)}), flush=True)
